@@ -115,6 +115,8 @@ def parse_args(argv=None):
                     help="the N ranks of --gpus N are THREADS of this one process, each with its own handle (SURVEY 8e's \"one process with 8 "
                          "handles\"): rank r drives device r, or every rank the device F110_BENCH_DEVICE names.  The same legs, control plane, "
                          "digests and records as one process per GPU (the contract's launch form, and the default); no NUMA pinning per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed in their last step (rank 0's observation) to DIR/<name>.npy")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # tests: no GPU, a sleep stands in for the step
     return ap.parse_args(argv)
 
@@ -235,15 +237,24 @@ class Rendezvous(object):
             self.sock.close()
 
 
+def build_and_count_devices():
+    """build() and the number of visible HIP devices, in a child process that exits before any rank starts: the launcher
+    itself never opens the GPU, so a job of N ranks holds it in N processes"""
+    code = "import sys; sys.path.insert(0, %r); import __graft_entry__; __graft_entry__.build(); from f1tenth_gym_amd import _ffi; " \
+           "print('devices', _ffi.device_count())" % ROOT
+    out = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, text=True, timeout=1800)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("devices ")]
+    if out.returncode != 0 or not lines:
+        raise SystemExit("bench.py: build / device count failed (exit %d)" % out.returncode)
+    return int(lines[-1].split()[1])
+
+
 def spawn_ranks(args, argv):
     """`python bench.py --gpus N` outside any launcher: start the N ranks (one process per GPU of this
     node), stream rank 0's stdout through, fail if any rank fails.  Returns the exit code."""
     n = args.gpus
     if not args.stub:
-        from f1tenth_gym_amd import _ffi
-        import __graft_entry__
-        __graft_entry__.build()
-        have = _ffi.device_count()
+        have = build_and_count_devices()
         if have < n and "F110_BENCH_DEVICE" not in os.environ:   # (the testing aid puts every rank on one named device)
             print("bench.py: --gpus %d but only %d HIP device(s) visible — refusing to run a smaller job under that label" % (n, have),
                   file=sys.stderr)
@@ -878,6 +889,32 @@ def leg_record(rdv, total_agents, t):
             "gather_ok": None if all(o < 0 for o in oks) else bool(all(o != 0.0 for o in oks))}
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much
+DUMP_SCAN_AGENTS = 4096         # scans of a fixed, seeded sample of agents (all 65536 of them would be 566 MB)
+DUMP_FIELDS = ("state", "poses_x", "poses_y", "poses_theta", "linear_vels_x", "ang_vels_z", "collisions", "collision_idx", "in_collision")
+
+
+def dump_outputs(sim, out_dir):
+    """--dump-outputs: the observation the timed steps left on the device after the last of them, as a caller of the step
+    reads it back (BatchSim.get): every agent's state and scalar fields, and the scans of DUMP_SCAN_AGENTS agents drawn with
+    a fixed seed (their indices in scans_agents.npy).  float64 throughout (integer fields converted).  With the same
+    arguments the inputs are the same from run to run, so two builds can be compared file for file."""
+    import numpy as np
+    o = sim.get("scans", *DUMP_FIELDS)
+    n, beams = o["scans"].shape
+    out = {f: np.asarray(o[f], dtype=np.float64) for f in DUMP_FIELDS}
+    room = (DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values())) // (8 * (beams + 1))
+    k = int(min(n, DUMP_SCAN_AGENTS, room))
+    agents = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    out["scans"] = np.ascontiguousarray(o["scans"][agents])
+    out["scans_agents"] = agents.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def main(argv=None, ident=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -887,6 +924,8 @@ def main(argv=None, ident=None):
         return thread_ranks(args, argv)
     if ident is None and args.gpus > 1 and "RANK" not in os.environ:
         return spawn_ranks(args, argv)
+    if args.dump_outputs and args.stub:
+        raise SystemExit("bench.py: --dump-outputs needs the real step (not --stub)")
     rdv = Rendezvous(ident)
     if rdv.world != args.gpus:
         if rdv.rank == 0:
@@ -925,6 +964,8 @@ def main(argv=None, ident=None):
     else:
         wl = Workload(args, rdv, args.agents, total_needed)
         timed = wl.run(args.steps, args.warmup, "timed")
+        if args.dump_outputs and rdv.rank == 0:     # before anything else steps the handle again
+            dump_outputs(wl.sim, args.dump_outputs)
         head = leg_record(rdv, total_agents, timed)
         if args.gather:
             rccl_ranks = wl.sim.comm_info()[0]

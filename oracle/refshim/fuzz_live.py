@@ -2,8 +2,8 @@
 
 tests/test_reference_fuzz.py walks 25 hand-written configurations.  This script draws configurations at random — track,
 resolution / origin / yaw overrides, beams, fov, eps, theta_dis, max_range for `ScanSimulator2D`; cars, integrator, time step,
-lidar offset, steps for `Simulator`; the same plus ego index for `F110Env` — adds them to that module's case tables and
-runs its three checks on each (the reference imported from /root/reference through ref_loader, the oracle beside it).
+lidar offset, steps for `Simulator`; the same plus ego index for `F110Env` — records the reference on each (gen_fuzz_golden.py) and
+runs that module's three checks on the records (the reference imported from /root/reference through ref_loader, the oracle beside it).
     python oracle/refshim/fuzz_live.py 0 100        # seeds 0..99: one scan, one simulator and (every third seed) one env case each
 """
 import os
@@ -12,7 +12,7 @@ import tempfile
 import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 
 TRACKS = ["example_map", "berlin", "skirk", "vegas", "stata_basement"]
@@ -28,12 +28,11 @@ def draw_map(rng):
 
 
 def main(first, last):
-    import test_reference_fuzz as T
-    if not T.ref_loader.reference_available():
+    import gen_fuzz_golden as G     # the reference's side of each check; test_reference_fuzz holds the oracle against it
+    T = G.T
+    if not G.ref_loader.reference_available():
         print("the reference tree is not here: nothing to do"); return 1
     bad = []
-    for tab in ("SCAN_CASES", "SIM_CASES", "ENV_CASES"):      # index -> case, so that a seed's case keeps its index whatever ran before it
-        setattr(T, tab, dict(enumerate(getattr(T, tab))))
     for seed in range(first, last):
         rng = np.random.default_rng(300000 + seed)
         name, res, org = draw_map(rng)
@@ -47,15 +46,15 @@ def main(first, last):
         env = env[:2] + (int(rng.integers(0, env[1])),) + env[3:]
         if rng.random() < 0.5:      # laps by circling forwards at full lock instead of back and forth through the start zone
             env = env[:6] + (int(rng.integers(150, 330)), "circle")
-        jobs = [("scan", T.SCAN_CASES, scan, T.test_scan_simulator_ctor_and_map_sweep, True),
-                ("sim", T.SIM_CASES, sim, T.test_simulator_sweep, True)]
+        jobs = [("scan", scan, lambda c, i, tmp: T.check_scan_case(c, i, G.record_scan(c, i, tmp))),
+                ("sim", sim, lambda c, i, tmp: T.check_sim_case(c, i, G.record_sim(c, i, tmp)))]
         if seed % 3 == 0:
-            jobs.append(("env", T.ENV_CASES, env, T.test_f110env_sweep, False))
-        for kind, table, case, fn, wants_tmp in jobs:
-            idx = 1000 + seed; table[idx] = case      # (the checks seed their own generators with the case index)
+            jobs.append(("env", env, lambda c, i, tmp: T.check_env_case(c, i, G.record_env(c, i))))
+        for kind, case, fn in jobs:
+            idx = 1000 + seed       # (the checks seed their own generators with the case index)
             try:
                 with tempfile.TemporaryDirectory() as tmp:
-                    fn(idx, tmp) if wants_tmp else fn(idx)
+                    fn(case, idx, tmp)
                 print("ok seed %d %s %s" % (seed, kind, case), flush=True)
             except Exception as ex:     # noqa: BLE001 — report and go on
                 bad.append((seed, kind))

@@ -1222,9 +1222,27 @@ def gen_star_exports(ns):
     save("star_exports", **out)
 
 
+def gen_public_names(ns):
+    """the public names `from f110_gym.envs import *` brings in (envs/__init__.py:1-5 star-imports dynamic_models, laser_models,
+    base_classes and collision_models): every public function / class those modules define, their unittest classes and script
+    mains aside, plus F110Env — read off the modules' sources (their names only)"""
+    import ast
+    want = {"F110Env"}
+    for mod in ("dynamic_models", "laser_models", "collision_models", "base_classes"):
+        with open(os.path.join(ref_loader._ENV_DIR, mod + ".py")) as f:
+            tree = ast.parse(f.read())
+        for node in tree.body:
+            if isinstance(node, ast.FunctionDef) and not node.name.startswith("_") and node.name != "main":
+                want.add(node.name)
+            elif isinstance(node, ast.ClassDef) and not any(getattr(b, "attr", getattr(b, "id", "")) == "TestCase" for b in node.bases):
+                want.add(node.name)
+    save("reference_public_names", names=np.array(sorted(want)))
+
+
 GROUPS = {"star_exports": gen_star_exports, "scan_ctor": gen_scan_ctor, "scan_rotated": gen_scan_rotated, "env_defaults": gen_env_defaults, "sim_variants": gen_sim_variants, "sim_many": gen_sim_many, "planner": gen_planner, "data": lambda ns: copy_data(), "dynamics": gen_dynamics, "update_pose": gen_update_pose,
           "scan": gen_scan, "ttc": gen_ttc, "collision": gen_collision, "raycast": gen_raycast,
-          "sim": gen_sim, "sim_multi": gen_sim_multi, "env": gen_env, "env2": gen_env2, "env3": gen_env3, "env_kwargs": gen_env_kwargs, "env_updates": gen_env_updates, "waypoint_follow": gen_waypoint_follow}
+          "sim": gen_sim, "sim_multi": gen_sim_multi, "env": gen_env, "env2": gen_env2, "env3": gen_env3, "env_kwargs": gen_env_kwargs, "env_updates": gen_env_updates, "waypoint_follow": gen_waypoint_follow,
+          "public_names": gen_public_names}
 
 
 def main(argv):

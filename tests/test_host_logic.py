@@ -330,20 +330,9 @@ def test_every_script_of_the_repo_compiles():
 def test_alias_package_exports_every_public_name_of_the_reference():
     """`from f110_gym.envs import *` in the reference (envs/__init__.py:1-5) star-imports dynamic_models, laser_models, base_classes and
     collision_models: every public function / class those modules define (their unittest classes and script mains aside) must come out of
-    the alias package too.  Build container only (reads the reference's module sources for their NAMES)."""
-    import ast
-    ref = "/root/reference/gym/f110_gym/envs"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference tree is not here")
-    want = {"F110Env"}
-    for mod in ("dynamic_models", "laser_models", "collision_models", "base_classes"):
-        with open(os.path.join(ref, mod + ".py")) as f:
-            tree = ast.parse(f.read())
-        for node in tree.body:
-            if isinstance(node, ast.FunctionDef) and not node.name.startswith("_") and node.name != "main":
-                want.add(node.name)
-            elif isinstance(node, ast.ClassDef) and not any(getattr(b, "attr", getattr(b, "id", "")) == "TestCase" for b in node.bases):
-                want.add(node.name)
+    the alias package too.  The names were read off the reference's module sources (oracle/refshim/gen_golden.py public_names)."""
+    from _util import gold
+    want = set(str(n) for n in gold("reference_public_names")["names"])
     ns = {}
     exec("from f110_gym.envs import *", ns)
     assert not (want - set(ns)), sorted(want - set(ns))
