@@ -4,7 +4,7 @@ Python host + ctypes over a C ABI (include/f110.h) + hand-written HIP kernels fo
 The names mirror the reference package f110_gym.envs so existing code ports by changing the
 import:  F110Env, Simulator, Integrator, ScanSimulator2D and the free kernel functions.
 """
-from .core import BatchSim, DeviceArray, DEFAULT_PARAMS  # noqa: F401
+from .core import BatchSim, DeviceArray, StateBlob, DEFAULT_PARAMS  # noqa: F401
 from .sim import Integrator, Simulator  # noqa: F401
 from .laser import ScanSimulator2D  # noqa: F401
 from .racecar import RaceCar  # noqa: F401

@@ -67,6 +67,8 @@ class HostBlock(C.Structure):
 
 
 GATHER_F64, GATHER_F32 = 0, 1
+STATE_SCANS = 1          # f110_state_* flags: the blob also holds the last scans
+STATE_HEADER_BYTES, STATE_VERSION = 256, 1
 STEP_AUTO_RESET, STEP_NO_SYNC, STEP_ACTIONS_MAPPED, STEP_SPIN_WAIT, STEP_NO_FUSE, STEP_POLL = 1, 2, 4, 8, 16, 32
 
 
@@ -125,6 +127,12 @@ PROTOTYPES = {
     "f110_step_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f110_get_obs": (C.c_int, [C.c_void_p, C.POINTER(ObsHost)]),
     "f110_set_state": (C.c_int, [C.c_void_p, _dp, _dp, _i32p]),
+    "f110_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+    "f110_state_save_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "f110_state_load_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "f110_clone_envs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "f110_state_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "f110_state_load": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f110_get_device_views": (C.c_int, [C.c_void_p, C.POINTER(DeviceViews)]),
     "f110_stream_fence": (C.c_int, [C.c_void_p]),
     "f110_device_mem_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

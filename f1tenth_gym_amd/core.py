@@ -201,6 +201,65 @@ class DeviceArray(object):
         self.ptr = None
 
 
+# the 256-byte header of a state blob (include/f110.h, f110_state_*)
+STATE_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("k", "<i4"), ("A", "<i4"), ("B", "<i4"), ("flags", "<i4"),
+                         ("cols", "<u4"), ("noise_mode", "<i4"), ("noise_rows", "<i4"), ("n_maps", "<i4"), ("ego_idx", "<i4"),
+                         ("max_step", "<i8"), ("noise_id", "<u8", (4,)), ("std_dev", "<f8"), ("total_bytes", "<u8"),
+                         ("reserved", "<u8", (19,))])
+assert STATE_HEADER.itemsize == _ffi.STATE_HEADER_BYTES
+STATE_MAGIC = b"F110SNAP"
+STATE_COLUMNS = {"agent": 1, "scans": 2, "rng": 4, "rng_seed": 8, "episode": 16, "params": 32, "env_map": 64}
+NOISE_MODES = ("off", "table", "shared_rng", "per_agent_rng")
+
+
+class StateBlob(object):
+    """An exact snapshot of simulator state (BatchSim.save_state / save_envs): `data` is the blob as a NumPy uint8 buffer,
+    `header` its parsed header (a dict).  It holds state, not configuration: the maps, tables, per-slot params and noise
+    source must already be set on the handle it is loaded into (the load refuses a blob that does not fit)."""
+
+    def __init__(self, data):
+        data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data)
+        if data.dtype != np.uint8 or data.ndim != 1:
+            raise ValueError("a state blob is a 1-D uint8 buffer")
+        if data.nbytes < STATE_HEADER.itemsize:
+            raise ValueError("a state blob is at least %d bytes (got %d)" % (STATE_HEADER.itemsize, data.nbytes))
+        h = data[:STATE_HEADER.itemsize].view(STATE_HEADER)[0]
+        if bytes(h["magic"]) != STATE_MAGIC:
+            raise ValueError("not a simulator state blob (bad magic %r)" % bytes(h["magic"]))
+        if int(h["version"]) != _ffi.STATE_VERSION:
+            raise ValueError("state blob format version %d, this package reads version %d" % (int(h["version"]), _ffi.STATE_VERSION))
+        if int(h["total_bytes"]) != data.nbytes:
+            raise ValueError("state blob of %d bytes, its header says %d" % (data.nbytes, int(h["total_bytes"])))
+        cols = int(h["cols"])
+        self.data = data
+        self.header = {
+            "version": int(h["version"]), "num_envs": int(h["k"]), "num_agents": int(h["A"]), "num_beams": int(h["B"]),
+            "scans": bool(int(h["flags"]) & _ffi.STATE_SCANS), "columns": tuple(n for n, b in STATE_COLUMNS.items() if cols & b),
+            "noise_mode": NOISE_MODES[int(h["noise_mode"])] if 0 <= int(h["noise_mode"]) < len(NOISE_MODES) else int(h["noise_mode"]),
+            "noise_rows": int(h["noise_rows"]), "noise_id": tuple(int(v) for v in h["noise_id"]), "std_dev": float(h["std_dev"]),
+            "n_maps": int(h["n_maps"]), "ego_idx": int(h["ego_idx"]), "max_step": int(h["max_step"]), "total_bytes": int(h["total_bytes"])}
+
+    @property
+    def num_envs(self):
+        return self.header["num_envs"]
+
+    @property
+    def nbytes(self):
+        return self.data.nbytes
+
+    def to_bytes(self):
+        return self.data.tobytes()
+
+    @classmethod
+    def from_bytes(cls, raw):
+        return cls(np.frombuffer(bytes(raw), dtype=np.uint8).copy())
+
+    def __repr__(self):
+        h = self.header
+        return "StateBlob(%d envs x %d agents, %d beams, columns=%s, %d bytes)" % (
+            h["num_envs"], h["num_agents"], h["num_beams"], ",".join(h["columns"]), h["total_bytes"])
+
+
 class BatchSim(object):
     def __init__(self, params=None, num_envs=1, num_agents=2, num_beams=1080, fov=4.7, eps=0.0001,
                  theta_dis=2000, max_range=30.0, time_step=0.01, integrator=_ffi.INTEGRATOR_RK4,
@@ -749,11 +808,120 @@ class BatchSim(object):
         return out
 
     def set_state(self, state, steer_buf=None, buf_count=None):
+        """A PARTIAL setter (f110_set_state): RaceCar.state, the steering FIFO and its count only.  step_count, the collision
+        flags, agent_poses, noise-stream positions and the episode arrays stay as they are, so a batch "restored" this way
+        diverges at its first noisy scan — save_state / load_state restore all of it."""
         state = as_f64(state, (self.N, 7))
         sb = None if steer_buf is None else as_f64(steer_buf, (self.N, 2))
         bc = None if buf_count is None else np.ascontiguousarray(buf_count, dtype=np.int32)
         check(_ffi.lib().f110_set_state(self._h, dptr(state), None if sb is None else dptr(sb),
                                         None if bc is None else i32ptr(bc)), self._h)
+
+    # ------------------------------------------------------------------ exact snapshot / restore / clone (f110_state_*)
+    def _state_call(self, rc):
+        if rc == _ffi.ERR_STATE:   # a blob that does not fit this handle
+            raise ValueError(_ffi.last_error(self._h))
+        check(rc, self._h)
+
+    def state_bytes(self, n_envs=None, scans=False):
+        """bytes of a blob of n_envs envs (all by default) with this handle's current columns"""
+        return int(_ffi.lib().f110_state_bytes(self._h, self.E if n_envs is None else int(n_envs), _ffi.STATE_SCANS if scans else 0))
+
+    def save_state(self, scans=True, out=None):
+        """every env's state (and the last scans) -> StateBlob.  out: a uint8 buffer of state_bytes() bytes to fill (pinned_empty
+        memory copies at full rate)"""
+        flags = _ffi.STATE_SCANS if scans else 0
+        n = self.state_bytes(None, scans)
+        buf = np.empty(n, dtype=np.uint8) if out is None else out
+        if buf.dtype != np.uint8 or buf.ndim != 1 or buf.nbytes != n or not buf.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint8 buffer of %d bytes" % n)
+        self._state_call(_ffi.lib().f110_state_save(self._h, buf.ctypes.data, flags))
+        return StateBlob(buf)
+
+    def load_state(self, blob):
+        """restore every env from a save_state blob of a handle of the same shape (agents, beams, envs) and configuration"""
+        blob = blob if isinstance(blob, StateBlob) else StateBlob(blob)
+        self._state_call(_ffi.lib().f110_state_load(self._h, blob.data.ctypes.data))
+
+    def _indices(self, idx, what, limit):
+        """(pointer, count, keep-alive) of an index list: a DeviceArray of int32 as it is, host indices checked and uploaded"""
+        if isinstance(idx, DeviceArray):
+            if idx.dtype != np.int32 or len(idx.shape) != 1:
+                raise ValueError("%s: a device index list is a 1-D int32 DeviceArray" % what)
+            return idx.ptr, idx.shape[0], idx, None
+        a = np.atleast_1d(np.asarray(idx))
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("%s must be a 1-D list of integer indices" % what)
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= limit):
+            raise ValueError("%s: indices must lie in [0, %d), got %s" % (what, limit, a[(a < 0) | (a >= limit)][:8].tolist()))
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        if a.size == 0:
+            return None, 0, None, a
+        d = self.device_array((a.size,), np.int32)
+        d.upload(a)
+        return d.ptr, a.size, d, a
+
+    @staticmethod
+    def _status_ptr(d_status):
+        return None if d_status is None else (d_status.ptr if isinstance(d_status, DeviceArray) else int(d_status))
+
+    def save_envs(self, env_idx, scans=False, device=False):
+        """the state of envs env_idx (host indices or an int32 DeviceArray) -> a StateBlob whose entry j is env env_idx[j], or
+        (device=True) a DeviceArray holding the blob, which load_envs takes without a host round trip"""
+        ptr, k, keep, _ = self._indices(env_idx, "env_idx", self.E)
+        if k == 0:
+            raise ValueError("env_idx is empty")
+        flags = _ffi.STATE_SCANS if scans else 0
+        d_blob = self.device_array((self.state_bytes(k, scans),), np.uint8)
+        self._state_call(_ffi.lib().f110_state_save_device(self._h, ptr, k, d_blob.ptr, flags))
+        del keep
+        if device:
+            return d_blob
+        blob = StateBlob(d_blob.download())
+        d_blob.free()
+        return blob
+
+    def load_envs(self, blob, src, dst, d_status=None):
+        """blob entry src[j] -> env dst[j] (several dst may share a src).  Host index lists are checked (range, no dst twice:
+        ValueError); device lists (int32 DeviceArrays) are not — their out-of-range entries are skipped and counted into the
+        device int32 d_status, and a dst named twice is undefined."""
+        d_blob, tmp = blob, None
+        if not isinstance(blob, DeviceArray):
+            blob = blob if isinstance(blob, StateBlob) else StateBlob(blob)
+            tmp = d_blob = self.device_array((blob.nbytes,), np.uint8)
+            d_blob.upload(blob.data)
+            k_blob = blob.num_envs
+        else:
+            k_blob = None
+        sp, ks, skeep, _ = self._indices(src, "src", k_blob if k_blob is not None else 1 << 30)
+        dp, kd, dkeep, dh = self._indices(dst, "dst", self.E)
+        if ks != kd:
+            raise ValueError("src and dst must have the same length (%d != %d)" % (ks, kd))
+        if dh is not None and np.unique(dh).size != dh.size:
+            raise ValueError("dst names an env more than once")
+        if kd:
+            self._state_call(_ffi.lib().f110_state_load_device(self._h, d_blob.ptr, sp, dp, kd, self._status_ptr(d_status)))
+        del skeep, dkeep
+        if tmp is not None:
+            tmp.free()
+
+    def clone_envs(self, src, dst, d_status=None):
+        """env src[j] -> env dst[j] on the device, one launch (the branching primitive: MCTS, forked rollouts).  Host index
+        lists are checked: in range, src and dst disjoint, no dst twice (ValueError); device lists are not (out-of-range entries
+        are skipped and counted into d_status)."""
+        sp, ks, skeep, sh = self._indices(src, "src", self.E)
+        dp, kd, dkeep, dh = self._indices(dst, "dst", self.E)
+        if ks != kd:
+            raise ValueError("src and dst must have the same length (%d != %d)" % (ks, kd))
+        if dh is not None:
+            if np.unique(dh).size != dh.size:
+                raise ValueError("dst names an env more than once")
+            if sh is not None and np.intersect1d(sh, dh).size:
+                raise ValueError("src and dst overlap (envs %s): a clone reads and writes disjoint envs" % np.intersect1d(sh, dh)[:8].tolist())
+        if kd:
+            self._state_call(_ffi.lib().f110_clone_envs_device(self._h, sp, dp, kd, self._status_ptr(d_status)))
+        del skeep, dkeep
 
     # ------------------------------------------------------------------ timing (bench.py)
     def timer_begin(self):

@@ -123,6 +123,12 @@ struct f110_sim {
     double *noise_ahead_block = nullptr;
     std::vector<double *> noise_retired;   // earlier, smaller blocks of the cache (steps in flight may read them): freed with the cache
     long long noise_ub = 0;          // upper bound of any agent's step_count (steps since the last full reset)
+    // identity of the noise source, for the state blobs (0 off, 1 table, 2 shared stream, 3 a stream per agent): the table's
+    // FNV-1a hash / rows / beams, or the shared stream's PCG64 words
+    int noise_src = 0;
+    uint64_t noise_src_id[4] = {0, 0, 0, 0};
+    void *d_state_blob = nullptr;    // f110_state_save / _load: the device side of the whole-handle blob (grows on demand)
+    size_t state_blob_bytes = 0;
     unsigned long long *d_lookups = nullptr;  // f110_scan_lookup_count
     bool lookups_on = false;
     // the single-block step captured as a HIP graph (f110_config.step_graph): one submission per step
@@ -811,6 +817,7 @@ void f110_destroy(f110_sim *h)
     if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
     (void)f110_comm_destroy(h);
     h->comm_inflight = false;
+    if (h->d_state_blob) (void)hipFree(h->d_state_blob);
     if (h->comm_stream) { (void)hipStreamSynchronize(h->comm_stream); (void)hipStreamDestroy(h->comm_stream); h->comm_stream = nullptr; }
     for (hipEvent_t e : {h->ev_step_done, h->ev_gather_done[0], h->ev_gather_done[1]})
         if (e) (void)hipEventDestroy(e);
@@ -1255,6 +1262,8 @@ static void noise_release(f110_sim *h)
     h->dev.rng_rowstate = nullptr;
     h->noise_rows_ready = 0;
     h->noise_rows_alloc = 0;
+    h->noise_src = 0;
+    for (uint64_t &w : h->noise_src_id) w = 0;
 }
 
 int f110_set_noise_table(f110_sim *h, const double *noise, int32_t rows, int32_t B)
@@ -1270,6 +1279,13 @@ int f110_set_noise_table(f110_sim *h, const double *noise, int32_t rows, int32_t
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->dev.noise = h->d_noise;
     h->dev.noise_rows = rows;
+    uint64_t fnv = 0xcbf29ce484222325ull;   // FNV-1a 64 of the table's bytes
+    const unsigned char *bytes = reinterpret_cast<const unsigned char *>(noise);
+    for (size_t i = 0, n = sizeof(double) * (size_t)rows * B; i < n; ++i) fnv = (fnv ^ bytes[i]) * 0x100000001b3ull;
+    h->noise_src = 1;
+    h->noise_src_id[0] = fnv;
+    h->noise_src_id[1] = (uint64_t)rows;
+    h->noise_src_id[2] = (uint64_t)B;
     return F110_OK;
 }
 
@@ -1300,6 +1316,7 @@ int f110_set_noise_rng(f110_sim *h, const uint64_t *state_inc, int32_t per_agent
         HIPCHK(h, hipMemcpy(h->d_rng_seed, state_inc, sizeof(U128) * 2 * N, hipMemcpyHostToDevice));
         h->dev.rng_seed = h->d_rng_seed;
         h->dev.noise_rng = 2;
+        h->noise_src = 3;
         return F110_OK;
     }
     // capacity: 164 s of simulated time by default.  Rows are generated on demand, and the memory behind
@@ -1318,6 +1335,8 @@ int f110_set_noise_rng(f110_sim *h, const uint64_t *state_inc, int32_t per_agent
     h->dev.noise_rows = rows;
     h->dev.noise_rng = 1;
     h->noise_rows_ready = 0;
+    h->noise_src = 2;
+    for (int w = 0; w < 4; ++w) h->noise_src_id[w] = state_inc[w];
     return noise_cache_extend(h, std::min(rows, 256));
 }
 
@@ -2764,6 +2783,293 @@ int f110_set_state(f110_sim *h, const double *state7, const double *steer_buf, c
     }
     if (buf_count) HIPCHK(h, hipMemcpyAsync(h->dev.buf_cnt, buf_count, N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- exact snapshot / restore / clone (include/f110.h f110_state_*) ------------------------------------------------------
+// The columns a blob carries are the ones active on the handle: the per-agent core always, device-noise positions / seeds,
+// the episode arrays, per-agent params and the env-map slot while those exist.  Everything else a step reads (scan_pose,
+// dir_start, ray_hdr, opp_window, opp_verts, the tiny step's shadow columns, the iTTC flags) is rewritten by every step form
+// before it is read, so it is not state.
+static uint32_t state_col_set(const f110_sim *h)
+{
+    uint32_t c = F110_STATE_COL_AGENT;
+    if (h->dev.noise_rng) c |= F110_STATE_COL_RNG;
+    if (h->dev.noise_rng == 2) c |= F110_STATE_COL_RNG_SEED;
+    if (h->has_episode) c |= F110_STATE_COL_EPISODE;
+    if (h->dev.params_per_agent) c |= F110_STATE_COL_PARAMS;
+    if (h->multi_map) c |= F110_STATE_COL_ENV_MAP;
+    return c;
+}
+
+// the column table of a blob of k envs with column set `cols` (fixed order: the layout depends on cols, k, A and B only);
+// returns the blob's total bytes
+static size_t state_columns(const f110_sim *h, uint32_t cols, int k, StateCols *out)
+{
+    StateCols t{};
+    const size_t N = (size_t)h->N;
+    const uint32_t A = (uint32_t)h->cfg.num_agents, B = (uint32_t)h->cfg.num_beams;
+    size_t off = F110_STATE_HEADER_BYTES;
+    auto add = [&](void *live, uint32_t bytes, uint32_t per_env, uint32_t kind = 0) {
+        StateCol &c = t.c[t.n++];
+        c.live = static_cast<char *>(live);
+        c.bytes = bytes;
+        c.per_env = per_env;
+        c.kind = kind;
+        c.off = off;
+        off += (((size_t)k * per_env * bytes) + 255) / 256 * 256;
+    };
+    for (int r = 0; r < 7; ++r) add(h->dev.state + r * N, 8, A);
+    for (int r = 0; r < 2; ++r) add(h->dev.steer_buf + r * N, 8, A);
+    add(h->dev.buf_cnt, 4, A);
+    for (int r = 0; r < 3; ++r) add(h->dev.snap_pose + r * N, 8, A);
+    add(h->dev.collisions, 8, A);
+    add(h->dev.collision_idx, 8, A);
+    add(h->dev.in_collision, 4, A);
+    add(h->dev.step_count, 4, A);
+    if (cols & F110_STATE_COL_RNG) add(h->d_rng_state, sizeof(U128), A, h->dev.noise_rng == 1 ? kStateColRngShared : 0);
+    if (cols & F110_STATE_COL_RNG_SEED) add(h->d_rng_seed, 2 * sizeof(U128), A);
+    if (cols & F110_STATE_COL_EPISODE) {
+        const EpisodeArrays &ep = h->ep;
+        add(ep.start_poses, 24, A);
+        add(ep.near_start, 1, A);
+        add(ep.toggle, 8, A);
+        add(ep.lap_count, 8, A);
+        add(ep.lap_time, 8, A);
+        add(ep.checkpoint, 1, A);
+        add(ep.rot, 32, 1);
+        add(ep.current_time, 8, 1);
+        add(ep.done, 1, 1);
+    }
+    if (cols & F110_STATE_COL_PARAMS) add(h->d_params_all, NPARAMS * 8, A);
+    if (cols & F110_STATE_COL_ENV_MAP) add(h->d_env_map, 4, 1);
+    if (cols & F110_STATE_COL_SCANS) add(h->dev.scans, B * 8, A);   // last: launched on its own (state_launch)
+    t.num_envs = h->cfg.num_envs;
+    t.step_count = h->dev.step_count;
+    t.rowstate = h->d_rng_rowstate;
+    t.noise_rows = h->dev.noise_rows;
+    if (out) *out = t;
+    return off;
+}
+
+enum StateDir { STATE_PACK, STATE_UNPACK, STATE_CLONE };
+
+// the copy as launches on the main stream: the small columns in one (a workgroup row per column), the scans in a second launch
+// sized for them, so neither waits on the other's grid
+static int state_launch(f110_sim *h, StateDir dir, const StateCols &all, const StateHeader *hdr, char *blob, int blob_k,
+                        const int32_t *src, const int32_t *dst, int k, int32_t *status)
+{
+    if (k <= 0) return F110_OK;
+    StateCols parts[2] = {all, all};
+    parts[0].n = 0;
+    parts[1].n = 0;
+    for (int i = 0; i < all.n; ++i) {
+        StateCols &p = parts[all.c[i].bytes > 1024 ? 1 : 0];
+        p.c[p.n++] = all.c[i];
+    }
+    for (int part = 0; part < 2; ++part) {
+        const StateCols &p = parts[part];
+        if (p.n == 0) continue;
+        uint64_t units = 0;
+        for (int i = 0; i < p.n; ++i) {
+            const uint32_t b = p.c[i].bytes, unit = (b & 15u) == 0u ? 16u : ((b & 7u) == 0u ? 8u : ((b & 3u) == 0u ? 4u : 1u));
+            units = std::max<uint64_t>(units, (uint64_t)(b / unit) * p.c[i].per_env * (uint64_t)k);
+        }
+        const dim3 grid((unsigned)std::min<uint64_t>((units + 255) / 256, part == 0 ? 2048u : 8192u), (unsigned)p.n), block(256);
+        int32_t *st = part == 0 ? status : nullptr;   // an entry is counted once, by the first launch
+        if (dir == STATE_PACK) {   // (both launches store the same header)
+            hipLaunchKernelGGL(k_state_pack, grid, block, 0, h->stream, p, *hdr, src, k, blob, st);
+        } else if (dir == STATE_UNPACK) {
+            hipLaunchKernelGGL(k_state_unpack, grid, block, 0, h->stream, p, blob, blob_k, src, dst, k, st);
+        } else {
+            hipLaunchKernelGGL(k_clone_envs, grid, block, 0, h->stream, p, src, dst, k, st);
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    return F110_OK;
+}
+
+size_t f110_state_bytes(const f110_sim *h, int32_t n_envs, int32_t flags)
+{
+    if (!h || n_envs < 0) return 0;
+    return state_columns(h, state_col_set(h) | ((flags & F110_STATE_SCANS) ? F110_STATE_COL_SCANS : 0u), n_envs, nullptr);
+}
+
+static StateHeader state_header(const f110_sim *h, int k, int32_t flags, uint32_t cols, size_t bytes)
+{
+    StateHeader hd{};
+    std::memcpy(hd.magic, "F110SNAP", 8);
+    hd.version = F110_STATE_VERSION;
+    hd.k = k;
+    hd.A = h->cfg.num_agents;
+    hd.B = h->cfg.num_beams;
+    hd.flags = flags & F110_STATE_SCANS;
+    hd.cols = cols;
+    hd.noise_mode = h->noise_src;
+    hd.noise_rows = h->dev.noise_rows;
+    hd.n_maps = h->multi_map ? 1 + (int32_t)h->extra_maps.size() : 0;
+    hd.ego_idx = h->has_episode ? h->ep.ego_idx : -1;
+    hd.max_step = h->noise_ub;   // the host's bound on every agent's step_count
+    for (int w = 0; w < 4; ++w) hd.noise_id[w] = h->noise_src_id[w];
+    hd.std_dev = h->dev.noise_rng ? h->noise_gen.scale : 0.0;
+    hd.total_bytes = bytes;
+    return hd;
+}
+
+static const char *state_col_name(uint32_t bit)
+{
+    switch (bit) {
+    case F110_STATE_COL_RNG: return "device-noise stream positions";
+    case F110_STATE_COL_RNG_SEED: return "per-agent noise seeds";
+    case F110_STATE_COL_EPISODE: return "episode (f110_episode_init)";
+    case F110_STATE_COL_PARAMS: return "per-agent params (f110_set_params_batch)";
+    case F110_STATE_COL_ENV_MAP: return "env map slots (f110_set_env_maps)";
+    default: return "agent";
+    }
+}
+
+// may the blob with header hd go into h?  (F110_ERR_STATE with a message when not)
+static int state_check(f110_sim *h, const StateHeader &hd)
+{
+    if (std::memcmp(hd.magic, "F110SNAP", 8) != 0) return fail(h, F110_ERR_STATE, "not a simulator state blob (bad magic)");
+    if (hd.version != F110_STATE_VERSION)
+        return fail(h, F110_ERR_STATE, "state blob format version %u, this library reads version %d", hd.version, F110_STATE_VERSION);
+    if (hd.A != h->cfg.num_agents || hd.B != h->cfg.num_beams)
+        return fail(h, F110_ERR_STATE, "state blob of %d agents per env x %d beams, this handle has %d x %d", hd.A, hd.B, h->cfg.num_agents,
+                    h->cfg.num_beams);
+    if (hd.k < 0) return fail(h, F110_ERR_STATE, "state blob with a negative env count");
+    static const char *modes[] = {"no noise", "a noise table", "the shared device noise stream", "per-agent device noise streams"};
+    const int mb = hd.noise_mode, mh = h->noise_src;
+    if (mb < 0 || mb > 3) return fail(h, F110_ERR_STATE, "state blob with an unknown noise mode %d", mb);
+    if (mb != mh) return fail(h, F110_ERR_STATE, "state blob saved with %s, this handle has %s", modes[mb], modes[mh]);
+    if ((mb == 1 || mb == 2) && std::memcmp(hd.noise_id, h->noise_src_id, sizeof hd.noise_id) != 0)
+        return fail(h, F110_ERR_STATE, "state blob saved with a different %s (%s)", mb == 1 ? "noise table" : "noise seed",
+                    mb == 1 ? "table contents" : "PCG64 state");
+    if (mb >= 2 && hd.std_dev != h->noise_gen.scale)
+        return fail(h, F110_ERR_STATE, "state blob saved with noise std_dev %g, this handle has %g", hd.std_dev, h->noise_gen.scale);
+    const uint32_t want = state_col_set(h), have = hd.cols & ~(uint32_t)F110_STATE_COL_SCANS;
+    for (uint32_t bit = F110_STATE_COL_RNG; bit <= F110_STATE_COL_ENV_MAP; bit <<= 1) {
+        if ((have & bit) && !(want & bit))
+            return fail(h, F110_ERR_STATE, "state blob holds %s columns, which are not active on this handle", state_col_name(bit));
+        if (!(have & bit) && (want & bit))
+            return fail(h, F110_ERR_STATE, "state blob has no %s columns, which are active on this handle", state_col_name(bit));
+    }
+    if (!(have & F110_STATE_COL_AGENT) || (hd.cols & ~0x7fu)) return fail(h, F110_ERR_STATE, "state blob with an unknown column set 0x%x", hd.cols);
+    if ((hd.cols & F110_STATE_COL_SCANS) != ((hd.flags & F110_STATE_SCANS) ? (uint32_t)F110_STATE_COL_SCANS : 0u))
+        return fail(h, F110_ERR_STATE, "state blob header is inconsistent (flags / columns)");
+    if ((have & F110_STATE_COL_ENV_MAP) && hd.n_maps > 1 + (int)h->extra_maps.size())
+        return fail(h, F110_ERR_STATE, "state blob uses %d map slots, this handle has %d", hd.n_maps, 1 + (int)h->extra_maps.size());
+    if (hd.total_bytes != state_columns(h, hd.cols, hd.k, nullptr)) return fail(h, F110_ERR_STATE, "state blob size does not match its header");
+    if (hd.max_step < 0) return fail(h, F110_ERR_STATE, "state blob with a negative step bound");
+    return F110_OK;
+}
+
+// host invariants after restored / cloned entries landed (stream-ordered on the main stream)
+static int state_after_load(f110_sim *h, long long max_step, bool whole)
+{
+    h->noise_ub = whole ? max_step : std::max(h->noise_ub, max_step);   // the row cache grows to it at the next step (f110_step_device)
+    if (h->multi_map) {   // the slots changed under the scan order: rebuild it from the restored assignment
+        std::vector<int32_t> em((size_t)h->cfg.num_envs);
+        HIPCHK(h, hipMemcpyAsync(em.data(), h->d_env_map, sizeof(int32_t) * em.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        TRY(f110_set_env_maps(h, em.data()));
+    }
+    return F110_OK;
+}
+
+int f110_state_save_device(f110_sim *h, const int32_t *d_env_idx, int32_t k, void *d_blob, int32_t flags)
+{
+    if (!h || !d_blob) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    if (k < 0 || (!d_env_idx && k != h->cfg.num_envs))
+        return fail(h, F110_ERR_INVALID, "f110_state_save_device: k = %d (without an index list k must be num_envs = %d)", k, h->cfg.num_envs);
+    if (reinterpret_cast<uintptr_t>(d_blob) & 15u) return fail(h, F110_ERR_INVALID, "f110_state_save_device: the blob must be 16-byte aligned");
+    const uint32_t cols = state_col_set(h) | ((flags & F110_STATE_SCANS) ? F110_STATE_COL_SCANS : 0u);
+    StateCols t;
+    const size_t bytes = state_columns(h, cols, k, &t);
+    const StateHeader hd = state_header(h, k, flags, cols, bytes);
+    if (k == 0) {
+        HIPCHK(h, hipMemcpyAsync(d_blob, &hd, sizeof hd, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return F110_OK;
+    }
+    return state_launch(h, STATE_PACK, t, &hd, static_cast<char *>(d_blob), 0, d_env_idx, nullptr, k, nullptr);
+}
+
+static int state_load_blob(f110_sim *h, const StateHeader &hd, const void *d_blob, const int32_t *d_src, const int32_t *d_dst, int32_t k,
+                           int32_t *d_status, bool whole)
+{
+    TRY(state_check(h, hd));
+    StateCols t;
+    (void)state_columns(h, hd.cols, hd.k, &t);   // the blob's sections (the scans only when it has them)
+    TRY(state_launch(h, STATE_UNPACK, t, nullptr, static_cast<char *>(const_cast<void *>(d_blob)), hd.k, d_src, d_dst, k, d_status));
+    return state_after_load(h, hd.max_step, whole);
+}
+
+int f110_state_load_device(f110_sim *h, const void *d_blob, const int32_t *d_src, const int32_t *d_dst, int32_t k, int32_t *d_status)
+{
+    if (!h || !d_blob) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    if (k < 0) return fail(h, F110_ERR_INVALID, "f110_state_load_device: k = %d", k);
+    if (reinterpret_cast<uintptr_t>(d_blob) & 15u) return fail(h, F110_ERR_INVALID, "f110_state_load_device: the blob must be 16-byte aligned");
+    StateHeader hd{};
+    HIPCHK(h, hipMemcpyAsync(&hd, d_blob, sizeof hd, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return state_load_blob(h, hd, d_blob, d_src, d_dst, k, d_status, false);
+}
+
+int f110_clone_envs_device(f110_sim *h, const int32_t *d_src, const int32_t *d_dst, int32_t k, int32_t *d_status)
+{
+    if (!h || !d_src || !d_dst) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    if (k < 0) return fail(h, F110_ERR_INVALID, "f110_clone_envs_device: k = %d", k);
+    StateCols t;
+    (void)state_columns(h, state_col_set(h) | F110_STATE_COL_SCANS, k, &t);   // the observation travels with the state
+    TRY(state_launch(h, STATE_CLONE, t, nullptr, nullptr, 0, d_src, d_dst, k, d_status));
+    return state_after_load(h, h->noise_ub, false);   // (clones are copies of envs of this handle: the step bound holds)
+}
+
+static int state_scratch(f110_sim *h, size_t bytes)
+{
+    if (bytes <= h->state_blob_bytes) return F110_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_state_blob) (void)hipFree(h->d_state_blob);
+    h->d_state_blob = nullptr;
+    h->state_blob_bytes = 0;
+    HIPCHK(h, hipMalloc(&h->d_state_blob, bytes));
+    h->state_blob_bytes = bytes;
+    return F110_OK;
+}
+
+int f110_state_save(f110_sim *h, void *h_blob, int32_t flags)
+{
+    if (!h || !h_blob) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    const int E = h->cfg.num_envs;
+    const uint32_t cols = state_col_set(h) | ((flags & F110_STATE_SCANS) ? F110_STATE_COL_SCANS : 0u);
+    StateCols t;
+    const size_t bytes = state_columns(h, cols, E, &t);
+    TRY(state_scratch(h, bytes));
+    const StateHeader hd = state_header(h, E, flags, cols, bytes);
+    TRY(state_launch(h, STATE_PACK, t, &hd, static_cast<char *>(h->d_state_blob), 0, nullptr, nullptr, E, nullptr));
+    HIPCHK(h, hipMemcpyAsync(h_blob, h->d_state_blob, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+int f110_state_load(f110_sim *h, const void *h_blob)
+{
+    if (!h || !h_blob) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    StateHeader hd;
+    std::memcpy(&hd, h_blob, sizeof hd);
+    TRY(state_check(h, hd));
+    if (hd.k != h->cfg.num_envs)
+        return fail(h, F110_ERR_STATE, "state blob of %d envs, this handle has %d (f110_state_load_device takes index lists)", hd.k, h->cfg.num_envs);
+    TRY(state_scratch(h, hd.total_bytes));
+    HIPCHK(h, hipMemcpyAsync(h->d_state_blob, h_blob, hd.total_bytes, hipMemcpyHostToDevice, h->stream));
+    TRY(state_load_blob(h, hd, h->d_state_blob, nullptr, nullptr, hd.k, nullptr, true));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // the caller's buffer is consumed on return
     return F110_OK;
 }
 

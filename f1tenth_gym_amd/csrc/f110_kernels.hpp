@@ -3238,3 +3238,107 @@ __global__ void k_interleave_cs(const double *__restrict__ sines, const double *
     if (i < n) cs[i] = make_double2(cosines[i], sines[i]);
 }
 
+
+// ---- exact snapshot / restore / clone of the simulator state (f110_state_*, f110_clone_envs_device) ----------------------------
+// The host lists every column a step or the episode logic reads (StateCols, built by state_columns in f110_hip.hip).  A column is
+// items of `bytes` bytes, `per_env` items per env (A: a per-agent column, 1: a per-env one), item i of the live column at
+// live + i * bytes.  In a blob each column is one section [k * per_env][bytes] starting at `off`, so the threads of a wave move
+// consecutive items (or consecutive 16-byte words of one wide item, the scans) — coalesced on both sides.  One routine serves
+// the three directions: live env -> blob entry (pack), blob entry -> live env (unpack), live env -> live env (clone).
+constexpr int kStateMaxCols = 32;
+constexpr uint32_t kStateColRngShared = 1;   // rng_state in the shared-stream mode (see k_state_pack)
+struct StateCol {
+    char *live;
+    uint64_t off;
+    uint32_t bytes, per_env;
+    uint32_t kind, pad;
+};
+struct StateCols {
+    StateCol c[kStateMaxCols];
+    int32_t n, num_envs;
+    const int32_t *step_count;   // kStateColRngShared: the live step counters ...
+    const U128 *rowstate;        // ... the row cache's start states [noise_rows + 1] ...
+    int32_t noise_rows, pad;     // ... and its capacity
+};
+
+// the 256 bytes at the start of every blob (include/f110.h documents the fields; f1tenth_gym_amd/core.py StateBlob parses them)
+struct StateHeader {
+    char magic[8];          // "F110SNAP"
+    uint32_t version;
+    int32_t k, A, B, flags;
+    uint32_t cols;          // F110_STATE_COL_* present
+    int32_t noise_mode, noise_rows, n_maps, ego_idx;
+    int64_t max_step;       // upper bound of every step_count in the blob
+    uint64_t noise_id[4];
+    double std_dev;
+    uint64_t total_bytes;
+    uint64_t reserved[19];
+};
+static_assert(sizeof(StateHeader) == 256, "the blob header is 256 bytes");
+
+template <bool SRC_LIVE, bool DST_LIVE>
+__device__ __forceinline__ void state_copy(const StateCols &cols, const char *__restrict__ blob_src, char *__restrict__ blob_dst,
+                                           const int32_t *__restrict__ src_idx, const int32_t *__restrict__ dst_idx, int k, int src_lim,
+                                           int32_t *status)
+{
+    const int ci = (int)blockIdx.y;
+    if (ci >= cols.n) return;
+    const StateCol c = cols.c[ci];
+    const uint32_t unit = (c.bytes & 15u) == 0u ? 16u : ((c.bytes & 7u) == 0u ? 8u : ((c.bytes & 3u) == 0u ? 4u : 1u));
+    const uint32_t upi = c.bytes / unit;                 // units per item
+    const uint64_t upe = (uint64_t)upi * c.per_env;      // units per index-list entry
+    const uint64_t total = upe * (uint64_t)k;
+    const int E = cols.num_envs;
+    for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < total; u += (uint64_t)gridDim.x * blockDim.x) {
+        const int j = (int)(u / upe);
+        const uint64_t r = u - (uint64_t)j * upe;
+        const uint32_t s = (uint32_t)(r / upi), w = (uint32_t)(r - (uint64_t)s * upi);
+        const int se = src_idx ? src_idx[j] : j;
+        const int de = dst_idx ? dst_idx[j] : j;
+        const bool ok = se >= 0 && se < src_lim && (!DST_LIVE || (de >= 0 && de < E));
+        if (!ok) {   // skipped, counted once per entry
+            if (ci == 0 && r == 0 && status) atomicAdd(status, 1);
+            continue;
+        }
+        const uint64_t si = (uint64_t)se * c.per_env + s, di = (uint64_t)de * c.per_env + s;
+        const char *src = SRC_LIVE ? c.live + si * c.bytes : blob_src + c.off + si * c.bytes;
+        char *dst = DST_LIVE ? c.live + di * c.bytes : blob_dst + c.off + di * c.bytes;
+        src += (uint64_t)w * unit;
+        dst += (uint64_t)w * unit;
+        if (SRC_LIVE && !DST_LIVE && c.kind == kStateColRngShared) {
+            // the shared stream: an agent still inside the row cache never advanced its own state, so the blob gets the stream
+            // position of its next row from the cache's start states — a canonical value whatever cache size the target has
+            const int32_t n = cols.step_count[si];
+            if (n >= 0 && n <= cols.noise_rows) src = reinterpret_cast<const char *>(cols.rowstate + n);
+        }
+        switch (unit) {
+        case 16: *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(src); break;
+        case 8: *reinterpret_cast<uint2 *>(dst) = *reinterpret_cast<const uint2 *>(src); break;
+        case 4: *reinterpret_cast<uint32_t *>(dst) = *reinterpret_cast<const uint32_t *>(src); break;
+        default: *dst = *src; break;
+        }
+    }
+}
+
+// live env env_idx[j] (env j when env_idx is null) -> blob entry j; the first workgroup also stores the header
+__global__ void __launch_bounds__(256) k_state_pack(StateCols cols, StateHeader hdr, const int32_t *__restrict__ env_idx, int k, char *__restrict__ blob,
+                                                    int32_t *status)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < sizeof(StateHeader) / 8)
+        reinterpret_cast<uint64_t *>(blob)[threadIdx.x] = reinterpret_cast<const uint64_t *>(&hdr)[threadIdx.x];
+    state_copy<true, false>(cols, nullptr, blob, env_idx, nullptr, k, cols.num_envs, status);
+}
+
+// blob entry src[j] (j when src is null) -> live env dst[j]; several dst may name one src
+__global__ void __launch_bounds__(256) k_state_unpack(StateCols cols, const char *__restrict__ blob, int blob_k, const int32_t *__restrict__ src,
+                                                      const int32_t *__restrict__ dst, int k, int32_t *status)
+{
+    state_copy<false, true>(cols, blob, nullptr, src, dst, k, blob_k, status);
+}
+
+// live env src[j] -> live env dst[j] in one launch (src and dst disjoint, no dst twice: the host checks host-side index lists)
+__global__ void __launch_bounds__(256) k_clone_envs(StateCols cols, const int32_t *__restrict__ src, const int32_t *__restrict__ dst, int k,
+                                                    int32_t *status)
+{
+    state_copy<true, true>(cols, nullptr, nullptr, src, dst, k, cols.num_envs, status);
+}

@@ -8,6 +8,7 @@ advances one zero-action step and returns a 4-tuple (:306-349), `step(action)` r
 scope for this build: `render()` raises NotImplementedError.
 `gym` is optional: when importable F110Env subclasses gym.Env, otherwise `object`.
 """
+import copy
 import os
 
 import numpy as np
@@ -177,7 +178,21 @@ class F110Env(_EnvBase):
         self.collisions = obs['collisions']
         done, toggles = self._lap.update_single(obs['poses_x'], obs['poses_y'], obs['collisions'], self.timestep)
         info = {'checkpoint_done': toggles}
+        self._last = (obs, reward, done, info)
         return obs, reward, done, info
+
+    def snapshot(self):
+        """an exact copy of the env: simulator state (device blob), lap bookkeeping and the last (obs, reward, done, info)"""
+        return {"sim": self.sim.snapshot(), "host": copy.deepcopy((self._lap, self.poses_x, self.poses_y, self.poses_theta,
+                                                                    self.collisions, self.current_obs, self.render_obs,
+                                                                    getattr(self, "_last", None)))}
+
+    def restore(self, snap):
+        """back to a snapshot(); returns the (obs, reward, done, info) of the step before it"""
+        self.sim.restore(snap["sim"])
+        (self._lap, self.poses_x, self.poses_y, self.poses_theta, self.collisions, self.current_obs, self.render_obs,
+         self._last) = copy.deepcopy(snap["host"])
+        return copy.deepcopy(self._last)
 
     def reset(self, poses):
         poses = np.asarray(poses, dtype=np.float64)
@@ -355,6 +370,27 @@ class F110VecEnv(object):
             self._last = (obs, reward, done, info)
             return self._last
         return self.step(np.zeros((self.num_envs, self.num_agents, 2)))
+
+    def snapshot(self):
+        """an exact copy of the vector env: simulator state (device blob, episode columns included with device_logic), the
+        host lap bookkeeping, the start poses and the last (obs, reward, done, info)"""
+        return {"sim": self.sim.snapshot(), "host": copy.deepcopy((self._lap, self._start_poses, self._last))}
+
+    def restore(self, snap):
+        """back to a snapshot(); returns the (obs, reward, done, info) of the step before it.  With device_logic the page-locked
+        views step() hands out show that observation again."""
+        self.sim.restore(snap["sim"])
+        self._lap, self._start_poses, last = copy.deepcopy(snap["host"])
+        if self.device_logic and last is not None and not self.copy_obs:
+            obs, r, done, info = self._ret_views   # write the saved observation into the block's views
+            for mine, saved in ((obs, last[0]), (info, last[3])):
+                for k, v in mine.items():
+                    if isinstance(v, np.ndarray):
+                        np.copyto(v, saved[k])
+            np.copyto(done, last[2])
+            last = self._ret_views
+        self._last = last
+        return last
 
     def _step_device(self, actions, sync=True):
         b, hb = self.sim.batch, self._hb

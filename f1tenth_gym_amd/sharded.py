@@ -185,6 +185,20 @@ class ShardedVecEnv(object):
         self._after_step()
         return self._assemble(parts)
 
+    def snapshot(self):
+        """an exact copy of every shard (F110VecEnv.snapshot: one state blob per shard)"""
+        return {"shard_sizes": list(self.shard_sizes), "shards": self._each(lambda k, s: s.snapshot())}
+
+    def restore(self, snap):
+        """back to a snapshot() of a ShardedVecEnv with the same shard sizes; returns the (obs, reward, done, info) of the step
+        before it"""
+        if list(snap["shard_sizes"]) != list(self.shard_sizes):
+            raise ValueError("the snapshot has shard sizes %s, this env %s" % (snap["shard_sizes"], self.shard_sizes))
+        parts = self._each(lambda k, s: s.restore(snap["shards"][k]))
+        if any(p is None for p in parts):
+            return None
+        return self._assemble(parts)
+
     @property
     def action_buffers(self):
         """per shard: the page-locked [E_k][A][2] buffer its kernels read in place (fill them and call step(None))"""

@@ -5,6 +5,7 @@ Same constructor arguments, attributes (`agent_poses`, `collisions`, `collision_
 the per-agent Python loop is replaced by one device step over all envs.  Extension:
 `num_envs=E` steps E independent copies in lockstep (observations gain a leading env axis).
 """
+import copy
 from enum import Enum
 
 import numpy as np
@@ -154,6 +155,31 @@ class Simulator(object):
         self._b.reset(flat, env_mask)
         if env_mask is None or np.all(env_mask):
             self._steps_since_full_reset = 0
+
+    def snapshot(self, scans=True):
+        """an exact copy of the simulation state: the device blob (BatchSim.save_state) and the host side — the steps since the
+        last full reset, the noise table's position (noise_mode='table') and the host mirrors of the last step"""
+        snap = {"blob": self._b.save_state(scans=scans), "steps": self._steps_since_full_reset,
+                "mirrors": copy.deepcopy((self.agent_poses, self.collisions, self.collision_idx, self._state, self._in_collision))}
+        if self._noise is not None:
+            snap["noise"] = (self._noise.rows.shape[0], copy.deepcopy(self._noise.rng.bit_generator.state))
+        return snap
+
+    def restore(self, snap):
+        """back to a snapshot() of this Simulator (or of one with the same shape and configuration)"""
+        if self._noise is not None:
+            if "noise" not in snap:
+                raise ValueError("the snapshot was taken without a noise table (noise_mode='table')")
+            rows, rng_state = snap["noise"]
+            if self._noise.rows.shape[0] < rows:
+                raise ValueError("the snapshot's noise table (%d rows) is longer than this Simulator's (%d)" % (rows, self._noise.rows.shape[0]))
+            if self._noise.rows.shape[0] != rows:   # the table as it was: the prefix is the same stream
+                self._noise.rows = self._noise.rows[:rows].copy()
+                self._noise.rng.bit_generator.state = copy.deepcopy(rng_state)
+                self._b.set_noise_table(self._noise.rows)
+        self._b.load_state(snap["blob"])
+        self._steps_since_full_reset = snap["steps"]
+        self.agent_poses, self.collisions, self.collision_idx, self._state, self._in_collision = copy.deepcopy(snap["mirrors"])
 
     def step(self, control_inputs):
         E, A = self.num_envs, self.num_agents

@@ -298,9 +298,58 @@ typedef struct f110_obs_host {
     int32_t *step_count;    /* [N]  steps since reset */
 } f110_obs_host;
 int f110_get_obs(f110_sim *h, const f110_obs_host *out);
+/* A PARTIAL setter: RaceCar.state, the steering delay FIFO and its count, nothing else.  It leaves step_count (which picks the
+ * noise row), in_collision / collisions / collision_idx / agent_poses, the agents' noise-stream positions, the episode arrays and
+ * the host's bound on the steps since the last full reset as they are — a batch "restored" this way diverges at its first noisy
+ * scan.  The exact snapshot / restore / clone of every column is f110_state_* / f110_clone_envs_device below. */
 int f110_set_state(f110_sim *h, const double *h_state7 /* [N][7] */,
                    const double *h_steer_buf /* [N][2] newest first, or NULL */,
                    const int32_t *h_buf_count /* [N] or NULL */);
+
+/* ---- exact snapshot, restore and clone of the simulator state (save / resume, roll-back, branching; the reference deep-copies
+ * its Python objects, base_classes.py:98-112, f110_env.py:165-189).  A blob is a 256-byte header followed by one section per
+ * column, [column][k * A] for per-agent columns and [column][k] for per-env ones (k = envs in the blob), each section 256-byte
+ * aligned.  It carries, per agent: state[7], the steer FIFO [2] and its count, agent_poses[3], collisions, collision_idx,
+ * in_collision, step_count, the noise-stream position (any device noise) and seed (per-agent streams); per env, once
+ * f110_episode_init has run: start poses, start_rot[4], current_time, done and per agent near_start, toggle, lap_count, lap_time,
+ * checkpoint; the [A][18] rows of f110_set_params_batch and the env's map slot while those are active; optionally
+ * (F110_STATE_SCANS) the last scans [k * A][B].  NOT carried — configuration the target must already have: the maps and their
+ * slots' tables, the beam / trig tables, the per-slot params, the noise table or seed, the auto re-seat poses.
+ * Header (little-endian): char magic[8] "F110SNAP"; uint32 version (F110_STATE_VERSION); int32 k, A, B, flags; uint32 columns
+ * (F110_STATE_COL_*); int32 noise_mode (0 off, 1 table, 2 shared PCG64 stream, 3 a stream per agent), noise_rows, n_maps,
+ * ego_idx; int64 max_step (>= every step_count in the blob); uint64 noise_id[4] (shared stream: the PCG64 words of
+ * f110_set_noise_rng; table: {FNV-1a 64 of its bytes, rows, B, 0}); double std_dev; uint64 total_bytes; zeros to 256.
+ * A load refuses (F110_ERR_STATE, with a message) a blob of another version, A or B, another noise source, or a column set other
+ * than the columns active on the target (episode, params, env map, noise); E may differ: entries are per env.  After a load
+ * the host's bound on the steps since the last full reset covers every restored step_count, so the noise row cache grows as
+ * far as the restored episodes need.  Every call joins a two-block step first; a save is stream-ordered behind the step before
+ * it and a load in front of the step after it.  Out-of-range indices of the device forms are skipped (nothing is read or written
+ * out of bounds) and counted into *d_status (device int32, may be NULL); a dst named twice is undefined there.
+ * f110_clone_envs_device: env src[j] -> env dst[j] in one launch, no blob — src and dst must be disjoint. */
+#define F110_STATE_VERSION 1
+#define F110_STATE_SCANS 1            /* flags: the blob also holds the last scans */
+enum {
+    F110_STATE_COL_AGENT = 1,         /* state, steer FIFO, count, agent_poses, collision flags, step_count (always) */
+    F110_STATE_COL_SCANS = 2,
+    F110_STATE_COL_RNG = 4,           /* noise-stream position per agent (device noise) */
+    F110_STATE_COL_RNG_SEED = 8,      /* per-agent streams: the seed words */
+    F110_STATE_COL_EPISODE = 16,
+    F110_STATE_COL_PARAMS = 32,       /* f110_set_params_batch rows */
+    F110_STATE_COL_ENV_MAP = 64       /* f110_set_env_maps slot */
+};
+#define F110_STATE_HEADER_BYTES 256
+/* bytes of a blob of n_envs envs (the handle's current column set) */
+size_t f110_state_bytes(const f110_sim *h, int32_t n_envs, int32_t flags);
+/* envs d_env_idx[0..k) (NULL: every env, k must be num_envs) -> the device blob d_blob (16-byte aligned), asynchronous */
+int f110_state_save_device(f110_sim *h, const int32_t *d_env_idx, int32_t k, void *d_blob, int32_t flags);
+/* blob entry d_src[j] (NULL: j) -> env d_dst[j] (NULL: j), j < k; several dst may name one src.  Reads the header (a small
+ * synchronous copy), then asynchronous. */
+int f110_state_load_device(f110_sim *h, const void *d_blob, const int32_t *d_src, const int32_t *d_dst, int32_t k, int32_t *d_status);
+int f110_clone_envs_device(f110_sim *h, const int32_t *d_src, const int32_t *d_dst, int32_t k, int32_t *d_status);
+/* the whole handle to / from host memory (f110_state_bytes(h, num_envs, flags) bytes; f110_host_alloc memory for a full-rate
+ * copy); both return once the copy is complete */
+int f110_state_save(f110_sim *h, void *h_blob, int32_t flags);
+int f110_state_load(f110_sim *h, const void *h_blob);
 
 /* device-resident observation buffers (valid until f110_destroy; contents valid after the
  * step that produced them completes on the stream).  SoA columns of N doubles. */
