@@ -78,6 +78,17 @@ class DeviceViews(C.Structure):
                 ("in_collision", C.c_void_p), ("step_count", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class TrackViews(C.Structure):
+    """struct f110_track_views: device pointers of the step's track columns"""
+    _fields_ = [("s", C.c_void_p), ("ds", C.c_void_p), ("lateral", C.c_void_p), ("heading_error", C.c_void_p),
+                ("segment", C.c_void_p)]
+
+
+class TrackHost(C.Structure):
+    """f110_track_host: host destinations of the track columns (any may be NULL)"""
+    _fields_ = [("s", _dp), ("ds", _dp), ("lateral", _dp), ("heading_error", _dp), ("segment", _i32p)]
+
+
 # name -> (restype, argtypes); every symbol include/f110.h declares
 PROTOTYPES = {
     "f110_last_error": (C.c_char_p, [C.c_void_p]),
@@ -169,6 +180,12 @@ PROTOTYPES = {
     "f110_ttc_batch": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int32, C.c_double, _i32p]),
     "f110_raycast_batch": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int32, _dp, _i32p]),
     "f110_get_range_batch": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp]),
+    "f110_track_set": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32]),
+    "f110_track_enable": (C.c_int, [C.c_void_p, C.c_int32]),
+    "f110_track_views": (C.c_int, [C.c_void_p, C.POINTER(TrackViews)]),
+    "f110_track_get": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
+    "f110_track_host_block": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
+    "f110_track_project_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp]),
     "f110_edt_sq": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, _u32p]),
     "f110_beam_dir_index_batch": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i32p]),
     "f110_dt_from_bitmap": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, C.c_double, _dp]),

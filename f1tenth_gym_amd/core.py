@@ -959,6 +959,70 @@ class BatchSim(object):
             res.append(lk)
         return res[0] if len(res) == 1 else tuple(res)
 
+    # ------------------------------------------------------------------ track progress (f110_track_*)
+    TRACK_FIELDS = ("s", "ds", "lateral", "heading_error", "segment")
+
+    def set_track(self, track, slot=0):
+        """attach a raceline (a Track, an [M][2] array or a csv path) to map slot `slot`; returns the Track"""
+        from .track import Track
+        t = Track.coerce(track)
+        xy = np.ascontiguousarray(t.xy, dtype=np.float64)
+        check(_ffi.lib().f110_track_set(self._h, int(slot), dptr(xy), xy.shape[0], 1 if t.closed else 0), self._h)
+        self.tracks = dict(getattr(self, "tracks", {}))
+        self.tracks[int(slot)] = t
+        return t
+
+    def enable_track(self, on=True):
+        """with on, every step also produces the track columns (s, ds, lateral, heading_error, segment)"""
+        check(_ffi.lib().f110_track_enable(self._h, 1 if on else 0), self._h)
+        self.track_on = bool(on)
+
+    def track_views(self):
+        """the track columns in device memory: DeviceArrays [N] (float64; segment int32), stable for the handle's life"""
+        v = _ffi.TrackViews()
+        check(_ffi.lib().f110_track_views(self._h, C.byref(v)), self._h)
+        N = self.N
+        return {"s": DeviceArray(self, (N,), np.float64, v.s), "ds": DeviceArray(self, (N,), np.float64, v.ds),
+                "lateral": DeviceArray(self, (N,), np.float64, v.lateral),
+                "heading_error": DeviceArray(self, (N,), np.float64, v.heading_error),
+                "segment": DeviceArray(self, (N,), np.int32, v.segment)}
+
+    def get_track(self):
+        """host copy of the last step's track columns"""
+        N = self.N
+        out = {k: np.empty(N) for k in self.TRACK_FIELDS[:4]}
+        out["segment"] = np.empty(N, dtype=np.int32)
+        o = _ffi.TrackHost(dptr(out["s"]), dptr(out["ds"]), dptr(out["lateral"]), dptr(out["heading_error"]), i32ptr(out["segment"]))
+        check(_ffi.lib().f110_track_get(self._h, C.byref(o)), self._h)
+        return out
+
+    def track_host_block(self, fields=TRACK_FIELDS):
+        """page-locked views step_host fills with the track columns (with the host block's completion semantics);
+        returns {name: NumPy view}, overwritten by every step_host"""
+        fields = tuple(fields)
+        N = self.N
+        views = {}
+        o = _ffi.TrackHost()
+        for f in fields:
+            if f not in self.TRACK_FIELDS:
+                raise KeyError(f)
+            v = self.pinned_empty((N,), np.int32 if f == "segment" else np.float64)
+            v[...] = 0
+            views[f] = v
+            setattr(o, f, i32ptr(v) if f == "segment" else dptr(v))
+        check(_ffi.lib().f110_track_host_block(self._h, C.byref(o)), self._h)
+        self._track_pinned = views   # (the block must outlive its registration)
+        return views
+
+    def track_project_batch(self, poses, slot=0):
+        """unit form: host poses [m][3] on the track of `slot` -> [m][5] = s, lateral, heading_error, segment, t"""
+        p = as_f64(poses)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("poses must be [m][3]")
+        out = np.empty((p.shape[0], 5))
+        check(_ffi.lib().f110_track_project_batch(self._h, int(slot), dptr(p), p.shape[0], dptr(out)), self._h)
+        return out
+
     # ------------------------------------------------------------------ the reference's example policy
     def pure_pursuit_batch(self, waypoints, poses, lookahead, vgain, wheelbase, max_reacquire=20.0):
         """PurePursuitPlanner.plan (examples/waypoint_follow.py:203-217) for host poses [m][3];

@@ -187,6 +187,26 @@ struct f110_sim {
     bool tiny_host_request = false;   // ... with one agent per env: what k_host_block would be handed
     HostBlock tiny_hb{};
     int tiny_episode = 0, tiny_auto_reset = 0;
+    // track progress (f110_track_*): a polyline per map slot, the step's columns, the per-agent cache of s
+    struct TrackSlot {
+        double *d_cols = nullptr;   // [7][nseg] (TrackCol)
+        int32_t nseg = 0, closed = 0;
+        double L = 0.0;
+    };
+    std::vector<TrackSlot> tracks;        // indexed by map slot (shorter than the slot list: the rest have no track)
+    TrackDesc *d_tracks = nullptr;        // [n_tracks_dev] what the kernels read
+    int n_tracks_dev = 0;
+    bool tracks_dirty = true;             // d_tracks does not reflect `tracks` / the slot count
+    bool track_lds = false;               // some track fits the LDS-staged form
+    bool track_on = false, track_checked = false;   // f110_track_enable; every env's slot has a track (checked since the last change)
+    std::vector<int32_t> env_map_host;    // f110_set_env_maps' assignment (meaningful while multi_map)
+    double *d_trk = nullptr;              // [4][N] s, ds, lateral, heading_error
+    int32_t *d_trk_seg = nullptr;         // [N]
+    double *d_trk_cache = nullptr;        // [3][N] cached s, x, y
+    int32_t *d_trk_ok = nullptr;          // [N]
+    f110_track_host trk_pinned{};         // f110_track_host_block, host pointers ...
+    HostBlock trk_hb{};                   // ... and their device views (the trk_* fields)
+    bool trk_pinned_on = false;
     // timing
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool profiling = false;
@@ -262,6 +282,9 @@ static int join_groups(f110_sim *h)
         (h)->touched = true;                              \
     } while (0)
 
+static int track_invalidate(f110_sim *h);     // (below, with the track entry points)
+static int track_prepare(f110_sim *h);
+static int track_launch(f110_sim *h, hipStream_t st, int mode, int begin, int count);
 static bool tiny_applies(const f110_sim *h);   // (below, with the step)
 static void noise_release(f110_sim *h);        // (below, with the noise entry points)
 
@@ -856,6 +879,13 @@ void f110_destroy(f110_sim *h)
     if (h->d_maps_full) (void)hipFree(h->d_maps_full);
     if (h->d_env_map) (void)hipFree(h->d_env_map);
     if (h->d_scan_order) (void)hipFree(h->d_scan_order);
+    for (auto &ts : h->tracks)
+        if (ts.d_cols) (void)hipFree(ts.d_cols);
+    {
+        void *tp[] = {h->d_tracks, h->d_trk, h->d_trk_seg, h->d_trk_cache, h->d_trk_ok};
+        for (void *p : tp)
+            if (p) (void)hipFree(p);
+    }
     {
         void *eptrs[] = {h->ep.start_poses, h->ep.rot, h->ep.current_time, h->ep.near_start, h->ep.toggle,
                          h->ep.lap_count, h->ep.lap_time, h->ep.done, h->ep.checkpoint, h->d_rot_stage, h->d_packed};
@@ -911,6 +941,7 @@ static int finish_map(f110_sim *h, int H, int W, double res, double ox, double o
 {
     ScanConst &k = h->k;
     h->multi_map = false;       // slot 0 changed: f110_set_env_maps has to be called again
+    TRY(track_invalidate(h));
     h->dev.maps_full = nullptr;
     h->dev.env_map = nullptr;
     fill_map_fields(k, H, W, res, ox, oy, oc, os);
@@ -1067,6 +1098,7 @@ int f110_set_env_maps(f110_sim *h, const int32_t *h_env_map)
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     ENTER(h);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    TRY(track_invalidate(h));   // the slots change under the cached s
     if (!h_env_map) {   // back to one map for everybody
         h->multi_map = false;
         h->dev.maps_full = nullptr;
@@ -1123,6 +1155,7 @@ int f110_set_env_maps(f110_sim *h, const int32_t *h_env_map)
     h->dev.maps_full = h->d_maps_full;
     h->dev.env_map = h->d_env_map;
     h->multi_map = true;
+    h->env_map_host.assign(h_env_map, h_env_map + E);
     return F110_OK;
 }
 
@@ -1812,6 +1845,20 @@ int f110_host_free(f110_sim *h, void *p)
         const char *hi = lo + (it != g_host_blocks.end() ? it->second : 1);
         auto inside = [&](const void *q) { return q && static_cast<const char *>(q) >= lo && static_cast<const char *>(q) < hi; };
         for (f110_sim *o : g_handles) {
+            if (o->trk_pinned_on) {
+                const f110_track_host &t = o->trk_pinned;
+                const void *tp[] = {t.s, t.ds, t.lateral, t.heading_error, t.segment};
+                bool thit = false;
+                for (const void *q : tp) thit = thit || inside(q);
+                if (thit) {
+                    if (o != h) {
+                        (void)hipSetDevice(o->cfg.device_id);
+                        (void)hipStreamSynchronize(o->stream);
+                    }
+                    o->trk_pinned_on = false;
+                    o->trk_pinned = f110_track_host{};
+                }
+            }
             if (!o->hb_valid && !o->fused_valid) continue;
             const f110_host_block &b = o->hb_host;
             const void *ptrs[] = {b.scans, b.state, b.agent_poses, b.collisions, b.collision_idx, b.in_collision, b.lap_times, b.lap_counts, b.toggles,
@@ -1957,9 +2004,19 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     // less per step); its parameters live in device memory and are rewritten only when they change
     // (not with F110_STEP_SPIN_WAIT: the completion word needs a system-scope release per workgroup, and the pair kernel
     // has N / 32 of them with the scan's dirty lines still in L2 — measured 0.657 -> 0.767 ms at 32 768 envs)
-    const bool want_fuse = A == 2 && !(flags & F110_STEP_NO_FUSE) && (!spin || tiny);
+    // tracking: the track columns are computed behind the step's last kernel, so the host block is k_host_block (no epilogue)
+    const bool want_fuse = A == 2 && !(flags & F110_STEP_NO_FUSE) && (!spin || tiny) && !h->track_on;
     h->tiny_request = tiny;
-    h->tiny_host_request = tiny && A == 1;
+    h->tiny_host_request = tiny && A == 1 && !h->track_on;
+    if (h->track_on && h->trk_pinned_on) {
+        hbk.trk_src = h->d_trk;
+        hbk.trk_seg_src = h->d_trk_seg;
+        hbk.trk_s = h->trk_hb.trk_s;
+        hbk.trk_ds = h->trk_hb.trk_ds;
+        hbk.trk_lat = h->trk_hb.trk_lat;
+        hbk.trk_head = h->trk_hb.trk_head;
+        hbk.trk_seg = h->trk_hb.trk_seg;
+    }
     if (h->tiny_host_request) {
         h->tiny_hb = hbk;
         h->tiny_episode = episode ? 1 : 0;
@@ -2317,6 +2374,7 @@ static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions)
     if (host && A == 2) h->tiny.fh = h->fused_host_copy;   // (what d_fused holds: f110_step_host keeps the two equal)
     // one env of two cars: finalize_duo_tiny puts the scans into the caller's block early (its idle wave copies, the window lanes follow)
     h->tiny.host_scans = (host && h->hb_valid && h->hb_scans_by_kernel && A == 2 && N == 2 && !(kExperimental && h->exp.tiny_general_tail)) ? h->hb_dev.scans : nullptr;
+    if (h->track_on) TRY(track_launch(h, st, kTrackHead, 0, N));
 #define TINY(P, I, H_) hipLaunchKernelGGL((k_step_tiny<P, I, H_>), grid, block, 0, st, dev, h->k, j, d_actions, h->tiny, ep, hb, episode, auto_reset)
     const bool ident = h->k.ident_rot != 0;
     if (A == 2) {
@@ -2328,6 +2386,10 @@ static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions)
     }
 #undef TINY
     h->last_launches = 1;
+    if (h->track_on) {   // (f110_step_host runs the host block as k_host_block behind this: no host epilogue while tracking)
+        TRY(track_launch(h, st, kTrackPost, 0, N));
+        h->last_launches += 2;
+    }
     return F110_OK;
 }
 
@@ -2341,6 +2403,7 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
     // the scan kernel of this step, decided ONCE: the launch below and what k_integrate prepares for it
     // (the longest-first list counter) follow the same answer
     const ScanKind scan = pick_scan(h, begin, count);
+    if (h->track_on) TRY(track_launch(h, st, kTrackHead, begin, count));   // s of the pose this step starts from (cache misses only)
     dev.sched_count_zero = scan == SCAN_AGENT_SCHED ? h->d_tcount + (h->task_epoch & 1u) : nullptr;
     if (dev.noise_rng && (dev.noise_rng == 2 || h->noise_ub >= (long long)dev.noise_rows)) {
         const int apb = dev.noise_rng == 2 ? 16 : 64;   // per-agent streams: every agent needs a row, keep the waves many
@@ -2572,6 +2635,8 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
         hipLaunchKernelGGL(k_finalize_solo, grid1d(count, 256), dim3(256), 0, st, dev);
     }
     if (ev) HIPCHK(h, hipEventRecord(ev[3], st));
+    // the track columns of the observation: from snap_pose, the post-step pose no re-seat overwrites (k_host_block runs behind)
+    if (h->track_on) TRY(track_launch(h, st, kTrackPost, begin, count));
     return F110_OK;
 }
 
@@ -2623,6 +2688,7 @@ int f110_step_device(f110_sim *h, const double *d_actions)
     if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
     if (!h->beams_uniform) return fail(h, F110_ERR_STATE, kBeamsMsg);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    if (h->track_on) TRY(track_prepare(h));
     const int N = h->N, A = h->cfg.num_agents;
     h->dev.path_stats = h->path_stats_on ? h->d_path_stats : nullptr;
     if (h->comm_overlap && h->comm_swap_next) {
@@ -3619,3 +3685,276 @@ int f110_helper_batch(f110_sim *h, int32_t op, const double *in, int32_t m, int3
 }
 
 }  // extern "C"
+
+// ---- track progress (f110_track_*) ---------------------------------------------------------------------------------------------
+static int track_alloc(f110_sim *h)
+{
+    if (h->d_trk) return F110_OK;
+    const size_t N = (size_t)h->N;
+    TRY(dmalloc(h, &h->d_trk, 4 * N));
+    TRY(dmalloc(h, &h->d_trk_seg, N));
+    TRY(dmalloc(h, &h->d_trk_cache, 3 * N));
+    TRY(dmalloc(h, &h->d_trk_ok, N));
+    HIPCHK(h, hipMemsetAsync(h->d_trk, 0, 4 * N * sizeof(double), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_trk_seg, 0, N * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_trk_ok, 0, N * sizeof(int32_t), h->stream));
+    return F110_OK;
+}
+
+// the cached s no longer belongs to the slots / tracks: every agent is re-projected at the head of its next step
+static int track_invalidate(f110_sim *h)
+{
+    h->track_checked = false;
+    if (h->d_trk_ok) HIPCHK(h, hipMemsetAsync(h->d_trk_ok, 0, (size_t)h->N * sizeof(int32_t), h->stream));
+    return F110_OK;
+}
+
+// the kernels' slot table, one entry per registered map slot (slots without a track: nseg = 0)
+static int track_upload(f110_sim *h)
+{
+    const int slots = 1 + (int)h->extra_maps.size();
+    if (!h->tracks_dirty && h->n_tracks_dev == slots) return F110_OK;
+    std::vector<TrackDesc> desc((size_t)slots);
+    h->track_lds = false;
+    for (int m = 0; m < slots; ++m) {
+        desc[m] = TrackDesc{nullptr, 0, 0, 0.0};
+        if (m < (int)h->tracks.size() && h->tracks[m].nseg > 0) {
+            const f110_sim::TrackSlot &ts = h->tracks[m];
+            desc[m] = TrackDesc{ts.d_cols, ts.nseg, ts.closed, ts.L};
+            h->track_lds = h->track_lds || ts.nseg <= kTrackLdsSegs;
+        }
+    }
+    if (h->n_tracks_dev != slots) {
+        if (h->d_tracks) HIPCHK(h, hipFree(h->d_tracks));
+        h->d_tracks = nullptr;
+        TRY(dmalloc(h, &h->d_tracks, (size_t)slots));
+        h->n_tracks_dev = slots;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_tracks, desc.data(), sizeof(TrackDesc) * slots, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (desc is a local; rare: only after a change)
+    h->tracks_dirty = false;
+    return F110_OK;
+}
+
+static bool track_has(const f110_sim *h, int slot) { return slot >= 0 && slot < (int)h->tracks.size() && h->tracks[slot].nseg > 0; }
+
+static int track_check(f110_sim *h)
+{
+    if (h->track_checked) return F110_OK;
+    if (!h->multi_map) {
+        if (!track_has(h, 0)) return fail(h, F110_ERR_STATE, "track progress: map slot 0 has no track (f110_track_set)");
+    } else {
+        for (size_t e = 0; e < h->env_map_host.size(); ++e)
+            if (!track_has(h, h->env_map_host[e]))
+                return fail(h, F110_ERR_STATE, "track progress: env %d is on map slot %d, which has no track (f110_track_set)", (int)e, h->env_map_host[e]);
+    }
+    h->track_checked = true;
+    return F110_OK;
+}
+
+// f110_step_device, tracking on: the slot table is current and every env's slot has a track
+static int track_prepare(f110_sim *h)
+{
+    TRY(track_check(h));
+    if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size()) {
+        TRY(join_groups(h));
+        h->main_dirty = true;
+        TRY(track_upload(h));
+    }
+    return F110_OK;
+}
+
+// one projection pass of the step over agents [begin, begin + count) on stream st
+static int track_launch(f110_sim *h, hipStream_t st, int mode, int begin, int count)
+{
+    if (count <= 0) return F110_OK;
+    const size_t N = (size_t)h->N;
+    TrackJob j{};
+    j.tracks = h->d_tracks;
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.A = h->cfg.num_agents;
+    j.begin = begin;
+    j.count = count;
+    j.stride = 1;
+    if (mode == kTrackHead) {
+        j.px = h->dev.state;        // x, y of the live state (what the last writer left)
+        j.py = h->dev.state + N;
+        j.pth = h->dev.state + 4 * N;
+    } else {
+        j.px = h->dev.snap_pose;    // the post-step pose of the observation
+        j.py = h->dev.snap_pose + N;
+        j.pth = h->dev.snap_pose + 2 * N;
+    }
+    j.s = h->d_trk;
+    j.ds = h->d_trk + N;
+    j.lat = h->d_trk + 2 * N;
+    j.head = h->d_trk + 3 * N;
+    j.seg = h->d_trk_seg;
+    j.c_s = h->d_trk_cache;
+    j.c_x = h->d_trk_cache + N;
+    j.c_y = h->d_trk_cache + 2 * N;
+    j.c_ok = h->d_trk_ok;
+    j.hint = h->d_trk_seg;   // (the head pass reads it before the post pass of the same block rewrites it: stream order)
+    const dim3 grid = grid1d((size_t)count * kTrackLanes, 256);
+    if (mode == kTrackHead) {
+        if (h->track_lds) hipLaunchKernelGGL((k_track_project<kTrackHead, true>), grid, dim3(256), 0, st, j);
+        else hipLaunchKernelGGL((k_track_project<kTrackHead, false>), grid, dim3(256), 0, st, j);
+    } else {
+        if (h->track_lds) hipLaunchKernelGGL((k_track_project<kTrackPost, true>), grid, dim3(256), 0, st, j);
+        else hipLaunchKernelGGL((k_track_project<kTrackPost, false>), grid, dim3(256), 0, st, j);
+    }
+    HIPCHK(h, hipGetLastError());
+    return F110_OK;
+}
+
+int f110_track_set(f110_sim *h, int32_t slot, const double *h_xy, int32_t M, int32_t closed)
+{
+    if (!h || !h_xy) return fail(h, F110_ERR_INVALID, "f110_track_set: null argument");
+    ENTER(h);
+    const int slots = 1 + (int)h->extra_maps.size();
+    if (slot < 0 || slot >= slots) return fail(h, F110_ERR_INVALID, "f110_track_set: slot %d, but %d map slots are registered", slot, slots);
+    if (M < 2 || M > (1 << 24)) return fail(h, F110_ERR_INVALID, "f110_track_set: a track needs 2 .. 2^24 points, got %d", M);
+    int m = M;
+    if (closed && std::memcmp(h_xy, h_xy + 2 * (size_t)(M - 1), 2 * sizeof(double)) == 0) m -= 1;   // a closed csv repeats its first point
+    if (closed && m < 3) return fail(h, F110_ERR_INVALID, "f110_track_set: a closed track needs 3 distinct points, got %d", m);
+    for (size_t q = 0; q < 2 * (size_t)m; ++q)
+        if (!std::isfinite(h_xy[q])) return fail(h, F110_ERR_INVALID, "f110_track_set: point %d is not finite", (int)(q / 2));
+    const int nseg = closed ? m : m - 1;
+    std::vector<double> cols(7 * (size_t)nseg);
+    double cum = 0.0;
+    for (int k = 0; k < nseg; ++k) {
+        const int k1 = k + 1 == m ? 0 : k + 1;
+        const double ax = h_xy[2 * k], ay = h_xy[2 * k + 1];
+        const double dx = h_xy[2 * k1] - ax, dy = h_xy[2 * k1 + 1] - ay;
+        const double l2 = dx * dx + dy * dy;
+        if (!(l2 > 0.0)) return fail(h, F110_ERR_INVALID, "f110_track_set: segment %d -> %d has zero length", k, k1);
+        const double len = std::sqrt(l2);
+        cols[k] = ax;
+        cols[(size_t)nseg + k] = ay;
+        cols[2 * (size_t)nseg + k] = dx;
+        cols[3 * (size_t)nseg + k] = dy;
+        cols[4 * (size_t)nseg + k] = l2;
+        cols[5 * (size_t)nseg + k] = len;
+        cols[6 * (size_t)nseg + k] = cum;
+        cum += len;
+    }
+    double *d_cols = nullptr;
+    TRY(dmalloc(h, &d_cols, cols.size()));
+    const hipError_t e = hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+        (void)hipFree(d_cols);
+        return fail(h, F110_ERR_HIP, "f110_track_set: upload failed: %s", hipGetErrorString(e));
+    }
+    if ((int)h->tracks.size() <= slot) h->tracks.resize((size_t)slot + 1);
+    f110_sim::TrackSlot &ts = h->tracks[slot];
+    if (ts.d_cols) HIPCHK(h, hipFree(ts.d_cols));   // (synchronised above: no step reads the old table any more)
+    ts.d_cols = d_cols;
+    ts.nseg = nseg;
+    ts.closed = closed ? 1 : 0;
+    ts.L = cum;
+    h->tracks_dirty = true;
+    TRY(track_alloc(h));
+    return track_invalidate(h);
+}
+
+int f110_track_enable(f110_sim *h, int32_t on)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (on) {
+        TRY(track_alloc(h));
+        h->track_checked = false;
+        TRY(track_check(h));
+        TRY(track_upload(h));
+    }
+    h->track_on = on != 0;
+    return F110_OK;
+}
+
+int f110_track_views(f110_sim *h, struct f110_track_views *out)
+{
+    if (!h || !out) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    TRY(track_alloc(h));
+    const size_t N = (size_t)h->N;
+    out->s = h->d_trk;
+    out->ds = h->d_trk + N;
+    out->lateral = h->d_trk + 2 * N;
+    out->heading_error = h->d_trk + 3 * N;
+    out->segment = h->d_trk_seg;
+    return F110_OK;
+}
+
+int f110_track_get(f110_sim *h, const f110_track_host *out)
+{
+    if (!h || !out) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    TRY(track_alloc(h));
+    const size_t N = (size_t)h->N;
+    TRY(copy_col(h, out->s, h->d_trk, N));
+    TRY(copy_col(h, out->ds, h->d_trk + N, N));
+    TRY(copy_col(h, out->lateral, h->d_trk + 2 * N, N));
+    TRY(copy_col(h, out->heading_error, h->d_trk + 3 * N, N));
+    if (out->segment) HIPCHK(h, hipMemcpyAsync(out->segment, h->d_trk_seg, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+int f110_track_host_block(f110_sim *h, const f110_track_host *pinned)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // a F110_STEP_NO_SYNC step may still be storing into the previous block
+    h->trk_pinned_on = false;
+    h->trk_pinned = f110_track_host{};
+    h->trk_hb = HostBlock{};
+    if (!pinned || !(pinned->s || pinned->ds || pinned->lateral || pinned->heading_error || pinned->segment)) return F110_OK;
+    HostBlock d{};
+    void *p = nullptr;
+    TRY(map_host_ptr(h, pinned->s, &p, "track s"));
+    d.trk_s = static_cast<double *>(p);
+    TRY(map_host_ptr(h, pinned->ds, &p, "track ds"));
+    d.trk_ds = static_cast<double *>(p);
+    TRY(map_host_ptr(h, pinned->lateral, &p, "track lateral"));
+    d.trk_lat = static_cast<double *>(p);
+    TRY(map_host_ptr(h, pinned->heading_error, &p, "track heading_error"));
+    d.trk_head = static_cast<double *>(p);
+    TRY(map_host_ptr(h, pinned->segment, &p, "track segment"));
+    d.trk_seg = static_cast<int32_t *>(p);
+    TRY(track_alloc(h));
+    h->trk_hb = d;
+    h->trk_pinned = *pinned;
+    h->trk_pinned_on = true;
+    return F110_OK;
+}
+
+int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, int32_t m, double *h_out)
+{
+    if (!h || (m > 0 && (!h_poses || !h_out))) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    if (m < 0) return fail(h, F110_ERR_INVALID, "f110_track_project_batch: m = %d", m);
+    if (!track_has(h, slot)) return fail(h, F110_ERR_STATE, "f110_track_project_batch: map slot %d has no track (f110_track_set)", slot);
+    if (m == 0) return F110_OK;
+    TRY(track_upload(h));
+    Scratch sc(h);
+    double *dp = nullptr, *dout = nullptr;
+    TRY(sc.up(h_poses, 3 * (size_t)m, &dp));
+    TRY(sc.up<double>(nullptr, 5 * (size_t)m, &dout));
+    TrackJob j{};
+    j.tracks = h->d_tracks;
+    j.A = 1;
+    j.count = m;
+    j.unit_slot = slot;
+    j.px = dp;
+    j.py = dp + 1;
+    j.pth = dp + 2;
+    j.stride = 3;
+    j.unit_out = dout;
+    const dim3 grid = grid1d((size_t)m * kTrackLanes, 256);
+    if (h->tracks[slot].nseg <= kTrackLdsSegs) hipLaunchKernelGGL((k_track_project<kTrackUnit, true>), grid, dim3(256), 0, h->stream, j);
+    else hipLaunchKernelGGL((k_track_project<kTrackUnit, false>), grid, dim3(256), 0, h->stream, j);
+    HIPCHK(h, hipGetLastError());
+    TRY(sc.down(h_out, dout, 5 * (size_t)m));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}

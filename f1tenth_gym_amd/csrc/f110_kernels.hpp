@@ -136,6 +136,12 @@ struct HostBlock {
     // runtime, a kernel's stores ~2); nullptr: the caller copies them (big batches: one DMA copy at link rate)
     double *scans;                  // [N][num_beams] page-locked, or nullptr
     int32_t num_beams, pad_beams;
+    // f110_track_host_block: the step's track columns (device [4][N] s, ds, lateral, heading_error + [N] segment, written by
+    // k_track_project before this kernel runs) into page-locked memory; trk_src nullptr = none
+    const double *trk_src;
+    const int32_t *trk_seg_src;
+    double *trk_s, *trk_ds, *trk_lat, *trk_head;
+    int32_t *trk_seg;
 };
 
 // rows [first, first + count) of the device scans into the host block, by every thread of the workgroup
@@ -2343,6 +2349,13 @@ __device__ __forceinline__ void host_block_body(const AgentArrays &a, const Epis
 #pragma unroll
             for (int c = 0; c < 3; ++c) hb.agent_poses[c * N + i] = a.snap_pose[c * N + i];
         }
+        if (hb.trk_src) {
+            if (hb.trk_s) hb.trk_s[i] = hb.trk_src[i];
+            if (hb.trk_ds) hb.trk_ds[i] = hb.trk_src[N + i];
+            if (hb.trk_lat) hb.trk_lat[i] = hb.trk_src[2 * N + i];
+            if (hb.trk_head) hb.trk_head[i] = hb.trk_src[3 * N + i];
+            if (hb.trk_seg) hb.trk_seg[i] = hb.trk_seg_src[i];
+        }
         if (episode) {
             const int e = e0 + le;
             const double ct = ep.current_time[e] + ep.timestep;  // f110_env.py:295 (written back in phase 2)
@@ -3236,6 +3249,187 @@ __global__ void k_interleave_cs(const double *__restrict__ sines, const double *
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) cs[i] = make_double2(cosines[i], sines[i]);
+}
+
+// ---- track progress (f110_track_*): per-agent projection on the raceline of the env's map slot ------------------------------
+// A track is a polyline of nseg segments, stored per slot as seven SoA columns [7][nseg]: ax, ay, dx, dy, l2 = dx²+dy², len =
+// sqrt(l2), cum (float64 running sum of len, built on the host).  The search is nearest_on_trajectory's (f110_math.hpp) with
+// k_pure_pursuit's split: the 16 lanes of a group take every 16th segment, keep their first minimum, and a lexicographic
+// (dist, index) min across the group picks np.argmin's winner.
+// Pruning: the group first measures the segment that won this agent's last projection (any segment's distance is an upper bound
+// of the minimum), and a lane skips segment k when |p - mid_k| - len_k / 2 — a lower bound of its true distance — exceeds the
+// smaller of that bound and the lane's running minimum by more than kTrackPruneMargin (1 um, far above the float64 rounding of
+// either side at any map size).  A skipped segment's computed distance is then strictly larger than the minimum: it can neither
+// win nor tie, so the winner is the full first-minimum search's, bit for bit.
+struct TrackDesc {
+    const double *cols;   // [7][nseg] or nullptr (the slot has no track)
+    int32_t nseg, closed;
+    double L;             // total length (the closing segment included when closed)
+};
+enum TrackCol { kTrkAx = 0, kTrkAy, kTrkDx, kTrkDy, kTrkL2, kTrkLen, kTrkCum };
+
+// what one projection pass reads and writes.  Step forms: agents [begin, begin + count), slot = env_map[i / A] (slot 0 when
+// env_map is nullptr).  Unit form: poses [count][3], the track `unit_slot`, out [count][5].
+struct TrackJob {
+    const TrackDesc *tracks;
+    const int32_t *env_map;
+    int32_t A, begin, count, unit_slot;
+    const double *px, *py, *pth;   // pose columns, `stride` apart per agent
+    int32_t stride, pad_;
+    double *s, *ds, *lat, *head;   // [N] (post-step form)
+    int32_t *seg;                  // [N]
+    double *c_s, *c_x, *c_y;       // [N] cache: s and the pose it belongs to
+    int32_t *c_ok;                 // [N] the cache entry is valid (cleared by f110_track_set / f110_set_env_maps / state loads)
+    const int32_t *hint;           // [N] segment of the agent's last projection (a pruning seed, any value is safe), or nullptr
+    double *unit_out;              // [count][5]: s, lateral, heading_error, segment, t
+};
+enum TrackMode { kTrackHead = 0, kTrackPost = 1, kTrackUnit = 2 };
+constexpr int kTrackLanes = 16;
+constexpr int kTrackLdsSegs = 1024;   // 48 KB of LDS: ax, ay, dx, dy, l2, len per segment
+constexpr int kTrackLdsCols = 6;
+constexpr double kTrackPruneMargin = 1e-6;
+
+__device__ __forceinline__ uint64_t track_bits(double v) { return (uint64_t)__double_as_longlong(v); }
+
+// wrap(theta - atan2(dy, dx)) into [-pi, pi)
+__device__ __forceinline__ double track_wrap_angle(double e)
+{
+    const double two_pi = 2.0 * M_PI;
+    double w = fmod(e + M_PI, two_pi);
+    if (w < 0.0) w += two_pi;
+    if (w >= two_pi) w -= two_pi;
+    return w - M_PI;
+}
+
+template <int MODE, bool LDS>
+__global__ void __launch_bounds__(256) k_track_project(TrackJob j)
+{
+    __shared__ double s_tab[LDS ? kTrackLdsCols * kTrackLdsSegs : 1];
+    __shared__ int s_slot, s_staged;
+    const int gid = (blockIdx.x * blockDim.x + threadIdx.x) / kTrackLanes;
+    const int sub = threadIdx.x & (kTrackLanes - 1);
+    const bool live = gid < j.count;
+    const int g = live ? gid : j.count - 1;   // idle groups shadow the last agent so the wave stays convergent
+    const int i = MODE == kTrackUnit ? g : j.begin + g;
+    const int slot = MODE == kTrackUnit ? j.unit_slot : (j.env_map ? j.env_map[i / j.A] : 0);
+    const TrackDesc td = j.tracks[slot];
+    const double px = j.px[(size_t)i * j.stride], py = j.py[(size_t)i * j.stride];
+    // the head pass re-projects only agents whose pose changed bitwise since their cached s
+    bool work = live && td.nseg > 0;
+    if (MODE == kTrackHead && work)
+        work = !(j.c_ok[i] && track_bits(j.c_x[i]) == track_bits(px) && track_bits(j.c_y[i]) == track_bits(py));
+    if (LDS) {
+        // stage the track of the workgroup's first agent when it fits (and, in the head pass, when somebody needs it)
+        if (threadIdx.x == 0) s_slot = slot;
+        const int any = __syncthreads_or(work ? 1 : 0);
+        const TrackDesc t0 = j.tracks[s_slot];
+        const bool stage = any && t0.nseg > 0 && t0.nseg <= kTrackLdsSegs;
+        if (stage) {
+            for (int q = threadIdx.x; q < kTrackLdsCols * t0.nseg; q += blockDim.x) {
+                const int c = q / t0.nseg, k = q - c * t0.nseg;
+                s_tab[c * kTrackLdsSegs + k] = t0.cols[(size_t)c * t0.nseg + k];
+            }
+        }
+        if (threadIdx.x == 0) s_staged = stage ? 1 : 0;
+        __syncthreads();
+    }
+    if (!work) {
+        if (MODE == kTrackPost && live && sub == 0) {   // (no track on this slot: f110_step refuses it, so this is never read)
+            j.s[i] = j.ds[i] = j.lat[i] = j.head[i] = NAN;
+            j.seg[i] = -1;
+        }
+        return;
+    }
+    const bool from_lds = LDS && s_staged && slot == s_slot;
+    const double *src = td.cols;
+    size_t cs = (size_t)td.nseg;
+    if (LDS && from_lds) {
+        src = s_tab;
+        cs = kTrackLdsSegs;
+    }
+    // ---- nearest_point_on_trajectory (examples/waypoint_follow.py:15-50), f110_math.hpp's arithmetic
+    double dist = INFINITY, tb = 0.0, seed = INFINITY;
+    int best = 0x7fffffff;
+    if (j.hint) {   // the last winner's distance: an upper bound of the minimum (NaN for a NaN pose: then nothing is skipped)
+        int k = j.hint[i];
+        k = k < 0 ? 0 : (k >= td.nseg ? td.nseg - 1 : k);
+        const double ax = src[k], ay = src[cs + k], dx = src[2 * cs + k], dy = src[3 * cs + k], l2 = src[4 * cs + k];
+        double t = ((px - ax) * dx + (py - ay) * dy) / l2;
+        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+        const double rx = px - (ax + t * dx), ry = py - (ay + t * dy);
+        seed = sqrt(rx * rx + ry * ry);
+    }
+    for (int k = sub; k < td.nseg; k += kTrackLanes) {
+        const double ax = src[k], ay = src[cs + k], dx = src[2 * cs + k], dy = src[3 * cs + k];
+        const double mx = px - (ax + 0.5 * dx), my = py - (ay + 0.5 * dy);
+        const double reach = (seed < dist ? seed : dist) + 0.5 * src[5 * cs + k] + kTrackPruneMargin;
+        if (mx * mx + my * my > reach * reach) continue;
+        const double l2 = src[4 * cs + k];
+        double t = ((px - ax) * dx + (py - ay) * dy) / l2;
+        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+        const double rx = px - (ax + t * dx), ry = py - (ay + t * dy);
+        const double d = sqrt(rx * rx + ry * ry);
+        if (d < dist) {
+            dist = d;
+            tb = t;
+            best = k;
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < kTrackLanes; m <<= 1) {
+        const double od = __shfl_xor(dist, m, kTrackLanes), ot = __shfl_xor(tb, m, kTrackLanes);
+        const int ob = __shfl_xor(best, m, kTrackLanes);
+        if (od < dist || (od == dist && ob < best)) {
+            dist = od;
+            tb = ot;
+            best = ob;
+        }
+    }
+    if (best == 0x7fffffff) {   // every distance NaN: np.argmin -> 0, t = 0 (as the serial loop leaves them)
+        best = 0;
+        tb = 0.0;
+    }
+    if (sub != 0) return;
+    const size_t n = (size_t)td.nseg;
+    const double *c = td.cols;
+    const double ax = c[best], ay = c[n + best], dx = c[2 * n + best], dy = c[3 * n + best];
+    const double s = c[6 * n + best] + tb * c[5 * n + best];
+    if (MODE == kTrackHead) {
+        j.c_s[i] = s;
+        j.c_x[i] = px;
+        j.c_y[i] = py;
+        j.c_ok[i] = 1;
+        return;
+    }
+    const double rx = px - (ax + tb * dx), ry = py - (ay + tb * dy);
+    const double cross = dx * ry - dy * rx;
+    const double lat = cross < 0.0 ? -dist : dist;
+    const double theta = j.pth[(size_t)i * j.stride];
+    const double herr = track_wrap_angle(theta - atan2(dy, dx));
+    if (MODE == kTrackUnit) {
+        double *o = j.unit_out + 5 * (size_t)i;
+        o[0] = s;
+        o[1] = lat;
+        o[2] = herr;
+        o[3] = (double)best;
+        o[4] = tb;
+        return;
+    }
+    double d = s - j.c_s[i];   // the head pass left the cache valid for the pose this step started from
+    if (td.closed) {
+        const double half = 0.5 * td.L;
+        if (d > half) d -= td.L;
+        else if (d <= -half) d += td.L;
+    }
+    j.s[i] = s;
+    j.ds[i] = d;
+    j.lat[i] = lat;
+    j.head[i] = herr;
+    j.seg[i] = best;
+    j.c_s[i] = s;
+    j.c_x[i] = px;
+    j.c_y[i] = py;
+    j.c_ok[i] = 1;
 }
 
 

@@ -16,6 +16,7 @@ import numpy as np
 from . import _ffi
 from .core import DEFAULT_PARAMS
 from .sim import Integrator, Simulator
+from .track import Track
 
 try:  # pragma: no cover - gym is absent from the build image
     import gym as _gym
@@ -129,6 +130,16 @@ class _LapLogic(object):
         return done, self.toggle_list >= 4
 
 
+def _reward_mode(reward):
+    if reward not in ('timestep', 'progress'):
+        raise ValueError("reward must be 'timestep' (the reference's) or 'progress' (the ego's progress along the track)")
+    return reward
+
+
+# the track columns' observation keys -> their names in BatchSim.track_views / track_host_block
+_TRACK_OBS = {key: src for src, key in Simulator.TRACK_KEYS}
+
+
 class F110Env(_EnvBase):
     metadata = {'render.modes': ['human', 'human_fast']}
     render_callbacks = []
@@ -154,6 +165,15 @@ class F110Env(_EnvBase):
                              device_id=kwargs.get('device_id', 0),
                              map_layout=kwargs.get('map_layout', _ffi.MAP_DEFAULT))
         self.sim.set_map(self.map_path, self.map_ext)
+        # track progress (no reference counterpart): track= adds the obs keys of Simulator.TRACK_KEYS; reward='progress' pays the
+        # ego's progress of the step (metres along the track) instead of the reference's constant timestep
+        self.reward_mode = _reward_mode(kwargs.get('reward', 'timestep'))
+        self.track = None
+        if kwargs.get('track') is not None:
+            self.track = self.sim.set_track(Track.coerce(kwargs['track']))
+            self.sim.enable_track()
+        elif self.reward_mode == 'progress':
+            raise ValueError("reward='progress' needs a track (track=...)")
         self.render_obs = None
         self.current_obs = None
 
@@ -173,7 +193,7 @@ class F110Env(_EnvBase):
         obs['lap_counts'] = self._lap.lap_counts[0]
         self.current_obs = obs
         self.render_obs = {k: obs[k] for k in ('ego_idx', 'poses_x', 'poses_y', 'poses_theta', 'lap_times', 'lap_counts')}
-        reward = self.timestep
+        reward = self.timestep if self.reward_mode == 'timestep' else float(obs['progress_delta'][self.ego_idx])
         self.poses_x, self.poses_y, self.poses_theta = obs['poses_x'], obs['poses_y'], obs['poses_theta']
         self.collisions = obs['collisions']
         done, toggles = self._lap.update_single(obs['poses_x'], obs['poses_y'], obs['collisions'], self.timestep)
@@ -248,10 +268,16 @@ class F110VecEnv(object):
     Domain randomisation over tracks: `extra_maps=[(yaml_path, ext), ...]` registers further maps
     (slots 1, 2, ...; `map` is slot 0) and `env_map=[slot per env]` assigns them; `set_env_maps()`
     re-assigns later.
+
+    Track progress (no reference counterpart): `track=` (a Track, an [M][2] array or a csv path) puts a raceline on
+    slot 0, `tracks={slot: track}` one per map slot.  The observation then also carries progress, progress_delta,
+    lateral_offset, heading_error and track_segment ([E][A] each; obs_fields selects among them too — by default all of them), and
+    reward='progress' makes the reward the ego's progress_delta, [E].
     """
 
     # every key of the reference's observation (base_classes.py:594-610, docs/api/obv.rst:6-14)
     _ALL = ("scans", "poses_x", "poses_y", "poses_theta", "linear_vels_x", "linear_vels_y", "ang_vels_z", "collisions")
+    _TRACK = tuple(key for _, key in Simulator.TRACK_KEYS)
 
     # what the device episode logic can bring back next to `done` (info keys + the two lap arrays of obs)
     _EPISODE = ("lap_times", "lap_counts", "toggle_list", "near_starts", "checkpoint_done")
@@ -268,7 +294,15 @@ class F110VecEnv(object):
         self.ego_idx = kwargs.get('ego_idx', 0)
         self.auto_reset = auto_reset
         self.device_logic = bool(device_logic)
-        self.obs_fields = tuple(self._ALL if obs_fields is None else obs_fields)
+        tracks = dict(kwargs.get('tracks') or {})
+        if kwargs.get('track') is not None:
+            tracks[0] = kwargs['track']
+        self.reward_mode = _reward_mode(kwargs.get('reward', 'timestep'))
+        if self.reward_mode == 'progress' and not tracks:
+            raise ValueError("reward='progress' needs a track (track= or tracks=)")
+        self.obs_fields = tuple((self._ALL + (self._TRACK if tracks else ())) if obs_fields is None else obs_fields)
+        if not tracks and any(f in self._TRACK for f in self.obs_fields):
+            raise ValueError("the track fields of obs_fields need a track (track= or tracks=)")
         self._lap = _LapLogic(self.num_envs, self.num_agents, self.ego_idx)
         self.sim = Simulator(self.params, self.num_agents, self.seed, time_step=self.timestep,
                              integrator=kwargs.get('integrator', Integrator.RK4),   # (no ego_idx: see obs['ego_idx'] below)
@@ -286,6 +320,9 @@ class F110VecEnv(object):
             self.map_slots.append((path, ext))
         if kwargs.get('env_map') is not None:
             self.set_env_maps(kwargs['env_map'])
+        self.tracks = {int(slot): self.sim.set_track(Track.coerce(t), int(slot)) for slot, t in sorted(tracks.items())}
+        if self.tracks:
+            self.sim.enable_track()
         self._start_poses = None
         self._d_actions = None
         self.copy_obs = bool(copy_obs)
@@ -326,6 +363,8 @@ class F110VecEnv(object):
                 obs[f] = np.zeros((E, A))      # base_classes.py:603: always 0. in the reference
             elif f == "scans":
                 obs[f] = v["scans"].reshape(E, A, -1)
+            elif f in _TRACK_OBS:
+                continue                       # (the track block, below)
             else:
                 obs[f] = v[f].reshape(E, A)
         info = {}
@@ -334,7 +373,15 @@ class F110VecEnv(object):
             if f in ("near_starts", "checkpoint_done"):
                 arr = arr.view(np.bool_)
             (obs if f in ("lap_times", "lap_counts") else info)[f] = arr
-        self._ret_views = (obs, self.timestep, v["done"].view(np.bool_), info)
+        reward = self.timestep
+        if self.tracks:   # the track columns: page-locked views step_host fills next to the block
+            tv = b.track_host_block()
+            for f in self.obs_fields:
+                if f in _TRACK_OBS:
+                    obs[f] = tv[_TRACK_OBS[f]].reshape(E, A)
+            if self.reward_mode == 'progress':
+                reward = tv["ds"].reshape(E, A)[:, self.ego_idx]
+        self._ret_views = (obs, reward, v["done"].view(np.bool_), info)
 
     def update_params_batch(self, params):
         """a vehicle parameter set per agent of every env ([E*A] dicts or [E*A][18] array; None: back
@@ -388,6 +435,8 @@ class F110VecEnv(object):
                     if isinstance(v, np.ndarray):
                         np.copyto(v, saved[k])
             np.copyto(done, last[2])
+            if isinstance(r, np.ndarray):
+                np.copyto(r, last[1])
             last = self._ret_views
         self._last = last
         return last
@@ -409,6 +458,7 @@ class F110VecEnv(object):
         if self.copy_obs:
             obs = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in obs.items()}
             done, info = done.copy(), {k: v.copy() for k, v in info.items()}
+            r = r.copy() if isinstance(r, np.ndarray) else r
         self._last = (obs, r, done, info)
         return self._last
 
@@ -429,6 +479,10 @@ class F110VecEnv(object):
         if actions is None:
             raise ValueError("step(None) (actions taken from env.action_buffer) needs device_logic=True")
         obs = self.sim.step(actions)
+        for f in self._TRACK:
+            if f in obs and f not in self.obs_fields:
+                del obs[f]
+        reward = self.timestep if self.reward_mode == 'timestep' else self.sim.batch.get_track()["ds"].reshape(self.num_envs, self.num_agents)[:, self.ego_idx]
         done, toggles = self._lap.update(obs['poses_x'], obs['poses_y'], obs['collisions'], self.timestep)
         obs['lap_times'] = self._lap.lap_times
         obs['lap_counts'] = self._lap.lap_counts
@@ -437,5 +491,5 @@ class F110VecEnv(object):
         if self.auto_reset and done.any():
             self.sim.reset(self._start_poses, done)
             self._lap.reset(self._start_poses, done)
-        self._last = (obs, self.timestep, done, info)
+        self._last = (obs, reward, done, info)
         return self._last

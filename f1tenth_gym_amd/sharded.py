@@ -16,7 +16,8 @@ A device id may appear more than once in `devices` (several handles on one GPU â
 The optional observation gather (`gather_obs=True`, BASELINE configs[3]) leaves EVERY shard's scans + 7 scalars per
 agent on EVERY device after each step â€” one RCCL communicator over the handles, `f110_comm_all_gather_obs` on each
 shard's stream (float32 transport / gather to one root: `gather_f32=True`, `gather_root=k`); `gathered_views()`
-hands out the per-device receive buffers ([shards][N_k][B] and [shards][7][N_k]).  It needs equal shards.
+hands out the per-device receive buffers ([shards][N_k][B] and [shards][7][N_k]).  It needs equal shards.  The gather does not carry the
+track columns (track= / tracks= of F110VecEnv): they come back through each shard's observation as usual.
 
 For a device-resident RL loop use `shards[k].device_views()` (actions and observations never leave the GPU that owns
 them); the array-returning step() here is the host-driven form, like F110VecEnv's.
@@ -130,14 +131,16 @@ class ShardedVecEnv(object):
         if self._out is None:
             def alloc(v):
                 return np.empty((self.num_envs,) + v.shape[1:], dtype=v.dtype)
-            o0, _, d0, i0 = parts[0]
+            o0, r0, d0, i0 = parts[0]
             self._out = ({k: (alloc(v) if isinstance(v, np.ndarray) else v) for k, v in o0.items()}, alloc(np.asarray(d0)),
-                         {k: alloc(v) for k, v in i0.items()})
-        obs, done, info = self._out
+                         {k: alloc(v) for k, v in i0.items()}, alloc(r0) if isinstance(r0, np.ndarray) else None)
+        obs, done, info, reward = self._out
 
         def fill(k, _shard=None):
-            o, _, d, i = parts[k]
+            o, r, d, i = parts[k]
             lo, hi = self.bounds[k], self.bounds[k + 1]
+            if reward is not None:   # reward='progress': [E] per shard
+                reward[lo:hi] = r
             for name, v in o.items():
                 if isinstance(v, np.ndarray):
                     obs[name][lo:hi] = v
@@ -152,7 +155,7 @@ class ShardedVecEnv(object):
         else:
             for k in range(len(parts)):
                 fill(k)
-        return obs, self.timestep, done, info
+        return obs, (self.timestep if reward is None else reward), done, info
 
     # ------------------------------------------------------------------ the env API (F110VecEnv's, over all shards)
     def reset(self, poses, env_mask=None):

@@ -119,6 +119,21 @@ class Simulator(object):
                 self._noise = ScanNoise(seed, num_beams, scan_noise_std)
         self._steps_since_full_reset = 0
         self._hb = None
+        self._track_on = False
+        self._thb = None
+
+    # track progress (BatchSim.set_track / enable_track): the observation gains the keys below, [num_agents] each
+    TRACK_KEYS = (("s", "progress"), ("ds", "progress_delta"), ("lateral", "lateral_offset"), ("heading_error", "heading_error"),
+                  ("segment", "track_segment"))
+
+    def set_track(self, track, slot=0):
+        """attach a raceline (a Track, an [M][2] array or a csv path) to map slot `slot`; returns the Track"""
+        return self._b.set_track(track, slot)
+
+    def enable_track(self, on=True):
+        """with on, every observation carries progress, progress_delta, lateral_offset, heading_error and track_segment"""
+        self._b.enable_track(on)
+        self._track_on = bool(on)
 
     @property
     def batch(self):
@@ -195,8 +210,11 @@ class Simulator(object):
             if hb is None:
                 hb = self._hb = self._b.host_block(("scans", "state", "agent_poses", "collisions", "collision_idx", "in_collision"))
             hb.actions[...] = actions
+            if self._track_on and self._thb is None:
+                self._thb = self._b.track_host_block()
             self._b.step_host_inplace(hb)
             v = hb.views
+            trk = {k: a.copy() for k, a in self._thb.items()} if self._track_on else None
             scans, s7 = v["scans"].copy(), v["state"].copy()      # s7: [7][N], the block's own layout
             poses, coll, cidx, inc = v["agent_poses"].T.copy(), v["collisions"].copy(), v["collision_idx"].copy(), v["in_collision"].copy()
         else:
@@ -205,6 +223,7 @@ class Simulator(object):
             self._b.step(actions)
             o = self._b.get("scans", "state", "agent_poses", "collisions", "collision_idx", "in_collision")
             scans, s7, poses, coll, cidx, inc = o["scans"], o["state"].T, o["agent_poses"], o["collisions"], o["collision_idx"], o["in_collision"]
+            trk = self._b.get_track() if self._track_on else None
         self._steps_since_full_reset += 1
         self._state = s7.T            # [N][7]
         self._in_collision = inc
@@ -242,4 +261,7 @@ class Simulator(object):
                             'poses_x': st[:, :, 0], 'poses_y': st[:, :, 1], 'poses_theta': st[:, :, 4],
                             'linear_vels_x': st[:, :, 3], 'linear_vels_y': np.zeros((E, A)),
                             'ang_vels_z': st[:, :, 5], 'collisions': self.collisions}
+        if trk is not None:
+            for src, key in self.TRACK_KEYS:
+                observations[key] = trk[src].reshape(E, A) if self._batched else trk[src]
         return observations

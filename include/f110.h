@@ -544,6 +544,44 @@ int f110_scan_lookup_count(f110_sim *h, int32_t enable, int64_t *out2);
 /* table index int(theta_index) of every beam for M headings (get_scan :167-184) */
 int f110_beam_dir_index_batch(f110_sim *h, const double *h_thetas, int32_t m, int32_t *h_idx);
 
+/* ---- track progress (no reference counterpart: what racing RL setups built on the reference compute on the host) ----
+ * A track is a polyline of M points (x, y) in map coordinates, attached to a map slot (0 = f110_set_map_*, 1.. = f110_add_map_*).
+ * closed != 0 adds the segment M-1 -> 0; a closed track whose last point equals its first bitwise drops that repeat first.
+ * Refused (F110_ERR_INVALID): M < 2 (M < 3 closed), non-finite points, a zero-length segment (the closing one included).
+ * Projection = examples/waypoint_follow.py:15-50 nearest_point_on_trajectory (first segment with the smallest distance, t clipped
+ * to [0, 1]).  Per agent: s = cum[k] + t len[k] (metres along the track), lateral = signed distance to the projection (> 0 left of
+ * the segment direction), heading_error = wrap(theta - atan2(dy, dx)) into [-pi, pi), segment = k, ds = s(after) - s(before) of the
+ * step just taken (closed: wrapped into (-L/2, L/2]).  The columns belong to the observation of the step: computed from the same
+ * post-step pose as poses_x / poses_y / poses_theta, before any in-step re-seat.  "before" is a per-agent cache of s and the pose it
+ * was computed from, used only while that pose equals the current one bitwise (else the agent is re-projected at the head of the
+ * step), so every pose writer (resets, re-seats, f110_set_state, state loads, clones) is covered without knowing about tracks. */
+int f110_track_set(f110_sim *h, int32_t slot, const double *h_xy /* [M][2] */, int32_t M, int32_t closed);
+/* on != 0: every step entry point also produces the track columns.  F110_ERR_STATE (at this call or at the next step) while an
+ * env is assigned to a slot without a track.  Off by default: the step is then exactly what it is without tracks. */
+int f110_track_enable(f110_sim *h, int32_t on);
+struct f110_track_views {   /* (a struct tag, no typedef: the entry point below has the same name) */
+    double *s;              /* [N] device pointers, stable for the life of the handle */
+    double *ds;             /* [N] */
+    double *lateral;        /* [N] */
+    double *heading_error;  /* [N] */
+    int32_t *segment;       /* [N] */
+};
+int f110_track_views(f110_sim *h, struct f110_track_views *out);
+typedef struct f110_track_host {
+    double *s;              /* [N] any pointer may be NULL */
+    double *ds;
+    double *lateral;
+    double *heading_error;
+    int32_t *segment;
+} f110_track_host;
+/* host copy of the last step's columns (synchronous) */
+int f110_track_get(f110_sim *h, const f110_track_host *out);
+/* page-locked destinations (f110_host_alloc) f110_step_host fills alongside its host block, with the block's completion
+ * semantics; NULL (or every pointer NULL) unregisters */
+int f110_track_host_block(f110_sim *h, const f110_track_host *pinned);
+/* unit form: h_poses [m][3] on the track of `slot`; h_out [m][5] = s, lateral, heading_error, segment, t */
+int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, int32_t m, double *h_out);
+
 #ifdef __cplusplus
 }
 #endif
