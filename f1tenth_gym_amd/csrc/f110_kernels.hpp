@@ -3385,13 +3385,18 @@ __global__ void __launch_bounds__(256) k_track_project(TrackJob j)
             best = ob;
         }
     }
-    if (best == 0x7fffffff) {   // every distance NaN: np.argmin -> 0, t = 0 (as the serial loop leaves them)
-        best = 0;
-        tb = 0.0;
-    }
     if (sub != 0) return;
     const size_t n = (size_t)td.nseg;
     const double *c = td.cols;
+    if (best == 0x7fffffff) {   // no distance below +inf (every one NaN for a NaN pose): np.argmin -> 0, with segment 0's own t and
+        best = 0;               // distance, as the reference returns them (its clip passes NaN through)
+        const double dx = c[2 * n], dy = c[3 * n];
+        double t = ((px - c[0]) * dx + (py - c[n]) * dy) / c[4 * n];
+        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+        const double rx = px - (c[0] + t * dx), ry = py - (c[n] + t * dy);
+        tb = t;
+        dist = sqrt(rx * rx + ry * ry);
+    }
     const double ax = c[best], ay = c[n + best], dx = c[2 * n + best], dy = c[3 * n + best];
     const double s = c[6 * n + best] + tb * c[5 * n + best];
     if (MODE == kTrackHead) {

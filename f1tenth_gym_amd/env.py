@@ -399,18 +399,22 @@ class F110VecEnv(object):
             v.update(self.sim.batch.episode_device_views())
         return v
 
-    def reset(self, poses, env_mask=None):
+    def reset(self, poses, env_mask=None, reseat_only=False):
+        """env_mask None: every env, then one zero-action step (f110_env.py:319-334).  A partial mask re-seats the masked envs
+        only and returns the last step's tuple with their done cleared.  reseat_only=True takes that path even when env_mask
+        covers every env (ShardedVecEnv: a shard's slice of a partial global mask may)."""
         poses = np.asarray(poses, dtype=np.float64).reshape(self.num_envs, self.num_agents, 3)
         self._start_poses = poses.copy() if self._start_poses is None or env_mask is None else \
             np.where(np.asarray(env_mask, dtype=bool)[:, None, None], poses, self._start_poses)
+        partial = env_mask is not None and (bool(reseat_only) or not np.all(env_mask))
+        steps = self.sim._steps_since_full_reset
         if self.device_logic:
             self.sim.batch.episode_reset(poses.reshape(-1, 3), env_mask)
-            if env_mask is None or np.all(env_mask):
-                self.sim._steps_since_full_reset = 0
         else:
             self.sim.reset(poses, env_mask)
             self._lap.reset(poses, env_mask)
-        if env_mask is not None and not np.all(env_mask) and self._last is not None:
+        self.sim._steps_since_full_reset = steps if partial else 0
+        if partial and self._last is not None:
             # partial reset: re-seat only (class docstring); envs in mid-episode are not stepped
             obs, reward, done, info = self._last
             done = np.where(np.asarray(env_mask, dtype=bool), False, done)

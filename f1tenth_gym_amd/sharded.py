@@ -162,7 +162,9 @@ class ShardedVecEnv(object):
         poses = np.asarray(poses, dtype=np.float64).reshape(self.num_envs, self.num_agents, 3)
         ps = self._slices(poses)
         ms = [None] * len(self.shards) if env_mask is None else self._slices(np.asarray(env_mask, dtype=bool))
-        parts = self._each(lambda k, s: s.reset(ps[k], ms[k]))
+        # "partial" is decided once, from the global mask: a shard whose slice is all True re-seats too, as one handle would
+        partial = env_mask is not None and not np.all(env_mask)
+        parts = self._each(lambda k, s: s.reset(ps[k], ms[k], reseat_only=partial))
         self._after_step()
         return self._assemble(parts)
 

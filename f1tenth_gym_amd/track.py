@@ -98,9 +98,7 @@ class Track(object):
             ry = py - (a[:, 1] + t * d[:, 1])
             dist = np.sqrt(rx * rx + ry * ry)
             k = int(np.argmin(dist))
-            tk = float(t[k])
-            if np.isnan(dist[k]):
-                tk = 0.0
+            tk = float(t[k])      # (a NaN pose: segment 0 with t and distance NaN, as the reference's np.clip leaves them)
             cross = d[k, 0] * ry[k] - d[k, 1] * rx[k]
             herr = np.mod(th - np.arctan2(d[k, 1], d[k, 0]) + np.pi, 2 * np.pi) - np.pi
             out[r] = (self.cum[k] + tk * self.seg_len[k], -dist[k] if cross < 0 else dist[k], herr, k, tk)

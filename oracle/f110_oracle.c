@@ -961,7 +961,7 @@ int64_t orc_sim_lookups(orc_sim *s) { return s->lookups; }
 int orc_nearest_on_trajectory(const double *wp, int M, double px, double py, double *dist,
                               double *t_out)
 {
-    int best = 0;
+    int best = 0, picked = 0;
     double best_d = INFINITY, best_t = 0.0;
     for (int k = 0; k + 1 < M; ++k) {
         const double ax = wp[3 * k], ay = wp[3 * k + 1];
@@ -978,7 +978,17 @@ int orc_nearest_on_trajectory(const double *wp, int M, double px, double py, dou
             best_d = d;
             best_t = t;
             best = k;
+            picked = 1;
         }
+    }
+    if (!picked && M > 1) {   /* no distance below +inf (a NaN pose): np.argmin -> 0, and segment 0's own t and distance */
+        const double ax = wp[0], ay = wp[1], dx = wp[3] - ax, dy = wp[4] - ay;
+        double t = ((px - ax) * dx + (py - ay) * dy) / (dx * dx + dy * dy);
+        if (t < 0.0) t = 0.0;
+        if (t > 1.0) t = 1.0;
+        const double ex = px - (ax + t * dx), ey = py - (ay + t * dy);
+        best_t = t;
+        best_d = sqrt(ex * ex + ey * ey);
     }
     *dist = best_d;
     *t_out = best_t;

@@ -99,3 +99,50 @@ def write_variant_yaml(tmp_dir, name, resolution, origin):
         f.write("image: %s.png\nresolution: %r\norigin: [%r, %r, %r]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n"
                 % (os.path.basename(stem), float(resolution), float(origin[0]), float(origin[1]), float(origin[2])))
     return stem + ".yaml"
+
+
+def track_oracle(track, poses):
+    """[m][5] = s, lateral, heading_error, segment, t of poses [m][3] on a Track, from the oracle's nearest_on_trajectory (C, the
+    reference's arithmetic: first minimum, t clipped to [0, 1])"""
+    from oracle import orc
+    pts = track.points_closed()
+    wp = np.column_stack([pts, np.zeros(len(pts))])
+    out = np.empty((len(poses), 5))
+    for r, (px, py, th) in enumerate(np.asarray(poses, dtype=np.float64).reshape(-1, 3)):
+        i, dist, t = orc.nearest_on_trajectory(wp, px, py)
+        dx, dy = pts[i + 1, 0] - pts[i, 0], pts[i + 1, 1] - pts[i, 1]
+        rx, ry = px - (pts[i, 0] + t * dx), py - (pts[i, 1] + t * dy)
+        herr = np.mod(th - np.arctan2(dy, dx) + np.pi, 2 * np.pi) - np.pi
+        out[r] = (track.cum[i] + t * track.seg_len[i], -dist if dx * ry - dy * rx < 0 else dist, herr, i, t)
+    return out
+
+
+def track_distances_ld(track, poses):
+    """[m][nseg] exact-ish point-to-segment distances in np.longdouble, computed independently of the float64 arithmetic the kernel
+    and the oracle share (the closest point by projection, clipped, then the distance — all in extended precision)"""
+    pts = track.points_closed().astype(np.longdouble)
+    a, d = pts[:-1], pts[1:] - pts[:-1]
+    l2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+    p = np.asarray(poses, dtype=np.float64).reshape(-1, 3)[:, :2].astype(np.longdouble)
+    rx0 = p[:, None, 0] - a[None, :, 0]
+    ry0 = p[:, None, 1] - a[None, :, 1]
+    t = np.clip((rx0 * d[None, :, 0] + ry0 * d[None, :, 1]) / l2[None, :], 0, 1)
+    rx, ry = rx0 - t * d[None, :, 0], ry0 - t * d[None, :, 1]
+    return np.sqrt(rx * rx + ry * ry)
+
+
+def check_track_winner(track, poses, segment, tol=1e-9):
+    """the segment chosen for each pose lies within tol metres of the true minimum distance over all segments (extended precision);
+    -> None, or a message naming the first pose that fails"""
+    p = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    seg = np.asarray(segment).astype(np.int64)
+    for lo in range(0, p.shape[0], 256):
+        dd = track_distances_ld(track, p[lo:lo + 256])
+        got = dd[np.arange(dd.shape[0]), seg[lo:lo + 256]]
+        gap = got - dd.min(axis=1)
+        bad = np.nonzero(~(gap <= tol))[0]
+        if bad.size:
+            r = lo + int(bad[0])
+            return "pose %d %s: segment %d is %.3e m farther than segment %d" % (
+                r, p[r, :2].tolist(), seg[r], float(gap[bad[0]]), int(np.argmin(dd[bad[0]])))
+    return None

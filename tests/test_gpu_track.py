@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import pytest
 
-from _util import MAPS, bench_start_poses, load_map_image, map_stem, raceline
+from _util import MAPS, bench_start_poses, check_track_winner, load_map_image, map_stem, raceline, track_oracle as _oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -28,21 +28,6 @@ def amd():
 
 def _track(amd, xy=None, closed=True):
     return amd.Track.from_xy(raceline()[:, 1:3] if xy is None else xy, closed=closed)
-
-
-def _oracle(track, poses):
-    """[m][5] = s, lateral, heading_error, segment, t from the oracle's nearest_on_trajectory (C, the reference's arithmetic)"""
-    from oracle import orc
-    pts = track.points_closed()
-    wp = np.column_stack([pts, np.zeros(len(pts))])
-    out = np.empty((len(poses), 5))
-    for r, (px, py, th) in enumerate(np.asarray(poses, dtype=np.float64).reshape(-1, 3)):
-        i, dist, t = orc.nearest_on_trajectory(wp, px, py)
-        dx, dy = pts[i + 1, 0] - pts[i, 0], pts[i + 1, 1] - pts[i, 1]
-        rx, ry = px - (pts[i, 0] + t * dx), py - (pts[i, 1] + t * dy)
-        herr = np.mod(th - np.arctan2(dy, dx) + np.pi, 2 * np.pi) - np.pi
-        out[r] = (track.cum[i] + t * track.seg_len[i], -dist if dx * ry - dy * rx < 0 else dist, herr, i, t)
-    return out
 
 
 def _check_cols(got, want, what=""):
@@ -86,11 +71,64 @@ def _wiggly_loop(n):
     return np.column_stack([r * np.cos(a), r * np.sin(a)])
 
 
-@pytest.mark.parametrize("case", ["vertices", "equidistant", "far", "raceline", "big5000", "open", "closed_square"])
+def _mixed_polyline(rng, n, closed=False):
+    """n + 1 points whose segment lengths are log-uniform over 1 mm .. 50 m, turning by up to 2 rad at each vertex"""
+    ln = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), n))
+    ang = np.cumsum(rng.uniform(-2.0, 2.0, n))
+    xy = np.vstack([[0.0, 0.0], np.cumsum(np.column_stack([ln * np.cos(ang), ln * np.sin(ang)]), axis=0)])
+    return xy[:-1] if closed else xy
+
+
+def _ngon(n, r=3.0, c=(0.0, 0.0)):
+    a = 2 * np.pi * np.arange(n) / n
+    return np.column_stack([c[0] + r * np.cos(a), c[1] + r * np.sin(a)])
+
+
+UNIT_CASES = ["vertices", "equidistant", "far", "raceline", "big5000", "open", "closed_square", "lds1023", "lds1024", "lds1025",
+              "open2", "closed3", "mixed", "shift1e5", "shift1e6", "ngon37_centre", "shared_vertices", "nan_pose"]
+
+
+@pytest.mark.parametrize("case", UNIT_CASES)
 def test_unit_parity_vs_oracle(amd, case):
     rng = np.random.default_rng(5)
     sq = np.array([[0.0, 0.0], [2.0, 0.0], [2.0, 2.0], [0.0, 2.0]])
-    if case == "vertices":
+    if case.startswith("lds"):   # both sides of the LDS staging limit (kTrackLdsSegs = 1024 segments)
+        t = _track(amd, _wiggly_loop(int(case[3:])))
+        poses = np.column_stack([rng.uniform(-12, 12, (2048, 2)), rng.uniform(-7, 7, 2048)])
+        poses[:256, :2] = t.xy[rng.integers(0, t.num_points, 256)] + rng.normal(0, 1e-3, (256, 2))
+    elif case == "open2":       # 2 segments, 14 idle lanes
+        t = _track(amd, np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 2.0]]), closed=False)
+        poses = np.column_stack([rng.uniform(-2, 3, (1024, 2)), rng.uniform(-7, 7, 1024)])
+    elif case == "closed3":
+        t = _track(amd, np.array([[0.0, 0.0], [3.0, 0.0], [1.0, 2.0]]))
+        poses = np.column_stack([rng.uniform(-2, 4, (1024, 2)), rng.uniform(-7, 7, 1024)])
+        poses[:3, :2] = [[4.0 / 3, 2.0 / 3], [1.5, -1.0], [1.0, 1.0]]   # the centroid, beyond a corner, near a vertex
+    elif case == "mixed":       # segment lengths from 1 mm to 50 m in one track: pruning bounds of every size
+        t = _track(amd, _mixed_polyline(rng, 600), closed=False)
+        lo, hi = t.xy.min(axis=0) - 5, t.xy.max(axis=0) + 5
+        poses = np.column_stack([rng.uniform(lo, hi, (2048, 2)), rng.uniform(-7, 7, 2048)])
+        k = rng.integers(0, t.num_points - 1, 512)
+        w = rng.uniform(0, 1, (512, 1))
+        poses[:512, :2] = (1 - w) * t.xy[k] + w * t.xy[k + 1] + rng.normal(0, 1e-3, (512, 2))
+    elif case.startswith("shift"):   # far from the origin: the 1 um margin against float64 rounding of 1e5..1e6 m coordinates
+        off = float(case[5:])
+        t = _track(amd, raceline()[:, 1:3] + off)
+        lo, hi = t.xy.min(axis=0) - 2, t.xy.max(axis=0) + 2
+        poses = np.column_stack([rng.uniform(lo, hi, (2048, 2)), rng.uniform(-7, 7, 2048)])
+        poses[:256, :2] = t.xy[rng.integers(0, t.num_points, 256)]
+    elif case == "ngon37_centre":   # all 37 distances equal up to rounding: the last bits and the first-index rule decide
+        t = _track(amd, _ngon(37))
+        poses = np.column_stack([rng.normal(0.0, 1e-15, (512, 2)), rng.uniform(-7, 7, 512)])
+        poses[:8, :2] = 0.0
+    elif case == "shared_vertices":   # exactly on a vertex: two segments at distance 0, the first one wins
+        t = _track(amd, _mixed_polyline(rng, 300, closed=True))
+        poses = np.column_stack([t.xy, rng.uniform(-7, 7, t.num_points)])
+    elif case == "nan_pose":
+        t = _track(amd)
+        poses = np.column_stack([rng.uniform(-50, 20, (64, 2)), rng.uniform(-7, 7, 64)])
+        poses[0::3, 0] = np.nan
+        poses[1::3, 1] = np.nan
+    elif case == "vertices":
         t = _track(amd)
         poses = np.column_stack([t.xy, rng.uniform(-7, 7, t.num_points)])
     elif case == "equidistant":
@@ -123,6 +161,14 @@ def test_unit_parity_vs_oracle(amd, case):
     np.testing.assert_array_equal(got[:, 4], want[:, 4], err_msg="t")
     if case == "equidistant":
         assert got[0, 3] == 0 and got[1, 3] == 0 and got[2, 3] == 3   # ties: the first segment wins
+    if case == "nan_pose":   # the reference: np.argmin over all-NaN distances -> 0, t[0] NaN (its clip passes NaN through)
+        nan = np.isnan(poses[:, 0]) | np.isnan(poses[:, 1])
+        assert np.all(got[nan, 3] == 0) and np.all(np.isnan(got[nan, 4])) and np.all(np.isnan(got[nan, 0]))
+        assert np.all(np.isnan(want[nan, 4])) and np.all(np.isnan(want[nan, 0]))
+        assert np.array_equal(got[nan, :2], t.project(poses[nan])[:, :2], equal_nan=True)
+        poses, got = poses[~nan], got[~nan]
+    msg = check_track_winner(t, poses, got[:, 3])   # an independent extended-precision check of the winner
+    assert msg is None, case + ": " + msg
     s.close()
 
 
@@ -273,6 +319,148 @@ def test_two_maps_with_different_tracks(amd):
     for sl, t in ((0, t0), (1, t1)):
         m = slot == sl
         _check_cols(_cols(tr)[m], _oracle(t, post[m]), "slot %d" % sl)
+    s.close()
+
+
+# ------------------------------------------------------------------ the pruning seed (the last winner) and the LDS staging
+def _start_on(t, rng, n):
+    """n poses on random vertices of a track, heading along the segment that starts there"""
+    k = rng.integers(0, t.num_segments, n)
+    pts = t.points_closed()
+    d = pts[k + 1] - pts[k]
+    return np.column_stack([pts[k], np.arctan2(d[:, 1], d[:, 0])])
+
+
+def _step_via(s, path, act, hb, d_act):
+    if path == "step":
+        s.step(act)
+    elif path == "step_device":
+        d_act.upload(act)
+        s.step_device(d_act)
+    else:
+        s.step_host(hb, act, fuse=path != "step_host_no_fuse")
+
+
+def _check_step_winner(s, track, pre, what, rows=None):
+    """_check_step, plus the extended-precision check of every winner"""
+    rows = slice(None) if rows is None else rows
+    tr = s.get_track()
+    post = _poses_of(s)[rows]
+    want = _oracle(track, post)
+    _check_cols(_cols(tr)[rows], want, what)
+    ds = track.wrap_ds(want[:, 0] - _oracle(track, pre[rows])[:, 0])
+    np.testing.assert_array_equal(tr["ds"][rows], ds, err_msg=what + " ds")
+    msg = check_track_winner(track, post, tr["segment"][rows])
+    assert msg is None, what + ": " + msg
+
+
+STEP_PATHS = ["step", "step_device", "step_host", "step_host_no_fuse"]
+
+
+@pytest.mark.parametrize("nseg", [782, 1025, 5000])
+@pytest.mark.parametrize("path", STEP_PATHS)
+def test_adversarial_hints_after_set_state(amd, nseg, path):
+    """the step forms seed the search with the agent's last winning segment.  set_state moves agents (a) to the point of the track
+    farthest along it from that segment and (b) to near-tie points between two distant segments: the seed is then far from the
+    winner, and the result must still be the full first-minimum search's, bit for bit"""
+    E, A = 40, 2
+    N = E * A
+    t = _track(amd) if nseg == 782 else _track(amd, _wiggly_loop(nseg))
+    assert t.num_segments == nseg
+    rng = np.random.default_rng(nseg)
+    s = _sim(amd, E, A, t)
+    s.reset(_start_on(t, rng, N))
+    d_act = s.device_array((N, 2))
+    hb = s.host_block(("state", "agent_poses"))
+    pts = t.points_closed()
+    mid = 0.5 * (pts[:-1] + pts[1:])
+    acts = _actions(24, N, seed=nseg, vmax=5.0)
+    for k in range(24):
+        pre = s.get("state")["state"][:, [0, 1, 4]]
+        _step_via(s, path, acts[k], hb, d_act)
+        _check_step_winner(s, t, pre, "%s nseg %d step %d" % (path, nseg, k))
+        if k % 4 != 3:
+            continue
+        seg = s.get_track()["segment"].astype(np.int64)
+        st = s.get("state")["state"].copy()
+        far = (seg + nseg // 2) % nseg                           # (a) the opposite side of the track from the last winner
+        st[0::2, 0:2] = mid[far[0::2]]
+        other = (seg[1::2] + rng.integers(nseg // 4, 3 * nseg // 4 + 1, seg[1::2].size)) % nseg
+        tie = 0.5 * (mid[seg[1::2]] + mid[other])                  # (b) halfway between the winner's midpoint and a distant one
+        st[1::2, 0:2] = tie + rng.normal(0.0, 1e-12, tie.shape) * (rng.random((tie.shape[0], 1)) < 0.5)
+        s.set_state(st)
+    s.close()
+
+
+@pytest.mark.parametrize("layout", ["small_big", "big_small", "same_count"])
+@pytest.mark.parametrize("A", [1, 2])
+def test_mixed_slot_workgroups(amd, A, layout):
+    """two slots, one track of <= kTrackLdsSegs segments (staged in LDS) and one of more (read from global memory); env_map
+    alternates in runs of 5 envs, so slot changes fall inside the 16-agent workgroups — some workgroups' first agent sits on
+    the staged slot, some on the other.  same_count: two different tracks of 1000 segments each (both fit the LDS; only the
+    workgroup's first agent's slot is staged, and a table of the right size but the wrong slot must not be read)"""
+    E = 80
+    N = E * A
+    small, big = _track(amd, _wiggly_loop(600)), _track(amd, 1.2 * _wiggly_loop(2048))
+    tracks = {"small_big": (small, big), "big_small": (big, small),
+              "same_count": (_track(amd, _wiggly_loop(1000)), _track(amd, 1.2 * _wiggly_loop(1000)))}[layout]
+    s = amd.BatchSim(num_envs=E, num_agents=A)
+    s.set_map_image(*load_map_image("example_map"))
+    s.set_noise_rng(SEED, STD)
+    s.add_map_image(*load_map_image("example_map"))
+    s.set_track(tracks[0], 0)
+    s.set_track(tracks[1], 1)
+    env_map = (np.arange(E) // 5) % 2
+    s.set_env_maps(env_map)
+    s.enable_track()
+    slot = np.repeat(env_map, A)
+    rng = np.random.default_rng(A)
+    poses = np.empty((N, 3))
+    for sl in (0, 1):
+        poses[slot == sl] = _start_on(tracks[sl], rng, int((slot == sl).sum()))
+    s.reset(poses)
+    d_act = s.device_array((N, 2))
+    hb = s.host_block(("state", "agent_poses"))
+    acts = _actions(30, N, seed=20 + A, vmax=6.0)
+    for k in range(30):
+        path = STEP_PATHS[k % len(STEP_PATHS)]
+        pre = s.get("state")["state"][:, [0, 1, 4]]
+        _step_via(s, path, acts[k], hb, d_act)
+        for sl in (0, 1):
+            _check_step_winner(s, tracks[sl], pre, "A=%d %s %s step %d slot %d" % (A, layout, path, k, sl), slot == sl)
+        if k == 14:   # swap the slots' tracks mid-run: every cached s and every seed goes stale at once
+            tracks = tracks[::-1]
+            s.set_track(tracks[0], 0)
+            s.set_track(tracks[1], 1)
+    s.close()
+
+
+@pytest.mark.parametrize("how", ["clone_envs", "load_envs"])
+def test_a_load_onto_another_slot_at_the_same_pose_re_projects(amd, how):
+    """two envs at bitwise the same pose on two slots with different tracks; env 0 copied onto env 1 moves env 1 to slot 0 without
+    changing its pose bits, so only the cache invalidation of the load tells the next step that env 1's cached s is stale"""
+    A = 2
+    t0, t1 = _track(amd), _track(amd, _wiggly_loop(1500))
+    s = amd.BatchSim(num_envs=2, num_agents=A)
+    s.set_map_image(*load_map_image("example_map"))
+    s.add_map_image(*load_map_image("example_map"))
+    s.set_track(t0, 0)
+    s.set_track(t1, 1)
+    s.set_env_maps([0, 1])
+    s.enable_track()
+    p = bench_start_poses(1, A, gap_wp=4)
+    s.reset(np.vstack([p, p]))
+    act = np.tile([[0.1, 3.0]], (2 * A, 1))
+    s.step(act)
+    post = _poses_of(s)
+    assert np.array_equal(post[:A], post[A:])
+    if how == "clone_envs":
+        s.clone_envs([0], [1])
+    else:
+        s.load_envs(s.save_envs([0]), [0], [1])
+    pre = s.get("state")["state"][:, [0, 1, 4]]
+    s.step(act)
+    _check_step_winner(s, t0, pre, how + " (both envs on slot 0 now)")
     s.close()
 
 
