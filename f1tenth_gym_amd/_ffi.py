@@ -186,6 +186,7 @@ PROTOTYPES = {
     "f110_track_get": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
     "f110_track_host_block": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
     "f110_track_project_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp]),
+    "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
     "f110_edt_sq": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, _u32p]),
     "f110_beam_dir_index_batch": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i32p]),
     "f110_dt_from_bitmap": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, C.c_double, _dp]),

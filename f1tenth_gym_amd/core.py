@@ -1023,6 +1023,44 @@ class BatchSim(object):
         check(_ffi.lib().f110_track_project_batch(self._h, int(slot), dptr(p), p.shape[0], dptr(out)), self._h)
         return out
 
+    # ------------------------------------------------------------------ rendering (f110_render_device)
+    def render_device(self, agents=None, width=64, height=64, view='ego', m_per_px=0.05, center=(0.0, 0.0), angle=0.0,
+                      fwd_offset=0.0, layers=('map', 'cars'), car_size=None, rgb=False, palette=None, out=None):
+        """class images of the last observation, one frame per camera agent (None: every agent): uint8 DeviceArrays
+        classes [F][H][W] (render.CLASSES) and, with rgb, [F][H][W][3] = palette[classes] -> classes or (classes, rgb).
+        view 'world' (center, angle), 'follow' (the agent's pose + fwd_offset along its heading, north up) or 'ego' (heading
+        up); layers from ('map', 'track', 'scan', 'cars') or 'all'; car_size (length, width) overrides every agent's params.
+        Enqueued on the handle's stream (no host wait); `out` = (classes[, rgb]) DeviceArrays to reuse."""
+        from . import render as R
+        spec = R.make_spec(width, height, view, m_per_px, center, angle, fwd_offset, layers, car_size)
+        a = R.check_agents(agents, self.N, spec)
+        pal = R.check_palette(palette)
+        F, H, W = a.size, spec.height, spec.width
+        if out is not None:
+            out = tuple(out) if isinstance(out, (tuple, list)) else (out,)
+            want = [((F, H, W), np.uint8)] + ([((F, H, W, 3), np.uint8)] if rgb else [])
+            if len(out) != len(want) or any(tuple(o.shape) != s or o.dtype != d for o, (s, d) in zip(out, want)):
+                raise ValueError("out must be %s DeviceArrays of shapes %s" % (len(want), [s for s, _ in want]))
+            cls, img = out[0], (out[1] if rgb else None)
+        else:
+            cls = DeviceArray(self, (F, H, W), np.uint8)
+            img = DeviceArray(self, (F, H, W, 3), np.uint8) if rgb else None
+        ap = None if agents is None else a.ctypes.data_as(_ffi._i32p)
+        check(_ffi.lib().f110_render_device(self._h, C.byref(spec), ap, F, cls.ptr, img.ptr if img is not None else None,
+                                            pal.ctypes.data_as(_ffi._u8p)), self._h)
+        return (cls, img) if rgb else cls
+
+    def render(self, agents=None, **spec):
+        """render_device, downloaded (synchronises): NumPy uint8 classes [F][H][W], or (classes, rgb) with rgb=True"""
+        res = self.render_device(agents, **spec)
+        res = res if isinstance(res, tuple) else (res,)
+        try:
+            host = tuple(r.download() for r in res)
+        finally:
+            for r in res:
+                r.free()
+        return host if len(host) > 1 else host[0]
+
     # ------------------------------------------------------------------ the reference's example policy
     def pure_pursuit_batch(self, waypoints, poses, lookahead, vgain, wheelbase, max_reacquire=20.0):
         """PurePursuitPlanner.plan (examples/waypoint_follow.py:203-217) for host poses [m][3];

@@ -79,6 +79,7 @@ struct f110_sim {
     struct MapSlot {
         double *d_dt_row = nullptr, *d_dt_pad = nullptr;
         ScanConst k{};
+        uint8_t *d_occ = nullptr;   // f110_render_device's occupancy grid, built on first use
     };
     std::vector<MapSlot> extra_maps;
     MapFast *d_maps_fast = nullptr;
@@ -190,7 +191,8 @@ struct f110_sim {
     // track progress (f110_track_*): a polyline per map slot, the step's columns, the per-agent cache of s
     struct TrackSlot {
         double *d_cols = nullptr;   // [7][nseg] (TrackCol)
-        int32_t nseg = 0, closed = 0;
+        double *d_pts = nullptr;    // [npts][2] the points (after the closed-track dedupe), what a render draws
+        int32_t nseg = 0, closed = 0, npts = 0;
         double L = 0.0;
     };
     std::vector<TrackSlot> tracks;        // indexed by map slot (shorter than the slot list: the rest have no track)
@@ -207,6 +209,18 @@ struct f110_sim {
     f110_track_host trk_pinned{};         // f110_track_host_block, host pointers ...
     HostBlock trk_hb{};                   // ... and their device views (the trk_* fields)
     bool trk_pinned_on = false;
+    // rendering (f110_render_device): slot 0's occupancy grid, the slot table as last uploaded, per-frame / per-agent records
+    uint8_t *d_occ0 = nullptr;
+    std::vector<RenderSlot> render_slots;
+    RenderSlot *d_render_slots = nullptr;
+    size_t render_slots_cap = 0;
+    RenderFrame *d_render_frames = nullptr;
+    size_t render_frames_cap = 0;
+    RenderCar *d_render_cars = nullptr;
+    int32_t *d_render_agents = nullptr;
+    size_t render_agents_cap = 0;
+    uint8_t *d_render_stage = nullptr;   // [F][H][pitch] when the caller's buffer cannot take 32-bit stores
+    size_t render_stage_cap = 0;
     // timing
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool profiling = false;
@@ -874,13 +888,21 @@ void f110_destroy(f110_sim *h)
     for (auto &ms : h->extra_maps) {
         if (ms.d_dt_row) (void)hipFree(ms.d_dt_row);
         if (ms.d_dt_pad) (void)hipFree(ms.d_dt_pad);
+        if (ms.d_occ) (void)hipFree(ms.d_occ);
     }
     if (h->d_maps_fast) (void)hipFree(h->d_maps_fast);
     if (h->d_maps_full) (void)hipFree(h->d_maps_full);
     if (h->d_env_map) (void)hipFree(h->d_env_map);
     if (h->d_scan_order) (void)hipFree(h->d_scan_order);
-    for (auto &ts : h->tracks)
+    for (auto &ts : h->tracks) {
         if (ts.d_cols) (void)hipFree(ts.d_cols);
+        if (ts.d_pts) (void)hipFree(ts.d_pts);
+    }
+    {
+        void *rp[] = {h->d_occ0, h->d_render_slots, h->d_render_frames, h->d_render_cars, h->d_render_agents, h->d_render_stage};
+        for (void *p : rp)
+            if (p) (void)hipFree(p);
+    }
     {
         void *tp[] = {h->d_tracks, h->d_trk, h->d_trk_seg, h->d_trk_cache, h->d_trk_ok};
         for (void *p : tp)
@@ -944,6 +966,7 @@ static int finish_map(f110_sim *h, int H, int W, double res, double ox, double o
     TRY(track_invalidate(h));
     h->dev.maps_full = nullptr;
     h->dev.env_map = nullptr;
+    if (h->d_occ0) { (void)hipFree(h->d_occ0); h->d_occ0 = nullptr; }   // a render rebuilds it from the new table
     fill_map_fields(k, H, W, res, ox, oy, oc, os);
     HIPCHK(h, hipMemcpyAsync(&k.oob_value, h->d_dt_row + ((size_t)H * W - 1), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     k.table = h->d_dt_row;
@@ -3838,17 +3861,26 @@ int f110_track_set(f110_sim *h, int32_t slot, const double *h_xy, int32_t M, int
         cols[6 * (size_t)nseg + k] = cum;
         cum += len;
     }
-    double *d_cols = nullptr;
+    double *d_cols = nullptr, *d_pts = nullptr;
     TRY(dmalloc(h, &d_cols, cols.size()));
-    const hipError_t e = hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (dmalloc(h, &d_pts, 2 * (size_t)m) != F110_OK) {
+        (void)hipFree(d_cols);
+        return F110_ERR_NOMEM;
+    }
+    hipError_t e = hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pts, h_xy, 2 * (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
         (void)hipFree(d_cols);
+        (void)hipFree(d_pts);
         return fail(h, F110_ERR_HIP, "f110_track_set: upload failed: %s", hipGetErrorString(e));
     }
     if ((int)h->tracks.size() <= slot) h->tracks.resize((size_t)slot + 1);
     f110_sim::TrackSlot &ts = h->tracks[slot];
     if (ts.d_cols) HIPCHK(h, hipFree(ts.d_cols));   // (synchronised above: no step reads the old table any more)
+    if (ts.d_pts) HIPCHK(h, hipFree(ts.d_pts));
     ts.d_cols = d_cols;
+    ts.d_pts = d_pts;
+    ts.npts = m;
     ts.nseg = nseg;
     ts.closed = closed ? 1 : 0;
     ts.L = cum;
@@ -3956,5 +3988,152 @@ int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, i
     HIPCHK(h, hipGetLastError());
     TRY(sc.down(h_out, dout, 5 * (size_t)m));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- rendering --------------------------------------------------------------------------------------------------------------
+// rendering.py's clear colour (OUTSIDE, FREE), its map points and waypoint_follow.py's waypoints (WALL, TRACK), then SCAN, CAR, SELF
+static const uint8_t kDefaultPalette[F110_NCLASSES * 3] = {9, 32, 87, 9, 32, 87, 183, 193, 222, 183, 193, 222, 255, 190, 0, 99, 52, 94, 172, 97, 185};
+
+template <typename T>
+static int render_grow(f110_sim *h, T **p, size_t *cap, size_t count)
+{
+    if (*p && *cap >= count) return F110_OK;
+    if (*p) HIPCHK(h, hipFree(*p));   // (hipFree waits for the renders in flight that read it)
+    *p = nullptr;
+    *cap = 0;
+    TRY(dmalloc(h, p, count));
+    *cap = count;
+    return F110_OK;
+}
+
+// the occupancy grid of a slot's table, built the first time a render reads the slot
+static int render_occ(f110_sim *h, const ScanConst &k, uint8_t **occ)
+{
+    if (*occ) return F110_OK;
+    const size_t n = (size_t)k.height * k.width;
+    TRY(dmalloc(h, occ, n));
+    hipLaunchKernelGGL(k_render_occ, grid1d(n, 256), dim3(256), 0, h->stream, k.table, k.row_bytes, k.height, k.width, *occ);
+    HIPCHK(h, hipGetLastError());
+    return F110_OK;
+}
+
+int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t *h_agents, int32_t n_frames, uint8_t *d_classes,
+                       uint8_t *d_rgb, const uint8_t *h_palette)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (!spec || !d_classes) return fail(h, F110_ERR_INVALID, "f110_render_device: spec and d_classes are required");
+    const f110_render_spec sp = *spec;
+    const int W = sp.width, H = sp.height, N = h->N, A = h->cfg.num_agents;
+    if (W < 1 || W > 4096 || H < 1 || H > 4096) return fail(h, F110_ERR_INVALID, "f110_render_device: width and height must be in 1..4096 (got %d x %d)", W, H);
+    if (!(std::isfinite(sp.m_per_px) && sp.m_per_px > 0)) return fail(h, F110_ERR_INVALID, "f110_render_device: m_per_px must be finite and > 0");
+    if (sp.view < F110_VIEW_WORLD || sp.view > F110_VIEW_EGO) return fail(h, F110_ERR_INVALID, "f110_render_device: unknown view %d", sp.view);
+    if (sp.layers & ~F110_LAYER_ALL) return fail(h, F110_ERR_INVALID, "f110_render_device: unknown layer bits 0x%x", sp.layers);
+    if (n_frames < 1) return fail(h, F110_ERR_INVALID, "f110_render_device: n_frames = %d", n_frames);
+    if (!h_agents && n_frames != N) return fail(h, F110_ERR_INVALID, "f110_render_device: without an agent list n_frames must be N = %d (got %d)", N, n_frames);
+    if (h_agents)
+        for (int f = 0; f < n_frames; ++f)
+            if (h_agents[f] < 0 || h_agents[f] >= N) return fail(h, F110_ERR_INVALID, "f110_render_device: frame %d: agent %d is outside [0, %d)", f, h_agents[f], N);
+    if ((unsigned long long)n_frames * (unsigned long long)H * (unsigned long long)W > (1ull << 31))
+        return fail(h, F110_ERR_INVALID, "f110_render_device: %d frames of %d x %d pixels exceed 2^31", n_frames, H, W);
+    if (sp.view == F110_VIEW_WORLD && !(std::isfinite(sp.center_x) && std::isfinite(sp.center_y) && std::isfinite(sp.angle)))
+        return fail(h, F110_ERR_INVALID, "f110_render_device: the WORLD camera needs a finite centre and angle");
+    if (sp.view != F110_VIEW_WORLD && !std::isfinite(sp.fwd_offset)) return fail(h, F110_ERR_INVALID, "f110_render_device: fwd_offset is not finite");
+    ENTER(h);
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    const int F = n_frames;
+    const int slots = 1 + (int)h->extra_maps.size();
+    // the slot table: the map fields, the occupancy grid when MAP is drawn, the track points
+    std::vector<RenderSlot> rs((size_t)slots);
+    for (int m = 0; m < slots; ++m) {
+        const ScanConst &k = m == 0 ? h->k : h->extra_maps[m - 1].k;
+        RenderSlot &r = rs[m];
+        r = RenderSlot{};
+        if (sp.layers & F110_LAYER_MAP) TRY(render_occ(h, k, m == 0 ? &h->d_occ0 : &h->extra_maps[m - 1].d_occ));
+        r.occ = m == 0 ? h->d_occ0 : h->extra_maps[m - 1].d_occ;
+        if ((sp.layers & F110_LAYER_TRACK) && m < (int)h->tracks.size() && h->tracks[m].d_pts) {
+            r.pts = h->tracks[m].d_pts;
+            r.npts = h->tracks[m].npts;
+        }
+        r.height = k.height;
+        r.width = k.width;
+        r.res = k.res;
+        r.inv_res = k.inv_res;
+        r.orig_x = k.orig_x;
+        r.orig_y = k.orig_y;
+        r.orig_c = k.orig_c;
+        r.orig_s = k.orig_s;
+        r.w_res = k.w_res;
+        r.h_res = k.h_res;
+    }
+    if (h->render_slots.size() != rs.size() || std::memcmp(h->render_slots.data(), rs.data(), rs.size() * sizeof(RenderSlot)) != 0) {
+        TRY(render_grow(h, &h->d_render_slots, &h->render_slots_cap, rs.size()));
+        h->render_slots = rs;   // (a pageable source: consumed before the call returns)
+        HIPCHK(h, hipMemcpyAsync(h->d_render_slots, h->render_slots.data(), rs.size() * sizeof(RenderSlot), hipMemcpyHostToDevice, h->stream));
+    }
+    TRY(render_grow(h, &h->d_render_frames, &h->render_frames_cap, (size_t)F));
+    if (!h->d_render_cars) TRY(dmalloc(h, &h->d_render_cars, (size_t)N));
+    if (h_agents) {
+        TRY(render_grow(h, &h->d_render_agents, &h->render_agents_cap, (size_t)F));
+        HIPCHK(h, hipMemcpyAsync(h->d_render_agents, h_agents, (size_t)F * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    }
+    // 32-bit stores straight into the caller's buffer when its rows allow them, else into an aligned copy with padded rows
+    const bool direct = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_classes) % 4 == 0);
+    const int pitch = (W + 3) & ~3;
+    uint8_t *target = d_classes;
+    if (!direct) {
+        TRY(render_grow(h, &h->d_render_stage, &h->render_stage_cap, (size_t)F * H * pitch));
+        target = h->d_render_stage;
+    }
+    RenderJob j{};
+    j.snap = h->dev.snap_pose;
+    j.params = h->dev.params;
+    j.params_per_agent = h->dev.params_per_agent;
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.slots = h->d_render_slots;
+    j.agents = h_agents ? h->d_render_agents : nullptr;
+    j.frames = h->d_render_frames;
+    j.cars = h->d_render_cars;
+    j.cls = target;
+    j.scans = h->dev.scans;
+    j.F = F;
+    j.N = N;
+    j.A = A;
+    j.W = W;
+    j.H = H;
+    j.pitch = pitch;
+    j.view = sp.view;
+    j.layers = sp.layers;
+    j.B = h->cfg.num_beams;
+    j.words_per_frame = (uint32_t)(pitch / 4) * (uint32_t)H;
+    j.blocks_per_frame = (j.words_per_frame + 255) / 256;
+    j.mpp = sp.m_per_px;
+    j.center_x = sp.center_x;
+    j.center_y = sp.center_y;
+    j.angle = sp.angle;
+    j.fwd = sp.fwd_offset;
+    j.car_len = sp.car_length;
+    j.car_wid = sp.car_width;
+    j.lidar_dist = h->cfg.lidar_dist;
+    j.cull_r = (0.5 * std::hypot((double)W, (double)H) + 1.0) * sp.m_per_px * 1.01;
+    hipLaunchKernelGGL(k_render_setup, grid1d((size_t)std::max(F, N), 256), dim3(256), 0, h->stream, j);
+    hipLaunchKernelGGL(k_render_raster, dim3((unsigned)((size_t)F * j.blocks_per_frame)), dim3(256), 0, h->stream, j);
+    HIPCHK(h, hipGetLastError());
+    if (sp.layers & F110_LAYER_TRACK) {
+        uint32_t most = 0;
+        for (const RenderSlot &r : rs) most = std::max(most, (uint32_t)r.npts);
+        if (most > 0) hipLaunchKernelGGL(k_render_points<false>, grid1d((size_t)F * most, 256), dim3(256), 0, h->stream, j, h->k, most);
+    }
+    if (sp.layers & F110_LAYER_SCAN)
+        hipLaunchKernelGGL(k_render_points<true>, grid1d((size_t)F * j.B, 256), dim3(256), 0, h->stream, j, h->k, (uint32_t)j.B);
+    HIPCHK(h, hipGetLastError());
+    if (!direct || d_rgb) {
+        RenderPalette pal{};
+        std::memcpy(pal.rgb, h_palette ? h_palette : kDefaultPalette, sizeof pal.rgb);
+        const size_t total = (size_t)F * H * W;
+        hipLaunchKernelGGL(k_render_finish, grid1d(total, 256), dim3(256), 0, h->stream, target, direct ? W : pitch, W, H, total,
+                           direct ? nullptr : d_classes, d_rgb, pal);
+        HIPCHK(h, hipGetLastError());
+    }
     return F110_OK;
 }

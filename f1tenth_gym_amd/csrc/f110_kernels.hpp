@@ -3541,3 +3541,258 @@ __global__ void __launch_bounds__(256) k_clone_envs(StateCols cols, const int32_
 {
     state_copy<true, true>(cols, nullptr, nullptr, src, dst, k, cols.num_envs, status);
 }
+
+// ---- rendering (f110_render_device) -----------------------------------------------------------------------------------------
+// rendering.py's scene (map points, one quad per car) as a class image, one uint8 per pixel; include/f110.h states the rules.
+// k_render_setup turns the spec into one record per frame (centre, cos / sin of the camera angle, env, slot) and one per agent
+// (get_vertices' corners and their bounding box), so no pixel evaluates trigonometry.  k_render_raster classifies MAP and CARS:
+// one workgroup covers part of one frame (the records are wave-uniform: scalar loads), each lane 4 adjacent pixels of a row, one
+// 32-bit store.  The map test reads a per-slot byte grid (1 where dt == 0), 8x smaller than the float64 table.  k_render_points
+// then scatters TRACK points and SCAN hits (two ordered launches); a point overwrites only a lower class, so the only concurrent
+// writes to one byte store the same value.  k_render_finish writes the palette image (and the caller's class buffer when the
+// raster wrote into an aligned staging copy).
+struct RenderSlot {
+    const uint8_t *occ;    // [height][width] 1 where the distance table is 0
+    const double *pts;     // [npts][2] the slot's track points (nullptr: no track)
+    int32_t height, width, npts, pad_;
+    double res, inv_res, orig_x, orig_y, orig_c, orig_s, w_res, h_res;
+};
+struct RenderFrame {
+    double cx, cy, c, s;
+    int32_t env, slot, self, valid;   // valid = 0: a FOLLOW / EGO camera on an agent with a non-finite pose (all OUTSIDE)
+};
+struct RenderCar {
+    double v[8];      // box_vertices: [rl, rr, fr, fl] (x, y)
+    double bb[4];     // xmin, xmax, ymin, ymax, widened by kRenderBoxSlack
+    int32_t draw, pad_[3];
+};
+constexpr double kRenderBoxSlack = 1e-6;   // the box test proper decides; the bounding box only skips cars far from a pixel
+
+struct RenderJob {
+    const double *snap;         // [3][N] Simulator.agent_poses
+    const double *params;       // [A][18] or [N][18]
+    const int32_t *env_map;     // [E] or nullptr (every env on slot 0)
+    const RenderSlot *slots;
+    const int32_t *agents;      // [F] camera agents, or nullptr (frame f = agent f)
+    RenderFrame *frames;        // [F]
+    RenderCar *cars;            // [N]
+    uint8_t *cls;               // [F][H][pitch]
+    const double *scans;        // [N][B]
+    int32_t F, N, A, W, H, pitch, view, layers, params_per_agent, B;
+    uint32_t words_per_frame, blocks_per_frame;   // raster: pitch / 4 * H, its workgroups
+    double mpp, center_x, center_y, angle, fwd, car_len, car_wid, lidar_dist;
+    double cull_r;   // the frame's half-diagonal plus a pixel and 1 %: a point farther from the centre lands in no pixel
+};
+
+__device__ __forceinline__ bool render_finite(double x, double y, double t) { return isfinite(x) && isfinite(y) && isfinite(t); }
+
+// lanes [0, F): the frame records; lanes [0, N): the car records
+__global__ void __launch_bounds__(256) k_render_setup(RenderJob j)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t N = (size_t)j.N;
+    if (t < j.F) {
+        const int n = j.agents ? j.agents[t] : t;
+        const int e = n / j.A;
+        RenderFrame fr;
+        fr.env = e;
+        fr.slot = j.env_map ? j.env_map[e] : 0;
+        fr.self = n;
+        fr.valid = 1;
+        const double x = j.snap[n], y = j.snap[N + n], th = j.snap[2 * N + n];
+        if (j.view == 0) {
+            fr.cx = j.center_x;
+            fr.cy = j.center_y;
+            cos_sin(j.angle, fr.c, fr.s);
+        } else {
+            double ch, sh;
+            cos_sin(th, ch, sh);
+            fr.cx = x + j.fwd * ch;
+            fr.cy = y + j.fwd * sh;
+            if (j.view == 1) {
+                fr.c = 1.0;
+                fr.s = 0.0;
+            } else {
+                cos_sin(th - kPi / 2, fr.c, fr.s);
+            }
+            if (!render_finite(x, y, th)) fr.valid = 0;
+        }
+        j.frames[t] = fr;
+    }
+    if (t < j.N) {
+        RenderCar car;
+        const double x = j.snap[t], y = j.snap[N + t], th = j.snap[2 * N + t];
+        const double *p = j.params + (size_t)(j.params_per_agent ? t : t % j.A) * NPARAMS;
+        const bool over = j.car_len > 0.0 && j.car_wid > 0.0;
+        box_vertices(x, y, th, over ? j.car_len : p[P_LENGTH], over ? j.car_wid : p[P_WIDTH], car.v);
+        car.draw = render_finite(x, y, th) ? 1 : 0;
+        double x0 = car.v[0], x1 = car.v[0], y0 = car.v[1], y1 = car.v[1];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) {
+            x0 = fmin(x0, car.v[2 * q]);
+            x1 = fmax(x1, car.v[2 * q]);
+            y0 = fmin(y0, car.v[2 * q + 1]);
+            y1 = fmax(y1, car.v[2 * q + 1]);
+        }
+        car.bb[0] = x0 - kRenderBoxSlack;
+        car.bb[1] = x1 + kRenderBoxSlack;
+        car.bb[2] = y0 - kRenderBoxSlack;
+        car.bb[3] = y1 + kRenderBoxSlack;
+        car.pad_[0] = car.pad_[1] = car.pad_[2] = 0;
+        j.cars[t] = car;
+    }
+}
+
+// int(v / res) of xy_2_rc :83-84 (cell_index's rule: the reciprocal decides unless the quotient is within 1e-9 of an integer)
+__device__ __forceinline__ int render_cell(double v, double res, double inv_res, int n)
+{
+    const double q = v * inv_res;
+    int ci = (int)q;
+    const double fr = q - (double)ci;
+    if (fr < 1e-9 || fr > 1.0 - 1e-9) ci = (int)(v / res);
+    return ci < n ? ci : n - 1;   // (v < n * res rounded can still divide to n)
+}
+
+__device__ __forceinline__ int render_pixel(const RenderJob &j, const RenderFrame &fr, const RenderSlot &ms, double x, double y)
+{
+    int cls = 1;   // FREE (also what MAP off leaves)
+    if (j.layers & F110_LAYER_MAP) {
+        const double xt = x - ms.orig_x, yt = y - ms.orig_y;
+        const double xr = xt * ms.orig_c + yt * ms.orig_s;
+        const double yr = -xt * ms.orig_s + yt * ms.orig_c;
+        const bool inside = (xr >= 0) & (xr < ms.w_res) & (yr >= 0) & (yr < ms.h_res);
+        cls = 0;
+        if (inside) {
+            const int c = render_cell(xr, ms.res, ms.inv_res, ms.width), r = render_cell(yr, ms.res, ms.inv_res, ms.height);
+            cls = ms.occ[(size_t)r * ms.width + c] ? 2 : 1;
+        }
+    }
+    if (j.layers & F110_LAYER_CARS) {
+        const int a0 = fr.env * j.A;
+        for (int a = 0; a < j.A; ++a) {
+            const RenderCar &car = j.cars[a0 + a];
+            if (!car.draw || x < car.bb[0] || x > car.bb[1] || y < car.bb[2] || y > car.bb[3]) continue;
+            bool in = true;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int q1 = (q + 1) & 3;
+                const double ax = car.v[2 * q], ay = car.v[2 * q + 1], bx = car.v[2 * q1], by = car.v[2 * q1 + 1];
+                in = in && ((bx - ax) * (y - ay) - (by - ay) * (x - ax) >= 0.0);
+            }
+            if (in) {
+                const int k = (a0 + a == fr.self) ? 6 : 5;
+                cls = k > cls ? k : cls;
+            }
+        }
+    }
+    return cls;
+}
+
+// MAP and CARS: lane = 4 adjacent pixels of one row of one frame (pitch % 4 == 0; pixels j >= W are padding, left 0)
+__global__ void __launch_bounds__(256) k_render_raster(RenderJob j)
+{
+    const uint32_t f = blockIdx.x / j.blocks_per_frame;
+    const uint32_t w = (blockIdx.x - f * j.blocks_per_frame) * blockDim.x + threadIdx.x;
+    if (w >= j.words_per_frame) return;
+    const uint32_t wpr = (uint32_t)j.pitch >> 2;
+    const int i = (int)(w / wpr), j0 = (int)(w - (uint32_t)i * wpr) * 4;
+    const RenderFrame fr = j.frames[f];
+    uint32_t word = 0;
+    if (fr.valid) {
+        const RenderSlot ms = j.slots[fr.slot];
+        const double v = ((double)j.H * 0.5 - ((double)i + 0.5)) * j.mpp;
+        const double vs = v * fr.s, vc = v * fr.c;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (j0 + q >= j.W) break;
+            const double u = (((double)(j0 + q) + 0.5) - (double)j.W * 0.5) * j.mpp;
+            const double x = fr.cx + (u * fr.c - vs);
+            const double y = fr.cy + (u * fr.s + vc);
+            word |= (uint32_t)render_pixel(j, fr, ms, x, y) << (8 * q);
+        }
+    }
+    *reinterpret_cast<uint32_t *>(j.cls + ((size_t)f * j.H + i) * j.pitch + j0) = word;
+}
+
+// TRACK (SCAN = false: lane = (frame, track point)) or SCAN (lane = (frame, beam)) points into the class image
+template <bool SCAN>
+__global__ void __launch_bounds__(256) k_render_points(RenderJob j, ScanConst k, uint32_t per_frame)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)j.F * per_frame) return;
+    const int f = (int)(t / per_frame), p = (int)(t - (size_t)f * per_frame);
+    const RenderFrame fr = j.frames[f];
+    if (!fr.valid) return;
+    double px, py;
+    if (SCAN) {
+        const size_t N = (size_t)j.N;
+        const int n = fr.self;
+        const double r = j.scans[(size_t)n * j.B + p];
+        if (!(r < k.max_range)) return;
+        double st[5] = {j.snap[n], j.snap[N + n], 0.0, 0.0, j.snap[2 * N + n]};
+        double sp[3];
+        const bool on_axle = j.lidar_dist == 0.0 && fabs(st[4]) < 1e300 && !(st[0] == 0.0 && signbit(st[0])) && !(st[1] == 0.0 && signbit(st[1]));
+        if (on_axle) {   // fan_finish's lidar pose (base_classes.py:407-409)
+            sp[0] = st[0];
+            sp[1] = st[1];
+        } else {
+            double ch, sh;
+            cos_sin(st[4], ch, sh);
+            sp[0] = st[0] + j.lidar_dist * ch;
+            sp[1] = st[1] + j.lidar_dist * sh;
+        }
+        sp[2] = st[4];
+        if (!render_finite(sp[0], sp[1], sp[2])) return;
+        const double ox = sp[0] - fr.cx, oy = sp[1] - fr.cy;
+        if (!(r <= sqrt(ox * ox + oy * oy) + j.cull_r)) return;   // the hit is beyond the frame whatever the beam's direction
+        const double2 cs = k.cs[beam_dir_index(k, scan_start_index(k, sp[2]), p)];
+        px = sp[0] + r * cs.x;
+        py = sp[1] + r * cs.y;
+    } else {
+        const RenderSlot ms = j.slots[fr.slot];
+        if (p >= ms.npts) return;
+        px = ms.pts[2 * p];
+        py = ms.pts[2 * p + 1];
+    }
+    const double dx = px - fr.cx, dy = py - fr.cy;
+    if (!(dx * dx + dy * dy <= j.cull_r * j.cull_r)) return;   // (NaN included) before the divisions
+    const double up = dx * fr.c + dy * fr.s, vp = -dx * fr.s + dy * fr.c;
+    const double fi = floor((double)j.H * 0.5 - vp / j.mpp), fj = floor(up / j.mpp + (double)j.W * 0.5);
+    if (!(fi >= 0.0 && fi < (double)j.H && fj >= 0.0 && fj < (double)j.W)) return;
+    uint8_t *dst = j.cls + ((size_t)f * j.H + (size_t)fi) * j.pitch + (size_t)fj;
+    const uint8_t cls = SCAN ? 4 : 3;
+    if (*dst < cls) *dst = cls;
+}
+
+struct RenderPalette {
+    uint8_t rgb[F110_NCLASSES * 3];
+    uint8_t pad_[11];
+};
+
+// pixel -> rgb = palette[class] (rgb != nullptr), and the staged classes (row pitch `pitch`) into the caller's dense buffer
+__global__ void __launch_bounds__(256) k_render_finish(const uint8_t *__restrict__ staged, int pitch, int W, int H, size_t total,
+                                                       uint8_t *__restrict__ cls, uint8_t *__restrict__ rgb, RenderPalette pal)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= total) return;
+    const size_t row = q / (size_t)W, col = q - row * (size_t)W;
+    uint8_t c = staged[row * (size_t)pitch + col];
+    if (c >= F110_NCLASSES) c = 0;
+    if (cls) cls[q] = c;
+    if (rgb) {
+        rgb[3 * q] = pal.rgb[3 * c];
+        rgb[3 * q + 1] = pal.rgb[3 * c + 1];
+        rgb[3 * q + 2] = pal.rgb[3 * c + 2];
+    }
+    (void)H;
+}
+
+// the per-slot occupancy grid: 1 where the distance table holds 0 (the cells rays stop in)
+__global__ void __launch_bounds__(256) k_render_occ(const double *__restrict__ table, int row_bytes, int H, int W, uint8_t *__restrict__ occ)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (size_t)H * W) return;
+    const size_t r = q / (size_t)W, c = q - r * (size_t)W;
+    const double d = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(table) + r * (size_t)row_bytes + c * 8);
+    occ[q] = d == 0.0 ? 1 : 0;
+}

@@ -4,8 +4,9 @@
 Kept from the reference: constructor kwargs and defaults (:104-159), `reset(poses)` that
 advances one zero-action step and returns a 4-tuple (:306-349), `step(action)` returning
 (obs, reward=timestep, done, info={'checkpoint_done': ...}) (:263-304), the lap/finish logic
-(:204-246), `update_map`, `update_params`, `add_render_callback`.  Rendering (pyglet) is out of
-scope for this build: `render()` raises NotImplementedError.
+(:204-246), `update_map`, `update_params`, `add_render_callback`.  `render('rgb_array')` draws the
+scene on the device; the pyglet window ('human', 'human_fast') is out of scope and raises
+NotImplementedError.
 `gym` is optional: when importable F110Env subclasses gym.Env, otherwise `object`.
 """
 import copy
@@ -140,8 +141,38 @@ def _reward_mode(reward):
 _TRACK_OBS = {key: src for src, key in Simulator.TRACK_KEYS}
 
 
+# F110Env.render('rgb_array'): the reference window at its first draw — 1000 x 800 pixels, zoom 1.2 on the 50 px/m scene
+# (rendering.py), centred on the map origin
+RENDER_DEFAULTS = {"width": 1000, "height": 800, "view": "world", "m_per_px": 0.024, "center": (0.0, 0.0), "angle": 0.0,
+                   "fwd_offset": 0.0, "layers": None, "car_size": None, "palette": None}
+
+
+def _render_spec(base, spec):
+    """base updated by spec, validated (ValueError); layers None = every layer that has data"""
+    from . import render as R
+    unknown = set(spec) - set(RENDER_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown render option(s): %s" % ", ".join(sorted(unknown)))
+    out = dict(base)
+    out.update(spec)
+    R.make_spec(**{k: v for k, v in out.items() if k not in ("palette", "layers")})
+    if out["layers"] is not None:
+        R.layer_bits(out["layers"])
+    R.check_palette(out["palette"])
+    return out
+
+
+def _render_call(sim, agents, spec, rgb, device):
+    layers = spec["layers"]
+    if layers is None:
+        layers = ("map", "scan", "cars") + (("track",) if getattr(sim.batch, "tracks", None) else ())
+    kw = {k: v for k, v in spec.items() if k != "layers"}
+    b = sim.batch
+    return (b.render_device if device else b.render)(agents, layers=layers, rgb=rgb, **kw)
+
+
 class F110Env(_EnvBase):
-    metadata = {'render.modes': ['human', 'human_fast']}
+    metadata = {'render.modes': ['human', 'human_fast', 'rgb_array']}
     render_callbacks = []
 
     def __init__(self, **kwargs):
@@ -176,6 +207,7 @@ class F110Env(_EnvBase):
             raise ValueError("reward='progress' needs a track (track=...)")
         self.render_obs = None
         self.current_obs = None
+        self._render_view = dict(RENDER_DEFAULTS)
 
     # attributes user code reads off the reference env
     lap_times = property(lambda self: self._lap.lap_times[0])
@@ -231,9 +263,17 @@ class F110Env(_EnvBase):
     def add_render_callback(self, callback_func):
         F110Env.render_callbacks.append(callback_func)
 
+    def set_render_view(self, **spec):
+        """change what render('rgb_array') draws: width, height, view ('world' / 'follow' / 'ego'), m_per_px, center, angle,
+        fwd_offset, layers (None: every layer that has data), car_size, palette"""
+        self._render_view = _render_spec(self._render_view, spec)
+
     def render(self, mode='human'):
-        assert mode in ['human', 'human_fast']
-        raise NotImplementedError("rendering (pyglet) is outside this build's scope; use obs['poses_*']")
+        """mode='rgb_array': uint8 [H][W][3] of the last observation, drawn on the device with the ego as SELF"""
+        assert mode in self.metadata['render.modes']
+        if mode != 'rgb_array':
+            raise NotImplementedError("the pyglet window is outside this build's scope; use render('rgb_array') for frames")
+        return _render_call(self.sim, [int(self.ego_idx)], self._render_view, True, False)[1][0]
 
 
 class F110VecEnv(object):
@@ -398,6 +438,23 @@ class F110VecEnv(object):
         if self.device_logic:
             v.update(self.sim.batch.episode_device_views())
         return v
+
+    def _ego_agents(self, env_idx):
+        e = np.arange(self.num_envs) if env_idx is None else np.asarray(env_idx, dtype=np.int64).reshape(-1)
+        if e.size < 1 or np.any(e < 0) or np.any(e >= self.num_envs):
+            raise ValueError("env indices must be a non-empty list in [0, %d)" % self.num_envs)
+        return e * self.num_agents + int(self.ego_idx)
+
+    def render(self, env_idx=None, **spec):
+        """host RGB frames uint8 [n][H][W][3] of envs env_idx (None: all), each env's ego the camera agent; spec as
+        F110Env.set_render_view (defaults: F110Env.render's window)"""
+        sp = _render_spec(RENDER_DEFAULTS, spec)
+        return _render_call(self.sim, self._ego_agents(env_idx), sp, True, False)[1]
+
+    def render_device(self, agents=None, **spec):
+        """BatchSim.render_device on this env's simulator: class crops (and RGB with rgb=True) as DLPack-exportable
+        DeviceArrays, one frame per agent of `agents` (global indices env * num_agents + agent; None: every agent)"""
+        return self.sim.batch.render_device(agents, **spec)
 
     def reset(self, poses, env_mask=None, reseat_only=False):
         """env_mask None: every env, then one zero-action step (f110_env.py:319-334).  A partial mask re-seats the masked envs

@@ -227,6 +227,22 @@ class ShardedVecEnv(object):
         ms = [None] * len(self.shards) if env_map is None else self._slices(np.asarray(env_map, dtype=np.int32))
         self._each(lambda k, s: s.set_env_maps(ms[k]))
 
+    def render(self, env_idx=None, **spec):
+        """F110VecEnv.render over the shards: global env indices (None: all) -> host RGB [n][H][W][3] in the order given"""
+        e = np.arange(self.num_envs) if env_idx is None else np.asarray(env_idx, dtype=np.int64).reshape(-1)
+        if e.size < 1 or np.any(e < 0) or np.any(e >= self.num_envs):
+            raise ValueError("env indices must be a non-empty list in [0, %d)" % self.num_envs)
+        bounds = np.asarray(self.bounds)
+        shard = np.searchsorted(bounds, e, side="right") - 1
+        out = None
+        for k in np.unique(shard):
+            sel = np.nonzero(shard == k)[0]
+            frames = self.shards[k].render(e[sel] - bounds[k], **spec)
+            if out is None:
+                out = np.empty((e.size,) + frames.shape[1:], dtype=frames.dtype)
+            out[sel] = frames
+        return out
+
     def device_views(self):
         """per shard: F110VecEnv.device_views() (device-resident observation of that shard's envs, on its GPU)"""
         return self._each(lambda k, s: s.device_views())

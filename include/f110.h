@@ -582,6 +582,35 @@ int f110_track_host_block(f110_sim *h, const f110_track_host *pinned);
 /* unit form: h_poses [m][3] on the track of `slot`; h_out [m][5] = s, lateral, heading_error, segment, t */
 int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, int32_t m, double *h_out);
 
+/* ---- rendering (rendering.py draws with pyglet: map points, one quad per car, a label; this is its rgb_array form) ----
+ * A render makes F frames of H x W pixels, one uint8 class per pixel (the highest that applies wins):
+ *   0 OUTSIDE  the pixel centre is outside env e's map (xy_2_rc's bounds test)   1 FREE  inside, dt != 0
+ *   2 WALL     inside, dt == 0 (the lidar's obstacles)                             3 TRACK a point of the slot's track (f110_track_set)
+ *   4 SCAN     a lidar hit (range < max_range) of the camera agent                  5 CAR   inside another agent's box of env e
+ *   6 SELF     inside the camera agent's box
+ * Each frame has a camera agent n (global index) of env e = n / A.  Poses are Simulator.agent_poses (the observation's), scans the
+ * last step's.  Pixel (i, j), row 0 at the top: u = ((j + 0.5) - W/2) m_per_px, v = (H/2 - (i + 0.5)) m_per_px,
+ * x = cx + (u cos(phi) - v sin(phi)), y = cy + (u sin(phi) + v cos(phi)), all float64.  WORLD: (cx, cy, phi) = (center_x, center_y,
+ * angle); FOLLOW: the camera agent's pose plus fwd_offset along its heading, phi = 0; EGO: the same centre, phi = theta - pi/2.
+ * Boxes are get_vertices' (collision_models.py:218-260) with the agent's own length / width, or car_length / car_width when both
+ * are > 0.  An agent with a non-finite pose is not drawn; a FOLLOW / EGO frame on one is all OUTSIDE.  A layer that is off adds
+ * none of its classes (MAP off: FREE wherever nothing else is drawn).  A render changes no simulator state. */
+enum { F110_VIEW_WORLD = 0, F110_VIEW_FOLLOW = 1, F110_VIEW_EGO = 2 };
+enum { F110_LAYER_MAP = 1, F110_LAYER_TRACK = 2, F110_LAYER_SCAN = 4, F110_LAYER_CARS = 8, F110_LAYER_ALL = 15 };
+enum { F110_CLASS_OUTSIDE = 0, F110_CLASS_FREE = 1, F110_CLASS_WALL = 2, F110_CLASS_TRACK = 3, F110_CLASS_SCAN = 4, F110_CLASS_CAR = 5,
+       F110_CLASS_SELF = 6, F110_NCLASSES = 7 };
+typedef struct f110_render_spec {
+    int32_t width, height, view /* F110_VIEW_WORLD / _FOLLOW / _EGO */, layers /* F110_LAYER_* bits */;
+    double m_per_px, center_x, center_y, angle /* WORLD only */, fwd_offset, car_length, car_width /* <= 0: params */;
+} f110_render_spec;
+/* F frames into d_classes [F][H][W] (required) and, if d_rgb != NULL, d_rgb [F][H][W][3] = palette[class]
+ * (h_palette [7][3] or NULL = default).  h_agents [F] camera agents, or NULL with n_frames == N (frame f = agent f).
+ * Asynchronous on the handle's stream, behind both env blocks of the last step; the next step waits for it.
+ * Refused (F110_ERR_INVALID, nothing launched or written): W or H outside 1..4096, m_per_px not finite and > 0, an unknown view
+ * or layer bit, an agent outside [0, N), n_frames < 1 (or != N without h_agents), F*H*W > 2^31. */
+int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t *h_agents, int32_t n_frames,
+                       uint8_t *d_classes, uint8_t *d_rgb, const uint8_t *h_palette);
+
 #ifdef __cplusplus
 }
 #endif
