@@ -53,6 +53,12 @@ class EpisodeHost(C.Structure):
                 ("near_starts", _u8p), ("done", _u8p), ("checkpoint_done", _u8p)]
 
 
+class ResetSamplerSpec(C.Structure):
+    """struct f110_reset_sampler"""
+    _fields_ = [("s_lo", C.c_double), ("s_hi", C.c_double), ("gap", C.c_double), ("lateral", C.c_double),
+                ("heading", C.c_double), ("clearance", C.c_double), ("attempts", C.c_int32), ("pad", C.c_int32)]
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -187,6 +193,13 @@ PROTOTYPES = {
     "f110_track_host_block": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
     "f110_track_project_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp]),
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
+    "f110_pcg64_seed_spawn": (C.c_int, [_u32p, C.c_int32, C.c_uint64, C.c_int32, _u64p]),
+    "f110_reset_sampler_set": (C.c_int, [C.c_void_p, C.c_void_p, _u64p]),
+    "f110_reset_sample": (C.c_int, [C.c_void_p, _u8p]),
+    "f110_reset_sample_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "f110_reset_sampler_stats": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_int32]),
+    "f110_reset_sampler_poses": (C.c_int, [C.c_void_p, _dp]),
+    "f110_episode_start_views": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "f110_edt_sq": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, _u32p]),
     "f110_beam_dir_index_batch": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i32p]),
     "f110_dt_from_bitmap": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, C.c_double, _dp]),

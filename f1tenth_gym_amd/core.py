@@ -208,7 +208,7 @@ STATE_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("k", "<i4"), ("A"
                          ("reserved", "<u8", (19,))])
 assert STATE_HEADER.itemsize == _ffi.STATE_HEADER_BYTES
 STATE_MAGIC = b"F110SNAP"
-STATE_COLUMNS = {"agent": 1, "scans": 2, "rng": 4, "rng_seed": 8, "episode": 16, "params": 32, "env_map": 64}
+STATE_COLUMNS = {"agent": 1, "scans": 2, "rng": 4, "rng_seed": 8, "episode": 16, "params": 32, "env_map": 64, "reset_rng": 128}
 NOISE_MODES = ("off", "table", "shared_rng", "per_agent_rng")
 
 
@@ -754,13 +754,16 @@ class BatchSim(object):
     def episode_device_views(self):
         v = _ffi.EpisodeViews()
         check(_ffi.lib().f110_episode_device_views(self._h, C.byref(v)), self._h)
+        sp, sr = C.c_void_p(), C.c_void_p()
+        check(_ffi.lib().f110_episode_start_views(self._h, C.byref(sp), C.byref(sr)), self._h)
         N, E = self.N, self.E
         return {"done": DeviceArray(self, (E,), np.uint8, v.done),
                 "checkpoint_done": DeviceArray(self, (N,), np.uint8, v.checkpoint_done),
                 "lap_times": DeviceArray(self, (N,), np.float64, v.lap_times),
                 "lap_counts": DeviceArray(self, (N,), np.float64, v.lap_counts),
                 "toggles": DeviceArray(self, (N,), np.float64, v.toggles),
-                "current_time": DeviceArray(self, (E,), np.float64, v.current_time)}
+                "current_time": DeviceArray(self, (E,), np.float64, v.current_time),
+                "start_poses": DeviceArray(self, (N, 3), np.float64, sp.value), "start_rot": DeviceArray(self, (E, 4), np.float64, sr.value)}
 
     def device_mem_info(self):
         """(free, total) bytes of the handle's GPU"""
@@ -922,6 +925,61 @@ class BatchSim(object):
         if kd:
             self._state_call(_ffi.lib().f110_clone_envs_device(self._h, sp, dp, kd, self._status_ptr(d_status)))
         del skeep, dkeep
+
+    # ------------------------------------------------------------------ randomised start poses
+    def set_reset_sampler(self, seed, s_range=(0.0, 1.0), gap=1.0, lateral=0.0, heading=0.0, clearance=None, attempts=16,
+                          env_base=0):
+        """arm the start-pose sampler: every explicit sample_reset and every in-step re-seat then draws the env's start poses on
+        its slot's track (f110_reset_sampler_set).  seed: a ResetSampler (its settings win) or anything SeedSequence takes; env
+        e draws from PCG64(SeedSequence(seed, spawn_key=(env_base + e,))).  clearance None: half the car's diagonal.
+        Returns the ResetSampler."""
+        from .reset_sampler import ResetSampler
+        rs = seed if isinstance(seed, ResetSampler) else ResetSampler(seed, s_range, gap, lateral, heading, clearance, attempts)
+        if int(env_base) < 0:
+            raise ValueError("env_base must be >= 0, got %d" % int(env_base))
+        words = np.ascontiguousarray(rs.streams(self.E, int(env_base)), dtype=np.uint64)
+        spec = rs.spec(float(self.params['length']), float(self.params['width']))
+        check(_ffi.lib().f110_reset_sampler_set(self._h, C.byref(spec), words.ctypes.data_as(_ffi._u64p)), self._h)
+        self.reset_sampler = rs
+        return rs
+
+    def clear_reset_sampler(self):
+        check(_ffi.lib().f110_reset_sampler_set(self._h, None, None), self._h)
+        self.reset_sampler = None
+
+    reset_sampler = None
+
+    def sample_reset(self, env_mask=None):
+        """explicit draw for the envs of env_mask (None: all): f110_reset (and the episode reset) to the drawn poses"""
+        mptr, m = None, None
+        if env_mask is not None:
+            m = np.ascontiguousarray(env_mask, dtype=np.uint8)
+            if m.shape != (self.E,):
+                raise ValueError("env_mask must have num_envs=%d entries" % self.E)
+            mptr = m.ctypes.data_as(_ffi._u8p)
+        check(_ffi.lib().f110_reset_sample(self._h, mptr), self._h)
+
+    def sample_reset_device(self, d_mask=None):
+        ptr = None if d_mask is None else (d_mask.ptr if isinstance(d_mask, DeviceArray) else int(d_mask))
+        check(_ffi.lib().f110_reset_sample_device(self._h, ptr), self._h)
+
+    def reset_sampler_stats(self, clear=False, attempts=False):
+        """{'draws', 'fallbacks'} since the last clear; attempts=True adds 'attempt' [E] (winning attempt of each env's last
+        draw, -1 = fallback / none)"""
+        v = (C.c_uint64 * 2)()
+        att = np.empty((self.E,), dtype=np.int32) if attempts else None
+        check(_ffi.lib().f110_reset_sampler_stats(self._h, v, None if att is None else att.ctypes.data_as(_ffi._i32p),
+                                                  1 if clear else 0), self._h)
+        out = {"draws": int(v[0]), "fallbacks": int(v[1])}
+        if att is not None:
+            out["attempt"] = att
+        return out
+
+    def reset_sampler_poses(self):
+        """[N][3] poses of each env's last reset of any kind (what an explicit fallback resets to; after a draw: the drawn ones)"""
+        out = np.empty((self.N, 3))
+        check(_ffi.lib().f110_reset_sampler_poses(self._h, dptr(out)), self._h)
+        return out
 
     # ------------------------------------------------------------------ timing (bench.py)
     def timer_begin(self):

@@ -221,6 +221,12 @@ struct f110_sim {
     size_t render_agents_cap = 0;
     uint8_t *d_render_stage = nullptr;   // [F][H][pitch] when the caller's buffer cannot take 32-bit stores
     size_t render_stage_cap = 0;
+    // randomised start poses (f110_reset_sampler_*): the settings, each env's stream, the explicit fallback poses, the counters
+    struct ResetSampler {
+        bool on = false;
+        SamplerJob job{};            // settings + device buffers; tracks / maps / mode are filled per launch
+        bool defer = false;          // inside f110_step_host / f110_episode_step*: the caller launches the draw after its last kernel
+    } rs;
     // timing
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool profiling = false;
@@ -301,6 +307,9 @@ static int track_prepare(f110_sim *h);
 static int track_launch(f110_sim *h, hipStream_t st, int mode, int begin, int count);
 static bool tiny_applies(const f110_sim *h);   // (below, with the step)
 static void noise_release(f110_sim *h);        // (below, with the noise entry points)
+static void sampler_release(f110_sim *h);      // (below, with the reset sampler)
+static int sampler_launch(f110_sim *h, hipStream_t st, int mode, int e0, int count, const uint8_t *d_mask, int ego);
+static int sampler_after_step(f110_sim *h, bool grouped);
 
 // RAII scratch for the unit entry points
 struct Scratch {
@@ -871,6 +880,7 @@ void f110_destroy(f110_sim *h)
         if (ge) (void)hipEventDestroy(ge);
     if (h->ev_main) (void)hipEventDestroy(h->ev_main);
     noise_release(h);
+    sampler_release(h);
     if (h->noise_stream) (void)hipStreamDestroy(h->noise_stream);
     if (h->ev_noise) (void)hipEventDestroy(h->ev_noise);
     if (h->ev_noise_src) (void)hipEventDestroy(h->ev_noise_src);
@@ -1455,6 +1465,8 @@ int f110_reset_device(f110_sim *h, const double *d_poses, const uint8_t *d_env_m
     ENTER(h);
     if (!d_env_mask) h->noise_ub = 0;   // every agent's step_count is 0 again
     hipLaunchKernelGGL(k_reset, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, d_poses, d_env_mask);
+    if (h->rs.on)
+        hipLaunchKernelGGL(k_sampler_keep, grid1d(h->N, 256), dim3(256), 0, h->stream, h->rs.job.last, d_poses, d_env_mask, h->N, h->cfg.num_agents);
     HIPCHK(h, hipGetLastError());
     return F110_OK;
 }
@@ -1476,8 +1488,162 @@ int f110_reset_collided_device(f110_sim *h, const double *d_start_poses, int32_t
     if (!h || !d_start_poses) return fail(h, F110_ERR_INVALID, "null argument");
     ENTER(h);
     if (ego_idx < 0 || ego_idx >= h->cfg.num_agents) return fail(h, F110_ERR_INVALID, "Index given is out of bounds for list of agents.");
+    if (h->rs.on) TRY(track_prepare(h));
     hipLaunchKernelGGL(k_reset_collided, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, d_start_poses, ego_idx, d_count);
     HIPCHK(h, hipGetLastError());
+    if (h->rs.on) TRY(sampler_launch(h, h->stream, kSampleCollided, 0, h->cfg.num_envs, nullptr, ego_idx));
+    return F110_OK;
+}
+
+// ---- randomised start poses (f110_reset_sampler_*) ------------------------------------------------------------
+static void sampler_release(f110_sim *h)
+{
+    SamplerJob &j = h->rs.job;
+    void *ptrs[] = {j.stream, j.last, j.cand, j.out_poses, j.out_rot, j.attempt, j.counters};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    j = SamplerJob{};
+    h->rs.on = false;
+}
+
+// one k_reset_sample over envs [e0, e0 + count) on stream st (track_prepare has run)
+static int sampler_launch(f110_sim *h, hipStream_t st, int mode, int e0, int count, const uint8_t *d_mask, int ego)
+{
+    if (count <= 0) return F110_OK;
+    SamplerJob j = h->rs.job;
+    j.tracks = h->d_tracks;
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.maps = h->multi_map ? h->d_maps_full : cold_consts(h);
+    if (!j.maps) return fail(h, F110_ERR_HIP, "f110_reset_sample: constant upload failed");
+    j.mode = mode;
+    j.mask = d_mask;
+    j.ego = ego;
+    hipLaunchKernelGGL(k_reset_sample, grid1d(count, 256), dim3(256), 0, st, j, h->dev, h->ep, h->has_episode ? 1 : 0, e0, count);
+    HIPCHK(h, hipGetLastError());
+    return F110_OK;
+}
+
+// the draw behind a call that may have re-seated envs in-step (its last kernel is on the main stream, or per env block)
+static int sampler_after_step(f110_sim *h, bool grouped)
+{
+    const int E = h->cfg.num_envs;
+    if (!grouped) TRY(sampler_launch(h, h->stream, kSampleMarker, 0, E, nullptr, 0));
+    else {
+        const int per = group_envs(h);
+        for (int g = 0; g < h->groups; ++g) {   // (as f110_step_device's loop: every env block on its own stream)
+            const int e0 = g * per, e1 = std::min(E, e0 + per);
+            if (e0 >= e1) break;
+            TRY(sampler_launch(h, h->gstreams[g], kSampleMarker, e0, e1 - e0, nullptr, 0));
+        }
+    }
+    if (h->last_launches > 0) h->last_launches += 1;   // (the one-launch step is two launches with the draw behind it)
+    return F110_OK;
+}
+
+int f110_pcg64_seed_spawn(const uint32_t *h_entropy, int32_t n_words, uint64_t e0, int32_t n, uint64_t *h_out)
+{
+    if (!h_entropy || !h_out || n_words < 1 || n_words > 1 << 20 || n < 0) return fail(nullptr, F110_ERR_INVALID, "f110_pcg64_seed_spawn: bad argument");
+    for (int32_t q = 0; q < n; ++q) pcg64_seed_spawn(h_entropy, n_words, e0 + (uint64_t)q, h_out + 4 * (size_t)q);
+    return F110_OK;
+}
+
+int f110_reset_sampler_set(f110_sim *h, const f110_reset_sampler *spec, const uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!spec) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        sampler_release(h);
+        return F110_OK;
+    }
+    if (!h_streams) return fail(h, F110_ERR_INVALID, "f110_reset_sampler_set: null stream words");
+    const f110_reset_sampler &c = *spec;
+    if (!(c.s_lo >= 0.0 && c.s_lo < c.s_hi && c.s_hi <= 1.0)) return fail(h, F110_ERR_INVALID, "reset sampler: need 0 <= s_lo < s_hi <= 1, got %g, %g", c.s_lo, c.s_hi);
+    if (!(c.gap > 0.0 && std::isfinite(c.gap))) return fail(h, F110_ERR_INVALID, "reset sampler: gap must be finite and > 0, got %g", c.gap);
+    if (!(c.lateral >= 0.0 && std::isfinite(c.lateral))) return fail(h, F110_ERR_INVALID, "reset sampler: lateral must be finite and >= 0, got %g", c.lateral);
+    if (!(c.heading >= 0.0 && std::isfinite(c.heading))) return fail(h, F110_ERR_INVALID, "reset sampler: heading must be finite and >= 0, got %g", c.heading);
+    if (!(c.clearance >= 0.0 && std::isfinite(c.clearance))) return fail(h, F110_ERR_INVALID, "reset sampler: clearance must be finite and >= 0, got %g", c.clearance);
+    if (c.attempts < 1 || c.attempts > 1024) return fail(h, F110_ERR_INVALID, "reset sampler: attempts must be in 1 .. 1024, got %d", c.attempts);
+    TRY(track_prepare(h));   // every env's slot has a track (F110_ERR_STATE otherwise)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    sampler_release(h);
+    const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
+    SamplerJob &j = h->rs.job;
+    TRY(dmalloc(h, &j.stream, 2 * E));
+    TRY(dmalloc(h, &j.last, 3 * N));
+    TRY(dmalloc(h, &j.cand, 3 * N));
+    TRY(dmalloc(h, &j.out_poses, 3 * N));
+    TRY(dmalloc(h, &j.out_rot, 4 * E));
+    TRY(dmalloc(h, &j.attempt, E));
+    TRY(dmalloc(h, &j.counters, 2));
+    // {state.hi, state.lo, inc.hi, inc.lo} per env is the layout of two U128 {hi, lo}
+    HIPCHK(h, hipMemcpy(j.stream, h_streams, sizeof(U128) * 2 * E, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemset(j.last, 0, sizeof(double) * 3 * N));
+    HIPCHK(h, hipMemset(j.attempt, 0xff, sizeof(int32_t) * E));
+    HIPCHK(h, hipMemset(j.counters, 0, 2 * sizeof(unsigned long long)));
+    j.s_lo = c.s_lo;
+    j.s_hi = c.s_hi;
+    j.gap = c.gap;
+    j.lateral = c.lateral;
+    j.heading = c.heading;
+    j.clearance = c.clearance;
+    j.attempts = c.attempts;
+    j.A = h->cfg.num_agents;
+    h->rs.on = true;
+    return F110_OK;
+}
+
+int f110_reset_sample_device(f110_sim *h, const uint8_t *d_env_mask)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!h->rs.on) return fail(h, F110_ERR_STATE, "f110_reset_sample: no reset sampler is armed (f110_reset_sampler_set)");
+    TRY(track_prepare(h));
+    const SamplerJob &j = h->rs.job;
+    TRY(sampler_launch(h, h->stream, kSampleExplicit, 0, h->cfg.num_envs, d_env_mask, 0));
+    if (!d_env_mask) h->noise_ub = 0;
+    if (h->has_episode)
+        hipLaunchKernelGGL(k_episode_reset, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, h->ep, j.out_poses, j.out_rot, d_env_mask);
+    hipLaunchKernelGGL(k_reset, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, j.out_poses, d_env_mask);
+    HIPCHK(h, hipGetLastError());
+    return F110_OK;
+}
+
+int f110_reset_sample(f110_sim *h, const uint8_t *h_env_mask)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (h_env_mask) HIPCHK(h, hipMemcpyAsync(h->d_mask, h_env_mask, (size_t)h->cfg.num_envs, hipMemcpyHostToDevice, h->stream));
+    TRY(f110_reset_sample_device(h, h_env_mask ? h->d_mask : nullptr));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // the host mask is consumed on return
+    return F110_OK;
+}
+
+int f110_reset_sampler_stats(f110_sim *h, uint64_t *out2, int32_t *h_attempt, int32_t clear)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!h->rs.on) return fail(h, F110_ERR_STATE, "no reset sampler is armed (f110_reset_sampler_set)");
+    const SamplerJob &j = h->rs.job;
+    unsigned long long v[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(v, j.counters, sizeof v, hipMemcpyDeviceToHost, h->stream));
+    if (h_attempt) HIPCHK(h, hipMemcpyAsync(h_attempt, j.attempt, sizeof(int32_t) * h->cfg.num_envs, hipMemcpyDeviceToHost, h->stream));
+    if (clear) HIPCHK(h, hipMemsetAsync(j.counters, 0, sizeof v, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (out2) {
+        out2[0] = v[0];
+        out2[1] = v[1];
+    }
+    return F110_OK;
+}
+
+int f110_reset_sampler_poses(f110_sim *h, double *h_poses)
+{
+    if (!h || !h_poses) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    if (!h->rs.on) return fail(h, F110_ERR_STATE, "no reset sampler is armed (f110_reset_sampler_set)");
+    HIPCHK(h, hipMemcpyAsync(h_poses, h->rs.job.last, sizeof(double) * 3 * h->N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }
 
@@ -1782,6 +1948,8 @@ int f110_episode_reset(f110_sim *h, const double *poses, const double *rot, cons
     if (!dm) h->noise_ub = 0;
     hipLaunchKernelGGL(k_episode_reset, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, h->ep, h->d_poses, h->d_rot_stage, dm);
     hipLaunchKernelGGL(k_reset, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, h->d_poses, dm);
+    if (h->rs.on)
+        hipLaunchKernelGGL(k_sampler_keep, grid1d(h->N, 256), dim3(256), 0, h->stream, h->rs.job.last, h->d_poses, dm, h->N, h->cfg.num_agents);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
@@ -1791,7 +1959,11 @@ int f110_episode_step_device(f110_sim *h, const double *d_actions)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     if (!h->has_episode) return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
-    TRY(f110_step_device(h, d_actions));
+    h->rs.defer = true;
+    const int rc_step = f110_step_device(h, d_actions);
+    h->rs.defer = false;
+    if (rc_step != F110_OK) return rc_step;
+    const bool draw = h->rs.on && h->dev.reseat_poses;
     if (h->last_blocks == 2 && h->groups_busy) {
         // the step went out as two env blocks: each block's _check_done behind it on the block's own stream (an env's
         // lap bookkeeping reads that env's agents only), no join — the device-resident loop stays two independent halves
@@ -1802,11 +1974,13 @@ int f110_episode_step_device(f110_sim *h, const double *d_actions)
             hipLaunchKernelGGL(k_episode, grid1d(e1 - e0, 256), dim3(256), 0, h->gstreams[g], h->dev, h->ep, e1 - e0, e0);
         }
         HIPCHK(h, hipGetLastError());
+        if (draw) TRY(sampler_after_step(h, true));
         return F110_OK;
     }
     ENTER(h);   // _check_done reads every group's poses and flags
     hipLaunchKernelGGL(k_episode, grid1d(h->cfg.num_envs, 256), dim3(256), 0, h->stream, h->dev, h->ep, h->cfg.num_envs);
     HIPCHK(h, hipGetLastError());
+    if (draw) TRY(sampler_after_step(h, false));
     h->touched = false;   // the next step may split: what this call left on the main stream is forked from (main_dirty)
     return F110_OK;
 }
@@ -1815,6 +1989,10 @@ int f110_episode_reset_done_device(f110_sim *h, int32_t *d_count)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     if (!h->has_episode) return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
+    if (h->rs.on && (h->tracks_dirty || !h->track_checked)) {   // (the slot table is current behind any step of an armed sampler)
+        HIPCHK(h, hipSetDevice(h->cfg.device_id));
+        TRY(track_prepare(h));
+    }
     if (h->last_blocks == 2 && h->groups_busy && !h->touched) {   // behind a two-block f110_episode_step_device: per block, no join
         HIPCHK(h, hipSetDevice(h->cfg.device_id));
         const int per = group_envs(h), E = h->cfg.num_envs, A = h->cfg.num_agents;
@@ -1822,6 +2000,7 @@ int f110_episode_reset_done_device(f110_sim *h, int32_t *d_count)
             const int e0 = g * per, e1 = std::min(E, e0 + per);
             if (e0 >= e1) break;
             hipLaunchKernelGGL(k_episode_reset_done, grid1d((e1 - e0) * A, 256), dim3(256), 0, h->gstreams[g], h->dev, h->ep, d_count, e0 * A, (e1 - e0) * A);
+            if (h->rs.on) TRY(sampler_launch(h, h->gstreams[g], kSampleDone, e0, e1 - e0, nullptr, 0));   // (done[] is still set)
             hipLaunchKernelGGL(k_episode_clear_done, grid1d(e1 - e0, 256), dim3(256), 0, h->gstreams[g], h->ep, e1 - e0, e0);
         }
         HIPCHK(h, hipGetLastError());
@@ -1829,6 +2008,7 @@ int f110_episode_reset_done_device(f110_sim *h, int32_t *d_count)
     }
     ENTER(h);
     hipLaunchKernelGGL(k_episode_reset_done, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, h->ep, d_count);
+    if (h->rs.on) TRY(sampler_launch(h, h->stream, kSampleDone, 0, h->cfg.num_envs, nullptr, 0));
     hipLaunchKernelGGL(k_episode_clear_done, grid1d(h->cfg.num_envs, 256), dim3(256), 0, h->stream, h->ep, h->cfg.num_envs);
     HIPCHK(h, hipGetLastError());
     h->touched = false;   // (as in f110_episode_step_device: the loop step / reset_done / step / ... may split from its second round on)
@@ -1912,7 +2092,10 @@ int f110_episode_step_host(f110_sim *h, const double *h_actions, int32_t auto_re
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs, bytes = f110_episode_packed_bytes(h);
     if (!h->d_packed) HIPCHK(h, hipMalloc(&h->d_packed, bytes));
     HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
-    TRY(f110_step_device(h, h->d_actions));
+    h->rs.defer = true;
+    const int rc_step = f110_step_device(h, h->d_actions);
+    h->rs.defer = false;
+    if (rc_step != F110_OK) return rc_step;
     ENTER(h);
     hipLaunchKernelGGL(k_episode, grid1d(E, 256), dim3(256), 0, h->stream, h->dev, h->ep, (int)E);
     double *cols = reinterpret_cast<double *>(h->d_packed);
@@ -1924,6 +2107,7 @@ int f110_episode_step_host(f110_sim *h, const double *h_actions, int32_t auto_re
         hipLaunchKernelGGL(k_episode_clear_done, grid1d(E, 256), dim3(256), 0, h->stream, h->ep, (int)E);
     }
     HIPCHK(h, hipGetLastError());
+    if (h->rs.on && (auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, false));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }
@@ -2062,7 +2246,9 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     h->fuse_request = want_fuse;
     h->fuse_seq = spin ? hbk.seq : 0;
     h->fused_done = false;
+    h->rs.defer = true;
     const int rc_step = f110_step_device(h, d_act);
+    h->rs.defer = false;
     h->fuse_request = false;
     h->tiny_request = h->tiny_host_request = false;
     h->tiny_actions_host = nullptr;
@@ -2076,6 +2262,9 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     // the scans are contiguous in HBM already: a DMA copy, behind the kernel (the re-seat leaves scans alone)
     if (out->scans && !h->hb_scans_by_kernel) HIPCHK(h, hipMemcpyAsync(out->scans, h->dev.scans, sizeof(double) * N * (size_t)h->cfg.num_beams, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipGetLastError());
+    // a re-seat inside this call (auto reset, or an armed f110_set_auto_reseat): the draw, behind the block (which keeps the
+    // terminal observation), stream-ordered in front of the next step
+    if (h->rs.on && ((flags & F110_STEP_AUTO_RESET) || h->dev.reseat_poses)) TRY(sampler_after_step(h, false));
     const auto t_enq = std::chrono::steady_clock::now();
     if (spin) {
         // poll the completion word the last workgroup stores (no runtime call on the way out); a kernel that
@@ -2170,6 +2359,16 @@ int f110_episode_device_views(f110_sim *h, f110_episode_views *v)
     v->lap_counts = h->ep.lap_count;
     v->toggles = h->ep.toggle;
     v->current_time = h->ep.current_time;
+    return F110_OK;
+}
+
+int f110_episode_start_views(f110_sim *h, double **d_start_poses, double **d_start_rot)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!h->has_episode) return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
+    if (d_start_poses) *d_start_poses = h->ep.start_poses;
+    if (d_start_rot) *d_start_rot = h->ep.rot;
     return F110_OK;
 }
 
@@ -2711,7 +2910,7 @@ int f110_step_device(f110_sim *h, const double *d_actions)
     if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
     if (!h->beams_uniform) return fail(h, F110_ERR_STATE, kBeamsMsg);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    if (h->track_on) TRY(track_prepare(h));
+    if (h->track_on || h->rs.on) TRY(track_prepare(h));
     const int N = h->N, A = h->cfg.num_agents;
     h->dev.path_stats = h->path_stats_on ? h->d_path_stats : nullptr;
     if (h->comm_overlap && h->comm_swap_next) {
@@ -2784,6 +2983,9 @@ int f110_step_device(f110_sim *h, const double *d_actions)
         }
         h->groups_busy = true;
     }
+    // an in-step re-seat armed (f110_set_auto_reseat): the draw for the envs it re-seated, behind the step (per env block);
+    // f110_step_host / f110_episode_step* launch it after their own last kernel instead
+    if (h->rs.on && h->dev.reseat_poses && !h->rs.defer) TRY(sampler_after_step(h, grouped));
     h->touched = false;
     h->last_blocks = grouped ? h->groups : 1;
     h->noise_ub += 1;
@@ -2888,18 +3090,28 @@ static uint32_t state_col_set(const f110_sim *h)
     if (h->has_episode) c |= F110_STATE_COL_EPISODE;
     if (h->dev.params_per_agent) c |= F110_STATE_COL_PARAMS;
     if (h->multi_map) c |= F110_STATE_COL_ENV_MAP;
+    if (h->rs.on) c |= F110_STATE_COL_RESET_RNG;
     return c;
 }
 
 // the column table of a blob of k envs with column set `cols` (fixed order: the layout depends on cols, k, A and B only);
 // returns the blob's total bytes
+// the most columns state_columns adds: the agent core 17, noise 2, episode 9, params 1, env map 1, reset sampler 2, scans 1
+constexpr int kStateColsUsed = 17 + 2 + 9 + 1 + 1 + 2 + 1;
+static_assert(kStateColsUsed <= kStateMaxCols, "StateCols::c cannot hold every column state_columns may add");
+
 static size_t state_columns(const f110_sim *h, uint32_t cols, int k, StateCols *out)
 {
     StateCols t{};
     const size_t N = (size_t)h->N;
     const uint32_t A = (uint32_t)h->cfg.num_agents, B = (uint32_t)h->cfg.num_beams;
     size_t off = F110_STATE_HEADER_BYTES;
+    bool overflow = false;
     auto add = [&](void *live, uint32_t bytes, uint32_t per_env, uint32_t kind = 0) {
+        if (t.n >= kStateMaxCols) {   // (kStateColsUsed rules this out; never index past the table)
+            overflow = true;
+            return;
+        }
         StateCol &c = t.c[t.n++];
         c.live = static_cast<char *>(live);
         c.bytes = bytes;
@@ -2932,13 +3144,18 @@ static size_t state_columns(const f110_sim *h, uint32_t cols, int k, StateCols *
     }
     if (cols & F110_STATE_COL_PARAMS) add(h->d_params_all, NPARAMS * 8, A);
     if (cols & F110_STATE_COL_ENV_MAP) add(h->d_env_map, 4, 1);
+    if (cols & F110_STATE_COL_RESET_RNG) {
+        add(h->rs.job.stream, 2 * sizeof(U128), 1);   // the env's sampler stream {state, inc}
+        add(h->rs.job.last, 24, A);                   // ... and its explicit-draw fallback poses
+    }
     if (cols & F110_STATE_COL_SCANS) add(h->dev.scans, B * 8, A);   // last: launched on its own (state_launch)
     t.num_envs = h->cfg.num_envs;
     t.step_count = h->dev.step_count;
     t.rowstate = h->d_rng_rowstate;
     t.noise_rows = h->dev.noise_rows;
+    if (overflow) t.n = -1;   // state_launch refuses the table
     if (out) *out = t;
-    return off;
+    return overflow ? 0 : off;
 }
 
 enum StateDir { STATE_PACK, STATE_UNPACK, STATE_CLONE };
@@ -2948,6 +3165,7 @@ enum StateDir { STATE_PACK, STATE_UNPACK, STATE_CLONE };
 static int state_launch(f110_sim *h, StateDir dir, const StateCols &all, const StateHeader *hdr, char *blob, int blob_k,
                         const int32_t *src, const int32_t *dst, int k, int32_t *status)
 {
+    if (all.n < 1 || all.n > kStateMaxCols) return fail(h, F110_ERR_STATE, "state columns: %d columns do not fit the column table", all.n);
     if (k <= 0) return F110_OK;
     StateCols parts[2] = {all, all};
     parts[0].n = 0;
@@ -3013,6 +3231,7 @@ static const char *state_col_name(uint32_t bit)
     case F110_STATE_COL_EPISODE: return "episode (f110_episode_init)";
     case F110_STATE_COL_PARAMS: return "per-agent params (f110_set_params_batch)";
     case F110_STATE_COL_ENV_MAP: return "env map slots (f110_set_env_maps)";
+    case F110_STATE_COL_RESET_RNG: return "reset sampler (f110_reset_sampler_set)";
     default: return "agent";
     }
 }
@@ -3037,13 +3256,13 @@ static int state_check(f110_sim *h, const StateHeader &hd)
     if (mb >= 2 && hd.std_dev != h->noise_gen.scale)
         return fail(h, F110_ERR_STATE, "state blob saved with noise std_dev %g, this handle has %g", hd.std_dev, h->noise_gen.scale);
     const uint32_t want = state_col_set(h), have = hd.cols & ~(uint32_t)F110_STATE_COL_SCANS;
-    for (uint32_t bit = F110_STATE_COL_RNG; bit <= F110_STATE_COL_ENV_MAP; bit <<= 1) {
+    for (uint32_t bit = F110_STATE_COL_RNG; bit <= F110_STATE_COL_RESET_RNG; bit <<= 1) {
         if ((have & bit) && !(want & bit))
             return fail(h, F110_ERR_STATE, "state blob holds %s columns, which are not active on this handle", state_col_name(bit));
         if (!(have & bit) && (want & bit))
             return fail(h, F110_ERR_STATE, "state blob has no %s columns, which are active on this handle", state_col_name(bit));
     }
-    if (!(have & F110_STATE_COL_AGENT) || (hd.cols & ~0x7fu)) return fail(h, F110_ERR_STATE, "state blob with an unknown column set 0x%x", hd.cols);
+    if (!(have & F110_STATE_COL_AGENT) || (hd.cols & ~0xffu)) return fail(h, F110_ERR_STATE, "state blob with an unknown column set 0x%x", hd.cols);
     if ((hd.cols & F110_STATE_COL_SCANS) != ((hd.flags & F110_STATE_SCANS) ? (uint32_t)F110_STATE_COL_SCANS : 0u))
         return fail(h, F110_ERR_STATE, "state blob header is inconsistent (flags / columns)");
     if ((have & F110_STATE_COL_ENV_MAP) && hd.n_maps > 1 + (int)h->extra_maps.size())

@@ -3444,7 +3444,7 @@ __global__ void __launch_bounds__(256) k_track_project(TrackJob j)
 // live + i * bytes.  In a blob each column is one section [k * per_env][bytes] starting at `off`, so the threads of a wave move
 // consecutive items (or consecutive 16-byte words of one wide item, the scans) — coalesced on both sides.  One routine serves
 // the three directions: live env -> blob entry (pack), blob entry -> live env (unpack), live env -> live env (clone).
-constexpr int kStateMaxCols = 32;
+constexpr int kStateMaxCols = 40;   // (StateCols is a kernel argument: 40 x 32 bytes; state_columns uses at most 33)
 constexpr uint32_t kStateColRngShared = 1;   // rng_state in the shared-stream mode (see k_state_pack)
 struct StateCol {
     char *live;
@@ -3795,4 +3795,163 @@ __global__ void __launch_bounds__(256) k_render_occ(const double *__restrict__ t
     const size_t r = q / (size_t)W, c = q - r * (size_t)W;
     const double d = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(table) + r * (size_t)row_bytes + c * 8);
     occ[q] = d == 0.0 ? 1 : 0;
+}
+
+// ---- randomised start poses (f110_reset_sampler_*) -----------------------------------------------------------
+// One lane per env.  Env e owns the PCG64 stream {state, inc} = stream[2e], stream[2e + 1]; a uniform is NumPy's
+// Generator.random() (pcg_to_double of the next output).  An attempt draws s0 = L (s_lo + u (s_hi - s_lo)) and, per agent j,
+// (u_l, u_h): agent j sits j gap behind s0, d = lateral (2 u_l - 1) to the left of its segment, heading jitter h = heading (2 u_h - 1).
+// The candidate poses are staged in cand [N][3]; the attempt is valid when every agent is on the track (open: s >= 0), in
+// bounds of its slot's table with dt >= clearance, and every pair of agents is 2 clearance apart.  Which envs draw is the mode:
+enum SampleMode {
+    kSampleExplicit = 0,   // f110_reset_sample: envs of `mask` (nullptr: all); the result goes to out_poses / out_rot for k_reset
+    kSampleMarker = 1,     // behind a step that re-seats: envs whose first agent has step_count 0 (only a re-seat sets it there)
+    kSampleCollided = 2,   // behind f110_reset_collided_device: envs whose ego (`ego`) has collisions != 0
+    kSampleDone = 3        // behind k_episode_reset_done: envs whose done flag is still set
+};
+struct SamplerJob {
+    const TrackDesc *tracks;   // [slots] (f110_track_set)
+    const int32_t *env_map;    // [E] or nullptr (slot 0)
+    const ScanConst *maps;     // [slots] with env_map, else [1]
+    U128 *stream;              // [E][2] {state, inc}
+    double *last;              // [N][3] poses of the env's last reset (host or drawn): the explicit fallback
+    double *cand;              // [N][3] scratch
+    double *out_poses;         // [N][3] explicit: what the reset gets
+    double *out_rot;           // [E][4] explicit: start_rot of the ego's pose
+    int32_t *attempt;          // [E] winning attempt of the env's last draw, -1 = fallback
+    unsigned long long *counters;   // [2] draws, fallbacks
+    const uint8_t *mask;       // kSampleExplicit: [E] or nullptr
+    double s_lo, s_hi, gap, lateral, heading, clearance;
+    int32_t attempts, A, ego, mode;
+};
+
+__device__ __forceinline__ double sampler_uniform(U128 &st, U128 inc)
+{
+    st = pcg_step(st, inc);
+    return pcg_to_double(pcg_output(st));
+}
+
+// start_rot (f110_env.py:331) of heading theta, row-major
+__device__ __forceinline__ void sampler_rot(double theta, double *r)
+{
+    const double c = cos(-theta), s = sin(-theta);
+    r[0] = c;
+    r[1] = -s;
+    r[2] = s;
+    r[3] = c;
+}
+
+// envs [e0, e0 + count)
+__global__ void __launch_bounds__(256) k_reset_sample(SamplerJob j, AgentArrays a, EpisodeArrays ep, int has_ep, int e0, int count)
+{
+    const int e = e0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int N = a.n_agents_total, A = j.A;
+    const bool live = e < e0 + count;
+    bool drew = false, fell = false;
+    if (live) {
+        const int i0 = e * A;
+        if (j.mode == kSampleExplicit) drew = !j.mask || j.mask[e];
+        else if (j.mode == kSampleMarker) drew = a.step_count[i0] == 0;
+        else if (j.mode == kSampleCollided) drew = a.collisions[i0 + j.ego] != 0.0;
+        else drew = ep.done[e] != 0;
+    }
+    if (drew) {
+        const int i0 = e * A;
+        const int slot = j.env_map ? j.env_map[e] : 0;
+        const TrackDesc td = j.tracks[slot];
+        const ScanConst &k = j.maps[j.env_map ? slot : 0];
+        const int nseg = td.nseg;
+        const double *ax = td.cols + (size_t)kTrkAx * nseg, *ay = td.cols + (size_t)kTrkAy * nseg;
+        const double *dxs = td.cols + (size_t)kTrkDx * nseg, *dys = td.cols + (size_t)kTrkDy * nseg;
+        const double *len = td.cols + (size_t)kTrkLen * nseg, *cum = td.cols + (size_t)kTrkCum * nseg;
+        const double L = td.L, need2 = (2.0 * j.clearance) * (2.0 * j.clearance);
+        U128 st = j.stream[2 * (size_t)e];
+        const U128 inc = j.stream[2 * (size_t)e + 1];
+        int won = -1;
+        for (int att = 0; att < j.attempts && won < 0; ++att) {
+            const double s0 = L * (j.s_lo + sampler_uniform(st, inc) * (j.s_hi - j.s_lo));
+            bool ok = true;
+            for (int q = 0; q < A; ++q) {
+                double s = s0 - (double)q * j.gap;
+                if (td.closed) {
+                    s = fmod(s, L);
+                    if (s < 0.0) s += L;
+                }
+                const double ul = sampler_uniform(st, inc), uh = sampler_uniform(st, inc);
+                const double d = j.lateral * (2.0 * ul - 1.0), hj = j.heading * (2.0 * uh - 1.0);
+                int lo = 0, hi = nseg - 1;   // the last segment with cum[k] <= s (0 when none)
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (cum[mid] <= s) lo = mid;
+                    else hi = mid - 1;
+                }
+                const int sk = lo;
+                double t = (s - cum[sk]) / len[sk];
+                t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+                const double sdx = dxs[sk], sdy = dys[sk], sl = len[sk];
+                const double x = (ax[sk] + t * sdx) + d * (-sdy / sl);
+                const double y = (ay[sk] + t * sdy) + d * (sdx / sl);
+                const double th = atan2(sdy, sdx) + hj;
+                const size_t i = (size_t)i0 + q;
+                j.cand[3 * i] = x;
+                j.cand[3 * i + 1] = y;
+                j.cand[3 * i + 2] = th;
+                int r, c;
+                const double dist = sample_distance<LAYOUT_ROWMAJOR, false, false>(k, nullptr, x, y, r, c);
+                ok = ok && (td.closed || s >= 0.0) && r >= 0 && dist >= j.clearance;
+            }
+            for (int p = 0; p < A && ok; ++p)
+                for (int q = p + 1; q < A && ok; ++q) {
+                    const size_t ip = (size_t)i0 + p, iq = (size_t)i0 + q;
+                    const double ddx = j.cand[3 * ip] - j.cand[3 * iq], ddy = j.cand[3 * ip + 1] - j.cand[3 * iq + 1];
+                    ok = ddx * ddx + ddy * ddy >= need2;
+                }
+            if (ok) won = att;
+        }
+        j.stream[2 * (size_t)e] = st;
+        j.attempt[e] = won;
+        fell = won < 0;
+        if (j.mode == kSampleExplicit) {
+            // the reset gets the drawn poses, or (fallback) the poses of the env's last reset
+            const double *src = fell ? j.last : j.cand;
+            for (int q = 0; q < A; ++q) {
+                const size_t i = (size_t)i0 + q;
+                for (int c = 0; c < 3; ++c) j.out_poses[3 * i + c] = src[3 * i + c];
+                if (!fell)
+                    for (int c = 0; c < 3; ++c) j.last[3 * i + c] = j.cand[3 * i + c];
+            }
+            sampler_rot(src[3 * ((size_t)i0 + ep.ego_idx) + 2], j.out_rot + 4 * (size_t)e);
+        } else if (!fell) {
+            // the re-seat already zeroed the state: its pose columns become the drawn poses
+            for (int q = 0; q < A; ++q) {
+                const size_t i = (size_t)i0 + q;
+                const double x = j.cand[3 * i], y = j.cand[3 * i + 1], th = j.cand[3 * i + 2];
+                a.state[i] = x;
+                a.state[(size_t)N + i] = y;
+                a.state[4 * (size_t)N + i] = th;
+                j.last[3 * i] = x;
+                j.last[3 * i + 1] = y;
+                j.last[3 * i + 2] = th;
+                if (has_ep) {
+                    ep.start_poses[3 * i] = x;
+                    ep.start_poses[3 * i + 1] = y;
+                    ep.start_poses[3 * i + 2] = th;
+                }
+            }
+            if (has_ep) sampler_rot(j.cand[3 * ((size_t)i0 + ep.ego_idx) + 2], ep.rot + 4 * (size_t)e);
+        }
+    }
+    const unsigned long long bd = __ballot(drew), bf = __ballot(fell);
+    if ((threadIdx.x & 63u) == 0u && bd) {
+        atomicAdd(&j.counters[0], (unsigned long long)__popcll(bd));
+        if (bf) atomicAdd(&j.counters[1], (unsigned long long)__popcll(bf));
+    }
+}
+
+// host resets while a sampler is armed: the masked envs' poses become their explicit-draw fallback
+__global__ void k_sampler_keep(double *__restrict__ last, const double *__restrict__ poses, const uint8_t *__restrict__ env_mask, int N, int A)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N || (env_mask && !env_mask[i / A])) return;
+    for (int c = 0; c < 3; ++c) last[3 * (size_t)i + c] = poses[3 * (size_t)i + c];
 }

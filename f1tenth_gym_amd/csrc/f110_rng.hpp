@@ -146,6 +146,60 @@ inline void pcg64_seed_from_u64(uint64_t seed, uint64_t out[4])
     out[3] = inc.lo;
 }
 
+// np.random.PCG64(np.random.SeedSequence(entropy, spawn_key=(e,))) = SeedSequence(entropy).spawn(E)[e]: the same words as above
+// for the assembled entropy — the run entropy as little-endian uint32 words (NumPy's _coerce_to_uint32_array of the seed),
+// zero-filled to the pool size because a spawn key follows, then the words of e (0 -> [0]).  Words past the pool size are mixed
+// into every pool word after the pool's own cross-mix (bit_generator.pyx mix_entropy).
+inline void pcg64_seed_spawn(const uint32_t *run, int n_run, uint64_t e, uint64_t out[4])
+{
+    const uint32_t INIT_A = 0x43b0d7e5u, MULT_A = 0x931e8875u, INIT_B = 0x8b51f9ddu, MULT_B = 0x58f38dedu;
+    const uint32_t MIX_L = 0xca01f9ddu, MIX_R = 0x4973f715u;
+    const uint32_t key[2] = {(uint32_t)e, (uint32_t)(e >> 32)};
+    const int n_key = (e >> 32) ? 2 : 1;
+    const int n_pre = n_run > 4 ? n_run : 4, n_all = n_pre + n_key;
+    auto word = [&](int q) -> uint32_t { return q < n_pre ? (q < n_run ? run[q] : 0u) : key[q - n_pre]; };
+    uint32_t pool[4], hc = INIT_A;
+    auto hashmix = [&](uint32_t v) {
+        v ^= hc;
+        hc *= MULT_A;
+        v *= hc;
+        v ^= v >> 16;
+        return v;
+    };
+    auto mix = [&](uint32_t x, uint32_t y) {
+        uint32_t r = MIX_L * x - MIX_R * y;
+        r ^= r >> 16;
+        return r;
+    };
+    for (int i = 0; i < 4; ++i) pool[i] = hashmix(word(i));
+    for (int s = 0; s < 4; ++s)
+        for (int d = 0; d < 4; ++d)
+            if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
+    for (int s = 4; s < n_all; ++s)
+        for (int d = 0; d < 4; ++d) pool[d] = mix(pool[d], hashmix(word(s)));
+    uint32_t w[8], hb = INIT_B;
+    for (int i = 0; i < 8; ++i) {
+        uint32_t v = pool[i & 3];
+        v ^= hb;
+        hb *= MULT_B;
+        v *= hb;
+        v ^= v >> 16;
+        w[i] = v;
+    }
+    uint64_t q[4];
+    for (int i = 0; i < 4; ++i) q[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    const U128 initstate = {q[0], q[1]}, initseq = {q[2], q[3]};
+    U128 inc = {(initseq.hi << 1) | (initseq.lo >> 63), (initseq.lo << 1) | 1ull};
+    U128 st = {0, 0};
+    st = pcg_step(st, inc);
+    st = add128(st, initstate);
+    st = pcg_step(st, inc);
+    out[0] = st.hi;
+    out[1] = st.lo;
+    out[2] = inc.hi;
+    out[3] = inc.lo;
+}
+
 // ---- glibc 2.35 log1p (sysdeps/ieee754/dbl-64/s_log1p.c: fdlibm's algorithm with the
 // polynomial evaluated in the split form glibc uses), restated for x in (-1, 0] — the only
 // arguments the ziggurat tail feeds it (-next_double).

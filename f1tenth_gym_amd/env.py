@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _ffi
 from .core import DEFAULT_PARAMS
+from .reset_sampler import ResetSampler
 from .sim import Integrator, Simulator
 from .track import Track
 
@@ -205,6 +206,11 @@ class F110Env(_EnvBase):
             self.sim.enable_track()
         elif self.reward_mode == 'progress':
             raise ValueError("reward='progress' needs a track (track=...)")
+        # randomised start poses: random_start= (a ResetSampler or a dict of its settings) makes reset() without
+        # poses draw them on the track
+        self.random_start = None
+        if kwargs.get('random_start') is not None:
+            self.random_start = self.sim.batch.set_reset_sampler(ResetSampler.coerce(kwargs['random_start']))
         self.render_obs = None
         self.current_obs = None
         self._render_view = dict(RENDER_DEFAULTS)
@@ -246,10 +252,18 @@ class F110Env(_EnvBase):
          self._last) = copy.deepcopy(snap["host"])
         return copy.deepcopy(self._last)
 
-    def reset(self, poses):
-        poses = np.asarray(poses, dtype=np.float64)
+    def reset(self, poses=None):
+        """poses None (random_start only): the start poses are drawn on the track"""
         self.collisions = np.zeros((self.num_agents,))
-        self.sim.reset(poses)               # raises ValueError on a pose-count mismatch
+        if poses is None:
+            if self.random_start is None:
+                raise ValueError("reset() without poses needs random_start=")
+            self.sim.batch.sample_reset()
+            self.sim._steps_since_full_reset = 0
+            poses = self.sim.batch.reset_sampler_poses()
+        else:
+            poses = np.asarray(poses, dtype=np.float64)
+            self.sim.reset(poses)           # raises ValueError on a pose-count mismatch
         self._lap.reset(poses)
         action = np.zeros((self.num_agents, 2))
         return self.step(action)            # f110_env.py:337-338: reset advances one step
@@ -363,6 +377,12 @@ class F110VecEnv(object):
         self.tracks = {int(slot): self.sim.set_track(Track.coerce(t), int(slot)) for slot, t in sorted(tracks.items())}
         if self.tracks:
             self.sim.enable_track()
+        # randomised start poses: reset() without poses and every auto re-seat draw them on the env's track;
+        # env_base = this handle's first global env index (ShardedVecEnv)
+        self.random_start = None
+        if kwargs.get('random_start') is not None:
+            self.random_start = self.sim.batch.set_reset_sampler(ResetSampler.coerce(kwargs['random_start']),
+                                                                 env_base=int(kwargs.get('env_base', 0)))
         self._start_poses = None
         self._d_actions = None
         self.copy_obs = bool(copy_obs)
@@ -456,20 +476,30 @@ class F110VecEnv(object):
         DeviceArrays, one frame per agent of `agents` (global indices env * num_agents + agent; None: every agent)"""
         return self.sim.batch.render_device(agents, **spec)
 
-    def reset(self, poses, env_mask=None, reseat_only=False):
+    def reset(self, poses=None, env_mask=None, reseat_only=False):
         """env_mask None: every env, then one zero-action step (f110_env.py:319-334).  A partial mask re-seats the masked envs
         only and returns the last step's tuple with their done cleared.  reseat_only=True takes that path even when env_mask
-        covers every env (ShardedVecEnv: a shard's slice of a partial global mask may)."""
-        poses = np.asarray(poses, dtype=np.float64).reshape(self.num_envs, self.num_agents, 3)
-        self._start_poses = poses.copy() if self._start_poses is None or env_mask is None else \
-            np.where(np.asarray(env_mask, dtype=bool)[:, None, None], poses, self._start_poses)
+        covers every env (ShardedVecEnv: a shard's slice of a partial global mask may).  poses None (random_start only): the
+        masked envs draw their start poses on the device."""
         partial = env_mask is not None and (bool(reseat_only) or not np.all(env_mask))
         steps = self.sim._steps_since_full_reset
-        if self.device_logic:
-            self.sim.batch.episode_reset(poses.reshape(-1, 3), env_mask)
+        if poses is None:
+            if self.random_start is None:
+                raise ValueError("reset() without poses needs random_start=")
+            b = self.sim.batch
+            b.sample_reset(env_mask)       # (with device_logic also the episode reset)
+            poses = b.reset_sampler_poses().reshape(self.num_envs, self.num_agents, 3)
+            if not self.device_logic:
+                self._lap.reset(poses, env_mask)
         else:
-            self.sim.reset(poses, env_mask)
-            self._lap.reset(poses, env_mask)
+            poses = np.asarray(poses, dtype=np.float64).reshape(self.num_envs, self.num_agents, 3)
+            if self.device_logic:
+                self.sim.batch.episode_reset(poses.reshape(-1, 3), env_mask)
+            else:
+                self.sim.reset(poses, env_mask)
+                self._lap.reset(poses, env_mask)
+        self._start_poses = poses.copy() if self._start_poses is None or env_mask is None else \
+            np.where(np.asarray(env_mask, dtype=bool)[:, None, None], poses, self._start_poses)
         self.sim._steps_since_full_reset = steps if partial else 0
         if partial and self._last is not None:
             # partial reset: re-seat only (class docstring); envs in mid-episode are not stepped
@@ -550,7 +580,14 @@ class F110VecEnv(object):
         info = {'checkpoint_done': toggles, 'toggle_list': self._lap.toggle_list.copy(),
                 'near_starts': self._lap.near_starts.copy()}
         if self.auto_reset and done.any():
-            self.sim.reset(self._start_poses, done)
+            if self.random_start is not None:   # the draw on the device, the drawn poses back for the host lap logic
+                self.sim.batch.sample_reset(done)
+                if np.all(done):
+                    self.sim._steps_since_full_reset = 0
+                drawn = self.sim.batch.reset_sampler_poses().reshape(self.num_envs, self.num_agents, 3)
+                self._start_poses = np.where(done[:, None, None], drawn, self._start_poses)
+            else:
+                self.sim.reset(self._start_poses, done)
             self._lap.reset(self._start_poses, done)
         self._last = (obs, reward, done, info)
         return self._last

@@ -88,11 +88,14 @@ class ShardedVecEnv(object):
         self.timestep = kwargs.get('timestep', 0.01)
         kwargs.setdefault('device_logic', True)
         env_map = kwargs.pop('env_map', None)
+        if kwargs.get('random_start') is not None:   # one sampler for every shard (seed=None: its entropy drawn once), env_base per shard
+            from .reset_sampler import ResetSampler
+            kwargs['random_start'] = ResetSampler.coerce(kwargs['random_start'])
         self._workers = [_Worker(k) for k in range(K)]
         self.shards = [None] * K
 
         def make(k):
-            kw = dict(kwargs, device_id=self.devices[k])
+            kw = dict(kwargs, device_id=self.devices[k], env_base=int(self.bounds[k]))
             if env_map is not None:
                 kw['env_map'] = np.asarray(env_map)[self.bounds[k]:self.bounds[k + 1]]
             self.shards[k] = F110VecEnv(self.shard_sizes[k], **kw)
@@ -158,9 +161,10 @@ class ShardedVecEnv(object):
         return obs, (self.timestep if reward is None else reward), done, info
 
     # ------------------------------------------------------------------ the env API (F110VecEnv's, over all shards)
-    def reset(self, poses, env_mask=None):
-        poses = np.asarray(poses, dtype=np.float64).reshape(self.num_envs, self.num_agents, 3)
-        ps = self._slices(poses)
+    def reset(self, poses=None, env_mask=None):
+        """poses None: every masked env draws its start poses (random_start)"""
+        ps = [None] * len(self.shards) if poses is None else \
+            self._slices(np.asarray(poses, dtype=np.float64).reshape(self.num_envs, self.num_agents, 3))
         ms = [None] * len(self.shards) if env_mask is None else self._slices(np.asarray(env_mask, dtype=bool))
         # "partial" is decided once, from the global mask: a shard whose slice is all True re-seats too, as one handle would
         partial = env_mask is not None and not np.all(env_mask)

@@ -335,7 +335,8 @@ enum {
     F110_STATE_COL_RNG_SEED = 8,      /* per-agent streams: the seed words */
     F110_STATE_COL_EPISODE = 16,
     F110_STATE_COL_PARAMS = 32,       /* f110_set_params_batch rows */
-    F110_STATE_COL_ENV_MAP = 64       /* f110_set_env_maps slot */
+    F110_STATE_COL_ENV_MAP = 64,      /* f110_set_env_maps slot */
+    F110_STATE_COL_RESET_RNG = 128    /* f110_reset_sampler_set: per env its stream {state, inc}, per agent its fallback pose */
 };
 #define F110_STATE_HEADER_BYTES 256
 /* bytes of a blob of n_envs envs (the handle's current column set) */
@@ -581,6 +582,54 @@ int f110_track_get(f110_sim *h, const f110_track_host *out);
 int f110_track_host_block(f110_sim *h, const f110_track_host *pinned);
 /* unit form: h_poses [m][3] on the track of `slot`; h_out [m][5] = s, lateral, heading_error, segment, t */
 int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, int32_t m, double *h_out);
+
+/* ---- randomised start poses (no reference counterpart: training setups built on the reference pick a random waypoint, add
+ * lateral / heading jitter, check the spot is free and call reset(poses) on the host).  A reset sampler draws an env's start
+ * poses on the track of its map slot (f110_track_set; every env's slot must have one: F110_ERR_STATE at arming, or at the next
+ * call that would draw).  Env e owns one PCG64 stream, np.random.PCG64(np.random.SeedSequence(seed, spawn_key=(e,))) with e the
+ * GLOBAL env index (f110_pcg64_seed_spawn), uniforms = Generator.random().  One draw, A agents, track length L, segments
+ * (ax, ay, dx, dy, len, cum), float64 without contraction, every attempt consuming exactly 1 + 2A uniforms in this order:
+ *   s0 = L * (s_lo + u * (s_hi - s_lo)); per agent j: s = s0 - j * gap (closed: s = fmod(s, L), + L when < 0), u_l, u_h,
+ *   d = lateral * (2 u_l - 1), h = heading * (2 u_h - 1), k = the last segment with cum[k] <= s (0 when none),
+ *   t = clip((s - cum[k]) / len[k], 0, 1), x = (ax + t dx) + d * (-dy / len), y = (ay + t dy) + d * (dx / len),
+ *   theta = atan2(dy, dx) + h  (the device's atan2: within an ulp of NumPy's).
+ *   Valid: every agent on the track (open: s >= 0), inside its slot's map (xy_2_rc) with dt[r][c] >= clearance, every pair
+ *   (xi - xj)^2 + (yi - yj)^2 >= (2 clearance)^2.  The first valid attempt wins; none: a fallback (counted).
+ * Explicit draw (f110_reset_sample*): f110_reset of the env to the drawn poses (and f110_episode_reset once f110_episode_init ran,
+ * start_rot computed on the device: within an ulp of NumPy's cos / sin); on a fallback to the poses of the env's last reset of any
+ * kind while the sampler was armed (zeros before the first one).
+ * In-step draw: every call that re-seats envs (f110_set_auto_reseat, f110_reset_collided_device, the auto reset of
+ * f110_step_host / f110_episode_step_host, f110_episode_reset_done_device) draws for the envs it re-seated, behind its last
+ * kernel (per env block behind a two-block step), stream-ordered in front of the next call; the env ends as the re-seat would
+ * have left it had its start poses been the drawn ones, with episode logic also start poses and start_rot; a fallback keeps the
+ * re-seat's pose and the start columns.  Observations already written (the host block) stay the pre-re-seat ones.
+ * Without a sampler nothing of this runs.  The stream position is state (F110_STATE_COL_RESET_RNG); the settings are configuration. */
+typedef struct f110_reset_sampler {
+    double s_lo, s_hi;     /* fractions of the track length, 0 <= s_lo < s_hi <= 1 */
+    double gap;            /* metres between consecutive agents along the track, > 0 */
+    double lateral;        /* largest lateral offset (m), >= 0 */
+    double heading;        /* largest heading jitter (rad), >= 0 */
+    double clearance;      /* metres, >= 0 */
+    int32_t attempts;      /* 1 .. 1024 */
+    int32_t pad;
+} f110_reset_sampler;
+/* {state.hi, state.lo, inc.hi, inc.lo} of PCG64(SeedSequence(entropy, spawn_key=(e,))) for e = e0 .. e0 + n - 1, host only:
+ * h_entropy = the seed as NumPy's SeedSequence assembles it (little-endian uint32 words of an int, the words of every element
+ * of a sequence one after the other), n_words >= 1 (a seed of 0 is the one word 0).  out [n][4]. */
+int f110_pcg64_seed_spawn(const uint32_t *h_entropy, int32_t n_words, uint64_t e0, int32_t n, uint64_t *h_out);
+/* arm (spec != NULL; h_streams [num_envs][4] from f110_pcg64_seed_spawn) or disarm (spec = NULL).  Out-of-range settings:
+ * F110_ERR_INVALID.  Arming clears the counters and the fallback poses. */
+int f110_reset_sampler_set(f110_sim *h, const f110_reset_sampler *spec, const uint64_t *h_streams);
+/* explicit draws for the envs of the mask ([num_envs], NULL = all); _device is asynchronous on the handle's stream */
+int f110_reset_sample(f110_sim *h, const uint8_t *h_env_mask);
+int f110_reset_sample_device(f110_sim *h, const uint8_t *d_env_mask);
+/* out2 (or NULL) = {draws, fallbacks} since the last clear; h_attempt [num_envs] (or NULL) = the winning attempt of each env's last
+ * draw, -1 = a fallback or no draw yet; clear != 0 zeroes the counters */
+int f110_reset_sampler_stats(f110_sim *h, uint64_t *out2, int32_t *h_attempt, int32_t clear);
+/* h_poses [N][3] = each env's poses of its last reset of any kind (what an explicit fallback resets to) */
+int f110_reset_sampler_poses(f110_sim *h, double *h_poses);
+/* device pointers of the episode logic's start poses [N][3] and start_rot [num_envs][4] (f110_episode_init) */
+int f110_episode_start_views(f110_sim *h, double **d_start_poses, double **d_start_rot);
 
 /* ---- rendering (rendering.py draws with pyglet: map points, one quad per car, a label; this is its rgb_array form) ----
  * A render makes F frames of H x W pixels, one uint8 class per pixel (the highest that applies wins):
