@@ -132,7 +132,6 @@ struct f110_sim {
     size_t state_blob_bytes = 0;
     unsigned long long *d_lookups = nullptr;  // f110_scan_lookup_count
     bool lookups_on = false;
-    // the single-block step captured as a HIP graph (f110_config.step_graph): one submission per step
     int collide_mode = 0;        // where the pair tests run: 0 side stream, 1 fused into k_integrate, 2 in line, 3 inside k_finalize (A = 2)
     // longest-first order of the scan tasks (TaskSched, small batches): double-buffered flags / lists / counters
     bool task_order = false;
@@ -175,19 +174,13 @@ struct f110_sim {
     double hs_enqueue_us = 0, hs_wait_us = 0;    // f110_step_host_stats
     FusedHost *d_fused = nullptr;                // device copy of {episode arrays, host block, flags} for the pair kernel's epilogue
     FusedHost fused_host_copy{};                 // what d_fused holds
-    bool fused_valid = false, fuse_request = false, fused_done = false;
-    unsigned long long fuse_seq = 0;
+    bool fused_valid = false;
     long long hs_calls = 0;
     // the whole step of a tiny batch as ONE launch (k_step_tiny): counters + shadow columns, allocated on first use
     TinyCtl tiny{};
     void *tiny_mem = nullptr;
     int tiny_off = 0;                 // lab A/B (f110_exp_set "step_tiny" = 0): the three-kernel form also for tiny batches
     int last_launches = 0;            // kernels the most recent step submitted its work as (f110_step_launches)
-    const double *tiny_actions_host = nullptr;   // f110_step_host -> step_tiny: the caller's [N][2] actions (host memory), for this call
-    bool tiny_request = false;        // f110_step_host: this step is one k_step_tiny launch
-    bool tiny_host_request = false;   // ... with one agent per env: what k_host_block would be handed
-    HostBlock tiny_hb{};
-    int tiny_episode = 0, tiny_auto_reset = 0;
     // track progress (f110_track_*): a polyline per map slot, the step's columns, the per-agent cache of s
     struct TrackSlot {
         double *d_cols = nullptr;   // [7][nseg] (TrackCol)
@@ -225,7 +218,6 @@ struct f110_sim {
     struct ResetSampler {
         bool on = false;
         SamplerJob job{};            // settings + device buffers; tracks / maps / mode are filled per launch
-        bool defer = false;          // inside f110_step_host / f110_episode_step*: the caller launches the draw after its last kernel
     } rs;
     // timing
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
@@ -233,6 +225,18 @@ struct f110_sim {
     std::vector<hipEvent_t> prof_events;  // per step: before integrate, before scan, after scan, after finalize
     size_t prof_used = 0;
     char err[512] = {0};
+};
+
+// What one step is asked to do beyond a plain f110_step_device (the default-constructed request).  Built on the stack of
+// f110_step_host / f110_episode_step_*, handed down to step_range / step_tiny, gone when the call returns.
+struct StepRequest {
+    bool tiny = false;                      // this step is ONE k_step_tiny launch (f110_step_host decided: tiny_applies)
+    const double *tiny_actions = nullptr;   // ... whose arguments carry the caller's [N][2] actions (host memory)
+    bool fuse = false;                      // A = 2: host block + episode logic ride in the pair kernel / the last workgroup (d_fused)
+    unsigned long long seq = 0;             // ... with this completion number (0: nobody spins on the word)
+    const HostBlock *hb = nullptr;          // one car per env, one launch: what k_host_block would be handed ...
+    int episode = 0, auto_reset = 0;        // ... (block, episode logic on, re-seat finished envs)
+    bool defer_draw = false;                // the caller launches the reset sampler's draw itself, behind its own last kernel
 };
 
 static thread_local char g_err[512] = {0};
@@ -268,8 +272,6 @@ static int dmalloc(f110_sim *h, T **p, size_t count)
         int rc_ = (expr);      \
         if (rc_ != F110_OK) return rc_; \
     } while (0)
-
-static int group_envs(const f110_sim *h);   // envs per env block (defined with f110_step_device)
 
 // The group streams' outstanding work becomes a dependency of the main stream (stream-ordered, no
 // host wait).  Every entry point except the step itself starts with it, so the env groups are an
@@ -309,7 +311,64 @@ static bool tiny_applies(const f110_sim *h);   // (below, with the step)
 static void noise_release(f110_sim *h);        // (below, with the noise entry points)
 static void sampler_release(f110_sim *h);      // (below, with the reset sampler)
 static int sampler_launch(f110_sim *h, hipStream_t st, int mode, int e0, int count, const uint8_t *d_mask, int ego);
-static int sampler_after_step(f110_sim *h, bool grouped);
+// the step behind f110_step_device, f110_step_host and f110_episode_step_* (below, with step_range); host_written: the step's
+// own kernel wrote the caller's host block (rq.fuse / rq.hb were honoured)
+static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &rq, bool &host_written);
+
+// ---- env blocks: on which streams, over which env ranges, does a call launch? -------------------------------
+constexpr int kMaxEnvBlocks = 16;
+struct EnvBlock { hipStream_t stream; int e0, count; };   // envs [e0, e0 + count) on `stream`
+struct EnvBlocks {
+    EnvBlock b[kMaxEnvBlocks];
+    int n = 0;
+    const EnvBlock *begin() const { return b; }
+    const EnvBlock *end() const { return b + n; }
+};
+
+// how the env axis is cut into `groups` blocks: whole envs, whole 64-agent waves where possible
+static int group_envs(const f110_sim *h)
+{
+    const int E = h->cfg.num_envs, G = h->groups;
+    int per = (E + G - 1) / G;
+#ifdef F110_EXPERIMENTAL
+    if (G == 2 && h->exp.group_split > 0) per = std::max(1, (int)((long long)E * h->exp.group_split / 100));   // probe: uneven halves
+#endif
+    if (per >= 64) per = (per + 63) / 64 * 64;
+    return per;
+}
+
+// submit: every env block on its own stream (a grouped step, and the sampler draw behind it); empty blocks are dropped
+static EnvBlocks env_blocks_submit(const f110_sim *h)
+{
+    EnvBlocks w;
+    const int per = group_envs(h), E = h->cfg.num_envs;
+    for (int g = 0; g < h->groups && g * per < E; ++g) w.b[w.n++] = EnvBlock{h->gstreams[g], g * per, std::min(per, E - g * per)};
+    return w;
+}
+
+// the whole batch on the main stream
+static EnvBlocks env_blocks_main(const f110_sim *h)
+{
+    EnvBlocks w;
+    w.b[w.n++] = EnvBlock{h->stream, 0, h->cfg.num_envs};
+    return w;
+}
+
+// follow: a device-resident call behind the step.  Right behind a two-block step (nothing else through the handle since) it
+// rides the two blocks, each on the block's own stream, without a join; otherwise it is an ordinary entry point (ENTER) on
+// the main stream.  A caller whose work reads per env / per agent only ends with `h->touched = false`: the next step may
+// split again (it forks from what the call left on the main stream: main_dirty); behind the blocks touched is false already.
+static int env_blocks_follow(f110_sim *h, EnvBlocks &w)
+{
+    if (h->last_blocks == 2 && h->groups_busy && !h->touched) {   // (two blocks went out: groups == 2)
+        HIPCHK(h, hipSetDevice(h->cfg.device_id));
+        w = env_blocks_submit(h);
+        return F110_OK;
+    }
+    ENTER(h);
+    w = env_blocks_main(h);
+    return F110_OK;
+}
 
 // RAII scratch for the unit entry points
 struct Scratch {
@@ -654,7 +713,7 @@ int f110_create(const f110_config *cfg, f110_sim **out)
         int G = cfg->step_groups;
         h->groups_auto = G <= 0;
         if (G <= 0) G = 2;
-        G = std::min(std::min(G, 16), cfg->num_envs);
+        G = std::min(std::min(G, kMaxEnvBlocks), cfg->num_envs);
         h->groups = G;
         // pair tests + opponent windows inside the finalize kernel: A = 2 (k_finalize_pair_roles) and every A up to
         // kMaxAgentsMulti = 256 (k_finalize_multi up to 16, k_finalize_multi_tiled above: an env's ordered pairs in tiles of a
@@ -1234,6 +1293,15 @@ int f110_set_trig_tables(f110_sim *h, const double *s, const double *c, int32_t 
 static const char *const kBeamsMsg = "the beam tables (f110_set_beam_tables) are not the uniform ramp scan_angles[i] = scan_angles[0] + i*inc of base_classes.py:133-134: "
                                      "the step's opponent ray-cast assumes it; such tables are served by f110_raycast_batch / f110_ttc_batch only";
 
+// what every stepping entry point asks before it enqueues anything (args: its pointer arguments are all there)
+static int check_step(f110_sim *h, bool args)
+{
+    if (!h || !args) return fail(h, F110_ERR_INVALID, "null argument");
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (!h->beams_uniform) return fail(h, F110_ERR_STATE, kBeamsMsg);
+    return F110_OK;
+}
+
 int f110_set_beam_tables(f110_sim *h, const double *sa, const double *co, const double *sd, int32_t B)
 {
     if (!h || !sa || !co || !sd) return fail(h, F110_ERR_INVALID, "null argument");
@@ -1523,19 +1591,10 @@ static int sampler_launch(f110_sim *h, hipStream_t st, int mode, int e0, int cou
     return F110_OK;
 }
 
-// the draw behind a call that may have re-seated envs in-step (its last kernel is on the main stream, or per env block)
-static int sampler_after_step(f110_sim *h, bool grouped)
+// the draw behind a call that may have re-seated envs in-step, where that call's last kernel ran (the main stream, or per env block)
+static int sampler_after_step(f110_sim *h, const EnvBlocks &where)
 {
-    const int E = h->cfg.num_envs;
-    if (!grouped) TRY(sampler_launch(h, h->stream, kSampleMarker, 0, E, nullptr, 0));
-    else {
-        const int per = group_envs(h);
-        for (int g = 0; g < h->groups; ++g) {   // (as f110_step_device's loop: every env block on its own stream)
-            const int e0 = g * per, e1 = std::min(E, e0 + per);
-            if (e0 >= e1) break;
-            TRY(sampler_launch(h, h->gstreams[g], kSampleMarker, e0, e1 - e0, nullptr, 0));
-        }
-    }
+    for (const EnvBlock &b : where) TRY(sampler_launch(h, b.stream, kSampleMarker, b.e0, b.count, nullptr, 0));
     if (h->last_launches > 0) h->last_launches += 1;   // (the one-launch step is two launches with the draw behind it)
     return F110_OK;
 }
@@ -1959,29 +2018,20 @@ int f110_episode_step_device(f110_sim *h, const double *d_actions)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     if (!h->has_episode) return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
-    h->rs.defer = true;
-    const int rc_step = f110_step_device(h, d_actions);
-    h->rs.defer = false;
-    if (rc_step != F110_OK) return rc_step;
-    const bool draw = h->rs.on && h->dev.reseat_poses;
-    if (h->last_blocks == 2 && h->groups_busy) {
-        // the step went out as two env blocks: each block's _check_done behind it on the block's own stream (an env's
-        // lap bookkeeping reads that env's agents only), no join — the device-resident loop stays two independent halves
-        const int per = group_envs(h), E = h->cfg.num_envs;
-        for (int g = 0; g < 2; ++g) {
-            const int e0 = g * per, e1 = std::min(E, e0 + per);
-            if (e0 >= e1) break;
-            hipLaunchKernelGGL(k_episode, grid1d(e1 - e0, 256), dim3(256), 0, h->gstreams[g], h->dev, h->ep, e1 - e0, e0);
-        }
-        HIPCHK(h, hipGetLastError());
-        if (draw) TRY(sampler_after_step(h, true));
-        return F110_OK;
-    }
-    ENTER(h);   // _check_done reads every group's poses and flags
-    hipLaunchKernelGGL(k_episode, grid1d(h->cfg.num_envs, 256), dim3(256), 0, h->stream, h->dev, h->ep, h->cfg.num_envs);
+    TRY(check_step(h, d_actions != nullptr));
+    StepRequest rq;
+    rq.defer_draw = true;
+    bool host_written = false;
+    TRY(step_submit(h, d_actions, rq, host_written));
+    // _check_done behind the step: after a two-block step on each block's own stream (an env's lap bookkeeping reads that env's
+    // agents only), no join — the device-resident loop stays two independent halves.  (Right after a successful step `touched`
+    // is false, so the follow rule's `!touched` changes nothing here.)
+    EnvBlocks w;
+    TRY(env_blocks_follow(h, w));
+    for (const EnvBlock &b : w) hipLaunchKernelGGL(k_episode, grid1d(b.count, 256), dim3(256), 0, b.stream, h->dev, h->ep, b.count, b.e0);
     HIPCHK(h, hipGetLastError());
-    if (draw) TRY(sampler_after_step(h, false));
-    h->touched = false;   // the next step may split: what this call left on the main stream is forked from (main_dirty)
+    if (h->rs.on && h->dev.reseat_poses) TRY(sampler_after_step(h, w));
+    h->touched = false;
     return F110_OK;
 }
 
@@ -1993,25 +2043,16 @@ int f110_episode_reset_done_device(f110_sim *h, int32_t *d_count)
         HIPCHK(h, hipSetDevice(h->cfg.device_id));
         TRY(track_prepare(h));
     }
-    if (h->last_blocks == 2 && h->groups_busy && !h->touched) {   // behind a two-block f110_episode_step_device: per block, no join
-        HIPCHK(h, hipSetDevice(h->cfg.device_id));
-        const int per = group_envs(h), E = h->cfg.num_envs, A = h->cfg.num_agents;
-        for (int g = 0; g < 2; ++g) {
-            const int e0 = g * per, e1 = std::min(E, e0 + per);
-            if (e0 >= e1) break;
-            hipLaunchKernelGGL(k_episode_reset_done, grid1d((e1 - e0) * A, 256), dim3(256), 0, h->gstreams[g], h->dev, h->ep, d_count, e0 * A, (e1 - e0) * A);
-            if (h->rs.on) TRY(sampler_launch(h, h->gstreams[g], kSampleDone, e0, e1 - e0, nullptr, 0));   // (done[] is still set)
-            hipLaunchKernelGGL(k_episode_clear_done, grid1d(e1 - e0, 256), dim3(256), 0, h->gstreams[g], h->ep, e1 - e0, e0);
-        }
-        HIPCHK(h, hipGetLastError());
-        return F110_OK;
+    EnvBlocks w;   // behind a two-block f110_episode_step_device: per block, no join (a re-seat touches the finished env's own agents only)
+    TRY(env_blocks_follow(h, w));
+    const int A = h->cfg.num_agents;
+    for (const EnvBlock &b : w) {
+        hipLaunchKernelGGL(k_episode_reset_done, grid1d(b.count * A, 256), dim3(256), 0, b.stream, h->dev, h->ep, d_count, b.e0 * A, b.count * A);
+        if (h->rs.on) TRY(sampler_launch(h, b.stream, kSampleDone, b.e0, b.count, nullptr, 0));   // (done[] is still set)
+        hipLaunchKernelGGL(k_episode_clear_done, grid1d(b.count, 256), dim3(256), 0, b.stream, h->ep, b.count, b.e0);
     }
-    ENTER(h);
-    hipLaunchKernelGGL(k_episode_reset_done, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, h->ep, d_count);
-    if (h->rs.on) TRY(sampler_launch(h, h->stream, kSampleDone, 0, h->cfg.num_envs, nullptr, 0));
-    hipLaunchKernelGGL(k_episode_clear_done, grid1d(h->cfg.num_envs, 256), dim3(256), 0, h->stream, h->ep, h->cfg.num_envs);
     HIPCHK(h, hipGetLastError());
-    h->touched = false;   // (as in f110_episode_step_device: the loop step / reset_done / step / ... may split from its second round on)
+    h->touched = false;   // (the loop step / reset_done / step / ... may split from its second round on)
     return F110_OK;
 }
 
@@ -2086,16 +2127,15 @@ int f110_episode_step_host(f110_sim *h, const double *h_actions, int32_t auto_re
 {
     if (!h || !h_actions || !h_packed) return fail(h, F110_ERR_INVALID, "null argument");
     if (!h->has_episode) return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
-    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
-    if (!h->beams_uniform) return fail(h, F110_ERR_STATE, kBeamsMsg);
+    TRY(check_step(h, true));
     ENTER(h);
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs, bytes = f110_episode_packed_bytes(h);
     if (!h->d_packed) HIPCHK(h, hipMalloc(&h->d_packed, bytes));
     HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
-    h->rs.defer = true;
-    const int rc_step = f110_step_device(h, h->d_actions);
-    h->rs.defer = false;
-    if (rc_step != F110_OK) return rc_step;
+    StepRequest rq;
+    rq.defer_draw = true;
+    bool host_written = false;
+    TRY(step_submit(h, h->d_actions, rq, host_written));
     ENTER(h);
     hipLaunchKernelGGL(k_episode, grid1d(E, 256), dim3(256), 0, h->stream, h->dev, h->ep, (int)E);
     double *cols = reinterpret_cast<double *>(h->d_packed);
@@ -2107,7 +2147,7 @@ int f110_episode_step_host(f110_sim *h, const double *h_actions, int32_t auto_re
         hipLaunchKernelGGL(k_episode_clear_done, grid1d(E, 256), dim3(256), 0, h->stream, h->ep, (int)E);
     }
     HIPCHK(h, hipGetLastError());
-    if (h->rs.on && (auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, false));
+    if (h->rs.on && (auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, env_blocks_main(h)));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }
@@ -2130,9 +2170,7 @@ static int map_host_ptr(f110_sim *h, const void *host, void **dev, const char *w
 
 int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *out, int32_t flags)
 {
-    if (!h || !h_actions || !out) return fail(h, F110_ERR_INVALID, "null argument");
-    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
-    if (!h->beams_uniform) return fail(h, F110_ERR_STATE, kBeamsMsg);
+    TRY(check_step(h, h_actions && out));
     const bool episode = h->has_episode;
     if (!episode && (out->lap_times || out->lap_counts || out->toggles || out->current_time || out->near_starts ||
                      out->checkpoint_done || out->done || (flags & F110_STEP_AUTO_RESET)))
@@ -2197,8 +2235,13 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
         d_act = h->hb_actions_dev;   // k_integrate reads the [N][2] block over PCIe, once, coalesced
     else if (!tiny)                  // (k_step_tiny gets the actions as kernel arguments)
         HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
-    h->tiny_actions_host = tiny ? h_actions : nullptr;
     const int A = h->cfg.num_agents;
+    StepRequest rq;
+    rq.tiny = tiny;
+    rq.tiny_actions = tiny ? h_actions : nullptr;
+    rq.episode = episode ? 1 : 0;
+    rq.auto_reset = (flags & F110_STEP_AUTO_RESET) ? 1 : 0;
+    rq.defer_draw = true;   // (the draw follows the host block, below)
     HostBlock hbk = h->hb_dev;
     if (spin) {
         void *p = nullptr;
@@ -2212,9 +2255,7 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     // (not with F110_STEP_SPIN_WAIT: the completion word needs a system-scope release per workgroup, and the pair kernel
     // has N / 32 of them with the scan's dirty lines still in L2 — measured 0.657 -> 0.767 ms at 32 768 envs)
     // tracking: the track columns are computed behind the step's last kernel, so the host block is k_host_block (no epilogue)
-    const bool want_fuse = A == 2 && !(flags & F110_STEP_NO_FUSE) && (!spin || tiny) && !h->track_on;
-    h->tiny_request = tiny;
-    h->tiny_host_request = tiny && A == 1 && !h->track_on;
+    rq.fuse = A == 2 && !(flags & F110_STEP_NO_FUSE) && (!spin || tiny) && !h->track_on;
     if (h->track_on && h->trk_pinned_on) {
         hbk.trk_src = h->d_trk;
         hbk.trk_seg_src = h->d_trk_seg;
@@ -2224,18 +2265,13 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
         hbk.trk_head = h->trk_hb.trk_head;
         hbk.trk_seg = h->trk_hb.trk_seg;
     }
-    if (h->tiny_host_request) {
-        h->tiny_hb = hbk;
-        h->tiny_episode = episode ? 1 : 0;
-        h->tiny_auto_reset = (flags & F110_STEP_AUTO_RESET) ? 1 : 0;
-    }
-    if (want_fuse) {
+    if (rq.fuse) {
         FusedHost fh{};
         if (episode) fh.ep = h->ep;
         fh.hb = hbk;
-        fh.hb.seq = 0;   // (the sequence number travels in the kernel arguments)
-        fh.episode = episode ? 1 : 0;
-        fh.auto_reset = (flags & F110_STEP_AUTO_RESET) ? 1 : 0;
+        fh.hb.seq = 0;   // (the sequence number travels in the kernel arguments: rq.seq)
+        fh.episode = rq.episode;
+        fh.auto_reset = rq.auto_reset;
         if (!h->d_fused) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_fused), sizeof(FusedHost)));
         if (!h->fused_valid || std::memcmp(&fh, &h->fused_host_copy, sizeof fh) != 0) {
             h->fused_host_copy = fh;
@@ -2243,28 +2279,22 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
             h->fused_valid = true;
         }
     }
-    h->fuse_request = want_fuse;
-    h->fuse_seq = spin ? hbk.seq : 0;
-    h->fused_done = false;
-    h->rs.defer = true;
-    const int rc_step = f110_step_device(h, d_act);
-    h->rs.defer = false;
-    h->fuse_request = false;
-    h->tiny_request = h->tiny_host_request = false;
-    h->tiny_actions_host = nullptr;
-    if (rc_step != F110_OK) return rc_step;
+    rq.seq = spin ? hbk.seq : 0;
+    if (tiny && A == 1 && !h->track_on) rq.hb = &hbk;
+    bool host_written = false;
+    TRY(step_submit(h, d_act, rq, host_written));
     ENTER(h);
-    if (!h->fused_done) {
+    if (!host_written) {
         const int epb = A >= 256 ? 1 : 256 / A;
         hipLaunchKernelGGL(k_host_block, dim3((unsigned)((E + epb - 1) / epb)), dim3(256), 0, h->stream, h->dev, h->ep, hbk, (int)E, epb,
-                           episode ? 1 : 0, (flags & F110_STEP_AUTO_RESET) ? 1 : 0);
+                           rq.episode, rq.auto_reset);
     }
     // the scans are contiguous in HBM already: a DMA copy, behind the kernel (the re-seat leaves scans alone)
     if (out->scans && !h->hb_scans_by_kernel) HIPCHK(h, hipMemcpyAsync(out->scans, h->dev.scans, sizeof(double) * N * (size_t)h->cfg.num_beams, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipGetLastError());
     // a re-seat inside this call (auto reset, or an armed f110_set_auto_reseat): the draw, behind the block (which keeps the
     // terminal observation), stream-ordered in front of the next step
-    if (h->rs.on && ((flags & F110_STEP_AUTO_RESET) || h->dev.reseat_poses)) TRY(sampler_after_step(h, false));
+    if (h->rs.on && (rq.auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, env_blocks_main(h)));
     const auto t_enq = std::chrono::steady_clock::now();
     if (spin) {
         // poll the completion word the last workgroup stores (no runtime call on the way out); a kernel that
@@ -2541,7 +2571,7 @@ static int tiny_setup(f110_sim *h)
     return F110_OK;
 }
 
-static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions)
+static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions, const StepRequest &rq, bool &host_written)
 {
     TRY(tiny_setup(h));
     const int N = h->N, A = h->cfg.num_agents;
@@ -2561,39 +2591,31 @@ static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions)
     h->tiny.tasks_per_agent = ((uint32_t)h->k.num_beams + 63u) / 64u;
     h->tiny.trace = kExperimental ? reinterpret_cast<unsigned long long *>(h->exp.tiny_trace) : nullptr;
     h->tiny.act_inline = 0;
-    if (h->tiny_actions_host && N <= kTinyMaxAgents) {   // f110_step_host: the caller's actions travel with the launch
-        std::memcpy(h->tiny.act, h->tiny_actions_host, sizeof(double) * 2 * (size_t)N);
+    if (rq.tiny_actions && N <= kTinyMaxAgents) {   // f110_step_host: the caller's actions travel with the launch
+        std::memcpy(h->tiny.act, rq.tiny_actions, sizeof(double) * 2 * (size_t)N);
         h->tiny.act_inline = 1;
     }
     h->tiny.start_word = nullptr;
     h->tiny.skip = kExperimental ? (h->exp.tiny_start_probe == 2 ? 1 : (h->exp.tiny_general_tail ? 2 : 0)) : 0;
-    if (kExperimental && h->exp.tiny_start_probe && h->hb_seq_host && h->fuse_seq) {
+    if (kExperimental && h->exp.tiny_start_probe && h->hb_seq_host && rq.seq) {
         void *p = nullptr;
         TRY(map_host_ptr(h, h->hb_seq_host, &p, "completion word"));
         h->tiny.start_word = reinterpret_cast<unsigned long long *>(p) + 1;
         h->tiny.start_seq = h->hb_seq;
     }
     const dim3 grid(((unsigned)N * h->tiny.tasks_per_agent + 3u) / 4u), block(256);
-    EpisodeArrays ep{};
-    HostBlock hb{};
-    int episode = 0, auto_reset = 0;
-    bool host = false;
-    if (A == 2) {
-        if (h->fuse_request && !dev.reseat_poses) {   // f110_step_host: host block + episode logic as the last workgroup's epilogue
-            dev.fused_host = h->d_fused;
-            dev.fused_seq = h->fuse_seq;
-            h->fused_done = true;
-            host = true;
-        }
-    } else if (h->tiny_host_request && !dev.reseat_poses) {
-        ep = h->ep;
-        hb = h->tiny_hb;
-        episode = h->tiny_episode;
-        auto_reset = h->tiny_auto_reset;
-        h->fused_done = true;
-        host = true;
+    // f110_step_host: host block + episode logic as the last workgroup's epilogue; two cars per env read them from d_fused,
+    // one car per env (solo) gets them as kernel arguments
+    const bool host = !dev.reseat_poses && (A == 2 ? rq.fuse : rq.hb != nullptr), solo = host && A != 2;
+    host_written = host;
+    if (host && A == 2) {
+        dev.fused_host = h->d_fused;
+        dev.fused_seq = rq.seq;
+        h->tiny.fh = h->fused_host_copy;   // (what d_fused holds: f110_step_host keeps the two equal)
     }
-    if (host && A == 2) h->tiny.fh = h->fused_host_copy;   // (what d_fused holds: f110_step_host keeps the two equal)
+    const EpisodeArrays ep = solo ? h->ep : EpisodeArrays{};
+    const HostBlock hb = solo ? *rq.hb : HostBlock{};
+    const int episode = solo ? rq.episode : 0, auto_reset = solo ? rq.auto_reset : 0;
     // one env of two cars: finalize_duo_tiny puts the scans into the caller's block early (its idle wave copies, the window lanes follow)
     h->tiny.host_scans = (host && h->hb_valid && h->hb_scans_by_kernel && A == 2 && N == 2 && !(kExperimental && h->exp.tiny_general_tail)) ? h->hb_dev.scans : nullptr;
     if (h->track_on) TRY(track_launch(h, st, kTrackHead, 0, N));
@@ -2615,7 +2637,8 @@ static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions)
     return F110_OK;
 }
 
-static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const double *d_actions, int collide_mode, hipEvent_t *ev)
+static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const double *d_actions, int collide_mode, hipEvent_t *ev, const StepRequest &rq,
+                      bool &host_written)
 {
     const int N = h->N, A = h->cfg.num_agents, B = h->k.num_beams;
     AgentArrays dev = h->dev;
@@ -2823,10 +2846,10 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
             // the workgroups many (measured: 65 536 agents AG 32 / 16 / 4: 0.726 / 0.738 / 0.815 ms; 4096 agents AG 16 / 4:
             // 0.1047 / 0.1053).  (Rounds 2-3's forms — fixed lanes per agent, the prologue dealt by agent — were retired in round 5.)
             lanes = N >= 32768 ? 8 : (N >= 4096 ? 16 : 64);
-            if (h->fuse_request && begin == 0 && count == N && !dev.reseat_poses) {   // f110_step_host: host block + episode logic as this kernel's epilogue
+            if (rq.fuse && begin == 0 && count == N && !dev.reseat_poses) {   // f110_step_host: host block + episode logic as this kernel's epilogue
                 dev.fused_host = h->d_fused;
-                dev.fused_seq = h->fuse_seq;
-                h->fused_done = true;
+                dev.fused_seq = rq.seq;
+                host_written = true;
             }
             if (dev.fused_host) {   // the instantiation that carries the f110_step_host epilogue
                 if (lanes <= 8) hipLaunchKernelGGL((k_finalize_pair_roles<32, true>), dim3((count + 31) / 32), dim3(256), 0, st, dev, B);
@@ -2876,18 +2899,6 @@ static bool env_blocks_pay(int N, int A)
     return true;
 }
 
-// how the env axis is cut into `groups` blocks: whole envs, whole 64-agent waves where possible
-static int group_envs(const f110_sim *h)
-{
-    const int E = h->cfg.num_envs, G = h->groups;
-    int per = (E + G - 1) / G;
-#ifdef F110_EXPERIMENTAL
-    if (G == 2 && h->exp.group_split > 0) per = std::max(1, (int)((long long)E * h->exp.group_split / 100));   // probe: uneven halves
-#endif
-    if (per >= 64) per = (per + 63) / 64 * 64;
-    return per;
-}
-
 int f110_step_groups(f110_sim *h, int32_t *groups, int32_t *probes, int32_t *last)
 {
     if (!h) return fail(h, F110_ERR_INVALID, "null argument");
@@ -2904,11 +2915,9 @@ int f110_step_launches(f110_sim *h, int32_t *launches)
     return F110_OK;
 }
 
-int f110_step_device(f110_sim *h, const double *d_actions)
+static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &rq, bool &host_written)
 {
-    if (!h || !d_actions) return fail(h, F110_ERR_INVALID, "null argument");
-    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
-    if (!h->beams_uniform) return fail(h, F110_ERR_STATE, kBeamsMsg);
+    host_written = false;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     if (h->track_on || h->rs.on) TRY(track_prepare(h));
     const int N = h->N, A = h->cfg.num_agents;
@@ -2948,11 +2957,12 @@ int f110_step_device(f110_sim *h, const double *d_actions)
     // (two groups borrow the side stream, which the older collide forms use themselves)
     // a tiny batch (the reference's own shape: one env of two cars) is ONE launch: integrate, scan, finalize and — under
     // f110_step_host — the observation block and the completion word, in k_step_tiny
-    const bool tiny = h->tiny_request && !prof;   // (f110_step_host decided: tiny_applies)
+    const bool tiny = rq.tiny && !prof;   // (f110_step_host decided: tiny_applies)
     const bool grouped = !tiny && h->groups > 1 && !prof && (h->multi_map || agent_aligned(h)) && h->dir_stride == 0 &&
                          !(h->gstreams[0] == h->stream && h->collide_mode != 3 && A > 1) &&
                          (!h->groups_auto || (!h->touched && env_blocks_pay(N, A)));
     h->last_launches = 0;
+    const EnvBlocks w = grouped ? env_blocks_submit(h) : env_blocks_main(h);
     if (!grouped) {
         TRY(join_groups(h));
         h->main_dirty = true;
@@ -2961,12 +2971,8 @@ int f110_step_device(f110_sim *h, const double *d_actions)
             for (int i = 0; i < 4; ++i)
                 if (!(ev[i] = prof_event(h))) return fail(h, F110_ERR_HIP, "hipEventCreate failed");
         }
-        const int cmode = h->collide_mode;
-        if (tiny) {
-            TRY(step_tiny(h, h->stream, d_actions));
-        } else {
-            TRY(step_range(h, h->stream, 0, N, d_actions, cmode, prof ? ev : nullptr));
-        }
+        if (tiny) TRY(step_tiny(h, h->stream, d_actions, rq, host_written));
+        else TRY(step_range(h, h->stream, 0, N, d_actions, h->collide_mode, prof ? ev : nullptr, rq, host_written));
     } else {
         if (h->main_dirty) {
             HIPCHK(h, hipEventRecord(h->ev_main, h->stream));
@@ -2974,23 +2980,25 @@ int f110_step_device(f110_sim *h, const double *d_actions)
                 if (gs != h->stream) HIPCHK(h, hipStreamWaitEvent(gs, h->ev_main, 0));
             h->main_dirty = false;
         }
-        const int per = group_envs(h), E = h->cfg.num_envs;
         const int mode = h->collide_mode == 3 ? 3 : ((A == 2 || A == 4) ? 1 : 2);
-        for (int g = 0; g < h->groups; ++g) {
-            const int e0 = g * per, e1 = std::min(E, e0 + per);
-            if (e0 >= e1) break;
-            TRY(step_range(h, h->gstreams[g], e0 * A, (e1 - e0) * A, d_actions, mode == 0 ? 2 : mode, nullptr));
-        }
+        for (const EnvBlock &b : w) TRY(step_range(h, b.stream, b.e0 * A, b.count * A, d_actions, mode, nullptr, rq, host_written));
         h->groups_busy = true;
     }
     // an in-step re-seat armed (f110_set_auto_reseat): the draw for the envs it re-seated, behind the step (per env block);
-    // f110_step_host / f110_episode_step* launch it after their own last kernel instead
-    if (h->rs.on && h->dev.reseat_poses && !h->rs.defer) TRY(sampler_after_step(h, grouped));
+    // f110_step_host / f110_episode_step* launch it after their own last kernel instead (rq.defer_draw)
+    if (h->rs.on && h->dev.reseat_poses && !rq.defer_draw) TRY(sampler_after_step(h, w));
     h->touched = false;
     h->last_blocks = grouped ? h->groups : 1;
     h->noise_ub += 1;
     HIPCHK(h, hipGetLastError());
     return F110_OK;
+}
+
+int f110_step_device(f110_sim *h, const double *d_actions)
+{
+    TRY(check_step(h, d_actions != nullptr));
+    bool host_written = false;
+    return step_submit(h, d_actions, StepRequest{}, host_written);
 }
 
 int f110_stream_fence(f110_sim *h)
@@ -3002,9 +3010,7 @@ int f110_stream_fence(f110_sim *h)
 
 int f110_step(f110_sim *h, const double *actions)
 {
-    if (!h || !actions) return fail(h, F110_ERR_INVALID, "null argument");
-    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
-    if (!h->beams_uniform) return fail(h, F110_ERR_STATE, kBeamsMsg);
+    TRY(check_step(h, actions != nullptr));
     ENTER(h);   // the previous step (possibly still running on the group streams) reads d_actions
     HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, sizeof(double) * 2 * h->N, hipMemcpyHostToDevice, h->stream));
     TRY(f110_step_device(h, h->d_actions));
@@ -3583,27 +3589,19 @@ int f110_pure_pursuit_device(f110_sim *h, const double *d_waypoints, int32_t M, 
     if (!d_actions) return fail(h, F110_ERR_INVALID, "pure pursuit: null actions buffer");
     const int N = h->N;
     const double *st = h->dev.state;
-    if (h->last_blocks == 2 && h->groups_busy && !h->touched) {
-        // a closed device-side loop (plan, step, plan, ...) behind a two-block step: each block's agents are planned for on the
-        // block's own stream (a pose in, an action out, per agent), so the two halves of the batch stay independent
-        HIPCHK(h, hipSetDevice(h->cfg.device_id));
-        const int per = group_envs(h), E = h->cfg.num_envs, A = h->cfg.num_agents;
-        for (int g = 0; g < 2; ++g) {
-            const int e0 = g * per, e1 = std::min(E, e0 + per);
-            if (e0 >= e1) break;
-            const size_t i0 = (size_t)e0 * A;
-            const int n = (e1 - e0) * A;
-            hipLaunchKernelGGL(k_pure_pursuit, grid1d((size_t)n * kPlanLanes, 256), dim3(256), 0, h->gstreams[g], d_waypoints, M, st + i0, st + N + i0,
-                               st + 4 * (size_t)N + i0, 1, n, lookahead, vgain, wheelbase, max_reacquire, d_actions + 2 * i0);
-        }
-        HIPCHK(h, hipGetLastError());
-        return F110_OK;
+    // a closed device-side loop (plan, step, plan, ...) behind a two-block step: each block's agents are planned for on the
+    // block's own stream (a pose in, an action out, per agent), so the two halves of the batch stay independent
+    EnvBlocks w;
+    TRY(env_blocks_follow(h, w));
+    const int A = h->cfg.num_agents;
+    for (const EnvBlock &b : w) {
+        const size_t i0 = (size_t)b.e0 * A;
+        const int n = b.count * A;
+        hipLaunchKernelGGL(k_pure_pursuit, grid1d((size_t)n * kPlanLanes, 256), dim3(256), 0, b.stream, d_waypoints, M, st + i0, st + N + i0,
+                           st + 4 * (size_t)N + i0, 1, n, lookahead, vgain, wheelbase, max_reacquire, d_actions + 2 * i0);
     }
-    ENTER(h);
-    hipLaunchKernelGGL(k_pure_pursuit, grid1d((size_t)N * kPlanLanes, 256), dim3(256), 0, h->stream, d_waypoints, M, st, st + N, st + 4 * (size_t)N, 1, N, lookahead,
-                       vgain, wheelbase, max_reacquire, d_actions);
     HIPCHK(h, hipGetLastError());
-    h->touched = false;   // (the next step may split: it forks from what this call left on the main stream)
+    h->touched = false;
     return F110_OK;
 }
 
@@ -3614,26 +3612,16 @@ int f110_scan_policy_device(f110_sim *h, double steer_gain, double steer_max, do
     if (h->cfg.num_beams > 2048) return fail(h, F110_ERR_INVALID, "scan policy: at most 2048 beams (the rows are staged in LDS)");
     if (h->cfg.num_beams < 64) return fail(h, F110_ERR_INVALID, "scan policy: needs at least 64 beams (one per sector)");
     if (!(sector_limit >= h->cfg.fov / 128.)) return fail(h, F110_ERR_INVALID, "scan policy: sector_limit must be at least fov/128 (half a sector), else no sector is eligible");
-    const int N = h->N, B = h->cfg.num_beams;
-    if (h->last_blocks == 2 && h->groups_busy && !h->touched) {
-        // behind a two-block step: each block's agents on the block's own stream (an agent reads its own scan row only)
-        HIPCHK(h, hipSetDevice(h->cfg.device_id));
-        const int per = group_envs(h), E = h->cfg.num_envs, A = h->cfg.num_agents;
-        for (int g = 0; g < 2; ++g) {
-            const int e0 = g * per, e1 = std::min(E, e0 + per);
-            if (e0 >= e1) break;
-            const int n = (e1 - e0) * A;
-            hipLaunchKernelGGL(k_scan_policy, grid1d((size_t)n * 64, 256), dim3(256), (size_t)4 * B * sizeof(double), h->gstreams[g], h->dev.scans, B, h->cfg.fov, e0 * A, n, steer_gain, steer_max,
-                               sector_limit, v_lo, v_hi, d_ref, d_actions);
-        }
-        HIPCHK(h, hipGetLastError());
-        return F110_OK;
+    EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (an agent reads its own scan row only)
+    TRY(env_blocks_follow(h, w));
+    const int A = h->cfg.num_agents, B = h->cfg.num_beams;
+    for (const EnvBlock &b : w) {
+        const int n = b.count * A;
+        hipLaunchKernelGGL(k_scan_policy, grid1d((size_t)n * 64, 256), dim3(256), (size_t)4 * B * sizeof(double), b.stream, h->dev.scans, B, h->cfg.fov, b.e0 * A, n, steer_gain, steer_max,
+                           sector_limit, v_lo, v_hi, d_ref, d_actions);
     }
-    ENTER(h);
-    hipLaunchKernelGGL(k_scan_policy, grid1d((size_t)N * 64, 256), dim3(256), (size_t)4 * B * sizeof(double), h->stream, h->dev.scans, B, h->cfg.fov, 0, N, steer_gain, steer_max, sector_limit,
-                       v_lo, v_hi, d_ref, d_actions);
     HIPCHK(h, hipGetLastError());
-    h->touched = false;   // (as f110_pure_pursuit_device: the next step may split)
+    h->touched = false;
     return F110_OK;
 }
 

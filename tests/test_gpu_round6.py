@@ -416,6 +416,43 @@ def test_which_steps_take_the_one_launch_form(amd):
         s.close()
 
 
+@pytest.mark.parametrize("E,form", [(2, "one_launch"), (3, "fused")])
+def test_a_step_request_does_not_outlive_its_call(amd, E, form):
+    """what f110_step_host asks of its step — the one-launch form (2 envs of 2 cars), the host block as the pair kernel's epilogue
+    (3 envs of 2 cars) — holds for that call only: a plain step_device on the same handle right after it takes the per-kernel form
+    and writes no host block (the page-locked views keep the step()'s observation); the device state after the two steps is, bit for
+    bit, that of a twin handle that took the same two actions through BatchSim.step"""
+    A = 2
+    kw = dict(map=map_stem("example_map"), map_ext=".png", num_agents=A, device_logic=True)
+    v, twin = amd.F110VecEnv(E, **kw), amd.F110VecEnv(E, **kw)
+    poses = bench_start_poses(E, A).reshape(E, A, 3)
+    v.reset(poses)
+    twin.reset(poses)
+    rng = np.random.default_rng(E)
+    acts = [np.stack([rng.uniform(-0.4, 0.4, E * A), rng.uniform(1.0, 7.0, E * A)], axis=1) for _ in range(2)]
+    b = v.sim.batch
+    obs, _, done, info = v.step(acts[0].reshape(E, A, 2))
+    assert b.step_launches() == (1 if form == "one_launch" else 0)
+    views = dict(obs, done=done, **info)
+    seen = {k: np.array(x) for k, x in views.items()}
+    d = b.device_array((E * A, 2))
+    d.upload(acts[1])
+    b.step_device(d)
+    b.sync()
+    assert b.step_launches() == 0, "a plain device step: the per-kernel form"
+    for k in seen:
+        assert np.array_equal(np.asarray(views[k]), seen[k]), (k, "a plain device step writes no host block")
+    for a in acts:
+        twin.sim.batch.step(a)
+    fields = ("scans", "state", "collisions", "collision_idx", "in_collision", "agent_poses", "step_count")
+    mine, ref = b.get(*fields), twin.sim.batch.get(*fields)
+    assert not np.array_equal(mine["state"][:, 0], seen["poses_x"].reshape(-1)), "the second step moved the cars: a written block would show it"
+    for k in fields:
+        assert np.array_equal(mine[k], ref[k]), k
+    b.close()
+    twin.sim.batch.close()
+
+
 @pytest.mark.parametrize("A", [2, 1])
 def test_f110env_episodes_switch_between_the_step_forms_vs_oracle(amd, A):
     """tools/debug/f110env_soak.py: F110Env driven reset() / step() until done / reset() ... against the oracle at every step, the noise
