@@ -59,6 +59,17 @@ class ResetSamplerSpec(C.Structure):
                 ("heading", C.c_double), ("clearance", C.c_double), ("attempts", C.c_int32), ("pad", C.c_int32)]
 
 
+class ObsSpec(C.Structure):
+    """struct f110_obs_spec"""
+    _fields_ = [("beam_lo", C.c_int32), ("beam_hi", C.c_int32), ("sectors", C.c_int32), ("pool", C.c_int32),
+                ("features", C.c_int32), ("frames", C.c_int32), ("flags", C.c_int32), ("pad", C.c_int32),
+                ("range_clip", C.c_double), ("range_scale", C.c_double), ("feat_scale", C.c_double * 8)]
+
+
+OBS_POOL_MIN, OBS_POOL_MEAN, OBS_POOL_CENTER = 0, 1, 2
+OBS_FILL, OBS_MAX_FRAMES, OBS_MAX_STACK = 1, 16, 8192
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -193,6 +204,8 @@ PROTOTYPES = {
     "f110_track_host_block": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
     "f110_track_project_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp]),
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
+    "f110_obs_encode_device": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p, C.c_void_p]),
+    "f110_obs_encode_batch": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), _dp, _dp, _i32p, C.c_int32, C.c_void_p]),
     "f110_pcg64_seed_spawn": (C.c_int, [_u32p, C.c_int32, C.c_uint64, C.c_int32, _u64p]),
     "f110_reset_sampler_set": (C.c_int, [C.c_void_p, C.c_void_p, _u64p]),
     "f110_reset_sample": (C.c_int, [C.c_void_p, _u8p]),

@@ -267,6 +267,7 @@ class BatchSim(object):
                  scan_block=0, scan_tasks_per_wave=0, step_groups=0, step_graph=0, exp=None):
         self._h = None
         self._device_arrays = set()   # finalisers of the DeviceArrays this handle owns memory for
+        self._obs_stacks = {}         # encode_obs_device(out=None): id(encoder) -> (encoder, its stack)
         L = _ffi.lib()
         self.params = dict(DEFAULT_PARAMS if params is None else params)
         self.E, self.A, self.B = int(num_envs), int(num_agents), int(num_beams)
@@ -1118,6 +1119,58 @@ class BatchSim(object):
             for r in res:
                 r.free()
         return host if len(host) > 1 else host[0]
+
+    # ------------------------------------------------------------------ compact observations (f110_obs_encode_*)
+    def encode_obs_device(self, enc, out=None, fill=False, pinned=None):
+        """the last step's observation as float32 [N][F][D] (obs_encoder.ObsEncoder), newest frame last: the frames of `out`
+        move down by one and the new frame goes last; agents that start an episode (step_count 1), or all with fill, get
+        every frame set to it.  `out` is the caller's stack (a float32 DeviceArray of enc.shape(N)); None: one buffer per
+        encoder, allocated (and filled) on the first call and reused from then on.  Enqueued on the handle's stream, per env
+        block behind a two-block step (no host wait).  pinned: a pinned_empty float32 array of the same shape that also
+        receives the stack, complete after sync()."""
+        from .obs_encoder import ObsEncoder
+        enc = ObsEncoder.coerce(enc)
+        enc.check_beams(self.B)
+        shape = enc.shape(self.N)
+        if out is None:
+            out = self._obs_stacks.get(id(enc))
+            if out is None or out[0] is not enc or out[1].ptr is None:
+                out = (enc, DeviceArray(self, shape, np.float32))   # (the encoder is held: its id stays its own)
+                self._obs_stacks[id(enc)] = out
+                fill = True
+            out = out[1]
+        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
+            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
+        pp = None
+        if pinned is not None:
+            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
+                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
+            pp = pinned.ctypes.data
+        spec = enc.spec(fill)
+        check(_ffi.lib().f110_obs_encode_device(self._h, C.byref(spec), out.ptr, pp), self._h)
+        return out
+
+    def encode_obs(self, enc, out=None, fill=False):
+        """encode_obs_device, downloaded (synchronises): NumPy float32 [N][F][D]"""
+        return self.encode_obs_device(enc, out, fill).download()
+
+    def obs_encode_batch(self, enc, scans, cols, step_count, stack, fill=False):
+        """unit form on host arrays: scans [m][B], cols [m][8] (the eight feature sources in obs_encoder.FEATURES order),
+        step_count [m], stack float32 [m][F][D] -> the updated stack (a new array)"""
+        from .obs_encoder import ObsEncoder
+        enc = ObsEncoder.coerce(enc)
+        enc.check_beams(self.B)
+        scans, cols = as_f64(scans), as_f64(cols)
+        m = scans.shape[0]
+        if scans.shape != (m, self.B) or cols.shape != (m, 8):
+            raise ValueError("scans must be [m][%d] and cols [m][8]" % self.B)
+        sc = np.ascontiguousarray(step_count, dtype=np.int32)
+        st = np.array(stack, dtype=np.float32, order="C")
+        if sc.shape != (m,) or st.shape != enc.shape(m):
+            raise ValueError("step_count must be [m] and stack %s" % (enc.shape(m),))
+        spec = enc.spec(fill)
+        check(_ffi.lib().f110_obs_encode_batch(self._h, C.byref(spec), dptr(scans), dptr(cols), i32ptr(sc), m, st.ctypes.data), self._h)
+        return st
 
     # ------------------------------------------------------------------ the reference's example policy
     def pure_pursuit_batch(self, waypoints, poses, lookahead, vgain, wheelbase, max_reacquire=20.0):

@@ -202,6 +202,7 @@ struct f110_sim {
     f110_track_host trk_pinned{};         // f110_track_host_block, host pointers ...
     HostBlock trk_hb{};                   // ... and their device views (the trk_* fields)
     bool trk_pinned_on = false;
+    const float *obs_pinned = nullptr;    // f110_obs_encode_device: the page-locked block its last copy went to
     // rendering (f110_render_device): slot 0's occupancy grid, the slot table as last uploaded, per-frame / per-agent records
     uint8_t *d_occ0 = nullptr;
     std::vector<RenderSlot> render_slots;
@@ -2103,6 +2104,12 @@ int f110_host_free(f110_sim *h, void *p)
                     o->trk_pinned = f110_track_host{};
                 }
             }
+            if (inside(o->obs_pinned)) {   // an encode's copy (on the env blocks' streams) may still be on its way into the block
+                (void)hipSetDevice(o->cfg.device_id);
+                for (hipStream_t gs : o->gstreams) (void)hipStreamSynchronize(gs);
+                (void)hipStreamSynchronize(o->stream);
+                o->obs_pinned = nullptr;
+            }
             if (!o->hb_valid && !o->fused_valid) continue;
             const f110_host_block &b = o->hb_host;
             const void *ptrs[] = {b.scans, b.state, b.agent_poses, b.collisions, b.collision_idx, b.in_collision, b.lap_times, b.lap_counts, b.toggles,
@@ -3622,6 +3629,160 @@ int f110_scan_policy_device(f110_sim *h, double steer_gain, double steer_max, do
     }
     HIPCHK(h, hipGetLastError());
     h->touched = false;
+    return F110_OK;
+}
+
+// ---- compact observations (include/f110.h) ----------------------------------------------------------------------------------
+// the spec's refusals; on success the kernel's row spec, W's first beam and F.  unit: the eight sources come from the caller
+static int obs_check_spec(f110_sim *h, const f110_obs_spec *spec, const void *out, bool unit, ObsRowSpec &rs, int &beam_lo)
+{
+    if (!spec || !out) return fail(h, F110_ERR_INVALID, "obs encode: spec and the output buffer are required");
+    const f110_obs_spec &sp = *spec;
+    const int B = h->cfg.num_beams;
+    int lo = sp.beam_lo, hi = sp.beam_hi;
+    if (lo == 0 && hi == 0) hi = B;
+    if (lo < 0 || hi > B || lo >= hi) return fail(h, F110_ERR_INVALID, "obs encode: beams [%d, %d) are not a range within the %d beams", sp.beam_lo, sp.beam_hi, B);
+    const int W = hi - lo, K = sp.sectors;
+    if (K < 0 || K > W) return fail(h, F110_ERR_INVALID, "obs encode: sectors = %d is outside 0..%d (the beams used)", K, W);
+    if (sp.pool < F110_OBS_POOL_MIN || sp.pool > F110_OBS_POOL_CENTER) return fail(h, F110_ERR_INVALID, "obs encode: unknown pool %d", sp.pool);
+    if (sp.features & ~F110_OBS_ALL_FEATURES) return fail(h, F110_ERR_INVALID, "obs encode: unknown feature bits 0x%x", sp.features);
+    if (sp.flags & ~F110_OBS_FILL) return fail(h, F110_ERR_INVALID, "obs encode: unknown flags 0x%x", sp.flags);
+    if (sp.frames < 1 || sp.frames > F110_OBS_MAX_FRAMES) return fail(h, F110_ERR_INVALID, "obs encode: frames = %d is outside 1..%d", sp.frames, F110_OBS_MAX_FRAMES);
+    if (K > 0 && !(std::isfinite(sp.range_clip) && sp.range_clip > 0 && std::isfinite(sp.range_scale) && sp.range_scale > 0))
+        return fail(h, F110_ERR_INVALID, "obs encode: range_clip and range_scale must be finite and > 0");
+    rs = ObsRowSpec{};
+    for (int c = 0; c < F110_OBS_NFEATURES; ++c) {
+        if (!(sp.features >> c & 1)) continue;
+        if (!(std::isfinite(sp.feat_scale[c]) && sp.feat_scale[c] != 0.0)) return fail(h, F110_ERR_INVALID, "obs encode: feat_scale[%d] must be finite and non-zero", c);
+        rs.feat[rs.nfeat] = c;
+        rs.feat_scale[rs.nfeat++] = sp.feat_scale[c];
+    }
+    for (int c = rs.nfeat; c < F110_OBS_NFEATURES; ++c) rs.feat_scale[c] = 1.0;
+    const int D = K + rs.nfeat;
+    if (D == 0) return fail(h, F110_ERR_INVALID, "obs encode: no sectors and no features (D = 0)");
+    if ((long long)sp.frames * D > F110_OBS_MAX_STACK)
+        return fail(h, F110_ERR_INVALID, "obs encode: frames * D = %lld exceeds %d", (long long)sp.frames * D, (int)F110_OBS_MAX_STACK);
+    if (reinterpret_cast<uintptr_t>(out) % (unit ? 4 : 16) != 0) return fail(h, F110_ERR_INVALID, "obs encode: the output buffer is not %d-byte aligned", unit ? 4 : 16);
+    if (!unit && (sp.features & F110_OBS_TRACK_FEATURES) && !h->track_on)
+        return fail(h, F110_ERR_STATE, "obs encode: LATERAL / HEADING_ERROR / DS need tracking (f110_track_enable)");
+    rs.W = W;
+    rs.K = K;
+    rs.pool = sp.pool;
+    rs.D = D;
+    rs.clip = sp.range_clip;
+    rs.scale = sp.range_scale;
+    beam_lo = lo;
+    return F110_OK;
+}
+
+// LDS per wave and waves per workgroup: the row (when it fits next to the stack image in 64 KiB) and the image [F * D + 3]; the
+// workgroup size of 1..4 waves that packs the most waves into a CU's 160 KiB
+static void obs_plan_lds(ObsJob &j)
+{
+    const int img = ((j.F * j.rs.D + 3) * 4 + 15) & ~15;
+    const int row = j.rs.K > 0 ? (j.rs.W * 8 + 15) & ~15 : 0;
+    j.row_bytes = (row > 0 && row + img <= 65536) ? row : 0;
+    j.wave_bytes = j.row_bytes + img;
+    int best = 1, best_waves = 0;
+    for (int w = 1; w <= 4; ++w) {
+        if ((long long)w * j.wave_bytes > 65536) break;
+        const int per_cu = std::min(32, (int)(163840 / ((long long)w * j.wave_bytes)) * w);
+        if (per_cu >= best_waves) {
+            best_waves = per_cu;
+            best = w;
+        }
+    }
+    j.waves = best;
+}
+
+static void obs_launch(const ObsJob &j, hipStream_t st)
+{
+    const dim3 grid((unsigned)((j.n + j.waves - 1) / j.waves)), block((unsigned)(64 * j.waves));
+    const size_t lds = (size_t)j.waves * j.wave_bytes;
+    if (j.row_bytes > 0 || j.rs.K == 0) hipLaunchKernelGGL(k_obs_encode<true>, grid, block, lds, st, j);
+    else hipLaunchKernelGGL(k_obs_encode<false>, grid, block, lds, st, j);   // a row too long for LDS: the sectors are walked in HBM
+}
+
+int f110_obs_encode_device(f110_sim *h, const f110_obs_spec *spec, float *d_out, float *h_pinned)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ObsJob j{};
+    TRY(obs_check_spec(h, spec, d_out, false, j.rs, j.beam_lo));
+    const size_t N = (size_t)h->N;
+    const size_t per_agent = (size_t)spec->frames * j.rs.D;
+    if (h_pinned) {
+        std::lock_guard<std::mutex> lk(g_registry_mu);
+        const char *p = reinterpret_cast<const char *>(h_pinned);
+        auto it = g_host_blocks.upper_bound(p);
+        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
+        if (it != g_host_blocks.begin()) {
+            --it;
+            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
+        }
+        if (!inside) return fail(h, F110_ERR_INVALID, "obs encode: h_pinned is not [N][F][D] floats of f110_host_alloc memory");
+    }
+    EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (an agent reads and writes its own rows only)
+    TRY(env_blocks_follow(h, w));
+    const double *st = h->dev.state;
+    const double *src[F110_OBS_NFEATURES] = {st + 3 * N, st + 2 * N, st + 5 * N, st + 6 * N, h->dev.collisions,
+                                             h->d_trk ? h->d_trk + 2 * N : nullptr, h->d_trk ? h->d_trk + 3 * N : nullptr, h->d_trk ? h->d_trk + N : nullptr};
+    for (int f = 0; f < F110_OBS_NFEATURES; ++f) j.fptr[f] = src[f < j.rs.nfeat ? j.rs.feat[f] : 0];
+    j.col_stride = 1;
+    j.scans = h->dev.scans;
+    j.step_count = h->dev.step_count;
+    j.out = d_out;
+    j.B = h->cfg.num_beams;
+    j.F = spec->frames;
+    j.fill = (spec->flags & F110_OBS_FILL) ? 1 : 0;
+    obs_plan_lds(j);
+    const int A = h->cfg.num_agents;
+    for (const EnvBlock &b : w) {
+        j.i0 = b.e0 * A;
+        j.n = b.count * A;
+        obs_launch(j, b.stream);
+        if (h_pinned)
+            HIPCHK(h, hipMemcpyAsync(h_pinned + (size_t)j.i0 * per_agent, d_out + (size_t)j.i0 * per_agent, (size_t)j.n * per_agent * sizeof(float),
+                                     hipMemcpyDeviceToHost, b.stream));
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h_pinned) h->obs_pinned = h_pinned;
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_obs_encode_batch(f110_sim *h, const f110_obs_spec *spec, const double *h_scans, const double *h_cols, const int32_t *h_step_count,
+                          int32_t m, float *h_inout)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ObsJob j{};
+    TRY(obs_check_spec(h, spec, h_inout, true, j.rs, j.beam_lo));
+    if (!h_scans || !h_cols || !h_step_count || m < 0) return fail(h, F110_ERR_INVALID, "obs encode: bad argument");
+    if (m == 0) return F110_OK;
+    ENTER(h);
+    Scratch s(h);
+    const size_t B = (size_t)h->cfg.num_beams, per_agent = (size_t)spec->frames * j.rs.D;
+    double *ds = nullptr, *dc = nullptr;
+    int32_t *dn = nullptr;
+    float *dout = nullptr;
+    TRY(s.up(h_scans, (size_t)m * B, &ds));
+    TRY(s.up(h_cols, (size_t)m * F110_OBS_NFEATURES, &dc));
+    TRY(s.up(h_step_count, (size_t)m, &dn));
+    TRY(s.up(h_inout, (size_t)m * per_agent, &dout));
+    for (int f = 0; f < F110_OBS_NFEATURES; ++f) j.fptr[f] = dc + (f < j.rs.nfeat ? j.rs.feat[f] : 0);
+    j.col_stride = F110_OBS_NFEATURES;
+    j.scans = ds;
+    j.step_count = dn;
+    j.out = dout;
+    j.B = (int)B;
+    j.F = spec->frames;
+    j.fill = (spec->flags & F110_OBS_FILL) ? 1 : 0;
+    j.i0 = 0;
+    j.n = m;
+    obs_plan_lds(j);
+    obs_launch(j, h->stream);
+    HIPCHK(h, hipGetLastError());
+    TRY(s.down(h_inout, dout, (size_t)m * per_agent));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }
 

@@ -3955,3 +3955,116 @@ __global__ void k_sampler_keep(double *__restrict__ last, const double *__restri
     if (i >= N || (env_mask && !env_mask[i / A])) return;
     for (int c = 0; c < 3; ++c) last[3 * (size_t)i + c] = poses[3 * (size_t)i + c];
 }
+
+// ---- compact observations (f110_obs_encode_*; include/f110.h states the rule, f110_math.hpp obs_* is the per-row arithmetic) ----
+// One wave per agent, k_scan_policy's pattern: the W beams of the row go through LDS with 64-lane coalesced loads (walking the
+// sectors straight from HBM touches 64 lines per instruction), then lane l takes elements l, l + 64, ... of the new frame (K above
+// or below 64).  The agent's stack [F][D] is assembled in LDS as well: frames 1..F-1 are LOADED into the places of frames 0..F-2
+// before anything is stored (one wave owns the agent: no race, no second buffer), the new frame goes behind them (or into all F
+// places at an episode start), and the image leaves as 16-byte stores: the image sits in LDS at the agent's phase (first float
+// of the stack modulo 4), so an aligned global float4 is an aligned LDS float4 whatever F * D is.
+// HBM traffic per agent: 8 W (row) + 4 D (F - 1) (old frames) + 4 D F (stack) bytes.  Every load a wave needs (row, old frames,
+// its lanes' features, step_count) is issued before anything waits: the old frames are fetched whether or not the agent turns out
+// to start an episode (a start overwrites them in LDS), so a wave makes one trip to memory, not one per dependency.
+struct ObsJob {
+    ObsRowSpec rs;
+    const double *scans;                 // [.][B]
+    const double *fptr[kObsFeatures];    // feature j (output order) of agent i = fptr[j][i * col_stride]
+    size_t col_stride;
+    const int32_t *step_count;           // [.]
+    float *out;                          // [.][F][D]
+    int32_t B, beam_lo, F, fill;
+    int32_t i0, n;                       // agents [i0, i0 + n)
+    int32_t waves, wave_bytes, row_bytes;   // waves per workgroup; LDS per wave; of which the row (0: not staged)
+};
+
+template <bool STAGED>
+__global__ void __launch_bounds__(256) k_obs_encode(ObsJob j)
+{
+    extern __shared__ double obs_lds[];
+    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+    const int a = (int)blockIdx.x * j.waves + wave;
+    if (a >= j.n) return;
+    const size_t i = (size_t)j.i0 + (size_t)a;
+    const ObsRowSpec &s = j.rs;
+    const int W = s.W, K = s.K, D = s.D, F = j.F;
+    char *base = reinterpret_cast<char *>(obs_lds) + (size_t)wave * (size_t)j.wave_bytes;
+    double *mine = reinterpret_cast<double *>(base);
+    const size_t g0 = i * (size_t)F * (size_t)D;          // first float of the agent's stack
+    const int phase = (int)(g0 & 3u);
+    float *img = reinterpret_cast<float *>(base + j.row_bytes) + phase;
+    const double *row = j.scans + i * (size_t)j.B + j.beam_lo;
+    float *stack = j.out + g0;
+    const bool start = obs_episode_start(j.step_count[i], j.fill);
+    const int keep = (F - 1) * D;
+    if (STAGED && K > 0) {
+        // 16 loads in flight per lane, and the next round's loads issued before this round's LDS stores: a 1080-beam row is one
+        // memory round trip (a small batch has few waves per SIMD to hide a second one behind)
+        constexpr int U = 16;
+        double cur[U], nxt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = lane + 64 * u < W ? row[lane + 64 * u] : 0.;
+        for (int b = lane; b < W; b += 64 * U) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) nxt[u] = b + 64 * (U + u) < W ? row[b + 64 * (U + u)] : 0.;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (b + 64 * u < W) mine[b + 64 * u] = cur[u];
+#pragma unroll
+            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        }
+    }
+    // frames 1..F-1 into the places of frames 0..F-2, without waiting for step_count (an episode start overwrites them below)
+    if (!j.fill)
+        for (int t = lane; t < keep; t += 64) img[t] = stack[t + D];
+    // the lane's feature (at most one: fewer than 64 of them), loaded up front with the row, not behind the pooling
+    const int ef = K + ((lane - K) & 63);
+    double fx = 0., fdiv = 1.;
+    if (ef < D) {
+        const int f = ef - K;
+        const double *p = j.fptr[0];
+        fdiv = s.feat_scale[0];
+#pragma unroll
+        for (int c = 1; c < kObsFeatures; ++c) {   // (static indices: the job lives in kernel-argument registers)
+            p = f == c ? j.fptr[c] : p;
+            fdiv = f == c ? s.feat_scale[c] : fdiv;
+        }
+        fx = p[i * j.col_stride];
+    }
+    __builtin_amdgcn_wave_barrier();   // (one wave: its LDS accesses are in order; the barrier only pins the compiler)
+    // the bounds of sector e = lane, lane + 64, ...: k W = q K + r, stepped by 64 W = dq K + dr per round (no division in the loop)
+    int q0 = 0, r0 = 0, q1 = 0, r1 = 0, dq = 0, dr = 0;
+    if (K > 0 && W < (1 << 25)) {   // (64 W fits 32 bits: the short division)
+        const uint32_t w0 = (uint32_t)lane * (uint32_t)W, w1 = w0 + (uint32_t)W, ws = 64u * (uint32_t)W, k = (uint32_t)K;
+        q0 = (int)(w0 / k), r0 = (int)(w0 % k), q1 = (int)(w1 / k), r1 = (int)(w1 % k), dq = (int)(ws / k), dr = (int)(ws % k);
+    } else if (K > 0) {
+        const long long w0 = (long long)lane * W, w1 = w0 + W, ws = 64ll * W;
+        q0 = (int)(w0 / K), r0 = (int)(w0 % K), q1 = (int)(w1 / K), r1 = (int)(w1 % K), dq = (int)(ws / K), dr = (int)(ws % K);
+    }
+    for (int e = lane; e < D; e += 64) {
+        float v;
+        if (e < K) {
+            v = STAGED ? obs_pool(s, mine, q0, q1) : obs_pool(s, row, q0, q1);
+            q0 += dq, r0 += dr, q1 += dq, r1 += dr;
+            if (r0 >= K) ++q0, r0 -= K;
+            if (r1 >= K) ++q1, r1 -= K;
+        } else {
+            v = obs_feature(fx, fdiv);
+        }
+        if (start) {
+            for (int f = 0; f < F; ++f) img[f * D + e] = v;
+        } else {
+            img[keep + e] = v;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const int total = F * D;
+    int head = (4 - phase) & 3;
+    head = head < total ? head : total;
+    if (lane < head) stack[lane] = img[lane];
+    const int nvec = (total - head) >> 2;
+    for (int q = lane; q < nvec; q += 64)
+        *reinterpret_cast<float4 *>(stack + head + 4 * q) = *reinterpret_cast<const float4 *>(img + head + 4 * q);
+    const int tail = head + 4 * nvec;
+    if (tail + lane < total) stack[tail + lane] = img[tail + lane];
+}

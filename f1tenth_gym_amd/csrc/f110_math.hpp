@@ -1188,4 +1188,77 @@ F110_HD void pure_pursuit_plan(const double *wp, int M, double px, double py, do
     steer = atan(wheelbase / radius);
 }
 
+// ------------------------------------------------------------------ compact observations (include/f110.h, f110_obs_spec)
+// No reference counterpart.  Compares, float64 adds and divides, one float64 -> float32 conversion: no libm, nothing to contract.
+constexpr int kObsFeatures = 8;
+enum { OBS_POOL_MIN = 0, OBS_POOL_MEAN = 1, OBS_POOL_CENTER = 2 };
+
+struct ObsRowSpec {
+    int32_t W, K;         // beams used, sectors (the row pointer handed to obs_element starts at beam_lo)
+    int32_t pool, D;      // D = K + nfeat
+    int32_t nfeat;
+    int32_t feat[kObsFeatures];          // feature j (in output order) reads source column feat[j]
+    double clip, scale;
+    double feat_scale[kObsFeatures];     // divisor of feature j (output order)
+};
+
+// np.minimum(v, clip): a NaN operand is the result
+F110_HD double obs_minimum(double v, double clip) { return v != v ? v : (v < clip ? v : clip); }
+
+// the lidar value of beams [b0, b1) of a row (relative to beam_lo): pooling, clip / scale / cast
+F110_HD float obs_pool(const ObsRowSpec &s, const double *row, int b0, int b1)
+{
+    double v;
+    if (s.pool == OBS_POOL_CENTER) {
+        v = row[(b0 + b1 - 1) >> 1];
+    } else if (s.pool == OBS_POOL_MEAN) {
+        v = row[b0];
+        for (int b = b0 + 1; b < b1; ++b) v = v + row[b];
+        v = v / (double)(b1 - b0);
+    } else {
+        v = row[b0];
+        for (int b = b0 + 1; b < b1; ++b) {
+            const double r = row[b];
+            v = (r < v || r != r) ? r : v;   // a NaN sticks: nothing compares below it and it is not replaced
+        }
+    }
+    return (float)(obs_minimum(v, s.clip) / s.scale);
+}
+
+// lidar value k of a row: sector k covers beams floor(k W / K) .. floor((k + 1) W / K) exclusive
+F110_HD float obs_sector(const ObsRowSpec &s, const double *row, int k)
+{
+    return obs_pool(s, row, (int)(((long long)k * s.W) / s.K), (int)(((long long)(k + 1) * s.W) / s.K));
+}
+
+F110_HD float obs_feature(double x, double divisor) { return (float)(x / divisor); }
+
+// element j of the new frame: the K lidar values, then the features in bit order.  cols[c * stride] = source column c
+F110_HD float obs_element(const ObsRowSpec &s, const double *row, const double *cols, size_t stride, int j)
+{
+    if (j < s.K) return obs_sector(s, row, j);
+    const int f = j - s.K;
+    return obs_feature(cols[(size_t)s.feat[f] * stride], s.feat_scale[f]);
+}
+
+// does this agent's stack start over (all frames = the new frame)?
+F110_HD bool obs_episode_start(int step_count, int fill) { return fill != 0 || step_count == 1; }
+
+// the whole update of one agent's stack [F][D], serially (the kernel spreads obs_element over a wave and moves the frames
+// through LDS; this is the same rule in one place, and what the unit harness runs)
+F110_HD void obs_update_stack(const ObsRowSpec &s, const double *row, const double *cols, size_t stride, int step_count, int fill,
+                              int F, float *stack)
+{
+    const int D = s.D;
+    if (obs_episode_start(step_count, fill)) {
+        for (int j = 0; j < D; ++j) {
+            const float v = obs_element(s, row, cols, stride, j);
+            for (int f = 0; f < F; ++f) stack[(size_t)f * D + j] = v;
+        }
+        return;
+    }
+    for (size_t t = 0; t + D < (size_t)F * D; ++t) stack[t] = stack[t + D];
+    for (int j = 0; j < D; ++j) stack[(size_t)(F - 1) * D + j] = obs_element(s, row, cols, stride, j);
+}
+
 }  // namespace f110

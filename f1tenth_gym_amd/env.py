@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _ffi
 from .core import DEFAULT_PARAMS
+from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
 from .sim import Integrator, Simulator
 from .track import Track
@@ -327,6 +328,15 @@ class F110VecEnv(object):
     slot 0, `tracks={slot: track}` one per map slot.  The observation then also carries progress, progress_delta,
     lateral_offset, heading_error and track_segment ([E][A] each; obs_fields selects among them too — by default all of them), and
     reward='progress' makes the reward the ego's progress_delta, [E].
+
+    Compact observations (no reference counterpart): `obs_encoder=` (an ObsEncoder or a dict of its settings) adds
+    obs['encoded'], float32 [E][A][F][D]: pooled lidar sectors and scaled state / track columns, the last F frames stacked
+    (newest last, refilled when an env starts an episode).  It is encoded on the device behind the step and lands in page-locked
+    memory with the rest of the block, so it needs device_logic=True (ValueError otherwise; a host-logic loop calls
+    env.sim.batch.encode_obs(enc) after its step instead).  The array is a persistent view like the others, overwritten by every
+    step() / reset().  'encoded' is also an obs_fields entry (present by default with an encoder); an encoder's track features
+    need a track.  The frame stack lives in device memory of this env (`encoded_stack`, a DeviceArray [E*A][F][D] for
+    device-resident consumers) and is part of snapshot() / restore().
     """
 
     # every key of the reference's observation (base_classes.py:594-610, docs/api/obv.rst:6-14)
@@ -337,7 +347,7 @@ class F110VecEnv(object):
     _EPISODE = ("lap_times", "lap_counts", "toggle_list", "near_starts", "checkpoint_done")
 
     def __init__(self, num_envs, auto_reset=False, device_logic=False, obs_fields=None, copy_obs=False,
-                 episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, **kwargs):
+                 episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, **kwargs):
         self.num_envs = int(num_envs)
         self.seed = kwargs.get('seed', 12345)
         self.map_name, self.map_path = _resolve_map_path(kwargs)
@@ -354,7 +364,19 @@ class F110VecEnv(object):
         self.reward_mode = _reward_mode(kwargs.get('reward', 'timestep'))
         if self.reward_mode == 'progress' and not tracks:
             raise ValueError("reward='progress' needs a track (track= or tracks=)")
-        self.obs_fields = tuple((self._ALL + (self._TRACK if tracks else ())) if obs_fields is None else obs_fields)
+        self.obs_encoder = None if obs_encoder is None else ObsEncoder.coerce(obs_encoder)
+        self.obs_fields = tuple((self._ALL + (self._TRACK if tracks else ()) + (("encoded",) if self.obs_encoder is not None else ()))
+                                if obs_fields is None else obs_fields)
+        if "encoded" in self.obs_fields and self.obs_encoder is None:
+            raise ValueError("the obs_fields entry 'encoded' needs obs_encoder=")
+        if self.obs_encoder is not None:
+            if not self.device_logic:
+                raise ValueError("obs_encoder= needs device_logic=True (a host-logic loop calls env.sim.batch.encode_obs(enc) after its step)")
+            if self.obs_encoder.needs_track and not tracks:
+                raise ValueError("the encoder's track features need a track (track= or tracks=)")
+            self.obs_encoder.check_beams(kwargs.get('num_beams', 1080))
+        self._encode = self.obs_encoder is not None and "encoded" in self.obs_fields
+        self.encoded_stack = None
         if not tracks and any(f in self._TRACK for f in self.obs_fields):
             raise ValueError("the track fields of obs_fields need a track (track= or tracks=)")
         self._lap = _LapLogic(self.num_envs, self.num_agents, self.ego_idx)
@@ -423,8 +445,8 @@ class F110VecEnv(object):
                 obs[f] = np.zeros((E, A))      # base_classes.py:603: always 0. in the reference
             elif f == "scans":
                 obs[f] = v["scans"].reshape(E, A, -1)
-            elif f in _TRACK_OBS:
-                continue                       # (the track block, below)
+            elif f in _TRACK_OBS or f == "encoded":
+                continue                       # (the track block and the encoder's block, below)
             else:
                 obs[f] = v[f].reshape(E, A)
         info = {}
@@ -441,6 +463,13 @@ class F110VecEnv(object):
                     obs[f] = tv[_TRACK_OBS[f]].reshape(E, A)
             if self.reward_mode == 'progress':
                 reward = tv["ds"].reshape(E, A)[:, self.ego_idx]
+        if self._encode:   # the frame stack in device memory, and the page-locked copy every step's encode ends with
+            shape = self.obs_encoder.shape(E * A)
+            self.encoded_stack = b.device_array(shape, np.float32)
+            self._enc_pinned = b.pinned_empty(shape, np.float32)
+            self._enc_pinned[...] = 0.0
+            self._enc_fill = True          # the first encode, and the one after a restore without a saved stack
+            obs["encoded"] = self._enc_pinned.reshape((E, A) + shape[1:])
         self._ret_views = (obs, reward, v["done"].view(np.bool_), info)
 
     def update_params_batch(self, params):
@@ -512,18 +541,26 @@ class F110VecEnv(object):
     def snapshot(self):
         """an exact copy of the vector env: simulator state (device blob, episode columns included with device_logic), the
         host lap bookkeeping, the start poses and the last (obs, reward, done, info)"""
-        return {"sim": self.sim.snapshot(), "host": copy.deepcopy((self._lap, self._start_poses, self._last))}
+        snap = {"sim": self.sim.snapshot(), "host": copy.deepcopy((self._lap, self._start_poses, self._last))}
+        if self._encode:
+            snap["encoded_stack"] = None if self._enc_fill else self.encoded_stack.download()
+        return snap
 
     def restore(self, snap):
         """back to a snapshot(); returns the (obs, reward, done, info) of the step before it.  With device_logic the page-locked
         views step() hands out show that observation again."""
         self.sim.restore(snap["sim"])
         self._lap, self._start_poses, last = copy.deepcopy(snap["host"])
+        if self._encode:   # the frame stack as it was; a snapshot without one: the next encode fills every frame
+            stack = snap.get("encoded_stack")
+            self._enc_fill = stack is None
+            if stack is not None:
+                self.encoded_stack.upload(stack)
         if self.device_logic and last is not None and not self.copy_obs:
             obs, r, done, info = self._ret_views   # write the saved observation into the block's views
             for mine, saved in ((obs, last[0]), (info, last[3])):
                 for k, v in mine.items():
-                    if isinstance(v, np.ndarray):
+                    if isinstance(v, np.ndarray) and k in saved:   # (a snapshot taken without an encoder has no 'encoded')
                         np.copyto(v, saved[k])
             np.copyto(done, last[2])
             if isinstance(r, np.ndarray):
@@ -538,7 +575,15 @@ class F110VecEnv(object):
             self.sim._noise.ensure(b, self.sim._steps_since_full_reset + 1)
         if actions is not None and actions is not self.action_buffer:
             hb.actions[...] = np.asarray(actions, dtype=np.float64).reshape(hb.actions.shape)
-        b.step_host(hb, None, auto_reset=self.auto_reset, sync=sync, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait)
+        if self._encode:
+            # one wait per step: the step enqueued without a wait, the encode and its copy into page-locked memory behind it
+            b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait)
+            b.encode_obs_device(self.obs_encoder, self.encoded_stack, fill=self._enc_fill, pinned=self._enc_pinned)
+            self._enc_fill = False
+            if sync:
+                b.sync()
+        else:
+            b.step_host(hb, None, auto_reset=self.auto_reset, sync=sync, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait)
         self.sim._steps_since_full_reset += 1
         if not sync:
             return None

@@ -91,6 +91,9 @@ class ShardedVecEnv(object):
         if kwargs.get('random_start') is not None:   # one sampler for every shard (seed=None: its entropy drawn once), env_base per shard
             from .reset_sampler import ResetSampler
             kwargs['random_start'] = ResetSampler.coerce(kwargs['random_start'])
+        if kwargs.get('obs_encoder') is not None:    # one encoder for every shard; obs['encoded'] is concatenated along the env axis
+            from .obs_encoder import ObsEncoder
+            kwargs['obs_encoder'] = ObsEncoder.coerce(kwargs['obs_encoder'])
         self._workers = [_Worker(k) for k in range(K)]
         self.shards = [None] * K
 

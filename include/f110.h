@@ -660,6 +660,64 @@ typedef struct f110_render_spec {
 int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t *h_agents, int32_t n_frames,
                        uint8_t *d_classes, uint8_t *d_rgb, const uint8_t *h_palette);
 
+/* ---- compact observations (no reference counterpart: what RL setups built on the reference compute on the host from
+ * obs['scans'] before a policy sees it: a few pooled ranges, a few state columns, the last few frames stacked) ----
+ * An encode turns the observation of the last step into out [N][F][D] float32.  It runs only when called, changes no simulator
+ * state, and no step launches anything for it.  Every operation is one correctly rounded IEEE operation (compare, float64 add,
+ * float64 divide, float64 -> float32 round-to-nearest-even); there is no trigonometry and no libm call, so results are defined
+ * bit for bit.
+ * Lidar part: beams [beam_lo, beam_hi) of the handle's B (0, 0 = all), W = beam_hi - beam_lo, cut into K = sectors sectors,
+ *   0 <= K <= W (K = 0: no lidar part).  Sector k covers beams b0 = beam_lo + floor(k W / K) .. b1 = beam_lo + floor((k + 1) W / K)
+ *   exclusive (integer arithmetic; never empty since K <= W).  v = pool of the sector:
+ *     MIN     the smallest range; NaN if any beam is NaN (np.min)
+ *     MEAN    ranges added in ascending beam order in float64, uncontracted, starting from the first beam, divided by b1 - b0
+ *     CENTER  beam (b0 + b1 - 1) >> 1
+ *   value = (float)(minimum(v, range_clip) / range_scale): minimum propagates NaN (np.minimum), the division is float64.
+ * Feature part: the set bits of `features`, in ascending bit order behind the lidar values, each (float)(x / feat_scale[bit]):
+ *     VX = state[3], STEER = state[2], YAW_RATE = state[5], SLIP = state[6], COLLISION = the collisions column,
+ *     LATERAL, HEADING_ERROR, DS = the track columns of the step (f110_track_enable; F110_ERR_STATE while tracking is off).
+ *   feat_scale entries of bits that are not set are ignored.  D = K + popcount(features).
+ * Frames: F = frames, 1..16.  out[n][F-1] is the newest frame, out[n][0] the oldest.  A call moves agent n's frames 1..F-1 to
+ *   0..F-2 and writes the new frame last.  The stack is the CALLER's buffer: the handle keeps no copy of it (and the state blobs
+ *   do not contain it); pass the same buffer to every call.
+ *   Episode starts: an agent whose step_count is 1 holds the first observation of an episode (after f110_reset + one step, and
+ *   on the first step after an in-step re-seat): all F of its frames are set to the new frame.  An agent whose step_count is 0
+ *   was re-seated inside the step just taken: its scans are still the finished episode's terminal ones, and it is encoded like
+ *   any other agent (shift; lidar from those terminal scans, the feature columns as they stand after the re-seat).  Callers who
+ *   bootstrap from terminal observations use the separate re-seat (f110_reset_collided_device) and encode in front of it.
+ *   F110_OBS_FILL in flags treats every agent as an episode start: for the first call on a fresh buffer, and after a state load
+ *   into a buffer of unknown content.
+ * Refused (F110_ERR_INVALID, nothing launched or written): beam_lo < 0, beam_hi > B, beam_lo >= beam_hi (other than 0, 0),
+ *   K < 0 or K > W, an unknown pool, feature bit or flag, F outside 1..16, range_clip or range_scale not finite and > 0 (checked
+ *   when K > 0), a zero or non-finite feat_scale of a set bit, D = 0, F * D > F110_OBS_MAX_STACK, a null output or one that is not
+ *   16-byte aligned. */
+enum { F110_OBS_POOL_MIN = 0, F110_OBS_POOL_MEAN = 1, F110_OBS_POOL_CENTER = 2 };
+enum { F110_OBS_VX = 1, F110_OBS_STEER = 2, F110_OBS_YAW_RATE = 4, F110_OBS_SLIP = 8, F110_OBS_COLLISION = 16, F110_OBS_LATERAL = 32,
+       F110_OBS_HEADING_ERROR = 64, F110_OBS_DS = 128, F110_OBS_NFEATURES = 8,
+       F110_OBS_TRACK_FEATURES = F110_OBS_LATERAL | F110_OBS_HEADING_ERROR | F110_OBS_DS, F110_OBS_ALL_FEATURES = 255 };
+enum { F110_OBS_FILL = 1 };
+enum { F110_OBS_MAX_FRAMES = 16, F110_OBS_MAX_STACK = 8192 /* floats per agent: a wave keeps its agent's stack in LDS */ };
+typedef struct f110_obs_spec {
+    int32_t beam_lo, beam_hi;   /* 0, 0 = all beams */
+    int32_t sectors;            /* K */
+    int32_t pool;               /* F110_OBS_POOL_* */
+    int32_t features;           /* F110_OBS_* bits */
+    int32_t frames;             /* F */
+    int32_t flags;              /* F110_OBS_FILL */
+    int32_t pad;
+    double range_clip, range_scale;
+    double feat_scale[F110_OBS_NFEATURES];   /* indexed by bit number */
+} f110_obs_spec;
+/* d_out [N][F][D] float32 in device memory.  Asynchronous on the handle's stream; right behind a two-block step it runs per env
+ * block on the block's own stream (as f110_scan_policy_device does), so a device-resident loop keeps its blocks and the results
+ * are those of one block.  h_pinned (or NULL): page-locked memory of f110_host_alloc (anything else: F110_ERR_INVALID) of the
+ * same size that receives a copy of the whole stack, asynchronously behind the encode; f110_sync completes it. */
+int f110_obs_encode_device(f110_sim *h, const f110_obs_spec *spec, float *d_out, float *h_pinned);
+/* unit form on host arrays (with or without a map; spec->beam_* refer to the handle's B): h_scans [m][B], h_cols [m][8] = the
+ * eight feature sources in bit order (all eight may be asked for), h_step_count [m], h_inout [m][F][D] updated in place. */
+int f110_obs_encode_batch(f110_sim *h, const f110_obs_spec *spec, const double *h_scans, const double *h_cols, const int32_t *h_step_count,
+                          int32_t m, float *h_inout);
+
 #ifdef __cplusplus
 }
 #endif
