@@ -11,7 +11,10 @@ Two policies:
     package on torch's side), running on the simulator's own stream (`torch.cuda.ExternalStream(views["stream"])`) and writing the
     action buffer in place.
 
-    python examples/rl_loop_device.py [--envs 4096] [--steps 500] [--torch]
+--opponent gap: the policy drives each env's car 0 only; the other cars drive themselves with a follow-the-gap controller
+(`BatchSim.set_controllers` / `follow_gap_device`) that overwrites their rows of the action buffer on the device.
+
+    python examples/rl_loop_device.py [--envs 4096] [--steps 500] [--torch] [--opponent gap]
 """
 import argparse
 import os
@@ -38,6 +41,7 @@ def main(argv=None):
     ap.add_argument("--agents", type=int, default=2)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--torch", action="store_true")
+    ap.add_argument("--opponent", choices=("policy", "gap"), default="policy", help="who drives the cars other than car 0")
     args = ap.parse_args(argv)
     E, A = args.envs, args.agents
     N = E * A
@@ -77,6 +81,18 @@ def main(argv=None):
         def policy():
             sim.scan_policy_device(actions)
 
+    if args.opponent == "gap":                # cars 1 .. A-1 of every env: scripted, behind the policy's write of the buffer
+        assign = np.zeros((E, A), dtype=np.int32)
+        assign[:, 0] = -1
+        sim.set_controllers(assign, [amd.GapFollower()])
+        ego_policy = policy
+
+        def policy():
+            ego_policy()
+            if args.torch:
+                sim.fence()                   # (torch wrote on the main stream: the controllers follow it there)
+            sim.follow_gap_device(actions)
+
     sim.episode_step_device(actions)          # the first observation
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -89,10 +105,12 @@ def main(argv=None):
     laps = ep["lap_counts"].download()
     print("%d envs x %d agents, %d steps: %.3f ms per step, %.1f M agent-steps/s; %d env resets, %d envs done right now, max lap count %.0f (%s policy)"
           % (E, A, args.steps, dt / args.steps * 1e3, N * args.steps / dt / 1e6, int(d_resets.download()[0]), done_now, laps.max(),
-             "torch MLP via DLPack" if args.torch else "built-in scan"))
+             ("torch MLP via DLPack" if args.torch else "built-in scan") + (", gap-following opponents" if args.opponent == "gap" else "")))
     if args.torch:
         # the tensors made by from_dlpack view the simulator's memory: they go first (BatchSim.close() refuses while they live)
         del scans_t, act_t, policy
+        if args.opponent == "gap":
+            del ego_policy
         torch.cuda.synchronize()
     sim.close()
     return N * args.steps / dt

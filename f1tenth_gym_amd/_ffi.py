@@ -70,6 +70,19 @@ OBS_POOL_MIN, OBS_POOL_MEAN, OBS_POOL_CENTER = 0, 1, 2
 OBS_FILL, OBS_MAX_FRAMES, OBS_MAX_STACK = 1, 16, 8192
 
 
+class GapFollowerSpec(C.Structure):
+    """struct f110_gap_follower"""
+    _fields_ = [("beam_lo", C.c_int32), ("beam_hi", C.c_int32), ("smooth", C.c_int32), ("target", C.c_int32),
+                ("range_clip", C.c_double), ("bubble_radius", C.c_double), ("gap_threshold", C.c_double),
+                ("steer_gain", C.c_double), ("steer_max", C.c_double), ("v_lo", C.c_double), ("v_hi", C.c_double), ("d_ref", C.c_double),
+                ("steer_slow", C.c_double), ("v_turn", C.c_double), ("v_blocked", C.c_double)]
+
+
+GAP_TARGET_CENTER, GAP_TARGET_FURTHEST = 0, 1
+GAP_MAX_SPECS, GAP_MAX_SMOOTH, GAP_MAX_WINDOW = 8, 63, 4096
+STEP_SCRIPTED = 64
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -206,6 +219,9 @@ PROTOTYPES = {
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
     "f110_obs_encode_device": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p, C.c_void_p]),
     "f110_obs_encode_batch": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), _dp, _dp, _i32p, C.c_int32, C.c_void_p]),
+    "f110_controllers_set": (C.c_int, [C.c_void_p, C.POINTER(GapFollowerSpec), C.c_int32, _i32p]),
+    "f110_follow_gap_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "f110_follow_gap_batch": (C.c_int, [C.c_void_p, C.POINTER(GapFollowerSpec), _dp, _i32p, C.c_int32, _dp, _i32p]),
     "f110_pcg64_seed_spawn": (C.c_int, [_u32p, C.c_int32, C.c_uint64, C.c_int32, _u64p]),
     "f110_reset_sampler_set": (C.c_int, [C.c_void_p, C.c_void_p, _u64p]),
     "f110_reset_sample": (C.c_int, [C.c_void_p, _u8p]),

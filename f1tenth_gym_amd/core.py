@@ -697,10 +697,13 @@ class BatchSim(object):
         n = max(o[0], 1.0)
         return int(o[0]), o[1] / n, o[2] / n
 
-    def step_host(self, hb, actions=None, auto_reset=False, sync=True, mapped_actions=True, spin=False, fuse=True, poll=True):
+    def step_host(self, hb, actions=None, auto_reset=False, sync=True, mapped_actions=True, spin=False, fuse=True, poll=True, scripted=False):
         """f110_step_host: `actions` (None: hb.actions as the caller filled it in place) up, the step, the
-        episode logic if episode_init was called, hb's fields down — one ABI call."""
+        episode logic if episode_init was called, hb's fields down — one ABI call.  scripted: the armed controllers
+        (set_controllers) replace their agents' rows on the device before the step."""
         flags = (_ffi.STEP_AUTO_RESET if auto_reset else 0) | (0 if sync else _ffi.STEP_NO_SYNC) | (_ffi.STEP_SPIN_WAIT if spin else 0)
+        if scripted:
+            flags |= _ffi.STEP_SCRIPTED
         if not fuse:
             flags |= _ffi.STEP_NO_FUSE
         if poll:
@@ -1171,6 +1174,55 @@ class BatchSim(object):
         spec = enc.spec(fill)
         check(_ffi.lib().f110_obs_encode_batch(self._h, C.byref(spec), dptr(scans), dptr(cols), i32ptr(sc), m, st.ctypes.data), self._h)
         return st
+
+    # ------------------------------------------------------------------ scripted cars (f110_controllers_set / f110_follow_gap_*)
+    def set_controllers(self, assign, controllers):
+        """arm follow-the-gap controllers: `controllers` a list of 1 .. 8 gap_follower.GapFollower (or dicts of their settings),
+        `assign` int32 [N] (or [E][A]): -1 = external, else the index of the agent's controller.  Nothing is launched; the
+        controllers act in follow_gap_device and in step_host(scripted=True)."""
+        from .gap_follower import GapFollower, MAX_SPECS
+        ctrls = [GapFollower.coerce(c) for c in controllers]
+        if not (1 <= len(ctrls) <= MAX_SPECS):
+            raise ValueError("1 .. %d controllers, got %d" % (MAX_SPECS, len(ctrls)))
+        a = np.ascontiguousarray(np.asarray(assign).reshape(-1), dtype=np.int32)
+        if a.shape != (self.N,):
+            raise ValueError("assign must hold one entry per agent (%d), got %d" % (self.N, a.size))
+        specs = (_ffi.GapFollowerSpec * len(ctrls))(*[c.spec(self.B) for c in ctrls])
+        check(_ffi.lib().f110_controllers_set(self._h, specs, len(ctrls), i32ptr(a)), self._h)
+        self.controllers, self.controller_assign = ctrls, a
+
+    def clear_controllers(self):
+        """disarm the controllers"""
+        check(_ffi.lib().f110_controllers_set(self._h, None, 0, None), self._h)
+        self.controllers, self.controller_assign = [], None
+
+    def follow_gap_device(self, d_actions):
+        """the armed controllers write their agents' rows of the device action buffer [N][2] from the last step's scans; the
+        other rows are left alone.  Enqueued on the handle's stream, per env block behind a two-block step (no host wait)."""
+        a = d_actions.ptr if isinstance(d_actions, DeviceArray) else int(d_actions)
+        check(_ffi.lib().f110_follow_gap_device(self._h, a), self._h)
+
+    def follow_gap(self, scans, controller=None, step_count=None, info=False):
+        """unit form on host arrays: scans [m][B] -> actions [m][2] (and, with info, int32 [m][5]: closest beam, bubble
+        half-width, gap start, gap end, target beam, relative to the window; -1s for a blocked row).  step_count [m]: rows
+        with 0 get (0, 0)."""
+        from .gap_follower import GapFollower
+        c = GapFollower() if controller is None else GapFollower.coerce(controller)
+        scans = as_f64(scans)
+        m = scans.shape[0]
+        if scans.shape != (m, self.B):
+            raise ValueError("scans must be [m][%d]" % self.B)
+        sc = None
+        if step_count is not None:
+            sc = np.ascontiguousarray(step_count, dtype=np.int32)
+            if sc.shape != (m,):
+                raise ValueError("step_count must be [m]")
+        act = np.zeros((m, 2))
+        inf = np.zeros((m, 5), dtype=np.int32) if info else None
+        spec = c.spec(self.B)
+        check(_ffi.lib().f110_follow_gap_batch(self._h, C.byref(spec), dptr(scans), None if sc is None else i32ptr(sc), m, dptr(act),
+                                               None if inf is None else i32ptr(inf)), self._h)
+        return (act, inf) if info else act
 
     # ------------------------------------------------------------------ the reference's example policy
     def pure_pursuit_batch(self, waypoints, poses, lookahead, vgain, wheelbase, max_reacquire=20.0):

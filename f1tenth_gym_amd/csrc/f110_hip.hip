@@ -203,6 +203,10 @@ struct f110_sim {
     HostBlock trk_hb{};                   // ... and their device views (the trk_* fields)
     bool trk_pinned_on = false;
     const float *obs_pinned = nullptr;    // f110_obs_encode_device: the page-locked block its last copy went to
+    // scripted cars (f110_controllers_set): the specs and the per-agent assignment in device memory; gap_specs == 0: disarmed
+    GapSpec *d_gap_specs = nullptr;
+    int32_t *d_gap_assign = nullptr;
+    int gap_specs = 0, gap_max_w = 0;
     // rendering (f110_render_device): slot 0's occupancy grid, the slot table as last uploaded, per-frame / per-agent records
     uint8_t *d_occ0 = nullptr;
     std::vector<RenderSlot> render_slots;
@@ -319,6 +323,7 @@ static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &
 // ---- env blocks: on which streams, over which env ranges, does a call launch? -------------------------------
 constexpr int kMaxEnvBlocks = 16;
 struct EnvBlock { hipStream_t stream; int e0, count; };   // envs [e0, e0 + count) on `stream`
+static void gap_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions);   // (below, with the controllers)
 struct EnvBlocks {
     EnvBlock b[kMaxEnvBlocks];
     int n = 0;
@@ -968,6 +973,8 @@ void f110_destroy(f110_sim *h)
         if (ts.d_cols) (void)hipFree(ts.d_cols);
         if (ts.d_pts) (void)hipFree(ts.d_pts);
     }
+    if (h->d_gap_specs) (void)hipFree(h->d_gap_specs);
+    if (h->d_gap_assign) (void)hipFree(h->d_gap_assign);
     {
         void *rp[] = {h->d_occ0, h->d_render_slots, h->d_render_frames, h->d_render_cars, h->d_render_agents, h->d_render_stage};
         for (void *p : rp)
@@ -2182,9 +2189,12 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     if (!episode && (out->lap_times || out->lap_counts || out->toggles || out->current_time || out->near_starts ||
                      out->checkpoint_done || out->done || (flags & F110_STEP_AUTO_RESET)))
         return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
+    const bool scripted = (flags & F110_STEP_SCRIPTED) != 0;
+    if (scripted && h->gap_specs == 0) return fail(h, F110_ERR_STATE, "f110_step_host: F110_STEP_SCRIPTED without controllers (f110_controllers_set)");
     ENTER(h);
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
-    const bool mapped_actions = (flags & F110_STEP_ACTIONS_MAPPED) != 0;
+    // scripted cars: the actions always go through the staging buffer, where the controllers overwrite their agents' rows
+    const bool mapped_actions = (flags & F110_STEP_ACTIONS_MAPPED) != 0 && !scripted;
     if (!h->hb_valid || std::memcmp(&h->hb_host, out, sizeof *out) != 0 || h->hb_actions_host != (mapped_actions ? h_actions : nullptr)) {
         HostBlock d{};
         void *p = nullptr;
@@ -2229,7 +2239,7 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     const auto t_in = std::chrono::steady_clock::now();
     // a tiny batch is one launch whose last workgroup writes the block (k_step_tiny): its completion is ONE word stored by one
     // workgroup, so the host always waits on that word (no runtime call on the way out)
-    const bool tiny = tiny_applies(h) && !(flags & (F110_STEP_NO_FUSE | F110_STEP_NO_SYNC)) && !h->dev.reseat_poses;
+    const bool tiny = tiny_applies(h) && !(flags & (F110_STEP_NO_FUSE | F110_STEP_NO_SYNC | F110_STEP_SCRIPTED)) && !h->dev.reseat_poses;
     const bool spin = ((flags & F110_STEP_SPIN_WAIT) || tiny) && !(flags & F110_STEP_NO_SYNC) && (!out->scans || (h->hb_valid && h->hb_scans_by_kernel));
     if (spin && !h->hb_seq_host) {
         HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&h->hb_seq_host), 64, hipHostMallocDefault));
@@ -2242,6 +2252,10 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
         d_act = h->hb_actions_dev;   // k_integrate reads the [N][2] block over PCIe, once, coalesced
     else if (!tiny)                  // (k_step_tiny gets the actions as kernel arguments)
         HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
+    if (scripted) {   // the scans are the last step's, the staged rows of scripted agents are replaced, external rows stay
+        gap_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions);
+        HIPCHK(h, hipGetLastError());
+    }
     const int A = h->cfg.num_agents;
     StepRequest rq;
     rq.tiny = tiny;
@@ -3782,6 +3796,155 @@ int f110_obs_encode_batch(f110_sim *h, const f110_obs_spec *spec, const double *
     obs_launch(j, h->stream);
     HIPCHK(h, hipGetLastError());
     TRY(s.down(h_inout, dout, (size_t)m * per_agent));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- scripted cars: follow the gap (include/f110.h) --------------------------------------------------------------------------
+// the spec's refusals; on success the kernel's spec
+static int gap_check_spec(f110_sim *h, const f110_gap_follower *g, GapSpec &o)
+{
+    if (!g) return fail(h, F110_ERR_INVALID, "gap follower: null spec");
+    const int B = h->cfg.num_beams;
+    int lo = g->beam_lo, hi = g->beam_hi;
+    if (lo == 0 && hi == 0) hi = B;
+    if (lo < 0 || hi > B || lo >= hi) return fail(h, F110_ERR_INVALID, "gap follower: beams [%d, %d) are not a range within the %d beams", g->beam_lo, g->beam_hi, B);
+    const int W = hi - lo;
+    if (W > kGapMaxWindow) return fail(h, F110_ERR_INVALID, "gap follower: a window of %d beams exceeds %d", W, kGapMaxWindow);
+    if (B < 2) return fail(h, F110_ERR_INVALID, "gap follower: needs at least 2 beams (the angle increment)");
+    if (g->smooth < 1 || g->smooth > F110_GAP_MAX_SMOOTH || !(g->smooth & 1) || g->smooth > W)
+        return fail(h, F110_ERR_INVALID, "gap follower: smooth = %d must be odd, within 1..%d and at most the %d beams of the window", g->smooth, (int)F110_GAP_MAX_SMOOTH, W);
+    if (g->target != F110_GAP_TARGET_CENTER && g->target != F110_GAP_TARGET_FURTHEST) return fail(h, F110_ERR_INVALID, "gap follower: unknown target %d", g->target);
+    const double d[] = {g->range_clip, g->bubble_radius, g->gap_threshold, g->steer_gain, g->steer_max, g->v_lo, g->v_hi, g->d_ref, g->steer_slow, g->v_turn, g->v_blocked};
+    for (double x : d)
+        if (!std::isfinite(x)) return fail(h, F110_ERR_INVALID, "gap follower: every setting must be finite");
+    if (!(g->range_clip > 0) || !(g->d_ref > 0)) return fail(h, F110_ERR_INVALID, "gap follower: range_clip and d_ref must be > 0");
+    if (g->bubble_radius < 0 || g->gap_threshold < 0 || g->steer_slow < 0) return fail(h, F110_ERR_INVALID, "gap follower: bubble_radius, gap_threshold and steer_slow must be >= 0");
+    if (g->steer_max < 0) return fail(h, F110_ERR_INVALID, "gap follower: steer_max must be >= 0");
+    if (g->v_lo > g->v_hi) return fail(h, F110_ERR_INVALID, "gap follower: v_lo exceeds v_hi");
+    o = GapSpec{};
+    o.lo = lo, o.W = W, o.S = g->smooth, o.target = g->target;
+    o.clip = g->range_clip, o.bubble = g->bubble_radius, o.thresh = g->gap_threshold;
+    o.steer_gain = g->steer_gain, o.steer_max = g->steer_max, o.v_lo = g->v_lo, o.v_hi = g->v_hi, o.d_ref = g->d_ref;
+    o.steer_slow = g->steer_slow, o.v_turn = g->v_turn, o.v_blocked = g->v_blocked;
+    return F110_OK;
+}
+
+// LDS per wave (v and p of the widest window) and the workgroup size of 1..4 waves that packs the most waves into a CU's 160 KiB
+static void gap_plan_lds(GapJob &j, int max_w)
+{
+    j.wave_bytes = (2 * max_w * 8 + 15) & ~15;
+    int best = 1, best_waves = 0;
+    for (int w = 1; w <= 4; ++w) {
+        if ((long long)w * j.wave_bytes > 65536) break;
+        const int per_cu = std::min(32, (int)(163840 / ((long long)w * j.wave_bytes)) * w);
+        if (per_cu >= best_waves) {
+            best_waves = per_cu;
+            best = w;
+        }
+    }
+    j.waves = best;
+}
+
+static void gap_launch(const GapJob &j, hipStream_t st)
+{
+    if (j.n <= 0) return;
+    hipLaunchKernelGGL(k_follow_gap, dim3((unsigned)((j.n + j.waves - 1) / j.waves)), dim3((unsigned)(64 * j.waves)), (size_t)j.waves * j.wave_bytes, st, j);
+}
+
+// the armed controllers over the agents of one env block, into d_actions [N][2]
+static void gap_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions)
+{
+    GapJob j{};
+    j.specs = h->d_gap_specs;
+    j.assign = h->d_gap_assign;
+    j.scans = h->dev.scans;
+    j.step_count = h->dev.step_count;
+    j.actions = d_actions;
+    j.fov = h->cfg.fov;
+    j.B = h->cfg.num_beams;
+    j.i0 = b.e0 * h->cfg.num_agents;
+    j.n = b.count * h->cfg.num_agents;
+    gap_plan_lds(j, h->gap_max_w);
+    gap_launch(j, b.stream);
+}
+
+int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_specs, const int32_t *h_assign)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (n_specs == 0 && !specs && !h_assign) {   // disarm
+        ENTER(h);
+        h->gap_specs = 0;
+        return F110_OK;
+    }
+    if (!specs || !h_assign || n_specs < 1 || n_specs > F110_GAP_MAX_SPECS)
+        return fail(h, F110_ERR_INVALID, "controllers: 1..%d specs and an assignment, or NULL, 0, NULL", (int)F110_GAP_MAX_SPECS);
+    GapSpec gs[kGapMaxSpecs];
+    int max_w = 0;
+    for (int k = 0; k < n_specs; ++k) {
+        TRY(gap_check_spec(h, specs + k, gs[k]));
+        max_w = std::max(max_w, (int)gs[k].W);
+    }
+    const size_t N = (size_t)h->N;
+    for (size_t i = 0; i < N; ++i)
+        if (h_assign[i] < -1 || h_assign[i] >= n_specs) return fail(h, F110_ERR_INVALID, "controllers: assignment[%zu] = %d is outside -1..%d", i, h_assign[i], n_specs - 1);
+    ENTER(h);
+    if (!h->d_gap_specs) TRY(dmalloc(h, &h->d_gap_specs, (size_t)kGapMaxSpecs));
+    if (!h->d_gap_assign) TRY(dmalloc(h, &h->d_gap_assign, N));
+    HIPCHK(h, hipMemcpyAsync(h->d_gap_specs, gs, sizeof(GapSpec) * n_specs, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_gap_assign, h_assign, sizeof(int32_t) * N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (the sources are the caller's and this function's stack)
+    h->gap_specs = n_specs;
+    h->gap_max_w = max_w;
+    return F110_OK;
+}
+
+int f110_follow_gap_device(f110_sim *h, double *d_actions)
+{
+    if (!h || !d_actions) return fail(h, F110_ERR_INVALID, "follow gap: null argument");
+    if (reinterpret_cast<uintptr_t>(d_actions) % 16 != 0) return fail(h, F110_ERR_INVALID, "follow gap: the actions buffer is not 16-byte aligned");
+    if (h->gap_specs == 0) return fail(h, F110_ERR_STATE, "follow gap: no controllers are armed (f110_controllers_set)");
+    EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (an agent reads its own scan row only)
+    TRY(env_blocks_follow(h, w));
+    for (const EnvBlock &b : w) gap_launch_armed(h, b, d_actions);
+    HIPCHK(h, hipGetLastError());
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_follow_gap_batch(f110_sim *h, const f110_gap_follower *spec, const double *h_scans, const int32_t *h_step_count, int32_t m,
+                          double *h_actions, int32_t *h_info)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    GapSpec gs;
+    TRY(gap_check_spec(h, spec, gs));
+    if (!h_scans || !h_actions || m < 0) return fail(h, F110_ERR_INVALID, "follow gap: bad argument");
+    if (m == 0) return F110_OK;
+    ENTER(h);
+    Scratch s(h);
+    const size_t B = (size_t)h->cfg.num_beams;
+    GapSpec *dspec = nullptr;
+    double *ds = nullptr, *da = nullptr;
+    int32_t *dn = nullptr, *di = nullptr;
+    TRY(s.up(&gs, 1, &dspec));
+    TRY(s.up(h_scans, (size_t)m * B, &ds));
+    if (h_step_count) TRY(s.up(h_step_count, (size_t)m, &dn));
+    TRY(s.up((const double *)nullptr, (size_t)m * 2, &da));
+    if (h_info) TRY(s.up((const int32_t *)nullptr, (size_t)m * 5, &di));
+    GapJob j{};
+    j.specs = dspec;
+    j.scans = ds;
+    j.step_count = dn;
+    j.actions = da;
+    j.info = di;
+    j.fov = h->cfg.fov;
+    j.B = (int)B;
+    j.n = m;
+    gap_plan_lds(j, gs.W);
+    gap_launch(j, h->stream);
+    HIPCHK(h, hipGetLastError());
+    TRY(s.down(h_actions, da, (size_t)m * 2));
+    if (h_info) TRY(s.down(h_info, di, (size_t)m * 5));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }

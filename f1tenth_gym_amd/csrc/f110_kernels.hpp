@@ -4068,3 +4068,151 @@ __global__ void __launch_bounds__(256) k_obs_encode(ObsJob j)
     const int tail = head + 4 * nvec;
     if (tail + lane < total) stack[tail + lane] = img[tail + lane];
 }
+
+// ---- follow the gap (f110_controllers_set / f110_follow_gap_*; include/f110.h states the rule, f110_math.hpp gap_* the arithmetic) ----
+// One wave per scripted agent, k_scan_policy's pattern.  A wave whose agent is external leaves after one 4-byte load.  The W beams
+// of the window go through LDS with 64-lane coalesced loads, 12 in flight per lane and the next round's issued before this
+// round's LDS stores, clipped on the way in (v).  From there every pass gives lane l the beams l, l + 64, ...: consecutive lanes
+// read consecutive doubles (ds_read_b64, no bank conflict), and nobody walks the window alone.
+//   smooth + closest point: lane-local first minimum of p = the window mean, kept in LDS next to v; a lexicographic
+//     (value, index) minimum across the wave picks np.argmin's winner
+//   gap: round r's free flags are one ballot; lane r keeps it, so lane r holds the 64 beams [64 r, 64 r + 64) as a bit mask
+//     (W <= 4096 = 64 lanes x 64 bits).  Its summary (runs at either end, longest run) costs as many steps as its longest run, and
+//     gap_run_merge folds the 64 summaries in lane order (xor butterfly: the lane with the bit clear is the left operand)
+//   target FURTHEST: the same (value, index) reduction over the gap's beams, largest value, lowest index
+// LDS per wave: 16 W bytes (v and p), so the workgroup size (1..4 waves) is chosen per launch for the most waves per CU.
+// HBM traffic per scripted agent: 8 W (window) + 4 (assignment) + 4 (step_count) + 16 (action) bytes, plus the spec (cached).
+constexpr int kGapMaxWindow = 4096;
+constexpr int kGapMaxSpecs = 8;
+
+struct GapJob {
+    const GapSpec *specs;        // device memory
+    const int32_t *assign;       // [.] -1 = external, else the spec; null: spec 0 for every agent (unit form)
+    const double *scans;         // [.][B]
+    const int32_t *step_count;   // [.] or null (no agent is fresh)
+    double *actions;             // [.][2]
+    int32_t *info;               // [.][5] or null
+    double fov;
+    int32_t B, i0, n;            // agents [i0, i0 + n)
+    int32_t waves, wave_bytes;   // waves per workgroup; LDS per wave (>= 16 W of every spec)
+};
+
+__global__ void __launch_bounds__(256) k_follow_gap(GapJob j)
+{
+    extern __shared__ double gap_lds[];
+    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+    const int a = (int)blockIdx.x * j.waves + wave;
+    if (a >= j.n) return;
+    const size_t i = (size_t)j.i0 + (size_t)a;
+    int k = j.assign ? j.assign[i] : 0;
+    if (k < 0) return;                       // external: nothing loaded, nothing written
+    k = __builtin_amdgcn_readfirstlane(k);   // (one agent per wave: the spec is read with scalar loads)
+    const GapSpec s = j.specs[k];
+    const int sc = j.step_count ? j.step_count[i] : 1;
+    const int W = s.W;
+    const double *row = j.scans + i * (size_t)j.B + s.lo;
+    double *v = reinterpret_cast<double *>(reinterpret_cast<char *>(gap_lds) + (size_t)wave * (size_t)j.wave_bytes);
+    double *p = v + W;
+    double2 *act = reinterpret_cast<double2 *>(j.actions) + i;
+    int32_t *info = j.info ? j.info + 5 * i : nullptr;
+    if (sc == 0) {   // re-seated inside the step just taken: the scans are the finished episode's
+        if (lane == 0) *act = make_double2(0.0, 0.0);
+        if (info && lane < 5) info[lane] = -1;
+        return;
+    }
+    {
+        constexpr int U = 12;
+        double cur[U], nxt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = lane + 64 * u < W ? row[lane + 64 * u] : 0.;
+        for (int b = lane; b < W; b += 64 * U) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) nxt[u] = b + 64 * (U + u) < W ? row[b + 64 * (U + u)] : 0.;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (b + 64 * u < W) v[b + 64 * u] = gap_clip(cur[u], s.clip);
+#pragma unroll
+            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        }
+    }
+    __builtin_amdgcn_wave_barrier();   // (one wave: its LDS accesses are in order; the barrier only pins the compiler)
+    // ---- smooth, closest point
+    double best = INFINITY;
+    int c = 0x7fffffff;
+    for (int b = lane; b < W; b += 64) {
+        const double pb = gap_window_mean(v, W, s.S, b);
+        p[b] = pb;
+        if (pb < best || c == 0x7fffffff) {
+            best = pb;
+            c = b;
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double ob = __shfl_xor(best, off);
+        const int oc = __shfl_xor(c, off);
+        if (ob < best || (ob == best && oc < c)) {
+            best = ob;
+            c = oc;
+        }
+    }
+    const int half = gap_bubble_half(best, j.fov / (double)(j.B - 1), s.bubble, W);
+    // ---- free beams: lane r keeps round r's ballot
+    unsigned long long mask = 0;
+    const int rounds = (W + 63) >> 6;
+    for (int r = 0; r < rounds; ++r) {
+        const int b = 64 * r + lane;
+        const bool fr = b < W && gap_free(p[b < W ? b : 0], b, c, half, s.thresh);
+        const unsigned long long m = __ballot(fr);
+        if (lane == r) mask = m;
+    }
+    const int left = W - 64 * lane;
+    GapRun run = gap_run_of_mask(mask, 64 * lane, left < 0 ? 0 : (left < 64 ? left : 64));
+    if (left <= 0) run.start = W;   // (empty chunks sit at the window's end: a seam's start is read off the right operand)
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        GapRun o;
+        o.start = __shfl_xor(run.start, off);
+        o.len = __shfl_xor(run.len, off);
+        o.lead = __shfl_xor(run.lead, off);
+        o.trail = __shfl_xor(run.trail, off);
+        o.best = __shfl_xor(run.best, off);
+        o.best_start = __shfl_xor(run.best_start, off);
+        run = (lane & off) ? gap_run_merge(o, run) : gap_run_merge(run, o);
+    }
+    if (info && lane == 0) info[0] = c, info[1] = half;
+    if (run.best == 0) {
+        if (lane == 0) *act = make_double2(0.0, s.v_blocked);
+        if (info && lane >= 2 && lane < 5) info[lane] = -1;
+        return;
+    }
+    const int g0 = run.best_start, g1 = g0 + run.best;
+    int t = (g0 + g1 - 1) >> 1;
+    __builtin_amdgcn_wave_barrier();
+    if (s.target == GAP_TARGET_FURTHEST) {
+        double far = -INFINITY;
+        t = 0x7fffffff;
+        for (int b = g0 + lane; b < g1; b += 64) {
+            const double pb = p[b];
+            if (pb > far || t == 0x7fffffff) {
+                far = pb;
+                t = b;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double of = __shfl_xor(far, off);
+            const int ot = __shfl_xor(t, off);
+            if (ot != 0x7fffffff && (t == 0x7fffffff || of > far || (of == far && ot < t))) {
+                far = of;
+                t = ot;
+            }
+        }
+    }
+    if (lane == 0) {
+        double steer, speed;
+        gap_action(s, gap_beam_angle(j.fov, j.B, s.lo + t), p[t], steer, speed);
+        *act = make_double2(steer, speed);
+        if (info) info[2] = g0, info[3] = g1, info[4] = t;
+    }
+}

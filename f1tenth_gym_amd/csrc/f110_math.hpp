@@ -1261,4 +1261,157 @@ F110_HD void obs_update_stack(const ObsRowSpec &s, const double *row, const doub
     for (int j = 0; j < D; ++j) stack[(size_t)(F - 1) * D + j] = obs_element(s, row, cols, stride, j);
 }
 
+// ------------------------------------------------------------------ follow the gap (include/f110.h, f110_gap_follower)
+// No reference counterpart.  Compares, float64 adds, multiplies and divides, one ceil: no libm, nothing to contract.
+enum { GAP_TARGET_CENTER = 0, GAP_TARGET_FURTHEST = 1 };
+
+struct GapSpec {
+    int32_t lo, W;        // first beam of the window, beams in it
+    int32_t S, target;    // smoothing length (odd), GAP_TARGET_*
+    double clip, bubble, thresh;
+    double steer_gain, steer_max, v_lo, v_hi, d_ref, steer_slow, v_turn, v_blocked;
+};
+
+// step 1: the clipped range; a NaN beam counts as an obstacle at the car
+F110_HD double gap_clip(double r, double clip) { return r != r ? 0.0 : (r < clip ? r : clip); }
+
+// step 2: the mean of the clipped ranges v[a .. b) around beam i, every window summed on its own in ascending order
+F110_HD double gap_window_mean(const double *v, int W, int S, int i)
+{
+    const int h = S >> 1;
+    const int a = i - h > 0 ? i - h : 0, b = i + h + 1 < W ? i + h + 1 : W;
+    double sum = 0.0;
+    for (int k = a; k < b; ++k) sum = sum + v[k];
+    return sum / (double)(b - a);
+}
+
+// step 4: the bubble's half-width in beams around the closest point (smoothed range pc)
+F110_HD int gap_bubble_half(double pc, double inc, double radius, int W)
+{
+    const double den = pc * inc;
+    const double kb = den > 0.0 ? radius / den : INFINITY;
+    if (!(kb < (double)W)) return W;
+    return (int)ceil(kb);
+}
+
+// step 5: is beam i (smoothed range pi) free?
+F110_HD bool gap_free(double pi, int i, int c, int half, double thresh)
+{
+    const int d = i > c ? i - c : c - i;
+    return d > half && pi > thresh;
+}
+
+// the runs of free beams of a contiguous chunk [start, start + len): the run at its lower end, the run at its upper end and its
+// longest run (lowest start on equal length).  lead == len says every beam is free.  An empty chunk (len 0) is the identity.
+struct GapRun {
+    int32_t start, len, lead, trail, best, best_start;
+};
+
+// a chunk of up to 64 beams from its free bits (bit k = beam start + k; bits at and above len are clear)
+F110_HD GapRun gap_run_of_mask(unsigned long long m, int start, int len)
+{
+    GapRun r;
+    r.start = start;
+    r.len = len;
+    r.lead = ~m ? (int)__builtin_ctzll(~m) : 64;
+    const unsigned long long top = len > 0 ? (m << (64 - len)) : 0ull;   // the chunk's last beam in bit 63
+    r.trail = ~top ? (int)__builtin_clzll(~top) : 64;
+    if (len == 0) r.lead = r.trail = 0;
+    // x keeps the positions from which at least `best` free bits run upwards
+    unsigned long long x = m;
+    int best = 0, pos = 0;
+    while (x) {
+        ++best;
+        pos = (int)__builtin_ctzll(x);
+        x &= x >> 1;
+    }
+    r.best = best;
+    r.best_start = start + pos;
+    return r;
+}
+
+// a followed directly by b (a.start + a.len == b.start): associative.  The candidates for the longest run come in ascending
+// start order (a's, the run across the seam, b's), so a later one wins only when it is strictly longer.
+F110_HD GapRun gap_run_merge(const GapRun &a, const GapRun &b)
+{
+    GapRun r;
+    r.start = a.start;
+    r.len = a.len + b.len;
+    r.lead = a.lead == a.len ? a.len + b.lead : a.lead;
+    r.trail = b.trail == b.len ? b.len + a.trail : b.trail;
+    r.best = a.best;
+    r.best_start = a.best_start;
+    const int seam = a.trail + b.lead;
+    if (seam > r.best) {
+        r.best = seam;
+        r.best_start = b.start - a.trail;
+    }
+    if (b.best > r.best) {
+        r.best = b.best;
+        r.best_start = b.best_start;
+    }
+    return r;
+}
+
+F110_HD double gap_beam_angle(double fov, int B, int beam)
+{
+    const double inc = fov / (double)(B - 1);
+    return -fov / 2. + inc * (double)beam;
+}
+
+// step 7: the action from the target beam's angle and its smoothed range
+F110_HD void gap_action(const GapSpec &s, double angle, double pt, double &steer, double &speed)
+{
+    steer = s.steer_gain * angle;
+    steer = steer > s.steer_max ? s.steer_max : (steer < -s.steer_max ? -s.steer_max : steer);
+    const double f = pt / s.d_ref;
+    speed = s.v_lo + (s.v_hi - s.v_lo) * (f < 1. ? f : 1.);
+    if (fabs(steer) > s.steer_slow) speed = speed < s.v_turn ? speed : s.v_turn;
+}
+
+// one agent's whole rule, serially (the kernel spreads the same pieces over a wave; this is what the unit harness runs).
+// row = the agent's B ranges; v, p: scratch of W doubles each; info (or null) = c, half-width, g0, g1, t (-1s when blocked or
+// when step_count is 0)
+F110_HD void gap_follow_row(const GapSpec &s, const double *row, int B, double fov, int step_count, double *v, double *p,
+                            double *action, int32_t *info)
+{
+    if (info)
+        for (int k = 0; k < 5; ++k) info[k] = -1;
+    if (step_count == 0) {
+        action[0] = 0.0;
+        action[1] = 0.0;
+        return;
+    }
+    const int W = s.W;
+    for (int i = 0; i < W; ++i) v[i] = gap_clip(row[s.lo + i], s.clip);
+    int c = 0;
+    for (int i = 0; i < W; ++i) {
+        p[i] = gap_window_mean(v, W, s.S, i);
+        if (p[i] < p[c]) c = i;
+    }
+    const int half = gap_bubble_half(p[c], fov / (double)(B - 1), s.bubble, W);
+    GapRun all{};
+    for (int i0 = 0; i0 < W; i0 += 64) {
+        const int len = W - i0 < 64 ? W - i0 : 64;
+        unsigned long long m = 0;
+        for (int k = 0; k < len; ++k) m |= (unsigned long long)gap_free(p[i0 + k], i0 + k, c, half, s.thresh) << k;
+        all = gap_run_merge(all, gap_run_of_mask(m, i0, len));
+    }
+    if (info) info[0] = c, info[1] = half;
+    if (all.best == 0) {
+        action[0] = 0.0;
+        action[1] = s.v_blocked;
+        return;
+    }
+    const int g0 = all.best_start, g1 = g0 + all.best;
+    int t = (g0 + g1 - 1) >> 1;
+    if (s.target == GAP_TARGET_FURTHEST) {
+        t = g0;
+        for (int i = g0 + 1; i < g1; ++i)
+            if (p[i] > p[t]) t = i;
+    }
+    if (info) info[2] = g0, info[3] = g1, info[4] = t;
+    gap_action(s, gap_beam_angle(fov, B, s.lo + t), p[t], action[0], action[1]);
+}
+
 }  // namespace f110

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _ffi
 from .core import DEFAULT_PARAMS
+from .gap_follower import coerce_scripted
 from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
 from .sim import Integrator, Simulator
@@ -337,6 +338,13 @@ class F110VecEnv(object):
     step() / reset().  'encoded' is also an obs_fields entry (present by default with an encoder); an encoder's track features
     need a track.  The frame stack lives in device memory of this env (`encoded_stack`, a DeviceArray [E*A][F][D] for
     device-resident consumers) and is part of snapshot() / restore().
+
+    Scripted cars (no reference counterpart): `scripted={slot: GapFollower | dict}` lets every env's car `slot`
+    drive itself with a follow-the-gap controller that runs on the device on the last step's scans; `scripted=(assign,
+    [controllers])` assigns per agent (assign int32 [E][A]: -1 = the caller's action, else an index into controllers).
+    step(actions) keeps its [E][A][2] shape: the rows of scripted cars are ignored and replaced on the device.  A scripted
+    car takes the zero action on the first step of an episode (reset()'s own step, and the step after an in-step re-seat).
+    It needs device_logic=True (ValueError otherwise).  Controllers hold no state: snapshots do not change.
     """
 
     # every key of the reference's observation (base_classes.py:594-610, docs/api/obv.rst:6-14)
@@ -347,7 +355,7 @@ class F110VecEnv(object):
     _EPISODE = ("lap_times", "lap_counts", "toggle_list", "near_starts", "checkpoint_done")
 
     def __init__(self, num_envs, auto_reset=False, device_logic=False, obs_fields=None, copy_obs=False,
-                 episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, **kwargs):
+                 episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, scripted=None, **kwargs):
         self.num_envs = int(num_envs)
         self.seed = kwargs.get('seed', 12345)
         self.map_name, self.map_path = _resolve_map_path(kwargs)
@@ -376,6 +384,14 @@ class F110VecEnv(object):
                 raise ValueError("the encoder's track features need a track (track= or tracks=)")
             self.obs_encoder.check_beams(kwargs.get('num_beams', 1080))
         self._encode = self.obs_encoder is not None and "encoded" in self.obs_fields
+        self.scripted = None
+        if scripted is not None:
+            if not self.device_logic:
+                raise ValueError("scripted= needs device_logic=True (any other loop arms env.sim.batch.set_controllers and calls "
+                                 "BatchSim.follow_gap_device on its device action buffer)")
+            self.scripted = coerce_scripted(scripted, self.num_envs, self.num_agents)
+            for c in self.scripted[1]:
+                c.window(kwargs.get('num_beams', 1080))
         self.encoded_stack = None
         if not tracks and any(f in self._TRACK for f in self.obs_fields):
             raise ValueError("the track fields of obs_fields need a track (track= or tracks=)")
@@ -418,6 +434,8 @@ class F110VecEnv(object):
             b.episode_init(self.ego_idx)
             self._d_actions = b.device_array((self.num_envs * self.num_agents, 2))
             self._build_host_block()
+            if self.scripted is not None:
+                b.set_controllers(*self.scripted)
 
     def _build_host_block(self):
         """the page-locked block f110_step_host fills, and the (obs, reward, done, info) tuple of views into it
@@ -577,13 +595,15 @@ class F110VecEnv(object):
             hb.actions[...] = np.asarray(actions, dtype=np.float64).reshape(hb.actions.shape)
         if self._encode:
             # one wait per step: the step enqueued without a wait, the encode and its copy into page-locked memory behind it
-            b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait)
+            b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
+                        scripted=self.scripted is not None)
             b.encode_obs_device(self.obs_encoder, self.encoded_stack, fill=self._enc_fill, pinned=self._enc_pinned)
             self._enc_fill = False
             if sync:
                 b.sync()
         else:
-            b.step_host(hb, None, auto_reset=self.auto_reset, sync=sync, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait)
+            b.step_host(hb, None, auto_reset=self.auto_reset, sync=sync, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
+                        scripted=self.scripted is not None)
         self.sim._steps_since_full_reset += 1
         if not sync:
             return None

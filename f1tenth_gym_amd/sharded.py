@@ -94,6 +94,11 @@ class ShardedVecEnv(object):
         if kwargs.get('obs_encoder') is not None:    # one encoder for every shard; obs['encoded'] is concatenated along the env axis
             from .obs_encoder import ObsEncoder
             kwargs['obs_encoder'] = ObsEncoder.coerce(kwargs['obs_encoder'])
+        scripted = kwargs.pop('scripted', None)      # scripted cars: the global assignment [E][A], sliced by shard; the controllers shared
+        if scripted is not None:
+            from .gap_follower import coerce_scripted
+            scripted = coerce_scripted(scripted, E, self.num_agents)
+        self.scripted = scripted
         self._workers = [_Worker(k) for k in range(K)]
         self.shards = [None] * K
 
@@ -101,6 +106,8 @@ class ShardedVecEnv(object):
             kw = dict(kwargs, device_id=self.devices[k], env_base=int(self.bounds[k]))
             if env_map is not None:
                 kw['env_map'] = np.asarray(env_map)[self.bounds[k]:self.bounds[k + 1]]
+            if scripted is not None:
+                kw['scripted'] = (scripted[0][self.bounds[k]:self.bounds[k + 1]], scripted[1])
             self.shards[k] = F110VecEnv(self.shard_sizes[k], **kw)
         try:
             _wait([w.submit(lambda k=k: make(k)) for k, w in enumerate(self._workers)])

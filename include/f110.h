@@ -272,6 +272,11 @@ typedef struct f110_host_block {
                                        bounded: after 250 us the call sleeps in hipStreamSynchronize */
 #define F110_STEP_NO_FUSE 16        /* A/B: always run the episode logic + host block as a kernel of their own (with 2
                                        agents per env they are otherwise the finalize kernel's epilogue) */
+#define F110_STEP_SCRIPTED 64       /* scripted cars (f110_controllers_set, below): h_actions is staged into device memory (as
+                                       without F110_STEP_ACTIONS_MAPPED, which is ignored), the armed controllers overwrite their
+                                       agents' rows there from the scans of the last step, and the step runs from that buffer.
+                                       The one-launch form of tiny batches does not apply.  F110_ERR_STATE with nothing armed.
+                                       Without the flag the call does not look at the controllers at all. */
 int f110_step_host(f110_sim *h, const double *h_actions /* [N][2] */, const f110_host_block *out, int32_t flags);
 /* measurement aid: {calls, host microseconds spent enqueuing, host microseconds spent waiting} of the
  * f110_step_host calls since the last read (cleared by the read) */
@@ -717,6 +722,60 @@ int f110_obs_encode_device(f110_sim *h, const f110_obs_spec *spec, float *d_out,
  * eight feature sources in bit order (all eight may be asked for), h_step_count [m], h_inout [m][F][D] updated in place. */
 int f110_obs_encode_batch(f110_sim *h, const f110_obs_spec *spec, const double *h_scans, const double *h_cols, const int32_t *h_step_count,
                           int32_t m, float *h_inout);
+
+/* ---- scripted cars: a follow-the-gap controller per agent (no reference counterpart: the standard reactive F1TENTH planner,
+ * for the cars of an env that no policy drives) ----
+ * A controller turns an agent's scan row of the last step into an action (steer, speed), the layout f110_step_device takes.  It
+ * runs only when called (f110_follow_gap_device, or f110_step_host with F110_STEP_SCRIPTED), keeps no state between calls and
+ * changes no simulator state; the state blobs do not contain it.  Every operation is one correctly rounded IEEE operation
+ * (compare, float64 add, multiply, divide) or ceil; there is no libm call and nothing is contracted, so results are defined bit
+ * for bit.
+ * With r the agent's row, beams [lo, hi) = [beam_lo, beam_hi) (0, 0 = all B), W = hi - lo, S = smooth, inc = fov / (B - 1) and
+ * angle(b) = -fov / 2. + inc * (double)b:
+ *   1 clip     v[i] = r[lo + i] < range_clip ? r[lo + i] : range_clip; a NaN beam gives v[i] = 0
+ *   2 smooth   p[i] = (v[a] + v[a + 1] + ... + v[b - 1]) / (double)(b - a), a = max(0, i - S / 2), b = min(W, i + S / 2 + 1); the
+ *              adds run in ascending order starting from 0.0 + v[a], every window summed on its own (no running sum)
+ *   3 closest  c = the first index of the minimum of p
+ *   4 bubble   den = p[c] * inc; kb = den > 0 ? bubble_radius / den : +inf; half-width = W if !(kb < W), else (int)ceil(kb);
+ *              q = p with q[i] = 0 for |i - c| <= half-width
+ *   5 gap      beam i is free when q[i] > gap_threshold; [g0, g1) = the longest run of free beams, the lowest g0 on equal
+ *              length; with no free beam the action is (0.0, v_blocked)
+ *   6 target   CENTER: t = (g0 + g1 - 1) >> 1; FURTHEST: t = the first index of the maximum of q within the gap
+ *   7 action   steer = clamp(steer_gain * angle(lo + t), +-steer_max); f = p[t] / d_ref;
+ *              speed = v_lo + (v_hi - v_lo) * (f < 1 ? f : 1); if fabs(steer) > steer_slow, speed = min(speed, v_turn)
+ * An agent whose step_count is 0 was re-seated inside the step just taken and its scans are still the finished episode's: it
+ * gets (0, 0), the zero-action step of the reference's reset().
+ * Refused (F110_ERR_INVALID, nothing launched or written): beam_lo < 0, beam_hi > B, beam_lo >= beam_hi (other than 0, 0),
+ *   W > F110_GAP_MAX_WINDOW, B < 2, smooth even, outside 1..63 or above W, an unknown target, a non-finite setting, range_clip or
+ *   d_ref not > 0, bubble_radius, gap_threshold or steer_slow < 0, steer_max < 0, v_lo > v_hi. */
+enum { F110_GAP_TARGET_CENTER = 0, F110_GAP_TARGET_FURTHEST = 1 };
+enum { F110_GAP_MAX_SPECS = 8, F110_GAP_MAX_SMOOTH = 63, F110_GAP_MAX_WINDOW = 4096 /* a wave keeps one free bit per beam */ };
+typedef struct f110_gap_follower {
+    int32_t beam_lo, beam_hi;   /* 0, 0 = all beams (the usual choice at 1080 beams: 180, 900) */
+    int32_t smooth;             /* S, odd (5) */
+    int32_t target;             /* F110_GAP_TARGET_* */
+    double range_clip;          /* m (10.0) */
+    double bubble_radius;       /* m (0.6) */
+    double gap_threshold;       /* m (1.5) */
+    double steer_gain, steer_max;      /* (1.0, 0.4189) */
+    double v_lo, v_hi, d_ref;          /* (1.5, 4.0, 8.0) */
+    double steer_slow, v_turn;         /* (0.2, 2.5) */
+    double v_blocked;                  /* (0.5) */
+} f110_gap_follower;
+/* arms the controllers: specs [n_specs], 1 <= n_specs <= F110_GAP_MAX_SPECS, and h_assign [N] int32: -1 = external (the agent's
+ * action comes from the caller), else the index of the agent's spec (anything else: F110_ERR_INVALID, nothing changed).
+ * NULL, 0, NULL disarms them.  Arming launches nothing and no step looks at it without F110_STEP_SCRIPTED. */
+int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_specs, const int32_t *h_assign);
+/* writes the armed agents' rows of d_actions [N][2] (device memory, 16-byte aligned) from the scans of the last step; rows of
+ * external agents are never written (their waves leave before they load anything else).  Asynchronous on the handle's stream;
+ * right behind a two-block step it runs per env block on the block's own stream (as f110_scan_policy_device does).
+ * F110_ERR_STATE with nothing armed. */
+int f110_follow_gap_device(f110_sim *h, double *d_actions);
+/* unit form on host arrays (with or without a map; spec->beam_* refer to the handle's B and fov): h_scans [m][B], h_step_count
+ * [m] or NULL (no row is fresh), h_actions [m][2], h_info [m][5] int32 or NULL: c, half-width, g0, g1, t; g0, g1, t are -1 for a
+ * blocked row, all five for a row whose step_count is 0. */
+int f110_follow_gap_batch(f110_sim *h, const f110_gap_follower *spec, const double *h_scans, const int32_t *h_step_count, int32_t m,
+                          double *h_actions, int32_t *h_info);
 
 #ifdef __cplusplus
 }
