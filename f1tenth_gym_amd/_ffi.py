@@ -83,6 +83,16 @@ GAP_MAX_SPECS, GAP_MAX_SMOOTH, GAP_MAX_WINDOW = 8, 63, 4096
 STEP_SCRIPTED = 64
 
 
+class TrackPreviewSpec(C.Structure):
+    """struct f110_track_preview"""
+    _fields_ = [("points", C.c_int32), ("channels", C.c_int32), ("frame", C.c_int32), ("flags", C.c_int32),
+                ("offset", C.c_double), ("spacing", C.c_double), ("scale", C.c_double * 8)]
+
+
+PREVIEW_X, PREVIEW_Y, PREVIEW_TAN_X, PREVIEW_TAN_Y, PREVIEW_ATTR0, PREVIEW_ATTR1, PREVIEW_ATTR2, PREVIEW_ATTR3 = (1 << b for b in range(8))
+PREVIEW_NCHANNELS, PREVIEW_FRAME_EGO, PREVIEW_FRAME_WORLD, PREVIEW_MAX_POINTS, TRACK_MAX_ATTRS = 8, 0, 1, 32, 4
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -216,6 +226,9 @@ PROTOTYPES = {
     "f110_track_get": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
     "f110_track_host_block": (C.c_int, [C.c_void_p, C.POINTER(TrackHost)]),
     "f110_track_project_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp]),
+    "f110_track_set_attrs": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32]),
+    "f110_track_preview_device": (C.c_int, [C.c_void_p, C.POINTER(TrackPreviewSpec), C.c_void_p, C.c_void_p]),
+    "f110_track_preview_batch": (C.c_int, [C.c_void_p, C.POINTER(TrackPreviewSpec), C.c_int32, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
     "f110_obs_encode_device": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p, C.c_void_p]),
     "f110_obs_encode_batch": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), _dp, _dp, _i32p, C.c_int32, C.c_void_p]),

@@ -1032,7 +1032,20 @@ class BatchSim(object):
         check(_ffi.lib().f110_track_set(self._h, int(slot), dptr(xy), xy.shape[0], 1 if t.closed else 0), self._h)
         self.tracks = dict(getattr(self, "tracks", {}))
         self.tracks[int(slot)] = t
+        if t.attrs is not None:    # (f110_track_set itself cleared the slot's attributes)
+            self.set_track_attrs(slot, t.attrs)
         return t
+
+    def set_track_attrs(self, slot, attrs):
+        """per-point attributes of the track on `slot` for the preview's attr channels: [M][C] float64, M the track's point
+        count, C in 1 .. 4; None clears them.  set_track uploads a Track's own attrs."""
+        if attrs is None:
+            check(_ffi.lib().f110_track_set_attrs(self._h, int(slot), None, 0, 0), self._h)
+            return
+        a = as_f64(attrs)
+        if a.ndim != 2:
+            raise ValueError("attrs must be [M][C]")
+        check(_ffi.lib().f110_track_set_attrs(self._h, int(slot), dptr(a), a.shape[0], a.shape[1]), self._h)
 
     def enable_track(self, on=True):
         """with on, every step also produces the track columns (s, ds, lateral, heading_error, segment)"""
@@ -1084,6 +1097,49 @@ class BatchSim(object):
         out = np.empty((p.shape[0], 5))
         check(_ffi.lib().f110_track_project_batch(self._h, int(slot), dptr(p), p.shape[0], dptr(out)), self._h)
         return out
+
+    # ------------------------------------------------------------------ track preview (f110_track_preview_*)
+    def track_preview_device(self, preview, out=None, pinned=None):
+        """the raceline ahead of every agent (track_preview.TrackPreview) as a float32 DeviceArray [N][P][D], from the s column
+        and the pose of the step just taken.  `out`: a float32 DeviceArray of preview.shape(N) to reuse (None: a new one).
+        Enqueued on the handle's stream, per env block behind a two-block step (no host wait).  pinned: a pinned_empty float32
+        array of the same shape that also receives the result, complete after sync().  Needs enable_track()."""
+        from .track_preview import TrackPreview
+        pv = TrackPreview.coerce(preview)
+        shape = pv.shape(self.N)
+        if out is None:
+            out = DeviceArray(self, shape, np.float32)
+        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
+            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
+        pp = None
+        if pinned is not None:
+            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
+                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
+            pp = pinned.ctypes.data
+        spec = pv.spec()
+        check(_ffi.lib().f110_track_preview_device(self._h, C.byref(spec), out.ptr, pp), self._h)
+        return out
+
+    def track_preview(self, poses, s, preview, slot=0, raw=False, segments=False):
+        """unit form on host arrays: poses [m][3] and their arc lengths s [m] (track_project_batch's first column) on the track
+        of `slot` -> float32 [m][P][D]; with raw also float64 [m][P][8] (every channel before scaling, absent attributes 0.0),
+        with segments also int32 [m][P] (each station's segment)"""
+        from .track_preview import TrackPreview
+        pv = TrackPreview.coerce(preview)
+        p = as_f64(poses)
+        sv = np.asarray(s, dtype=np.float64).reshape(-1)
+        if p.ndim != 2 or p.shape[1] != 3 or sv.shape[0] != p.shape[0]:
+            raise ValueError("poses must be [m][3] and s [m]")
+        m = p.shape[0]
+        rows = np.ascontiguousarray(np.concatenate([p, sv[:, None]], axis=1))
+        out = np.zeros(pv.shape(m), dtype=np.float32)
+        rw = np.zeros((m, pv.points, 8)) if raw else None
+        sg = np.zeros((m, pv.points), dtype=np.int32) if segments else None
+        spec = pv.spec()
+        check(_ffi.lib().f110_track_preview_batch(self._h, C.byref(spec), int(slot), dptr(rows), m, out.ctypes.data,
+                                                  None if rw is None else dptr(rw), None if sg is None else i32ptr(sg)), self._h)
+        res = [out] + ([rw] if raw else []) + ([sg] if segments else [])
+        return res[0] if len(res) == 1 else tuple(res)
 
     # ------------------------------------------------------------------ rendering (f110_render_device, DESIGN §6c)
     def render_device(self, agents=None, width=64, height=64, view='ego', m_per_px=0.05, center=(0.0, 0.0), angle=0.0,

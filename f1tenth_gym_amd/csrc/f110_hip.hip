@@ -185,11 +185,14 @@ struct f110_sim {
     struct TrackSlot {
         double *d_cols = nullptr;   // [7][nseg] (TrackCol)
         double *d_pts = nullptr;    // [npts][2] the points (after the closed-track dedupe), what a render draws
+        double *d_attr = nullptr;   // [nattr][npts] per-point attributes (f110_track_set_attrs), or null
+        int32_t nattr = 0;
         int32_t nseg = 0, closed = 0, npts = 0;
         double L = 0.0;
     };
     std::vector<TrackSlot> tracks;        // indexed by map slot (shorter than the slot list: the rest have no track)
     TrackDesc *d_tracks = nullptr;        // [n_tracks_dev] what the kernels read
+    PreviewAttr *d_track_attrs = nullptr; // [n_tracks_dev] the slots' attribute columns (k_track_preview), uploaded with d_tracks
     int n_tracks_dev = 0;
     bool tracks_dirty = true;             // d_tracks does not reflect `tracks` / the slot count
     bool track_lds = false;               // some track fits the LDS-staged form
@@ -203,6 +206,7 @@ struct f110_sim {
     HostBlock trk_hb{};                   // ... and their device views (the trk_* fields)
     bool trk_pinned_on = false;
     const float *obs_pinned = nullptr;    // f110_obs_encode_device: the page-locked block its last copy went to
+    const float *preview_pinned = nullptr;   // f110_track_preview_device: likewise
     // scripted cars (f110_controllers_set): the specs and the per-agent assignment in device memory; gap_specs == 0: disarmed
     GapSpec *d_gap_specs = nullptr;
     int32_t *d_gap_assign = nullptr;
@@ -972,6 +976,7 @@ void f110_destroy(f110_sim *h)
     for (auto &ts : h->tracks) {
         if (ts.d_cols) (void)hipFree(ts.d_cols);
         if (ts.d_pts) (void)hipFree(ts.d_pts);
+        if (ts.d_attr) (void)hipFree(ts.d_attr);
     }
     if (h->d_gap_specs) (void)hipFree(h->d_gap_specs);
     if (h->d_gap_assign) (void)hipFree(h->d_gap_assign);
@@ -981,7 +986,7 @@ void f110_destroy(f110_sim *h)
             if (p) (void)hipFree(p);
     }
     {
-        void *tp[] = {h->d_tracks, h->d_trk, h->d_trk_seg, h->d_trk_cache, h->d_trk_ok};
+        void *tp[] = {h->d_tracks, h->d_track_attrs, h->d_trk, h->d_trk_seg, h->d_trk_cache, h->d_trk_ok};
         for (void *p : tp)
             if (p) (void)hipFree(p);
     }
@@ -2111,11 +2116,12 @@ int f110_host_free(f110_sim *h, void *p)
                     o->trk_pinned = f110_track_host{};
                 }
             }
-            if (inside(o->obs_pinned)) {   // an encode's copy (on the env blocks' streams) may still be on its way into the block
+            if (inside(o->obs_pinned) || inside(o->preview_pinned)) {   // an encode's or a preview's copy (on the env blocks' streams) may still be on its way into the block
                 (void)hipSetDevice(o->cfg.device_id);
                 for (hipStream_t gs : o->gstreams) (void)hipStreamSynchronize(gs);
                 (void)hipStreamSynchronize(o->stream);
-                o->obs_pinned = nullptr;
+                if (inside(o->obs_pinned)) o->obs_pinned = nullptr;
+                if (inside(o->preview_pinned)) o->preview_pinned = nullptr;
             }
             if (!o->hb_valid && !o->fused_valid) continue;
             const f110_host_block &b = o->hb_host;
@@ -4269,22 +4275,30 @@ static int track_upload(f110_sim *h)
     const int slots = 1 + (int)h->extra_maps.size();
     if (!h->tracks_dirty && h->n_tracks_dev == slots) return F110_OK;
     std::vector<TrackDesc> desc((size_t)slots);
+    std::vector<PreviewAttr> attrs((size_t)slots);
     h->track_lds = false;
     for (int m = 0; m < slots; ++m) {
         desc[m] = TrackDesc{nullptr, 0, 0, 0.0};
+        attrs[m] = PreviewAttr{nullptr, 0, 0};
         if (m < (int)h->tracks.size() && h->tracks[m].nseg > 0) {
             const f110_sim::TrackSlot &ts = h->tracks[m];
             desc[m] = TrackDesc{ts.d_cols, ts.nseg, ts.closed, ts.L};
+            attrs[m] = PreviewAttr{ts.d_attr, ts.nattr, ts.npts};
             h->track_lds = h->track_lds || ts.nseg <= kTrackLdsSegs;
         }
     }
     if (h->n_tracks_dev != slots) {
         if (h->d_tracks) HIPCHK(h, hipFree(h->d_tracks));
         h->d_tracks = nullptr;
+        if (h->d_track_attrs) HIPCHK(h, hipFree(h->d_track_attrs));
+        h->d_track_attrs = nullptr;
+        h->n_tracks_dev = 0;
         TRY(dmalloc(h, &h->d_tracks, (size_t)slots));
+        TRY(dmalloc(h, &h->d_track_attrs, (size_t)slots));
         h->n_tracks_dev = slots;
     }
     HIPCHK(h, hipMemcpyAsync(h->d_tracks, desc.data(), sizeof(TrackDesc) * slots, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_track_attrs, attrs.data(), sizeof(PreviewAttr) * slots, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (desc is a local; rare: only after a change)
     h->tracks_dirty = false;
     return F110_OK;
@@ -4409,6 +4423,9 @@ int f110_track_set(f110_sim *h, int32_t slot, const double *h_xy, int32_t M, int
     f110_sim::TrackSlot &ts = h->tracks[slot];
     if (ts.d_cols) HIPCHK(h, hipFree(ts.d_cols));   // (synchronised above: no step reads the old table any more)
     if (ts.d_pts) HIPCHK(h, hipFree(ts.d_pts));
+    if (ts.d_attr) HIPCHK(h, hipFree(ts.d_attr));   // a new track: the old one's attributes go with it
+    ts.d_attr = nullptr;
+    ts.nattr = 0;
     ts.d_cols = d_cols;
     ts.d_pts = d_pts;
     ts.npts = m;
@@ -4518,6 +4535,193 @@ int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, i
     else hipLaunchKernelGGL((k_track_project<kTrackUnit, false>), grid, dim3(256), 0, h->stream, j);
     HIPCHK(h, hipGetLastError());
     TRY(sc.down(h_out, dout, 5 * (size_t)m));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- track preview (f110_track_set_attrs / f110_track_preview_*, include/f110.h) ------------------------------------------------
+int f110_track_set_attrs(f110_sim *h, int32_t slot, const double *h_attr, int32_t M, int32_t C)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (!track_has(h, slot)) return fail(h, F110_ERR_INVALID, "f110_track_set_attrs: map slot %d has no track (f110_track_set)", slot);
+    f110_sim::TrackSlot &ts = h->tracks[slot];
+    const bool clear = !h_attr && M == 0 && C == 0;
+    std::vector<double> cols;
+    if (!clear) {
+        if (!h_attr) return fail(h, F110_ERR_INVALID, "f110_track_set_attrs: null attributes (NULL, 0, 0 clears them)");
+        if (M != ts.npts) return fail(h, F110_ERR_INVALID, "f110_track_set_attrs: %d rows, but the track on slot %d has %d points", M, slot, ts.npts);
+        if (C < 1 || C > F110_TRACK_MAX_ATTRS) return fail(h, F110_ERR_INVALID, "f110_track_set_attrs: 1..%d attributes per point, got %d", (int)F110_TRACK_MAX_ATTRS, C);
+        cols.resize((size_t)M * C);
+        for (int k = 0; k < M; ++k)
+            for (int c = 0; c < C; ++c) {
+                const double v = h_attr[(size_t)k * C + c];
+                if (!std::isfinite(v)) return fail(h, F110_ERR_INVALID, "f110_track_set_attrs: attribute %d of point %d is not finite", c, k);
+                cols[(size_t)c * M + k] = v;   // [C][M]: a station reads one column at k and k + 1
+            }
+    }
+    ENTER(h);
+    double *d_attr = nullptr;
+    if (!clear) {
+        TRY(dmalloc(h, &d_attr, cols.size()));
+        const hipError_t e = hipMemcpyAsync(d_attr, cols.data(), cols.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(d_attr);
+            return fail(h, F110_ERR_HIP, "f110_track_set_attrs: upload failed: %s", hipGetErrorString(e));
+        }
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (the source is a local; no preview reads the old columns any more)
+    if (ts.d_attr) HIPCHK(h, hipFree(ts.d_attr));
+    ts.d_attr = d_attr;
+    ts.nattr = clear ? 0 : C;
+    h->tracks_dirty = true;
+    return F110_OK;
+}
+
+// the spec's refusals; on success the kernel's spec
+static int preview_check_spec(f110_sim *h, const f110_track_preview *p, PreviewSpec &o)
+{
+    if (!p) return fail(h, F110_ERR_INVALID, "track preview: null spec");
+    if (p->points < 1 || p->points > F110_PREVIEW_MAX_POINTS) return fail(h, F110_ERR_INVALID, "track preview: points = %d is outside 1..%d", p->points, (int)F110_PREVIEW_MAX_POINTS);
+    if (p->channels == 0 || (p->channels & ~((1 << F110_PREVIEW_NCHANNELS) - 1))) return fail(h, F110_ERR_INVALID, "track preview: channels = 0x%x is empty or has an unknown bit", p->channels);
+    if (p->frame != F110_PREVIEW_FRAME_EGO && p->frame != F110_PREVIEW_FRAME_WORLD) return fail(h, F110_ERR_INVALID, "track preview: unknown frame %d", p->frame);
+    if (p->flags != 0) return fail(h, F110_ERR_INVALID, "track preview: flags = %d must be 0", p->flags);
+    if (!(std::isfinite(p->offset) && p->offset >= 0.0)) return fail(h, F110_ERR_INVALID, "track preview: offset must be finite and >= 0");
+    if (!(std::isfinite(p->spacing) && p->spacing > 0.0)) return fail(h, F110_ERR_INVALID, "track preview: spacing must be finite and > 0");
+    o = PreviewSpec{};
+    for (int b = 0; b < F110_PREVIEW_NCHANNELS; ++b) {
+        o.scale[b] = 1.0;
+        if (!(p->channels >> b & 1)) continue;
+        if (!(std::isfinite(p->scale[b]) && p->scale[b] != 0.0)) return fail(h, F110_ERR_INVALID, "track preview: scale[%d] must be finite and non-zero", b);
+        o.scale[b] = p->scale[b];
+        o.D += 1;
+    }
+    o.P = p->points;
+    o.channels = p->channels;
+    o.frame = p->frame;
+    o.offset = p->offset;
+    o.spacing = p->spacing;
+    return F110_OK;
+}
+
+// what a slot in use must offer: a track, the requested attribute columns, and on a closed track more length than the reach
+static int preview_check_slot(f110_sim *h, const PreviewSpec &sp, int slot)
+{
+    if (!track_has(h, slot)) return fail(h, F110_ERR_STATE, "track preview: map slot %d has no track (f110_track_set)", slot);
+    const f110_sim::TrackSlot &ts = h->tracks[slot];
+    for (int a = 0; a < F110_TRACK_MAX_ATTRS; ++a)
+        if ((sp.channels >> (4 + a) & 1) && a >= ts.nattr)
+            return fail(h, F110_ERR_STATE, "track preview: attribute %d is requested, but the track on slot %d has %d (f110_track_set_attrs)", a, slot, ts.nattr);
+    const double reach = sp.offset + (double)(sp.P - 1) * sp.spacing;
+    if (ts.closed && !(ts.L > reach))
+        return fail(h, F110_ERR_STATE, "track preview: the closed track on slot %d is %.6g m long, not longer than the preview's reach of %.6g m", slot, ts.L, reach);
+    return F110_OK;
+}
+
+static void preview_launch(PreviewJob &j, hipStream_t st)
+{
+    if (j.count <= 0) return;
+    j.shift = 0;
+    while ((1 << j.shift) < j.sp.P) ++j.shift;
+    hipLaunchKernelGGL(k_track_preview, grid1d((size_t)j.count << j.shift, 256), dim3(256), 0, st, j);
+}
+
+int f110_track_preview_device(f110_sim *h, const f110_track_preview *spec, float *d_out, float *h_pinned)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    PreviewJob j{};
+    TRY(preview_check_spec(h, spec, j.sp));
+    if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return fail(h, F110_ERR_INVALID, "track preview: d_out is null or not 16-byte aligned");
+    const size_t N = (size_t)h->N, per_agent = (size_t)j.sp.P * j.sp.D;
+    if (h_pinned) {
+        std::lock_guard<std::mutex> lk(g_registry_mu);
+        const char *p = reinterpret_cast<const char *>(h_pinned);
+        auto it = g_host_blocks.upper_bound(p);
+        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
+        if (it != g_host_blocks.begin()) {
+            --it;
+            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
+        }
+        if (!inside) return fail(h, F110_ERR_INVALID, "track preview: h_pinned is not [N][P][D] floats of f110_host_alloc memory");
+    }
+    if (!h->track_on) return fail(h, F110_ERR_STATE, "track preview: tracking is off (f110_track_enable)");
+    if (!h->multi_map) TRY(preview_check_slot(h, j.sp, 0));
+    else {
+        std::vector<char> seen(1 + h->extra_maps.size(), 0);
+        for (int32_t m : h->env_map_host) {
+            if (m >= 0 && m < (int)seen.size() && seen[m]) continue;
+            TRY(preview_check_slot(h, j.sp, m));
+            seen[m] = 1;
+        }
+    }
+    if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size()) {   // (attributes set since the last step)
+        ENTER(h);
+        TRY(track_upload(h));
+    }
+    EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (an agent reads its own rows and writes its own block)
+    TRY(env_blocks_follow(h, w));
+    j.tracks = h->d_tracks;
+    j.attrs = h->d_track_attrs;
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.A = h->cfg.num_agents;
+    j.unit_slot = -1;
+    j.px = h->dev.snap_pose;   // the post-step pose of the observation, the one s was computed from
+    j.py = h->dev.snap_pose + N;
+    j.pth = h->dev.snap_pose + 2 * N;
+    j.ps = h->d_trk;
+    j.stride = 1;
+    j.out = d_out;
+    for (const EnvBlock &b : w) {
+        j.begin = b.e0 * j.A;
+        j.count = b.count * j.A;
+        preview_launch(j, b.stream);
+        if (h_pinned)
+            HIPCHK(h, hipMemcpyAsync(h_pinned + (size_t)j.begin * per_agent, d_out + (size_t)j.begin * per_agent, (size_t)j.count * per_agent * sizeof(float),
+                                     hipMemcpyDeviceToHost, b.stream));
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h_pinned) h->preview_pinned = h_pinned;
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_track_preview_batch(f110_sim *h, const f110_track_preview *spec, int32_t slot, const double *h_in, int32_t m, float *h_out,
+                             double *h_raw, int32_t *h_seg)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    PreviewJob j{};
+    TRY(preview_check_spec(h, spec, j.sp));
+    if (m < 0 || (m > 0 && (!h_in || !h_out))) return fail(h, F110_ERR_INVALID, "track preview: bad argument");
+    TRY(preview_check_slot(h, j.sp, slot));
+    if (m == 0) return F110_OK;
+    ENTER(h);
+    TRY(track_upload(h));
+    Scratch sc(h);
+    const size_t rows = (size_t)m * j.sp.P;
+    double *din = nullptr, *draw = nullptr;
+    float *dout = nullptr;
+    int32_t *dseg = nullptr;
+    TRY(sc.up(h_in, 4 * (size_t)m, &din));
+    TRY(sc.up<float>(nullptr, rows * j.sp.D, &dout));
+    if (h_raw) TRY(sc.up<double>(nullptr, rows * F110_PREVIEW_NCHANNELS, &draw));
+    if (h_seg) TRY(sc.up<int32_t>(nullptr, rows, &dseg));
+    j.tracks = h->d_tracks;
+    j.attrs = h->d_track_attrs;
+    j.A = 1;
+    j.count = m;
+    j.unit_slot = slot;
+    j.px = din;
+    j.py = din + 1;
+    j.pth = din + 2;
+    j.ps = din + 3;
+    j.stride = 4;
+    j.out = dout;
+    j.raw = draw;
+    j.seg = dseg;
+    preview_launch(j, h->stream);
+    HIPCHK(h, hipGetLastError());
+    TRY(sc.down(h_out, dout, rows * j.sp.D));
+    if (h_raw) TRY(sc.down(h_raw, draw, rows * F110_PREVIEW_NCHANNELS));
+    if (h_seg) TRY(sc.down(h_seg, dseg, rows));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }

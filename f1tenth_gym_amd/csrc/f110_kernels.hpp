@@ -4216,3 +4216,103 @@ __global__ void __launch_bounds__(256) k_follow_gap(GapJob j)
         if (info) info[2] = g0, info[3] = g1, info[4] = t;
     }
 }
+
+// ---- track preview (f110_track_preview_*; include/f110.h states the rule, f110_math.hpp preview_* the arithmetic) ----------------
+// A group of G lanes per agent, G the next power of two >= P (1..32), one station per lane; 256 / G agents per workgroup.  What a
+// station costs is its dependent chain: the agent's s and pose, then ~log2(nseg) probes of the binary search on cum, then one
+// round of independent loads of the winning segment's columns and attributes.  The probes are the long part, so cum — and only
+// cum, 8 bytes per segment — of the workgroup's first agent's slot is staged in LDS when it has at most kPreviewLdsSegs segments
+// (16 KiB; the example raceline's 782 take 6 KiB); a lane whose agent sits on another slot, or on a longer track, probes the same
+// column in L2.  The rule defines k uniquely, so where the probes were served does not show.  The other columns are read once
+// per station from L2, where neighbouring stations share lines.
+// The agent's [P][D] floats go through LDS: lane j leaves its D values at j * D, then the group's lanes store the P * D floats in
+// order, consecutive lanes consecutive floats.  The channel loop is unrolled over the eight bits, so the values stay in named
+// registers (no private array indexed at run time) and the scales come from the kernel arguments.
+// LDS: 16 KiB (cum) + 8 KiB (outputs) per workgroup of 4 waves.  Idle groups shadow the last agent and idle lanes the last
+// station, so every lane reaches both barriers; they store nothing.
+constexpr int kPreviewLdsSegs = 2048;
+
+struct PreviewAttr {
+    const double *a;   // [C][npts] or nullptr
+    int32_t C, npts;
+};
+
+// device form: agents [begin, begin + count), slot = env_map[i / A] (slot 0 when env_map is nullptr), unit_slot = -1.
+// unit form: rows [0, count) on the track `unit_slot`.
+struct PreviewJob {
+    const TrackDesc *tracks;
+    const PreviewAttr *attrs;
+    const int32_t *env_map;
+    int32_t A, begin, count, unit_slot;
+    const double *px, *py, *pth, *ps;   // pose and s columns, `stride` apart per agent
+    int32_t stride, shift;              // lanes per agent = 1 << shift
+    float *out;                         // [.][P][D]
+    double *raw;                        // [.][P][8] or nullptr
+    int32_t *seg;                       // [.][P] or nullptr
+    PreviewSpec sp;
+};
+
+__global__ void __launch_bounds__(256) k_track_preview(PreviewJob j)
+{
+    __shared__ double s_cum[kPreviewLdsSegs];
+    __shared__ float s_out[256 * PREVIEW_NCHANNELS];
+    __shared__ int s_slot;
+    const int P = j.sp.P, D = j.sp.D, G = 1 << j.shift;
+    const int gid = (int)((blockIdx.x * 256u + threadIdx.x) >> j.shift);
+    const int sub = (int)threadIdx.x & (G - 1);
+    const bool live = gid < j.count;
+    const int i = j.begin + (live ? gid : j.count - 1);
+    const int slot = j.unit_slot >= 0 ? j.unit_slot : (j.env_map ? j.env_map[i / j.A] : 0);
+    if (threadIdx.x == 0) s_slot = slot;
+    __syncthreads();
+    const int slot0 = s_slot;
+    const TrackDesc t0 = j.tracks[slot0];
+    const bool staged = t0.nseg > 0 && t0.nseg <= kPreviewLdsSegs;
+    if (staged) {
+        const double *cum0 = t0.cols + (size_t)kTrkCum * t0.nseg;
+        for (int q = (int)threadIdx.x; q < t0.nseg; q += 256) s_cum[q] = cum0[q];
+    }
+    __syncthreads();
+    const TrackDesc td = j.tracks[slot];
+    const PreviewAttr at = j.attrs[slot];
+    const bool work = live && td.nseg > 0;   // (a slot without a track is refused on the host)
+    const int st = sub < P ? sub : P - 1;
+    float *mine = s_out + ((int)threadIdx.x - sub) * PREVIEW_NCHANNELS;
+    if (td.nseg > 0) {
+        PreviewTrack tr;
+        tr.cols = td.cols;
+        tr.attr = at.a;
+        tr.nseg = td.nseg;
+        tr.closed = td.closed;
+        tr.C = at.a ? at.C : 0;
+        tr.npts = td.closed ? td.nseg : td.nseg + 1;
+        tr.L = td.L;
+        const size_t r = (size_t)i * j.stride;
+        const double px = j.px[r], py = j.py[r], s = j.ps[r];
+        double c = 1.0, sn = 0.0;
+        if (j.sp.frame == PREVIEW_FRAME_EGO) cos_sin(j.pth[r], c, sn);
+        const double sj = preview_station_s(s, j.sp.offset, j.sp.spacing, st, td.closed, td.L);
+        const int k = (staged && slot == slot0) ? preview_segment(s_cum, td.nseg, sj)
+                                                : preview_segment(td.cols + (size_t)kTrkCum * td.nseg, td.nseg, sj);
+        double v[PREVIEW_NCHANNELS];
+        preview_station(tr, k, sj, j.sp.frame, px, py, c, sn, v);
+        if (work && sub < P) {
+            float *o = mine + sub * D;
+            int n = 0;
+#pragma unroll
+            for (int b = 0; b < PREVIEW_NCHANNELS; ++b)
+                if (j.sp.channels >> b & 1) o[n++] = preview_scaled(v[b], j.sp.scale[b]);
+            const size_t row = (size_t)i * P + sub;
+            if (j.raw) {
+#pragma unroll
+                for (int b = 0; b < PREVIEW_NCHANNELS; ++b) j.raw[row * PREVIEW_NCHANNELS + b] = v[b];
+            }
+            if (j.seg) j.seg[row] = k;
+        }
+    }
+    __syncthreads();
+    if (work) {
+        float *dst = j.out + (size_t)i * P * D;
+        for (int q = sub; q < P * D; q += G) dst[q] = mine[q];
+    }
+}

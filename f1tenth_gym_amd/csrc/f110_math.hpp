@@ -1414,4 +1414,108 @@ F110_HD void gap_follow_row(const GapSpec &s, const double *row, int B, double f
     gap_action(s, gap_beam_angle(fov, B, s.lo + t), p[t], action[0], action[1]);
 }
 
+// ------------------------------------------------------------------ track preview (include/f110.h, f110_track_preview)
+// No reference counterpart.  Float64 adds, multiplies, divides and compares, nothing to contract; the EGO frame's one cos_sin is
+// the only libm call.
+enum { PREVIEW_FRAME_EGO = 0, PREVIEW_FRAME_WORLD = 1 };
+enum { PREVIEW_NCHANNELS = 8, PREVIEW_MAX_ATTRS = 4 };
+
+struct PreviewSpec {
+    int32_t P, channels;   // stations; channel bits
+    int32_t frame, D;      // PREVIEW_FRAME_*; popcount(channels)
+    double offset, spacing;
+    double scale[PREVIEW_NCHANNELS];
+};
+
+// a track as the preview reads it: the segment columns [7][nseg] (ax, ay, dx, dy, l2, len, cum) and the attributes [C][npts]
+struct PreviewTrack {
+    const double *cols;
+    const double *attr;   // or null (C == 0)
+    int32_t nseg, closed, C, npts;
+    double L;
+};
+
+// station j's arc length: one wrap on a closed track
+F110_HD double preview_station_s(double s, double offset, double spacing, int j, int closed, double L)
+{
+    const double d = offset + (double)j * spacing;
+    double sj = s + d;
+    if (closed && sj >= L) sj = sj - L;
+    return sj;
+}
+
+// the last segment with cum[k] <= s, 0 when there is none (a NaN s: 0)
+F110_HD int preview_segment(const double *cum, int nseg, double s)
+{
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cum[mid] <= s) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// np.clip(t, 0, 1): NaN passes
+F110_HD double preview_clip01(double t) { return t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t); }
+
+// the eight channel values of the station at arc length sj in segment k, before scaling; (c, sn) = cos, sin of the pose's heading
+// (read in the EGO frame only); an absent attribute is 0.0
+F110_HD void preview_station(const PreviewTrack &tr, int k, double sj, int frame, double px, double py, double c, double sn, double *v)
+{
+    const size_t n = (size_t)tr.nseg;
+    const double *q = tr.cols;
+    const double ax = q[k], ay = q[n + k], dx = q[2 * n + k], dy = q[3 * n + k], len = q[5 * n + k], cum = q[6 * n + k];
+    const double t = preview_clip01((sj - cum) / len);
+    const double X = ax + t * dx, Y = ay + t * dy;
+    const double ux = dx / len, uy = dy / len;
+    if (frame == PREVIEW_FRAME_WORLD) {
+        v[0] = X;
+        v[1] = Y;
+        v[2] = ux;
+        v[3] = uy;
+    } else {
+        const double rx = X - px, ry = Y - py;
+        v[0] = c * rx + sn * ry;
+        v[1] = c * ry - sn * rx;
+        v[2] = c * ux + sn * uy;
+        v[3] = c * uy - sn * ux;
+    }
+    const int k1 = k + 1 == tr.npts ? 0 : k + 1;   // (only a closed track's last segment ends at point 0)
+#pragma unroll
+    for (int a = 0; a < PREVIEW_MAX_ATTRS; ++a) {
+        double w = 0.0;
+        if (a < tr.C) {
+            const double a0 = tr.attr[(size_t)a * tr.npts + k], a1 = tr.attr[(size_t)a * tr.npts + k1];
+            w = a0 + t * (a1 - a0);
+        }
+        v[4 + a] = w;
+    }
+}
+
+// one output element: a float64 divide, then the conversion (round to nearest even)
+F110_HD float preview_scaled(double v, double scale) { return (float)(v / scale); }
+
+// one row's whole preview, serially (the kernel gives every station a lane; this is what the unit harness runs).
+// out [P][D], raw [P][8] or null, seg [P] or null
+F110_HD void preview_row(const PreviewSpec &sp, const PreviewTrack &tr, double px, double py, double theta, double s, float *out,
+                         double *raw, int32_t *seg)
+{
+    double c = 1.0, sn = 0.0;
+    if (sp.frame == PREVIEW_FRAME_EGO) cos_sin(theta, c, sn);
+    const double *cum = tr.cols + 6 * (size_t)tr.nseg;
+    for (int j = 0; j < sp.P; ++j) {
+        const double sj = preview_station_s(s, sp.offset, sp.spacing, j, tr.closed, tr.L);
+        const int k = preview_segment(cum, tr.nseg, sj);
+        double v[PREVIEW_NCHANNELS];
+        preview_station(tr, k, sj, sp.frame, px, py, c, sn, v);
+        float *o = out + (size_t)j * sp.D;
+        for (int b = 0; b < PREVIEW_NCHANNELS; ++b) {
+            if (raw) raw[(size_t)j * PREVIEW_NCHANNELS + b] = v[b];
+            if (sp.channels >> b & 1) *o++ = preview_scaled(v[b], sp.scale[b]);
+        }
+        if (seg) seg[j] = k;
+    }
+}
+
 }  // namespace f110

@@ -20,6 +20,7 @@ from .gap_follower import coerce_scripted
 from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
 from .sim import Integrator, Simulator
+from .track_preview import TrackPreview
 from .track import Track
 
 try:  # pragma: no cover - gym is absent from the build image
@@ -208,6 +209,13 @@ class F110Env(_EnvBase):
             self.sim.enable_track()
         elif self.reward_mode == 'progress':
             raise ValueError("reward='progress' needs a track (track=...)")
+        # track preview: track_preview= adds obs['track_preview'], float32 [A][P][D], computed on the device after the step
+        self.track_preview = None
+        if kwargs.get('track_preview') is not None:
+            self.track_preview = TrackPreview.coerce(kwargs['track_preview'])
+            if self.track is None:
+                raise ValueError("track_preview= needs a track (track=...)")
+            self.track_preview.check_track(self.track)
         # randomised start poses: random_start= (a ResetSampler or a dict of its settings) makes reset() without
         # poses draw them on the track
         self.random_start = None
@@ -229,6 +237,10 @@ class F110Env(_EnvBase):
 
     def step(self, action):
         obs = self.sim.step(action)
+        if self.track_preview is not None:
+            pv = self.sim.batch.track_preview_device(self.track_preview)
+            obs['track_preview'] = pv.download()
+            pv.free()
         obs['lap_times'] = self._lap.lap_times[0]
         obs['lap_counts'] = self._lap.lap_counts[0]
         self.current_obs = obs
@@ -345,6 +357,13 @@ class F110VecEnv(object):
     step(actions) keeps its [E][A][2] shape: the rows of scripted cars are ignored and replaced on the device.  A scripted
     car takes the zero action on the first step of an episode (reset()'s own step, and the step after an in-step re-seat).
     It needs device_logic=True (ValueError otherwise).  Controllers hold no state: snapshots do not change.
+
+    Track preview (no reference counterpart): `track_preview=` (a TrackPreview or a dict of its settings) adds
+    obs['track_preview'], float32 [E][A][P][D]: P stations of the raceline ahead of each car, in its own frame or the map's,
+    with the track's interpolated attributes (Track(attrs=...)).  It belongs to the observation it comes with (that step's
+    poses and progress), is computed on the device behind the step and lands in page-locked memory with the rest of the
+    block, so it needs device_logic=True and a track (ValueError otherwise; any other loop calls
+    env.sim.batch.track_preview_device after its step).  A persistent view like the others; it holds no state.
     """
 
     # every key of the reference's observation (base_classes.py:594-610, docs/api/obv.rst:6-14)
@@ -355,7 +374,8 @@ class F110VecEnv(object):
     _EPISODE = ("lap_times", "lap_counts", "toggle_list", "near_starts", "checkpoint_done")
 
     def __init__(self, num_envs, auto_reset=False, device_logic=False, obs_fields=None, copy_obs=False,
-                 episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, scripted=None, **kwargs):
+                 episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, scripted=None,
+                 track_preview=None, **kwargs):
         self.num_envs = int(num_envs)
         self.seed = kwargs.get('seed', 12345)
         self.map_name, self.map_path = _resolve_map_path(kwargs)
@@ -392,6 +412,16 @@ class F110VecEnv(object):
             self.scripted = coerce_scripted(scripted, self.num_envs, self.num_agents)
             for c in self.scripted[1]:
                 c.window(kwargs.get('num_beams', 1080))
+        self.track_preview = None
+        if track_preview is not None:
+            self.track_preview = TrackPreview.coerce(track_preview)
+            if not self.device_logic:
+                raise ValueError("track_preview= needs device_logic=True (any other loop calls env.sim.batch.track_preview_device after its step)")
+            if not tracks:
+                raise ValueError("track_preview= needs a track (track= or tracks=)")
+            tracks = {slot: Track.coerce(t) for slot, t in tracks.items()}
+            for t in tracks.values():
+                self.track_preview.check_track(t)
         self.encoded_stack = None
         if not tracks and any(f in self._TRACK for f in self.obs_fields):
             raise ValueError("the track fields of obs_fields need a track (track= or tracks=)")
@@ -488,6 +518,12 @@ class F110VecEnv(object):
             self._enc_pinned[...] = 0.0
             self._enc_fill = True          # the first encode, and the one after a restore without a saved stack
             obs["encoded"] = self._enc_pinned.reshape((E, A) + shape[1:])
+        if self.track_preview is not None:   # the preview in device memory, and the page-locked copy every step's call ends with
+            shape = self.track_preview.shape(E * A)
+            self.preview_buffer = b.device_array(shape, np.float32)
+            self._prv_pinned = b.pinned_empty(shape, np.float32)
+            self._prv_pinned[...] = 0.0
+            obs["track_preview"] = self._prv_pinned.reshape((E, A) + shape[1:])
         self._ret_views = (obs, reward, v["done"].view(np.bool_), info)
 
     def update_params_batch(self, params):
@@ -593,12 +629,15 @@ class F110VecEnv(object):
             self.sim._noise.ensure(b, self.sim._steps_since_full_reset + 1)
         if actions is not None and actions is not self.action_buffer:
             hb.actions[...] = np.asarray(actions, dtype=np.float64).reshape(hb.actions.shape)
-        if self._encode:
-            # one wait per step: the step enqueued without a wait, the encode and its copy into page-locked memory behind it
+        if self._encode or self.track_preview is not None:
+            # one wait per step: the step enqueued without a wait, the encode / the preview and their copies into page-locked memory behind it
             b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
                         scripted=self.scripted is not None)
-            b.encode_obs_device(self.obs_encoder, self.encoded_stack, fill=self._enc_fill, pinned=self._enc_pinned)
-            self._enc_fill = False
+            if self._encode:
+                b.encode_obs_device(self.obs_encoder, self.encoded_stack, fill=self._enc_fill, pinned=self._enc_pinned)
+                self._enc_fill = False
+            if self.track_preview is not None:
+                b.track_preview_device(self.track_preview, self.preview_buffer, pinned=self._prv_pinned)
             if sync:
                 b.sync()
         else:

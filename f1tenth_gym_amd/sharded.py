@@ -94,6 +94,9 @@ class ShardedVecEnv(object):
         if kwargs.get('obs_encoder') is not None:    # one encoder for every shard; obs['encoded'] is concatenated along the env axis
             from .obs_encoder import ObsEncoder
             kwargs['obs_encoder'] = ObsEncoder.coerce(kwargs['obs_encoder'])
+        if kwargs.get('track_preview') is not None:  # one preview for every shard; obs['track_preview'] is concatenated along the env axis
+            from .track_preview import TrackPreview
+            kwargs['track_preview'] = TrackPreview.coerce(kwargs['track_preview'])
         scripted = kwargs.pop('scripted', None)      # scripted cars: the global assignment [E][A], sliced by shard; the controllers shared
         if scripted is not None:
             from .gap_follower import coerce_scripted

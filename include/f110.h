@@ -777,6 +777,62 @@ int f110_follow_gap_device(f110_sim *h, double *d_actions);
 int f110_follow_gap_batch(f110_sim *h, const f110_gap_follower *spec, const double *h_scans, const int32_t *h_step_count, int32_t m,
                           double *h_actions, int32_t *h_info);
 
+/* ---- track preview: the raceline ahead of each agent, in its own frame (no reference counterpart: what trajectory-aided and
+ * pure-pursuit-style policies interpolate from the waypoints on the host) ----
+ * Per-point attributes.  A track may carry up to F110_TRACK_MAX_ATTRS float64 columns per point (curvature, a speed profile,
+ * cos / sin of a heading ...): h_attr [M][C], M the slot's point count as f110_track_set stored it (a closed track's repeated
+ * last point dropped).  Refused (F110_ERR_INVALID, nothing changed): another M, C outside 1..4, a non-finite value, a slot
+ * without a track.  NULL, 0, 0 clears them, and so does f110_track_set on the slot.  They are configuration like the track and
+ * not part of the state blobs.  Attributes are interpolated linearly, value by value: pass kappa, vx or cos / sin columns, not an
+ * angle such as psi, whose wrap a linear blend does not know about. */
+enum { F110_TRACK_MAX_ATTRS = 4 };
+int f110_track_set_attrs(f110_sim *h, int32_t slot, const double *h_attr /* [M][C] */, int32_t M, int32_t C);
+/* The preview.  It runs only when called, keeps no state in the handle and changes no simulator state.  Everything is float64
+ * without contraction, every operation one correctly rounded IEEE operation except the one cos / sin of the EGO frame.
+ * Agent n's track (the one on its env's map slot) has the segments (ax, ay, dx, dy, len, cum)[k] and the total length L; s_n is
+ * its `s` column and (px, py, theta) the pose that column was computed from: the observation's pose of the step just taken, the
+ * one no in-step re-seat overwrites (agent_poses; it keeps the heading a car arrived with where a wall hit zeroed the state's yaw
+ * behind it, so poses_theta of such a car reads 0).  The preview belongs to that observation, as the other track columns do.  Station j of P:
+ *   d_j = offset + (double)j * spacing;  s_j = s_n + d_j;  on a closed track: if (s_j >= L) s_j = s_j - L, once
+ *   k   = the last segment with cum[k] <= s_j, 0 when there is none (so a NaN s_j gives 0): the reset sampler's rule
+ *   t   = clip((s_j - cum[k]) / len[k], 0, 1), the clip passing NaN
+ *   X = ax[k] + t * dx[k], Y = ay[k] + t * dy[k];  ux = dx[k] / len[k], uy = dy[k] / len[k]
+ *   attr_c = a[c][k] + t * (a[c][k1] - a[c][k]), k1 = k + 1, on a closed track 0 behind the last segment (an open track has the
+ *   point k + 1)
+ * On an open track a station beyond the end clips to the last point (t = 1 on the last segment).
+ * Frames.  WORLD: the channels are X, Y, ux, uy.  EGO: c = cos theta, sn = sin theta, rx = X - px, ry = Y - py and the channels
+ * are c * rx + sn * ry, c * ry - sn * rx, c * ux + sn * uy, c * uy - sn * ux.  The attributes are the same in both.
+ * Output.  out[n][j][.] holds the channels of the set bits in ascending bit order, each (float)(value / scale[bit]): a float64
+ * divide, then the conversion, rounding to nearest even.
+ * Refused with F110_ERR_INVALID, nothing launched or written: points outside 1..32, channels 0 or with an unknown bit, an unknown
+ *   frame, flags != 0, offset not finite or < 0, spacing not finite or <= 0 (also when points == 1), a zero or non-finite scale of
+ *   a set bit, a null or not 16-byte aligned d_out, an h_pinned that is not [N][P][D] floats of f110_host_alloc memory.
+ * Refused with F110_ERR_STATE: tracking is off (device form), a slot in use has no track, a requested attribute channel is not
+ *   present on a slot in use, a closed track in use has L <= offset + (P - 1) * spacing (one subtraction must be enough).
+ * Not offered: a spacing that depends on the speed, stations behind the car, angle-aware interpolation of attributes. */
+enum { F110_PREVIEW_X = 1, F110_PREVIEW_Y = 2, F110_PREVIEW_TAN_X = 4, F110_PREVIEW_TAN_Y = 8,
+       F110_PREVIEW_ATTR0 = 16, F110_PREVIEW_ATTR1 = 32, F110_PREVIEW_ATTR2 = 64, F110_PREVIEW_ATTR3 = 128, F110_PREVIEW_NCHANNELS = 8 };
+enum { F110_PREVIEW_FRAME_EGO = 0, F110_PREVIEW_FRAME_WORLD = 1 };
+enum { F110_PREVIEW_MAX_POINTS = 32 };
+typedef struct f110_track_preview {
+    int32_t points;     /* P, 1..32 stations */
+    int32_t channels;   /* F110_PREVIEW_* bits; D = popcount */
+    int32_t frame;      /* F110_PREVIEW_FRAME_* */
+    int32_t flags;      /* 0 */
+    double offset;      /* metres ahead of the agent's projection to station 0, >= 0 */
+    double spacing;     /* metres between stations, > 0 (ignored when P == 1, but still validated) */
+    double scale[F110_PREVIEW_NCHANNELS];   /* by bit number; entries of clear bits are ignored */
+} f110_track_preview;
+/* device form: d_out [N][P][D] float32 in device memory.  Asynchronous on the handle's stream; right behind a two-block step it
+ * runs per env block on the block's own stream (as f110_obs_encode_device does).  h_pinned (or NULL): f110_host_alloc memory of
+ * the same shape that receives a copy behind the kernel, complete after f110_sync. */
+int f110_track_preview_device(f110_sim *h, const f110_track_preview *spec, float *d_out /* [N][P][D] */, float *h_pinned);
+/* unit form on host arrays, on the track of `slot` (tracking need not be on): h_in [m][4] = x, y, theta, s per row.  It does not
+ * project: s comes from f110_track_project_batch.  h_out [m][P][D]; h_raw [m][P][8] or NULL: all eight channel values before
+ * scaling, an absent attribute 0.0; h_seg [m][P] or NULL: k per station. */
+int f110_track_preview_batch(f110_sim *h, const f110_track_preview *spec, int32_t slot, const double *h_in /* [m][4] x, y, theta, s */,
+                             int32_t m, float *h_out /* [m][P][D] */, double *h_raw /* [m][P][8] or NULL */, int32_t *h_seg /* [m][P] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
