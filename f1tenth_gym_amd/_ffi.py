@@ -93,6 +93,16 @@ PREVIEW_X, PREVIEW_Y, PREVIEW_TAN_X, PREVIEW_TAN_Y, PREVIEW_ATTR0, PREVIEW_ATTR1
 PREVIEW_NCHANNELS, PREVIEW_FRAME_EGO, PREVIEW_FRAME_WORLD, PREVIEW_MAX_POINTS, TRACK_MAX_ATTRS = 8, 0, 1, 32, 4
 
 
+class NeighborsSpec(C.Structure):
+    """struct f110_neighbors"""
+    _fields_ = [("k", C.c_int32), ("channels", C.c_int32), ("flags", C.c_int32), ("pad_", C.c_int32),
+                ("max_range", C.c_double), ("pad", C.c_double), ("scale", C.c_double * 10)]
+
+
+NBR_DX, NBR_DY, NBR_DIST, NBR_COS_DTH, NBR_SIN_DTH, NBR_V_X, NBR_V_Y, NBR_GAP_S, NBR_VALID, NBR_INDEX = (1 << b for b in range(10))
+NBR_NCHANNELS, NBR_MAX_K, NBR_MAX_AGENTS = 10, 8, 256
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -229,6 +239,8 @@ PROTOTYPES = {
     "f110_track_set_attrs": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32]),
     "f110_track_preview_device": (C.c_int, [C.c_void_p, C.POINTER(TrackPreviewSpec), C.c_void_p, C.c_void_p]),
     "f110_track_preview_batch": (C.c_int, [C.c_void_p, C.POINTER(TrackPreviewSpec), C.c_int32, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
+    "f110_neighbors_device": (C.c_int, [C.c_void_p, C.POINTER(NeighborsSpec), C.c_void_p, C.c_void_p]),
+    "f110_neighbors_batch": (C.c_int, [C.c_void_p, C.POINTER(NeighborsSpec), C.c_int32, C.c_double, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
     "f110_obs_encode_device": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p, C.c_void_p]),
     "f110_obs_encode_batch": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), _dp, _dp, _i32p, C.c_int32, C.c_void_p]),

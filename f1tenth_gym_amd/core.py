@@ -1141,6 +1141,48 @@ class BatchSim(object):
         res = [out] + ([rw] if raw else []) + ([sg] if segments else [])
         return res[0] if len(res) == 1 else tuple(res)
 
+    # ------------------------------------------------------------------ neighbours (f110_neighbors_*)
+    def neighbors_device(self, spec, out=None, pinned=None):
+        """every agent's K nearest opponents of its own env (neighbors.Neighbors) as a float32 DeviceArray [N][K][D], from the pose,
+        the speed and (for 'gap_s') the s column of the step just taken.  `out`: a float32 DeviceArray of spec.shape(N) to reuse
+        (None: a new one).  Enqueued on the handle's stream, per env block behind a two-block step (no host wait).  pinned: a
+        pinned_empty float32 array of the same shape that also receives the result, complete after sync().  'gap_s' needs
+        enable_track()."""
+        from .neighbors import Neighbors
+        nb = Neighbors.coerce(spec)
+        shape = nb.shape(self.N)
+        if out is None:
+            out = DeviceArray(self, shape, np.float32)
+        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
+            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
+        pp = None
+        if pinned is not None:
+            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
+                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
+            pp = pinned.ctypes.data
+        sp = nb.spec()
+        check(_ffi.lib().f110_neighbors_device(self._h, C.byref(sp), out.ptr, pp), self._h)
+        return out
+
+    def neighbors(self, rows, spec, A, track_L=0.0, raw=False, indices=False):
+        """unit form on host arrays: rows [m][5] = x, y, theta, v, s in env-major order, m a multiple of A (1 .. 256, whatever this
+        handle's num_agents is); track_L > 0 wraps 'gap_s' as a closed track of that length -> float32 [m][K][D]; with raw also
+        float64 [m][K][10] (every channel before scaling; an empty slot pad, 'valid' 0.0), with indices also int32 [m][K] (-1: empty)"""
+        from .neighbors import Neighbors
+        nb = Neighbors.coerce(spec)
+        r = as_f64(rows)
+        if r.ndim != 2 or r.shape[1] != 5:
+            raise ValueError("rows must be [m][5] = x, y, theta, v, s")
+        m = r.shape[0]
+        out = np.zeros(nb.shape(m), dtype=np.float32)
+        rw = np.zeros((m, nb.k, 10)) if raw else None
+        ix = np.zeros((m, nb.k), dtype=np.int32) if indices else None
+        sp = nb.spec()
+        check(_ffi.lib().f110_neighbors_batch(self._h, C.byref(sp), int(A), float(track_L), dptr(r), m, out.ctypes.data,
+                                              None if rw is None else dptr(rw), None if ix is None else i32ptr(ix)), self._h)
+        res = [out] + ([rw] if raw else []) + ([ix] if indices else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ------------------------------------------------------------------ rendering (f110_render_device, DESIGN §6c)
     def render_device(self, agents=None, width=64, height=64, view='ego', m_per_px=0.05, center=(0.0, 0.0), angle=0.0,
                       fwd_offset=0.0, layers=('map', 'cars'), car_size=None, rgb=False, palette=None, out=None):

@@ -207,6 +207,7 @@ struct f110_sim {
     bool trk_pinned_on = false;
     const float *obs_pinned = nullptr;    // f110_obs_encode_device: the page-locked block its last copy went to
     const float *preview_pinned = nullptr;   // f110_track_preview_device: likewise
+    const float *neighbors_pinned = nullptr; // f110_neighbors_device: likewise
     // scripted cars (f110_controllers_set): the specs and the per-agent assignment in device memory; gap_specs == 0: disarmed
     GapSpec *d_gap_specs = nullptr;
     int32_t *d_gap_assign = nullptr;
@@ -2116,12 +2117,13 @@ int f110_host_free(f110_sim *h, void *p)
                     o->trk_pinned = f110_track_host{};
                 }
             }
-            if (inside(o->obs_pinned) || inside(o->preview_pinned)) {   // an encode's or a preview's copy (on the env blocks' streams) may still be on its way into the block
+            if (inside(o->obs_pinned) || inside(o->preview_pinned) || inside(o->neighbors_pinned)) {   // an encode's, a preview's or a neighbour call's copy (on the env blocks' streams) may still be on its way into the block
                 (void)hipSetDevice(o->cfg.device_id);
                 for (hipStream_t gs : o->gstreams) (void)hipStreamSynchronize(gs);
                 (void)hipStreamSynchronize(o->stream);
                 if (inside(o->obs_pinned)) o->obs_pinned = nullptr;
                 if (inside(o->preview_pinned)) o->preview_pinned = nullptr;
+                if (inside(o->neighbors_pinned)) o->neighbors_pinned = nullptr;
             }
             if (!o->hb_valid && !o->fused_valid) continue;
             const f110_host_block &b = o->hb_host;
@@ -4722,6 +4724,150 @@ int f110_track_preview_batch(f110_sim *h, const f110_track_preview *spec, int32_
     TRY(sc.down(h_out, dout, rows * j.sp.D));
     if (h_raw) TRY(sc.down(h_raw, draw, rows * F110_PREVIEW_NCHANNELS));
     if (h_seg) TRY(sc.down(h_seg, dseg, rows));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- neighbours (f110_neighbors_*, include/f110.h) --------------------------------------------------------------------------------
+// the spec's refusals; on success the kernel's spec
+static int nbr_check_spec(f110_sim *h, const f110_neighbors *p, NbrSpec &o)
+{
+    if (!p) return fail(h, F110_ERR_INVALID, "neighbors: null spec");
+    if (p->k < 1 || p->k > F110_NBR_MAX_K) return fail(h, F110_ERR_INVALID, "neighbors: k = %d is outside 1..%d", p->k, (int)F110_NBR_MAX_K);
+    if (p->channels == 0 || (p->channels & ~((1 << F110_NBR_NCHANNELS) - 1))) return fail(h, F110_ERR_INVALID, "neighbors: channels = 0x%x is empty or has an unknown bit", p->channels);
+    if (p->flags != 0) return fail(h, F110_ERR_INVALID, "neighbors: flags = %d must be 0", p->flags);
+    if (!(p->max_range > 0.0)) return fail(h, F110_ERR_INVALID, "neighbors: max_range must be > 0 (+inf is allowed)");
+    if (!std::isfinite(p->pad)) return fail(h, F110_ERR_INVALID, "neighbors: pad must be finite");
+    o = NbrSpec{};
+    for (int b = 0; b < F110_NBR_NCHANNELS; ++b) {
+        o.scale[b] = 1.0;
+        if (!(p->channels >> b & 1)) continue;
+        if (!(std::isfinite(p->scale[b]) && p->scale[b] != 0.0)) return fail(h, F110_ERR_INVALID, "neighbors: scale[%d] must be finite and non-zero", b);
+        o.scale[b] = p->scale[b];
+        o.D += 1;
+    }
+    o.K = p->k;
+    o.KT = 1;
+    while (o.KT < o.K) o.KT *= 2;
+    o.channels = p->channels;
+    o.R2 = p->max_range * p->max_range;
+    o.pad = p->pad;
+    return F110_OK;
+}
+
+static void nbr_launch(NbrJob &j, hipStream_t st)
+{
+    if (j.envs <= 0) return;
+    j.shift = 0;
+    while ((1 << j.shift) < j.A) ++j.shift;
+    const dim3 grid = grid1d((size_t)j.envs, 256 >> j.shift), block(256);
+    switch (j.sp.KT) {
+    case 1: hipLaunchKernelGGL(k_neighbors<1>, grid, block, 0, st, j); break;
+    case 2: hipLaunchKernelGGL(k_neighbors<2>, grid, block, 0, st, j); break;
+    case 4: hipLaunchKernelGGL(k_neighbors<4>, grid, block, 0, st, j); break;
+    default: hipLaunchKernelGGL(k_neighbors<8>, grid, block, 0, st, j); break;
+    }
+}
+
+int f110_neighbors_device(f110_sim *h, const f110_neighbors *spec, float *d_out, float *h_pinned)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    NbrJob j{};
+    TRY(nbr_check_spec(h, spec, j.sp));
+    if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return fail(h, F110_ERR_INVALID, "neighbors: d_out is null or not 16-byte aligned");
+    const size_t N = (size_t)h->N, per_agent = (size_t)j.sp.K * j.sp.D;
+    if (h_pinned) {
+        std::lock_guard<std::mutex> lk(g_registry_mu);
+        const char *p = reinterpret_cast<const char *>(h_pinned);
+        auto it = g_host_blocks.upper_bound(p);
+        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
+        if (it != g_host_blocks.begin()) {
+            --it;
+            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
+        }
+        if (!inside) return fail(h, F110_ERR_INVALID, "neighbors: h_pinned is not [N][K][D] floats of f110_host_alloc memory");
+    }
+    const bool gap = (j.sp.channels & F110_NBR_GAP_S) != 0;
+    if (h->cfg.num_agents > F110_NBR_MAX_AGENTS) return fail(h, F110_ERR_STATE, "neighbors: %d agents per env, more than %d", h->cfg.num_agents, (int)F110_NBR_MAX_AGENTS);
+    if (gap) {
+        if (!h->track_on) return fail(h, F110_ERR_STATE, "neighbors: GAP_S is requested, but tracking is off (f110_track_enable)");
+        if (!h->multi_map) {
+            if (!track_has(h, 0)) return fail(h, F110_ERR_STATE, "neighbors: GAP_S is requested, but map slot 0 has no track (f110_track_set)");
+        } else {
+            for (int32_t m : h->env_map_host)
+                if (!track_has(h, m)) return fail(h, F110_ERR_STATE, "neighbors: GAP_S is requested, but map slot %d has no track (f110_track_set)", m);
+        }
+        if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size()) {
+            ENTER(h);
+            TRY(track_upload(h));
+        }
+    }
+    EnvBlocks w;   // behind a two-block step: each block's envs on the block's own stream (an agent reads its own env's rows and writes its own block)
+    TRY(env_blocks_follow(h, w));
+    j.tracks = gap ? h->d_tracks : nullptr;
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.A = h->cfg.num_agents;
+    j.px = h->dev.snap_pose;   // the post-step pose of the observation, the one s was computed from
+    j.py = h->dev.snap_pose + N;
+    j.pth = h->dev.snap_pose + 2 * N;
+    j.pv = h->dev.state + 3 * N;   // the live longitudinal speed (0 for an env re-seated inside the step)
+    j.ps = gap ? h->d_trk : nullptr;
+    j.stride = 1;
+    j.unit_L = 0.0;
+    j.out = d_out;
+    for (const EnvBlock &b : w) {
+        j.env0 = b.e0;
+        j.envs = b.count;
+        nbr_launch(j, b.stream);
+        if (h_pinned) {
+            const size_t i0 = (size_t)b.e0 * j.A, n = (size_t)b.count * j.A;
+            HIPCHK(h, hipMemcpyAsync(h_pinned + i0 * per_agent, d_out + i0 * per_agent, n * per_agent * sizeof(float), hipMemcpyDeviceToHost, b.stream));
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h_pinned) h->neighbors_pinned = h_pinned;
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, double track_L, const double *h_in, int32_t m, float *h_out,
+                         double *h_raw, int32_t *h_idx)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    NbrJob j{};
+    TRY(nbr_check_spec(h, spec, j.sp));
+    if (A < 1 || A > F110_NBR_MAX_AGENTS) return fail(h, F110_ERR_INVALID, "neighbors: A = %d is outside 1..%d", A, (int)F110_NBR_MAX_AGENTS);
+    if (!(track_L >= 0.0 && std::isfinite(track_L))) return fail(h, F110_ERR_INVALID, "neighbors: track_L must be finite and >= 0 (0: no wrap)");
+    if (m < 0 || m % A != 0 || (m > 0 && (!h_in || !h_out))) return fail(h, F110_ERR_INVALID, "neighbors: bad argument (m must be a multiple of A)");
+    if (m == 0) return F110_OK;
+    ENTER(h);
+    Scratch sc(h);
+    const size_t slots = (size_t)m * j.sp.K;
+    double *din = nullptr, *draw = nullptr;
+    float *dout = nullptr;
+    int32_t *didx = nullptr;
+    TRY(sc.up(h_in, 5 * (size_t)m, &din));
+    TRY(sc.up<float>(nullptr, slots * j.sp.D, &dout));
+    if (h_raw) TRY(sc.up<double>(nullptr, slots * F110_NBR_NCHANNELS, &draw));
+    if (h_idx) TRY(sc.up<int32_t>(nullptr, slots, &didx));
+    j.A = A;
+    j.env0 = 0;
+    j.envs = m / A;
+    j.px = din;
+    j.py = din + 1;
+    j.pth = din + 2;
+    j.pv = din + 3;
+    j.ps = din + 4;
+    j.stride = 5;
+    j.unit_L = track_L;
+    j.out = dout;
+    j.raw = draw;
+    j.idx = didx;
+    nbr_launch(j, h->stream);
+    HIPCHK(h, hipGetLastError());
+    TRY(sc.down(h_out, dout, slots * j.sp.D));
+    if (h_raw) TRY(sc.down(h_raw, draw, slots * F110_NBR_NCHANNELS));
+    if (h_idx) TRY(sc.down(h_idx, didx, slots));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }

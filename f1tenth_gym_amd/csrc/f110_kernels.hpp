@@ -4316,3 +4316,113 @@ __global__ void __launch_bounds__(256) k_track_preview(PreviewJob j)
         for (int q = sub; q < P * D; q += G) dst[q] = mine[q];
     }
 }
+
+// ---- neighbours (f110_neighbors_*; include/f110.h states the rule, f110_math.hpp nbr_* the arithmetic) ---------------------------
+// One lane per agent, a group of G lanes per env, G the next power of two >= A (1..256); 256 / G envs per workgroup.
+//  1. every lane loads its agent's columns, takes the one cos_sin and leaves (x, y, c, sn, v, s) in LDS, one column each (SoA,
+//     6 x 256 doubles = 12 KiB), so that a walk over b reads consecutive doubles of one column.
+//  2. every lane walks b = 0 .. A - 1 of its group: all lanes of a group read the same LDS address at the same time, which the LDS
+//     serves as a broadcast; the groups of a 32-lane half read doubles G apart, on different banks.  The KT best (d2, b) stay
+//     sorted in named registers (NbrBest<KT>, KT the power of two >= K: four instantiations, no register array indexed at run
+//     time).
+//  3. every lane re-reads its K winners' rows from LDS and evaluates the requested channels (unrolled over the ten bits, scales
+//     from the kernel arguments) into an LDS stage at its agent's place in the workgroup's output, which is one contiguous region
+//     of global memory (the live agents of a workgroup are consecutive); then all 256 lanes store the stage, consecutive lanes
+//     consecutive floats.  An agent's row of the stage has the odd pitch K * D | 1: at a pitch of 32 or 80 floats the lanes'
+//     writes would all meet on one or two banks.  The stage is 24 KiB: with the 12 KiB of columns a workgroup holds 36 KiB and
+//     four of them fit a CU's 160 KiB.  A workgroup's output can be 80 KiB (256 agents x 8 slots x 10 channels), so it goes out
+//     in pieces of whole agents (at most four); only the lanes of the piece evaluate, the others wait at the barrier.
+// Idle lanes (G > A) shadow the env's last agent and idle groups the workgroup's last env: they reach every barrier, write their
+// own LDS column slots only and store nothing.
+constexpr int kNbrStageFloats = 6144;
+
+// device form: envs [env0, env0 + envs), agent columns `stride` = 1 apart; the wrap length of GAP_S from tracks[env_map[e]] (slot 0
+// when env_map is nullptr), tracks == nullptr when GAP_S is not asked for.  unit form: rows [m][5], stride 5, env0 = 0, the wrap
+// length unit_L.
+struct NbrJob {
+    const TrackDesc *tracks;
+    const int32_t *env_map;
+    int32_t A, shift;                        // cars per env; lanes per env = 1 << shift
+    int32_t env0, envs;
+    const double *px, *py, *pth, *pv, *ps;   // ps == nullptr: s is not read (0.0)
+    int32_t stride;
+    double unit_L;
+    float *out;                              // [.][K][D]
+    double *raw;                             // [.][K][10] or nullptr
+    int32_t *idx;                            // [.][K] or nullptr
+    NbrSpec sp;
+};
+
+template <int KT>
+__global__ void __launch_bounds__(256) k_neighbors(NbrJob j)
+{
+    __shared__ double s_col[6][256];
+    __shared__ float s_out[kNbrStageFloats];
+    const int A = j.A, G = 1 << j.shift, K = j.sp.K, D = j.sp.D, KD = K * D;
+    const int tid = (int)threadIdx.x, sub = tid & (G - 1), grp = tid >> j.shift;
+    const int epw = 256 >> j.shift;
+    const int e_first = (int)blockIdx.x * epw;
+    const int e_here = min(epw, j.envs - e_first);   // >= 1 by the grid
+    const bool live = grp < e_here && sub < A;
+    const int e = j.env0 + e_first + (grp < e_here ? grp : e_here - 1);
+    const int a = sub < A ? sub : A - 1;
+    const size_t i = (size_t)e * A + a, r = i * j.stride;
+    NbrAgent me;
+    me.x = j.px[r];
+    me.y = j.py[r];
+    cos_sin(j.pth[r], me.c, me.sn);
+    me.v = j.pv[r];
+    me.s = j.ps ? j.ps[r] : 0.0;
+    double L = j.unit_L;
+    if (j.tracks) {
+        const TrackDesc td = j.tracks[j.env_map ? j.env_map[e] : 0];
+        L = td.closed ? td.L : 0.0;
+    }
+    s_col[0][tid] = me.x;
+    s_col[1][tid] = me.y;
+    s_col[2][tid] = me.c;
+    s_col[3][tid] = me.sn;
+    s_col[4][tid] = me.v;
+    s_col[5][tid] = me.s;
+    __syncthreads();
+    const int base = tid - sub;
+    NbrBest<KT> best;
+    best.clear();
+    for (int b = 0; b < A; ++b) best.offer(nbr_d2(me.x, me.y, s_col[0][base + b], s_col[1][base + b]), b, a, j.sp.R2);
+    const int n_live = e_here * A, w = grp * A + sub;   // the workgroup's live agents are consecutive; w: this one's place
+    const int KDp = KD | 1;                             // the stage's row pitch: odd, so the lanes' rows start on different banks
+    const int per = kNbrStageFloats / KDp;              // agents per piece (>= 75)
+    const int step_w = 256 / KD, step_c = 256 - step_w * KD;   // what 256 floats further on means in (agent, float of the agent)
+    float *dst = j.out + (size_t)(j.env0 + e_first) * A * KD;
+    for (int p0 = 0; p0 < n_live; p0 += per) {
+        if (live && w >= p0 && w < p0 + per) {
+            float *o = s_out + (w - p0) * KDp;
+#pragma unroll
+            for (int k = 0; k < KT; ++k) {
+                if (k < K) {
+                    const int ib = best.idx[k];
+                    const int q = base + (ib >= 0 ? ib : sub);
+                    NbrAgent nb;
+                    nb.x = s_col[0][q];
+                    nb.y = s_col[1][q];
+                    nb.c = s_col[2][q];
+                    nb.sn = s_col[3][q];
+                    nb.v = s_col[4][q];
+                    nb.s = s_col[5][q];
+                    const size_t slot = i * K + k;
+                    nbr_slot(j.sp, me, nb, ib, L, o + k * D, j.raw ? j.raw + slot * NBR_NCHANNELS : nullptr, j.idx ? j.idx + slot : nullptr);
+                }
+            }
+        }
+        __syncthreads();
+        const int nf = min(per, n_live - p0) * KD;
+        int qw = tid / KD, qc = tid - qw * KD;
+        for (int q = tid; q < nf; q += 256) {
+            dst[(size_t)p0 * KD + q] = s_out[qw * KDp + qc];
+            qw += step_w;
+            qc += step_c;
+            if (qc >= KD) qc -= KD, ++qw;
+        }
+        __syncthreads();
+    }
+}

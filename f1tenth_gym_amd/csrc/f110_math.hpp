@@ -1518,4 +1518,134 @@ F110_HD void preview_row(const PreviewSpec &sp, const PreviewTrack &tr, double p
     }
 }
 
+// ------------------------------------------------------------------ neighbours (include/f110.h, f110_neighbors)
+// No reference counterpart.  Float64 adds, multiplies, divides, compares and one sqrt, nothing to contract; the one cos_sin per
+// agent is the only libm call.
+enum { NBR_DX = 0, NBR_DY, NBR_DIST, NBR_COS_DTH, NBR_SIN_DTH, NBR_V_X, NBR_V_Y, NBR_GAP_S, NBR_VALID, NBR_INDEX, NBR_NCHANNELS };
+enum { NBR_MAX_K = 8, NBR_MAX_AGENTS = 256 };
+
+struct NbrSpec {
+    int32_t K, channels;   // slots; channel bits
+    int32_t D, KT;         // popcount(channels); the kept list's length: the power of two >= K
+    double R2, pad;        // max_range * max_range; what an empty slot holds
+    double scale[NBR_NCHANNELS];
+};
+
+// one agent as its env's other agents see it
+struct NbrAgent {
+    double x, y, c, sn, v, s;
+};
+
+F110_HD double nbr_d2(double xa, double ya, double xb, double yb)
+{
+    const double rx = xb - xa, ry = yb - ya;
+    return rx * rx + ry * ry;
+}
+
+// the KT best (d2, b) so far, ascending; idx < 0 marks an empty slot.  The candidates arrive in ascending b, so a strict compare
+// leaves equal d2 in ascending b.  Fully unrolled over constant indices: d and idx live in named registers.
+template <int KT>
+struct NbrBest {
+    double d[KT];
+    int32_t idx[KT];
+    F110_HD void clear()
+    {
+#pragma unroll
+        for (int q = 0; q < KT; ++q) d[q] = 0.0, idx[q] = -1;
+    }
+    // candidate b at d2, already found eligible
+    F110_HD void insert(double d2, int32_t b)
+    {
+#pragma unroll
+        for (int q = KT - 1; q >= 0; --q) {
+            const bool before = idx[q] < 0 || d2 < d[q];
+            if (q + 1 < KT) {
+                d[q + 1] = before ? d[q] : d[q + 1];
+                idx[q + 1] = before ? idx[q] : idx[q + 1];
+            }
+            d[q] = before ? d2 : d[q];
+            idx[q] = before ? b : idx[q];
+        }
+    }
+    // candidate b of agent a: the eligibility rule, then the insertion (a NaN d2 fails the compare)
+    F110_HD void offer(double d2, int32_t b, int32_t a, double R2)
+    {
+        if (b != a && d2 <= R2) insert(d2, b);
+    }
+};
+
+// g = s_b - s_a, wrapped once on a closed track of length L (L == 0: no wrap)
+F110_HD double nbr_gap(double sa, double sb, double L)
+{
+    double g = sb - sa;
+    if (L > 0.0) {
+        const double half = 0.5 * L;
+        if (g > half) g = g - L;
+        else if (g <= -half) g = g + L;
+    }
+    return g;
+}
+
+// the ten channel values of neighbour b (index ib) as a sees it, before scaling; only the bits of `mask` are evaluated, the rest 0.0
+F110_HD void nbr_values(const NbrAgent &a, const NbrAgent &b, int32_t ib, double L, int32_t mask, double *v)
+{
+    const double rx = b.x - a.x, ry = b.y - a.y;
+    const double cd = b.c * a.c + b.sn * a.sn, sd = b.sn * a.c - b.c * a.sn;
+    v[NBR_DX] = a.c * rx + a.sn * ry;
+    v[NBR_DY] = a.c * ry - a.sn * rx;
+    v[NBR_DIST] = (mask >> NBR_DIST & 1) ? sqrt(rx * rx + ry * ry) : 0.0;
+    v[NBR_COS_DTH] = cd;
+    v[NBR_SIN_DTH] = sd;
+    v[NBR_V_X] = b.v * cd - a.v;
+    v[NBR_V_Y] = b.v * sd;
+    v[NBR_GAP_S] = (mask >> NBR_GAP_S & 1) ? nbr_gap(a.s, b.s, L) : 0.0;
+    v[NBR_VALID] = 1.0;
+    v[NBR_INDEX] = (double)ib;
+}
+
+// one output element of a filled slot: a float64 divide, then the conversion (round to nearest even)
+F110_HD float nbr_scaled(double v, double scale) { return (float)(v / scale); }
+// ... and of an empty one
+F110_HD float nbr_empty(int bit, double pad) { return bit == NBR_VALID ? 0.0f : (float)pad; }
+
+// slot k's D floats at o (and its ten raw values and its index) from the winner b with index ib (< 0: none, b is not read)
+F110_HD void nbr_slot(const NbrSpec &sp, const NbrAgent &a, const NbrAgent &b, int32_t ib, double L, float *o, double *raw, int32_t *idx)
+{
+    double v[NBR_NCHANNELS] = {};
+    if (ib >= 0) nbr_values(a, b, ib, L, raw ? (1 << NBR_NCHANNELS) - 1 : sp.channels, v);
+#pragma unroll
+    for (int bit = 0; bit < NBR_NCHANNELS; ++bit) {
+        if (raw) raw[bit] = ib >= 0 ? v[bit] : (bit == NBR_VALID ? 0.0 : sp.pad);
+        if (sp.channels >> bit & 1) *o++ = ib >= 0 ? nbr_scaled(v[bit], sp.scale[bit]) : nbr_empty(bit, sp.pad);
+    }
+    if (idx) *idx = ib;
+}
+
+// one env, serially (the kernel gives every agent a lane; this is what the unit harness runs): rows [A][5] = x, y, theta, v, s;
+// out [A][K][D], raw [A][K][10] or null, idx [A][K] or null
+template <int KT>
+F110_HD void nbr_env(const NbrSpec &sp, const double *rows, int A, double L, NbrAgent *env, float *out, double *raw, int32_t *idx)
+{
+    for (int a = 0; a < A; ++a) {
+        const double *r = rows + 5 * (size_t)a;
+        env[a].x = r[0];
+        env[a].y = r[1];
+        cos_sin(r[2], env[a].c, env[a].sn);
+        env[a].v = r[3];
+        env[a].s = r[4];
+    }
+    for (int a = 0; a < A; ++a) {
+        NbrBest<KT> best;
+        best.clear();
+        for (int b = 0; b < A; ++b) best.offer(nbr_d2(env[a].x, env[a].y, env[b].x, env[b].y), b, a, sp.R2);
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            if (k >= sp.K) break;
+            const size_t slot = (size_t)a * sp.K + k;
+            const int32_t ib = best.idx[k];
+            nbr_slot(sp, env[a], env[ib >= 0 ? ib : a], ib, L, out + slot * sp.D, raw ? raw + slot * NBR_NCHANNELS : nullptr, idx ? idx + slot : nullptr);
+        }
+    }
+}
+
 }  // namespace f110

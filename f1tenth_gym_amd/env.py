@@ -21,6 +21,7 @@ from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
 from .sim import Integrator, Simulator
 from .track_preview import TrackPreview
+from .neighbors import Neighbors
 from .track import Track
 
 try:  # pragma: no cover - gym is absent from the build image
@@ -216,6 +217,12 @@ class F110Env(_EnvBase):
             if self.track is None:
                 raise ValueError("track_preview= needs a track (track=...)")
             self.track_preview.check_track(self.track)
+        # neighbours: neighbors= adds obs['neighbors'], float32 [A][K][D], computed on the device after the step
+        self.neighbors = None
+        if kwargs.get('neighbors') is not None:
+            self.neighbors = Neighbors.coerce(kwargs['neighbors'])
+            if self.neighbors.needs_track and self.track is None:
+                raise ValueError("neighbors= with 'gap_s' needs a track (track=...)")
         # randomised start poses: random_start= (a ResetSampler or a dict of its settings) makes reset() without
         # poses draw them on the track
         self.random_start = None
@@ -241,6 +248,10 @@ class F110Env(_EnvBase):
             pv = self.sim.batch.track_preview_device(self.track_preview)
             obs['track_preview'] = pv.download()
             pv.free()
+        if self.neighbors is not None:
+            nb = self.sim.batch.neighbors_device(self.neighbors)
+            obs['neighbors'] = nb.download()
+            nb.free()
         obs['lap_times'] = self._lap.lap_times[0]
         obs['lap_counts'] = self._lap.lap_counts[0]
         self.current_obs = obs
@@ -364,6 +375,12 @@ class F110VecEnv(object):
     poses and progress), is computed on the device behind the step and lands in page-locked memory with the rest of the
     block, so it needs device_logic=True and a track (ValueError otherwise; any other loop calls
     env.sim.batch.track_preview_device after its step).  A persistent view like the others; it holds no state.
+
+    Neighbours (no reference counterpart): `neighbors=` (a Neighbors or a dict of its settings) adds
+    obs['neighbors'], float32 [E][A][K][D]: each car's K nearest opponents of its own env in its own frame (position, distance,
+    relative heading and velocity, gap along the track, validity, index).  It belongs to the observation it comes with, is
+    computed on the device behind the step and lands in page-locked memory, so it needs device_logic=True, and a track only
+    for 'gap_s' (ValueError otherwise; any other loop calls env.sim.batch.neighbors_device after its step).  It holds no state.
     """
 
     # every key of the reference's observation (base_classes.py:594-610, docs/api/obv.rst:6-14)
@@ -375,7 +392,7 @@ class F110VecEnv(object):
 
     def __init__(self, num_envs, auto_reset=False, device_logic=False, obs_fields=None, copy_obs=False,
                  episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, scripted=None,
-                 track_preview=None, **kwargs):
+                 track_preview=None, neighbors=None, **kwargs):
         self.num_envs = int(num_envs)
         self.seed = kwargs.get('seed', 12345)
         self.map_name, self.map_path = _resolve_map_path(kwargs)
@@ -422,6 +439,13 @@ class F110VecEnv(object):
             tracks = {slot: Track.coerce(t) for slot, t in tracks.items()}
             for t in tracks.values():
                 self.track_preview.check_track(t)
+        self.neighbors = None
+        if neighbors is not None:
+            self.neighbors = Neighbors.coerce(neighbors)
+            if not self.device_logic:
+                raise ValueError("neighbors= needs device_logic=True (any other loop calls env.sim.batch.neighbors_device after its step)")
+            if self.neighbors.needs_track and not tracks:
+                raise ValueError("neighbors= with 'gap_s' needs a track (track= or tracks=)")
         self.encoded_stack = None
         if not tracks and any(f in self._TRACK for f in self.obs_fields):
             raise ValueError("the track fields of obs_fields need a track (track= or tracks=)")
@@ -524,6 +548,12 @@ class F110VecEnv(object):
             self._prv_pinned = b.pinned_empty(shape, np.float32)
             self._prv_pinned[...] = 0.0
             obs["track_preview"] = self._prv_pinned.reshape((E, A) + shape[1:])
+        if self.neighbors is not None:       # likewise the neighbours
+            shape = self.neighbors.shape(E * A)
+            self.neighbors_buffer = b.device_array(shape, np.float32)
+            self._nbr_pinned = b.pinned_empty(shape, np.float32)
+            self._nbr_pinned[...] = 0.0
+            obs["neighbors"] = self._nbr_pinned.reshape((E, A) + shape[1:])
         self._ret_views = (obs, reward, v["done"].view(np.bool_), info)
 
     def update_params_batch(self, params):
@@ -629,8 +659,8 @@ class F110VecEnv(object):
             self.sim._noise.ensure(b, self.sim._steps_since_full_reset + 1)
         if actions is not None and actions is not self.action_buffer:
             hb.actions[...] = np.asarray(actions, dtype=np.float64).reshape(hb.actions.shape)
-        if self._encode or self.track_preview is not None:
-            # one wait per step: the step enqueued without a wait, the encode / the preview and their copies into page-locked memory behind it
+        if self._encode or self.track_preview is not None or self.neighbors is not None:
+            # one wait per step: the step enqueued without a wait, the encode / the preview / the neighbours and their copies into page-locked memory behind it
             b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
                         scripted=self.scripted is not None)
             if self._encode:
@@ -638,6 +668,8 @@ class F110VecEnv(object):
                 self._enc_fill = False
             if self.track_preview is not None:
                 b.track_preview_device(self.track_preview, self.preview_buffer, pinned=self._prv_pinned)
+            if self.neighbors is not None:
+                b.neighbors_device(self.neighbors, self.neighbors_buffer, pinned=self._nbr_pinned)
             if sync:
                 b.sync()
         else:

@@ -97,6 +97,9 @@ class ShardedVecEnv(object):
         if kwargs.get('track_preview') is not None:  # one preview for every shard; obs['track_preview'] is concatenated along the env axis
             from .track_preview import TrackPreview
             kwargs['track_preview'] = TrackPreview.coerce(kwargs['track_preview'])
+        if kwargs.get('neighbors') is not None:      # one spec for every shard; obs['neighbors'] is concatenated along the env axis
+            from .neighbors import Neighbors
+            kwargs['neighbors'] = Neighbors.coerce(kwargs['neighbors'])
         scripted = kwargs.pop('scripted', None)      # scripted cars: the global assignment [E][A], sliced by shard; the controllers shared
         if scripted is not None:
             from .gap_follower import coerce_scripted

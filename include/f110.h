@@ -833,6 +833,56 @@ int f110_track_preview_device(f110_sim *h, const f110_track_preview *spec, float
 int f110_track_preview_batch(f110_sim *h, const f110_track_preview *spec, int32_t slot, const double *h_in /* [m][4] x, y, theta, s */,
                              int32_t m, float *h_out /* [m][P][D] */, double *h_raw /* [m][P][8] or NULL */, int32_t *h_seg /* [m][P] or NULL */);
 
+/* ---- neighbours: each agent's K nearest opponents of its own env, in its own frame (no reference counterpart: what overtaking,
+ * blocking and self-play setups compute with an all-pairs search on the host) ----
+ * It runs only when called, keeps no state in the handle and changes no simulator state.  Everything is float64 without
+ * contraction, every operation one correctly rounded IEEE operation except one cos and one sin per agent.
+ * Agent n = e * A + a looks at the other agents b != a of its env e.  Per agent: (x, y, theta) is the observation's pose of the step
+ * just taken (agent_poses, the one `s` was computed from and no in-step re-seat overwrites), v is state[3] as it stands (the
+ * encoder's VX rule: 0 for an env re-seated inside the step), s the track column (read only when GAP_S is asked for), and
+ * c_a = cos theta_a, sn_a = sin theta_a, computed once per agent.  For the pair (a, b):
+ *   rx = x_b - x_a;  ry = y_b - y_a;  d2 = rx * rx + ry * ry
+ * Candidate b is eligible iff b != a and d2 <= R2, R2 = max_range * max_range computed once (max_range > 0, +inf allowed); a NaN
+ * d2 is never eligible.  The eligible candidates are ordered by ascending d2, equal d2 by ascending b; the first K fill slots
+ * 0 .. K - 1.  Channels, by bit number:
+ *   0 DX      c_a * rx + sn_a * ry                 5 V_X    v_b * cd - v_a
+ *   1 DY      c_a * ry - sn_a * rx                 6 V_Y    v_b * sd
+ *   2 DIST    sqrt(d2)                             7 GAP_S  g = s_b - s_a; on a closed track of length L:
+ *   3 COS_DTH cd = c_b * c_a + sn_b * sn_a                  if (g > 0.5 * L) g = g - L; else if (g <= -0.5 * L) g = g + L
+ *   4 SIN_DTH sd = sn_b * c_a - c_b * sn_a         8 VALID  1.0        9 INDEX  (double)b
+ * Output.  out[n][k][.] holds the channels of the set bits in ascending bit order, each (float)(value / scale[bit]): a float64
+ * divide, then the conversion, rounding to nearest even.  A slot without a neighbour holds (float)pad in every requested channel,
+ * unscaled, except VALID, which is 0.0f there.  num_agents == 1 is legal: every slot is then empty.
+ * Refused with F110_ERR_INVALID, nothing launched or written: k outside 1..8, channels 0 or with an unknown bit, flags != 0,
+ *   max_range NaN or <= 0, a pad that is not finite, a zero or non-finite scale of a set bit, a null or not 16-byte aligned d_out,
+ *   an h_pinned that is not [N][K][D] floats of f110_host_alloc memory.
+ * Refused with F110_ERR_STATE: GAP_S while tracking is off, GAP_S while a slot in use has no track, num_agents > 256.
+ * Not offered: a field-of-view filter, ordering by track gap, race position, feeding the result into the encoder's stack, a
+ * slip-aware velocity. */
+enum { F110_NBR_DX = 1, F110_NBR_DY = 2, F110_NBR_DIST = 4, F110_NBR_COS_DTH = 8, F110_NBR_SIN_DTH = 16, F110_NBR_V_X = 32,
+       F110_NBR_V_Y = 64, F110_NBR_GAP_S = 128, F110_NBR_VALID = 256, F110_NBR_INDEX = 512, F110_NBR_NCHANNELS = 10 };
+enum { F110_NBR_MAX_K = 8, F110_NBR_MAX_AGENTS = 256 };
+typedef struct f110_neighbors {
+    int32_t k;          /* K, 1..8 slots per agent */
+    int32_t channels;   /* F110_NBR_* bits; D = popcount */
+    int32_t flags;      /* 0 */
+    int32_t pad_;       /* alignment; ignored */
+    double max_range;   /* metres, > 0, +inf allowed */
+    double pad;         /* what an empty slot holds, finite */
+    double scale[F110_NBR_NCHANNELS];   /* by bit number; entries of clear bits are ignored */
+} f110_neighbors;
+/* device form: d_out [N][K][D] float32 in device memory.  Asynchronous on the handle's stream; right behind a two-block step it
+ * runs per env block on the block's own stream (as f110_track_preview_device does).  h_pinned (or NULL): f110_host_alloc memory
+ * of the same shape that receives a copy behind the kernel, complete after f110_sync.  On a closed track GAP_S wraps with the
+ * length of the track on the env's map slot; on an open one it does not wrap. */
+int f110_neighbors_device(f110_sim *h, const f110_neighbors *spec, float *d_out /* [N][K][D] */, float *h_pinned);
+/* unit form on host arrays: h_in [m][5] = x, y, theta, v, s per row, env-major; m a multiple of A, A in 1..256 whatever the
+ * handle's num_agents is.  track_L > 0 wraps GAP_S as a closed track of that length, 0 does not wrap (anything else is refused).
+ * h_out [m][K][D]; h_raw [m][K][10] or NULL: all ten channel values before scaling, in an empty slot pad and VALID 0.0; h_idx
+ * [m][K] or NULL: b per slot, -1 for an empty one. */
+int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, double track_L, const double *h_in /* [m][5] x, y, theta, v, s */,
+                         int32_t m, float *h_out /* [m][K][D] */, double *h_raw /* [m][K][10] or NULL */, int32_t *h_idx /* [m][K] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
