@@ -85,6 +85,29 @@ def test_unit_form_matches_model_over_the_grid(amd):
         b.close()
 
 
+def test_unit_form_matches_model_over_the_launch_forms(amd):
+    """the rows of ref.launch_form_grid(): both sides of the staging rule (k_obs_encode<true> with exactly 64 KiB of LDS,
+    k_obs_encode<false> walking the window in HBM from beam_lo), F up to 16, F * D up to the cap, every phase of the aligned store.
+    profiles/obs_encoder_launch_forms.txt is to hold the kernel names a trace of this test sees."""
+    rng = np.random.default_rng(13)
+    rows = ref.launch_form_grid()
+    sims = {B: amd.BatchSim(num_envs=1, num_agents=1, num_beams=B) for B in sorted({r[0] for r in rows})}
+    forms = set()
+    for row in rows:
+        B, beams, K, pool, F, fill, feats, staged = row
+        enc = ref.launch_form_encoder(amd.ObsEncoder, row, SCALES)
+        W = B if beams is None else beams[1] - beams[0]
+        assert ref.planned_staged(W, F, enc.dim) is staged, row
+        scans, cols, sc, stack = ref.launch_form_inputs(rng, 7, row, enc.dim)
+        got = sims[B].obs_encode_batch(enc, scans, cols, sc, stack, fill)
+        _same_bits(got, ref.encode(enc, scans, cols, sc, stack, fill), "B=%d beams=%r K=%d %s F=%d fill=%r %s" % (
+            B, beams, K, pool, F, fill, "staged" if staged else "unstaged"))
+        forms.add(staged)
+    assert forms == {True, False}
+    for b in sims.values():
+        b.close()
+
+
 # ---- the device form through noisy steps with in-step re-seats ---------------------------------------------------------------
 def _sim(amd, E, A=2, B=1080, track=False, maps=False, **kw):
     s = amd.BatchSim(num_envs=E, num_agents=A, num_beams=B, **kw)
@@ -116,9 +139,12 @@ def _armed(s, E, A):
     ("track", 2, 1080, True, False, dict(sectors=7, pool="center", features=ref.FEATURES, frames=4)),
     ("beams_4096", 2, 4096, False, False, dict(sectors=270, pool="mean", features=("vx", "collision"), frames=2)),
     ("per_env_maps", 2, 1080, False, True, dict(sectors=108, pool="min", features=FIVE, frames=4)),
+    # F * D = 16 * 512 = 8192 next to a 4096-beam row: k_obs_encode<false>; the stack is 32 KiB per agent, 4 MiB in all
+    ("unstaged_16_frames", 2, 4096, True, False, dict(sectors=504, pool="mean", features=ref.FEATURES, frames=16)),
 ])
 def test_device_form_follows_model_through_reseats(amd, name, A, B, track, maps, enc_kw):
     E, T = 64, 120
+    assert ref.planned_staged(B, enc_kw["frames"], enc_kw["sectors"] + len(enc_kw["features"])) is (name != "unstaged_16_frames")
     s = _sim(amd, E, A, B, track, maps)
     d_act = _armed(s, E, A)
     enc = amd.ObsEncoder(range_clip=10.0, range_scale=10.0, scales=SCALES, **enc_kw)

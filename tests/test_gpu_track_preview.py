@@ -167,8 +167,24 @@ def test_device_form_follows_model_through_reseats(amd, race, A):
 
 # ---- two map slots ------------------------------------------------------------------------------------------------------------------
 def test_every_agent_gets_its_own_slots_stations(amd, race):
-    tab0, xy0, a0 = race
-    tab1, xy1, a1 = ref.circle(1500, radius=30.0, attrs=4)     # longer than the column the kernel stages
+    _two_slots(amd, race, "race", "circle_1500")
+
+
+@pytest.mark.parametrize("first,second", [("race", "circle_2049"), ("circle_2049", "race"), ("circle_2048", "race")])
+def test_two_slots_either_side_of_the_staging_boundary(amd, race, first, second):
+    _two_slots(amd, race, first, second)
+
+
+def _two_slots(amd, race, first, second):
+    """slot 0 / slot 1.  The kernel stages `cum` of the slot of the workgroup's first agent when that track has at most
+    ref.STAGED_SEGS = 2048 segments; every other lane probes its own slot's column in L2.  The 1500-segment circle is staged
+    where it comes first; the 2049-segment one never is: on slot 0 a workgroup that starts on it stages nothing, on slot 1 behind
+    the 782-segment raceline its lanes probe L2 next to staged ones.  The three assignments put either slot first in a workgroup
+    (16 envs a workgroup with P = 8, 32 with P = 3: envs 0, 16, 32, ... start one)."""
+    made = {"race": lambda: race, "circle_1500": lambda: ref.circle(1500, radius=30.0, attrs=4),
+            "circle_2049": lambda: ref.circle_2049(True, 4), "circle_2048": lambda: ref.circle_2048(True, 4)}
+    (tab0, xy0, a0), (tab1, xy1, a1) = made[first](), made[second]()
+    assert (tab0.nseg, tab1.nseg) == tuple({"race": 782, "circle_1500": 1500, "circle_2049": 2049, "circle_2048": 2048}[n] for n in (first, second))
     E, A = 70, 2
     N = E * A
     s = amd.BatchSim(num_envs=E, num_agents=A)
@@ -176,7 +192,10 @@ def test_every_agent_gets_its_own_slots_stations(amd, race):
     s.add_map_image(*load_map_image("example_map"))
     s.set_track(_track(amd, xy0, True, a0), 0)
     s.set_track(_track(amd, xy1, True, a1), 1)
-    for env_map in (np.arange(E) % 2, (np.arange(E) + 1) % 2, (np.arange(E) // 3) % 2):   # either slot first in a workgroup
+    env_maps = (np.arange(E) % 2, (np.arange(E) + 1) % 2, (np.arange(E) // 3) % 2)   # either slot first in a workgroup
+    for step in (16, 32):                              # the first envs of the workgroups: all slot 0, all slot 1, mixed
+        assert [{int(m[e]) for e in range(0, E, step)} for m in env_maps] == [{0}, {1}, {0, 1}], step
+    for env_map in env_maps:
         s.set_env_maps(env_map)
         s.enable_track()
         s.reset(bench_start_poses(E, A))
@@ -184,6 +203,7 @@ def test_every_agent_gets_its_own_slots_stations(amd, race):
         slot = np.repeat(env_map, A)
         poses, arc = _pose_and_s(s)
         for p in (amd.TrackPreview(points=8, channels=ALL8, frame="world"), amd.TrackPreview(points=3, spacing=2.0, channels=ALL8, frame="ego")):
+            assert p.reach < min(tab0.L, tab1.L)
             out = s.track_preview_device(p).download()
             for m, tab in ((0, tab0), (1, tab1)):
                 _check_device(tab, p, poses[slot == m], arc[slot == m], out[slot == m], "slot %d %s" % (m, p.frame))

@@ -163,3 +163,46 @@ def test_harness_features_only_and_subnormal_results(hh):
     got = harness_encode(hh, enc, scans, cols, np.array([2, 2]), np.zeros((2, 1, 62), np.float32), False)
     want = ref.encode(enc, scans, cols, np.array([2, 2]), np.zeros((2, 1, 62), np.float32), False)
     assert np.array_equal(ref.bits(got), ref.bits(want)) and np.count_nonzero((np.abs(want) < 1.1754944e-38) & (want != 0)) >= 19
+
+
+# ---- the launch forms the host chooses: the staging rule's boundaries, F above 4, F * D at the cap ---------------------------------
+def test_launch_form_grid_sits_on_both_sides_of_the_staging_rule():
+    """the rule restated in the model file gives every row the side written next to it, so the grid cannot drift to one side;
+    both kinds of row that ask for exactly 64 KiB are present, and the products an encoder cannot have are named"""
+    rows = ref.launch_form_grid()
+    unstaged = exact = 0
+    seen_F, starts = set(), set()
+    for row in rows:
+        B, beams, K, pool, F, fill, feats, staged = row
+        enc = ref.launch_form_encoder(ObsEncoder, row, GRID_SCALES)
+        W = B if beams is None else beams[1] - beams[0]
+        assert enc.dim == K + len(feats) and ref.planned_staged(W, F, enc.dim) is staged, row
+        unstaged += not staged
+        exact += staged and ref.planned_lds(W, F, enc.dim) == ref.LDS_BYTES
+        seen_F.add(F)
+        if not staged and beams is not None and beams[0] != 0:
+            starts.add(pool)
+    assert unstaged >= 6 and exact >= 4 and {5, 8, 16} <= seen_F and starts == {"min", "mean", "center"}
+    windows = {(r[0] if r[1] is None else r[1][1] - r[1][0], r[4] * (r[2] + len(r[6]))) for r in rows}
+    assert {(8190, 1), (8191, 1), (8192, 1), (4096, 8188), (4096, 8190), (4096, 8192)} <= windows
+    # the rule itself at the boundary no encoder reaches: 8189 is the last staged product of a 4096-beam row, 8190 the first unstaged
+    assert ref.planned_staged(4096, 1, 8189) and ref.planned_lds(4096, 1, 8189) == 65536 and not ref.planned_staged(4096, 1, 8190)
+    assert ref.planned_staged(8190, 1, 1) and ref.planned_lds(8190, 1, 1) == 65536 and not ref.planned_staged(8191, 1, 1)
+    assert all(8189 % F or 8189 // F > 4096 + 8 for F in range(1, 17))
+    # every phase of the aligned store occurs among the staged everyday rows and among the unstaged ones
+    for staged in (True, False):
+        phases = {(i * r[4] * (r[2] + len(r[6]))) % 4 for r in rows if r[7] is staged for i in range(7)}
+        assert phases == {0, 1, 2, 3}, staged
+
+
+@needs_hipcc
+def test_harness_matches_model_over_the_launch_form_grid(hh):
+    rng = np.random.default_rng(13)
+    for row in ref.launch_form_grid():
+        B, beams, K, pool, F, fill, feats, staged = row
+        enc = ref.launch_form_encoder(ObsEncoder, row, GRID_SCALES)
+        scans, cols, sc, stack = ref.launch_form_inputs(rng, 7, row, enc.dim)
+        assert set(sc) == {0, 1, 2} and np.isnan(scans).any() and np.isinf(scans).any()
+        want = ref.encode(enc, scans, cols, sc, stack, fill)
+        got = harness_encode(hh, enc, scans, cols, sc, stack, fill)
+        assert np.array_equal(ref.bits(got), ref.bits(want)), row

@@ -179,6 +179,16 @@ def grid_case(k, case, rng, m=6):
     return tab, xy, a, s, poses, arc
 
 
+def test_grid_holds_both_sides_of_the_staging_boundary():
+    """the circles named after their segment counts have them, closed and open; the default circle is on the staged side"""
+    for closed in (True, False):
+        assert ref.circle_2048(closed, 0)[0].nseg == ref.STAGED_SEGS and ref.circle_2049(closed, 4)[0].nseg == ref.STAGED_SEGS + 1
+    assert ref.circle(closed=True)[0].nseg == 1500 <= ref.STAGED_SEGS
+    names = [c[0] for c in ref.unit_grid()]
+    assert names.count("circle_2048") == 16 and names.count("circle_2049") == 16
+    assert {(c[2], c[3], c[4]) for c in ref.unit_grid() if c[0] == "circle_2049"} == {(cl, a, P) for cl in (True, False) for a in (0, 4) for P in (1, 32)}
+
+
 def test_track_preview_method_matches_model_over_the_grid():
     """Track.preview (vectorised NumPy) against the model; the condition of the EGO bound: with NumPy's cos / sin on both sides
     no float32 output differs at all"""

@@ -169,11 +169,25 @@ def example_raceline(closed=True, attrs=4):
 
 
 def circle(n=1500, radius=30.0, closed=True, attrs=1):
-    """n points on a circle (n segments closed): longer than the LDS-staged column of the kernel"""
+    """n points on a circle (n segments closed, n - 1 open).  The kernel stages `cum` of a track of at most STAGED_SEGS segments
+    in LDS: the 1500 segments of the default are staged (they are more than the projection kernel stages, 1024)"""
     ang = 2.0 * np.pi * np.arange(n) / n
     xy = np.column_stack([radius * np.cos(ang) + 3.0, radius * np.sin(ang) - 2.0])
     a = None if attrs == 0 else np.column_stack([np.sin(3.0 * ang), 2.0 + np.cos(ang), ang * 0.0 + 1.5, np.cos(5.0 * ang)])[:, :attrs]
     return Tables(xy, closed, a), xy, a
+
+
+STAGED_SEGS = 2048    # kPreviewLdsSegs (f110_kernels.hpp): a longer track's `cum` is probed in L2
+
+
+def circle_2048(closed=True, attrs=1):
+    """2048 segments, closed or open: the longest track whose `cum` is staged"""
+    return circle(2048 if closed else 2049, closed=closed, attrs=attrs)
+
+
+def circle_2049(closed=True, attrs=1):
+    """2049 segments, closed or open: the shortest track whose `cum` is not staged"""
+    return circle(2049 if closed else 2050, closed=closed, attrs=attrs)
 
 
 def poses_near(tab, rng, m, spread=0.4):
@@ -210,6 +224,13 @@ def unit_grid():
                 for pi, P in enumerate(GRID_P):
                     if (ci + ai + pi) % 2 and name != "square":     # half the grid on the long tracks: the model is a Python loop
                         continue
+                    for frame in ("world", "ego"):
+                        out.append((name, make, closed, attrs, P, frame, chans[attrs]))
+    # either side of the staging boundary (appended: the cases above keep their place in the tests' random streams)
+    for name, make in (("circle_2048", circle_2048), ("circle_2049", circle_2049)):
+        for closed in (True, False):
+            for attrs in (0, 4):
+                for P in (1, 32):
                     for frame in ("world", "ego"):
                         out.append((name, make, closed, attrs, P, frame, chans[attrs]))
     return out
