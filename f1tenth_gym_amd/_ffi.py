@@ -103,6 +103,18 @@ NBR_DX, NBR_DY, NBR_DIST, NBR_COS_DTH, NBR_SIN_DTH, NBR_V_X, NBR_V_Y, NBR_GAP_S,
 NBR_NCHANNELS, NBR_MAX_K, NBR_MAX_AGENTS = 10, 8, 256
 
 
+class RolloutSpec(C.Structure):
+    """struct f110_rollout"""
+    _fields_ = [("k", C.c_int32), ("horizon", C.c_int32), ("repeat", C.c_int32), ("layout", C.c_int32), ("frame", C.c_int32),
+                ("channels", C.c_int32), ("traj", C.c_int32), ("pad_", C.c_int32), ("margin", C.c_double), ("scale", C.c_double * 10)]
+
+
+(ROLL_END_X, ROLL_END_Y, ROLL_END_COS, ROLL_END_SIN, ROLL_END_V, ROLL_END_YAW_RATE, ROLL_ALIVE, ROLL_MIN_CLEAR, ROLL_PROGRESS,
+ ROLL_END_LAT) = (1 << b for b in range(10))
+ROLL_NCHANNELS, ROLL_SHARED, ROLL_PER_AGENT, ROLL_FRAME_EGO, ROLL_FRAME_MAP = 10, 0, 1, 0, 1
+ROLL_MAX_K, ROLL_MAX_H, ROLL_MAX_REPEAT = 256, 64, 16
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -241,6 +253,8 @@ PROTOTYPES = {
     "f110_track_preview_batch": (C.c_int, [C.c_void_p, C.POINTER(TrackPreviewSpec), C.c_int32, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
     "f110_neighbors_device": (C.c_int, [C.c_void_p, C.POINTER(NeighborsSpec), C.c_void_p, C.c_void_p]),
     "f110_neighbors_batch": (C.c_int, [C.c_void_p, C.POINTER(NeighborsSpec), C.c_int32, C.c_double, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
+    "f110_rollout_device": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f110_rollout_batch": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.c_int32, _dp, _dp, _dp, C.c_int32, C.c_void_p, _dp, C.c_void_p, _dp]),
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
     "f110_obs_encode_device": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p, C.c_void_p]),
     "f110_obs_encode_batch": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), _dp, _dp, _i32p, C.c_int32, C.c_void_p]),

@@ -1183,6 +1183,86 @@ class BatchSim(object):
         res = [out] + ([rw] if raw else []) + ([ix] if indices else [])
         return res[0] if len(res) == 1 else tuple(res)
 
+    # ------------------------------------------------------------------ rollout (f110_rollout_*)
+    def rollout_device(self, spec, d_actions, out=None, traj=None, pinned=None):
+        """roll every agent's K candidates (rollout.Rollout) ahead from its live state: d_actions is a float64 DeviceArray of
+        spec.actions_shape(N) = (steer, speed) per candidate and action.  Returns the summary, a float32 DeviceArray [N][K][D], or
+        with spec.traj the pair (summary, trajectory [N][K][H][4]).  `out` / `traj`: DeviceArrays of those shapes to reuse (None: new
+        ones).  Enqueued on the handle's stream, per env block behind a two-block step (no host wait).  pinned: a pinned_empty
+        float32 array of the summary's shape that also receives it, complete after sync().  'progress' and 'end_lat' need a track
+        on every map slot in use (set_track); tracking need not be enabled."""
+        from .rollout import Rollout
+        ro = Rollout.coerce(spec)
+        shape, tshape, ashape = ro.shape(self.N), ro.traj_shape(self.N), ro.actions_shape(self.N)
+        if not isinstance(d_actions, DeviceArray) or tuple(d_actions.shape) != ashape or d_actions.dtype != np.float64:
+            raise ValueError("d_actions must be a float64 DeviceArray of shape %s" % (ashape,))
+        if out is None:
+            out = DeviceArray(self, shape, np.float32)
+        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
+            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
+        if not ro.traj:
+            if traj is not None:
+                raise ValueError("traj is given, but the rollout does not ask for the trajectory")
+        elif traj is None:
+            traj = DeviceArray(self, tshape, np.float32)
+        elif not isinstance(traj, DeviceArray) or tuple(traj.shape) != tshape or traj.dtype != np.float32:
+            raise ValueError("traj must be a float32 DeviceArray of shape %s" % (tshape,))
+        pp = None
+        if pinned is not None:
+            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
+                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
+            pp = pinned.ctypes.data
+        sp = ro.spec()
+        check(_ffi.lib().f110_rollout_device(self._h, C.byref(sp), d_actions.ptr, out.ptr, traj.ptr if ro.traj else None, pp), self._h)
+        return (out, traj) if ro.traj else out
+
+    def rollout(self, spec, actions):
+        """rollout_device on host candidates `actions` (spec.actions_shape(N)), returned as NumPy: the summary float32 [N][K][D],
+        or with spec.traj the pair (summary, trajectory)"""
+        from .rollout import Rollout
+        ro = Rollout.coerce(spec)
+        a = as_f64(actions)
+        if tuple(a.shape) != ro.actions_shape(self.N):
+            raise ValueError("actions must have shape %s" % (ro.actions_shape(self.N),))
+        with DeviceArray(self, a.shape, np.float64) as d_act:
+            d_act.upload(a)
+            res = self.rollout_device(ro, d_act)
+            res = res if ro.traj else (res,)
+            host = tuple(r.download() for r in res)
+            for r in res:
+                r.free()
+        return host if ro.traj else host[0]
+
+    def rollout_rows(self, spec, start, actions, slot=0, params=None, raw=False):
+        """unit form on host rows: start [m][10] = state[7], the steering FIFO's newest and older entry and its fill count (0, 1, 2),
+        all on map slot `slot`; params [m][18] (None: this handle's row of agent slot 0); actions spec.actions_shape(m) -> the summary
+        float32 [m][K][D]; with spec.traj also the trajectory float32 [m][K][H][4]; with raw also float64 [m][K][10] (every channel
+        before scaling; 'progress' and 'end_lat' 0.0 when the slot has no track) and, with spec.traj, the float64 trajectory"""
+        from .rollout import Rollout
+        ro = Rollout.coerce(spec)
+        st = as_f64(start)
+        if st.ndim != 2 or st.shape[1] != 10:
+            raise ValueError("start must be [m][10] = state[7], FIFO newest, FIFO older, FIFO count")
+        m = st.shape[0]
+        a = as_f64(actions)
+        if tuple(a.shape) != ro.actions_shape(m):
+            raise ValueError("actions must have shape %s" % (ro.actions_shape(m),))
+        pv = None
+        if params is not None:
+            pv = as_f64(params)
+            if tuple(pv.shape) != (m, 18):
+                raise ValueError("params must be [m][18]")
+        out = np.zeros(ro.shape(m), dtype=np.float32)
+        rw = np.zeros((m, ro.k, 10)) if raw else None
+        tr = np.zeros(ro.traj_shape(m), dtype=np.float32) if ro.traj else None
+        trw = np.zeros(ro.traj_shape(m)) if ro.traj and raw else None
+        sp = ro.spec()
+        check(_ffi.lib().f110_rollout_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), dptr(a), m, out.ctypes.data,
+                                            None if rw is None else dptr(rw), None if tr is None else tr.ctypes.data,
+                                            None if trw is None else dptr(trw)), self._h)
+        res = [out] + ([tr] if ro.traj else []) + ([rw] if raw else []) + ([trw] if trw is not None else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ------------------------------------------------------------------ rendering (f110_render_device, DESIGN §6c)
     def render_device(self, agents=None, width=64, height=64, view='ego', m_per_px=0.05, center=(0.0, 0.0), angle=0.0,
                       fwd_offset=0.0, layers=('map', 'cars'), car_size=None, rgb=False, palette=None, out=None):

@@ -208,6 +208,9 @@ struct f110_sim {
     const float *obs_pinned = nullptr;    // f110_obs_encode_device: the page-locked block its last copy went to
     const float *preview_pinned = nullptr;   // f110_track_preview_device: likewise
     const float *neighbors_pinned = nullptr; // f110_neighbors_device: likewise
+    const float *rollout_pinned = nullptr;   // f110_rollout_device: likewise
+    double *d_roll_end = nullptr;            // f110_rollout_device: the candidates' end positions between its two kernels (grows on demand)
+    size_t roll_end_cap = 0;
     // scripted cars (f110_controllers_set): the specs and the per-agent assignment in device memory; gap_specs == 0: disarmed
     GapSpec *d_gap_specs = nullptr;
     int32_t *d_gap_assign = nullptr;
@@ -987,7 +990,7 @@ void f110_destroy(f110_sim *h)
             if (p) (void)hipFree(p);
     }
     {
-        void *tp[] = {h->d_tracks, h->d_track_attrs, h->d_trk, h->d_trk_seg, h->d_trk_cache, h->d_trk_ok};
+        void *tp[] = {h->d_tracks, h->d_track_attrs, h->d_trk, h->d_trk_seg, h->d_trk_cache, h->d_trk_ok, h->d_roll_end};
         for (void *p : tp)
             if (p) (void)hipFree(p);
     }
@@ -2117,13 +2120,14 @@ int f110_host_free(f110_sim *h, void *p)
                     o->trk_pinned = f110_track_host{};
                 }
             }
-            if (inside(o->obs_pinned) || inside(o->preview_pinned) || inside(o->neighbors_pinned)) {   // an encode's, a preview's or a neighbour call's copy (on the env blocks' streams) may still be on its way into the block
+            if (inside(o->obs_pinned) || inside(o->preview_pinned) || inside(o->neighbors_pinned) || inside(o->rollout_pinned)) {   // an encode's, a preview's, a neighbour call's or a rollout's copy (on the env blocks' streams) may still be on its way into the block
                 (void)hipSetDevice(o->cfg.device_id);
                 for (hipStream_t gs : o->gstreams) (void)hipStreamSynchronize(gs);
                 (void)hipStreamSynchronize(o->stream);
                 if (inside(o->obs_pinned)) o->obs_pinned = nullptr;
                 if (inside(o->preview_pinned)) o->preview_pinned = nullptr;
                 if (inside(o->neighbors_pinned)) o->neighbors_pinned = nullptr;
+                if (inside(o->rollout_pinned)) o->rollout_pinned = nullptr;
             }
             if (!o->hb_valid && !o->fused_valid) continue;
             const f110_host_block &b = o->hb_host;
@@ -5016,5 +5020,202 @@ int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t 
                            direct ? nullptr : d_classes, d_rgb, pal);
         HIPCHK(h, hipGetLastError());
     }
+    return F110_OK;
+}
+
+// ---- rollout (f110_rollout_*, include/f110.h) ---------------------------------------------------------------------------------------
+// the spec's refusals; on success the kernel's spec
+static int roll_check_spec(f110_sim *h, const f110_rollout *p, RollSpec &o)
+{
+    if (!p) return fail(h, F110_ERR_INVALID, "rollout: null spec");
+    if (p->k < 1 || p->k > F110_ROLL_MAX_K) return fail(h, F110_ERR_INVALID, "rollout: k = %d is outside 1..%d", p->k, (int)F110_ROLL_MAX_K);
+    if (p->horizon < 1 || p->horizon > F110_ROLL_MAX_H) return fail(h, F110_ERR_INVALID, "rollout: horizon = %d is outside 1..%d", p->horizon, (int)F110_ROLL_MAX_H);
+    if (p->repeat < 1 || p->repeat > F110_ROLL_MAX_REPEAT) return fail(h, F110_ERR_INVALID, "rollout: repeat = %d is outside 1..%d", p->repeat, (int)F110_ROLL_MAX_REPEAT);
+    if (p->layout != F110_ROLL_SHARED && p->layout != F110_ROLL_PER_AGENT) return fail(h, F110_ERR_INVALID, "rollout: unknown layout %d", p->layout);
+    if (p->frame != F110_ROLL_FRAME_EGO && p->frame != F110_ROLL_FRAME_MAP) return fail(h, F110_ERR_INVALID, "rollout: unknown frame %d", p->frame);
+    if (p->channels == 0 || (p->channels & ~((1 << F110_ROLL_NCHANNELS) - 1))) return fail(h, F110_ERR_INVALID, "rollout: channels = 0x%x is empty or has an unknown bit", p->channels);
+    if (p->traj != 0 && p->traj != 1) return fail(h, F110_ERR_INVALID, "rollout: traj = %d must be 0 or 1", p->traj);
+    if (p->margin != p->margin) return fail(h, F110_ERR_INVALID, "rollout: margin is NaN");
+    o = RollSpec{};
+    for (int b = 0; b < F110_ROLL_NCHANNELS; ++b) {
+        o.scale[b] = 1.0;
+        const bool set = (p->channels >> b & 1) != 0;
+        if (set) o.D += 1;
+        if (!set && !(p->traj && b < 4)) continue;
+        if (!(std::isfinite(p->scale[b]) && p->scale[b] > 0.0)) return fail(h, F110_ERR_INVALID, "rollout: scale[%d] must be finite and > 0", b);
+        o.scale[b] = p->scale[b];
+    }
+    o.K = p->k;
+    o.H = p->horizon;
+    o.repeat = p->repeat;
+    o.layout = p->layout;
+    o.frame = p->frame;
+    o.channels = p->channels;
+    o.traj = p->traj;
+    o.margin = p->margin;
+    return F110_OK;
+}
+
+// agents [j.begin, j.begin + j.count): the candidates, then (track set) the two projections behind them on the same stream
+static void roll_launch(const RollJob &j, bool track, hipStream_t st)
+{
+    if (j.count <= 0) return;
+    const size_t lanes = (size_t)j.count * j.sp.K;
+    const dim3 grid = grid1d(lanes, 256), block(256);
+    const bool uni = j.sp.K % 64 == 0;
+    if (j.sp.traj) {
+        if (uni) hipLaunchKernelGGL((k_rollout<true, true>), grid, block, 0, st, j);
+        else hipLaunchKernelGGL((k_rollout<false, true>), grid, block, 0, st, j);
+    } else {
+        if (uni) hipLaunchKernelGGL((k_rollout<true, false>), grid, block, 0, st, j);
+        else hipLaunchKernelGGL((k_rollout<false, false>), grid, block, 0, st, j);
+    }
+    if (track) hipLaunchKernelGGL(k_rollout_track, grid1d(lanes * kTrackLanes, 256), block, 0, st, j);
+}
+
+int f110_rollout_device(f110_sim *h, const f110_rollout *spec, const double *d_actions, float *d_out, float *d_traj, float *h_pinned)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    RollJob j{};
+    TRY(roll_check_spec(h, spec, j.sp));
+    if (!d_actions || !d_out) return fail(h, F110_ERR_INVALID, "rollout: d_actions or d_out is null");
+    if (j.sp.traj && (!d_traj || reinterpret_cast<uintptr_t>(d_traj) % 16 != 0)) return fail(h, F110_ERR_INVALID, "rollout: traj = 1, but d_traj is null or not 16-byte aligned");
+    const size_t N = (size_t)h->N, per_agent = (size_t)j.sp.K * j.sp.D;
+    if (N * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "rollout: %zu agents x %d candidates do not fit 31 bits", N, j.sp.K);
+    if (h_pinned) {
+        std::lock_guard<std::mutex> lk(g_registry_mu);
+        const char *p = reinterpret_cast<const char *>(h_pinned);
+        auto it = g_host_blocks.upper_bound(p);
+        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
+        if (it != g_host_blocks.begin()) {
+            --it;
+            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
+        }
+        if (!inside) return fail(h, F110_ERR_INVALID, "rollout: h_pinned is not [N][K][D] floats of f110_host_alloc memory");
+    }
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    const bool track = (j.sp.channels & kRollTrackBits) != 0;
+    if (track) {
+        if (!h->multi_map) {
+            if (!track_has(h, 0)) return fail(h, F110_ERR_STATE, "rollout: PROGRESS or END_LAT is requested, but map slot 0 has no track (f110_track_set)");
+        } else {
+            for (int32_t m : h->env_map_host)
+                if (!track_has(h, m)) return fail(h, F110_ERR_STATE, "rollout: PROGRESS or END_LAT is requested, but map slot %d has no track (f110_track_set)", m);
+        }
+        if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size() || h->roll_end_cap < 2 * N * j.sp.K) {
+            ENTER(h);
+            TRY(track_upload(h));
+            TRY(render_grow(h, &h->d_roll_end, &h->roll_end_cap, 2 * N * j.sp.K));
+        }
+    }
+    EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (a candidate reads its own agent's rows and writes its own)
+    TRY(env_blocks_follow(h, w));
+    j.maps = h->multi_map ? h->d_maps_full : cold_consts(h);
+    if (!j.maps) return fail(h, F110_ERR_HIP, "rollout: constant upload failed");
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.tracks = track ? h->d_tracks : nullptr;
+    j.unit_slot = -1;
+    j.A = h->cfg.num_agents;
+    j.N = h->N;
+    j.params_per_agent = h->dev.params_per_agent;
+    j.state = h->dev.state;
+    j.steer_buf = h->dev.steer_buf;
+    j.buf_cnt = h->dev.buf_cnt;
+    j.params = h->dev.params;
+    j.integrator = h->dev.integrator;
+    j.time_step = h->dev.time_step;
+    j.lidar_dist = h->dev.lidar_dist;
+    j.actions = d_actions;
+    j.out = d_out;
+    j.traj = j.sp.traj ? d_traj : nullptr;
+    j.end_xy = track ? h->d_roll_end : nullptr;
+    for (const EnvBlock &b : w) {
+        j.begin = b.e0 * j.A;
+        j.count = b.count * j.A;
+        roll_launch(j, track, b.stream);
+        if (h_pinned)
+            HIPCHK(h, hipMemcpyAsync(h_pinned + (size_t)j.begin * per_agent, d_out + (size_t)j.begin * per_agent, (size_t)j.count * per_agent * sizeof(float),
+                                     hipMemcpyDeviceToHost, b.stream));
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h_pinned) h->rollout_pinned = h_pinned;
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start, const double *h_params, const double *h_actions,
+                       int32_t m, float *h_out, double *h_raw, float *h_traj, double *h_traj_raw)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    RollJob j{};
+    TRY(roll_check_spec(h, spec, j.sp));
+    if (m < 0 || (m > 0 && (!h_start || !h_actions || !h_out))) return fail(h, F110_ERR_INVALID, "rollout: bad argument");
+    if (j.sp.traj && m > 0 && !h_traj) return fail(h, F110_ERR_INVALID, "rollout: traj = 1, but h_traj is null");
+    if ((size_t)m * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "rollout: %d rows x %d candidates do not fit 31 bits", m, j.sp.K);
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "rollout: map slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    const bool want_track = (j.sp.channels & kRollTrackBits) != 0;
+    if (want_track && !track_has(h, slot)) return fail(h, F110_ERR_STATE, "rollout: PROGRESS or END_LAT is requested, but map slot %d has no track (f110_track_set)", slot);
+    const bool track = want_track || (h_raw && track_has(h, slot));
+    if (m == 0) return F110_OK;
+    ENTER(h);
+    if (track) TRY(track_upload(h));
+    // the rows as the live columns are laid out: state [7][m], the FIFO [2][m], its fill [m]
+    const size_t M = (size_t)m, cands = M * j.sp.K, steps = cands * j.sp.H;
+    std::vector<double> cols(9 * M);
+    std::vector<int32_t> cnt(M);
+    for (size_t r = 0; r < M; ++r) {
+        for (int c = 0; c < 9; ++c) cols[(size_t)c * M + r] = h_start[10 * r + c];
+        const double f = h_start[10 * r + 9];
+        if (!(f == 0.0 || f == 1.0 || f == 2.0)) return fail(h, F110_ERR_INVALID, "rollout: row %zu has a FIFO fill count of %g, not 0, 1 or 2", r, f);
+        cnt[r] = (int32_t)f;
+    }
+    ScanConst kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
+    Scratch sc(h);
+    double *dcols = nullptr, *dpar = nullptr, *dact = nullptr, *draw = nullptr, *dtraw = nullptr, *dend = nullptr;
+    int32_t *dcnt = nullptr;
+    ScanConst *dk = nullptr;
+    float *dout = nullptr, *dtraj = nullptr;
+    TRY(sc.up(cols.data(), cols.size(), &dcols));
+    TRY(sc.up(cnt.data(), cnt.size(), &dcnt));
+    TRY(sc.up(&kc, 1, &dk));
+    if (h_params) TRY(sc.up(h_params, M * NPARAMS, &dpar));
+    TRY(sc.up(h_actions, (j.sp.layout == F110_ROLL_PER_AGENT ? steps : (size_t)j.sp.K * j.sp.H) * 2, &dact));
+    TRY(sc.up<float>(nullptr, cands * j.sp.D, &dout));
+    if (h_raw) {
+        TRY(sc.up<double>(nullptr, cands * F110_ROLL_NCHANNELS, &draw));
+        HIPCHK(h, hipMemsetAsync(draw, 0, cands * F110_ROLL_NCHANNELS * sizeof(double), h->stream));
+    }
+    if (j.sp.traj) TRY(sc.up<float>(nullptr, steps * 4, &dtraj));
+    if (j.sp.traj && h_traj_raw) TRY(sc.up<double>(nullptr, steps * 4, &dtraw));
+    if (track) TRY(sc.up<double>(nullptr, cands * 2, &dend));
+    j.maps = dk;
+    j.tracks = track ? h->d_tracks : nullptr;
+    j.unit_slot = slot;
+    j.A = 1;
+    j.begin = 0;
+    j.count = m;
+    j.N = m;
+    j.params_per_agent = h_params ? 1 : 0;
+    j.state = dcols;
+    j.steer_buf = dcols + 7 * M;
+    j.buf_cnt = dcnt;
+    j.params = h_params ? dpar : h->d_params;
+    j.integrator = h->dev.integrator;
+    j.time_step = h->dev.time_step;
+    j.lidar_dist = h->dev.lidar_dist;
+    j.actions = dact;
+    j.out = dout;
+    j.raw = draw;
+    j.traj = dtraj;
+    j.traj_raw = dtraw;
+    j.end_xy = dend;
+    roll_launch(j, track, h->stream);
+    HIPCHK(h, hipGetLastError());
+    TRY(sc.down(h_out, dout, cands * j.sp.D));
+    if (h_raw) TRY(sc.down(h_raw, draw, cands * F110_ROLL_NCHANNELS));
+    if (dtraj) TRY(sc.down(h_traj, dtraj, steps * 4));
+    if (dtraw) TRY(sc.down(h_traj_raw, dtraw, steps * 4));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }

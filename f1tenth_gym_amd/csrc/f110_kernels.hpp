@@ -4426,3 +4426,195 @@ __global__ void __launch_bounds__(256) k_neighbors(NbrJob j)
         __syncthreads();
     }
 }
+
+// ---- rollout (f110_rollout_*; include/f110.h states the rule, f110_math.hpp roll_* the arithmetic) -------------------------------
+// k_rollout: one lane per (agent, candidate), candidate-minor, so an agent's K candidates are consecutive lanes; 256-lane workgroups
+// over the flat index.  A lane is one float64 dependent chain of H * repeat * ~1900 instructions with 16 bytes of action read per
+// ~1900 * repeat of them: what matters is waves per SIMD (registers), not memory.
+//  * the start state, the FIFO and the parameter row are loaded once per agent.  UNI (K a multiple of 64): every wave lies inside one
+//    agent, the agent index goes through readfirstlane and those loads are scalar; the parameters then stay in SGPRs.
+//  * TRAJ: a lane's trajectory row is H * 16 bytes, so the lanes of a store would be H * 16 bytes apart.  Each lane leaves its pose
+//    (one float4) in an LDS stage instead, kRollChunk actions deep with a row pitch of kRollChunk + 1 float4 (an even pitch would
+//    put every lane's write on the same banks); after every kRollChunk-th action (and the last) the workgroup stores the stage,
+//    consecutive lanes consecutive float4 of a row: 128 contiguous bytes per row and flush, the whole region contiguous when
+//    H <= kRollChunk.  The loops of roll_candidate have the same trip counts in every lane (a dead candidate idles through them), so
+//    the barriers of the flush are reached by all.
+//  * idle lanes (past count * K) shadow the last live one through every barrier and store nothing.
+//  * the summary row is D <= 10 floats per lane, rows consecutive: the lanes of one store are D * 4 bytes apart and the workgroup's
+//    region contiguous; once per candidate.
+// k_rollout_track (only when PROGRESS or END_LAT is asked for): 16 lanes per candidate project the agent's start position and then
+// the candidate's end position (k_rollout left it in end_xy) with k_track_project's search — every 16th segment per lane, the same
+// pruning rule (the end's seed is the start's winner), a lexicographic (distance, index) minimum across the group — and lane 0
+// writes the two values into the candidate's row.
+constexpr int kRollChunk = 8;
+constexpr int kRollPitch = kRollChunk + 1;
+
+// agents [begin, begin + count) of columns with N entries each (the live ones, or the unit form's uploaded rows).  The map of agent
+// n is maps[env_map ? env_map[n / A] : 0]; its track tracks[unit_slot >= 0 ? unit_slot : that slot].
+struct RollJob {
+    const ScanConst *maps;
+    const int32_t *env_map;
+    const TrackDesc *tracks;
+    int32_t unit_slot, A;
+    int32_t begin, count, N, params_per_agent;
+    const double *state;      // [7][N]
+    const double *steer_buf;  // [2][N]
+    const int32_t *buf_cnt;   // [N]
+    const double *params;     // [A][18] or [N][18] (params_per_agent)
+    int32_t integrator, pad_;
+    double time_step, lidar_dist;
+    const double *actions;    // [K][H][2] or [N][K][H][2]
+    float *out;               // [N][K][D]
+    double *raw;              // [N][K][10] or nullptr
+    float *traj;              // [N][K][H][4] or nullptr
+    double *traj_raw;         // [N][K][H][4] or nullptr
+    double *end_xy;           // [N][K][2] or nullptr: the end positions for k_rollout_track
+    RollSpec sp;
+};
+
+// roll_candidate's emit on the device: the pose of action h into the lane's row of the stage, and the flush
+struct RollEmitLds {
+    static constexpr bool kOn = true;
+    float4 *stage;       // the workgroup's stage [256][kRollPitch]
+    float4 *traj;        // the workgroup's first row of the output, or nullptr
+    double *raw_row;     // this lane's row of traj_raw, or nullptr
+    int rows, H;         // live lanes of this workgroup
+    double sx, sy, sc, ss;
+    __device__ __forceinline__ void operator()(int h, const double *v) const
+    {
+        if (raw_row) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) raw_row[4 * h + q] = v[q];
+        }
+        if (!traj) return;
+        const int tid = (int)threadIdx.x, slot = h % kRollChunk;
+        stage[tid * kRollPitch + slot] = make_float4(roll_scaled(v[0], sx), roll_scaled(v[1], sy), roll_scaled(v[2], sc), roll_scaled(v[3], ss));
+        if (slot != kRollChunk - 1 && h != H - 1) return;
+        __syncthreads();
+        const int cn = slot + 1, h0 = h - slot;
+        for (int q = tid; q < rows * cn; q += 256) {
+            const int row = q / cn, a = q - row * cn;
+            traj[(size_t)row * H + h0 + a] = stage[row * kRollPitch + a];
+        }
+        __syncthreads();
+    }
+};
+
+template <bool UNI, bool TRAJ>
+__global__ void __launch_bounds__(256) k_rollout(RollJob j)
+{
+    __shared__ float4 s_stage[TRAJ ? 256 * kRollPitch : 1];
+    const int K = j.sp.K, H = j.sp.H;
+    const long long total = (long long)j.count * K;
+    const long long g0 = (long long)blockIdx.x * 256, g_lane = g0 + (int)threadIdx.x;
+    const bool live = g_lane < total;
+    const long long g = live ? g_lane : total - 1;
+    int a = (int)(g / K);
+    const int kk = (int)(g - (long long)a * K);
+    if (UNI) a = __builtin_amdgcn_readfirstlane(a);
+    const int n = j.begin + a;
+    const size_t N = (size_t)j.N;
+    const size_t G = (size_t)j.begin * K + (size_t)g;   // the candidate's row in every output
+    const VehicleParams vp = load_params(j.params + (size_t)(j.params_per_agent ? n : n % j.A) * NPARAMS);
+    RollCar car;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) car.st[c] = j.state[(size_t)c * N + n];
+    car.b0 = j.steer_buf[n];
+    car.b1 = j.steer_buf[N + n];
+    car.cnt = j.buf_cnt[n];
+    const ScanConst &k = j.maps[j.env_map ? j.env_map[n / j.A] : 0];
+    const double *act = j.actions + (j.sp.layout == ROLL_PER_AGENT ? G : (size_t)kk) * H * 2;
+    int alive;
+    double min_clear;
+    RollFrame fr;
+    if constexpr (TRAJ) {
+        fr = roll_frame(j.sp.frame, car.st[0], car.st[1], car.st[4]);
+        RollEmitLds emit;
+        emit.stage = s_stage;
+        emit.traj = j.traj ? reinterpret_cast<float4 *>(j.traj) + ((size_t)j.begin * K + (size_t)g0) * H : nullptr;
+        emit.raw_row = j.traj_raw && live ? j.traj_raw + G * H * 4 : nullptr;
+        emit.rows = (int)(total - g0 < 256 ? total - g0 : 256);
+        emit.H = H;
+        emit.sx = j.sp.scale[ROLL_END_X];
+        emit.sy = j.sp.scale[ROLL_END_Y];
+        emit.sc = j.sp.scale[ROLL_END_COS];
+        emit.ss = j.sp.scale[ROLL_END_SIN];
+        roll_candidate(j.sp, k, vp, j.time_step, j.integrator, j.lidar_dist, car, act, fr, alive, min_clear, emit);
+    } else {
+        roll_candidate(j.sp, k, vp, j.time_step, j.integrator, j.lidar_dist, car, act, fr, alive, min_clear, RollEmitNone());
+        // the frame only now, from the start pose read again: four doubles fewer are live across the loop
+        fr = roll_frame(j.sp.frame, j.state[n], j.state[N + n], j.state[4 * N + n]);
+    }
+    if (!live) return;
+    double v[ROLL_NCHANNELS];
+    const int32_t all = (1 << ROLL_NCHANNELS) - 1;
+    roll_values(fr, car, alive, min_clear, j.raw ? all : j.sp.channels, v);
+    roll_store(j.sp, v, all & ~kRollTrackBits, j.out + G * j.sp.D, j.raw ? j.raw + G * ROLL_NCHANNELS : nullptr);
+    if (j.end_xy) {
+        j.end_xy[2 * G] = car.st[0];
+        j.end_xy[2 * G + 1] = car.st[1];
+    }
+}
+
+// k_track_project's search for one pose by the 16 lanes of a group: lane `sub` takes every 16th segment and keeps its first minimum;
+// a segment is skipped when a lower bound of its distance exceeds the smaller of the seed segment's distance (hint < 0: no seed)
+// and the lane's running minimum by more than kTrackPruneMargin, so it can neither win nor tie; every lane returns the group's
+// winner
+__device__ __forceinline__ void roll_search16(const TrackDesc &td, double px, double py, int hint, int sub, int &best, double &s, double &lat)
+{
+    const double *src = td.cols;
+    const size_t cs = (size_t)td.nseg;
+    double dist = INFINITY, tb = 0.0, seed = INFINITY;
+    best = 0x7fffffff;
+    if (hint >= 0) {
+        double t;
+        seed = track_seg_dist(src, cs, hint < td.nseg ? hint : td.nseg - 1, px, py, t);
+    }
+    for (int k = sub; k < td.nseg; k += kTrackLanes) {
+        const double ax = src[k], ay = src[cs + k], dx = src[2 * cs + k], dy = src[3 * cs + k];
+        const double mx = px - (ax + 0.5 * dx), my = py - (ay + 0.5 * dy);
+        const double reach = (seed < dist ? seed : dist) + 0.5 * src[5 * cs + k] + kTrackPruneMargin;
+        if (mx * mx + my * my > reach * reach) continue;
+        double t;
+        const double d = track_seg_dist(src, cs, k, px, py, t);
+        if (d < dist) {
+            dist = d;
+            tb = t;
+            best = k;
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < kTrackLanes; m <<= 1) {
+        const double od = __shfl_xor(dist, m, kTrackLanes), ot = __shfl_xor(tb, m, kTrackLanes);
+        const int ob = __shfl_xor(best, m, kTrackLanes);
+        if (od < dist || (od == dist && ob < best)) {
+            dist = od;
+            tb = ot;
+            best = ob;
+        }
+    }
+    if (best == 0x7fffffff) {   // no distance below +inf (a NaN pose): np.argmin -> 0, with segment 0's own t and distance
+        best = 0;
+        dist = track_seg_dist(src, cs, 0, px, py, tb);
+    }
+    track_winner(src, cs, best, tb, dist, px, py, s, lat);
+}
+
+__global__ void __launch_bounds__(256) k_rollout_track(RollJob j)
+{
+    const int K = j.sp.K;
+    const long long total = (long long)j.count * K;
+    const long long gid = ((long long)blockIdx.x * 256 + (int)threadIdx.x) / kTrackLanes;
+    const int sub = (int)threadIdx.x & (kTrackLanes - 1);
+    const bool live = gid < total;
+    const long long g = live ? gid : total - 1;   // idle groups shadow the last candidate: every lane takes part in every shuffle
+    const int n = j.begin + (int)(g / K);
+    const size_t G = (size_t)j.begin * K + (size_t)g;
+    const TrackDesc td = j.tracks[j.unit_slot >= 0 ? j.unit_slot : (j.env_map ? j.env_map[n / j.A] : 0)];
+    int seg0, seg1;
+    double s0, lat0, s1, lat1;
+    roll_search16(td, j.state[n], j.state[(size_t)j.N + n], -1, sub, seg0, s0, lat0);
+    roll_search16(td, j.end_xy[2 * G], j.end_xy[2 * G + 1], seg0, sub, seg1, s1, lat1);
+    if (sub != 0 || !live) return;
+    roll_store_track(j.sp, roll_progress(s0, s1, td.closed, td.L), lat1, j.out + G * j.sp.D, j.raw ? j.raw + G * ROLL_NCHANNELS : nullptr);
+}

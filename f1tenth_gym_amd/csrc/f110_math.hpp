@@ -1648,4 +1648,186 @@ F110_HD void nbr_env(const NbrSpec &sp, const double *rows, int A, double L, Nbr
     }
 }
 
+// ------------------------------------------------------------------ rollout (include/f110.h, f110_rollout)
+// No reference counterpart of its own: a candidate's motion is advance_vehicle (RaceCar.update_pose) called H * repeat times and its
+// clearance sample_distance (xy_2_rc + the table) at the reference point, both called as they are.  What is added here is the
+// bookkeeping around them (alive, the minimum, the frame, the scaling) and the projection of two poses on the track.
+enum { ROLL_END_X = 0, ROLL_END_Y, ROLL_END_COS, ROLL_END_SIN, ROLL_END_V, ROLL_END_YAW_RATE, ROLL_ALIVE, ROLL_MIN_CLEAR, ROLL_PROGRESS,
+       ROLL_END_LAT, ROLL_NCHANNELS };
+enum { ROLL_SHARED = 0, ROLL_PER_AGENT = 1 };
+enum { ROLL_FRAME_EGO = 0, ROLL_FRAME_WORLD = 1 };
+enum { ROLL_MAX_K = 256, ROLL_MAX_H = 64, ROLL_MAX_REPEAT = 16 };
+constexpr int32_t kRollTrackBits = 1 << ROLL_PROGRESS | 1 << ROLL_END_LAT;
+
+struct RollSpec {
+    int32_t K, H, repeat;       // candidates per agent; actions per candidate; sim steps an action is held
+    int32_t layout, frame;      // ROLL_SHARED / ROLL_PER_AGENT; ROLL_FRAME_*
+    int32_t channels, traj, D;  // channel bits; 1: the trajectory is written too; popcount(channels)
+    double margin;
+    double scale[ROLL_NCHANNELS];
+};
+
+// what a candidate starts from and carries: the agent's state, the steering FIFO (b0 the newest entry) and its fill
+struct RollCar {
+    double st[7], b0, b1;
+    int cnt;
+};
+
+// the frame the poses are reported in: the start pose's (one cos_sin per agent) or the map's
+struct RollFrame {
+    double x0, y0, c0, s0;
+    int ego;
+};
+
+F110_HD RollFrame roll_frame(int frame, double x, double y, double theta)
+{
+    RollFrame f{x, y, 1.0, 0.0, frame == ROLL_FRAME_EGO};
+    if (f.ego) cos_sin(theta, f.c0, f.s0);
+    return f;
+}
+
+// (x, y, cos, sin) of a pose in the frame; with_cs false leaves the heading's two values 0.0 (and its cos_sin out)
+F110_HD void roll_pose(const RollFrame &f, double x, double y, double theta, bool with_cs, double *v)
+{
+    double c = 0.0, s = 0.0;
+    if (with_cs) cos_sin(theta, c, s);
+    if (!f.ego) {
+        v[0] = x;
+        v[1] = y;
+        v[2] = c;
+        v[3] = s;
+        return;
+    }
+    const double rx = x - f.x0, ry = y - f.y0;
+    v[0] = f.c0 * rx + f.s0 * ry;
+    v[1] = f.c0 * ry - f.s0 * rx;
+    v[2] = with_cs ? c * f.c0 + s * f.s0 : 0.0;
+    v[3] = with_cs ? s * f.c0 - c * f.s0 : 0.0;
+}
+
+// one output element: a float64 divide, then the conversion (round to nearest even)
+F110_HD float roll_scaled(double v, double scale) { return (float)(v / scale); }
+
+// One candidate: H actions (steer, speed) at act[2 * h], each held `repeat` sim steps.  A step integrates, samples the clearance at
+// the reference point and keeps the minimum; the first sample that is not above the margin (or a NaN position, which reads
+// oob_value as every position outside the table does) kills the candidate: its state stays as that step left it.  The two loops are
+// not unrolled: advance_vehicle is ~1900 dependent instructions and appears once.  With Emit::kOn, emit(h, v) receives the pose
+// after action h's last repeat in the frame `fr` (read only then); every lane of a workgroup reaches every emit (a dead candidate
+// repeats its pose).
+struct RollEmitNone {
+    static constexpr bool kOn = false;
+    F110_HD void operator()(int, const double *) const {}
+};
+
+template <class Emit>
+F110_HD void roll_candidate(const RollSpec &sp, const ScanConst &k, const VehicleParams &vp, double dt, int integrator, double lidar_dist,
+                            RollCar &car, const double *act, const RollFrame &fr, int &alive, double &min_clear, const Emit &emit)
+{
+    bool live = true;
+    alive = 0;
+    min_clear = INFINITY;
+#pragma unroll 1
+    for (int h = 0; h < sp.H; ++h) {
+        const double steer = act[2 * h], speed = act[2 * h + 1];
+#pragma unroll 1
+        for (int r = 0; r < sp.repeat; ++r) {
+            if (!live) continue;
+            double scan_pose[3];
+            advance_vehicle(car.st, car.b0, car.b1, car.cnt, steer, speed, vp, dt, integrator, lidar_dist, scan_pose);
+            int row, col;
+            const double d = sample_distance<LAYOUT_ROWMAJOR, false, false>(k, nullptr, car.st[0], car.st[1], row, col);
+            if (!(d >= min_clear)) min_clear = d;
+            live = d > sp.margin && car.st[0] == car.st[0] && car.st[1] == car.st[1];
+            alive += live ? 1 : 0;
+        }
+        if (Emit::kOn) {
+            double v[4];
+            roll_pose(fr, car.st[0], car.st[1], car.st[4], true, v);
+            emit(h, v);
+        }
+    }
+}
+
+// the channel values of a finished candidate before scaling; PROGRESS and END_LAT are the track pass's (0.0 here).  Only the bits
+// of `mask` decide whether the end heading's cos_sin is taken.
+F110_HD void roll_values(const RollFrame &fr, const RollCar &car, int alive, double min_clear, int32_t mask, double *v)
+{
+    roll_pose(fr, car.st[0], car.st[1], car.st[4], (mask & (1 << ROLL_END_COS | 1 << ROLL_END_SIN)) != 0, v);
+    v[ROLL_END_V] = car.st[3];
+    v[ROLL_END_YAW_RATE] = car.st[5];
+    v[ROLL_ALIVE] = (double)alive;
+    v[ROLL_MIN_CLEAR] = min_clear;
+    v[ROLL_PROGRESS] = 0.0;
+    v[ROLL_END_LAT] = 0.0;
+}
+
+// a candidate's row of the summary (and of the raw values): the bits of `which` are written, the other requested ones skipped
+F110_HD void roll_store(const RollSpec &sp, const double *v, int32_t which, float *o, double *raw)
+{
+#pragma unroll
+    for (int bit = 0; bit < ROLL_NCHANNELS; ++bit) {
+        const bool mine = (which >> bit & 1) != 0;
+        if (raw && mine) raw[bit] = v[bit];
+        if (sp.channels >> bit & 1) {
+            if (mine) *o = roll_scaled(v[bit], sp.scale[bit]);
+            ++o;
+        }
+    }
+}
+
+// nearest_point_on_trajectory's arithmetic for segment k of the track columns [7][.] (ax, ay, dx, dy, l2, len, cum; `cs` apart):
+// the clipped parameter and the distance, as k_track_project computes them
+F110_HD double track_seg_dist(const double *cols, size_t cs, int k, double px, double py, double &t)
+{
+    const double ax = cols[k], ay = cols[cs + k], dx = cols[2 * cs + k], dy = cols[3 * cs + k], l2 = cols[4 * cs + k];
+    t = ((px - ax) * dx + (py - ay) * dy) / l2;
+    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    const double rx = px - (ax + t * dx), ry = py - (ay + t * dy);
+    return sqrt(rx * rx + ry * ry);
+}
+
+// arc length and signed lateral offset (left of the segment's direction is positive) of the winner (best, t, dist)
+F110_HD void track_winner(const double *cols, size_t cs, int best, double t, double dist, double px, double py, double &s, double &lat)
+{
+    const double ax = cols[best], ay = cols[cs + best], dx = cols[2 * cs + best], dy = cols[3 * cs + best];
+    s = cols[6 * cs + best] + t * cols[5 * cs + best];
+    const double rx = px - (ax + t * dx), ry = py - (ay + t * dy);
+    const double cross = dx * ry - dy * rx;
+    lat = cross < 0.0 ? -dist : dist;
+}
+
+// the projection serially (the kernel gives a pose 16 lanes; this is what the unit harness runs): the first minimum over every
+// segment; when no distance is below +inf (a NaN pose) segment 0 with its own t and distance, as np.argmin returns it
+F110_HD void roll_project(const double *cols, int nseg, double px, double py, double &s, double &lat)
+{
+    double dist = INFINITY, tb = 0.0;
+    int best = 0x7fffffff;
+    for (int k = 0; k < nseg; ++k) {
+        double t;
+        const double d = track_seg_dist(cols, (size_t)nseg, k, px, py, t);
+        if (d < dist) {
+            dist = d;
+            tb = t;
+            best = k;
+        }
+    }
+    if (best == 0x7fffffff) {
+        best = 0;
+        dist = track_seg_dist(cols, (size_t)nseg, 0, px, py, tb);
+    }
+    track_winner(cols, (size_t)nseg, best, tb, dist, px, py, s, lat);
+}
+
+// s(end) - s(start), wrapped once into (-L/2, L/2] on a closed track
+F110_HD double roll_progress(double s_start, double s_end, int closed, double L) { return nbr_gap(s_start, s_end, closed ? L : 0.0); }
+
+// the track pass's two values into a candidate's row
+F110_HD void roll_store_track(const RollSpec &sp, double progress, double lat, float *o, double *raw)
+{
+    double v[ROLL_NCHANNELS] = {};
+    v[ROLL_PROGRESS] = progress;
+    v[ROLL_END_LAT] = lat;
+    roll_store(sp, v, kRollTrackBits, o, raw);
+}
+
 }  // namespace f110

@@ -883,6 +883,82 @@ int f110_neighbors_device(f110_sim *h, const f110_neighbors *spec, float *d_out 
 int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, double track_L, const double *h_in /* [m][5] x, y, theta, v, s */,
                          int32_t m, float *h_out /* [m][K][D] */, double *h_raw /* [m][K][10] or NULL */, int32_t *h_idx /* [m][K] or NULL */);
 
+/* ---- rollout: K candidate action sequences per agent rolled ahead from the agent's live state, against the map (no reference
+ * counterpart: what MPPI, motion-primitive and lattice planners and safety shields ask K times per agent per step — "if I apply
+ * this action sequence, where does the car end up, and does it leave the track?") ----
+ * It runs only when called, keeps no state in the handle, changes no simulator state and no blob format; no step launches it.
+ * Everything is float64 without contraction.
+ * Candidates.  A candidate is H actions (steer, speed), float64 exactly as the action buffer, each held for `repeat` sim steps.
+ * layout SHARED: d_actions is [K][H][2], one library for all agents; PER_AGENT: [N][K][H][2].
+ * Start.  Candidate k of agent n starts from the agent's LIVE columns: state[7], both entries of the steering FIFO and its fill
+ * count — what the next step would integrate from.
+ * One sim step is
+ *   1. one RaceCar.update_pose without the scan (the step's own integration: the two-step steering delay, the PID, the single-track
+ *      model with its low-speed branch, RK4 or Euler) with the handle's time_step, integrator and lidar_dist and the agent's own
+ *      parameter row (per agent slot, or f110_set_params_batch's);
+ *   2. one clearance sample d = dt[xy_2_rc(x, y)] on the row-major distance table of the env's map slot at the reference point
+ *      state[0..1] (NOT at the lidar); outside the table it is the table's last cell, as the scan sees it.
+ * A candidate is alive while d > margin, written so that a NaN d dies; a NaN position dies too (it reads the out-of-table value).
+ * The first step whose sample fails kills the candidate: its state stays as that step left it, and no further steps or samples
+ * are taken.  This is FREE FLIGHT AGAINST THE MAP: other cars, the iTTC check and the zeroing of the velocity on a collision are
+ * not modelled.  Until the simulator raises a collision flag the rollout is the simulator's own motion, bit for bit.
+ * Frame.  MAP, or EGO: the agent's pose at the start, with c0 = cos theta0, s0 = sin theta0 taken once per agent.  A pose
+ * (x, y, theta) with c = cos theta, s = sin theta reads in the MAP frame (x, y, c, s) and in the EGO frame, with rx = x - x0,
+ * ry = y - y0,  (c0 * rx + s0 * ry,  c0 * ry - s0 * rx,  c * c0 + s * s0,  s * c0 - c * s0).
+ * Channels, by bit number (raw float64 values per candidate):
+ *   0 END_X, 1 END_Y, 2 END_COS, 3 END_SIN   the end pose in the frame
+ *   4 END_V         state[3] at the end             5 END_YAW_RATE  state[5] at the end
+ *   6 ALIVE         sim steps completed with d > margin, 0 .. H * repeat
+ *   7 MIN_CLEAR     the minimum over the samples taken, the killing one included (m = +inf; per sample: if (!(d >= m)) m = d)
+ *   8 PROGRESS      s(end) - s(start): both positions are projected by this call with the track projection's first-minimum search
+ *                   (f110_track_*), the s column is not read; on a closed track of length L wrapped once:
+ *                   if (g > 0.5 * L) g = g - L; else if (g <= -0.5 * L) g = g + L
+ *   9 END_LAT       the signed lateral offset of the end position, the track projection's rule (left of the segment positive)
+ * PROGRESS and END_LAT need a track (f110_track_set) on every map slot in use; tracking need not be enabled.
+ * Output.  d_out[n][k][.] holds the channels of the set bits in ascending bit order, each (float)(value / scale[bit]): a float64
+ * divide, then the conversion, rounding to nearest even.  With traj = 1, d_traj[n][k][h][0..3] is the pose (x, y, cos, sin) after
+ * action h's last repeat, in the same frame, divided by the scales of END_X, END_Y, END_COS, END_SIN (read whether or not those
+ * bits are set); a dead candidate repeats its frozen pose.
+ * Refused with F110_ERR_INVALID, nothing launched or written: k outside 1..256, horizon outside 1..64, repeat outside 1..16 (so
+ * also k * horizon * repeat == 0), an unknown layout or frame, channels 0 or with an unknown bit, traj other than 0 or 1, a scale
+ * of a set bit (with traj: of bits 0..3 too) that is not finite and > 0, a NaN margin, a null d_actions or d_out, traj = 1 with a
+ * null d_traj, an h_pinned that is not [N][K][D] floats of f110_host_alloc memory.
+ * Refused with F110_ERR_STATE: no map, PROGRESS or END_LAT while a map slot in use has no track.
+ * Not offered: float32 action input, footprint-corner clearance, opponents, a built-in cost or argmax, feeding the result into
+ * the observation encoder, a keyword on the env layers (a rollout is a function of the caller's candidates, not an observation). */
+enum { F110_ROLL_END_X = 1, F110_ROLL_END_Y = 2, F110_ROLL_END_COS = 4, F110_ROLL_END_SIN = 8, F110_ROLL_END_V = 16,
+       F110_ROLL_END_YAW_RATE = 32, F110_ROLL_ALIVE = 64, F110_ROLL_MIN_CLEAR = 128, F110_ROLL_PROGRESS = 256, F110_ROLL_END_LAT = 512,
+       F110_ROLL_NCHANNELS = 10 };
+enum { F110_ROLL_SHARED = 0, F110_ROLL_PER_AGENT = 1 };
+enum { F110_ROLL_FRAME_EGO = 0, F110_ROLL_FRAME_MAP = 1 };
+enum { F110_ROLL_MAX_K = 256, F110_ROLL_MAX_H = 64, F110_ROLL_MAX_REPEAT = 16 };
+typedef struct f110_rollout {
+    int32_t k;          /* K, 1..256 candidates per agent */
+    int32_t horizon;    /* H, 1..64 actions per candidate */
+    int32_t repeat;     /* 1..16 sim steps each action is held */
+    int32_t layout;     /* F110_ROLL_SHARED / F110_ROLL_PER_AGENT */
+    int32_t frame;      /* F110_ROLL_FRAME_* */
+    int32_t channels;   /* F110_ROLL_* bits; D = popcount */
+    int32_t traj;       /* 0, or 1: the trajectory output is written too */
+    int32_t pad_;       /* alignment; ignored */
+    double margin;      /* metres; not NaN (-inf: nothing dies of its clearance) */
+    double scale[F110_ROLL_NCHANNELS];   /* by bit number; entries of clear bits are ignored (see traj) */
+} f110_rollout;
+/* device form: d_actions float64 in device memory in the spec's layout, d_out [N][K][D] and d_traj [N][K][H][4] (NULL when
+ * traj = 0) float32 in device memory.  Asynchronous on the handle's stream; right behind a two-block step it runs per env block on
+ * the block's own stream (as f110_neighbors_device does).  h_pinned (or NULL): f110_host_alloc memory of d_out's shape that
+ * receives a copy behind the kernels, complete after f110_sync. */
+int f110_rollout_device(f110_sim *h, const f110_rollout *spec, const double *d_actions, float *d_out /* [N][K][D] */,
+                        float *d_traj /* [N][K][H][4] or NULL */, float *h_pinned);
+/* unit form on host arrays, the same kernels on uploaded rows: h_start [m][10] = state[7], the FIFO's newest and older entry, its
+ * fill count (0, 1 or 2) per row, all on map slot `slot`; h_params [m][18] a parameter row per row, or NULL: the handle's row of
+ * agent slot 0; h_actions in the spec's layout with N = m.  h_out [m][K][D]; h_raw [m][K][10] or NULL: all ten channel values before
+ * scaling (PROGRESS and END_LAT 0.0 when the slot has no track); h_traj [m][K][H][4] float32 (with traj = 1) or NULL; h_traj_raw
+ * [m][K][H][4] float64, the same poses before scaling (with traj = 1), or NULL. */
+int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start /* [m][10] */,
+                       const double *h_params /* [m][18] or NULL */, const double *h_actions, int32_t m, float *h_out /* [m][K][D] */,
+                       double *h_raw /* [m][K][10] or NULL */, float *h_traj /* [m][K][H][4] or NULL */, double *h_traj_raw /* or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
