@@ -50,6 +50,7 @@ struct ExpSwitches {
     int group_split = 0;       // two env groups: percent of the envs in the first (0 = even)
     int integrate_fan = -1;    // 0 / 1: k_integrate_fan (thirteen waves per 64 agents, RK4) off / on at every size, -1 = default (small batches)
     int tiny_general_tail = 0;
+    int pair_wave = -1;        // A = 2: k_finalize_pair_wave (one-wave workgroups) 0 = never, 1 = in every step; -1 = default (in a step of two env blocks: from 24 576 agents, or when step_groups = 2 asks for the blocks)
     int tiny_start_probe = 0;  // k_step_tiny tells the host when its first workgroup starts (f110_step_host times launch -> start -> done)
     long probe_calls = 0;
     double probe_us[3] = {0, 0, 0};
@@ -250,6 +251,7 @@ struct StepRequest {
     const HostBlock *hb = nullptr;          // one car per env, one launch: what k_host_block would be handed ...
     int episode = 0, auto_reset = 0;        // ... (block, episode logic on, re-seat finished envs)
     bool defer_draw = false;                // the caller launches the reset sampler's draw itself, behind its own last kernel
+    bool env_blocks = false;                // step_submit: this step goes out as several env blocks, each on its own stream
 };
 
 static thread_local char g_err[512] = {0};
@@ -576,6 +578,7 @@ int f110_exp_set(f110_sim *h, const char *key, int32_t value)
         h->exp.probe_calls = 0;
         h->exp.probe_us[0] = h->exp.probe_us[1] = h->exp.probe_us[2] = 0;
     }
+    else if (k == "pair_wave") h->exp.pair_wave = value;
     else if (k == "tiny_general_tail") h->exp.tiny_general_tail = value;   // 1: one env of two cars finishes in finalize_pair_body (the tail before finalize_duo_tiny)
     else if (k == "tiny_trace_hi") h->exp.tiny_trace = (h->exp.tiny_trace & 0xffffffffull) | ((uint64_t)(uint32_t)value << 32);
     else if (k == "tiny_trace_lo") h->exp.tiny_trace = (h->exp.tiny_trace & ~0xffffffffull) | (uint64_t)(uint32_t)value;
@@ -2486,6 +2489,7 @@ static int noise_cache_extend(f110_sim *h, int upto)
 // Product build, one dispatch per (agents per env, beams) case:
 //   A = 1                      k_integrate -> scan -> k_finalize_solo
 //   A = 2                      k_integrate -> scan -> k_finalize_pair_roles    (pair test + window inside the last kernel)
+//                              ... k_finalize_pair_wave in a step of two env blocks  (the same as one-wave workgroups, which fit under the other block's scan)
 //   A = 3 .. 16                k_integrate -> scan -> k_finalize_multi         (the same for every ordered pair of an env)
 //   A = 17 .. 256              k_integrate -> scan -> k_finalize_multi_tiled   (the env's ordered pairs in tiles of 256 records)
 //   A > 256                    k_integrate -> { scan || k_collide on the side stream } -> k_finalize
@@ -2879,6 +2883,16 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
             // the workgroups many (measured: 65 536 agents AG 32 / 16 / 4: 0.726 / 0.738 / 0.815 ms; 4096 agents AG 16 / 4:
             // 0.1047 / 0.1053).  (Rounds 2-3's forms — fixed lanes per agent, the prologue dealt by agent — were retired in round 5.)
             lanes = N >= 32768 ? 8 : (N >= 4096 ? 16 : 64);
+            // k_finalize_pair_wave in a step of two env blocks: from 24 576 agents in the automatic mode, where the other block's scan
+            // fills the GPU and the 256-thread form waits for its tail (two blocks, 256-thread / one-wave form, lab build, ms per step:
+            // 8192 agents 0.1235 / 0.1333, 16 384: 0.1964 / 0.1987, 24 576: 0.2754 / 0.2747, 32 768: 0.3637 / 0.3586, 49 152: 0.5278 /
+            // 0.5218, 65 536: 0.6799 / 0.6515 — profiles/two_block_pair_sweep.txt).  step_groups = 2, two blocks on request, takes it at
+            // every size: that keeps the form reachable for small batches in the product build, where the tests hold it against the
+            // one-block step bit for bit.
+            bool pair_wave = rq.env_blocks && (!h->groups_auto || N >= 24576);
+#ifdef F110_EXPERIMENTAL
+            if (h->exp.pair_wave >= 0) pair_wave = h->exp.pair_wave != 0;
+#endif
             if (rq.fuse && begin == 0 && count == N && !dev.reseat_poses) {   // f110_step_host: host block + episode logic as this kernel's epilogue
                 dev.fused_host = h->d_fused;
                 dev.fused_seq = rq.seq;
@@ -2888,6 +2902,13 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
                 if (lanes <= 8) hipLaunchKernelGGL((k_finalize_pair_roles<32, true>), dim3((count + 31) / 32), dim3(256), 0, st, dev, B);
                 else if (lanes == 16) hipLaunchKernelGGL((k_finalize_pair_roles<16, true>), dim3((count + 15) / 16), dim3(256), 0, st, dev, B);
                 else hipLaunchKernelGGL((k_finalize_pair_roles<4, true>), dim3((count + 3) / 4), dim3(256), 0, st, dev, B);
+            } else if (pair_wave) {
+                // one-wave workgroups, which fit the slots the OTHER block's scan frees wave by wave (a 256-thread workgroup waits for
+                // that scan's tail).  Alone it is the slower form — one block at 65 536 agents 0.6933 -> 0.7032 ms with the lab switch
+                // pair_wave = 1 — so one block keeps the form below.  Priced in the bench's regime, re-seats armed; with re-seats off
+                // crashed pairs stay and their windows grow towards all B beams: there it still led, 1.159 -> 1.097 ms (same file).
+                constexpr int AG = kFinalizeWaveAgents;
+                hipLaunchKernelGGL(k_finalize_pair_wave<AG>, dim3((count + AG - 1) / AG), dim3(64), 0, st, dev, B);
             } else if (lanes <= 8) hipLaunchKernelGGL(k_finalize_pair_roles<32>, dim3((count + 31) / 32), dim3(256), 0, st, dev, B);
             else if (lanes == 16) hipLaunchKernelGGL(k_finalize_pair_roles<16>, dim3((count + 15) / 16), dim3(256), 0, st, dev, B);
             else hipLaunchKernelGGL(k_finalize_pair_roles<4>, dim3((count + 3) / 4), dim3(256), 0, st, dev, B);
@@ -2923,11 +2944,11 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
 // 8192 +5.8 %, 16 384 +9.5 %, 32 768 +3.7 %, 65 536 +1.7 %;  A = 1 / 4 / 8 at 16 384: +7.2 / +6.9 / +10.3 %, at 65 536: +5.7 / +4.1 / +4.4 %,
 // at 4096: -0.9 / -0.1 / +3.8 %.  Around 3000 .. 5000 agents the step IS its longest ray's chain of dependent samples: two
 // blocks have two such chains side by side and nothing to hide under them (a heavier finalize, A >= 8, changes that).
-// A = 2 above 32 768 agents stays one block for +1.7 %: one launch per kernel and step keeps the headline's per-kernel
-// accounting (rocprofv3 durations, PMC per dispatch) directly readable.
+// A = 2 above 32 768 agents stayed one block until the two-car finalize got its one-wave form (k_finalize_pair_wave, step_range),
+// which the second block runs under the first block's scan.  With it, one block -> the automatic mode's two blocks, A = 2
+// (profiles/two_block_pair_sweep.txt): see the table there; 65 536 agents 0.6851 -> 0.6414 ms (two_block_pair_bench.txt).
 static bool env_blocks_pay(int N, int A)
 {
-    if (A == 2 && N > 32768) return false;
     if (A <= 4 && N >= 2560 && N <= 5120) return false;
     return true;
 }
@@ -3014,7 +3035,9 @@ static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &
             h->main_dirty = false;
         }
         const int mode = h->collide_mode == 3 ? 3 : ((A == 2 || A == 4) ? 1 : 2);
-        for (const EnvBlock &b : w) TRY(step_range(h, b.stream, b.e0 * A, b.count * A, d_actions, mode, nullptr, rq, host_written));
+        StepRequest rb = rq;
+        rb.env_blocks = true;
+        for (const EnvBlock &b : w) TRY(step_range(h, b.stream, b.e0 * A, b.count * A, d_actions, mode, nullptr, rb, host_written));
         h->groups_busy = true;
     }
     // an in-step re-seat armed (f110_set_auto_reseat): the draw for the envs it re-seated, behind the step (per env block);

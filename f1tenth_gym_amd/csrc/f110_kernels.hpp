@@ -1399,8 +1399,9 @@ __device__ __forceinline__ void pair_host_epilogue(const AgentArrays &a, bool ag
 // flattened into one item list (a crashed pair sees windows of up to all beams; fixed lanes per agent serialise there).
 // Same functions on the same operands as k_collide + k_finalize: bit-identical.  (The earlier forms — fixed lanes per
 // agent, the prologue dealt by agent — were measured slower in round 3 and retired in round 5: DESIGN_HISTORY.md.)
-// (Round 5 also ran this kernel as one-wave workgroups at 8 waves per SIMD, NT = 64, so that a second env block's finalize fits under
-// the first block's scan: it hides, and costs what it hides — retired in round 6, DESIGN.md §8, profiles/r05_finalize_wave.txt.)
+// (Round 5 also ran this body as one-wave workgroups at 8 waves per SIMD, NT = 64, the three roles as branches of the one wave, so
+// that a second env block's finalize fits under the first block's scan: it hid, and cost what it hid (profiles/r05_finalize_wave.txt).
+// The one-wave form a two-block step launches today is K3w below, finalize_pair_wave_body, with the roles merged.)
 // The body is a device function of a 256-thread workgroup over the AG agents [first, first + AG) (round 6): k_finalize_pair_roles
 // runs it once per workgroup; k_step_tiny — the whole step of a tiny batch as ONE launch — runs it in its last workgroup.
 template <int AG, bool HOST>
@@ -1708,6 +1709,165 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HOST ?
         sig.seq = a.fused_seq;
         host_block_signal(sig);
     }
+}
+
+// ---- K3w: finalize_pair_body as ONE-WAVE workgroups, for a step that runs as two env blocks ---------------------------------------
+// A 256-thread workgroup of the other block's finalize waits until this block's scan runs out of workgroups; a one-wave workgroup
+// at 8 waves per SIMD fits the single slot a retiring scan wave frees, and its vector-ALU and latency work then runs under the scan's
+// texture-bound march (DESIGN.md §4 "Env blocks").  Round 5's one-wave form dealt the three roles as divergent branches of the wave
+// (+30 us alone).  Here the roles are MERGED: the 4 AG corner lanes and the AG cull lanes share one pass through the prologue — loads,
+// the opponent's box, cos_sin, both atan2, the square root — the point under a lane select, and part only at the last call
+// (vertex_beam_from_angles / disc_beam_range_from).  The pair test of env (slot, slot + 1) sits on the cull lane of its even agent,
+// behind a wave-uniform skip: cars within reach of each other are rare, and the wave that holds such a pair pays a second pass.
+// AG = 12: 48 + 12 = 60 lanes of the wave in the prologue, and window items (about half the agents see the opponent, up to ~31 beams)
+// that mostly fill their passes of 64.  Same functions on the same operands as finalize_pair_body: bit-identical.  No HOST form: a
+// host-synchronised step never runs as two blocks.
+template <int AG>
+__device__ __forceinline__ void finalize_pair_wave_body(const AgentArrays &a, int32_t B, const int first, const int end)
+{
+    constexpr int NT = 64;
+    constexpr int AGP = AG <= 2 ? 2 : (AG <= 4 ? 4 : (AG <= 8 ? 8 : 16));   // the prefix scan and the item search run over a power of two
+    static_assert(AG >= 2 && (AG & 1) == 0 && 5 * AG <= NT && AG <= AGP, "whole envs, and 4 AG corner + AG cull lanes fit the wave");
+    constexpr int R1 = 4 * AG;   // first lane of the cull role
+    // 64 VGPRs: GJK and box_range read a box's coordinates from LDS where they use them (volatile: not held in registers throughout)
+    typedef const volatile __attribute__((address_space(3))) double *LdsBox;
+    __shared__ double s_rec[AG][12];   // ex, ey, eth, the opponent's box (8), pad
+    __shared__ int s_idx[AG][4], s_cl[AG], s_ch[AG], s_hit[AG / 2];
+    __shared__ int s_lo[AG], s_cnt[AG], s_off[AGP + 1];
+    __shared__ double s_box[AG / 2][16];   // the pair test's two boxes
+    __shared__ int s_ab[NT][2];            // the item loop: each lane's (agent, beam) across its sincos
+    const int t = (int)threadIdx.x;
+    const int N = a.n_agents_total;
+    const int role = t < R1 ? 0 : (t < R1 + AG ? 1 : -1);
+    const int slot = role == 0 ? t >> 2 : t - R1, sub = t & 3;
+    bool near = false;   // cull lane of an even agent whose opponent's centre is within reach: the pair test below
+    if (role >= 0 && first + slot < end) {
+        const int i = first + slot, me = i & 1, o = i ^ 1;
+        const double ex = a.state[i], ey = a.state[(size_t)N + i];
+        const double th_live = a.state[4 * (size_t)N + i];   // == the :574 snapshot heading: nothing has zeroed it yet
+        const double ox = a.snap_pose[o], oy = a.snap_pose[(size_t)N + o], oth = a.snap_pose[2 * (size_t)N + o];
+        const int wall = a.in_collision[i];
+        const double eth = wall ? 0.0 : th_live;
+        const size_t prow = (size_t)(a.params_per_agent ? i : me) * NPARAMS;
+        const double blen = a.params[prow + P_LENGTH], bwid = a.params[prow + P_WIDTH];
+        double v[8];   // the opponent drawn with MY length / width (RaceCar.ray_cast_agents :223)
+        box_vertices(ox, oy, oth, blen, bwid, v);
+        double ce_, se_;
+        cos_sin(eth, ce_, se_);
+        const double head = atan2(se_, ce_);
+        const double px = role == 1 ? ox : (sub == 0 ? v[0] : (sub == 1 ? v[2] : (sub == 2 ? v[4] : v[6])));
+        const double py = role == 1 ? oy : (sub == 0 ? v[1] : (sub == 1 ? v[3] : (sub == 2 ? v[5] : v[7])));
+        const double dx = px - ex, dy = py - ey;
+        const double d2 = dx * dx + dy * dy;   // (cull lanes: the centre distance the pair test's reach check takes)
+        const double norm = sqrt(d2);
+        const double qx = role == 0 ? dx / norm : dx, qy = role == 0 ? dy / norm : dy;
+        const double dir = atan2(qy, qx);
+        if (role == 0) {
+            s_idx[slot][sub] = vertex_beam_from_angles(head, dir, a.scan_angles, B, a.angle_inc);
+            if (sub == 0) {
+                s_rec[slot][0] = ex;
+                s_rec[slot][1] = ey;
+                s_rec[slot][2] = eth;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) s_rec[slot][3 + c] = v[c];
+            }
+        } else {
+            int cl, ch;
+            disc_beam_range_from(norm, eth, dir, head, 0.5 * sqrt(blen * blen + bwid * bwid), a.scan_angles, B, a.angle_inc, cl, ch);
+            s_cl[slot] = cl;
+            s_ch[slot] = ch;
+            const double reach = sqrt(a.box_length * a.box_length + a.box_width * a.box_width) + 1e-3;
+            near = me == 0 && d2 <= reach * reach;
+        }
+    }
+    int hit = 0;
+    if (__ballot(near) != 0) {   // wave-uniform: almost never taken
+        if (near) {
+            // collision_multiple on the env's one pair, boxes with the Simulator's length / width (:549); i is the
+            // even agent: gjk_overlap(mine, other) here is gjk_overlap(other, mine) of the odd agent's call
+            const int i = first + slot, o = i ^ 1;   // (loaded again: nothing is kept live across the prologue for the rare case)
+            double *mine = s_box[slot >> 1], *other = mine + 8;
+            box_vertices(a.state[i], a.state[(size_t)N + i], a.state[4 * (size_t)N + i], a.box_length, a.box_width, mine);
+            box_vertices(a.snap_pose[o], a.snap_pose[(size_t)N + o], a.snap_pose[2 * (size_t)N + o], a.box_length, a.box_width, other);
+            hit = gjk_overlap_from<LdsBox>((LdsBox)mine, (LdsBox)other) ? 1 : 0;
+        }
+    }
+    if (role == 1 && (slot & 1) == 0) s_hit[slot >> 1] = hit;
+    __syncthreads();
+    if (t < AG) {
+        int lo = 0, cnt = 0;
+        if (first + t < end) {
+            const int i = first + t, me = i & 1;
+            const int i0 = s_idx[t][0], i1 = s_idx[t][1], i2 = s_idx[t][2], i3 = s_idx[t][3];
+            const int cl = s_cl[t], ch = s_ch[t];
+            const int my_hit = s_hit[t >> 1];
+            int ref_lo = i0 < i1 ? i0 : i1, t2 = i2 < i3 ? i2 : i3;
+            ref_lo = ref_lo < t2 ? ref_lo : t2;
+            int ref_hi = i0 > i1 ? i0 : i1;
+            t2 = i2 > i3 ? i2 : i3;
+            ref_hi = ref_hi > t2 ? ref_hi : t2;
+            lo = ref_lo > cl ? ref_lo : cl;
+            const int hi = ref_hi < ch ? ref_hi : ch;
+            cnt = hi >= lo ? hi - lo + 1 : 0;
+            const int wall = a.in_collision[i];
+            if (wall) {
+                a.state[3 * (size_t)N + i] = 0.;
+                a.state[4 * (size_t)N + i] = 0.;
+                a.state[5 * (size_t)N + i] = 0.;
+                a.state[6 * (size_t)N + i] = 0.;
+            }
+            a.collisions[i] = (my_hit || wall) ? 1.0 : 0.0;
+            a.collision_idx[i] = my_hit ? (double)(1 - me) : -1.0;
+            a.step_count[i] += 1;
+        }
+        s_lo[t] = lo;
+        s_cnt[t] = cnt;
+    }
+    __syncthreads();
+    {   // exclusive scan of the AG window lengths, padded to AGP (the entries past AG repeat the total: the search never lands there)
+        int c = t < AG ? s_cnt[t] : 0;
+#pragma unroll
+        for (int d = 1; d < AGP; d <<= 1) {
+            const int up = __shfl_up(c, d);
+            if (t >= d) c += up;
+        }
+        if (t < AGP) s_off[t + 1] = c;
+        if (t == 0) s_off[0] = 0;
+    }
+    __syncthreads();
+    for (int item = t; item < s_off[AG]; item += NT) {   // (the total is read again every pass, not kept in a register)
+        int ag = 0;   // the largest ag with s_off[ag] <= item (its window is not empty: item < s_off[ag + 1])
+#pragma unroll
+        for (int st = AGP / 2; st; st >>= 1)
+            if (s_off[ag + st] <= item) ag += st;
+        int b = s_lo[ag] + (item - s_off[ag]);
+        const double bt = s_rec[ag][2] + a.scan_angles[b];
+        // 64 VGPRs: nothing but the angle is held in registers across the sincos — the item's agent and beam wait in LDS, the
+        // record's other ten doubles and the beam's address are read / formed behind it
+        s_ab[item & (NT - 1)][0] = ag;
+        s_ab[item & (NT - 1)][1] = b;
+        double v3x, v3y;
+        sincos(bt + kPi / 2., &v3y, &v3x);
+        __asm__ volatile("" ::: "memory");
+        ag = s_ab[item & (NT - 1)][0];
+        b = s_ab[item & (NT - 1)][1];
+        double *sc = a.scans + (size_t)(first + ag) * B;
+        const double r0 = sc[b];
+        const double r = box_range_from<LdsBox>(s_rec[ag][0], s_rec[ag][1], v3x, v3y, (LdsBox)&s_rec[ag][3], r0);   // (each edge's corners from LDS where the edge needs them)
+        if (r < r0) sc[b] = r;
+    }
+    const int te = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // == t: one wave (formed again, not kept across the item loop)
+    if (a.reseat_poses && te < AG && first + te < end) {
+        const int i = first + te, ego = (i & ~1) + a.reseat_ego;
+        if (s_hit[te >> 1] || a.in_collision[ego] != 0) reseat_agent(a, i, i == ego);
+    }
+}
+
+constexpr int kFinalizeWaveAgents = 12;   // agents per one-wave workgroup (the launcher's grid follows it)
+template <int AG>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) k_finalize_pair_wave(AgentArrays a, int32_t B)   // 8 waves per SIMD = 64 VGPRs
+{
+    finalize_pair_wave_body<AG>(a, B, a.agent_begin + (int)blockIdx.x * AG, a.agent_begin + a.agent_count);
 }
 
 // ---- K3m: the same for envs of MORE than two agents (round 3) ---------------------------------------------

@@ -975,7 +975,9 @@ F110_HD void opponent_beam_window(double ex, double ey, double eth, const double
 }
 
 // the four get_range calls of ray_cast's inner loop (:341-345) for one beam
-F110_HD double box_range(double ex, double ey, double v3x, double v3y, const double *v, double r)
+// (V: const double * — or a volatile pointer into LDS: every corner read where its edge uses it, see finalize_pair_wave_body)
+template <typename V>
+F110_HD double box_range_from(double ex, double ey, double v3x, double v3y, V v, double r)
 {
     double rr = edge_range(ex, ey, v3x, v3y, v[0], v[1], v[2], v[3]);
     if (rr < r) r = rr;
@@ -986,6 +988,11 @@ F110_HD double box_range(double ex, double ey, double v3x, double v3y, const dou
     rr = edge_range(ex, ey, v3x, v3y, v[6], v[7], v[0], v[1]);
     if (rr < r) r = rr;
     return r;
+}
+
+F110_HD double box_range(double ex, double ey, double v3x, double v3y, const double *v, double r)
+{
+    return box_range_from<const double *>(ex, ey, v3x, v3y, v, r);
 }
 
 // ------------------------------------------------------------------ collision_models.py
@@ -1017,7 +1024,9 @@ F110_HD void box_vertices_cs(double x, double y, double c, double s, double leng
     }
 }
 
-F110_HD int furthest_vertex(const double *v, double dx, double dy)
+// (V: const double * — or a volatile pointer into LDS: every vertex read where it is used, see finalize_pair_wave_body)
+template <typename V>
+F110_HD int furthest_vertex(V v, double dx, double dy)
 {
     int best = 0;
     double bv = v[0] * dx + v[1] * dy;
@@ -1032,7 +1041,8 @@ F110_HD int furthest_vertex(const double *v, double dx, double dy)
     return best;
 }
 
-F110_HD void minkowski_support(const double *v1, const double *v2, double dx, double dy, double &ax, double &ay)
+template <typename V>
+F110_HD void minkowski_support(V v1, V v2, double dx, double dy, double &ax, double &ay)
 {
     const int i = furthest_vertex(v1, dx, dy);
     const int j = furthest_vertex(v2, -dx, -dy);
@@ -1050,7 +1060,8 @@ F110_HD void triple_product(double ax, double ay, double bx, double by, double c
 }
 
 // collision (GJK) :113-182 on two 4-vertex convex bodies
-F110_HD bool gjk_overlap(const double *v1, const double *v2)
+template <typename V>
+F110_HD bool gjk_overlap_from(V v1, V v2)
 {
     // simplex slots kept in scalars (no runtime-indexed arrays -> no scratch on gfx950)
     double s0x, s0y, s1x = 0, s1y = 0;
@@ -1105,6 +1116,8 @@ F110_HD bool gjk_overlap(const double *v1, const double *v2)
     }
     return false;
 }
+
+F110_HD bool gjk_overlap(const double *v1, const double *v2) { return gjk_overlap_from<const double *>(v1, v2); }
 
 // ------------------------------------------------------------------ examples/waypoint_follow.py
 // The reference's example policy (PurePursuitPlanner), so a closed loop can stay on the GPU.

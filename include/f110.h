@@ -105,7 +105,8 @@ int f110_is_experimental(void);
  * env, beams) case.  Keys: scan_flat, collide_mode (0 side stream | 1 fused into k_integrate | 2 in line | 3 inside k_finalize),
  * task_order, task_thr, task_cap_div (list capacity = tasks / div), task_rev (walk the list from its newest entry), long_prio,
  * scan_occupancy, scan_env_counter (fusion probes), integrate_duo (-1|0|1: k_integrate in one wave or two per 64 agents),
- * integrate_fan (-1|0|1), group_split, step_tiny (0: tiny batches through the three kernels too — the A/B of k_step_tiny), scan_trace_hi / scan_trace_lo (the two halves of the device address of a caller-owned
+ * integrate_fan (-1|0|1), group_split, pair_wave (-1|0|1: the A = 2 finalize as one-wave workgroups never / in every step; -1 = in a step of two env blocks, from 24 576 agents or under step_groups = 2),
+ * step_tiny (0: tiny batches through the three kernels too — the A/B of k_step_tiny), scan_trace_hi / scan_trace_lo (the two halves of the device address of a caller-owned
  * [launch waves][8] uint64 buffer that every wave of the step's scan kernel stamps with its begin / end clock, CU and samples:
  * tools/debug/scan_timeline.py; 0 = off).  Retired with the code they switched (numbers in DESIGN.md section 8 / DESIGN_HISTORY.md) — round 5:
  * dedupe_two_pass, no_window, finalize_lanes / _flat / _roles, pair_always, step_graph, ray_pass / ray_thr / ray_waves; round 6 (the
