@@ -103,6 +103,15 @@ NBR_DX, NBR_DY, NBR_DIST, NBR_COS_DTH, NBR_SIN_DTH, NBR_V_X, NBR_V_Y, NBR_GAP_S,
 NBR_NCHANNELS, NBR_MAX_K, NBR_MAX_AGENTS = 10, 8, 256
 
 
+class Obstacle(C.Structure):
+    """struct f110_obstacle"""
+    _fields_ = [("shape", C.c_int32), ("reserved", C.c_int32), ("x", C.c_double), ("y", C.c_double), ("c", C.c_double), ("s", C.c_double),
+                ("half_length", C.c_double), ("half_width", C.c_double)]
+
+
+OBST_BOX, OBST_DISC, MAX_OBSTACLES = 0, 1, 256
+
+
 class RolloutSpec(C.Structure):
     """struct f110_rollout"""
     _fields_ = [("k", C.c_int32), ("horizon", C.c_int32), ("repeat", C.c_int32), ("layout", C.c_int32), ("frame", C.c_int32),
@@ -181,6 +190,11 @@ PROTOTYPES = {
     "f110_add_map_image": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _i32p]),
     "f110_add_map_dt": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i32p]),
     "f110_set_env_maps": (C.c_int, [C.c_void_p, _i32p]),
+    "f110_add_map_obstacles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Obstacle), C.c_int32, _i32p]),
+    "f110_set_map_obstacles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Obstacle), C.c_int32]),
+    "f110_get_slot_dt": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "f110_slot_shape": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p]),
+    "f110_slot_table": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), _i32p]),
     "f110_set_params_batch": (C.c_int, [C.c_void_p, _dp]),
     "f110_reset_collided_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "f110_set_auto_reseat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

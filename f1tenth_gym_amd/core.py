@@ -410,12 +410,39 @@ class BatchSim(object):
             raise ValueError("env_map must have num_envs=%d entries (got %d)" % (self.E, m.shape[0]))
         check(_ffi.lib().f110_set_env_maps(self._h, m.ctypes.data_as(_ffi._i32p)), self._h)
 
-    def get_map_dt(self):
+    def get_map_dt(self, slot=0):
+        """the distance table of a map slot, row-major [height][width] (row 0 = bottom of the picture)"""
         h, w = C.c_int32(), C.c_int32()
-        check(_ffi.lib().f110_map_shape(self._h, C.byref(h), C.byref(w)), self._h)
+        check(_ffi.lib().f110_slot_shape(self._h, int(slot), C.byref(h), C.byref(w)), self._h)
         out = np.empty((h.value, w.value))
-        check(_ffi.lib().f110_get_map_dt(self._h, dptr(out)), self._h)
+        check(_ffi.lib().f110_get_slot_dt(self._h, int(slot), dptr(out)), self._h)
         return out
+
+    # ---- static obstacles in a derived map slot (extension, DESIGN §6j)
+    def add_obstacle_map(self, obstacles, base=0):
+        """register a map slot DERIVED from slot `base` (slot 0 or one of add_map_*) with `obstacles` (an Obstacles; None: a copy of
+        the base) stamped into its distance table on the device; returns its slot (set_env_maps).  The base's Track, if it has
+        one, is attached to the new slot too.  Obstacles are per slot: one padded table of device memory each."""
+        from .obstacles import Obstacles
+        ob = Obstacles.coerce(obstacles)
+        slot = C.c_int32(0)
+        check(_ffi.lib().f110_add_map_obstacles(self._h, int(base), ob.structs(), len(ob), C.byref(slot)), self._h)
+        t = getattr(self, "tracks", {}).get(int(base))
+        if t is not None:
+            self.set_track(t, slot=int(slot.value))
+        return int(slot.value)
+
+    def set_obstacles(self, slot, obstacles):
+        """re-stamp a derived slot in place, from its base: ordered behind the steps in flight and in front of the next one"""
+        from .obstacles import Obstacles
+        ob = Obstacles.coerce(obstacles)
+        check(_ffi.lib().f110_set_map_obstacles(self._h, int(slot), ob.structs(), len(ob)), self._h)
+
+    def map_table_address(self, slot=0):
+        """(device address of the slot's table cell [0][0], its row pitch in bytes): what the kernels read"""
+        p, rb = C.c_void_p(), C.c_int32()
+        check(_ffi.lib().f110_slot_table(self._h, int(slot), C.byref(p), C.byref(rb)), self._h)
+        return int(p.value or 0), int(rb.value)
 
     def set_beam_tables(self, scan_angles, cosines, side_distances):
         """replace the per-beam tables of check_ttc_jit / ray_cast (base_classes.py:125-158) — normally built from `params` at creation"""

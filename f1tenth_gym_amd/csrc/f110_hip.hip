@@ -81,10 +81,22 @@ struct f110_sim {
         double *d_dt_row = nullptr, *d_dt_pad = nullptr;
         ScanConst k{};
         uint8_t *d_occ = nullptr;   // f110_render_device's occupancy grid, built on first use
+        bool occ_stale = false;     // ... and again after f110_set_map_obstacles re-stamped the table (the allocation stays)
+        int base = -1;              // >= 0: a DERIVED slot (f110_add_map_obstacles), stamped from this base slot's table
     };
     std::vector<MapSlot> extra_maps;
     MapFast *d_maps_fast = nullptr;
     ScanConst *d_maps_full = nullptr;
+    int n_maps_dev = 0;                 // slots d_maps_full holds
+    // f110_*_map_obstacles: the byte mask, the active columns' distances and list, the boxes, the out-of-bounds value (grow-only)
+    struct ObstScratch {
+        uint8_t *mask = nullptr;
+        uint32_t *g = nullptr;
+        int32_t *cols = nullptr;
+        ObstBox *boxes = nullptr;
+        double *oob = nullptr;
+        size_t mask_cap = 0, g_cap = 0, cols_cap = 0;
+    } obst;
     int32_t *d_env_map = nullptr;
     uint32_t *d_scan_order = nullptr;   // [N] agents sorted by map slot (nullptr while every env is on one slot)
     bool multi_map = false;
@@ -978,6 +990,11 @@ void f110_destroy(f110_sim *h)
     }
     if (h->d_maps_fast) (void)hipFree(h->d_maps_fast);
     if (h->d_maps_full) (void)hipFree(h->d_maps_full);
+    {
+        void *op[] = {h->obst.mask, h->obst.g, h->obst.cols, h->obst.boxes, h->obst.oob};
+        for (void *p : op)
+            if (p) (void)hipFree(p);
+    }
     if (h->d_env_map) (void)hipFree(h->d_env_map);
     if (h->d_scan_order) (void)hipFree(h->d_scan_order);
     for (auto &ts : h->tracks) {
@@ -1243,7 +1260,9 @@ int f110_set_env_maps(f110_sim *h, const int32_t *h_env_map)
     if (h->d_maps_full) { (void)hipFree(h->d_maps_full); h->d_maps_full = nullptr; }
     if (!h->d_env_map) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_env_map), sizeof(int32_t) * E));
     HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_maps_fast), sizeof(MapFast) * M));
+    h->n_maps_dev = 0;
     HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_maps_full), sizeof(ScanConst) * M));
+    h->n_maps_dev = M;
     HIPCHK(h, hipMemcpyAsync(h->d_maps_fast, fast.data(), sizeof(MapFast) * M, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_maps_full, full.data(), sizeof(ScanConst) * M, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_env_map, h_env_map, sizeof(int32_t) * E, hipMemcpyHostToDevice, h->stream));
@@ -1292,6 +1311,181 @@ int f110_map_shape(f110_sim *h, int32_t *H, int32_t *W)
     if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
     if (H) *H = h->k.height;
     if (W) *W = h->k.width;
+    return F110_OK;
+}
+
+// ---- static obstacles in a derived map slot (include/f110.h) -------------------------------------------------
+static_assert(sizeof(f110_obstacle) == sizeof(Obstacle) && sizeof(Obstacle) == 56, "f110_obstacle and f110::Obstacle are one layout");
+static_assert((int)F110_OBST_BOX == (int)OBST_BOX && (int)F110_OBST_DISC == (int)OBST_DISC && (int)F110_MAX_OBSTACLES == kMaxObstacles, "obstacle enums");
+
+static const ScanConst &slot_consts(const f110_sim *h, int slot) { return slot == 0 ? h->k : h->extra_maps[slot - 1].k; }
+
+// the refusals that concern the list alone
+static int obstacles_check(f110_sim *h, const char *who, const f110_obstacle *obs, int n)
+{
+    if (n < 0 || n > F110_MAX_OBSTACLES) return fail(h, F110_ERR_INVALID, "%s: n = %d obstacles, 0..%d are allowed", who, n, (int)F110_MAX_OBSTACLES);
+    if (n > 0 && !obs) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    for (int i = 0; i < n; ++i) {
+        const f110_obstacle &o = obs[i];
+        if (o.shape != F110_OBST_BOX && o.shape != F110_OBST_DISC) return fail(h, F110_ERR_INVALID, "%s: obstacle %d: unknown shape %d", who, i, o.shape);
+        const double v[6] = {o.x, o.y, o.c, o.s, o.half_length, o.half_width};
+        for (double x : v)
+            if (!std::isfinite(x)) return fail(h, F110_ERR_INVALID, "%s: obstacle %d has a non-finite field", who, i);
+        if (o.half_length < 0 || o.half_width < 0) return fail(h, F110_ERR_INVALID, "%s: obstacle %d has a negative half extent", who, i);
+    }
+    return F110_OK;
+}
+
+// grow-only scratch: *cap counts bytes
+static int obst_grow(f110_sim *h, void **p, size_t *cap, size_t bytes)
+{
+    if (*cap >= bytes && *p) return F110_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    *cap = 0;
+    HIPCHK(h, hipMalloc(p, bytes > 0 ? bytes : 8));
+    *cap = bytes;
+    return F110_OK;
+}
+
+// Stamp `obs` into derived slot m (>= 1) from its base's table: everything on the main stream (the caller went through ENTER, so
+// steps in flight on the env blocks come first and the next step's blocks fork from behind this), then one wait for the new
+// out-of-bounds value.  The list has been checked.
+static int obstacles_stamp(f110_sim *h, const char *who, int m, const f110_obstacle *obs, int n)
+{
+    f110_sim::MapSlot &ms = h->extra_maps[m - 1];
+    const ScanConst &kb = slot_consts(h, ms.base);
+    const int H = ms.k.height, W = ms.k.width;
+    if (kb.height != H || kb.width != W)
+        return fail(h, F110_ERR_STATE, "%s: slot %d was derived from a %d x %d base, slot %d is %d x %d now", who, m, H, W, ms.base, kb.height, kb.width);
+    const ObstFrame fr{ms.k.res, ms.k.orig_x, ms.k.orig_y, ms.k.orig_c, ms.k.orig_s};
+    // the boxes that reach the table, and the union of their column ranges
+    std::vector<ObstBox> boxes;
+    std::vector<char> active((size_t)W, 0);
+    size_t max_cells = 0;
+    for (int i = 0; i < n; ++i) {
+        ObstBox b;
+        std::memcpy(&b.o, &obs[i], sizeof(Obstacle));
+        obstacle_cell_box(b.o, fr, H, W, b.c0, b.c1, b.r0, b.r1);
+        if (b.c0 > b.c1 || b.r0 > b.r1) continue;
+        for (int c = b.c0; c <= b.c1; ++c) active[c] = 1;
+        max_cells = std::max(max_cells, (size_t)(b.c1 - b.c0 + 1) * (size_t)(b.r1 - b.r0 + 1));
+        boxes.push_back(b);
+    }
+    std::vector<int32_t> cols;
+    for (int c = 0; c < W; ++c)
+        if (active[c]) cols.push_back(c);
+    const int Wa = (int)cols.size();
+    f110_sim::ObstScratch &sc = h->obst;
+    if (!sc.oob) TRY(dmalloc(h, &sc.oob, 1));
+    if (!sc.boxes) TRY(dmalloc(h, &sc.boxes, (size_t)F110_MAX_OBSTACLES));
+    if (Wa > 0) {
+        TRY(obst_grow(h, reinterpret_cast<void **>(&sc.mask), &sc.mask_cap, (size_t)H * W));
+        TRY(obst_grow(h, reinterpret_cast<void **>(&sc.g), &sc.g_cap, (size_t)H * Wa * sizeof(uint32_t)));
+        TRY(obst_grow(h, reinterpret_cast<void **>(&sc.cols), &sc.cols_cap, (size_t)W * sizeof(int32_t)));
+        HIPCHK(h, hipMemsetAsync(sc.mask, 0, (size_t)H * W, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sc.boxes, boxes.data(), boxes.size() * sizeof(ObstBox), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sc.cols, cols.data(), (size_t)Wa * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_obst_stamp, dim3((unsigned)((max_cells + 255) / 256), (unsigned)boxes.size()), dim3(256), 0, h->stream, sc.boxes, fr, W, sc.mask);
+        hipLaunchKernelGGL(k_obst_columns, grid1d((size_t)Wa, 64), dim3(64), 0, h->stream, sc.mask, sc.cols, H, W, Wa, sc.g);
+    }
+    double *oob_dev = (h->d_maps_full && m < h->n_maps_dev) ? &h->d_maps_full[m].oob_value : nullptr;
+    hipLaunchKernelGGL(k_obst_corner, dim3(1), dim3(256), 0, h->stream, sc.g, sc.cols, Wa, kb.table_rm, kb.row_bytes, H, W, ms.k.res, sc.oob, oob_dev);
+    hipLaunchKernelGGL(k_obst_rows, dim3((unsigned)((ms.k.pad_width + 255) / 256), (unsigned)ms.k.pad_height), dim3(256), 0, h->stream, sc.g, sc.cols, Wa,
+                       kb.table_rm, kb.row_bytes, H, W, ms.k.pad_border, ms.k.pad_width, ms.k.res, sc.oob, ms.d_dt_pad);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&ms.k.oob_value, sc.oob, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ms.occ_stale = true;
+    return F110_OK;
+}
+
+int f110_add_map_obstacles(f110_sim *h, int32_t base_slot, const f110_obstacle *h_obs, int32_t n, int32_t *slot)
+{
+    static const char *const who = "f110_add_map_obstacles";
+    if (!h || !slot) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    TRY(obstacles_check(h, who, h_obs, n));
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (base_slot < 0 || base_slot > (int)h->extra_maps.size())
+        return fail(h, F110_ERR_INVALID, "%s: base slot %d, but %d maps are registered", who, base_slot, 1 + (int)h->extra_maps.size());
+    if (base_slot > 0 && h->extra_maps[base_slot - 1].base >= 0) return fail(h, F110_ERR_INVALID, "%s: slot %d is itself derived; derive from its base, slot %d", who, base_slot, h->extra_maps[base_slot - 1].base);
+    if (!padded_family(h->cfg.map_layout)) return fail(h, F110_ERR_STATE, "%s needs map_layout = F110_MAP_PADDED_F64", who);
+    const ScanConst kb = slot_consts(h, base_slot);
+    if (kb.height > 16384 || kb.width > 16384) return fail(h, F110_ERR_INVALID, "%s: the base is %d x %d cells, at most 16384 a side are supported", who, kb.height, kb.width);
+    ENTER(h);
+    f110_sim::MapSlot ms;
+    ms.k = h->k;   // beam / trig / range constants are shared; the map fields are the base's
+    fill_map_fields(ms.k, kb.height, kb.width, kb.res, kb.orig_x, kb.orig_y, kb.orig_c, kb.orig_s);
+    if (!setup_padded(ms.k)) return fail(h, F110_ERR_INVALID, "f110_add_map: a per-env map must fit the padded layout (16-bit cell coordinates, < 4 GiB)");
+    TRY(dmalloc(h, &ms.d_dt_pad, (size_t)ms.k.pad_width * ms.k.pad_height));
+    ms.k.pad = ms.d_dt_pad;
+    ms.k.table = ms.k.table_rm = ms.d_dt_pad + (size_t)ms.k.pad_border * ms.k.pad_width + ms.k.pad_border;
+    ms.k.row_bytes = ms.k.pad_row_bytes;
+    ms.base = base_slot;
+    h->extra_maps.push_back(ms);
+    const int m = (int)h->extra_maps.size();
+    const int rc = obstacles_stamp(h, who, m, h_obs, n);
+    if (rc != F110_OK) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipFree(ms.d_dt_pad);
+        h->extra_maps.pop_back();
+        return rc;
+    }
+    *slot = m;
+    return F110_OK;
+}
+
+int f110_set_map_obstacles(f110_sim *h, int32_t slot, const f110_obstacle *h_obs, int32_t n)
+{
+    static const char *const who = "f110_set_map_obstacles";
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "%s: null argument", who);
+    TRY(obstacles_check(h, who, h_obs, n));
+    if (slot < 0 || slot > (int)h->extra_maps.size())
+        return fail(h, F110_ERR_INVALID, "%s: slot %d, but %d maps are registered", who, slot, 1 + (int)h->extra_maps.size());
+    if (slot == 0 || h->extra_maps[slot - 1].base < 0) return fail(h, F110_ERR_INVALID, "%s: slot %d is not a derived slot (f110_add_map_obstacles makes one)", who, slot);
+    {
+        const f110_sim::MapSlot &ms = h->extra_maps[slot - 1];
+        const ScanConst &kb = slot_consts(h, ms.base);
+        if (!h->has_map || kb.height != ms.k.height || kb.width != ms.k.width)
+            return fail(h, F110_ERR_STATE, "%s: slot %d was derived from a %d x %d base, slot %d is %d x %d now", who, slot, ms.k.height, ms.k.width, ms.base,
+                        kb.height, kb.width);
+    }
+    ENTER(h);
+    return obstacles_stamp(h, who, slot, h_obs, n);
+}
+
+int f110_slot_shape(f110_sim *h, int32_t slot, int32_t *H, int32_t *W)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "f110_slot_shape: slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    const ScanConst &k = slot_consts(h, slot);
+    if (H) *H = k.height;
+    if (W) *W = k.width;
+    return F110_OK;
+}
+
+int f110_slot_table(f110_sim *h, int32_t slot, const double **d_table, int32_t *row_bytes)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "f110_slot_table: slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    const ScanConst &k = slot_consts(h, slot);
+    if (d_table) *d_table = k.table_rm;
+    if (row_bytes) *row_bytes = k.row_bytes;
+    return F110_OK;
+}
+
+int f110_get_slot_dt(f110_sim *h, int32_t slot, double *out)
+{
+    if (!h || !out) return fail(h, F110_ERR_INVALID, "null argument");
+    if (slot == 0) return f110_get_map_dt(h, out);
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "f110_get_slot_dt: slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    ENTER(h);
+    const ScanConst &k = h->extra_maps[slot - 1].k;
+    const size_t row = (size_t)k.width * sizeof(double);
+    HIPCHK(h, hipMemcpy2DAsync(out, row, k.table_rm, (size_t)k.row_bytes, row, (size_t)k.height, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }
 
@@ -4916,11 +5110,12 @@ static int render_grow(f110_sim *h, T **p, size_t *cap, size_t count)
 }
 
 // the occupancy grid of a slot's table, built the first time a render reads the slot
-static int render_occ(f110_sim *h, const ScanConst &k, uint8_t **occ)
+static int render_occ(f110_sim *h, const ScanConst &k, uint8_t **occ, bool *stale)
 {
-    if (*occ) return F110_OK;
+    if (*occ && !(stale && *stale)) return F110_OK;
     const size_t n = (size_t)k.height * k.width;
-    TRY(dmalloc(h, occ, n));
+    if (!*occ) TRY(dmalloc(h, occ, n));
+    if (stale) *stale = false;
     hipLaunchKernelGGL(k_render_occ, grid1d(n, 256), dim3(256), 0, h->stream, k.table, k.row_bytes, k.height, k.width, *occ);
     HIPCHK(h, hipGetLastError());
     return F110_OK;
@@ -4957,7 +5152,7 @@ int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t 
         const ScanConst &k = m == 0 ? h->k : h->extra_maps[m - 1].k;
         RenderSlot &r = rs[m];
         r = RenderSlot{};
-        if (sp.layers & F110_LAYER_MAP) TRY(render_occ(h, k, m == 0 ? &h->d_occ0 : &h->extra_maps[m - 1].d_occ));
+        if (sp.layers & F110_LAYER_MAP) TRY(render_occ(h, k, m == 0 ? &h->d_occ0 : &h->extra_maps[m - 1].d_occ, m == 0 ? nullptr : &h->extra_maps[m - 1].occ_stale));
         r.occ = m == 0 ? h->d_occ0 : h->extra_maps[m - 1].d_occ;
         if ((sp.layers & F110_LAYER_TRACK) && m < (int)h->tracks.size() && h->tracks[m].d_pts) {
             r.pts = h->tracks[m].d_pts;

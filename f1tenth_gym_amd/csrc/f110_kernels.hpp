@@ -3259,6 +3259,127 @@ __global__ void k_build_padded(const double *__restrict__ rowmajor, int H, int W
     pad[i] = inside ? rowmajor[(size_t)r * W + c] : rowmajor[(size_t)H * W - 1];
 }
 
+// ---- static obstacles stamped into a derived map slot (f110_add_map_obstacles / f110_set_map_obstacles) --------
+// The slot's table is min(base table, res * sqrt(d2 to the nearest stamped cell)): the EDT of a union is the minimum of the EDTs.
+// Only the columns some obstacle's cell box touches (the ACTIVE columns, listed by the host) can hold a stamped cell, so the column
+// pass runs over those and the row pass takes its minimum over them: H * W * W_active instead of k_edt_rows' H * W * W.
+struct ObstBox {
+    Obstacle o;
+    int32_t c0, c1, r0, r1;   // obstacle_cell_box: non-empty (the host drops the others)
+};
+
+// blockIdx.y = obstacle, the x axis walks its cell box row by row.  mask [H][W] was zeroed on the stream; lanes of different
+// obstacles may store the same 1 to the same byte.
+__global__ void __launch_bounds__(256) k_obst_stamp(const ObstBox *__restrict__ boxes, ObstFrame f, int W, uint8_t *__restrict__ mask)
+{
+    const ObstBox b = boxes[blockIdx.y];
+    const uint32_t bw = (uint32_t)(b.c1 - b.c0 + 1), bh = (uint32_t)(b.r1 - b.r0 + 1);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= bw * bh) return;   // (bw * bh <= 16384^2 < 2^32: f110_add_map_obstacles checks the shape)
+    const uint32_t dr = t / bw;
+    const int r = b.r0 + (int)dr, c = b.c0 + (int)(t - dr * bw);
+    if (obstacle_hit(b.o, f, r, c)) mask[(size_t)r * W + c] = 1;
+}
+
+// k_edt_columns over the active columns: lane = active column a (table column cols[a]); g [H][Wa].  A column without a stamped
+// cell carries kEdtInf in every row.
+__global__ void k_obst_columns(const uint8_t *__restrict__ mask, const int32_t *__restrict__ cols, int H, int W, int Wa, uint32_t *__restrict__ g)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= Wa) return;
+    const int x = cols[a];
+    uint32_t run = kEdtInf;
+    for (int y = 0; y < H; ++y) {
+        run = mask[(size_t)y * W + x] ? 0 : (run >= kEdtInf ? kEdtInf : run + 1);
+        g[(size_t)y * Wa + a] = run;
+    }
+    run = kEdtInf;
+    for (int y = H - 1; y >= 0; --y) {
+        const uint32_t cur = g[(size_t)y * Wa + a];
+        run = (cur == 0) ? 0 : (run >= kEdtInf ? kEdtInf : run + 1);
+        if (run < cur) g[(size_t)y * Wa + a] = run;
+    }
+}
+
+// a d2 made of kEdtInf columns only (or of none) means "nothing stamped": any real one is below (W^2 + H^2 <= 2^29)
+constexpr uint32_t kObstNone = kEdtInf * kEdtInf;
+
+__device__ __forceinline__ double obst_value(double base, uint32_t d2, double res)
+{
+    if (d2 >= kObstNone) return base;
+    const double v = res * sqrt((double)d2);   // k_dt_from_d2's expression
+    return v < base ? v : base;
+}
+
+// The slot's out-of-bounds value T'[H-1][W-1], before the row pass needs it for the border: one workgroup reduces the corner
+// cell's candidates.  Written to *oob (the row pass and the host read it) and, when the env-map tables are on the device, into the
+// slot's ScanConst there.
+__global__ void __launch_bounds__(256) k_obst_corner(const uint32_t *__restrict__ g, const int32_t *__restrict__ cols, int Wa, const double *__restrict__ base,
+                                                     int base_row_bytes, int H, int W, double res, double *__restrict__ oob, double *__restrict__ oob_dev)
+{
+    __shared__ uint32_t part[256];
+    uint32_t best = 0xFFFFFFFFu;
+    for (int a = threadIdx.x; a < Wa; a += 256) {
+        const int d = W - 1 - cols[a];
+        const uint32_t v = g[(size_t)(H - 1) * Wa + a];
+        const uint32_t cand = (uint32_t)(d * d) + v * v;
+        best = cand < best ? cand : best;
+    }
+    part[threadIdx.x] = best;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) part[threadIdx.x] = part[threadIdx.x + s] < part[threadIdx.x] ? part[threadIdx.x + s] : part[threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double b = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + (size_t)(H - 1) * (size_t)base_row_bytes + (size_t)(W - 1) * 8);
+        const double v = obst_value(b, part[0], res);
+        *oob = v;
+        if (oob_dev) *oob_dev = v;
+    }
+}
+
+// The row pass, the minimum with the base and res * sqrt in one kernel, writing the slot's padded copy: blockIdx.y = padded row,
+// each lane one padded column.  A workgroup of an interior row stages the active columns' (index, g^2) in LDS, kObstChunk at a
+// time, and every lane walks them (broadcast reads); border cells (and whole border workgroups, before any barrier) store *oob.
+constexpr int kObstChunk = 2048;   // 16 KiB of LDS
+__global__ void __launch_bounds__(256) k_obst_rows(const uint32_t *__restrict__ g, const int32_t *__restrict__ cols, int Wa, const double *__restrict__ base,
+                                                   int base_row_bytes, int H, int W, int b, int Wp, double res, const double *__restrict__ oob,
+                                                   double *__restrict__ pad)
+{
+    __shared__ uint2 act[kObstChunk];
+    const int pr = blockIdx.y, pc0 = blockIdx.x * 256, pc = pc0 + (int)threadIdx.x;
+    const int r = pr - b, c = pc - b;
+    double *const out = pad + (size_t)pr * Wp + pc;
+    if (r < 0 || r >= H || pc0 - b >= W || pc0 + 255 - b < 0) {   // workgroup-uniform: nothing but border
+        if (pc < Wp) *out = *oob;
+        return;
+    }
+    uint32_t best = 0xFFFFFFFFu;
+    for (int a0 = 0; a0 < Wa; a0 += kObstChunk) {
+        const int n = Wa - a0 < kObstChunk ? Wa - a0 : kObstChunk;
+        if (a0) __syncthreads();   // the previous chunk has been read
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const uint32_t v = g[(size_t)r * Wa + a0 + i];
+            act[i] = make_uint2((uint32_t)cols[a0 + i], v * v);   // v <= kEdtInf: v^2 < 2^30
+        }
+        __syncthreads();
+        for (int i = 0; i < n; ++i) {
+            const uint2 e = act[i];
+            const int d = c - (int)e.x;   // |d| < 2^15: d^2 + g^2 < 2^31
+            const uint32_t cand = (uint32_t)(d * d) + e.y;
+            best = cand < best ? cand : best;
+        }
+    }
+    if (pc >= Wp) return;
+    if (c < 0 || c >= W) {
+        *out = *oob;
+        return;
+    }
+    const double bv = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + (size_t)r * (size_t)base_row_bytes + (size_t)c * 8);
+    *out = obst_value(bv, best, res);
+}
+
 
 // A reactive policy that CONSUMES the scans where the scan kernel left them (round 5; not a reference function — the stand-in
 // for an RL policy in a device-resident loop: examples/rl_loop_device.py, bench.py's "scans consumed on device" leg).  One wave

@@ -1843,4 +1843,58 @@ F110_HD void roll_store_track(const RollSpec &sp, double progress, double lat, f
     roll_store(sp, v, kRollTrackBits, o, raw);
 }
 
+// ------------------------------------------------------------------ static obstacles (f110_add_map_obstacles)
+enum { OBST_BOX = 0, OBST_DISC = 1 };
+constexpr int kMaxObstacles = 256;
+
+// struct f110_obstacle of include/f110.h, field for field
+struct Obstacle {
+    int32_t shape, reserved;
+    double x, y, c, s, half_length, half_width;
+};
+
+// the map fields the hit test reads (a slot's resolution and origin)
+struct ObstFrame {
+    double res, ox, oy, oc, os;
+};
+
+// Is the centre of table cell (r, col) inside the shape?  include/f110.h states the rule; float64 in exactly this order, no
+// contraction, no trigonometry: the NumPy model (tests/obstacles_ref.py) evaluates the same expressions and agrees bit for bit.
+F110_HD bool obstacle_hit(const Obstacle &o, const ObstFrame &f, int r, int col)
+{
+    const double px = ((double)col + 0.5) * f.res, py = ((double)r + 0.5) * f.res;
+    const double wx = f.ox + (px * f.oc - py * f.os), wy = f.oy + (px * f.os + py * f.oc);
+    const double dx = wx - o.x, dy = wy - o.y;
+    if (o.shape == OBST_DISC) return dx * dx + dy * dy <= o.half_length * o.half_length;
+    const double u = dx * o.c + dy * o.s, v = -dx * o.s + dy * o.c;
+    return fabs(u) <= o.half_length && fabs(v) <= o.half_width;
+}
+
+// A conservative cell box [c0, c1] x [r0, r1] around the shape, clamped to the table (empty: c0 > c1 or r0 > r1).  The shape lies
+// inside the circle of radius hypot(half_length, half_width) (a disc: half_length) around its centre; two cells of margin cover
+// the rounding of this arithmetic against obstacle_hit's ...
+F110_HD void obstacle_cell_box(const Obstacle &o, const ObstFrame &f, int H, int W, int &c0, int &c1, int &r0, int &r1)
+{
+    const double R = o.shape == OBST_DISC ? o.half_length : sqrt(o.half_length * o.half_length + o.half_width * o.half_width);
+    const double dx = o.x - f.ox, dy = o.y - f.oy;
+    const double inv = 1.0 / f.res;
+    const double tx = (dx * f.oc + dy * f.os) * inv - 0.5, ty = (-dx * f.os + dy * f.oc) * inv - 0.5;   // centre in cell-centre units
+    // ... and 1e-12 of the coordinates' magnitude covers it where they are huge; beyond 1e150 (squares overflow: inf <= inf is a
+    // hit by the rule) the box is the whole table
+    const double mag = fabs(o.x) + fabs(o.y) + fabs(f.ox) + fabs(f.oy) + ((double)W + (double)H) * f.res;
+    const bool wild = !(R <= 1e150) || !(mag <= 1e150);
+    const double m = R * inv * (1.0 + 1e-9) + 2.0 + 1e-12 * mag * inv;
+    // clamp in float64 BEFORE the conversion: a far-away centre must not overflow an int
+    const double lo_c = floor(tx - m), hi_c = ceil(tx + m), lo_r = floor(ty - m), hi_r = ceil(ty + m);
+    c0 = lo_c > 0.0 ? (lo_c < (double)W ? (int)lo_c : W) : 0;
+    c1 = hi_c < (double)(W - 1) ? (hi_c >= 0.0 ? (int)hi_c : -1) : W - 1;
+    r0 = lo_r > 0.0 ? (lo_r < (double)H ? (int)lo_r : H) : 0;
+    r1 = hi_r < (double)(H - 1) ? (hi_r >= 0.0 ? (int)hi_r : -1) : H - 1;
+    if (wild) {
+        c0 = r0 = 0;
+        c1 = W - 1;
+        r1 = H - 1;
+    }
+}
+
 }  // namespace f110

@@ -223,6 +223,11 @@ class F110Env(_EnvBase):
             self.neighbors = Neighbors.coerce(kwargs['neighbors'])
             if self.neighbors.needs_track and self.track is None:
                 raise ValueError("neighbors= with 'gap_s' needs a track (track=...)")
+        # static obstacles: obstacles= puts the env on a slot derived from slot 0 with the shapes stamped in
+        self.obstacle_slot = None
+        if kwargs.get('obstacles') is not None:
+            self.obstacle_slot = self.sim.batch.add_obstacle_map(kwargs['obstacles'], 0)
+            self.sim.batch.set_env_maps([self.obstacle_slot])
         # randomised start poses: random_start= (a ResetSampler or a dict of its settings) makes reset() without
         # poses draw them on the track
         self.random_start = None
@@ -294,7 +299,17 @@ class F110Env(_EnvBase):
         return self.step(action)            # f110_env.py:337-338: reset advances one step
 
     def update_map(self, map_path, map_ext):
+        """(an env made with obstacles= goes back to the plain map: call set_obstacles again to stamp them into the new one)"""
         self.sim.set_map(map_path, map_ext)
+        self.obstacle_slot = None
+
+    def set_obstacles(self, obstacles):
+        """stamp another Obstacles into this env's map (in place when the env already runs on a derived slot)"""
+        if self.obstacle_slot is None:
+            self.obstacle_slot = self.sim.batch.add_obstacle_map(obstacles, 0)
+            self.sim.batch.set_env_maps([self.obstacle_slot])
+        else:
+            self.sim.batch.set_obstacles(self.obstacle_slot, obstacles)
 
     def update_params(self, params, index=-1):
         self.sim.update_params(params, agent_idx=index)
@@ -347,6 +362,11 @@ class F110VecEnv(object):
     Domain randomisation over tracks: `extra_maps=[(yaml_path, ext), ...]` registers further maps
     (slots 1, 2, ...; `map` is slot 0) and `env_map=[slot per env]` assigns them; `set_env_maps()`
     re-assigns later.
+
+    Static obstacles (no reference counterpart): `obstacle_maps=[Obstacles | (base_slot, Obstacles), ...]` registers
+    map slots derived from slot 0 (or base_slot) with the shapes stamped into their distance tables on the device; they are numbered
+    after `extra_maps` and usable in `env_map`, and carry their base's track.  `set_obstacles(slot, obstacles)` re-draws one in
+    place between episodes.  Obstacles belong to a slot, not to an env: one padded table of device memory per slot.
 
     Track progress (no reference counterpart): `track=` (a Track, an [M][2] array or a csv path) puts a raceline on
     slot 0, `tracks={slot: track}` one per map slot.  The observation then also carries progress, progress_delta,
@@ -464,6 +484,15 @@ class F110VecEnv(object):
         for path, ext in kwargs.get('extra_maps', ()):
             self.sim.batch.add_map(path, ext)
             self.map_slots.append((path, ext))
+        # static obstacles: each entry registers a slot derived from slot 0 (or from the entry's base slot)
+        self.obstacle_slots = {}
+        for item in kwargs.get('obstacle_maps', ()):
+            base, ob = (int(item[0]), item[1]) if isinstance(item, tuple) and len(item) == 2 and isinstance(item[0], (int, np.integer)) else (0, item)
+            slot = self.sim.batch.add_obstacle_map(ob, base)
+            self.map_slots.append(self.map_slots[base])
+            self.obstacle_slots[slot] = base
+            if base in tracks and slot not in tracks:   # the same raceline (one Track object) on the derived slot
+                tracks[base] = tracks[slot] = Track.coerce(tracks[base])
         if kwargs.get('env_map') is not None:
             self.set_env_maps(kwargs['env_map'])
         self.tracks = {int(slot): self.sim.set_track(Track.coerce(t), int(slot)) for slot, t in sorted(tracks.items())}
@@ -565,6 +594,11 @@ class F110VecEnv(object):
         """env_map [num_envs]: which registered track each env runs on (None: all on slot 0)"""
         self.sim.batch.set_env_maps(env_map)
         self.env_map = None if env_map is None else np.asarray(env_map, dtype=np.int32).copy()
+
+    def set_obstacles(self, slot, obstacles):
+        """re-stamp the derived slot `slot` (one of obstacle_maps=) with another Obstacles, in place: it applies from the next step
+        on, behind whatever step is in flight"""
+        self.sim.batch.set_obstacles(slot, obstacles)
 
     def device_views(self):
         v = self.sim.batch.device_views()

@@ -243,6 +243,10 @@ class ShardedVecEnv(object):
     def update_map(self, map_path, map_ext):
         self._each(lambda k, s: s.sim.set_map(map_path, map_ext))
 
+    def set_obstacles(self, slot, obstacles):
+        """F110VecEnv.set_obstacles on every shard (the slots are numbered alike on all of them)"""
+        self._each(lambda k, s: s.set_obstacles(slot, obstacles))
+
     def set_env_maps(self, env_map):
         ms = [None] * len(self.shards) if env_map is None else self._slices(np.asarray(env_map, dtype=np.int32))
         self._each(lambda k, s: s.set_env_maps(ms[k]))

@@ -98,6 +98,18 @@ class Track(object):
         """the points the reference's nearest_point_on_trajectory sees for this track: p_0 appended when closed"""
         return np.vstack([self.xy, self.xy[:1]]) if self.closed else self.xy
 
+    def point_at(self, s):
+        """arc lengths s [m] (a closed track wraps them into [0, L), an open one clips them to [0, L]) -> (xy [m][2], unit
+        tangent [m][2]) on the polyline.  Host work: what places obstacles per map slot (Obstacles.random_on_track)."""
+        s = np.asarray(s, dtype=np.float64).reshape(-1)
+        L = self.length
+        s = np.mod(s, L) if self.closed else np.clip(s, 0.0, L)
+        k = np.clip(np.searchsorted(self.cum, s, side='right') - 1, 0, self.num_segments - 1)
+        pts = self.points_closed()
+        a, d = pts[:-1], pts[1:] - pts[:-1]
+        t = np.clip((s - self.cum[k]) / self.seg_len[k], 0.0, 1.0)
+        return a[k] + t[:, None] * d[k], d[k] / self.seg_len[k][:, None]
+
     def wrap_ds(self, ds):
         """progress of one step wrapped into (-L/2, L/2] on a closed track (open: unchanged)"""
         ds = np.array(ds, dtype=np.float64, copy=True)

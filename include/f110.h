@@ -152,6 +152,60 @@ int f110_add_map_dt(f110_sim *h, const double *h_dt, int32_t height, int32_t wid
                     double origin_s, int32_t *slot);
 int f110_set_env_maps(f110_sim *h, const int32_t *h_env_map);
 
+/* Extension (obstacle avoidance): static obstacles stamped into a map slot ON THE DEVICE.  A DERIVED slot has its
+ * base slot's geometry and a padded table of its own; everything that reads a slot's table (the scan, the iTTC wall check, the
+ * reset sampler's clearance test, the rollout's clearance sample, the render's occupancy grid) sees the obstacles with no change
+ * of its own.  Obstacles are per SLOT, not per env: memory is one padded table per derived slot.
+ *
+ * An obstacle: (x, y) its centre in map (world) coordinates; (c, s) the cosine and sine of its yaw AS THE CALLER COMPUTED THEM
+ * (the device calls no trigonometric function here); a box has half extents half_length (along its yaw) and half_width, a disc
+ * the radius half_length (c, s, half_width are then ignored but must be finite, half_width >= 0).  At most F110_MAX_OBSTACLES per slot.
+ *
+ * Table cell (r, c) — row 0 at the bottom, as the table is indexed — is STAMPED when its centre lies in a shape; float64 in
+ * exactly this order, never contracted, with the slot's resolution res, origin (ox, oy) and origin cosine / sine (oc, os):
+ *   px = ((double)c + 0.5) * res,  py = ((double)r + 0.5) * res
+ *   wx = ox + (px * oc - py * os), wy = oy + (px * os + py * oc)
+ *   dx = wx - x,  dy = wy - y
+ *   box:  u = dx * c + dy * s,  v = -dx * s + dy * c,  stamped iff fabs(u) <= half_length && fabs(v) <= half_width
+ *   disc: stamped iff dx * dx + dy * dy <= half_length * half_length
+ * Parts of a shape outside the table are ignored.  The slot's table is
+ *   T'[r][c] = min(T_base[r][c], res * sqrt((double)d2[r][c])),
+ * d2 the exact squared Euclidean distance, in cells, to the nearest stamped cell; where nothing is stamped inside the table
+ * T' = T_base.  For a base that came from an image this equals the reference pipeline (flip, threshold, resolution *
+ * distance_transform_edt) run on the image with the stamped cells blacked out, bit for bit: the EDT of a union of occupied sets is
+ * the elementwise minimum of the EDTs, and res * sqrt is monotone.  The slot's out-of-bounds value is T'[H-1][W-1]; the border of
+ * its padded copy holds that value.
+ *
+ * f110_add_map_obstacles registers a new slot derived from base_slot (slot 0 or a slot of f110_add_map_*, not a derived slot;
+ * n = 0: a copy of the base; h_obs may then be NULL).  Same preconditions as f110_add_map_*: the padded layout and a map that fits
+ * it (and sides of at most 16384 cells, as f110_add_map_image asks).  Takes effect at the next f110_set_env_maps.
+ * f110_set_map_obstacles re-stamps a derived slot IN PLACE from its base (not from its previous contents): the slot's table keeps
+ * its allocation and address, scratch (a byte mask, the active columns' distances) grows with the map, never with the number of
+ * calls.  The update is ordered behind every step in flight (on either env block) and in front of the next one, so the caller
+ * needs no synchronisation of its own; the call returns once the new out-of-bounds value has been read back.  It refreshes that
+ * value in the handle's constants and in the device-side slot table of f110_set_env_maps, marks the slot's cached render occupancy
+ * grid stale (the next render rebuilds it) and leaves track data alone.
+ * Refused (an error code, a message, nothing launched or written): null arguments, a slot out of range, a derived slot as base,
+ * f110_set_map_obstacles on a slot that is not derived, n < 0 or n > F110_MAX_OBSTACLES, an unknown shape, a non-finite field, a
+ * negative half extent, a base whose shape no longer matches (slot 0 re-set to another map since).
+ * f110_get_slot_dt / f110_slot_shape: f110_get_map_dt / f110_map_shape for any slot (the row-major table out of its padded copy).
+ * f110_slot_table: the device address of the slot's table cell [0][0] and its row pitch in bytes (what the kernels read). */
+enum { F110_OBST_BOX = 0, F110_OBST_DISC = 1 };
+enum { F110_MAX_OBSTACLES = 256 };
+typedef struct f110_obstacle {
+    int32_t shape;      /* F110_OBST_BOX / F110_OBST_DISC */
+    int32_t reserved;   /* alignment; ignored */
+    double x, y;        /* centre, map coordinates */
+    double c, s;        /* cos(yaw), sin(yaw) */
+    double half_length; /* >= 0; a disc's radius */
+    double half_width;  /* >= 0 */
+} f110_obstacle;
+int f110_add_map_obstacles(f110_sim *h, int32_t base_slot, const f110_obstacle *h_obs, int32_t n, int32_t *slot);
+int f110_set_map_obstacles(f110_sim *h, int32_t slot, const f110_obstacle *h_obs, int32_t n);
+int f110_get_slot_dt(f110_sim *h, int32_t slot, double *h_dt_out); /* row-major [height][width] */
+int f110_slot_shape(f110_sim *h, int32_t slot, int32_t *height, int32_t *width);
+int f110_slot_table(f110_sim *h, int32_t slot, const double **d_table, int32_t *row_bytes);
+
 /* Simulator.update_params base_classes.py:514-534 (agent_idx<0: all slots) */
 int f110_set_params(f110_sim *h, int32_t agent_idx, const double *h_params18);
 /* Extension (domain randomisation over vehicle dynamics): one parameter set per AGENT, h_params
