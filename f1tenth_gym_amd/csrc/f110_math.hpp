@@ -511,6 +511,22 @@ F110_HD uint32_t mul24(uint32_t a, uint32_t b)
 #endif
 }
 
+// what march_padded does with every byte offset it is about to load from: nothing, unless a host test program defines it
+// to check the offset against the table it built (tests/host_harness/march_chain_main.hip)
+#ifndef F110_MARCH_OFFSET_HOOK
+#define F110_MARCH_OFFSET_HOOK(off) ((void)0)
+#endif
+
+// true when the condition holds in any active lane of the wave (host: in this one "lane")
+F110_HD bool any_lane(bool c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __ballot(c) != 0ull;
+#else
+    return c;
+#endif
+}
+
 // One table value.  (Rounds 1-4 also had a 4x4-tiled float64 layout and a 1-byte-code + exact-value-LUT layout behind this
 // function — bit-identical, measured slower, retired in round 5: DESIGN_HISTORY.md.  `lut` is that layout's parameter.)
 template <int LAYOUT>
@@ -653,9 +669,13 @@ F110_HD bool march_padded(const ScanConst &k, double ux, double uy, double cux, 
 {
     double total = d;
     int n = 1;
-    bool redo = false;
+    // The give-up decision is a per-lane range limit, not a flag: a flag that is live across the back edge and part of
+    // the loop condition is carried as lane masks (five scalar mask instructions per sample on gfx950, for a decision
+    // taken on one sample in 10^7).  lim = -1 ends the loop at its next test, after the same load, total and n as the
+    // flag did: the loop only goes on past a d > eps, so where it would go on total > 0 > lim.
+    double lim = k.max_range;
     const char *base = reinterpret_cast<const char *>(k.pad);
-    while ((d > k.eps) & (total <= k.max_range) & !redo) {
+    while ((d > k.eps) & (total <= lim)) {
         ux = fma(d, cux, ux);
         uy = fma(d, cuy, uy);
         const uint32_t wx = low_word(ux + kFixBig);
@@ -665,17 +685,25 @@ F110_HD bool march_padded(const ScanConst &k, double ux, double uy, double cux, 
             hit_c = (int)(wx >> kFixFracBits);
             hit_r = (int)(wy >> kFixFracBits);
         }
-        if (((wx & 0xffffu) == 0u) | ((wy & 0xffffu) == 0u)) {
+        // one compare for "either fraction is zero": the product of the two 16-bit fractions; and one wave-uniform
+        // branch around the rare block for the (usual) wave that has no such lane, instead of an exec save / restore
+        const bool edge = mul24(wx & 0xffffu, wy & 0xffffu) == 0u;
+        if (__builtin_expect(any_lane(edge), 0)) {
             // within 2^-17 of a cell boundary, where the word (rounded to nearest) may name the
-            // cell above: take the floor, and give the ray up if it is closer than kPadGuard
-            redo = (fabs(ux - rint(ux)) < kPadGuard) | (fabs(uy - rint(uy)) < kPadGuard);
+            // cell above: take the floor, and give the ray up if it is closer than kPadGuard.
+            // (Evaluated by every lane of such a wave and selected per lane: the selects keep the block free of a second,
+            // divergent branch.  With one sample in 30 000 per lane, above, that is at most one wave-sample in 470.)
+            const bool near = (fabs(ux - rint(ux)) < kPadGuard) | (fabs(uy - rint(uy)) < kPadGuard);
+            lim = (edge & near) ? -1.0 : lim;
             const int fc = (int)floor(ux), fr = (int)floor(uy);
-            off = mul24((uint32_t)fr, (uint32_t)k.pad_row_bytes) + ((uint32_t)fc << 3);
+            const uint32_t off_floor = mul24((uint32_t)fr, (uint32_t)k.pad_row_bytes) + ((uint32_t)fc << 3);
+            off = edge ? off_floor : off;
             if (WANT_CELL) {
-                hit_c = fc;
-                hit_r = fr;
+                hit_c = edge ? fc : hit_c;
+                hit_r = edge ? fr : hit_r;
             }
         }
+        F110_MARCH_OFFSET_HOOK(off);
         d = *reinterpret_cast<const double *>(base + off);
         total += d;
         ++n;
@@ -690,7 +718,7 @@ F110_HD bool march_padded(const ScanConst &k, double ux, double uy, double cux, 
     }
     lookups = n;
     range = (total > k.max_range) ? k.max_range : total;
-    return !(redo | (n > k.pad_max_samples));
+    return !((lim < 0.0) | (n > k.pad_max_samples));
 }
 
 // (Round 5 also had march_padded_spec here — the tail of a long ray two samples per memory round trip where the table value
