@@ -32,7 +32,8 @@ def stamp_mask(obstacles, H, W, res, origin):
         dx = wx - x
         dy = wy - y
         if int(shape) == DISC:
-            m |= dx * dx + dy * dy <= hl * hl
+            with np.errstate(over="ignore"):   # (a radius whose square is inf: inf <= inf is a hit by the rule)
+                m |= dx * dx + dy * dy <= hl * hl
         else:
             u = dx * c + dy * s
             v = -dx * s + dy * c
@@ -138,3 +139,234 @@ def example_track():
 def large_obstacles(seed=3):
     """a dozen obstacles from random_on_track on example_map's raceline"""
     return Obstacles.random_on_track(example_track(), 12, seed, lateral=0.35, min_gap=4.0, keep_clear=[(0.97, 0.03)])
+
+
+# ---- fixtures for the kernels' edges (tests/test_gpu_obstacles_edges.py; conditions held in tests/test_obstacles_host.py) ----
+# Every table is built like small_image(): a literal rule, no file.  Fixture = (name, image, resolution, origin, lists); a list is
+# (label, Obstacles, cols) with cols the promised count of columns that hold a stamped cell: an int, a (lo, hi) range or None.
+EDGE_RES = 0.25        # coarse: the padded copy's border (ceil(max_range / res) + 66 cells a side) stays small
+PAD_SLACK = 2 + 64     # padded_border_cells (f110_math.hpp)
+
+
+def pad_border(max_range, res):
+    """padded_border_cells: the width of the padded copy's border in cells"""
+    return int(np.ceil(max_range * (1.0 / res))) + PAD_SLACK
+
+
+def cell_xy(r, c, res, origin):
+    """world coordinates of a point given in (fractional) cell units of a table (small_cell_xy for any table)"""
+    ox, oy, yaw = origin
+    px, py = c * res, r * res
+    return ox + px * np.cos(yaw) - py * np.sin(yaw), oy + px * np.sin(yaw) + py * np.cos(yaw)
+
+
+def sparse_image(H, W, seed, blocks=3):
+    """uint8 [H][W] top row first: free but for a few occupied blocks and single cells drawn from default_rng(seed); table cell
+    (H-1, W-1) stays free, so the base's out-of-bounds value is not 0"""
+    rng = np.random.default_rng(seed)
+    free = np.ones((H, W), dtype=bool)
+    for _ in range(blocks):
+        r, c = int(rng.integers(0, H)), int(rng.integers(0, W))
+        free[r:r + int(rng.integers(1, 4)), c:c + int(rng.integers(1, 6))] = False
+    for _ in range(max(2, (H * W) // 4000)):
+        free[int(rng.integers(0, H)), int(rng.integers(0, W))] = False
+    free[0, 0] = False
+    free[H - 1, W - 1] = True
+    if H * W == 1:
+        free[0, 0] = True
+    return np.ascontiguousarray(np.flipud(np.where(free, 255, 0).astype(np.uint8)))
+
+
+def _shapes(res, origin, boxes=(), discs=()):
+    """boxes (r, c, yaw relative to the table's rows, length, width) and discs (r, c, radius), centres in cell units, sizes in metres"""
+    ob = Obstacles()
+    if boxes:
+        ob = ob + Obstacles.boxes(np.array([cell_xy(b[0], b[1], res, origin) for b in boxes]), [b[2] + origin[2] for b in boxes],
+                                  [b[3] for b in boxes], [b[4] for b in boxes])
+    if discs:
+        ob = ob + Obstacles.discs(np.array([cell_xy(d[0], d[1], res, origin) for d in discs]), [d[2] for d in discs])
+    return ob
+
+
+def _bar(H, W, res, c0=None, c1=None):
+    """a thin box along the table's rows whose stamp is one cell high: the cells of row H // 2 in columns [c0, c1) (default: every
+    column).  Its axis lies 0.1 cell below that row's centres and it is 0.6 cell wide; its ends lie 0.3 cell past a cell centre."""
+    c0, c1 = 0 if c0 is None else c0, W if c1 is None else c1
+    return (H // 2 + 0.4, 0.5 * (c0 + c1), 0.0, (c1 - c0 - 0.4) * res, 0.6 * res)
+
+
+@functools.lru_cache(maxsize=None)
+def bar_fixture(W, H=40):
+    """wide (W = 4200: three chunks of k_obst_rows, 17 strides of k_obst_corner, 66 workgroups of k_obst_columns) and the chunk
+    boundary (W = 2048, 2049): the bar stamps a cell in every column; a few discs besides.  lists: bar + discs, discs only"""
+    res, origin = EDGE_RES, (-3.1, 2.2, 0.0)
+    discs = [(7.3, 0.07 * W + 0.6, 0.81), (31.8, 0.52 * W + 0.2, 1.13), (H - 2.4, W - 3.7, 0.66), (3.6, 0.93 * W + 0.4, 0.57)]
+    both = _shapes(res, origin, [_bar(H, W, res)], discs)
+    only = _shapes(res, origin, (), discs)
+    return ("bar%d" % W, sparse_image(H, W, 100 + W), res, origin, [("bar and discs", both, W), ("discs only", only, (8, 64))])
+
+
+@functools.lru_cache(maxsize=None)
+def mid_fixture():
+    """30 x 1500: between 300 and 1500 stamped columns and free ones besides: one trip of the chunk loop with n < kObstChunk, six
+    strides of the corner reduction; the turned box leaves columns of its cell box unstamped (kEdtInf in every row)"""
+    H, W, res, origin = 30, 1500, EDGE_RES, (1.7, -0.4, 0.0)
+    boxes = [_bar(H, W, res, 200, 900), (12.3, 1204.6, 0.7, 6.3, 0.9), (25.2, 1420.4, -0.3, 3.1, 1.3)]
+    discs = [(4.4, 77.7, 0.93), (21.6, 1010.3, 1.21), (H - 0.7, W - 9.2, 0.77)]
+    return ("mid", sparse_image(H, W, 7), res, origin, [("mid", _shapes(res, origin, boxes, discs), (300, 1500))])
+
+
+@functools.lru_cache(maxsize=None)
+def tall_fixture():
+    """2300 x 48: obstacles near row 0 and near row H - 1 only, the base's occupied cells near the middle rows: both sweeps of
+    k_obst_columns carry g into the thousands before the base takes over"""
+    H, W, res, origin = 2300, 48, EDGE_RES, (0.6, -1.9, 0.0)
+    free = np.ones((H, W), dtype=bool)
+    free[1148:1153, 0:7] = False
+    free[1171, 40] = False
+    img = np.ascontiguousarray(np.flipud(np.where(free, 255, 0).astype(np.uint8)))
+    boxes = [(2.7, 11.4, 0.5, 1.3, 0.7), (H - 3.4, 35.6, -0.4, 1.7, 0.9)]
+    discs = [(1.2, 40.3, 0.41), (H - 1.6, 6.7, 0.58)]
+    return ("tall", img, res, origin, [("tall", _shapes(res, origin, boxes, discs), (8, 40))])
+
+
+def edge_widths(max_range, res=EDGE_RES):
+    """table widths for a handle with this max_range: (pad_border + W) % 256 = 0, 1 and 255 — the interior ends on a workgroup's
+    last lane, on the next one's first, and one lane short — and a fourth whose interior spans at least three workgroups"""
+    b = pad_border(max_range, res)
+    ws = [40 + (t - b - 40) % 256 for t in (0, 1, 255)]
+    ws.append(ws[0] + 512)
+    assert [(b + w) % 256 for w in ws] == [0, 1, 255, 0] and (b + ws[3] - 1) // 256 - b // 256 >= 2
+    return ws
+
+
+EDGE_MAX_RANGES = (30.0, 47.5, 47.25)   # pad_border 186, 256 and 255: the interior starts mid-workgroup, on a first and on a last lane
+
+
+@functools.lru_cache(maxsize=None)
+def edge_fixture(W, H=24):
+    """24 rows, a turned origin: a box over column 0, a disc over column W - 1, one disc near (not on) the far corner, so the
+    border's value is neither 0 nor the base's"""
+    res, origin = EDGE_RES, (0.9, -2.3, 0.15)
+    boxes = [(9.3, 0.8, 0.4, 1.9, 0.8), (15.6, 0.5 * W + 0.3, -0.9, 2.3, 0.6)]
+    discs = [(5.4, W - 0.8, 0.83), (H - 3.3, W - 4.6, 0.52)]
+    return ("edge%d" % W, sparse_image(H, W, 300 + W, blocks=2), res, origin, [("edge", _shapes(res, origin, boxes, discs), (6, 40))])
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_fixtures():
+    """1 x 1, 1 x 300 and 300 x 1 under a turned origin; each long one with a list that stamps cells and one whose cell box reaches
+    the table but stamps nothing; the single cell with the one obstacle that stamps it"""
+    res, origin = EDGE_RES, (-0.4, 0.7, 0.3)
+    row = [("stamps", _shapes(res, origin, [(0.4, 211.3, 0.2, 2.1, 0.7)], [(0.6, 40.4, 0.9)]), (6, 30)),
+           ("stamps none", _shapes(res, origin, (), [(2.1, 150.5, 0.3 * res)]), 0)]
+    col = [("stamps", _shapes(res, origin, [(70.6, 0.3, 1.1, 1.9, 0.6)], [(250.2, 0.7, 0.8)]), 1),
+           ("stamps none", _shapes(res, origin, (), [(120.5, -1.2, 0.3 * res)]), 0)]
+    one = [("stamps", _shapes(res, origin, (), [(0.6, 0.4, 0.11)]), 1)]
+    return [("tiny1x1", sparse_image(1, 1, 1), res, origin, one), ("tiny1x300", sparse_image(1, 300, 2), res, origin, row),
+            ("tiny300x1", sparse_image(300, 1, 3), res, origin, col)]
+
+
+def nudged(ob, H, W, res, origin, margin=1e-7):
+    """the list with every shape whose boundary passes within `margin` of a cell centre moved by 1e-4 m in x until it does not"""
+    rows = np.array(ob.rows, copy=True)
+    for i in range(len(rows)):
+        while boundary_margin(Obstacles(rows[i:i + 1]), H, W, res, origin) <= margin:
+            rows[i, 1] += 1e-4
+    return Obstacles(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def small_lists():
+    """lists for the 96 x 128 fixture: the limit of 256 shapes (default_rng(256): boxes and discs all over the table and a little
+    beyond, many overlapping), its first 255, one of them, none; a box with both half extents 0; a disc of radius 1e200 (the rule
+    stamps every cell); shapes that all lie outside the table"""
+    H, W, res, origin = SMALL_H, SMALL_W, SMALL_RES, SMALL_ORIGIN
+    rng = np.random.default_rng(256)
+    r, c = rng.uniform(-4.0, H + 4.0, 256), rng.uniform(-4.0, W + 4.0, 256)
+    xy = np.array([small_cell_xy(a, b) for a, b in zip(r, c)])
+    full = Obstacles.boxes(xy[:150], rng.uniform(-np.pi, np.pi, 150), rng.uniform(0.05, 0.6, 150), rng.uniform(0.05, 0.4, 150))
+    full = nudged(full + Obstacles.discs(xy[150:], rng.uniform(0.02, 0.3, 106)), H, W, res, origin)
+    zero = Obstacles.boxes(np.array([small_cell_xy(40.3, 60.2)]), 0.3, 0.0, 0.0)
+    huge = Obstacles.discs(np.array([small_cell_xy(30.0, 50.0)]), 1e200)
+    outside = _shapes(res, origin, [(-9.3, 40.2, 0.3, 0.3, 0.2), (50.4, W + 11.6, 1.0, 0.4, 0.1)], [(H + 8.2, 30.3, 0.2), (-20.0, -20.0, 0.3)])
+    first = next(i for i in range(256) if stamp_mask(Obstacles(full.rows[i:i + 1]), H, W, res, origin).any())   # the first that stamps a cell
+    return [("256", full, None), ("255", Obstacles(full.rows[:255]), None), ("1", Obstacles(full.rows[first:first + 1]), None), ("0", Obstacles(), 0),
+            ("zero box", zero, 0), ("1e200 disc", huge, W), ("outside", outside, 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_fixtures():
+    """every new table with its lists, and the small table with the new lists"""
+    widths = sorted({w for mr in EDGE_MAX_RANGES for w in edge_widths(mr)})
+    return ([bar_fixture(4200), bar_fixture(2048), bar_fixture(2049), mid_fixture(), tall_fixture()] + [edge_fixture(w) for w in widths] + tiny_fixtures()
+            + [("small", small_image(), SMALL_RES, SMALL_ORIGIN, small_lists())])
+
+
+def stamped_columns(mask):
+    return int(mask.any(axis=0).sum())
+
+
+# ---- the rollout on a derived slot of the 96 x 128 fixture -------------------------------------------------------------------
+ROLL_K, ROLL_H, ROLL_REPEAT = 8, 10, 4
+ROLL_MARGIN = 0.12     # between list 0's out-of-bounds value (0.0: the far corner cell is stamped) and list 1's (0.7000000000000001)
+ROLL_LEAVERS = (13, 14, 15)   # the rows whose candidates leave the table
+
+
+def small_corridor_pose(phi, heading_offset=0.0):
+    """a pose on the small fixture's corridor at ring angle phi, heading along the ring (counter-clockwise in the table)"""
+    r, c = 48.0 + 26.3 * np.sin(phi), 64.0 + 38.0 * np.cos(phi)
+    x, y = small_cell_xy(r, c)
+    return [x, y, np.arctan2(26.3 * np.cos(phi), -38.0 * np.sin(phi)) + SMALL_ORIGIN[2] + heading_offset]
+
+
+@functools.lru_cache(maxsize=None)
+def rollout_case():
+    """(start [16][10], actions [K][H][2]): twelve cars round the corridor at 2 m/s with a full steering FIFO, one 12 cells in front
+    of list 0's first box, two in the free corner patch heading out of the table and one that starts outside it; eight candidates
+    (straight, both ways round, slow and fast) held ROLL_REPEAT steps per action"""
+    yaw = SMALL_ORIGIN[2]
+    poses = [small_corridor_pose(p) for p in np.linspace(0.1, 6.1, 12)]
+    for (r, c), th in (((38.0, 26.5), np.pi / 2), ((89.0, 119.0), np.pi / 4), ((92.0, 112.0), 0.1), ((99.0, 131.0), np.pi / 4)):
+        x, y = small_cell_xy(r, c)
+        poses.append([x, y, yaw + th])
+    start = np.zeros((len(poses), 10))
+    start[:, [0, 1, 4]] = np.array(poses)
+    start[:, 3] = 2.0
+    start[:, 9] = 2
+    actions = np.zeros((ROLL_K, ROLL_H, 2))
+    for k, (steer, speed) in enumerate([(0.0, 6.0), (0.0, 2.0), (0.25, 5.0), (-0.25, 5.0), (0.4, 3.0), (-0.4, 3.0), (0.1, 7.0), (-0.1, 7.0)]):
+        actions[k, :, 0], actions[k, :, 1] = steer, speed
+    for a in (start, actions):
+        a.setflags(write=False)
+    return start, actions
+
+
+@functools.lru_cache(maxsize=None)
+def rollout_table(which):
+    """the MODEL's table of the small fixture: 'base', or derived with small_obstacles(which)"""
+    base = table_from_bitmap(free_from_image(small_image()), SMALL_RES)
+    t = base if which == "base" else derived_table(base, small_obstacles(which), SMALL_RES, SMALL_ORIGIN)[0]
+    t.setflags(write=False)
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def rollout_flown(which):
+    """rollout_ref.fly of rollout_case() on a ScanOracle that holds rollout_table(which)"""
+    import rollout_ref
+    from oracle import orc
+    so = orc.ScanOracle(1080, 4.7)
+    so.set_map_dt(rollout_table(which), SMALL_RES, list(SMALL_ORIGIN))
+    start, actions = rollout_case()
+    params = np.tile(orc.params_vec(), (start.shape[0], 1))
+    return rollout_ref.fly(so, start, params, actions, False, ROLL_REPEAT, ROLL_MARGIN, 1)
+
+
+def rollout_left_table(which):
+    """bool [16][K]: the candidate's end position lies outside the table (the oracle's xy_2_rc answers (-1, -1))"""
+    from oracle import orc
+    so = orc.ScanOracle(1080, 4.7)
+    so.set_map_dt(rollout_table(which), SMALL_RES, list(SMALL_ORIGIN))
+    end = rollout_flown(which)[0]
+    return np.array([[so.xy_2_rc(e[0], e[1]) == (-1, -1) for e in row] for row in end])

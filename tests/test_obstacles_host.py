@@ -217,3 +217,110 @@ def test_harness_standalone_under_host_sanitizers(tmp_path):
                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     proc = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert proc.returncode == 0 and proc.stdout.startswith("ok: 1000 obstacles"), proc.stdout
+
+
+# ---- the fixtures for the kernels' edges (tests/test_gpu_obstacles_edges.py runs them on the device) ----------------------------
+def edge_cases():
+    """(fixture name, image, resolution, origin, list label, Obstacles, promised stamped-column count) of every new table and list"""
+    return [(name, img, res, origin, label, ob, cols) for name, img, res, origin, lists in ref.edge_fixtures() for label, ob, cols in lists]
+
+
+def promised(cols, n):
+    return True if cols is None else (n == cols if isinstance(cols, int) else cols[0] <= n <= cols[1])
+
+
+def test_edge_fixture_conditions():
+    """the margin of every list, the stamped-column counts the kernels' paths hang on, and what each table is there for"""
+    seen = {}
+    for name, img, res, origin, label, ob, cols in edge_cases():
+        H, W = img.shape
+        if label != "1e200 disc" and len(ob):   # (that disc's boundary is nowhere near the table)
+            assert ref.boundary_margin(ob, H, W, res, origin) > 1e-9, (name, label)
+        m = ref.stamp_mask(ob, H, W, res, origin)
+        n = ref.stamped_columns(m)
+        assert promised(cols, n), (name, label, n, cols)
+        seen[(name, label)] = (m, n)
+        free = ref.free_from_image(img)
+        assert free[H - 1, W - 1] and (H * W == 1 or not free.all()), name   # a base with occupied cells: the minimum with it matters
+    # three chunks of 2048 active columns, 17 strides of 256 and 66 workgroups of 64; exactly one chunk, and one more column
+    assert seen[("bar4200", "bar and discs")][1] == 4200 == 2 * 2048 + 104 and -(-4200 // 256) == 17 and -(-4200 // 64) == 66
+    assert seen[("bar2048", "bar and discs")][1] == 2048 and seen[("bar2049", "bar and discs")][1] == 2049
+    assert 300 <= seen[("mid", "mid")][1] <= 1500 and seen[("mid", "mid")][1] < 1500 - 300   # several strides, one short chunk, free columns left
+    m = seen[("tall", "tall")][0]
+    assert m[:6].any() and m[-6:].any() and not m[6:-6].any() and m.shape[0] > 2048
+    # the edge widths: computed from the border's formula for every max_range the device test constructs
+    borders = [ref.pad_border(mr, ref.EDGE_RES) for mr in ref.EDGE_MAX_RANGES]
+    assert sorted(b % 256 for b in borders) == [0, 186, 255]
+    for mr, b in zip(ref.EDGE_MAX_RANGES, borders):
+        ws = ref.edge_widths(mr)
+        assert [(b + w) % 256 for w in ws] == [0, 1, 255, 0] and (b + ws[3] - 1) // 256 - b // 256 >= 2
+        for w in ws:
+            m = seen[("edge%d" % w, "edge")][0]
+            assert m[:, 0].any() and m[:, w - 1].any() and not m[-1, -1], w
+    assert ref.edge_fixture(70)[3][2] != 0.0 and all(f[3][2] != 0.0 for f in ref.tiny_fixtures())
+    # the tiny tables and the lists on the small one
+    assert seen[("tiny1x1", "stamps")][0].all() and seen[("tiny1x300", "stamps")][1] > 0 and seen[("tiny300x1", "stamps")][0].sum() > 1
+    assert [len(ob) for _, ob, _ in ref.small_lists()[:4]] == [256, 255, 1, 0]
+    assert seen[("small", "256")][0].sum() > 3000 and seen[("small", "1")][0].any() and seen[("small", "1e200 disc")][0].all()
+    each = sum(int(ref.stamp_mask(Obstacles(ref.small_lists()[0][1].rows[i:i + 1]), ref.SMALL_H, ref.SMALL_W, ref.SMALL_RES, ref.SMALL_ORIGIN).sum()) for i in range(256))
+    assert each > 1.25 * seen[("small", "256")][0].sum()   # many overlap: the shapes' own cell counts add up to more than 1.25 times their union
+    for label in ("0", "zero box", "outside"):
+        assert not seen[("small", label)][0].any()
+    assert np.all(ref.small_lists()[4][1].rows[0, 5:] == 0.0)
+
+
+def test_edge_model_min_identity_equals_full_rebuild():
+    for name, img, res, origin, label, ob, cols in edge_cases():
+        base = ref.table_from_bitmap(ref.free_from_image(img), res)
+        t, m = ref.derived_table(base, ob, res, origin)
+        full = ref.table_from_bitmap(ref.free_from_image(ref.image_with_stamps(img, m)), res)
+        assert np.array_equal(t, full), (name, label)
+        assert (m.any() and not np.array_equal(t, base)) or (not m.any() and np.array_equal(t, base)), (name, label)
+    assert ref.derived_table(base, ref.small_lists()[5][1], res, origin)[0].max() == 0.0   # the 1e200 disc: all zeros, out-of-bounds value 0
+
+
+@needs_hipcc
+def test_harness_stamp_equals_model_mask_on_edge_fixtures(hh):
+    """the host instantiation's mask against the model's on every new table and list, and the ACTIVE column count Wa (the union of
+    the non-empty cell boxes' column ranges, as obstacles_stamp forms it): W on the bar tables and under the 1e200 disc (the `wild`
+    branch: the whole table), 0 for the empty list and for shapes that all lie outside, above 0 where a cell box reaches the table
+    and nothing is stamped"""
+    wa = {}
+    for name, img, res, origin, label, ob, cols in edge_cases():
+        H, W = img.shape
+        want = ref.stamp_mask(ob, H, W, res, origin)
+        got, boxes = harness_mask(hh, ob, H, W, res, origin)
+        assert np.array_equal(got.astype(bool), want), (name, label)
+        assert np.array_equal(harness_mask(hh, ob, H, W, res, origin, whole=True)[0], got), (name, label)
+        live = boxes[:len(ob)]
+        live = live[(live[:, 0] <= live[:, 1]) & (live[:, 2] <= live[:, 3])]
+        assert np.all(live[:, 0] >= 0) and np.all(live[:, 1] <= W - 1) and np.all(live[:, 2] >= 0) and np.all(live[:, 3] <= H - 1)
+        active = np.zeros(W, dtype=bool)
+        for c0, c1, r0, r1 in live:
+            active[c0:c1 + 1] = True
+        assert np.all(active[want.any(axis=0)]), (name, label)
+        wa[(name, label)] = int(active.sum())
+    assert (wa[("bar4200", "bar and discs")], wa[("bar2048", "bar and discs")], wa[("bar2049", "bar and discs")]) == (4200, 2048, 2049)
+    assert 256 < wa[("mid", "mid")] < 1500 and 0 < wa[("bar4200", "discs only")] < 256
+    assert wa[("small", "1e200 disc")] == ref.SMALL_W and wa[("small", "0")] == wa[("small", "outside")] == 0
+    assert wa[("small", "zero box")] > 0 and wa[("tiny1x300", "stamps none")] > 0 and wa[("tiny300x1", "stamps none")] == 1
+
+
+def test_rollout_case_on_the_derived_slot():
+    """the candidates of the rollout tests (tests/test_gpu_obstacles_edges.py), on the model alone: none comes within 1e-9 m of the
+    margin; some die in list 0's shapes, some pass where list 1 has one, and those that leave the table die with list 0 (whose
+    out-of-bounds value is 0.0) and survive with list 1 (0.7000000000000001)"""
+    assert ref.rollout_table(0)[-1, -1] == 0.0 and ref.rollout_table(1)[-1, -1] == 0.7000000000000001 == ref.rollout_table("base")[-1, -1]
+    assert 0.0 < ref.ROLL_MARGIN < 0.7
+    steps = ref.ROLL_H * ref.ROLL_REPEAT
+    alive = {w: ref.rollout_flown(w)[1] for w in ("base", 0, 1)}
+    for w in ("base", 0, 1):
+        assert np.all(ref.rollout_flown(w)[4] >= 1e-9), w                      # the model leaves out no candidate
+    corridor = np.arange(13)
+    assert np.count_nonzero(alive[0][corridor] < alive["base"][corridor]) >= 16     # die in one of list 0's shapes
+    assert np.count_nonzero((alive[1][corridor] < alive["base"][corridor]) & (alive[0][corridor] == alive["base"][corridor])) >= 8   # pass where list 1 has one
+    assert np.count_nonzero((alive[0][corridor] < alive["base"][corridor]) & (alive[1][corridor] == alive["base"][corridor])) >= 8
+    assert np.count_nonzero(alive["base"] == steps) >= 16 and np.count_nonzero(alive["base"][corridor] < steps) >= 16
+    out = ref.rollout_left_table(1)
+    assert np.count_nonzero(out) >= 20 and not out[corridor].any() and out[list(ref.ROLL_LEAVERS)].sum() == out.sum()
+    assert np.all(alive[1][out] == steps) and np.all(alive["base"][out] == steps) and np.all(alive[0][out] < steps)
