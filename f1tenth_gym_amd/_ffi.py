@@ -124,6 +124,17 @@ ROLL_NCHANNELS, ROLL_SHARED, ROLL_PER_AGENT, ROLL_FRAME_EGO, ROLL_FRAME_MAP = 10
 ROLL_MAX_K, ROLL_MAX_H, ROLL_MAX_REPEAT = 256, 64, 16
 
 
+class MppiSpec(C.Structure):
+    """struct f110_mppi"""
+    _fields_ = [("k", C.c_int32), ("horizon", C.c_int32), ("repeat", C.c_int32), ("shift", C.c_int32), ("margin", C.c_double),
+                ("sigma_steer", C.c_double), ("sigma_speed", C.c_double), ("steer_min", C.c_double), ("steer_max", C.c_double),
+                ("speed_min", C.c_double), ("speed_max", C.c_double), ("lambda_", C.c_double), ("w_dead", C.c_double),
+                ("w_clear", C.c_double), ("w_progress", C.c_double), ("w_lat", C.c_double), ("clear_ref", C.c_double), ("v_init", C.c_double)]
+
+
+MPPI_MAX_K, MPPI_MAX_H, MPPI_MAX_REPEAT = 256, 64, 16
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -269,6 +280,11 @@ PROTOTYPES = {
     "f110_neighbors_batch": (C.c_int, [C.c_void_p, C.POINTER(NeighborsSpec), C.c_int32, C.c_double, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
     "f110_rollout_device": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f110_rollout_batch": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.c_int32, _dp, _dp, _dp, C.c_int32, C.c_void_p, _dp, C.c_void_p, _dp]),
+    "f110_mppi_set": (C.c_int, [C.c_void_p, C.POINTER(MppiSpec), _i32p, C.c_int32, _u64p]),
+    "f110_mppi_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f110_mppi_get": (C.c_int, [C.c_void_p, _dp, _u64p]),
+    "f110_mppi_put": (C.c_int, [C.c_void_p, _dp, _u64p]),
+    "f110_mppi_batch": (C.c_int, [C.c_void_p, C.POINTER(MppiSpec), C.c_int32, _dp, _dp, _i32p, C.c_int32, _dp, _u64p, _dp, C.c_void_p, _dp, _dp, _dp]),
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
     "f110_obs_encode_device": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p, C.c_void_p]),
     "f110_obs_encode_batch": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), _dp, _dp, _i32p, C.c_int32, C.c_void_p]),

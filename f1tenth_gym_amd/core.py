@@ -1290,6 +1290,113 @@ class BatchSim(object):
         res = [out] + ([tr] if ro.traj else []) + ([rw] if raw else []) + ([trw] if trw is not None else [])
         return res[0] if len(res) == 1 else tuple(res)
 
+    # ------------------------------------------------------------------ MPPI planner (f110_mppi_*)
+    mppi_planner, mppi_agents = None, None
+
+    def set_mppi(self, spec, agents=None, seed=0, agent_base=0):
+        """arm the planner (mppi.Mppi or a dict of its settings) on `agents` (indices into the N agents, strictly ascending; None:
+        every agent).  Agent n draws from PCG64(SeedSequence(seed, spawn_key=(agent_base + n,))): agent_base is the handle's first
+        agent in a larger run (a shard), so that the run draws the same numbers however it is split.  Every nominal starts as
+        (0, v_init); nothing is launched.  The planner acts in mppi_device and in step_host(scripted=True).  Returns the Mppi."""
+        from .mppi import Mppi
+        from .reset_sampler import stream_words
+        mp = Mppi.coerce(spec)
+        a = np.arange(self.N, dtype=np.int32) if agents is None else np.ascontiguousarray(np.asarray(agents).reshape(-1), dtype=np.int32)
+        if int(agent_base) < 0:
+            raise ValueError("agent_base must be >= 0, got %d" % int(agent_base))
+        if a.size == 0 or a.min() < 0 or a.max() >= self.N or np.any(np.diff(a) <= 0):
+            raise ValueError("agents must be a strictly ascending list of 1 .. %d indices within 0 .. %d" % (self.N, self.N - 1))
+        lo = int(a[0])
+        words = np.ascontiguousarray(stream_words(seed, int(a[-1]) - lo + 1, int(agent_base) + lo)[a - lo], dtype=np.uint64)
+        sp = mp.spec()
+        check(_ffi.lib().f110_mppi_set(self._h, C.byref(sp), i32ptr(a), int(a.size), words.ctypes.data_as(_ffi._u64p)), self._h)
+        self.mppi_planner, self.mppi_agents = mp, a
+        return mp
+
+    def clear_mppi(self):
+        """disarm the planner and free its memory"""
+        check(_ffi.lib().f110_mppi_set(self._h, None, None, 0, None), self._h)
+        self.mppi_planner, self.mppi_agents = None, None
+
+    def mppi_device(self, d_actions, info=None):
+        """one planning call: the armed agents' rows of the device action buffer [N][2] (float64, the step's layout) are written
+        from their live state; the other rows are left alone.  info: a float32 DeviceArray [N][4] whose armed rows receive
+        mppi.INFO = (the lowest cost, the nominal's cost, the effective sample size, the index of the lowest cost).  Enqueued on
+        the handle's stream, per env block behind a two-block step (no host wait)."""
+        a = d_actions.ptr if isinstance(d_actions, DeviceArray) else int(d_actions)
+        ip = None
+        if info is not None:
+            if not isinstance(info, DeviceArray) or tuple(info.shape) != (self.N, 4) or info.dtype != np.float32:
+                raise ValueError("info must be a float32 DeviceArray of shape %s" % ((self.N, 4),))
+            ip = info.ptr
+        check(_ffi.lib().f110_mppi_device(self._h, a, ip), self._h)
+
+    def mppi(self, actions, info=False):
+        """mppi_device on a host action array [N][2]: a copy with the armed agents' rows replaced (and, with info, float32 [N][4],
+        zero in the other rows)"""
+        act = as_f64(actions, (self.N, 2))
+        with DeviceArray(self, (self.N, 2), np.float64) as d_act, DeviceArray(self, (self.N, 4), np.float32) as d_info:
+            d_act.upload(act)
+            d_info.upload(np.zeros((self.N, 4), dtype=np.float32))
+            self.mppi_device(d_act, d_info)
+            out, inf = d_act.download(), d_info.download()
+        return (out, inf) if info else out
+
+    def get_mppi_state(self):
+        """(nominal float64 [M][H][2], streams uint64 [M][4]) of the armed planner, in the armed list's order: what to keep next to
+        a state blob"""
+        mp = self.mppi_planner
+        if mp is None:
+            raise _ffi.F110LibraryError("no planner is armed (set_mppi)")
+        nom = np.zeros(mp.nominal_shape(self.mppi_agents.size))
+        words = np.zeros((self.mppi_agents.size, 4), dtype=np.uint64)
+        check(_ffi.lib().f110_mppi_get(self._h, dptr(nom), words.ctypes.data_as(_ffi._u64p)), self._h)
+        return nom, words
+
+    def set_mppi_state(self, nominal=None, streams=None):
+        """restore get_mppi_state's arrays, or seed the nominal (from a policy's prior, say): values must be finite and within
+        the planner's bounds.  None leaves that part alone."""
+        mp = self.mppi_planner
+        if mp is None:
+            raise _ffi.F110LibraryError("no planner is armed (set_mppi)")
+        m = self.mppi_agents.size
+        nom = None if nominal is None else as_f64(nominal, mp.nominal_shape(m))
+        words = None
+        if streams is not None:
+            words = np.ascontiguousarray(streams, dtype=np.uint64)
+            if words.shape != (m, 4):
+                raise ValueError("streams must be uint64 [%d][4]" % m)
+        check(_ffi.lib().f110_mppi_put(self._h, None if nom is None else dptr(nom), None if words is None else words.ctypes.data_as(_ffi._u64p)), self._h)
+
+    def mppi_rows(self, spec, start, nominal, streams, slot=0, params=None, fresh=None):
+        """unit form on host rows (the same kernels; the armed planner is not touched): start [m][10] as rollout_rows takes it,
+        nominal [m][H][2], streams uint64 [m][4], params [m][18] (None: this handle's row of agent slot 0), fresh int32 [m] (the
+        rows' step_count: 0 = a fresh row; None: none is).  Returns a dict: actions [m][2], info float32 [m][4], candidates
+        [m][K][H][2], cost [m][K], weight [m][K], nominal and streams after the call."""
+        from .mppi import Mppi
+        mp = Mppi.coerce(spec)
+        st = as_f64(start)
+        if st.ndim != 2 or st.shape[1] != 10:
+            raise ValueError("start must be [m][10] = state[7], FIFO newest, FIFO older, FIFO count")
+        m = st.shape[0]
+        nom = as_f64(nominal, mp.nominal_shape(m)).copy()
+        words = np.array(streams, dtype=np.uint64, order="C")
+        if words.shape != (m, 4):
+            raise ValueError("streams must be uint64 [%d][4]" % m)
+        pv = None if params is None else as_f64(params, (m, 18))
+        fr = None
+        if fresh is not None:
+            fr = np.ascontiguousarray(fresh, dtype=np.int32)
+            if fr.shape != (m,):
+                raise ValueError("fresh must be [m]")
+        act, inf = np.zeros((m, 2)), np.zeros((m, 4), dtype=np.float32)
+        cand, cost, wgt = np.zeros((m, mp.k, mp.horizon, 2)), np.zeros((m, mp.k)), np.zeros((m, mp.k))
+        sp = mp.spec()
+        check(_ffi.lib().f110_mppi_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), None if fr is None else i32ptr(fr),
+                                         m, dptr(nom), words.ctypes.data_as(_ffi._u64p), dptr(act), inf.ctypes.data, dptr(cand), dptr(cost),
+                                         dptr(wgt)), self._h)
+        return dict(actions=act, info=inf, candidates=cand, cost=cost, weight=wgt, nominal=nom, streams=words)
+
     # ------------------------------------------------------------------ rendering (f110_render_device, DESIGN §6c)
     def render_device(self, agents=None, width=64, height=64, view='ego', m_per_px=0.05, center=(0.0, 0.0), angle=0.0,
                       fwd_offset=0.0, layers=('map', 'cars'), car_size=None, rgb=False, palette=None, out=None):

@@ -228,6 +228,21 @@ struct f110_sim {
     GapSpec *d_gap_specs = nullptr;
     int32_t *d_gap_assign = nullptr;
     int gap_specs = 0, gap_max_w = 0;
+    std::vector<int32_t> gap_assign_host;   // the armed assignment (empty while disarmed): what f110_mppi_set checks its agents against
+    // MPPI planner (f110_mppi_set): m == 0: disarmed.  The nominal sequences and the streams are the planner's own memory.
+    struct Mppi {
+        MppiSpec sp{};
+        int m = 0;
+        std::vector<int32_t> agents;     // the armed list, ascending
+        int32_t *d_agents = nullptr;     // [m]
+        MppiSpec *d_spec = nullptr;      // sp, for the kernels
+        double *d_nominal = nullptr;     // [m][H][2]
+        uint64_t *d_streams = nullptr;   // [m][4]
+        double *d_V = nullptr;           // [m][K][H][2] the candidates of the last call
+        double *d_cost = nullptr;        // [m][K]
+        double *d_end = nullptr;         // [m][K][2] (only with a track weight)
+    } mppi;
+    U128 *d_mppi_jump = nullptr;         // [2][kMppiJumps] the candidates' jump constants (from the first arming on)
     // rendering (f110_render_device): slot 0's occupancy grid, the slot table as last uploaded, per-frame / per-agent records
     uint8_t *d_occ0 = nullptr;
     std::vector<RenderSlot> render_slots;
@@ -346,6 +361,10 @@ static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &
 constexpr int kMaxEnvBlocks = 16;
 struct EnvBlock { hipStream_t stream; int e0, count; };   // envs [e0, e0 + count) on `stream`
 static void gap_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions);   // (below, with the controllers)
+static int mppi_ready(f110_sim *h);                                                   // (below, with the planner)
+static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, float *d_info);
+static int mppi_upload_tracks(f110_sim *h);
+static void mppi_free(f110_sim *h);
 struct EnvBlocks {
     EnvBlock b[kMaxEnvBlocks];
     int n = 0;
@@ -1004,6 +1023,8 @@ void f110_destroy(f110_sim *h)
     }
     if (h->d_gap_specs) (void)hipFree(h->d_gap_specs);
     if (h->d_gap_assign) (void)hipFree(h->d_gap_assign);
+    mppi_free(h);
+    if (h->d_mppi_jump) (void)hipFree(h->d_mppi_jump);
     {
         void *rp[] = {h->d_occ0, h->d_render_slots, h->d_render_frames, h->d_render_cars, h->d_render_agents, h->d_render_stage};
         for (void *p : rp)
@@ -2399,7 +2420,9 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
                      out->checkpoint_done || out->done || (flags & F110_STEP_AUTO_RESET)))
         return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
     const bool scripted = (flags & F110_STEP_SCRIPTED) != 0;
-    if (scripted && h->gap_specs == 0) return fail(h, F110_ERR_STATE, "f110_step_host: F110_STEP_SCRIPTED without controllers (f110_controllers_set)");
+    if (scripted && h->gap_specs == 0 && h->mppi.m == 0)
+        return fail(h, F110_ERR_STATE, "f110_step_host: F110_STEP_SCRIPTED without controllers (f110_controllers_set) or a planner (f110_mppi_set)");
+    if (scripted && h->mppi.m > 0) TRY(mppi_ready(h));
     ENTER(h);
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
     // scripted cars: the actions always go through the staging buffer, where the controllers overwrite their agents' rows
@@ -2462,7 +2485,11 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     else if (!tiny)                  // (k_step_tiny gets the actions as kernel arguments)
         HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
     if (scripted) {   // the scans are the last step's, the staged rows of scripted agents are replaced, external rows stay
-        gap_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions);
+        if (h->gap_specs > 0) gap_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions);
+        if (h->mppi.m > 0) {   // the planner behind the controllers: its agents' rows, from the live state
+            TRY(mppi_upload_tracks(h));
+            TRY(mppi_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions, nullptr));
+        }
         HIPCHK(h, hipGetLastError());
     }
     const int A = h->cfg.num_agents;
@@ -4104,6 +4131,7 @@ int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_
     if (n_specs == 0 && !specs && !h_assign) {   // disarm
         ENTER(h);
         h->gap_specs = 0;
+        h->gap_assign_host.clear();
         return F110_OK;
     }
     if (!specs || !h_assign || n_specs < 1 || n_specs > F110_GAP_MAX_SPECS)
@@ -4117,6 +4145,8 @@ int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_
     const size_t N = (size_t)h->N;
     for (size_t i = 0; i < N; ++i)
         if (h_assign[i] < -1 || h_assign[i] >= n_specs) return fail(h, F110_ERR_INVALID, "controllers: assignment[%zu] = %d is outside -1..%d", i, h_assign[i], n_specs - 1);
+    for (int32_t n : h->mppi.agents)
+        if (h_assign[n] != -1) return fail(h, F110_ERR_INVALID, "controllers: agent %d is driven by the armed planner (f110_mppi_set)", n);
     ENTER(h);
     if (!h->d_gap_specs) TRY(dmalloc(h, &h->d_gap_specs, (size_t)kGapMaxSpecs));
     if (!h->d_gap_assign) TRY(dmalloc(h, &h->d_gap_assign, N));
@@ -4125,6 +4155,7 @@ int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (the sources are the caller's and this function's stack)
     h->gap_specs = n_specs;
     h->gap_max_w = max_w;
+    h->gap_assign_host.assign(h_assign, h_assign + N);
     return F110_OK;
 }
 
@@ -5434,6 +5465,335 @@ int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, cons
     if (h_raw) TRY(sc.down(h_raw, draw, cands * F110_ROLL_NCHANNELS));
     if (dtraj) TRY(sc.down(h_traj, dtraj, steps * 4));
     if (dtraw) TRY(sc.down(h_traj_raw, dtraw, steps * 4));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- MPPI planner (f110_mppi_*, include/f110.h) -------------------------------------------------------------------------------------
+// the spec's refusals; on success the kernels' spec
+static int mppi_check_spec(f110_sim *h, const f110_mppi *p, MppiSpec &o)
+{
+    if (!p) return fail(h, F110_ERR_INVALID, "mppi: null spec");
+    if (p->k < 1 || p->k > F110_MPPI_MAX_K) return fail(h, F110_ERR_INVALID, "mppi: k = %d is outside 1..%d", p->k, (int)F110_MPPI_MAX_K);
+    if (p->horizon < 1 || p->horizon > F110_MPPI_MAX_H) return fail(h, F110_ERR_INVALID, "mppi: horizon = %d is outside 1..%d", p->horizon, (int)F110_MPPI_MAX_H);
+    if (p->repeat < 1 || p->repeat > F110_MPPI_MAX_REPEAT) return fail(h, F110_ERR_INVALID, "mppi: repeat = %d is outside 1..%d", p->repeat, (int)F110_MPPI_MAX_REPEAT);
+    if (p->shift != 0 && p->shift != 1) return fail(h, F110_ERR_INVALID, "mppi: shift = %d must be 0 or 1", p->shift);
+    if (p->margin != p->margin) return fail(h, F110_ERR_INVALID, "mppi: margin is NaN");
+    const double d[] = {p->sigma_steer, p->sigma_speed, p->steer_min, p->steer_max, p->speed_min, p->speed_max, p->lambda,
+                        p->w_dead, p->w_clear, p->w_progress, p->w_lat, p->clear_ref, p->v_init};
+    for (double x : d)
+        if (!std::isfinite(x)) return fail(h, F110_ERR_INVALID, "mppi: every setting but the margin must be finite");
+    if (p->sigma_steer < 0 || p->sigma_speed < 0) return fail(h, F110_ERR_INVALID, "mppi: sigma_steer and sigma_speed must be >= 0");
+    if (p->steer_min > p->steer_max || p->speed_min > p->speed_max) return fail(h, F110_ERR_INVALID, "mppi: steer_min exceeds steer_max or speed_min exceeds speed_max");
+    if (!(p->lambda > 0)) return fail(h, F110_ERR_INVALID, "mppi: lambda must be > 0");
+    if (p->w_dead < 0 || p->w_clear < 0 || p->w_progress < 0 || p->w_lat < 0) return fail(h, F110_ERR_INVALID, "mppi: the weights must be >= 0");
+    if (p->v_init < p->speed_min || p->v_init > p->speed_max) return fail(h, F110_ERR_INVALID, "mppi: v_init is outside [speed_min, speed_max]");
+    o = MppiSpec{};
+    o.K = p->k, o.H = p->horizon, o.repeat = p->repeat, o.shift = p->shift;
+    o.margin = p->margin, o.sigma_steer = p->sigma_steer, o.sigma_speed = p->sigma_speed;
+    o.steer_min = p->steer_min, o.steer_max = p->steer_max, o.speed_min = p->speed_min, o.speed_max = p->speed_max, o.lambda = p->lambda;
+    o.w_dead = p->w_dead, o.w_clear = p->w_clear, o.w_progress = p->w_progress, o.w_lat = p->w_lat, o.clear_ref = p->clear_ref, o.v_init = p->v_init;
+    return F110_OK;
+}
+
+static void mppi_free(f110_sim::Mppi &p)
+{
+    void *ptrs[] = {p.d_agents, p.d_spec, p.d_nominal, p.d_streams, p.d_V, p.d_cost, p.d_end};
+    for (void *q : ptrs)
+        if (q) (void)hipFree(q);   // (hipFree waits for the calls in flight that read it)
+    p = f110_sim::Mppi{};
+}
+
+static void mppi_free(f110_sim *h) { mppi_free(h->mppi); }
+
+// the candidates' jump constants in device memory
+static int mppi_jump_ensure(f110_sim *h)
+{
+    if (h->d_mppi_jump) return F110_OK;
+    std::vector<U128> t(2 * (size_t)kMppiJumps);
+    mppi_jump_table(t.data(), t.data() + kMppiJumps);
+    TRY(dmalloc(h, &h->d_mppi_jump, t.size()));
+    HIPCHK(h, hipMemcpy(h->d_mppi_jump, t.data(), t.size() * sizeof(U128), hipMemcpyHostToDevice));
+    return F110_OK;
+}
+
+// the tracks the armed planner's projection reads (nothing to do without a track weight)
+static int mppi_upload_tracks(f110_sim *h)
+{
+    if (h->mppi.m > 0 && mppi_needs_track(h->mppi.sp)) TRY(track_upload(h));
+    return F110_OK;
+}
+
+// can the armed planner run?  The refusals of a call, nothing launched.
+static int mppi_ready(f110_sim *h)
+{
+    const f110_sim::Mppi &p = h->mppi;
+    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
+    if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
+    if (!mppi_needs_track(p.sp)) return F110_OK;
+    if (!h->multi_map) {
+        if (!track_has(h, 0)) return fail(h, F110_ERR_STATE, "mppi: w_progress or w_lat is set, but map slot 0 has no track (f110_track_set)");
+        return F110_OK;
+    }
+    const int A = h->cfg.num_agents;
+    int last = -1;
+    for (int32_t n : p.agents) {
+        const int e = n / A;
+        if (e == last) continue;
+        last = e;
+        const int32_t slot = h->env_map_host[e];
+        if (!track_has(h, slot)) return fail(h, F110_ERR_STATE, "mppi: w_progress or w_lat is set, but map slot %d has no track (f110_track_set)", slot);
+    }
+    return F110_OK;
+}
+
+// armed indices [j.i0, j.i0 + j.count): the candidates, (track) the projections, the update, one behind the other on `st`
+static void mppi_launch(const MppiJob &j, hipStream_t st)
+{
+    if (j.count <= 0) return;
+    const size_t lanes = (size_t)j.count * j.sp.K;
+    const dim3 block(256);
+    if (j.sp.K % 64 == 0) hipLaunchKernelGGL((k_mppi_roll<true>), grid1d(lanes, 256), block, 0, st, j);
+    else hipLaunchKernelGGL((k_mppi_roll<false>), grid1d(lanes, 256), block, 0, st, j);
+    if (j.end_xy) hipLaunchKernelGGL(k_mppi_track, grid1d(lanes * kTrackLanes, 256), block, 0, st, j);
+    const int gs = mppi_group_lanes(j.sp.K, j.sp.H);
+    hipLaunchKernelGGL(k_mppi_update, grid1d((size_t)j.count, 256 / gs), block, 0, st, j, gs);
+}
+
+// what every job of this handle shares: the step's constants and the generator's tables
+static void mppi_job_common(f110_sim *h, MppiJob &j)
+{
+    j.integrator = h->dev.integrator;
+    j.time_step = h->dev.time_step;
+    j.lidar_dist = h->dev.lidar_dist;
+    j.zk = h->d_zig_k;
+    j.zw = h->d_zig_w;
+    j.zf = h->d_zig_f;
+    j.jump_a = h->d_mppi_jump;
+    j.jump_g = h->d_mppi_jump + kMppiJumps;
+}
+
+// the armed planner over the agents of one env block: the ascending list is split at the block's bounds
+static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, float *d_info)
+{
+    const f110_sim::Mppi &p = h->mppi;
+    const int A = h->cfg.num_agents;
+    const bool track = mppi_needs_track(p.sp);
+    MppiJob j{};
+    j.maps = h->multi_map ? h->d_maps_full : cold_consts(h);
+    if (!j.maps) return fail(h, F110_ERR_HIP, "mppi: constant upload failed");
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.tracks = track ? h->d_tracks : nullptr;
+    j.unit_slot = -1;
+    j.A = A;
+    j.N = h->N;
+    j.params_per_agent = h->dev.params_per_agent;
+    j.agents = p.d_agents;
+    j.state = h->dev.state;
+    j.steer_buf = h->dev.steer_buf;
+    j.buf_cnt = h->dev.buf_cnt;
+    j.step_count = h->dev.step_count;
+    j.params = h->dev.params;
+    mppi_job_common(h, j);
+    j.nominal = p.d_nominal;
+    j.streams = p.d_streams;
+    j.V = p.d_V;
+    j.cost = p.d_cost;
+    j.end_xy = track ? p.d_end : nullptr;
+    j.actions = d_actions;
+    j.info = d_info;
+    j.sp_dev = p.d_spec;
+    j.sp = p.sp;
+    const int32_t n0 = b.e0 * A, n1 = (b.e0 + b.count) * A;
+    j.i0 = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n0) - p.agents.begin());
+    j.count = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n1) - p.agents.begin()) - j.i0;
+    mppi_launch(j, b.stream);
+    return F110_OK;
+}
+
+int f110_mppi_set(f110_sim *h, const f110_mppi *spec, const int32_t *h_agents, int32_t m, const uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (!spec && !h_agents && m == 0 && !h_streams) {   // disarm
+        ENTER(h);
+        mppi_free(h);
+        return F110_OK;
+    }
+    if (!spec || !h_agents || !h_streams) return fail(h, F110_ERR_INVALID, "mppi: a spec, the agents and their streams, or NULL, NULL, 0, NULL");
+    MppiSpec sp;
+    TRY(mppi_check_spec(h, spec, sp));
+    if (m < 1 || m > h->N) return fail(h, F110_ERR_INVALID, "mppi: %d armed agents, but the handle has 1..%d", m, h->N);
+    for (int32_t i = 0; i < m; ++i) {
+        if (h_agents[i] < 0 || h_agents[i] >= h->N) return fail(h, F110_ERR_INVALID, "mppi: agents[%d] = %d is outside 0..%d", i, h_agents[i], h->N - 1);
+        if (i > 0 && h_agents[i] <= h_agents[i - 1]) return fail(h, F110_ERR_INVALID, "mppi: the agents are not strictly ascending at [%d]", i);
+        if (!h->gap_assign_host.empty() && h->gap_assign_host[h_agents[i]] != -1)
+            return fail(h, F110_ERR_INVALID, "mppi: agent %d has a follow-the-gap controller (f110_controllers_set)", h_agents[i]);
+    }
+    if ((size_t)m * sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "mppi: %d agents x %d candidates do not fit 31 bits", m, sp.K);
+    ENTER(h);
+    TRY(mppi_jump_ensure(h));
+    f110_sim::Mppi p;   // built aside: a failure below leaves the planner that is armed (if any) as it is
+    const size_t M = (size_t)m, seq = (size_t)sp.H * 2, cands = M * sp.K;
+    std::vector<double> nominal(M * seq);
+    for (size_t q = 0; q < nominal.size(); ++q) nominal[q] = (q & 1) ? sp.v_init : 0.0;
+    int rc = dmalloc(h, &p.d_agents, M);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_spec, 1);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_nominal, M * seq);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_streams, 4 * M);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_V, cands * seq);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_cost, cands);
+    if (rc == F110_OK && mppi_needs_track(sp)) rc = dmalloc(h, &p.d_end, 2 * cands);
+    if (rc == F110_OK && (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(p.d_spec, &sp, sizeof sp, hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(p.d_nominal, nominal.data(), nominal.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess))
+        rc = fail(h, F110_ERR_HIP, "mppi: the upload failed");
+    if (rc != F110_OK) {
+        mppi_free(p);
+        return rc;
+    }
+    p.sp = sp;
+    p.agents.assign(h_agents, h_agents + m);
+    p.m = m;
+    mppi_free(h);
+    h->mppi = std::move(p);
+    return F110_OK;
+}
+
+int f110_mppi_device(f110_sim *h, double *d_actions, float *d_info)
+{
+    if (!h || !d_actions) return fail(h, F110_ERR_INVALID, "mppi: null argument");
+    TRY(mppi_ready(h));
+    if (mppi_needs_track(h->mppi.sp) && (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size())) {
+        ENTER(h);
+        TRY(track_upload(h));
+    }
+    EnvBlocks w;   // behind a two-block step: each block's armed agents on the block's own stream (an agent reads and writes its own rows)
+    TRY(env_blocks_follow(h, w));
+    for (const EnvBlock &b : w) TRY(mppi_launch_armed(h, b, d_actions, d_info));
+    HIPCHK(h, hipGetLastError());
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_mppi_get(f110_sim *h, double *h_nominal, uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    const f110_sim::Mppi &p = h->mppi;
+    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t M = (size_t)p.m;
+    if (h_nominal) HIPCHK(h, hipMemcpy(h_nominal, p.d_nominal, M * p.sp.H * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_streams) HIPCHK(h, hipMemcpy(h_streams, p.d_streams, 4 * M * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return F110_OK;
+}
+
+// a caller's nominal: finite and within the spec's bounds
+static int mppi_check_nominal(f110_sim *h, const MppiSpec &sp, const double *nominal, size_t rows)
+{
+    for (size_t q = 0; q < rows * sp.H * 2; ++q) {
+        const double x = nominal[q], lo = (q & 1) ? sp.speed_min : sp.steer_min, hi = (q & 1) ? sp.speed_max : sp.steer_max;
+        if (!std::isfinite(x) || x < lo || x > hi)
+            return fail(h, F110_ERR_INVALID, "mppi: nominal[%zu][%zu][%d] = %g is not finite or outside [%g, %g]", q / (2 * (size_t)sp.H), q / 2 % sp.H, (int)(q & 1), x, lo, hi);
+    }
+    return F110_OK;
+}
+
+int f110_mppi_put(f110_sim *h, const double *h_nominal, const uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    const f110_sim::Mppi &p = h->mppi;
+    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
+    const size_t M = (size_t)p.m;
+    if (h_nominal) TRY(mppi_check_nominal(h, p.sp, h_nominal, M));
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h_nominal) HIPCHK(h, hipMemcpy(p.d_nominal, h_nominal, M * p.sp.H * 2 * sizeof(double), hipMemcpyHostToDevice));
+    if (h_streams) HIPCHK(h, hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return F110_OK;
+}
+
+int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const double *h_start, const double *h_params, const int32_t *h_fresh, int32_t m,
+                    double *h_nominal, uint64_t *h_streams, double *h_actions, float *h_info, double *h_cand, double *h_cost, double *h_weight)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    MppiJob j{};
+    TRY(mppi_check_spec(h, spec, j.sp));
+    if (m < 0 || (m > 0 && (!h_start || !h_nominal || !h_streams))) return fail(h, F110_ERR_INVALID, "mppi: bad argument");
+    if ((size_t)m * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "mppi: %d rows x %d candidates do not fit 31 bits", m, j.sp.K);
+    if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "mppi: map slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    const bool track = mppi_needs_track(j.sp);
+    if (track && !track_has(h, slot)) return fail(h, F110_ERR_STATE, "mppi: w_progress or w_lat is set, but map slot %d has no track (f110_track_set)", slot);
+    if (m == 0) return F110_OK;
+    const size_t M = (size_t)m, seq = (size_t)j.sp.H * 2, cands = M * j.sp.K;
+    TRY(mppi_check_nominal(h, j.sp, h_nominal, M));
+    std::vector<double> cols(9 * M);
+    std::vector<int32_t> cnt(M);
+    for (size_t r = 0; r < M; ++r) {
+        for (int c = 0; c < 9; ++c) cols[(size_t)c * M + r] = h_start[10 * r + c];
+        const double f = h_start[10 * r + 9];
+        if (!(f == 0.0 || f == 1.0 || f == 2.0)) return fail(h, F110_ERR_INVALID, "mppi: row %zu has a FIFO fill count of %g, not 0, 1 or 2", r, f);
+        cnt[r] = (int32_t)f;
+    }
+    ENTER(h);
+    TRY(mppi_jump_ensure(h));
+    if (track) TRY(track_upload(h));
+    ScanConst kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
+    Scratch sc(h);
+    double *dcols = nullptr, *dpar = nullptr, *dnom = nullptr, *dV = nullptr, *dcost = nullptr, *dend = nullptr, *dw = nullptr, *dact = nullptr;
+    int32_t *dcnt = nullptr, *dfresh = nullptr;
+    uint64_t *dstr = nullptr;
+    ScanConst *dk = nullptr;
+    MppiSpec *dspec = nullptr;
+    float *dinfo = nullptr;
+    TRY(sc.up(cols.data(), cols.size(), &dcols));
+    TRY(sc.up(cnt.data(), cnt.size(), &dcnt));
+    TRY(sc.up(&kc, 1, &dk));
+    if (h_params) TRY(sc.up(h_params, M * NPARAMS, &dpar));
+    if (h_fresh) TRY(sc.up(h_fresh, M, &dfresh));
+    TRY(sc.up(&j.sp, 1, &dspec));
+    TRY(sc.up((const double *)h_nominal, M * seq, &dnom));
+    TRY(sc.up((const uint64_t *)h_streams, 4 * M, &dstr));
+    TRY(sc.up<double>(nullptr, cands * seq, &dV));
+    TRY(sc.up<double>(nullptr, cands, &dcost));
+    TRY(sc.up<double>(nullptr, cands, &dw));
+    TRY(sc.up<double>(nullptr, 2 * M, &dact));
+    TRY(sc.up<float>(nullptr, 4 * M, &dinfo));
+    if (track) TRY(sc.up<double>(nullptr, 2 * cands, &dend));
+    j.maps = dk;
+    j.tracks = track ? h->d_tracks : nullptr;
+    j.unit_slot = slot;
+    j.A = 1;
+    j.i0 = 0;
+    j.count = m;
+    j.N = m;
+    j.params_per_agent = h_params ? 1 : 0;
+    j.state = dcols;
+    j.steer_buf = dcols + 7 * M;
+    j.buf_cnt = dcnt;
+    j.step_count = dfresh;
+    j.params = h_params ? dpar : h->d_params;
+    mppi_job_common(h, j);
+    j.nominal = dnom;
+    j.streams = dstr;
+    j.V = dV;
+    j.cost = dcost;
+    j.end_xy = dend;
+    j.weight = dw;
+    j.actions = dact;
+    j.info = dinfo;
+    j.sp_dev = dspec;
+    mppi_launch(j, h->stream);
+    HIPCHK(h, hipGetLastError());
+    TRY(sc.down(h_nominal, dnom, M * seq));
+    TRY(sc.down(h_streams, dstr, 4 * M));
+    if (h_actions) TRY(sc.down(h_actions, dact, 2 * M));
+    if (h_info) TRY(sc.down(h_info, dinfo, 4 * M));
+    if (h_cand) TRY(sc.down(h_cand, dV, cands * seq));
+    if (h_cost) TRY(sc.down(h_cost, dcost, cands));
+    if (h_weight) TRY(sc.down(h_weight, dw, cands));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }

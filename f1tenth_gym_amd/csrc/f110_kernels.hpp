@@ -4899,3 +4899,165 @@ __global__ void __launch_bounds__(256) k_rollout_track(RollJob j)
     if (sub != 0 || !live) return;
     roll_store_track(j.sp, roll_progress(s0, s1, td.closed, td.L), lat1, j.out + G * j.sp.D, j.raw ? j.raw + G * ROLL_NCHANNELS : nullptr);
 }
+
+// ---- MPPI planner (f110_mppi_*; include/f110.h states the rule, f110_math.hpp / f110_rng.hpp mppi_* the arithmetic) ----
+// k_mppi_roll: one lane per (armed index, candidate), candidate-minor, 256-lane workgroups over the flat index, as k_rollout.  A lane
+//  * jumps the agent's generator by k * 2^20 steps with entry k of the jump table (two 128-bit multiplies), draws its 2 H normals
+//    one after the other and writes its row of V [M][K][H][2]: a prologue, so that the generator's registers are dead inside
+//    roll_candidate's ~1900-instruction step loop, which reads the row back (H * 16 bytes, the lane's own);
+//  * rolls the row with roll_candidate as it is and leaves the cost: complete without a track pass, else its first two terms
+//    and the end position for k_mppi_track.
+//  UNI (K a multiple of 64): a wave lies inside one agent, the agent goes through readfirstlane and its loads are scalar.
+// k_mppi_track (only when w_progress or w_lat is non-zero): k_rollout_track's scheme through the armed list: 16 lanes per candidate
+//  project the agent's start and the candidate's end; lane 0 adds the two track terms to the cost.
+// k_mppi_update: a group of GS lanes per armed agent, 256 / GS agents per workgroup; GS is the power of two >= max(2 H, min(K, 64)),
+//  at least 16 — with K = 8, H = 8 a workgroup serves 16 agents instead of one.  The costs go into LDS; every lane walks them for
+//  the minimum and its first index (LDS broadcasts; the same walk in every lane, so no reduction order to argue about); exp is
+//  taken once per candidate; lanes t < 2 H walk k = 0 .. K - 1 over V[i][k][t] (16 H contiguous bytes per k: coalesced), each with
+//  its own numerator; eta and q are summed by every lane in the same ascending order.  Idle groups shadow the last agent through
+//  the barriers and store nothing.
+struct MppiJob {
+    const ScanConst *maps;
+    const int32_t *env_map;
+    const TrackDesc *tracks;
+    int32_t unit_slot, A;
+    int32_t i0, count, N, params_per_agent;   // armed indices [i0, i0 + count); columns of N entries
+    const int32_t *agents;       // [M] the armed list, or nullptr: armed index i is row i (the unit form)
+    const double *state;         // [7][N]
+    const double *steer_buf;     // [2][N]
+    const int32_t *buf_cnt;      // [N]
+    const int32_t *step_count;   // [N] or nullptr (no row is fresh)
+    const double *params;        // [A][18] or [N][18]
+    int32_t integrator, pad_;
+    double time_step, lidar_dist;
+    const uint64_t *zk;          // the ziggurat's tables
+    const double *zw, *zf;
+    const U128 *jump_a, *jump_g; // [kMppiJumps]
+    double *nominal;             // [M][H][2]
+    uint64_t *streams;           // [M][4]
+    double *V;                   // [M][K][H][2]
+    double *cost;                // [M][K]
+    double *end_xy;              // [M][K][2] or nullptr: the end positions for k_mppi_track
+    double *weight;              // [M][K] or nullptr (the unit form's output)
+    double *actions;             // [N][2]
+    float *info;                 // [N][4] or nullptr
+    const MppiSpec *sp_dev;      // sp in device memory: what k_mppi_roll's epilogue reads, so that the cost's settings are not held in
+                                 // SGPRs across the step loop (they were spilled there)
+    MppiSpec sp;
+};
+
+template <bool UNI>
+__global__ void __launch_bounds__(256) k_mppi_roll(MppiJob j)
+{
+    const int K = j.sp.K, H = j.sp.H;
+    const long long total = (long long)j.count * K;
+    const long long g = (long long)blockIdx.x * 256 + (int)threadIdx.x;
+    if (g >= total) return;
+    int a = (int)(g / K);
+    const int kk = (int)(g - (long long)a * K);
+    if (UNI) a = __builtin_amdgcn_readfirstlane(a);
+    const int i = j.i0 + a;
+    const int n = j.agents ? j.agents[i] : i;
+    const size_t N = (size_t)j.N;
+    const size_t G = (size_t)i * K + (size_t)kk;
+    double *row = j.V + G * H * 2;
+    {
+        const bool fresh = j.step_count && j.step_count[n] == 0;
+        const ZigTables zt = {j.zk, j.zw, j.zf};
+        mppi_sample_row(j.sp, j.nominal + (size_t)i * H * 2, fresh, kk, j.streams + 4 * (size_t)i, j.jump_a[kk], j.jump_g[kk], zt, row);
+    }
+    const VehicleParams vp = load_params(j.params + (size_t)(j.params_per_agent ? n : n % j.A) * NPARAMS);
+    RollCar car;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) car.st[c] = j.state[(size_t)c * N + n];
+    car.b0 = j.steer_buf[n];
+    car.b1 = j.steer_buf[N + n];
+    car.cnt = j.buf_cnt[n];
+    const ScanConst &k = j.maps[j.env_map ? j.env_map[n / j.A] : 0];
+    const RollSpec rs = mppi_roll_spec(j.sp);
+    int alive;
+    double min_clear;
+    RollFrame fr;
+    roll_candidate(rs, k, vp, j.time_step, j.integrator, j.lidar_dist, car, row, fr, alive, min_clear, RollEmitNone());
+    // The cost's settings come from the spec's copy in device memory, NOT from j.sp: read from the kernel's arguments they are
+    // loaded at entry and held in SGPRs across the step loop, and the spill slots of that gave <UNI = false> a private segment of
+    // 20 bytes (§6i rules scratch out).  Keep every use of the spec behind the loop on `sp`.
+    const MppiSpec &sp = *j.sp_dev;
+    if (j.end_xy) {
+        j.cost[G] = mppi_cost_map(sp, alive, min_clear);
+        j.end_xy[2 * G] = car.st[0];
+        j.end_xy[2 * G + 1] = car.st[1];
+    } else {
+        j.cost[G] = mppi_cost(sp, alive, min_clear, 0.0, 0.0);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_mppi_track(MppiJob j)
+{
+    const int K = j.sp.K;
+    const long long total = (long long)j.count * K;
+    const long long gid = ((long long)blockIdx.x * 256 + (int)threadIdx.x) / kTrackLanes;
+    const int sub = (int)threadIdx.x & (kTrackLanes - 1);
+    const bool live = gid < total;
+    const long long g = live ? gid : total - 1;   // idle groups shadow the last candidate: every lane takes part in every shuffle
+    const int i = j.i0 + (int)(g / K);
+    const int n = j.agents ? j.agents[i] : i;
+    const size_t G = (size_t)j.i0 * K + (size_t)g;
+    const TrackDesc td = j.tracks[j.unit_slot >= 0 ? j.unit_slot : (j.env_map ? j.env_map[n / j.A] : 0)];
+    int seg0, seg1;
+    double s0, lat0, s1, lat1;
+    roll_search16(td, j.state[n], j.state[(size_t)j.N + n], -1, sub, seg0, s0, lat0);
+    roll_search16(td, j.end_xy[2 * G], j.end_xy[2 * G + 1], seg0, sub, seg1, s1, lat1);
+    if (sub != 0 || !live) return;
+    j.cost[G] = mppi_cost_track(j.sp, j.cost[G], roll_progress(s0, s1, td.closed, td.L), lat1);
+}
+
+constexpr int kMppiLdsCosts = 1024;   // (256 / GS) * K at its largest: GS = 64, K = 256
+
+// the lanes per agent of k_mppi_update
+inline int mppi_group_lanes(int K, int H)
+{
+    const int need = 2 * H > (K < 64 ? K : 64) ? 2 * H : (K < 64 ? K : 64);
+    int gs = 16;
+    while (gs < need) gs <<= 1;
+    return gs;
+}
+
+__global__ void __launch_bounds__(256) k_mppi_update(MppiJob j, int GS)
+{
+    __shared__ double s_cost[kMppiLdsCosts], s_w[kMppiLdsCosts];
+    const int K = j.sp.K, H = j.sp.H;
+    const int per = 256 / GS, grp = (int)threadIdx.x / GS, t = (int)threadIdx.x - grp * GS;
+    const long long a_raw = (long long)blockIdx.x * per + grp;
+    const bool live = a_raw < j.count;
+    const int i = j.i0 + (int)(live ? a_raw : j.count - 1);
+    const int n = j.agents ? j.agents[i] : i;
+    double *sc = s_cost + grp * K, *sw = s_w + grp * K;
+    const double *cost = j.cost + (size_t)i * K;
+    for (int k = t; k < K; k += GS) sc[k] = cost[k];
+    __syncthreads();
+    double beta;
+    int best;
+    mppi_min(sc, K, beta, best);
+    for (int k = t; k < K; k += GS) {
+        const double w = mppi_weight(j.sp, sc[k], beta, k);
+        sw[k] = w;
+        if (j.weight && live) j.weight[(size_t)i * K + k] = w;
+    }
+    __syncthreads();
+    double eta, q;
+    mppi_norms(sw, K, eta, q);
+    if (t < 2 * H) {
+        const double u = mppi_blend(sw, j.V + (size_t)i * K * H * 2, K, H, t, eta);
+        if (live) {
+            mppi_store_nominal(j.sp, j.nominal + (size_t)i * H * 2, t, u);
+            if (t < 2) j.actions[2 * (size_t)n + t] = u;
+        }
+    }
+    if (t != 0 || !live) return;
+    if (j.info) mppi_info(beta, sc[0], eta, q, best, j.info + 4 * (size_t)n);
+    uint64_t *st = j.streams + 4 * (size_t)i;
+    const U128 s1 = pcg_jump(U128{st[0], st[1]}, U128{st[2], st[3]}, j.jump_a[kMppiJumps - 1], j.jump_g[kMppiJumps - 1]);
+    st[0] = s1.hi;
+    st[1] = s1.lo;
+}

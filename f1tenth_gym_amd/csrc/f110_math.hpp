@@ -1925,4 +1925,125 @@ F110_HD void obstacle_cell_box(const Obstacle &o, const ObstFrame &f, int H, int
     }
 }
 
+// ------------------------------------------------------------------ MPPI planner (include/f110.h, f110_mppi)
+// The planner's own arithmetic around roll_candidate: the clamp of a sampled action, the cost of a rolled candidate, the weights and
+// the weighted update.  One text for the kernels (k_mppi_*) and the host harness (tests/host_harness/mppi_harness.hip); the draws
+// themselves are f110_rng.hpp's (mppi_normal, mppi_sample_row), which builds on this header.
+enum { MPPI_MAX_K = 256, MPPI_MAX_H = 64, MPPI_MAX_REPEAT = 16 };
+
+struct MppiSpec {
+    int32_t K, H, repeat, shift;
+    double margin, sigma_steer, sigma_speed, steer_min, steer_max, speed_min, speed_max, lambda;
+    double w_dead, w_clear, w_progress, w_lat, clear_ref, v_init;
+};
+
+// the rollout's spec of a planner's candidates: per-agent rows of V, no output channels of its own
+F110_HD RollSpec mppi_roll_spec(const MppiSpec &s)
+{
+    RollSpec r{};
+    r.K = s.K;
+    r.H = s.H;
+    r.repeat = s.repeat;
+    r.layout = ROLL_PER_AGENT;
+    r.frame = ROLL_FRAME_WORLD;
+    r.margin = s.margin;
+    for (int b = 0; b < ROLL_NCHANNELS; ++b) r.scale[b] = 1.0;
+    return r;
+}
+
+F110_HD bool mppi_needs_track(const MppiSpec &s) { return s.w_progress != 0.0 || s.w_lat != 0.0; }
+
+F110_HD double mppi_clamp(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// the nominal a candidate is drawn around: the stored one, or (0, v_init) on a fresh row; c = 0 steer, 1 speed
+F110_HD double mppi_nominal(const MppiSpec &s, const double *U, bool fresh, int h, int c) { return fresh ? (c ? s.v_init : 0.0) : U[2 * h + c]; }
+
+// one action of candidate k >= 1 from its two draws
+F110_HD void mppi_perturb(const MppiSpec &s, double u_steer, double u_speed, double e_s, double e_v, double *v)
+{
+    v[0] = mppi_clamp(u_steer + s.sigma_steer * e_s, s.steer_min, s.steer_max);
+    v[1] = mppi_clamp(u_speed + s.sigma_speed * e_v, s.speed_min, s.speed_max);
+}
+
+// the cost of a rolled candidate, accumulated in the header's order.  The kernels take it in two parts where the projection is a
+// pass of its own (the rollout's lane leaves the first two terms, the projection's lane adds the track's); the operations and their
+// order are the same.  Without a track pass progress = end_lat = 0.0.
+F110_HD double mppi_cost_map(const MppiSpec &s, int alive, double min_clear)
+{
+    double c = s.w_dead * (double)(s.H * s.repeat - alive);
+    c = c + s.w_clear * (min_clear < s.clear_ref ? s.clear_ref - min_clear : 0.0);
+    return c;
+}
+
+F110_HD double mppi_cost_track(const MppiSpec &s, double c, double progress, double end_lat)
+{
+    c = c - s.w_progress * progress;
+    c = c + s.w_lat * fabs(end_lat);
+    return c != c ? INFINITY : c;
+}
+
+F110_HD double mppi_cost(const MppiSpec &s, int alive, double min_clear, double progress, double end_lat)
+{
+    return mppi_cost_track(s, mppi_cost_map(s, alive, min_clear), progress, end_lat);
+}
+
+// the minimum of the K costs (none is NaN) and its first index
+F110_HD void mppi_min(const double *cost, int K, double &beta, int &best)
+{
+    beta = cost[0];
+    best = 0;
+    for (int k = 1; k < K; ++k)
+        if (cost[k] < beta) {
+            beta = cost[k];
+            best = k;
+        }
+}
+
+F110_HD bool mppi_finite(double x) { return x - x == 0.0; }
+
+// candidate k's weight; a beta that is not finite leaves the nominal alone: w = (1, 0, ...)
+F110_HD double mppi_weight(const MppiSpec &s, double cost, double beta, int k)
+{
+    if (!mppi_finite(beta)) return k == 0 ? 1.0 : 0.0;
+    return exp(-(cost - beta) / s.lambda);
+}
+
+// eta = sum w, q = sum w * w over ascending k from 0.0
+F110_HD void mppi_norms(const double *w, int K, double &eta, double &q)
+{
+    eta = 0.0;
+    q = 0.0;
+    for (int k = 0; k < K; ++k) {
+        eta = eta + w[k];
+        q = q + w[k] * w[k];
+    }
+}
+
+// U'[t] for element t = 2 * h + c of the sequence: V is the agent's [K][H][2], the sum over ascending k from 0.0
+F110_HD double mppi_blend(const double *w, const double *V, int K, int H, int t, double eta)
+{
+    double num = 0.0;
+    for (int k = 0; k < K; ++k) num = num + w[k] * V[(size_t)k * 2 * H + t];
+    return num / eta;
+}
+
+// element t of U' into the stored nominal: in place, or moved one action ahead with the last action kept
+F110_HD void mppi_store_nominal(const MppiSpec &s, double *U, int t, double u)
+{
+    if (!s.shift) {
+        U[t] = u;
+        return;
+    }
+    if (t >= 2) U[t - 2] = u;
+    if (t >= 2 * s.H - 2) U[t] = u;
+}
+
+F110_HD void mppi_info(double beta, double c0, double eta, double q, int best, float *o)
+{
+    o[0] = (float)beta;
+    o[1] = (float)c0;
+    o[2] = (float)(eta * eta / q);
+    o[3] = (float)best;
+}
+
 }  // namespace f110

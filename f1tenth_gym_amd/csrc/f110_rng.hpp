@@ -389,14 +389,66 @@ F110_HD int nth_set_bit(uint64_t m, int n)
     return ctz_u64(m);
 }
 
+// the state n steps ahead, given (A_n, G_n): A_n * s + G_n * inc
+F110_HD U128 pcg_jump(U128 s, U128 inc, U128 a, U128 g) { return add128(mul128(a, s), mul128(g, inc)); }
+
 // the state `n` steps ahead
 F110_HD U128 pcg_advance(U128 s, U128 inc, const U128 *ja, const U128 *jg, int n)
 {
     while (n > 64) {
-        s = add128(mul128(ja[64], s), mul128(jg[64], inc));
+        s = pcg_jump(s, inc, ja[64], jg[64]);
         n -= 64;
     }
-    return add128(mul128(ja[n], s), mul128(jg[n], inc));
+    return pcg_jump(s, inc, ja[n], jg[n]);
+}
+
+// ---- the MPPI planner's draws (include/f110.h, f110_mppi) ----------------------------------------------------------------------
+// Generator.standard_normal() one draw after the other from one generator: what a candidate's lane does 2 H times
+F110_HD double mppi_normal(U128 &st, U128 inc, const ZigTables &t)
+{
+    for (;;) {
+        st = pcg_step(st, inc);
+        const ZigAttempt z = zig_attempt(pcg_output(st), st, inc, t);
+        for (int q = 1; q < z.len; ++q) st = pcg_step(st, inc);
+        if (z.emit) return z.val;
+    }
+}
+
+// PCG64.advance(n) for n = j * 2^kMppiJumpLog2, j = 0 .. 256, as (A_n, G_n): the state n steps ahead is A_n * s + G_n * inc
+constexpr int kMppiJumpLog2 = 20;
+constexpr int kMppiJumps = 257;   // entry 256 = 2^28 steps: where a call leaves the agent's generator
+
+inline void mppi_jump_table(U128 *a, U128 *g)
+{
+    U128 a1 = {kPcgMultHi, kPcgMultLo}, g1 = {0, 1};
+    for (int q = 0; q < kMppiJumpLog2; ++q) {   // A_2n = A_n * A_n, G_2n = G_n * (A_n + 1)
+        g1 = mul128(g1, add128(a1, U128{0, 1}));
+        a1 = mul128(a1, a1);
+    }
+    a[0] = {0, 1};
+    g[0] = {0, 0};
+    for (int j = 1; j < kMppiJumps; ++j) {      // A_(n+J) = A_n * A_J, G_(n+J) = G_n * A_J + G_J
+        a[j] = mul128(a[j - 1], a1);
+        g[j] = add128(mul128(g[j - 1], a1), g1);
+    }
+}
+
+// candidate k's row V[k][H][2] around the nominal U (fresh: (0, v_init)); stream = the agent's {state.hi, state.lo, inc.hi, inc.lo},
+// (ja, jg) = entry k of the jump table.  Candidate 0 is the nominal itself, without a draw.
+F110_HD void mppi_sample_row(const MppiSpec &s, const double *U, bool fresh, int k, const uint64_t *stream, U128 ja, U128 jg, const ZigTables &t,
+                             double *row)
+{
+    if (k == 0) {
+        for (int q = 0; q < 2 * s.H; ++q) row[q] = mppi_nominal(s, U, fresh, q >> 1, q & 1);
+        return;
+    }
+    const U128 inc = {stream[2], stream[3]};
+    U128 st = pcg_jump(U128{stream[0], stream[1]}, inc, ja, jg);
+    for (int h = 0; h < s.H; ++h) {
+        const double e_s = mppi_normal(st, inc, t);
+        const double e_v = mppi_normal(st, inc, t);
+        mppi_perturb(s, mppi_nominal(s, U, fresh, h, 0), mppi_nominal(s, U, fresh, h, 1), e_s, e_v, row + 2 * h);
+    }
 }
 
 }  // namespace f110

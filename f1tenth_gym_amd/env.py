@@ -17,6 +17,7 @@ import numpy as np
 from . import _ffi
 from .core import DEFAULT_PARAMS
 from .gap_follower import coerce_scripted
+from .mppi import split_scripted
 from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
 from .sim import Integrator, Simulator
@@ -388,6 +389,10 @@ class F110VecEnv(object):
     step(actions) keeps its [E][A][2] shape: the rows of scripted cars are ignored and replaced on the device.  A scripted
     car takes the zero action on the first step of an episode (reset()'s own step, and the step after an in-step re-seat).
     It needs device_logic=True (ValueError otherwise).  Controllers hold no state: snapshots do not change.
+    An entry may instead be an Mppi, at most one per env object: every env's car `slot` then plans on the device from its
+    live state, behind the controllers, with the stream PCG64(SeedSequence(seed, spawn_key=(global agent index,))) of the env's
+    `seed`.  `planner=(slot, Mppi)` says the same next to the (assign, [controllers]) form.  The planner's nominal sequences and
+    stream positions are not part of snapshot() / restore(): keep env.sim.batch.get_mppi_state() next to a snapshot.
 
     Track preview (no reference counterpart): `track_preview=` (a TrackPreview or a dict of its settings) adds
     obs['track_preview'], float32 [E][A][P][D]: P stations of the raceline ahead of each car, in its own frame or the map's,
@@ -442,13 +447,25 @@ class F110VecEnv(object):
             self.obs_encoder.check_beams(kwargs.get('num_beams', 1080))
         self._encode = self.obs_encoder is not None and "encoded" in self.obs_fields
         self.scripted = None
-        if scripted is not None:
+        self.planner = None   # (slot, Mppi): every env's car `slot` plans
+        scripted, planner = split_scripted(scripted, kwargs.get('planner'))
+        if scripted is not None or planner is not None:
             if not self.device_logic:
-                raise ValueError("scripted= needs device_logic=True (any other loop arms env.sim.batch.set_controllers and calls "
-                                 "BatchSim.follow_gap_device on its device action buffer)")
+                raise ValueError("scripted= needs device_logic=True (any other loop arms env.sim.batch.set_controllers / set_mppi and calls "
+                                 "BatchSim.follow_gap_device / mppi_device on its device action buffer)")
+        if scripted is not None:
             self.scripted = coerce_scripted(scripted, self.num_envs, self.num_agents)
             for c in self.scripted[1]:
                 c.window(kwargs.get('num_beams', 1080))
+        if planner is not None:
+            slot, mp = planner
+            if not (0 <= slot < self.num_agents):
+                raise ValueError("scripted: slot %r is not one of the %d cars of an env" % (slot, self.num_agents))
+            if self.scripted is not None and np.any(self.scripted[0][:, slot] != -1):
+                raise ValueError("scripted: car %d has both a follow-the-gap controller and the planner" % slot)
+            if mp.needs_track and not tracks:
+                raise ValueError("the planner's w_progress and w_lat need a track (track= or tracks=)")
+            self.planner = (slot, mp)
         self.track_preview = None
         if track_preview is not None:
             self.track_preview = TrackPreview.coerce(track_preview)
@@ -519,6 +536,9 @@ class F110VecEnv(object):
             self._build_host_block()
             if self.scripted is not None:
                 b.set_controllers(*self.scripted)
+            if self.planner is not None:   # agent_base: this handle's first global agent (ShardedVecEnv), so a sharded run draws the same numbers
+                b.set_mppi(self.planner[1], np.arange(self.num_envs) * self.num_agents + self.planner[0], seed=self.seed,
+                           agent_base=int(kwargs.get('env_base', 0)) * self.num_agents)
 
     def _build_host_block(self):
         """the page-locked block f110_step_host fills, and the (obs, reward, done, info) tuple of views into it
@@ -696,7 +716,7 @@ class F110VecEnv(object):
         if self._encode or self.track_preview is not None or self.neighbors is not None:
             # one wait per step: the step enqueued without a wait, the encode / the preview / the neighbours and their copies into page-locked memory behind it
             b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
-                        scripted=self.scripted is not None)
+                        scripted=self.scripted is not None or self.planner is not None)
             if self._encode:
                 b.encode_obs_device(self.obs_encoder, self.encoded_stack, fill=self._enc_fill, pinned=self._enc_pinned)
                 self._enc_fill = False
@@ -708,7 +728,7 @@ class F110VecEnv(object):
                 b.sync()
         else:
             b.step_host(hb, None, auto_reset=self.auto_reset, sync=sync, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
-                        scripted=self.scripted is not None)
+                        scripted=self.scripted is not None or self.planner is not None)
         self.sim._steps_since_full_reset += 1
         if not sync:
             return None

@@ -101,6 +101,11 @@ class ShardedVecEnv(object):
             from .neighbors import Neighbors
             kwargs['neighbors'] = Neighbors.coerce(kwargs['neighbors'])
         scripted = kwargs.pop('scripted', None)      # scripted cars: the global assignment [E][A], sliced by shard; the controllers shared
+        from .mppi import split_scripted             # the planner: one for every shard; a shard's env_base gives its agents their global streams
+        scripted, planner = split_scripted(scripted, kwargs.pop('planner', None))
+        self.planner = planner
+        if planner is not None:
+            kwargs['planner'] = planner
         if scripted is not None:
             from .gap_follower import coerce_scripted
             scripted = coerce_scripted(scripted, E, self.num_agents)

@@ -330,8 +330,9 @@ typedef struct f110_host_block {
 #define F110_STEP_SCRIPTED 64       /* scripted cars (f110_controllers_set, below): h_actions is staged into device memory (as
                                        without F110_STEP_ACTIONS_MAPPED, which is ignored), the armed controllers overwrite their
                                        agents' rows there from the scans of the last step, and the step runs from that buffer.
-                                       The one-launch form of tiny batches does not apply.  F110_ERR_STATE with nothing armed.
-                                       Without the flag the call does not look at the controllers at all. */
+                                       An armed planner (f110_mppi_set, below) then writes its agents' rows behind them.
+                                       The one-launch form of tiny batches does not apply.  F110_ERR_STATE with neither kind
+                                       armed.  Without the flag the call looks at neither the controllers nor the planner. */
 int f110_step_host(f110_sim *h, const double *h_actions /* [N][2] */, const f110_host_block *out, int32_t flags);
 /* measurement aid: {calls, host microseconds spent enqueuing, host microseconds spent waiting} of the
  * f110_step_host calls since the last read (cleared by the read) */
@@ -819,7 +820,8 @@ typedef struct f110_gap_follower {
 } f110_gap_follower;
 /* arms the controllers: specs [n_specs], 1 <= n_specs <= F110_GAP_MAX_SPECS, and h_assign [N] int32: -1 = external (the agent's
  * action comes from the caller), else the index of the agent's spec (anything else: F110_ERR_INVALID, nothing changed).
- * NULL, 0, NULL disarms them.  Arming launches nothing and no step looks at it without F110_STEP_SCRIPTED. */
+ * NULL, 0, NULL disarms them.  Arming launches nothing and no step looks at it without F110_STEP_SCRIPTED.  An agent that the
+ * armed planner (f110_mppi_set) drives cannot have a controller too: F110_ERR_INVALID, nothing changed. */
 int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_specs, const int32_t *h_assign);
 /* writes the armed agents' rows of d_actions [N][2] (device memory, 16-byte aligned) from the scans of the last step; rows of
  * external agents are never written (their waves leave before they load anything else).  Asynchronous on the handle's stream;
@@ -979,8 +981,9 @@ int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, dou
  * of a set bit (with traj: of bits 0..3 too) that is not finite and > 0, a NaN margin, a null d_actions or d_out, traj = 1 with a
  * null d_traj, an h_pinned that is not [N][K][D] floats of f110_host_alloc memory.
  * Refused with F110_ERR_STATE: no map, PROGRESS or END_LAT while a map slot in use has no track.
- * Not offered: float32 action input, footprint-corner clearance, opponents, a built-in cost or argmax, feeding the result into
- * the observation encoder, a keyword on the env layers (a rollout is a function of the caller's candidates, not an observation). */
+ * Not offered: float32 action input, footprint-corner clearance, opponents, feeding the result into the observation encoder, a
+ * keyword on the env layers (a rollout is a function of the caller's candidates, not an observation).  A built-in cost and update
+ * on top of it is the MPPI planner below (f110_mppi_*). */
 enum { F110_ROLL_END_X = 1, F110_ROLL_END_Y = 2, F110_ROLL_END_COS = 4, F110_ROLL_END_SIN = 8, F110_ROLL_END_V = 16,
        F110_ROLL_END_YAW_RATE = 32, F110_ROLL_ALIVE = 64, F110_ROLL_MIN_CLEAR = 128, F110_ROLL_PROGRESS = 256, F110_ROLL_END_LAT = 512,
        F110_ROLL_NCHANNELS = 10 };
@@ -1013,6 +1016,81 @@ int f110_rollout_device(f110_sim *h, const f110_rollout *spec, const double *d_a
 int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start /* [m][10] */,
                        const double *h_params /* [m][18] or NULL */, const double *h_actions, int32_t m, float *h_out /* [m][K][D] */,
                        double *h_raw /* [m][K][10] or NULL */, float *h_traj /* [m][K][H][4] or NULL */, double *h_traj_raw /* or NULL */);
+
+/* ---- MPPI planner: a sampling planner per agent on top of the rollout (no reference counterpart: model predictive path integral
+ * control, the sampling planner run on F1TENTH cars, here for the cars of an env that plan instead of react) ----
+ * It runs only when called (f110_mppi_device, or f110_step_host with F110_STEP_SCRIPTED), changes no simulator state and no blob
+ * format.  A planner is armed on a handle with ONE spec, a strictly ascending list of M agent indices (the armed agents,
+ * 1 <= M <= N) and one PCG64 stream per armed agent.  The handle owns per armed agent a nominal sequence U[H][2] of (steer, speed)
+ * and the stream position (state.hi, state.lo, inc.hi, inc.lo, the words of f110_pcg64_seed_spawn).  Both are configuration of
+ * the planner, not simulator state: the state blobs do not contain them (f110_mppi_get / f110_mppi_put checkpoint them next to a
+ * blob).  Everything is float64 without contraction.
+ * One call does, for every armed agent n (the rows of other agents are never read or written), with K = k, H = horizon:
+ *   1 fresh row   if step_count[n] == 0 (at reset, or re-seated inside the step just taken): U[h] = (0.0, v_init) for every h first
+ *   2 candidates  V[0] = U, without a draw.  Candidate k >= 1 has its own generator: the agent's, advanced by k * 2^20 LCG steps
+ *                 (numpy.random.PCG64.advance's count).  For h = 0 .. H - 1 it draws e_s, then e_v, each one
+ *                 Generator.standard_normal() (NumPy's ziggurat, as the scan noise), and
+ *                   V[k][h] = (clamp(U[h][0] + sigma_steer * e_s, steer_min, steer_max),
+ *                              clamp(U[h][1] + sigma_speed * e_v, speed_min, speed_max)),  clamp(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x)
+ *                 After the call the agent's generator stands 2^28 steps further on, whatever K is.
+ *   3 rollout     every candidate is rolled as f110_rollout rolls it (above: the agent's live state, FIFO, fill count and
+ *                 parameter row, the handle's time step, integrator and lidar offset, the env's map slot) with the spec's repeat
+ *                 and margin; it yields ALIVE and MIN_CLEAR and, when w_progress or w_lat is non-zero, PROGRESS and END_LAT by
+ *                 the rollout's projection rule (then every map slot an armed agent uses needs a track, else F110_ERR_STATE;
+ *                 with both weights 0 no track is needed, nothing is projected and both values are 0.0)
+ *   4 cost        c = w_dead * (double)(H * repeat - ALIVE)
+ *                 c = c + w_clear * (MIN_CLEAR < clear_ref ? clear_ref - MIN_CLEAR : 0.0)
+ *                 c = c - w_progress * PROGRESS
+ *                 c = c + w_lat * fabs(END_LAT);   a NaN c becomes +inf
+ *   5 weights     beta = the minimum of c_k, best = its first index.  If beta is not finite: w_0 = 1, every other w_k = 0.
+ *                 Otherwise w_k = exp(-(c_k - beta) / lambda).  eta = sum w_k, q = sum w_k * w_k, both over ascending k from 0.0.
+ *   6 update      U'[h][c] = (sum_k w_k * V[k][h][c]) / eta, the sum over ascending k from 0.0.  The agent's row of d_actions is
+ *                 U'[0].  The stored nominal becomes U' (shift == 0), or U[h] = U'[h + 1] for h < H - 1 and U[H - 1] = U'[H - 1]
+ *                 (shift == 1).
+ *   7 info        d_info (or NULL) [N][4] float32: the armed rows hold (float)beta, (float)c_0, (float)(eta * eta / q), (float)best.
+ * The sums are defined bit for bit given the weights; exp and the rollout's sin / cos are the device's.
+ * Refused with F110_ERR_INVALID, nothing changed: k outside 1..256, horizon outside 1..64, repeat outside 1..16, shift other than
+ *   0 or 1, a NaN margin, any other setting not finite, a sigma < 0, steer_min > steer_max, speed_min > speed_max, lambda <= 0, a
+ *   weight < 0, v_init outside [speed_min, speed_max]; a list that is not strictly ascending or has an index outside 0 .. N - 1; an
+ *   armed agent with a follow-the-gap assignment (and f110_controllers_set on an armed agent); M * K >= 2^31.
+ * Not offered: several specs per handle, opponents, the iTTC check or the footprint in the prediction (the rollout's own limits),
+ * a control-effort term, a covariance or a temporal correlation of the noise, float32 candidates, the planner inside the state
+ * blobs. */
+enum { F110_MPPI_MAX_K = 256, F110_MPPI_MAX_H = 64, F110_MPPI_MAX_REPEAT = 16 };
+typedef struct f110_mppi {
+    int32_t k;          /* K, 1..256 candidates per agent (candidate 0 is the nominal itself) */
+    int32_t horizon;    /* H, 1..64 actions per candidate */
+    int32_t repeat;     /* 1..16 sim steps each action is held */
+    int32_t shift;      /* 0, or 1: the stored nominal moves one action ahead after every call */
+    double margin;      /* metres; not NaN: a candidate is alive while the clearance is above it */
+    double sigma_steer, sigma_speed;   /* >= 0 */
+    double steer_min, steer_max;       /* steer_min <= steer_max */
+    double speed_min, speed_max;       /* speed_min <= speed_max */
+    double lambda;      /* > 0: the temperature */
+    double w_dead, w_clear, w_progress, w_lat;   /* >= 0 */
+    double clear_ref;   /* metres: clearance below it costs w_clear per metre */
+    double v_init;      /* the speed of a fresh nominal, within [speed_min, speed_max] */
+} f110_mppi;
+/* arms the planner: h_agents [m] strictly ascending, h_streams [m][4] uint64.  NULL, NULL, 0, NULL disarms it and frees its
+ * memory.  Arming sets every nominal to (0, v_init) and launches nothing; no step looks at it without F110_STEP_SCRIPTED. */
+int f110_mppi_set(f110_sim *h, const f110_mppi *spec, const int32_t *h_agents, int32_t m, const uint64_t *h_streams /* [m][4] */);
+/* one planning call: the armed agents' rows of d_actions [N][2] float64 (device memory, the step's layout) and of d_info [N][4]
+ * float32 (or NULL).  Asynchronous on the handle's stream; right behind a two-block step it runs per env block on the block's own
+ * stream, the ascending list split at the block's bounds.  F110_ERR_STATE with nothing armed or without a map. */
+int f110_mppi_device(f110_sim *h, double *d_actions, float *d_info);
+/* the planner's own memory, in the armed list's order: h_nominal [m][H][2], h_streams [m][4]; either may be NULL.  get waits for
+ * the handle's work; put refuses (F110_ERR_INVALID, nothing changed) a nominal value that is not finite or outside the spec's
+ * bounds.  F110_ERR_STATE with nothing armed. */
+int f110_mppi_get(f110_sim *h, double *h_nominal, uint64_t *h_streams);
+int f110_mppi_put(f110_sim *h, const double *h_nominal, const uint64_t *h_streams);
+/* unit form on host arrays, the same kernels on uploaded rows laid out as f110_rollout_batch lays them: h_start [m][10] on map
+ * slot `slot`, h_params [m][18] or NULL, h_fresh [m] int32 (the rows' step_count; NULL: none is fresh), h_nominal [m][H][2] and
+ * h_streams [m][4] in and out.  Outputs, each may be NULL: h_actions [m][2], h_info [m][4], h_cand [m][K][H][2] (V), h_cost
+ * [m][K], h_weight [m][K].  The planner armed on the handle, if any, is not touched. */
+int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const double *h_start /* [m][10] */,
+                    const double *h_params /* [m][18] or NULL */, const int32_t *h_fresh /* [m] or NULL */, int32_t m,
+                    double *h_nominal /* [m][H][2] */, uint64_t *h_streams /* [m][4] */, double *h_actions /* [m][2] */,
+                    float *h_info /* [m][4] */, double *h_cand /* [m][K][H][2] */, double *h_cost /* [m][K] */, double *h_weight /* [m][K] */);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,352 @@
+"""CPU checks of the MPPI planner: the settings' validation, the struct layout against the header, the host
+instantiation of the mppi_* functions (tests/host_harness/mppi_harness.hip) against the Python model (tests/mppi_ref.py) and cases
+worked out by hand.  The GPU tests (tests/test_gpu_mppi.py) hold the kernels to the same model."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import mppi_ref as ref
+import rollout_ref as rr
+from f1tenth_gym_amd import Mppi, _ffi
+from f1tenth_gym_amd import mppi as mpm
+from oracle import orc
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+_dp = C.POINTER(C.c_double)
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.isfile("/opt/rocm/bin/hipcc"),
+                                 reason="hipcc needed to build the host harness")
+NAN, INF = float("nan"), float("inf")
+
+
+def track_cols(track):
+    """the seven segment columns f110_track_set uploads: ax, ay, dx, dy, l2, len, cum"""
+    pts = track.points_closed()
+    a, d = pts[:-1], pts[1:] - pts[:-1]
+    return np.ascontiguousarray(np.stack([a[:, 0], a[:, 1], d[:, 0], d[:, 1], d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1], track.seg_len, track.cum]))
+
+
+def hipcc():
+    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+# ---- validation ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kw", [
+    dict(k=0), dict(k=257), dict(k=-1), dict(k=2.5), dict(k=True),
+    dict(horizon=0), dict(horizon=65), dict(horizon=1.0),
+    dict(repeat=0), dict(repeat=17), dict(repeat=False),
+    dict(shift=2), dict(shift=-1), dict(shift="yes"), dict(shift=0.5),
+    dict(margin=NAN),
+    dict(sigma_steer=-0.1), dict(sigma_speed=-1.0), dict(sigma_steer=INF), dict(sigma_speed=NAN),
+    dict(steer_min=0.3, steer_max=0.2), dict(speed_min=3.0, speed_max=2.0, v_init=2.5), dict(steer_min=-INF), dict(speed_max=INF),
+    dict(lam=0.0), dict(lam=-1.0), dict(lam=INF), dict(lam=NAN),
+    dict(w_dead=-1.0), dict(w_clear=-0.5), dict(w_progress=-1e-9), dict(w_lat=-2.0), dict(w_dead=INF), dict(w_lat=NAN),
+    dict(clear_ref=INF), dict(clear_ref=NAN),
+    dict(v_init=0.4), dict(v_init=7.5), dict(v_init=NAN), dict(v_init="fast"),
+])
+def test_mppi_validation_refuses(kw):
+    with pytest.raises(ValueError):
+        Mppi(**kw)
+
+
+def test_mppi_defaults_struct_and_coerce():
+    p = Mppi()
+    assert (p.k, p.horizon, p.repeat, p.shift, p.steps, p.needs_track) == (64, 8, 3, True, 24, True)
+    assert not Mppi(w_progress=0.0, w_lat=0.0).needs_track and Mppi(w_progress=0.0, w_lat=0.1).needs_track
+    q = Mppi(k=256, horizon=64, repeat=16, shift=False, margin=-INF, sigma_steer=0.0, sigma_speed=0.0, steer_min=0.1, steer_max=0.1, speed_min=2.0,
+             speed_max=2.0, lam=1e-3, w_dead=0.0, w_clear=0.0, w_progress=0.0, w_lat=0.0, clear_ref=-1.0, v_init=2.0)
+    sp = q.spec()
+    assert (sp.k, sp.horizon, sp.repeat, sp.shift, sp.margin, sp.lambda_, sp.clear_ref, sp.v_init) == (256, 64, 16, 0, -INF, 1e-3, -1.0, 2.0)
+    assert q.nominal_shape(3) == (3, 64, 2) and np.all(q.fresh_nominal(3)[..., 0] == 0.0) and np.all(q.fresh_nominal(3)[..., 1] == 2.0)
+    S = _ffi.MppiSpec
+    assert C.sizeof(S) == 4 * 4 + 14 * 8
+    assert [getattr(S, n).offset for n, _ in S._fields_] == [0, 4, 8, 12] + [16 + 8 * i for i in range(14)]
+    assert Mppi.coerce(dict(k=3)).k == 3 and Mppi.coerce(p) is p
+    assert Mppi(**q.settings()).settings() == q.settings()
+    with pytest.raises(TypeError):
+        Mppi.coerce(7)
+    # the env layers' argument: one planner at most, taken out of the dict form
+    gap, planner = mpm.split_scripted({0: dict(smooth=3), 1: p})
+    assert gap == {0: dict(smooth=3)} and planner == (1, p)
+    assert mpm.split_scripted({1: p}) == (None, (1, p)) and mpm.split_scripted(None) == (None, None)
+    assert mpm.split_scripted(None, (0, dict(k=2)))[1][1].k == 2
+    with pytest.raises(ValueError):
+        mpm.split_scripted({0: p, 1: q})
+    with pytest.raises(ValueError):
+        mpm.split_scripted({0: p}, (1, q))
+
+
+def test_struct_and_constants_match_the_header():
+    """the struct's fields in the header's order and types, and the limits, read from include/f110.h"""
+    with open(os.path.join(os.path.dirname(HERE), "include", "f110.h")) as f:
+        src = f.read()
+    body = re.search(r"typedef struct f110_mppi \{(.*?)\} f110_mppi;", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for t, names in re.findall(r"(int32_t|double)\s+([\w\s,]+);", body):
+        fields += [(t, n.strip()) for n in names.split(",")]
+    ctype = {"int32_t": C.c_int32, "double": C.c_double}
+    mirror = _ffi.MppiSpec._fields_
+    assert [n for _, n in fields] == [n.rstrip("_") for n, _ in mirror]       # (`lambda` is a Python keyword: the mirror says lambda_)
+    assert all(ct is ctype[t] for (t, _), (_, ct) in zip(fields, mirror))
+    assert [n for _, n in fields] == ["lambda" if n == "lam" else n for n in ref.SPEC_INTS + ref.SPEC_FLOATS]       # (the model's order)
+    enums = dict(re.findall(r"(F110_MPPI_[A-Z_]+) = (\d+)", src))
+    for n in ("MAX_K", "MAX_H", "MAX_REPEAT"):
+        assert int(enums["F110_MPPI_" + n]) == getattr(_ffi, "MPPI_" + n) == getattr(mpm, n), n
+    for name in ("f110_mppi_set", "f110_mppi_device", "f110_mppi_get", "f110_mppi_put", "f110_mppi_batch"):
+        assert name in _ffi.PROTOTYPES and re.search(r"\bint %s\(" % name, src), name
+    assert "a built-in cost or argmax" not in src
+
+
+# ---- the host instantiation ---------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hh(tmp_path_factory):
+    src = os.path.join(HERE, "host_harness", "mppi_harness.hip")
+    lib = str(tmp_path_factory.mktemp("mppi_harness") / "libmppi_harness.so")
+    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", src, "-o", lib],
+                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return C.CDLL(lib)
+
+
+def harness(hh, s, so, start, params, nominal, streams, integrator, fresh=None, track=None, lidar_dist=0.0):
+    """the host instantiation's call for settings s (tests/mppi_ref.settings): the model's dict (without near, gap, beta, best)"""
+    K, H = int(s["k"]), int(s["horizon"])
+    start, params = (np.ascontiguousarray(a, dtype=np.float64) for a in (start, params))
+    m = start.shape[0]
+    nom = np.array(nominal, dtype=np.float64, order="C").reshape(m, H, 2)
+    words = np.array(streams, dtype=np.uint64, order="C").reshape(m, 4)
+    ints = np.array([s[n] for n in ref.SPEC_INTS], dtype=np.int32)
+    dbl = np.array([s[n] for n in ref.SPEC_FLOATS], dtype=np.float64)
+    fr = None if fresh is None else np.ascontiguousarray(fresh, dtype=np.int32)
+    cols = None if track is None else track_cols(track)
+    o = dict(actions=np.zeros((m, 2)), info=np.zeros((m, 4), dtype=np.float32), candidates=np.zeros((m, K, H, 2)), cost=np.zeros((m, K)),
+             weight=np.zeros((m, K)), raw=np.zeros((m, K, 4)))
+    c = so.cfg
+    hh.hh_mppi(so.dt.ctypes.data_as(_dp), c.height, c.width, C.c_double(c.resolution), C.c_double(c.orig_x), C.c_double(c.orig_y),
+               C.c_double(c.orig_c), C.c_double(c.orig_s), None if cols is None else cols.ctypes.data_as(_dp),
+               0 if track is None else track.num_segments, int(track is not None and track.closed), C.c_double(0.0 if track is None else track.length),
+               ints.ctypes.data_as(C.c_void_p), dbl.ctypes.data_as(_dp), C.c_double(rr.TIME_STEP), int(integrator), C.c_double(lidar_dist),
+               start.ctypes.data_as(_dp), params.ctypes.data_as(_dp), None if fr is None else fr.ctypes.data_as(C.c_void_p), m,
+               nom.ctypes.data_as(_dp), words.ctypes.data_as(C.c_void_p), o["actions"].ctypes.data_as(_dp), o["info"].ctypes.data_as(C.c_void_p),
+               o["candidates"].ctypes.data_as(_dp), o["cost"].ctypes.data_as(_dp), o["weight"].ctypes.data_as(_dp), o["raw"].ctypes.data_as(_dp))
+    o["nominal"], o["streams"] = nom, words
+    return o
+
+
+EXACT = ("candidates", "streams", "raw", "cost", "weight", "actions", "nominal", "info")
+
+
+def same_bits(got, want, keys=EXACT, what=""):
+    for key in keys:
+        g, w = np.ascontiguousarray(got[key]), np.ascontiguousarray(want[key])
+        assert g.shape == w.shape and g.dtype == w.dtype, (what, key)
+        assert np.array_equal(g.view(np.uint8), w.view(np.uint8)), "%s: %s differs from the model" % (what, key)
+
+
+def rows(map_name, m=6):
+    start, params = rr.grid_rows(map_name)
+    return start[:m], params[:m]
+
+
+def nominal_for(s, m, seed=5):
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.uniform(0.5 * s["steer_min"], 0.5 * s["steer_max"], (m, s["horizon"])),
+                     rng.uniform(s["speed_min"], s["speed_max"], (m, s["horizon"]))], axis=-1)
+
+
+def streams_for(seed, m, base=0):
+    return np.stack([ref.stream_of(seed, base + n) for n in range(m)])
+
+
+def test_streams_are_the_package_s_spawned_words():
+    from f1tenth_gym_amd.reset_sampler import stream_words
+    assert np.array_equal(stream_words(77, 5, 3), streams_for(77, 5, 3))
+
+
+@needs_hipcc
+@pytest.mark.parametrize("map_name", ["example_map", "berlin"])
+def test_harness_matches_model_over_a_grid(hh, map_name):
+    """K on both sides of a wave, H = 1 and 5, repeat 1 and 3, both integrators, shift 0 and 1, with and without the track weights:
+    everything bit for bit (the harness and the model share the oracle's arithmetic and glibc's exp)"""
+    so, track = rr.scan_oracle(map_name), rr.grid_track(map_name)
+    start, params = rows(map_name, 3)
+    q = 0
+    for K in (1, 2, 7, 65):
+        for H in (1, 5):
+            for repeat, integrator in ((1, 1), (3, 2)) if K > 2 else ((1, 1), (3, 2), (3, 1), (1, 2)):
+                with_track = q % 2 == 0
+                s = ref.settings(k=K, horizon=H, repeat=repeat, shift=q // 2 % 2, w_progress=3.0 if with_track else 0.0, w_lat=0.5 if with_track else 0.0,
+                                 lam=0.7 + 0.1 * (q % 3))
+                nom, words = nominal_for(s, 3, q), streams_for(100 + q, 3)
+                fresh = np.array([1, 0, 5], dtype=np.int32)
+                want = ref.plan(s, so, start, params, nom, words, integrator, fresh, track)
+                got = harness(hh, s, so, start, params, nom, words, integrator, fresh, track)
+                same_bits(got, want, what=(map_name, K, H, repeat, integrator, q))
+                assert np.all(want["candidates"][1, 0, :, 0] == 0.0) and np.all(want["candidates"][1, 0, :, 1] == s["v_init"])   # the fresh row
+                q += 1
+
+
+@needs_hipcc
+def test_draws_through_the_wedge_and_the_tail(hh):
+    """a seed whose candidates' draws take the ziggurat's wedge test AND its tail loop (searched here, on the CPU): V and the stream
+    positions still match NumPy's generator bit for bit"""
+    K, H = 64, 5
+    found = None
+    out = (C.c_int * 2)()
+    for seed in range(400):
+        words = ref.stream_of(seed, 0)
+        wedge = tail = 0
+        for k in range(1, K):
+            gw = ref.words_of(ref.generator(words, k << 20))
+            hh.hh_mppi_branches(gw.ctypes.data_as(C.c_void_p), 2 * H, out)
+            wedge, tail = wedge + out[0], tail + out[1]
+        if wedge > 0 and tail > 0:
+            found = (seed, wedge, tail)
+            break
+    assert found is not None
+    so = rr.scan_oracle("example_map")
+    start, params = rows("example_map", 1)
+    s = ref.settings(k=K, horizon=H, repeat=1, sigma_steer=0.05, sigma_speed=0.4, steer_min=-10.0, steer_max=10.0, speed_min=-50.0, speed_max=50.0)
+    nom, words = nominal_for(s, 1), ref.stream_of(found[0], 0)[None]
+    want = ref.plan(s, so, start, params, nom, words, 1)
+    got = harness(hh, s, so, start, params, nom, words, 1)
+    same_bits(got, want, what=found)
+    noise = (want["candidates"][0, 1:, :, 1] - nom[0, None, :, 1]) / s["sigma_speed"]
+    steer = (want["candidates"][0, 1:, :, 0] - nom[0, None, :, 0]) / s["sigma_steer"]
+    assert max(np.abs(noise).max(), np.abs(steer).max()) > 3.6541528853610088 - 1e-6      # a draw from beyond the ziggurat's base layer
+
+
+# ---- cases by hand --------------------------------------------------------------------------------------------------------------------
+P1 = orc.params_vec()[None, :]
+FREE = (rr.grid_rows("example_map")[0][0, 0], rr.grid_rows("example_map")[0][0, 1])   # a point on the example raceline
+
+
+def row(x, y, theta, v=0.0, fill=2):
+    return np.array([[x, y, 0.0, v, theta, 0.0, 0.0, 0.0, 0.0, float(fill)]])
+
+
+@needs_hipcc
+@pytest.mark.parametrize("H", [1, 5])
+@pytest.mark.parametrize("shift", [0, 1])
+def test_hand_one_candidate_is_the_nominal_and_the_shift(hh, H, shift):
+    """K = 1: the action is U[0], no draw is made (the stream still moves 2^28 steps), and the nominal stays or shifts"""
+    so = rr.scan_oracle("example_map")
+    s = ref.settings(k=1, horizon=H, repeat=2, shift=shift)
+    nom, words = nominal_for(s, 1, 9), streams_for(3, 1)
+    got = harness(hh, s, so, row(FREE[0], FREE[1], 0.7, v=2.0), P1, nom, words, 1)
+    assert got["actions"][0].tolist() == nom[0, 0].tolist() and got["weight"][0].tolist() == [1.0] and got["info"][0, 2:].tolist() == [1.0, 0.0]
+    want = nom[0].copy()
+    if shift:
+        want[:-1] = nom[0, 1:]
+    assert np.array_equal(got["nominal"][0], want)
+    assert np.array_equal(got["streams"][0], ref.words_of(ref.generator(words[0], 1 << 28)))
+    same_bits(got, ref.plan(s, so, row(FREE[0], FREE[1], 0.7, v=2.0), P1, nom, words, 1))
+    # K = 5: the same shift rule on U'
+    s5 = ref.settings(k=5, horizon=H, repeat=2, shift=shift)
+    g5 = harness(hh, s5, so, row(FREE[0], FREE[1], 0.7, v=2.0), P1, nom, words, 1)
+    w5 = ref.plan(s5, so, row(FREE[0], FREE[1], 0.7, v=2.0), P1, nom, words, 1)
+    same_bits(g5, w5)
+    _, Un, _, _, _, _ = ref.update(s5, w5["candidates"][0], list(w5["cost"][0]))
+    assert np.array_equal(g5["actions"][0], Un[0])
+    assert np.array_equal(g5["nominal"][0, -1], Un[-1]) and (H == 1 or np.array_equal(g5["nominal"][0, :-1], Un[1:] if shift else Un[:-1]))
+
+
+@needs_hipcc
+def test_hand_every_candidate_dead_at_its_first_step(hh):
+    """a start outside the map reads the table's last cell; with the margin at that value nothing survives a step: equal costs, equal
+    weights, the update is the plain mean of the candidates"""
+    so = rr.scan_oracle("example_map")
+    oob = float(so.dt[-1, -1])
+    s = ref.settings(k=6, horizon=3, repeat=2, margin=oob, clear_ref=0.0)
+    nom, words = nominal_for(s, 1), streams_for(11, 1)
+    st = row(-500.0, 900.0, 0.3, v=1.0)
+    got = harness(hh, s, so, st, P1, nom, words, 1)
+    assert np.all(got["raw"][0, :, 0] == 0.0) and np.all(got["raw"][0, :, 1] == oob)
+    assert np.all(got["cost"][0] == s["w_dead"] * 6.0) and np.all(got["weight"][0] == 1.0)
+    assert got["info"][0].tolist() == [np.float32(s["w_dead"] * 6.0), np.float32(s["w_dead"] * 6.0), 6.0, 0.0]
+    mean = np.zeros((3, 2))
+    for k in range(6):
+        mean = mean + got["candidates"][0, k]
+    assert np.array_equal(got["actions"][0], (mean / 6.0)[0])
+    same_bits(got, ref.plan(s, so, st, P1, nom, words, 1))
+
+
+@needs_hipcc
+def test_hand_a_nan_state_keeps_the_nominal(hh):
+    """a NaN position projects to a NaN arc length: every cost is NaN -> +inf, beta is not finite, w = (1, 0, ...), the action is U[0]"""
+    so, track = rr.scan_oracle("example_map"), rr.grid_track("example_map")
+    s = ref.settings(k=4, horizon=3, repeat=1, shift=0, w_progress=2.0)
+    nom, words = nominal_for(s, 1), streams_for(12, 1)
+    got = harness(hh, s, so, row(NAN, FREE[1], 0.0, v=1.0), P1, nom, words, 1, track=track)
+    assert np.all(got["cost"][0] == INF) and got["weight"][0].tolist() == [1.0, 0.0, 0.0, 0.0]
+    assert np.array_equal(got["nominal"][0], nom[0]) and np.array_equal(got["actions"][0], nom[0, 0])
+    assert got["info"][0].tolist() == [INF, INF, 1.0, 0.0]
+    assert np.array_equal(got["streams"][0], ref.words_of(ref.generator(words[0], 1 << 28)))
+
+
+@needs_hipcc
+def test_hand_cold_and_hot_temperatures(hh):
+    so, track = rr.scan_oracle("example_map"), rr.grid_track("example_map")
+    start, params = rows("example_map", 6)
+    nom = nominal_for(ref.settings(horizon=5), 6)
+    words = streams_for(13, 6)
+    cold = ref.settings(k=16, horizon=5, repeat=3, lam=1e-3, w_progress=10.0)
+    got = harness(hh, cold, so, start, params, nom, words, 1, track=track)
+    want = ref.plan(cold, so, start, params, nom, words, 1, track=track)
+    same_bits(got, want)
+    assert np.any(got["cost"] - got["cost"].min(axis=1, keepdims=True) > 1.0)
+    for n in range(6):   # the weights underflow to the winner: whoever costs 1 more than it has weight exp(-1000) = 0
+        far = got["cost"][n] - got["cost"][n].min() > 1.0
+        assert np.all(got["weight"][n][far] == 0.0) and got["weight"][n][int(want["best"][n])] == 1.0
+        if np.count_nonzero(got["weight"][n]) == 1:
+            assert np.array_equal(got["actions"][n], got["candidates"][n, int(want["best"][n]), 0])
+    hot = ref.settings(k=16, horizon=5, repeat=3, lam=1e6, w_progress=10.0)
+    got = harness(hh, hot, so, start, params, nom, words, 1, track=track)
+    same_bits(got, ref.plan(hot, so, start, params, nom, words, 1, track=track))
+    assert np.all(got["weight"] > 0.999) and np.all(got["info"][:, 2] > 15.99)
+    assert np.allclose(got["actions"], got["candidates"][:, :, 0].mean(axis=1), rtol=1e-3, atol=1e-6)
+
+
+@needs_hipcc
+def test_hand_both_clamps_bind(hh):
+    so = rr.scan_oracle("example_map")
+    s = ref.settings(k=64, horizon=5, repeat=1, sigma_steer=50.0, sigma_speed=500.0)
+    start, params = rows("example_map", 2)
+    nom, words = nominal_for(s, 2), streams_for(14, 2)
+    got = harness(hh, s, so, start, params, nom, words, 1)
+    V = got["candidates"][:, 1:]
+    for c, lo, hi in ((0, s["steer_min"], s["steer_max"]), (1, s["speed_min"], s["speed_max"])):
+        assert np.any(V[..., c] == lo) and np.any(V[..., c] == hi) and np.all((V[..., c] >= lo) & (V[..., c] <= hi))
+    same_bits(got, ref.plan(s, so, start, params, nom, words, 1))
+
+
+@needs_hipcc
+def test_hand_a_fresh_row_starts_from_rest(hh):
+    so = rr.scan_oracle("example_map")
+    s = ref.settings(k=5, horizon=4, repeat=2)
+    start, params = rows("example_map", 2)
+    nom, words = nominal_for(s, 2), streams_for(15, 2)
+    got = harness(hh, s, so, start, params, nom, words, 1, fresh=[0, 3])
+    assert np.all(got["candidates"][0, 0, :, 0] == 0.0) and np.all(got["candidates"][0, 0, :, 1] == s["v_init"])
+    assert np.array_equal(got["candidates"][1, 0], nom[1])
+    same_bits(got, ref.plan(s, so, start, params, nom, words, 1, fresh=[0, 3]))
+    # a fresh row's result does not depend on what was stored
+    other = harness(hh, s, so, start, params, nominal_for(s, 2, 77), words, 1, fresh=[0, 3])
+    same_bits({k: v[:1] for k, v in other.items()}, {k: v[:1] for k, v in got.items()})
+
+
+@needs_hipcc
+def test_harness_standalone_under_host_sanitizers(tmp_path):
+    """the planner's arithmetic as a stand-alone program (its own main) built for the HOST with the address and undefined-behaviour
+    sanitizers; nothing is loaded into Python"""
+    src = os.path.join(HERE, "host_harness", "mppi_harness.hip")
+    exe = str(tmp_path / "mppi_harness_san")
+    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-DMPPI_HARNESS_MAIN",
+                           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", src, "-o", exe],
+                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    proc = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert proc.returncode == 0 and proc.stdout.startswith("mppi harness: ok"), proc.stdout
