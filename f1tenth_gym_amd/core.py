@@ -260,6 +260,12 @@ class StateBlob(object):
             h["num_envs"], h["num_agents"], h["num_beams"], ",".join(h["columns"]), h["total_bytes"])
 
 
+def _with_extras(out, *optional):
+    """a unit form's result: `out` alone, or a tuple of it and the optional outputs that were asked for (not None)"""
+    res = (out,) + tuple(x for x in optional if x is not None)
+    return res[0] if len(res) == 1 else res
+
+
 class BatchSim(object):
     def __init__(self, params=None, num_envs=1, num_agents=2, num_beams=1080, fov=4.7, eps=0.0001,
                  theta_dis=2000, max_range=30.0, time_step=0.01, integrator=_ffi.INTEGRATOR_RK4,
@@ -1125,6 +1131,24 @@ class BatchSim(object):
         check(_ffi.lib().f110_track_project_batch(self._h, int(slot), dptr(p), p.shape[0], dptr(out)), self._h)
         return out
 
+    # ------------------------------------------------------------------ what the per-agent device forms share
+    def _f32_out(self, shape, out, name="out"):
+        """a device form's float32 output: a new DeviceArray of `shape` for None, else the caller's, which must be one"""
+        if out is None:
+            return DeviceArray(self, shape, np.float32)
+        if not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
+            raise ValueError("%s must be a float32 DeviceArray of shape %s" % (name, shape))
+        return out
+
+    @staticmethod
+    def _pinned_ptr(shape, pinned):
+        """the address of a pinned_empty float32 array of `shape` that also receives the output (None: no copy)"""
+        if pinned is None:
+            return None
+        if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
+            raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
+        return pinned.ctypes.data
+
     # ------------------------------------------------------------------ track preview (f110_track_preview_*, DESIGN §6g)
     def track_preview_device(self, preview, out=None, pinned=None):
         """the raceline ahead of every agent (track_preview.TrackPreview) as a float32 DeviceArray [N][P][D], from the s column
@@ -1134,15 +1158,8 @@ class BatchSim(object):
         from .track_preview import TrackPreview
         pv = TrackPreview.coerce(preview)
         shape = pv.shape(self.N)
-        if out is None:
-            out = DeviceArray(self, shape, np.float32)
-        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
-            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
-        pp = None
-        if pinned is not None:
-            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
-                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
-            pp = pinned.ctypes.data
+        out = self._f32_out(shape, out)
+        pp = self._pinned_ptr(shape, pinned)
         spec = pv.spec()
         check(_ffi.lib().f110_track_preview_device(self._h, C.byref(spec), out.ptr, pp), self._h)
         return out
@@ -1165,8 +1182,7 @@ class BatchSim(object):
         spec = pv.spec()
         check(_ffi.lib().f110_track_preview_batch(self._h, C.byref(spec), int(slot), dptr(rows), m, out.ctypes.data,
                                                   None if rw is None else dptr(rw), None if sg is None else i32ptr(sg)), self._h)
-        res = [out] + ([rw] if raw else []) + ([sg] if segments else [])
-        return res[0] if len(res) == 1 else tuple(res)
+        return _with_extras(out, rw, sg)
 
     # ------------------------------------------------------------------ neighbours (f110_neighbors_*)
     def neighbors_device(self, spec, out=None, pinned=None):
@@ -1178,15 +1194,8 @@ class BatchSim(object):
         from .neighbors import Neighbors
         nb = Neighbors.coerce(spec)
         shape = nb.shape(self.N)
-        if out is None:
-            out = DeviceArray(self, shape, np.float32)
-        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
-            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
-        pp = None
-        if pinned is not None:
-            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
-                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
-            pp = pinned.ctypes.data
+        out = self._f32_out(shape, out)
+        pp = self._pinned_ptr(shape, pinned)
         sp = nb.spec()
         check(_ffi.lib().f110_neighbors_device(self._h, C.byref(sp), out.ptr, pp), self._h)
         return out
@@ -1207,8 +1216,7 @@ class BatchSim(object):
         sp = nb.spec()
         check(_ffi.lib().f110_neighbors_batch(self._h, C.byref(sp), int(A), float(track_L), dptr(r), m, out.ctypes.data,
                                               None if rw is None else dptr(rw), None if ix is None else i32ptr(ix)), self._h)
-        res = [out] + ([rw] if raw else []) + ([ix] if indices else [])
-        return res[0] if len(res) == 1 else tuple(res)
+        return _with_extras(out, rw, ix)
 
     # ------------------------------------------------------------------ rollout (f110_rollout_*)
     def rollout_device(self, spec, d_actions, out=None, traj=None, pinned=None):
@@ -1223,22 +1231,13 @@ class BatchSim(object):
         shape, tshape, ashape = ro.shape(self.N), ro.traj_shape(self.N), ro.actions_shape(self.N)
         if not isinstance(d_actions, DeviceArray) or tuple(d_actions.shape) != ashape or d_actions.dtype != np.float64:
             raise ValueError("d_actions must be a float64 DeviceArray of shape %s" % (ashape,))
-        if out is None:
-            out = DeviceArray(self, shape, np.float32)
-        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
-            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
+        out = self._f32_out(shape, out)
         if not ro.traj:
             if traj is not None:
                 raise ValueError("traj is given, but the rollout does not ask for the trajectory")
-        elif traj is None:
-            traj = DeviceArray(self, tshape, np.float32)
-        elif not isinstance(traj, DeviceArray) or tuple(traj.shape) != tshape or traj.dtype != np.float32:
-            raise ValueError("traj must be a float32 DeviceArray of shape %s" % (tshape,))
-        pp = None
-        if pinned is not None:
-            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
-                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
-            pp = pinned.ctypes.data
+        else:
+            traj = self._f32_out(tshape, traj, "traj")
+        pp = self._pinned_ptr(shape, pinned)
         sp = ro.spec()
         check(_ffi.lib().f110_rollout_device(self._h, C.byref(sp), d_actions.ptr, out.ptr, traj.ptr if ro.traj else None, pp), self._h)
         return (out, traj) if ro.traj else out
@@ -1287,8 +1286,7 @@ class BatchSim(object):
         check(_ffi.lib().f110_rollout_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), dptr(a), m, out.ctypes.data,
                                             None if rw is None else dptr(rw), None if tr is None else tr.ctypes.data,
                                             None if trw is None else dptr(trw)), self._h)
-        res = [out] + ([tr] if ro.traj else []) + ([rw] if raw else []) + ([trw] if trw is not None else [])
-        return res[0] if len(res) == 1 else tuple(res)
+        return _with_extras(out, tr, rw, trw)
 
     # ------------------------------------------------------------------ MPPI planner (f110_mppi_*)
     mppi_planner, mppi_agents = None, None
@@ -1324,11 +1322,7 @@ class BatchSim(object):
         mppi.INFO = (the lowest cost, the nominal's cost, the effective sample size, the index of the lowest cost).  Enqueued on
         the handle's stream, per env block behind a two-block step (no host wait)."""
         a = d_actions.ptr if isinstance(d_actions, DeviceArray) else int(d_actions)
-        ip = None
-        if info is not None:
-            if not isinstance(info, DeviceArray) or tuple(info.shape) != (self.N, 4) or info.dtype != np.float32:
-                raise ValueError("info must be a float32 DeviceArray of shape %s" % ((self.N, 4),))
-            ip = info.ptr
+        ip = None if info is None else self._f32_out((self.N, 4), info, "info").ptr
         check(_ffi.lib().f110_mppi_device(self._h, a, ip), self._h)
 
     def mppi(self, actions, info=False):
@@ -1454,13 +1448,9 @@ class BatchSim(object):
                 self._obs_stacks[id(enc)] = out
                 fill = True
             out = out[1]
-        elif not isinstance(out, DeviceArray) or tuple(out.shape) != shape or out.dtype != np.float32:
-            raise ValueError("out must be a float32 DeviceArray of shape %s" % (shape,))
-        pp = None
-        if pinned is not None:
-            if not isinstance(pinned, np.ndarray) or pinned.dtype != np.float32 or tuple(pinned.shape) != shape or not pinned.flags.c_contiguous:
-                raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
-            pp = pinned.ctypes.data
+        else:
+            out = self._f32_out(shape, out)
+        pp = self._pinned_ptr(shape, pinned)
         spec = enc.spec(fill)
         check(_ffi.lib().f110_obs_encode_device(self._h, C.byref(spec), out.ptr, pp), self._h)
         return out

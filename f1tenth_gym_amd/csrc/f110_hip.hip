@@ -58,6 +58,9 @@ struct ExpSwitches {
     uint64_t scan_trace = 0;   // device address of a caller-owned [waves][8] uint64 buffer: clock stamps, hardware id, samples of every scan wave (0 = off)
 };
 
+// the device forms that copy a per-agent float32 output into a caller's page-locked block (env_blocks_output)
+enum PinnedDst { kPinnedObs, kPinnedPreview, kPinnedNeighbors, kPinnedRollout, kPinnedCount };
+
 struct f110_sim {
     f110_config cfg{};
     int N = 0;
@@ -218,10 +221,7 @@ struct f110_sim {
     f110_track_host trk_pinned{};         // f110_track_host_block, host pointers ...
     HostBlock trk_hb{};                   // ... and their device views (the trk_* fields)
     bool trk_pinned_on = false;
-    const float *obs_pinned = nullptr;    // f110_obs_encode_device: the page-locked block its last copy went to
-    const float *preview_pinned = nullptr;   // f110_track_preview_device: likewise
-    const float *neighbors_pinned = nullptr; // f110_neighbors_device: likewise
-    const float *rollout_pinned = nullptr;   // f110_rollout_device: likewise
+    const float *pinned_dst[kPinnedCount] = {};   // per device form: the page-locked block its last copy went to (f110_host_free)
     double *d_roll_end = nullptr;            // f110_rollout_device: the candidates' end positions between its two kernels (grows on demand)
     size_t roll_end_cap = 0;
     // scripted cars (f110_controllers_set): the specs and the per-agent assignment in device memory; gap_specs == 0: disarmed
@@ -414,6 +414,25 @@ static int env_blocks_follow(f110_sim *h, EnvBlocks &w)
     }
     ENTER(h);
     w = env_blocks_main(h);
+    return F110_OK;
+}
+
+// A device form with a per-agent float32 output d_out [N][per_agent], over the blocks env_blocks_follow gave it: launch(b) per
+// block, then (h_pinned set) the block's slice into the caller's page-locked copy on the block's stream, remembered for
+// f110_host_free.  Ends the call the way `follow` asks.  A new form of this kind is a spec check, a job fill, a launcher and
+// an enumerator of PinnedDst.
+template <typename Launch>
+static int env_blocks_output(f110_sim *h, const EnvBlocks &w, PinnedDst who, size_t per_agent, const float *d_out, float *h_pinned, Launch launch)
+{
+    const size_t A = (size_t)h->cfg.num_agents;
+    for (const EnvBlock &b : w) {
+        launch(b);
+        const size_t i0 = b.e0 * A * per_agent, n = b.count * A * per_agent;
+        if (h_pinned) HIPCHK(h, hipMemcpyAsync(h_pinned + i0, d_out + i0, n * sizeof(float), hipMemcpyDeviceToHost, b.stream));
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h_pinned) h->pinned_dst[who] = h_pinned;
+    h->touched = false;
     return F110_OK;
 }
 
@@ -687,6 +706,17 @@ static hipError_t streams_concurrent(hipStream_t a, hipStream_t b, bool *yes)
 static std::mutex g_registry_mu;
 static std::set<f110_sim *> g_handles;
 static std::map<const char *, size_t> g_host_blocks;
+
+// does ONE f110_host_alloc block (the one that starts at or below p) hold all of [p, p + bytes)?
+static bool pinned_block_holds(const void *p, size_t bytes)
+{
+    std::lock_guard<std::mutex> lk(g_registry_mu);
+    const char *q = static_cast<const char *>(p);
+    auto it = g_host_blocks.upper_bound(q);
+    if (it == g_host_blocks.begin()) return false;
+    --it;
+    return q + bytes <= it->first + it->second;
+}
 
 int f110_create(const f110_config *cfg, f110_sim **out)
 {
@@ -2338,14 +2368,16 @@ int f110_host_free(f110_sim *h, void *p)
                     o->trk_pinned = f110_track_host{};
                 }
             }
-            if (inside(o->obs_pinned) || inside(o->preview_pinned) || inside(o->neighbors_pinned) || inside(o->rollout_pinned)) {   // an encode's, a preview's, a neighbour call's or a rollout's copy (on the env blocks' streams) may still be on its way into the block
-                (void)hipSetDevice(o->cfg.device_id);
-                for (hipStream_t gs : o->gstreams) (void)hipStreamSynchronize(gs);
-                (void)hipStreamSynchronize(o->stream);
-                if (inside(o->obs_pinned)) o->obs_pinned = nullptr;
-                if (inside(o->preview_pinned)) o->preview_pinned = nullptr;
-                if (inside(o->neighbors_pinned)) o->neighbors_pinned = nullptr;
-                if (inside(o->rollout_pinned)) o->rollout_pinned = nullptr;
+            bool drained = false;
+            for (const float *&dst : o->pinned_dst) {
+                if (!inside(dst)) continue;
+                if (!drained) {   // a device form's copy (on the env blocks' streams) may still be on its way into the block
+                    (void)hipSetDevice(o->cfg.device_id);
+                    for (hipStream_t gs : o->gstreams) (void)hipStreamSynchronize(gs);
+                    (void)hipStreamSynchronize(o->stream);
+                    drained = true;
+                }
+                dst = nullptr;
             }
             if (!o->hb_valid && !o->fused_valid) continue;
             const f110_host_block &b = o->hb_host;
@@ -3902,17 +3934,41 @@ int f110_scan_policy_device(f110_sim *h, double steer_gain, double steer_max, do
     return F110_OK;
 }
 
+// ---- what the per-agent features' specs and launch plans share ------------------------------------------------------------------
+// a spec's beam window: 0, 0 is every beam, otherwise [lo, hi) must lie within the handle's beams; on success its first beam and width
+static int beam_window(f110_sim *h, const char *who, int lo, int hi, int *lo_out, int *W)
+{
+    const int B = h->cfg.num_beams, end = (lo == 0 && hi == 0) ? B : hi;
+    if (lo < 0 || end > B || lo >= end) return fail(h, F110_ERR_INVALID, "%s: beams [%d, %d) are not a range within the %d beams", who, lo, hi, B);
+    *lo_out = lo;
+    *W = end - lo;
+    return F110_OK;
+}
+
+// one wave per agent with wave_bytes of LDS: the workgroup size of 1..4 waves (within 64 KiB) that packs the most waves into a CU's 160 KiB
+static int plan_waves(int wave_bytes)
+{
+    int best = 1, best_waves = 0;
+    for (int w = 1; w <= 4; ++w) {
+        if ((long long)w * wave_bytes > 65536) break;
+        const int per_cu = std::min(32, (int)(163840 / ((long long)w * wave_bytes)) * w);
+        if (per_cu >= best_waves) {
+            best_waves = per_cu;
+            best = w;
+        }
+    }
+    return best;
+}
+
 // ---- compact observations (include/f110.h) ----------------------------------------------------------------------------------
 // the spec's refusals; on success the kernel's row spec, W's first beam and F.  unit: the eight sources come from the caller
 static int obs_check_spec(f110_sim *h, const f110_obs_spec *spec, const void *out, bool unit, ObsRowSpec &rs, int &beam_lo)
 {
     if (!spec || !out) return fail(h, F110_ERR_INVALID, "obs encode: spec and the output buffer are required");
     const f110_obs_spec &sp = *spec;
-    const int B = h->cfg.num_beams;
-    int lo = sp.beam_lo, hi = sp.beam_hi;
-    if (lo == 0 && hi == 0) hi = B;
-    if (lo < 0 || hi > B || lo >= hi) return fail(h, F110_ERR_INVALID, "obs encode: beams [%d, %d) are not a range within the %d beams", sp.beam_lo, sp.beam_hi, B);
-    const int W = hi - lo, K = sp.sectors;
+    int lo = 0, W = 0;
+    TRY(beam_window(h, "obs encode", sp.beam_lo, sp.beam_hi, &lo, &W));
+    const int K = sp.sectors;
     if (K < 0 || K > W) return fail(h, F110_ERR_INVALID, "obs encode: sectors = %d is outside 0..%d (the beams used)", K, W);
     if (sp.pool < F110_OBS_POOL_MIN || sp.pool > F110_OBS_POOL_CENTER) return fail(h, F110_ERR_INVALID, "obs encode: unknown pool %d", sp.pool);
     if (sp.features & ~F110_OBS_ALL_FEATURES) return fail(h, F110_ERR_INVALID, "obs encode: unknown feature bits 0x%x", sp.features);
@@ -3945,24 +4001,14 @@ static int obs_check_spec(f110_sim *h, const f110_obs_spec *spec, const void *ou
     return F110_OK;
 }
 
-// LDS per wave and waves per workgroup: the row (when it fits next to the stack image in 64 KiB) and the image [F * D + 3]; the
-// workgroup size of 1..4 waves that packs the most waves into a CU's 160 KiB
+// LDS per wave and waves per workgroup: the row (when it fits next to the stack image in 64 KiB) and the image [F * D + 3]
 static void obs_plan_lds(ObsJob &j)
 {
     const int img = ((j.F * j.rs.D + 3) * 4 + 15) & ~15;
     const int row = j.rs.K > 0 ? (j.rs.W * 8 + 15) & ~15 : 0;
     j.row_bytes = (row > 0 && row + img <= 65536) ? row : 0;
     j.wave_bytes = j.row_bytes + img;
-    int best = 1, best_waves = 0;
-    for (int w = 1; w <= 4; ++w) {
-        if ((long long)w * j.wave_bytes > 65536) break;
-        const int per_cu = std::min(32, (int)(163840 / ((long long)w * j.wave_bytes)) * w);
-        if (per_cu >= best_waves) {
-            best_waves = per_cu;
-            best = w;
-        }
-    }
-    j.waves = best;
+    j.waves = plan_waves(j.wave_bytes);
 }
 
 static void obs_launch(const ObsJob &j, hipStream_t st)
@@ -3980,17 +4026,8 @@ int f110_obs_encode_device(f110_sim *h, const f110_obs_spec *spec, float *d_out,
     TRY(obs_check_spec(h, spec, d_out, false, j.rs, j.beam_lo));
     const size_t N = (size_t)h->N;
     const size_t per_agent = (size_t)spec->frames * j.rs.D;
-    if (h_pinned) {
-        std::lock_guard<std::mutex> lk(g_registry_mu);
-        const char *p = reinterpret_cast<const char *>(h_pinned);
-        auto it = g_host_blocks.upper_bound(p);
-        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
-        if (it != g_host_blocks.begin()) {
-            --it;
-            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
-        }
-        if (!inside) return fail(h, F110_ERR_INVALID, "obs encode: h_pinned is not [N][F][D] floats of f110_host_alloc memory");
-    }
+    if (h_pinned && !pinned_block_holds(h_pinned, N * per_agent * sizeof(float)))
+        return fail(h, F110_ERR_INVALID, "obs encode: h_pinned is not [N][F][D] floats of f110_host_alloc memory");
     EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (an agent reads and writes its own rows only)
     TRY(env_blocks_follow(h, w));
     const double *st = h->dev.state;
@@ -4006,18 +4043,11 @@ int f110_obs_encode_device(f110_sim *h, const f110_obs_spec *spec, float *d_out,
     j.fill = (spec->flags & F110_OBS_FILL) ? 1 : 0;
     obs_plan_lds(j);
     const int A = h->cfg.num_agents;
-    for (const EnvBlock &b : w) {
+    return env_blocks_output(h, w, kPinnedObs, per_agent, d_out, h_pinned, [&](const EnvBlock &b) {
         j.i0 = b.e0 * A;
         j.n = b.count * A;
         obs_launch(j, b.stream);
-        if (h_pinned)
-            HIPCHK(h, hipMemcpyAsync(h_pinned + (size_t)j.i0 * per_agent, d_out + (size_t)j.i0 * per_agent, (size_t)j.n * per_agent * sizeof(float),
-                                     hipMemcpyDeviceToHost, b.stream));
-    }
-    HIPCHK(h, hipGetLastError());
-    if (h_pinned) h->obs_pinned = h_pinned;
-    h->touched = false;
-    return F110_OK;
+    });
 }
 
 int f110_obs_encode_batch(f110_sim *h, const f110_obs_spec *spec, const double *h_scans, const double *h_cols, const int32_t *h_step_count,
@@ -4062,10 +4092,8 @@ static int gap_check_spec(f110_sim *h, const f110_gap_follower *g, GapSpec &o)
 {
     if (!g) return fail(h, F110_ERR_INVALID, "gap follower: null spec");
     const int B = h->cfg.num_beams;
-    int lo = g->beam_lo, hi = g->beam_hi;
-    if (lo == 0 && hi == 0) hi = B;
-    if (lo < 0 || hi > B || lo >= hi) return fail(h, F110_ERR_INVALID, "gap follower: beams [%d, %d) are not a range within the %d beams", g->beam_lo, g->beam_hi, B);
-    const int W = hi - lo;
+    int lo = 0, W = 0;
+    TRY(beam_window(h, "gap follower", g->beam_lo, g->beam_hi, &lo, &W));
     if (W > kGapMaxWindow) return fail(h, F110_ERR_INVALID, "gap follower: a window of %d beams exceeds %d", W, kGapMaxWindow);
     if (B < 2) return fail(h, F110_ERR_INVALID, "gap follower: needs at least 2 beams (the angle increment)");
     if (g->smooth < 1 || g->smooth > F110_GAP_MAX_SMOOTH || !(g->smooth & 1) || g->smooth > W)
@@ -4086,20 +4114,11 @@ static int gap_check_spec(f110_sim *h, const f110_gap_follower *g, GapSpec &o)
     return F110_OK;
 }
 
-// LDS per wave (v and p of the widest window) and the workgroup size of 1..4 waves that packs the most waves into a CU's 160 KiB
+// LDS per wave (v and p of the widest window) and waves per workgroup
 static void gap_plan_lds(GapJob &j, int max_w)
 {
     j.wave_bytes = (2 * max_w * 8 + 15) & ~15;
-    int best = 1, best_waves = 0;
-    for (int w = 1; w <= 4; ++w) {
-        if ((long long)w * j.wave_bytes > 65536) break;
-        const int per_cu = std::min(32, (int)(163840 / ((long long)w * j.wave_bytes)) * w);
-        if (per_cu >= best_waves) {
-            best_waves = per_cu;
-            best = w;
-        }
-    }
-    j.waves = best;
+    j.waves = plan_waves(j.wave_bytes);
 }
 
 static void gap_launch(const GapJob &j, hipStream_t st)
@@ -4560,6 +4579,43 @@ static int track_upload(f110_sim *h)
 
 static bool track_has(const f110_sim *h, int slot) { return slot >= 0 && slot < (int)h->tracks.size() && h->tracks[slot].nseg > 0; }
 
+// every map slot in use has a track: slot 0, or under f110_set_env_maps the slot of every env (agents set: of the envs that
+// hold one of this ascending list of agents).  Refused as "<prefix>, but map slot %d has no track (f110_track_set)".
+static int tracks_in_use(f110_sim *h, const char *prefix, const std::vector<int32_t> *agents = nullptr)
+{
+    auto need = [&](int32_t slot) {
+        return track_has(h, slot) ? F110_OK : fail(h, F110_ERR_STATE, "%s, but map slot %d has no track (f110_track_set)", prefix, slot);
+    };
+    if (!h->multi_map) return need(0);
+    if (!agents) {
+        for (int32_t m : h->env_map_host) TRY(need(m));
+        return F110_OK;
+    }
+    const int A = h->cfg.num_agents;
+    int last = -1;
+    for (int32_t n : *agents) {
+        const int e = n / A;
+        if (e == last) continue;
+        last = e;
+        TRY(need(h->env_map_host[e]));
+    }
+    return F110_OK;
+}
+
+// the kernels' slot table reflects `tracks` and the slot count.  After a change the upload is an ordinary entry point on the
+// main stream (ENTER); the step (entry = false) joins its groups without becoming one.
+static int tracks_current(f110_sim *h, bool entry = true)
+{
+    if (!h->tracks_dirty && h->n_tracks_dev == 1 + (int)h->extra_maps.size()) return F110_OK;
+    if (entry) {
+        ENTER(h);
+    } else {
+        TRY(join_groups(h));
+        h->main_dirty = true;
+    }
+    return track_upload(h);
+}
+
 static int track_check(f110_sim *h)
 {
     if (h->track_checked) return F110_OK;
@@ -4578,12 +4634,7 @@ static int track_check(f110_sim *h)
 static int track_prepare(f110_sim *h)
 {
     TRY(track_check(h));
-    if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size()) {
-        TRY(join_groups(h));
-        h->main_dirty = true;
-        TRY(track_upload(h));
-    }
-    return F110_OK;
+    return tracks_current(h, false);
 }
 
 // one projection pass of the step over agents [begin, begin + count) on stream st
@@ -4886,17 +4937,8 @@ int f110_track_preview_device(f110_sim *h, const f110_track_preview *spec, float
     TRY(preview_check_spec(h, spec, j.sp));
     if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return fail(h, F110_ERR_INVALID, "track preview: d_out is null or not 16-byte aligned");
     const size_t N = (size_t)h->N, per_agent = (size_t)j.sp.P * j.sp.D;
-    if (h_pinned) {
-        std::lock_guard<std::mutex> lk(g_registry_mu);
-        const char *p = reinterpret_cast<const char *>(h_pinned);
-        auto it = g_host_blocks.upper_bound(p);
-        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
-        if (it != g_host_blocks.begin()) {
-            --it;
-            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
-        }
-        if (!inside) return fail(h, F110_ERR_INVALID, "track preview: h_pinned is not [N][P][D] floats of f110_host_alloc memory");
-    }
+    if (h_pinned && !pinned_block_holds(h_pinned, N * per_agent * sizeof(float)))
+        return fail(h, F110_ERR_INVALID, "track preview: h_pinned is not [N][P][D] floats of f110_host_alloc memory");
     if (!h->track_on) return fail(h, F110_ERR_STATE, "track preview: tracking is off (f110_track_enable)");
     if (!h->multi_map) TRY(preview_check_slot(h, j.sp, 0));
     else {
@@ -4907,10 +4949,7 @@ int f110_track_preview_device(f110_sim *h, const f110_track_preview *spec, float
             seen[m] = 1;
         }
     }
-    if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size()) {   // (attributes set since the last step)
-        ENTER(h);
-        TRY(track_upload(h));
-    }
+    TRY(tracks_current(h));   // (attributes set since the last step)
     EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (an agent reads its own rows and writes its own block)
     TRY(env_blocks_follow(h, w));
     j.tracks = h->d_tracks;
@@ -4924,18 +4963,11 @@ int f110_track_preview_device(f110_sim *h, const f110_track_preview *spec, float
     j.ps = h->d_trk;
     j.stride = 1;
     j.out = d_out;
-    for (const EnvBlock &b : w) {
+    return env_blocks_output(h, w, kPinnedPreview, per_agent, d_out, h_pinned, [&](const EnvBlock &b) {
         j.begin = b.e0 * j.A;
         j.count = b.count * j.A;
         preview_launch(j, b.stream);
-        if (h_pinned)
-            HIPCHK(h, hipMemcpyAsync(h_pinned + (size_t)j.begin * per_agent, d_out + (size_t)j.begin * per_agent, (size_t)j.count * per_agent * sizeof(float),
-                                     hipMemcpyDeviceToHost, b.stream));
-    }
-    HIPCHK(h, hipGetLastError());
-    if (h_pinned) h->preview_pinned = h_pinned;
-    h->touched = false;
-    return F110_OK;
+    });
 }
 
 int f110_track_preview_batch(f110_sim *h, const f110_track_preview *spec, int32_t slot, const double *h_in, int32_t m, float *h_out,
@@ -5028,31 +5060,14 @@ int f110_neighbors_device(f110_sim *h, const f110_neighbors *spec, float *d_out,
     TRY(nbr_check_spec(h, spec, j.sp));
     if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return fail(h, F110_ERR_INVALID, "neighbors: d_out is null or not 16-byte aligned");
     const size_t N = (size_t)h->N, per_agent = (size_t)j.sp.K * j.sp.D;
-    if (h_pinned) {
-        std::lock_guard<std::mutex> lk(g_registry_mu);
-        const char *p = reinterpret_cast<const char *>(h_pinned);
-        auto it = g_host_blocks.upper_bound(p);
-        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
-        if (it != g_host_blocks.begin()) {
-            --it;
-            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
-        }
-        if (!inside) return fail(h, F110_ERR_INVALID, "neighbors: h_pinned is not [N][K][D] floats of f110_host_alloc memory");
-    }
+    if (h_pinned && !pinned_block_holds(h_pinned, N * per_agent * sizeof(float)))
+        return fail(h, F110_ERR_INVALID, "neighbors: h_pinned is not [N][K][D] floats of f110_host_alloc memory");
     const bool gap = (j.sp.channels & F110_NBR_GAP_S) != 0;
     if (h->cfg.num_agents > F110_NBR_MAX_AGENTS) return fail(h, F110_ERR_STATE, "neighbors: %d agents per env, more than %d", h->cfg.num_agents, (int)F110_NBR_MAX_AGENTS);
     if (gap) {
         if (!h->track_on) return fail(h, F110_ERR_STATE, "neighbors: GAP_S is requested, but tracking is off (f110_track_enable)");
-        if (!h->multi_map) {
-            if (!track_has(h, 0)) return fail(h, F110_ERR_STATE, "neighbors: GAP_S is requested, but map slot 0 has no track (f110_track_set)");
-        } else {
-            for (int32_t m : h->env_map_host)
-                if (!track_has(h, m)) return fail(h, F110_ERR_STATE, "neighbors: GAP_S is requested, but map slot %d has no track (f110_track_set)", m);
-        }
-        if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size()) {
-            ENTER(h);
-            TRY(track_upload(h));
-        }
+        TRY(tracks_in_use(h, "neighbors: GAP_S is requested"));
+        TRY(tracks_current(h));
     }
     EnvBlocks w;   // behind a two-block step: each block's envs on the block's own stream (an agent reads its own env's rows and writes its own block)
     TRY(env_blocks_follow(h, w));
@@ -5067,19 +5082,11 @@ int f110_neighbors_device(f110_sim *h, const f110_neighbors *spec, float *d_out,
     j.stride = 1;
     j.unit_L = 0.0;
     j.out = d_out;
-    for (const EnvBlock &b : w) {
+    return env_blocks_output(h, w, kPinnedNeighbors, per_agent, d_out, h_pinned, [&](const EnvBlock &b) {
         j.env0 = b.e0;
         j.envs = b.count;
         nbr_launch(j, b.stream);
-        if (h_pinned) {
-            const size_t i0 = (size_t)b.e0 * j.A, n = (size_t)b.count * j.A;
-            HIPCHK(h, hipMemcpyAsync(h_pinned + i0 * per_agent, d_out + i0 * per_agent, n * per_agent * sizeof(float), hipMemcpyDeviceToHost, b.stream));
-        }
-    }
-    HIPCHK(h, hipGetLastError());
-    if (h_pinned) h->neighbors_pinned = h_pinned;
-    h->touched = false;
-    return F110_OK;
+    });
 }
 
 int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, double track_L, const double *h_in, int32_t m, float *h_out,
@@ -5272,6 +5279,90 @@ int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t 
     return F110_OK;
 }
 
+// ---- where the rollout's and the planner's candidates start (RollJob and MppiJob name these fields alike) ------------------------------
+template <typename Job>
+static void job_step_consts(const f110_sim *h, Job &j)
+{
+    j.integrator = h->dev.integrator;
+    j.time_step = h->dev.time_step;
+    j.lidar_dist = h->dev.lidar_dist;
+}
+
+// the live source: every agent's state, FIFO and parameter row, its env's map and (track) track
+template <typename Job>
+static int job_live_source(f110_sim *h, const char *who, bool track, Job &j)
+{
+    j.maps = h->multi_map ? h->d_maps_full : cold_consts(h);
+    if (!j.maps) return fail(h, F110_ERR_HIP, "%s: constant upload failed", who);
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.tracks = track ? h->d_tracks : nullptr;
+    j.unit_slot = -1;
+    j.A = h->cfg.num_agents;
+    j.N = h->N;
+    j.params_per_agent = h->dev.params_per_agent;
+    j.state = h->dev.state;
+    j.steer_buf = h->dev.steer_buf;
+    j.buf_cnt = h->dev.buf_cnt;
+    j.params = h->dev.params;
+    job_step_consts(h, j);
+    return F110_OK;
+}
+
+// the unit source: the caller's m start rows [m][10] on one map slot, kept here until the call has synchronised
+struct UnitRows {
+    std::vector<double> cols;    // as the live columns are laid out: state [7][m], the FIFO [2][m]
+    std::vector<int32_t> cnt;    // the FIFO's fill [m]
+    ScanConst kc{};              // the slot's constants
+};
+
+static int unit_slot_check(f110_sim *h, const char *who, int slot)
+{
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "%s: map slot %d, but %d maps are registered", who, slot, 1 + (int)h->extra_maps.size());
+    return F110_OK;
+}
+
+// the rows into columns; refuses a fill count other than 0, 1, 2.  Host memory only: nothing is enqueued.
+static int unit_rows(f110_sim *h, const char *who, const double *h_start, size_t M, UnitRows &u)
+{
+    u.cols.resize(9 * M);
+    u.cnt.resize(M);
+    for (size_t r = 0; r < M; ++r) {
+        for (int c = 0; c < 9; ++c) u.cols[(size_t)c * M + r] = h_start[10 * r + c];
+        const double f = h_start[10 * r + 9];
+        if (!(f == 0.0 || f == 1.0 || f == 2.0)) return fail(h, F110_ERR_INVALID, "%s: row %zu has a FIFO fill count of %g, not 0, 1 or 2", who, r, f);
+        u.cnt[r] = (int32_t)f;
+    }
+    return F110_OK;
+}
+
+// the columns, the slot's constants and the parameter rows (none: the handle's row of agent slot 0) into scratch memory, and the job's view of them
+template <typename Job>
+static int job_unit_source(f110_sim *h, Scratch &sc, int slot, bool track, UnitRows &u, const double *h_params, Job &j)
+{
+    const size_t M = u.cnt.size();
+    u.kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
+    double *dcols = nullptr, *dpar = nullptr;
+    int32_t *dcnt = nullptr;
+    ScanConst *dk = nullptr;
+    TRY(sc.up(u.cols.data(), u.cols.size(), &dcols));
+    TRY(sc.up(u.cnt.data(), u.cnt.size(), &dcnt));
+    TRY(sc.up(&u.kc, 1, &dk));
+    if (h_params) TRY(sc.up(h_params, M * NPARAMS, &dpar));
+    j.maps = dk;
+    j.tracks = track ? h->d_tracks : nullptr;
+    j.unit_slot = slot;
+    j.A = 1;
+    j.count = (int)M;
+    j.N = (int)M;
+    j.params_per_agent = h_params ? 1 : 0;
+    j.state = dcols;
+    j.steer_buf = dcols + 7 * M;
+    j.buf_cnt = dcnt;
+    j.params = h_params ? dpar : h->d_params;
+    job_step_consts(h, j);
+    return F110_OK;
+}
+
 // ---- rollout (f110_rollout_*, include/f110.h) ---------------------------------------------------------------------------------------
 // the spec's refusals; on success the kernel's spec
 static int roll_check_spec(f110_sim *h, const f110_rollout *p, RollSpec &o)
@@ -5331,65 +5422,30 @@ int f110_rollout_device(f110_sim *h, const f110_rollout *spec, const double *d_a
     if (j.sp.traj && (!d_traj || reinterpret_cast<uintptr_t>(d_traj) % 16 != 0)) return fail(h, F110_ERR_INVALID, "rollout: traj = 1, but d_traj is null or not 16-byte aligned");
     const size_t N = (size_t)h->N, per_agent = (size_t)j.sp.K * j.sp.D;
     if (N * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "rollout: %zu agents x %d candidates do not fit 31 bits", N, j.sp.K);
-    if (h_pinned) {
-        std::lock_guard<std::mutex> lk(g_registry_mu);
-        const char *p = reinterpret_cast<const char *>(h_pinned);
-        auto it = g_host_blocks.upper_bound(p);
-        bool inside = false;   // the block that starts at or below p holds all of [p, p + bytes)
-        if (it != g_host_blocks.begin()) {
-            --it;
-            inside = p + N * per_agent * sizeof(float) <= it->first + it->second;
-        }
-        if (!inside) return fail(h, F110_ERR_INVALID, "rollout: h_pinned is not [N][K][D] floats of f110_host_alloc memory");
-    }
+    if (h_pinned && !pinned_block_holds(h_pinned, N * per_agent * sizeof(float)))
+        return fail(h, F110_ERR_INVALID, "rollout: h_pinned is not [N][K][D] floats of f110_host_alloc memory");
     if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
     const bool track = (j.sp.channels & kRollTrackBits) != 0;
     if (track) {
-        if (!h->multi_map) {
-            if (!track_has(h, 0)) return fail(h, F110_ERR_STATE, "rollout: PROGRESS or END_LAT is requested, but map slot 0 has no track (f110_track_set)");
-        } else {
-            for (int32_t m : h->env_map_host)
-                if (!track_has(h, m)) return fail(h, F110_ERR_STATE, "rollout: PROGRESS or END_LAT is requested, but map slot %d has no track (f110_track_set)", m);
-        }
-        if (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size() || h->roll_end_cap < 2 * N * j.sp.K) {
+        TRY(tracks_in_use(h, "rollout: PROGRESS or END_LAT is requested"));
+        TRY(tracks_current(h));
+        if (h->roll_end_cap < 2 * N * j.sp.K) {
             ENTER(h);
-            TRY(track_upload(h));
             TRY(render_grow(h, &h->d_roll_end, &h->roll_end_cap, 2 * N * j.sp.K));
         }
     }
     EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (a candidate reads its own agent's rows and writes its own)
     TRY(env_blocks_follow(h, w));
-    j.maps = h->multi_map ? h->d_maps_full : cold_consts(h);
-    if (!j.maps) return fail(h, F110_ERR_HIP, "rollout: constant upload failed");
-    j.env_map = h->multi_map ? h->d_env_map : nullptr;
-    j.tracks = track ? h->d_tracks : nullptr;
-    j.unit_slot = -1;
-    j.A = h->cfg.num_agents;
-    j.N = h->N;
-    j.params_per_agent = h->dev.params_per_agent;
-    j.state = h->dev.state;
-    j.steer_buf = h->dev.steer_buf;
-    j.buf_cnt = h->dev.buf_cnt;
-    j.params = h->dev.params;
-    j.integrator = h->dev.integrator;
-    j.time_step = h->dev.time_step;
-    j.lidar_dist = h->dev.lidar_dist;
+    TRY(job_live_source(h, "rollout", track, j));
     j.actions = d_actions;
     j.out = d_out;
     j.traj = j.sp.traj ? d_traj : nullptr;
     j.end_xy = track ? h->d_roll_end : nullptr;
-    for (const EnvBlock &b : w) {
+    return env_blocks_output(h, w, kPinnedRollout, per_agent, d_out, h_pinned, [&](const EnvBlock &b) {
         j.begin = b.e0 * j.A;
         j.count = b.count * j.A;
         roll_launch(j, track, b.stream);
-        if (h_pinned)
-            HIPCHK(h, hipMemcpyAsync(h_pinned + (size_t)j.begin * per_agent, d_out + (size_t)j.begin * per_agent, (size_t)j.count * per_agent * sizeof(float),
-                                     hipMemcpyDeviceToHost, b.stream));
-    }
-    HIPCHK(h, hipGetLastError());
-    if (h_pinned) h->rollout_pinned = h_pinned;
-    h->touched = false;
-    return F110_OK;
+    });
 }
 
 int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start, const double *h_params, const double *h_actions,
@@ -5402,33 +5458,20 @@ int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, cons
     if (j.sp.traj && m > 0 && !h_traj) return fail(h, F110_ERR_INVALID, "rollout: traj = 1, but h_traj is null");
     if ((size_t)m * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "rollout: %d rows x %d candidates do not fit 31 bits", m, j.sp.K);
     if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
-    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "rollout: map slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    TRY(unit_slot_check(h, "rollout", slot));
     const bool want_track = (j.sp.channels & kRollTrackBits) != 0;
     if (want_track && !track_has(h, slot)) return fail(h, F110_ERR_STATE, "rollout: PROGRESS or END_LAT is requested, but map slot %d has no track (f110_track_set)", slot);
     const bool track = want_track || (h_raw && track_has(h, slot));
     if (m == 0) return F110_OK;
+    const size_t M = (size_t)m, cands = M * j.sp.K, steps = cands * j.sp.H;
+    UnitRows rows;
+    TRY(unit_rows(h, "rollout", h_start, M, rows));
     ENTER(h);
     if (track) TRY(track_upload(h));
-    // the rows as the live columns are laid out: state [7][m], the FIFO [2][m], its fill [m]
-    const size_t M = (size_t)m, cands = M * j.sp.K, steps = cands * j.sp.H;
-    std::vector<double> cols(9 * M);
-    std::vector<int32_t> cnt(M);
-    for (size_t r = 0; r < M; ++r) {
-        for (int c = 0; c < 9; ++c) cols[(size_t)c * M + r] = h_start[10 * r + c];
-        const double f = h_start[10 * r + 9];
-        if (!(f == 0.0 || f == 1.0 || f == 2.0)) return fail(h, F110_ERR_INVALID, "rollout: row %zu has a FIFO fill count of %g, not 0, 1 or 2", r, f);
-        cnt[r] = (int32_t)f;
-    }
-    ScanConst kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
     Scratch sc(h);
-    double *dcols = nullptr, *dpar = nullptr, *dact = nullptr, *draw = nullptr, *dtraw = nullptr, *dend = nullptr;
-    int32_t *dcnt = nullptr;
-    ScanConst *dk = nullptr;
+    double *dact = nullptr, *draw = nullptr, *dtraw = nullptr, *dend = nullptr;
     float *dout = nullptr, *dtraj = nullptr;
-    TRY(sc.up(cols.data(), cols.size(), &dcols));
-    TRY(sc.up(cnt.data(), cnt.size(), &dcnt));
-    TRY(sc.up(&kc, 1, &dk));
-    if (h_params) TRY(sc.up(h_params, M * NPARAMS, &dpar));
+    TRY(job_unit_source(h, sc, slot, track, rows, h_params, j));
     TRY(sc.up(h_actions, (j.sp.layout == F110_ROLL_PER_AGENT ? steps : (size_t)j.sp.K * j.sp.H) * 2, &dact));
     TRY(sc.up<float>(nullptr, cands * j.sp.D, &dout));
     if (h_raw) {
@@ -5438,21 +5481,6 @@ int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, cons
     if (j.sp.traj) TRY(sc.up<float>(nullptr, steps * 4, &dtraj));
     if (j.sp.traj && h_traj_raw) TRY(sc.up<double>(nullptr, steps * 4, &dtraw));
     if (track) TRY(sc.up<double>(nullptr, cands * 2, &dend));
-    j.maps = dk;
-    j.tracks = track ? h->d_tracks : nullptr;
-    j.unit_slot = slot;
-    j.A = 1;
-    j.begin = 0;
-    j.count = m;
-    j.N = m;
-    j.params_per_agent = h_params ? 1 : 0;
-    j.state = dcols;
-    j.steer_buf = dcols + 7 * M;
-    j.buf_cnt = dcnt;
-    j.params = h_params ? dpar : h->d_params;
-    j.integrator = h->dev.integrator;
-    j.time_step = h->dev.time_step;
-    j.lidar_dist = h->dev.lidar_dist;
     j.actions = dact;
     j.out = dout;
     j.raw = draw;
@@ -5531,20 +5559,7 @@ static int mppi_ready(f110_sim *h)
     if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
     if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
     if (!mppi_needs_track(p.sp)) return F110_OK;
-    if (!h->multi_map) {
-        if (!track_has(h, 0)) return fail(h, F110_ERR_STATE, "mppi: w_progress or w_lat is set, but map slot 0 has no track (f110_track_set)");
-        return F110_OK;
-    }
-    const int A = h->cfg.num_agents;
-    int last = -1;
-    for (int32_t n : p.agents) {
-        const int e = n / A;
-        if (e == last) continue;
-        last = e;
-        const int32_t slot = h->env_map_host[e];
-        if (!track_has(h, slot)) return fail(h, F110_ERR_STATE, "mppi: w_progress or w_lat is set, but map slot %d has no track (f110_track_set)", slot);
-    }
-    return F110_OK;
+    return tracks_in_use(h, "mppi: w_progress or w_lat is set", &p.agents);   // (only the envs of the armed agents)
 }
 
 // armed indices [j.i0, j.i0 + j.count): the candidates, (track) the projections, the update, one behind the other on `st`
@@ -5560,12 +5575,9 @@ static void mppi_launch(const MppiJob &j, hipStream_t st)
     hipLaunchKernelGGL(k_mppi_update, grid1d((size_t)j.count, 256 / gs), block, 0, st, j, gs);
 }
 
-// what every job of this handle shares: the step's constants and the generator's tables
+// what every job of this handle shares: the generator's tables
 static void mppi_job_common(f110_sim *h, MppiJob &j)
 {
-    j.integrator = h->dev.integrator;
-    j.time_step = h->dev.time_step;
-    j.lidar_dist = h->dev.lidar_dist;
     j.zk = h->d_zig_k;
     j.zw = h->d_zig_w;
     j.zf = h->d_zig_f;
@@ -5580,20 +5592,9 @@ static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, 
     const int A = h->cfg.num_agents;
     const bool track = mppi_needs_track(p.sp);
     MppiJob j{};
-    j.maps = h->multi_map ? h->d_maps_full : cold_consts(h);
-    if (!j.maps) return fail(h, F110_ERR_HIP, "mppi: constant upload failed");
-    j.env_map = h->multi_map ? h->d_env_map : nullptr;
-    j.tracks = track ? h->d_tracks : nullptr;
-    j.unit_slot = -1;
-    j.A = A;
-    j.N = h->N;
-    j.params_per_agent = h->dev.params_per_agent;
+    TRY(job_live_source(h, "mppi", track, j));
     j.agents = p.d_agents;
-    j.state = h->dev.state;
-    j.steer_buf = h->dev.steer_buf;
-    j.buf_cnt = h->dev.buf_cnt;
     j.step_count = h->dev.step_count;
-    j.params = h->dev.params;
     mppi_job_common(h, j);
     j.nominal = p.d_nominal;
     j.streams = p.d_streams;
@@ -5664,10 +5665,7 @@ int f110_mppi_device(f110_sim *h, double *d_actions, float *d_info)
 {
     if (!h || !d_actions) return fail(h, F110_ERR_INVALID, "mppi: null argument");
     TRY(mppi_ready(h));
-    if (mppi_needs_track(h->mppi.sp) && (h->tracks_dirty || h->n_tracks_dev != 1 + (int)h->extra_maps.size())) {
-        ENTER(h);
-        TRY(track_upload(h));
-    }
+    if (mppi_needs_track(h->mppi.sp)) TRY(tracks_current(h));
     EnvBlocks w;   // behind a two-block step: each block's armed agents on the block's own stream (an agent reads and writes its own rows)
     TRY(env_blocks_follow(h, w));
     for (const EnvBlock &b : w) TRY(mppi_launch_armed(h, b, d_actions, d_info));
@@ -5723,35 +5721,24 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
     if (m < 0 || (m > 0 && (!h_start || !h_nominal || !h_streams))) return fail(h, F110_ERR_INVALID, "mppi: bad argument");
     if ((size_t)m * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "mppi: %d rows x %d candidates do not fit 31 bits", m, j.sp.K);
     if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
-    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "mppi: map slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    TRY(unit_slot_check(h, "mppi", slot));
     const bool track = mppi_needs_track(j.sp);
     if (track && !track_has(h, slot)) return fail(h, F110_ERR_STATE, "mppi: w_progress or w_lat is set, but map slot %d has no track (f110_track_set)", slot);
     if (m == 0) return F110_OK;
     const size_t M = (size_t)m, seq = (size_t)j.sp.H * 2, cands = M * j.sp.K;
     TRY(mppi_check_nominal(h, j.sp, h_nominal, M));
-    std::vector<double> cols(9 * M);
-    std::vector<int32_t> cnt(M);
-    for (size_t r = 0; r < M; ++r) {
-        for (int c = 0; c < 9; ++c) cols[(size_t)c * M + r] = h_start[10 * r + c];
-        const double f = h_start[10 * r + 9];
-        if (!(f == 0.0 || f == 1.0 || f == 2.0)) return fail(h, F110_ERR_INVALID, "mppi: row %zu has a FIFO fill count of %g, not 0, 1 or 2", r, f);
-        cnt[r] = (int32_t)f;
-    }
+    UnitRows rows;
+    TRY(unit_rows(h, "mppi", h_start, M, rows));
     ENTER(h);
     TRY(mppi_jump_ensure(h));
     if (track) TRY(track_upload(h));
-    ScanConst kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
     Scratch sc(h);
-    double *dcols = nullptr, *dpar = nullptr, *dnom = nullptr, *dV = nullptr, *dcost = nullptr, *dend = nullptr, *dw = nullptr, *dact = nullptr;
-    int32_t *dcnt = nullptr, *dfresh = nullptr;
+    double *dnom = nullptr, *dV = nullptr, *dcost = nullptr, *dend = nullptr, *dw = nullptr, *dact = nullptr;
+    int32_t *dfresh = nullptr;
     uint64_t *dstr = nullptr;
-    ScanConst *dk = nullptr;
     MppiSpec *dspec = nullptr;
     float *dinfo = nullptr;
-    TRY(sc.up(cols.data(), cols.size(), &dcols));
-    TRY(sc.up(cnt.data(), cnt.size(), &dcnt));
-    TRY(sc.up(&kc, 1, &dk));
-    if (h_params) TRY(sc.up(h_params, M * NPARAMS, &dpar));
+    TRY(job_unit_source(h, sc, slot, track, rows, h_params, j));
     if (h_fresh) TRY(sc.up(h_fresh, M, &dfresh));
     TRY(sc.up(&j.sp, 1, &dspec));
     TRY(sc.up((const double *)h_nominal, M * seq, &dnom));
@@ -5762,19 +5749,7 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
     TRY(sc.up<double>(nullptr, 2 * M, &dact));
     TRY(sc.up<float>(nullptr, 4 * M, &dinfo));
     if (track) TRY(sc.up<double>(nullptr, 2 * cands, &dend));
-    j.maps = dk;
-    j.tracks = track ? h->d_tracks : nullptr;
-    j.unit_slot = slot;
-    j.A = 1;
-    j.i0 = 0;
-    j.count = m;
-    j.N = m;
-    j.params_per_agent = h_params ? 1 : 0;
-    j.state = dcols;
-    j.steer_buf = dcols + 7 * M;
-    j.buf_cnt = dcnt;
     j.step_count = dfresh;
-    j.params = h_params ? dpar : h->d_params;
     mppi_job_common(h, j);
     j.nominal = dnom;
     j.streams = dstr;
