@@ -13,7 +13,9 @@
 (b) the device form on 45 envs x 2 cars at K = 3 (agents straddle waves and a workgroup) with every agent, every other agent and
     only the last agent armed: the armed rows against the model evaluated on the device's own state, the others untouched.
 (c) ten consecutive plan-and-step calls with an env re-seated in mid-run; (d) two env blocks against one, two map slots with
-    different tracks, get / put and a state blob; (e) no effect on the step; (f) the refusals and the env layers; (g) the example."""
+    different tracks, get / put and a state blob; (e) no effect on the step; (f) the refusals and the env layers (a planner alone and
+    beside gap followers against loops written by hand); (g) the example.
+The kernels' lane groupings, limits and edge costs: tests/test_gpu_mppi_edges.py; the helpers both files share: tests/mppi_ref.py."""
 import ctypes as C
 import json
 import os
@@ -25,13 +27,13 @@ import pytest
 
 import mppi_ref as ref
 import rollout_ref as rr
-from _util import MAPS, bench_start_poses, load_map_image, map_stem, rel_err
+from _util import MAPS, bench_start_poses, load_map_image, map_stem
+from mppi_ref import check_rows, grid_settings, mppi_of, nominal_for, pin_fifo, same_bits, streams_for, two_maps, warm_sim
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSV = os.path.join(MAPS, "example_waypoints.csv")
-GATE = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -40,74 +42,6 @@ def amd():
     from f1tenth_gym_amd import _ffi
     assert _ffi.device_count() >= 1, "no MI355X visible: the HIP path cannot run (no CPU fallback)"
     return f1tenth_gym_amd
-
-
-def mppi_of(amd, s):
-    kw = {k: v for k, v in s.items()}
-    kw["shift"] = bool(kw["shift"])
-    return amd.Mppi(**kw)
-
-
-def _two_maps(amd, E=1, A=1, **kw):
-    """slot 0: example_map with its raceline; slot 1: berlin with the grid's open polyline"""
-    s = amd.BatchSim(num_envs=E, num_agents=A, **kw)
-    s.set_map_image(*load_map_image("example_map"))
-    assert s.add_map_image(*load_map_image("berlin")) == 1
-    s.set_track(rr.grid_track("example_map"), 0)
-    s.set_track(rr.grid_track("berlin"), 1)
-    return s
-
-
-def nominal_for(s, m, seed=5):
-    rng = np.random.default_rng(seed)
-    return np.stack([rng.uniform(0.5 * s["steer_min"], 0.5 * s["steer_max"], (m, s["horizon"])),
-                     rng.uniform(s["speed_min"], s["speed_max"], (m, s["horizon"]))], axis=-1)
-
-
-def streams_for(seed, agents):
-    return np.stack([ref.stream_of(seed, g) for g in agents])
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def gated(got, want, what, atol=1e-12):
-    """rel_err of got against want, after what rel_err cannot see (a NaN or an infinity gives it an excess that is not > 0): the
-    device's value is finite exactly where the model's is, and elsewhere it is the model's value itself (+inf, -inf or NaN)"""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, what
-    fin = np.isfinite(want)
-    assert np.array_equal(np.isfinite(got), fin), "%s: the device's value is not finite where the model's is (or the other way round)" % (what,)
-    assert np.array_equal(got[~fin], want[~fin], equal_nan=True), "%s: a value that is not finite differs from the model's" % (what,)
-    return rel_err(got[fin], want[fin], atol=atol)
-
-
-def check_rows(s, want, got, what, stats):
-    """got: the device's dict (actions, info, nominal, streams, and from the unit form candidates, cost, weight) against the model's"""
-    assert same_bits(got["streams"], want["streams"]), "%s: stream positions" % (what,)
-    if "candidates" in got:
-        assert same_bits(got["candidates"], want["candidates"]), "%s: the candidates V" % (what,)
-    m = want["actions"].shape[0]
-    keep = np.all(want["near"] >= 1e-9, axis=1)                                       # the model's clearance stays 1e-9 m away from the margin
-    sure = want["gap"] > 1e-9 * np.maximum(1.0, np.abs(want["beta"]))                 # the model's two lowest costs are apart ...
-    for n in np.flatnonzero(want["gap"] == 0.0):                                      # ... or the very same number from the very same rollout
-        tied = want["raw"][n][want["cost"][n] == want["beta"][n]]
-        sure[n] = bool(np.all(tied.view(np.uint64) == tied[0].view(np.uint64)))
-    stats["rows"] += m
-    stats["left_out"] += int(np.count_nonzero(~(keep & sure)))
-    for key in ("cost", "weight", "actions", "nominal"):
-        if key in got:
-            err = gated(got[key][keep], want[key][keep], (what, key))
-            print("%s: %s rel_err %.3e" % (what, key, err))
-            stats["rel_err"] = max(stats["rel_err"], err)
-            assert err < GATE, "%s: %s rel_err %.3e" % (what, key, err)
-    err = gated(got["info"][keep][:, :3], want["info"][keep][:, :3], (what, "info"), atol=1e-6)
-    print("%s: info rel_err %.3e" % (what, err))
-    assert err < GATE, "%s: info rel_err %.3e" % (what, err)
-    assert np.all(np.isfinite(got["info"][keep][:, 3])), "%s: best is not a number" % (what,)
-    assert np.array_equal(got["info"][keep & sure][:, 3], want["info"][keep & sure][:, 3]), "%s: best" % (what,)
 
 
 # ---- (a) the unit form against the model -----------------------------------------------------------------------------------------------
@@ -125,14 +59,6 @@ def grid_cases(map_name):
     return cases
 
 
-def grid_settings(case):
-    """the track weights are always on and the speed noise is small: two candidates whose speed commands both saturate the
-    acceleration move alike for as long as their own steering has not left the two-step delay, and would tie for the lowest cost"""
-    _, K, H, repeat, _, q = case
-    return ref.settings(k=K, horizon=H, repeat=repeat, shift=q // 2 % 2, margin=rr.GRID_MARGIN, w_progress=3.0, w_lat=0.25 * (1 + q % 3), lam=0.5 + 0.25 * (q % 3),
-                        sigma_steer=0.1, sigma_speed=0.3, speed_min=-2.0, v_init=1.0)
-
-
 GRID_FRESH = np.array([3, 0, 0, 7, 1, 2], dtype=np.int32)      # rows 1 and 2 (0.3 and 0.49 m/s) are fresh: they plan around v_init
 
 
@@ -148,7 +74,7 @@ def grid_inputs(case):
 
 @pytest.mark.parametrize("grid_map", rr.GRID_MAPS)
 def test_unit_form_matches_model_over_the_grid(amd, grid_map):
-    sims = {integ: _two_maps(amd, integrator=integ) for integ in (1, 2)}
+    sims = {integ: two_maps(amd, integrator=integ) for integ in (1, 2)}
     stats = {"rows": 0, "left_out": 0, "rel_err": 0.0}
     steps = 0
     for case in grid_cases(grid_map):
@@ -166,30 +92,6 @@ def test_unit_form_matches_model_over_the_grid(amd, grid_map):
 
 
 # ---- (b) the device form ------------------------------------------------------------------------------------------------------------------
-def warm_sim(amd, E, A, steps=15, **kw):
-    """E x A cars on example_map with its raceline after `steps` steps; the FIFO is then set to known values next to the state read
-    back (f110_set_state leaves step_count alone): (sim, start [N][10])"""
-    N = E * A
-    sim = amd.BatchSim(num_envs=E, num_agents=A, **kw)
-    sim.set_map_image(*load_map_image("example_map"))
-    sim.set_track(CSV)
-    sim.reset(bench_start_poses(E, A))
-    rng = np.random.default_rng(E)
-    for _ in range(steps):
-        sim.step(np.stack([rng.uniform(-0.1, 0.1, N), rng.uniform(2.0, 4.0, N)], axis=1))
-    return sim, pin_fifo(sim, rng)
-
-
-def pin_fifo(sim, rng, fifo=None, cnt=None):
-    """the live state as the model's start rows, with the FIFO set on the device to the values returned"""
-    N = sim.N
-    state = sim.get("state")["state"]
-    fifo = rng.uniform(-0.1, 0.1, (N, 2)) if fifo is None else fifo
-    cnt = np.full(N, 2, dtype=np.int32) if cnt is None else cnt
-    sim.set_state(state, fifo, cnt)
-    return np.concatenate([state, fifo, cnt[:, None].astype(np.float64)], axis=1)
-
-
 @pytest.mark.parametrize("armed", ["all", "every_other", "last"])
 def test_device_form_45_envs_of_2_cars(amd, armed):
     E, A, seed = 45, 2, 321
@@ -292,7 +194,7 @@ def test_two_env_blocks_against_one(amd):
 def test_two_map_slots_with_different_tracks(amd):
     E, A = 6, 2
     N = E * A
-    sim = _two_maps(amd, E, A)
+    sim = two_maps(amd, E, A)
     env_map = np.arange(E) % 2
     sim.set_env_maps(env_map)
     rows = {mp: rr.grid_rows(mp) for mp in rr.GRID_MAPS}
@@ -570,6 +472,46 @@ def test_vec_env_scripted_planner_is_the_hand_written_loop(amd):
         amd.F110VecEnv(2, scripted={0: env_planner(amd), 1: env_planner(amd)}, track=track, **ENV_KW)
     with pytest.raises(ValueError):
         amd.F110VecEnv(2, scripted={1: env_planner(amd)}, **ENV_KW)               # a track weight without a track
+
+
+def test_vec_env_gap_followers_and_planner_are_the_hand_written_loop(amd):
+    """car 0 of every env follows the gap, car 1 plans: the scripted step against a loop written by hand on a plain env's handle —
+    the controllers' device call, then the planner's, then the step — every observation bit for bit"""
+    from f1tenth_gym_amd.gap_follower import coerce_scripted
+    E = 6
+    track = amd.Track.from_csv(CSV)
+    env = amd.F110VecEnv(E, scripted={0: amd.GapFollower(), 1: env_planner(amd)}, track=track, **ENV_KW)
+    mine = run_env(env, E)
+    env.sim.batch.close()
+    hand = amd.F110VecEnv(E, track=track, **ENV_KW)
+    b = hand.sim.batch
+    b.set_controllers(*coerce_scripted({0: amd.GapFollower()}, E, 2))
+    b.set_mppi(env_planner(amd), np.arange(E) * 2 + 1, seed=ENV_KW["seed"])
+    d_act = b.device_array((2 * E, 2))
+    seen = []
+
+    class ByHand(object):
+        def reset(self, poses):
+            b.episode_reset(poses.reshape(-1, 3))
+            hand._start_poses = poses.copy()
+            hand.sim._steps_since_full_reset = 0
+            return self.step(np.zeros((E, 2, 2)))
+
+        def step(self, act):
+            d_act.upload(np.ascontiguousarray(act.reshape(-1, 2)))
+            b.follow_gap_device(d_act)
+            b.mppi_device(d_act)
+            seen.append((act.reshape(-1, 2).copy(), d_act.download()))
+            return hand.step(seen[-1][1].reshape(E, 2, 2))
+
+    theirs = run_env(ByHand(), E)
+    b.close()
+    for t, (x, y) in enumerate(zip(mine, theirs)):
+        for k in x:
+            assert same_bits(x[k], y[k]), (t, k)
+    # both kinds of scripted car replaced their rows (after the reset's own step), and both drive
+    assert all(np.all(given != taken) for given, taken in seen[2:])
+    assert mine[-1]["linear_vels_x"][:, 1].min() > 0.5 and mine[-1]["linear_vels_x"][:, 0].max() > 0.0, "the scripted cars do not move"
 
 
 def test_sharded_env_draws_the_numbers_of_one_handle(amd):

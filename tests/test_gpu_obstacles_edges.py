@@ -7,7 +7,8 @@ table, the border's residues).
     bit; the WHOLE padded copy (border included, read from the device) against that slot's; every border cell equal to cell
     [H-1][W-1]; base and unrelated slots untouched; the same after re-stamps in place, alternating between shapes on one handle too.
 (2) the rollout on a derived slot: the unit form against tests/rollout_ref.py on the model's table, the device form against an
-    image-made twin and against the unit form, before and after a re-stamp that changes the out-of-bounds value.
+    image-made twin and against the unit form, before and after a re-stamp that changes the out-of-bounds value.  The MPPI planner
+    on the same slot against tests/mppi_ref.py, the twin and its own device form.
 (3) a re-stamp enqueued behind a rollout (and behind the scripted cars' controllers) that rides the two env blocks.
 (4) the render of two derived slots in one call, and clone_envs from an env on a derived slot."""
 import numpy as np
@@ -343,6 +344,89 @@ def test_rollout_device_form_on_a_derived_slot(amd, late):
     assert np.count_nonzero(changed) >= 20 and np.all(runs[1][R:2 * R][leavers] == steps) and np.all(on_d[leavers] < steps)
     assert np.array_equal(runs[1][:R], on_0) and np.all(on_0[leavers] == steps)
     d_cand.free()
+    s.close()
+
+
+# ---- 2b. the MPPI planner on a derived slot ---------------------------------------------------------------------------------------
+MPPI_K, MPPI_H, MPPI_REPEAT = 8, 5, 4
+
+
+def _corridor_track(amd):
+    """a closed track through the small fixture's corridor: 48 points round the ring"""
+    return amd.Track(np.array([ref.small_corridor_pose(p)[:2] for p in np.linspace(0.0, 2.0 * np.pi, 48, endpoint=False)]))
+
+
+def _table_oracle(which):
+    from oracle import orc
+    so = orc.ScanOracle(1080, 4.7)
+    so.set_map_dt(ref.rollout_table(which), ref.SMALL_RES, list(ref.SMALL_ORIGIN))
+    return so
+
+
+def test_mppi_on_a_derived_slot(amd):
+    """the planner's unit form on the derived slot against tests/mppi_ref.py on the model's table, before and after a re-stamp that
+    lifts the out-of-bounds value over the margin, and bit for bit against the image-made twin; one device-form call per list with
+    eight envs each on slot 0, the derived slot and the twin, each group against the unit form of its slot.  The rows that leave the
+    table (ROLL_LEAVERS) die there under list 0 and live on under list 1: their action changes, and it is the model's."""
+    import mppi_ref as mref
+    from oracle import orc
+    start, _ = ref.rollout_case()
+    R = start.shape[0]
+    fx = _small_fx()
+    _, img, res, origin, _ = fx
+    origin = list(origin)
+    E, A = 24, 2
+    N = E * A
+    masks = [ref.stamp_mask(ref.small_obstacles(w), ref.SMALL_H, ref.SMALL_W, res, origin) for w in (0, 1)]
+    s = _handle(amd, fx, num_envs=E, num_agents=A)
+    im = [s.add_map_image(ref.image_with_stamps(img, m), res, origin) for m in masks]
+    d = s.add_obstacle_map(ref.small_obstacles(0))
+    track = _corridor_track(amd)
+    for slot in [0, d] + im:
+        s.set_track(track, slot)
+    st = mref.settings(k=MPPI_K, horizon=MPPI_H, repeat=MPPI_REPEAT, margin=ref.ROLL_MARGIN, w_progress=3.0, w_lat=0.5, speed_max=7.0, v_init=4.0,
+                       sigma_speed=1.5)
+    mp = mref.mppi_of(amd, st)
+    params = np.tile(orc.params_vec(), (R, 1))
+    rng = np.random.default_rng(77)
+    nom = np.stack([rng.uniform(-0.2, 0.2, (R, MPPI_H)), rng.uniform(3.0, 6.0, (R, MPPI_H))], axis=-1)
+    words = mref.streams_for(91, range(R))
+    rows = np.tile(start, (3, 1))
+    s.reset(np.ascontiguousarray(rows[:, [0, 1, 4]]))
+    s.set_state(rows[:, :7], rows[:, 7:9], rows[:, 9].astype(np.int32))
+    s.set_mppi(mp, None, seed=92)
+    stats = {"rows": 0, "left_out": 0, "rel_err": 0.0}
+    acts = []
+    for which in (0, 1):
+        if which:
+            s.set_obstacles(d, ref.small_obstacles(1))
+        assert np.array_equal(s.get_map_dt(d), ref.rollout_table(which))
+        want = mref.plan(st, _table_oracle(which), start, params, nom, words, 1, None, track)
+        got = s.mppi_rows(mp, start, nom, words, slot=d, params=params)
+        mref.check_rows(st, want, got, "list %d" % which, stats)
+        twin = s.mppi_rows(mp, start, nom, words, slot=im[which], params=params)
+        for key in got:
+            assert mref.same_bits(got[key], twin[key]), "list %d: %s on the derived slot differs from the image-made twin's" % (which, key)
+        acts.append((got["actions"], got["info"], want["actions"], want["raw"][:, :, 0]))
+        # the device form: no set_env_maps follows the re-stamp
+        s.set_env_maps([0] * 8 + [d] * 8 + [im[which]] * 8)
+        nom0, words0 = s.get_mppi_state()
+        count = s.get("step_count")["step_count"]
+        act, info = s.mppi(np.zeros((N, 2)), info=True)
+        nom1, words1 = s.get_mppi_state()
+        for q, slot in enumerate((0, d, im[which])):
+            idx = np.arange(q * R, (q + 1) * R)
+            unit = s.mppi_rows(mp, start, nom0[idx], words0[idx], slot=slot, fresh=count[idx])
+            for key, mine in (("actions", act), ("info", info), ("nominal", nom1), ("streams", words1)):
+                assert mref.same_bits(unit[key], mine[idx]), "list %d: %s of the device form differs from the unit form of slot %d" % (which, key, slot)
+    print("mppi on a derived slot: %d rows, %d left out, largest rel_err %.3e" % (stats["rows"], stats["left_out"], stats["rel_err"]))
+    assert stats["left_out"] * 100 <= stats["rows"], stats
+    # a row whose candidates leave the table: dead there under list 0, alive to the end under list 1
+    steps = float(MPPI_H * MPPI_REPEAT)
+    moved = [r for r in ref.ROLL_LEAVERS if np.any(acts[0][3][r] < steps) and np.all(acts[1][3][r] == steps) and not mref.same_bits(acts[0][0][r], acts[1][0][r])]
+    assert moved, "no leaver's action changed with the re-stamp"
+    for r in moved:
+        assert not np.array_equal(acts[0][2][r], acts[1][2][r]) and rel_err(acts[1][0][r], acts[1][2][r]) < 1e-5 and rel_err(acts[0][0][r], acts[0][2][r]) < 1e-5
     s.close()
 
 

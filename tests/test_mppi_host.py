@@ -14,6 +14,7 @@ import mppi_ref as ref
 import rollout_ref as rr
 from f1tenth_gym_amd import Mppi, _ffi
 from f1tenth_gym_amd import mppi as mpm
+from mppi_ref import nominal_for
 from oracle import orc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -102,6 +103,29 @@ def test_struct_and_constants_match_the_header():
     assert "a built-in cost or argmax" not in src
 
 
+@needs_hipcc
+def test_lane_table_is_the_rule_s(tmp_path):
+    """tests/test_gpu_mppi_edges.py's table of k_mppi_update's lane groupings against the Python copy of mppi_group_lanes, and the copy
+    against the function itself — its text taken out of f110_kernels.hpp and compiled for the host — over every (K, H): a change of
+    the rule makes the table stale here, without a GPU"""
+    with open(os.path.join(os.path.dirname(HERE), "f1tenth_gym_amd", "csrc", "f110_kernels.hpp")) as f:
+        src = f.read()
+    fn = re.search(r"inline int mppi_group_lanes\(int K, int H\)\s*\{.*?\n\}", src, flags=re.S).group(0)
+    cpp, lib = str(tmp_path / "group_lanes.cpp"), str(tmp_path / "libgroup_lanes.so")
+    with open(cpp, "w") as f:
+        f.write(fn + '\nextern "C" int group_lanes(int K, int H) { return mppi_group_lanes(K, H); }\n')
+    subprocess.check_call([hipcc(), "-x", "c++", "-O1", "-std=c++17", "-fPIC", "-shared", cpp, "-o", lib], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    rule = C.CDLL(lib).group_lanes
+    assert sorted({c[3] for c in ref.LANE_CASES}) == [16, 32, 64, 128]
+    for K, H, M, GS, per, repeat in ref.LANE_CASES:
+        assert ref.group_lanes(K, H) == GS and 256 // GS == per, (K, H)
+    for K in range(1, mpm.MAX_K + 1):
+        for H in range(1, mpm.MAX_H + 1):
+            gs = ref.group_lanes(K, H)
+            assert rule(K, H) == gs, "mppi_group_lanes(%d, %d) = %d, the Python copy says %d" % (K, H, rule(K, H), gs)
+            assert gs in (16, 32, 64, 128) and gs >= 2 * H and gs >= min(K, 64) and (256 // gs) * K <= 1024      # (kMppiLdsCosts)
+
+
 # ---- the host instantiation ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def hh(tmp_path_factory):
@@ -150,12 +174,6 @@ def same_bits(got, want, keys=EXACT, what=""):
 def rows(map_name, m=6):
     start, params = rr.grid_rows(map_name)
     return start[:m], params[:m]
-
-
-def nominal_for(s, m, seed=5):
-    rng = np.random.default_rng(seed)
-    return np.stack([rng.uniform(0.5 * s["steer_min"], 0.5 * s["steer_max"], (m, s["horizon"])),
-                     rng.uniform(s["speed_min"], s["speed_max"], (m, s["horizon"]))], axis=-1)
 
 
 def streams_for(seed, m, base=0):
@@ -208,16 +226,25 @@ def test_draws_through_the_wedge_and_the_tail(hh):
             found = (seed, wedge, tail)
             break
     assert found is not None
+    # the seed the GPU test uses (tests/test_gpu_mppi_edges.py) still takes both branches
+    words = ref.stream_of(ref.ZIG_SEED, 0)
+    wedge = tail = 0
+    for k in range(1, K):
+        gw = ref.words_of(ref.generator(words, k << 20))
+        hh.hh_mppi_branches(gw.ctypes.data_as(C.c_void_p), 2 * H, out)
+        wedge, tail = wedge + out[0], tail + out[1]
+    assert wedge > 0 and tail > 0, (ref.ZIG_SEED, wedge, tail)
     so = rr.scan_oracle("example_map")
     start, params = rows("example_map", 1)
-    s = ref.settings(k=K, horizon=H, repeat=1, sigma_steer=0.05, sigma_speed=0.4, steer_min=-10.0, steer_max=10.0, speed_min=-50.0, speed_max=50.0)
+    s = ref.zig_settings()
+    assert (s["k"], s["horizon"]) == (K, H)
     nom, words = nominal_for(s, 1), ref.stream_of(found[0], 0)[None]
     want = ref.plan(s, so, start, params, nom, words, 1)
     got = harness(hh, s, so, start, params, nom, words, 1)
     same_bits(got, want, what=found)
     noise = (want["candidates"][0, 1:, :, 1] - nom[0, None, :, 1]) / s["sigma_speed"]
     steer = (want["candidates"][0, 1:, :, 0] - nom[0, None, :, 0]) / s["sigma_steer"]
-    assert max(np.abs(noise).max(), np.abs(steer).max()) > 3.6541528853610088 - 1e-6      # a draw from beyond the ziggurat's base layer
+    assert max(np.abs(noise).max(), np.abs(steer).max()) > ref.ZIG_BASE - 1e-6      # a draw from beyond the ziggurat's base layer
 
 
 # ---- cases by hand --------------------------------------------------------------------------------------------------------------------
