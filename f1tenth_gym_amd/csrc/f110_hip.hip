@@ -72,6 +72,8 @@ struct f110_sim {
     bool has_map = false;
     uint32_t step_magic = 0, step_shift = 0;  // ray -> agent division constants of the step launch
     int scan_tasks_per_wave = 1, num_cus = 256;  // consecutive 64-ray tasks per wave
+    int scan_tasks_agent = 1;                    // ... of k_scan_rays_agent in its env order (ENV_ORDER), whose waves share noise samples between an env's agents
+    bool scan_env_order = false;                 // k_scan_rays_agent<.., ENV_ORDER> where the launch allows it
     bool scan_tasks_auto = false;                // chosen by batch size (f110_config.scan_tasks_per_wave = 0)
     double ttc_side_max = INFINITY, ttc_cos_max = INFINITY;  // see f110_set_beam_tables
     int dir_stride = 0;              // > 0: dedupe enabled
@@ -763,6 +765,8 @@ int f110_create(const f110_config *cfg, f110_sim **out)
     }
     if (cfg->scan_tasks_per_wave > 0) {
         h->scan_tasks_per_wave = cfg->scan_tasks_per_wave;
+        h->scan_tasks_agent = cfg->scan_tasks_per_wave;
+        h->scan_env_order = cfg->scan_tasks_per_wave > 1 && cfg->num_agents > 1;   // the caller groups tasks: the grouping that can share
     } else {
         // default: 3 consecutive tasks per wave once the batch fills every wave slot ~8 times over
         // (amortises the per-wave set-up); small batches are bound by their longest rays and want
@@ -772,6 +776,18 @@ int f110_create(const f110_config *cfg, f110_sim **out)
         const size_t t = tasks / (slots * 8);
         h->scan_tasks_per_wave = t < 1 ? 1 : (t > 3 ? 3 : (int)t);
         h->scan_tasks_auto = true;
+        // k_scan_rays_agent<.., ENV_ORDER> (an env's agents sector by sector, the noise sample kept while the key stays): two cars per
+        // env, from the size at which waves take several tasks; an even count, so that no pair is split between two waves.
+        // 2 / 3 / 4 tasks per wave in env order, ms per step (profiles/env_order_bench.txt; agent-major with 3 per wave in brackets):
+        // 65 536 agents 0.6230 / 0.6358 / 0.6206 (0.6313), 49 152: 0.4963 / 0.5079 / 0.5001, 32 768: 0.3411 / 0.3504 / 0.3456 (0.3481),
+        // 16 384: 0.1882 / 0.1908 / 0.1911 (0.1909).  Four cars per env LOSE in env order — 65 536 agents 0.7092 / 0.7280 / 0.7214
+        // against 0.7062: a wave that walks four cars' same sector no longer walks one car's neighbouring sectors, whose rays
+        // start in the same cells — so every other count keeps the agent-major order unless the caller sets the tasks per wave.
+        h->scan_tasks_agent = h->scan_tasks_per_wave;
+        if (cfg->num_agents == 2 && t >= 3) {
+            h->scan_env_order = true;
+            h->scan_tasks_agent = t >= 16 ? 4 : 2;
+        }
     }
     CKH(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     CKH(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
@@ -3019,10 +3035,14 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
         j.order = (h->multi_map && begin == 0 && count == N) ? h->d_scan_order : nullptr;
         const bool cnt = j.lookups_total != nullptr;
         // agent-aligned launch geometry: whole 64-ray tasks per agent, so every wave belongs to one agent (and one map)
+        const bool env_order = h->scan_env_order && !h->multi_map && (scan == SCAN_AGENT || scan == SCAN_AGENT_SCHED);
         auto agent_grid = [&](uint32_t tpa, dim3 &grid, uint32_t &wpb, int tpw) {
             (void)rays_grid(j, h->scan_block, tpw);
             j.n_tasks = (uint32_t)count * tpa;
             j.first_pose = (uint32_t)begin;
+            // k_scan_rays_agent<.., ENV_ORDER> walks an env's agents sector by sector (scan_task_agent): the launch must cover whole envs
+            j.agents_per_env = (env_order && A > 1 && begin % A == 0 && count % A == 0 && scan_task_inv_ok(tpa, (uint32_t)A)) ? (uint32_t)A : 1u;
+            j.agents_inv = scan_task_inv(j.agents_per_env);
             wpb = (uint32_t)h->scan_block / 64u;
             const uint32_t waves = (j.n_tasks + j.tasks_per_wave - 1) / j.tasks_per_wave;
             grid = dim3((waves + wpb - 1) / wpb);
@@ -3052,7 +3072,7 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
         case SCAN_AGENT_SCHED: {
             // longest-first: last step's long tasks are served by the first blocks of the launch
             const uint32_t tpa = ((uint32_t)B + 63u) / 64u;
-            agent_grid(tpa, grid, wpb, h->scan_tasks_per_wave);
+            agent_grid(tpa, grid, wpb, env_order ? h->scan_tasks_agent : h->scan_tasks_per_wave);
             const uint32_t parity = h->task_epoch & 1u;
             j.sched = h->tsched[parity];
             j.epoch_r = h->task_epoch - 1u;
@@ -3068,7 +3088,12 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
             // which start first, march at the idle chip's latency — does the shorter chain beat the lost throughput?
             if (h->exp.scan_occupancy > 0 && h->scan_block == 64) slds = (size_t)(160 * 1024 / (4 * h->exp.scan_occupancy)) & ~(size_t)255;
 #endif
-            if (h->k.ident_rot)
+            const bool eo = j.agents_per_env > 1;
+            if (h->k.ident_rot && eo)
+                hipLaunchKernelGGL((k_scan_rays_agent<false, true, false, true, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
+            else if (eo)
+                hipLaunchKernelGGL((k_scan_rays_agent<false, false, false, true, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
+            else if (h->k.ident_rot)
                 hipLaunchKernelGGL((k_scan_rays_agent<false, true, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
             else
                 hipLaunchKernelGGL((k_scan_rays_agent<false, false, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
@@ -3076,7 +3101,7 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
         }
         case SCAN_AGENT: {
             const uint32_t tpa = ((uint32_t)B + 63u) / 64u;
-            agent_grid(tpa, grid, wpb, h->scan_tasks_per_wave);
+            agent_grid(tpa, grid, wpb, env_order ? h->scan_tasks_agent : h->scan_tasks_per_wave);
             size_t lds = 0;
 #ifdef F110_EXPERIMENTAL
             // fusion-feasibility probes: the occupancy a kernel with k_finalize_pair's 118 VGPRs
@@ -3097,6 +3122,13 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
                 break;
             }
 #endif
+#define AGENT_SCAN_ENV(ID)                                                                                                                            \
+    do {                                                                                                                                              \
+        if (cnt)                                                                                                                                      \
+            hipLaunchKernelGGL((k_scan_rays_agent<false, ID, true, false, false, true>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);  \
+        else                                                                                                                                          \
+            hipLaunchKernelGGL((k_scan_rays_agent<false, ID, false, false, false, true>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa); \
+    } while (0)
 #define AGENT_SCAN(PM, ID)                                                                                                           \
     do {                                                                                                                             \
         if (cnt)                                                                                                                     \
@@ -3106,11 +3138,16 @@ static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const d
     } while (0)
             if (h->multi_map)
                 AGENT_SCAN(true, false);
+            else if (j.agents_per_env > 1 && h->k.ident_rot)
+                AGENT_SCAN_ENV(true);
+            else if (j.agents_per_env > 1)
+                AGENT_SCAN_ENV(false);
             else if (h->k.ident_rot)
                 AGENT_SCAN(false, true);
             else
                 AGENT_SCAN(false, false);
 #undef AGENT_SCAN
+#undef AGENT_SCAN_ENV
             break;
         }
         default: {   // SCAN_FLAT: ray = agent * B + beam (row-major table, few beams, or — product build — beams

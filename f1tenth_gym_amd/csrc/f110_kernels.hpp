@@ -575,11 +575,12 @@ struct RayJob {
     uint32_t div_magic, div_shift;  // ray / B == umulhi(ray, magic) >> shift (0: plain division)
     int32_t pad_dir, dir_stride;    // k_scan_dirs_agent: distinct directions per agent, rounded up to whole 64-direction tasks
     const void *reserved_dir_ranges;
-    uint32_t first_pose, reserved_spec; // k_scan_rays_agent: the launch covers agents first_pose .. (env group)
+    uint32_t first_pose, agents_per_env; // k_scan_rays_agent: the launch covers agents first_pose .. (env group); agents_per_env (in a
+                                         // formerly reserved word: the layout stays) = the A of scan_task_agent, 1 = agent-major order
     unsigned long long *lookups_total;  // COUNT variants: table lookups of every marched ray, summed (or nullptr)
     // longest-first task order (k_scan_rays_agent<.., SCHED>): see TaskSched
     TaskSched sched;   // by value: the kernel argument segment is the one read a wave never waits long for
-    uint32_t epoch_r, epoch_w, long_blocks, pad_blocks;
+    uint32_t epoch_r, epoch_w, long_blocks, agents_inv;   // agents_inv (a formerly reserved word) = scan_task_inv(agents_per_env)
     // fusion-feasibility probe (experimental build): per-env count of finished scan tasks, reset by the last arriver
     uint32_t *env_done;
     uint32_t tasks_per_env, long_prio;
@@ -795,10 +796,13 @@ __device__ __forceinline__ void load_map_fast(ScanConst &km, const MapFast *__re
 #ifndef F110_SCAN_WAVES_EXPR
 #define F110_SCAN_WAVES_EXPR 8
 #endif
-template <bool PER_ENV_MAP, bool IDENT, bool COUNT, bool SCHED = false, bool ENVCNT = false>
+// ENV_ORDER: the tasks walk an env's agents sector by sector (scan_task_agent) and the wave keeps its noise samples across them; chosen
+// by the host where it was measured to pay (f110_create) or where the caller sets the tasks per wave, never with a per-env order
+template <bool PER_ENV_MAP, bool IDENT, bool COUNT, bool SCHED = false, bool ENVCNT = false, bool ENV_ORDER = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(F110_SCAN_WAVES_EXPR))) k_scan_rays_agent(RayJob j, ScanConst k, const MapFast *__restrict__ maps_fast,
                                                           const ScanConst *__restrict__ maps_full, uint32_t tasks_per_agent)
 {
+    static_assert(!(ENV_ORDER && PER_ENV_MAP), "a per-env order and the env order exclude each other");
     const uint32_t B = (uint32_t)k.num_beams;
     uint32_t tpw = j.tasks_per_wave;
     const uint32_t lane = threadIdx.x & 63u;
@@ -837,13 +841,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(F110_S
     ScanConst km = k;
     const ScanConst *cold = j.k_cold;
     int cur_slot = -1;
+    // ENV_ORDER: the tasks walk an env's agents sector by sector (scan_task_agent): the wave's consecutive tasks are
+    // the same 64 beams of the env's cars, and all agents of an env are on the same noise row (they are reset together; the
+    // reference gives every car a generator of the same seed) — the lane's sample stays in `held` while the wave-uniform key
+    // (row, sector) stays the same.  held_row < 0: nothing held.  A task on last step's long list is skipped before the key is
+    // touched, so it never leaves a key that the held sample does not match.
+    double held = 0.0;
+    int held_row = -1;
+    uint32_t held_sec = 0;
 #ifdef F110_EXPERIMENTAL
     if (j.trace) trace_loop = wall_clock64();
 #endif
     for (uint32_t t = 0; t < tpw; ++t) {
         const uint32_t task = __builtin_amdgcn_readfirstlane(long_pass ? long_task : wave * tpw + t);
         if (task >= j.n_tasks) break;
-        const uint32_t pl = task / tasks_per_agent;                 // scalar
+        uint32_t pl, sec = 0;                                       // scalar
+        if (!ENV_ORDER) pl = task / tasks_per_agent;
+        else scan_task_agent(task, tasks_per_agent, j.agents_per_env, j.agents_inv, pl, sec);
         const uint32_t p = (PER_ENV_MAP && j.order) ? ((cu32_t)j.order)[pl] : j.first_pose + pl;
         // the task's two cold words — its stamp on last step's long list and its agent's header, both written by
         // other kernels on other XCDs — are requested together: one memory round trip, not two in a row (a small
@@ -861,7 +875,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(F110_S
         if (j.trace && trace_hdr == 0ull) trace_hdr = wall_clock64();   // (reading the clock waits for the scalar loads above)
 #endif
         if (SCHED && !long_pass && stamp == j.epoch_r) continue;   // served by the long pass
-        const int b = (int)((task - pl * tasks_per_agent) * 64u + lane);
+        // (decided here, where the wave is still whole, so that the key lives in SGPRs.  The lanes that leave at b >= B below
+        // miss the load under a key that says "held" — and hold no beam in any task of that key: b depends on sector and lane only)
+        const bool load_nz = !ENV_ORDER || row < 0 || row != held_row || sec != held_sec;   // row -2 is the agent's own row: never shared
+        if (ENV_ORDER) {
+            held_row = row;
+            held_sec = sec;
+        }
+        const int b = (int)((ENV_ORDER ? sec : task - pl * tasks_per_agent) * 64u + lane);
         if (b >= (int)B) continue;
         if (PER_ENV_MAP && slot != cur_slot) {   // wave-uniform
             cold = maps_full + slot;
@@ -871,7 +892,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(F110_S
         // the beam's noise sample is requested before the march so that its latency hides under it:
         // row of the table / row cache, or (row -2) the row k_noise_rows left in this agent's scans[]
         const double *nrow = row >= 0 ? j.noise + (size_t)row * B : j.ranges + (size_t)p * B;   // scalar
-        const double nz = row != -1 ? nrow[b] : 0.0;
+        if (ENV_ORDER && load_nz) held = row != -1 ? nrow[b] : 0.0;   // wave-uniform
+        const double nz = ENV_ORDER ? held : (row != -1 ? nrow[b] : 0.0);
         double2 cs = k.cs[beam_dir_index(k, start, b)];
 #ifdef F110_EXPERIMENTAL
         if (j.trace && trace_ops == 0ull) {

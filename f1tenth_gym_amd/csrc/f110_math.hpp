@@ -803,6 +803,24 @@ F110_HD int beam_dir_index(const ScanConst &k, double start, int i)
     return idx >= k.theta_dis ? k.theta_dis - 1 : idx;
 }
 
+// The agent-aligned scan's task order (k_scan_rays_agent without a per-env order): task id -> (agent of the launch, 64-beam
+// sector of its scan), walking an env's agents sector by sector: env = task / (tpa * A), sector = (task % (tpa * A)) / A,
+// agent in env = task % A (tpa * A is a multiple of A).  Consecutive tasks are then the SAME 64 beams of one env's cars, which
+// share their noise row.  A = 1 is the agent-major order (agent = task / tpa, sector = task % tpa).  A bijection from
+// [0, E * A * tpa) onto [0, E * A) x [0, tpa).
+// One division, as the agent-major order had: the small remainder is divided by A through a reciprocal the host passes,
+// inv_A = scan_task_inv(A) = floor(2^32 / A) + 1 (0 for A = 1: nothing to divide).  With inv_A * A = 2^32 + e, 0 < e <= A,
+// umulhi(rem, inv_A) == rem / A whenever rem * e < 2^32, and rem < tpa * A: exact for tpa * A * A <= 2^32 (scan_task_inv_ok;
+// a launch beyond that walks agent-major, A = 1).
+F110_HD uint32_t scan_task_inv(uint32_t A) { return A > 1u ? (uint32_t)(0x100000000ull / A) + 1u : 0u; }
+F110_HD bool scan_task_inv_ok(uint32_t tpa, uint32_t A) { return (unsigned long long)tpa * A * A <= 0x100000000ull; }
+F110_HD void scan_task_agent(uint32_t task, uint32_t tpa, uint32_t A, uint32_t inv_A, uint32_t &agent, uint32_t &sector)
+{
+    const uint32_t tpe = tpa * A, env = task / tpe, rem = task - env * tpe;
+    sector = inv_A ? (uint32_t)(((unsigned long long)rem * inv_A) >> 32) : rem;
+    agent = env * A + (rem - sector * A);
+}
+
 // check_ttc_jit :188-217 — one beam's predicate
 F110_HD bool ttc_beam_hit(double range, double side_distance, double vel, double beam_cos, double thresh)
 {
