@@ -19,6 +19,7 @@ from .track_preview import TrackPreview  # noqa: F401
 from .neighbors import Neighbors  # noqa: F401
 from .rollout import Rollout  # noqa: F401
 from .mppi import Mppi  # noqa: F401
+from .particle_filter import ParticleFilter  # noqa: F401
 from .obstacles import Obstacles  # noqa: F401
 from . import render  # noqa: F401
 from .functional import (accl_constraints, steering_constraint, vehicle_dynamics_ks, vehicle_dynamics_st, pid, func_KS, func_ST,  # noqa: F401

@@ -135,6 +135,17 @@ class MppiSpec(C.Structure):
 MPPI_MAX_K, MPPI_MAX_H, MPPI_MAX_REPEAT = 256, 64, 16
 
 
+class PfSpec(C.Structure):
+    """struct f110_pf"""
+    _fields_ = [("particles", C.c_int32), ("n_beams", C.c_int32), ("beam_first", C.c_int32), ("beam_stride", C.c_int32),
+                ("sigma_x", C.c_double), ("sigma_y", C.c_double), ("sigma_theta", C.c_double), ("init_x", C.c_double),
+                ("init_y", C.c_double), ("init_theta", C.c_double), ("sigma_hit", C.c_double), ("clip", C.c_double),
+                ("squash", C.c_double), ("resample_frac", C.c_double)]
+
+
+PF_MAX_P, PF_MAX_BEAMS = 1024, 128
+
+
 class EpisodeViews(C.Structure):
     _fields_ = [("done", C.c_void_p), ("checkpoint_done", C.c_void_p), ("lap_times", C.c_void_p),
                 ("lap_counts", C.c_void_p), ("toggles", C.c_void_p), ("current_time", C.c_void_p)]
@@ -256,6 +267,8 @@ PROTOTYPES = {
     "f110_scan_path_stats": (C.c_int, [C.c_void_p, C.c_int32, _i64p]),
     "f110_pure_pursuit_batch": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _dp]),
     "f110_pure_pursuit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "f110_pure_pursuit_poses_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                 C.c_void_p]),
     "f110_scan_policy_device": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "f110_dynamics_batch": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int32, _dp, _dp]),
     "f110_pid_batch": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int32, _dp]),
@@ -285,6 +298,12 @@ PROTOTYPES = {
     "f110_mppi_get": (C.c_int, [C.c_void_p, _dp, _u64p]),
     "f110_mppi_put": (C.c_int, [C.c_void_p, _dp, _u64p]),
     "f110_mppi_batch": (C.c_int, [C.c_void_p, C.POINTER(MppiSpec), C.c_int32, _dp, _dp, _i32p, C.c_int32, _dp, _u64p, _dp, C.c_void_p, _dp, _dp, _dp]),
+    "f110_pf_set": (C.c_int, [C.c_void_p, C.POINTER(PfSpec), _i32p, C.c_int32, _u64p]),
+    "f110_pf_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f110_pf_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _u64p]),
+    "f110_pf_put": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _u64p]),
+    "f110_pf_batch": (C.c_int, [C.c_void_p, C.POINTER(PfSpec), C.c_int32, _dp, _dp, _i32p, C.c_int32, _dp, _dp, _dp, _u64p, _dp, C.c_void_p, _dp,
+                                _i32p, _dp, _dp]),
     "f110_render_device": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, _u8p]),
     "f110_obs_encode_device": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p, C.c_void_p]),
     "f110_obs_encode_batch": (C.c_int, [C.c_void_p, C.POINTER(ObsSpec), _dp, _dp, _i32p, C.c_int32, C.c_void_p]),

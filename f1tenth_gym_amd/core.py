@@ -1391,6 +1391,119 @@ class BatchSim(object):
                                          dptr(wgt)), self._h)
         return dict(actions=act, info=inf, candidates=cand, cost=cost, weight=wgt, nominal=nom, streams=words)
 
+    # ------------------------------------------------------------------ particle filter (f110_pf_*)
+    pf_filter, pf_agents = None, None
+
+    def set_particle_filter(self, spec, agents=None, seed=0, agent_base=0):
+        """arm the filter (particle_filter.ParticleFilter or a dict of its settings) on `agents` (indices into the N agents, strictly
+        ascending; None: every agent).  Agent n draws from PCG64(SeedSequence(seed, spawn_key=(agent_base + n,))): agent_base is the
+        handle's first agent in a larger run (a shard), so that the run draws the same numbers however it is split.  Every cloud
+        starts as zeros with uniform weights and becomes a cloud around its car at the first call after a reset (or through
+        set_pf_state); nothing is launched.  The filter acts in localize_device.  Returns the ParticleFilter."""
+        from .particle_filter import ParticleFilter
+        from .reset_sampler import stream_words
+        pf = ParticleFilter.coerce(spec)
+        pf.check_beams(self.B)
+        a = np.arange(self.N, dtype=np.int32) if agents is None else np.ascontiguousarray(np.asarray(agents).reshape(-1), dtype=np.int32)
+        if int(agent_base) < 0:
+            raise ValueError("agent_base must be >= 0, got %d" % int(agent_base))
+        if a.size == 0 or a.min() < 0 or a.max() >= self.N or np.any(np.diff(a) <= 0):
+            raise ValueError("agents must be a strictly ascending list of 1 .. %d indices within 0 .. %d" % (self.N, self.N - 1))
+        lo = int(a[0])
+        words = np.ascontiguousarray(stream_words(seed, int(a[-1]) - lo + 1, int(agent_base) + lo)[a - lo], dtype=np.uint64)
+        sp = pf.spec()
+        check(_ffi.lib().f110_pf_set(self._h, C.byref(sp), i32ptr(a), int(a.size), words.ctypes.data_as(_ffi._u64p)), self._h)
+        self.pf_filter, self.pf_agents = pf, a
+        return pf
+
+    def clear_particle_filter(self):
+        """disarm the filter and free its memory"""
+        check(_ffi.lib().f110_pf_set(self._h, None, None, 0, None), self._h)
+        self.pf_filter, self.pf_agents = None, None
+
+    def localize_device(self, d_pose, d_info=None):
+        """one localisation call: the armed agents' rows of the float64 DeviceArray d_pose [N][3] receive the estimate (x, y, theta)
+        from their live scan and the pose's move since the last call; the other rows are left alone.  d_info: a float32 DeviceArray
+        [N][4] whose armed rows receive particle_filter.INFO = (the effective sample size, the cloud's spread in metres, the
+        estimate's distance from the true pose, 1 if the cloud was resampled).  Enqueued on the handle's stream, per env block
+        behind a two-block step (no host wait)."""
+        if isinstance(d_pose, DeviceArray):
+            if tuple(d_pose.shape) != (self.N, 3) or d_pose.dtype != np.float64:
+                raise ValueError("d_pose must be a float64 DeviceArray of shape %s" % ((self.N, 3),))
+            p = d_pose.ptr
+        else:
+            p = int(d_pose)
+        ip = None if d_info is None else self._f32_out((self.N, 4), d_info, "d_info").ptr
+        check(_ffi.lib().f110_pf_device(self._h, p, ip), self._h)
+
+    def localize(self):
+        """localize_device into fresh host arrays: (pose float64 [N][3], info float32 [N][4]), NaN in the rows that are not armed"""
+        with DeviceArray(self, (self.N, 3), np.float64) as d_pose, DeviceArray(self, (self.N, 4), np.float32) as d_info:
+            d_pose.upload(np.full((self.N, 3), np.nan))
+            d_info.upload(np.full((self.N, 4), np.nan, dtype=np.float32))
+            self.localize_device(d_pose, d_info)
+            return d_pose.download(), d_info.download()
+
+    def _pf_armed(self):
+        if self.pf_filter is None:
+            raise _ffi.F110LibraryError("no filter is armed (set_particle_filter)")
+        return self.pf_filter, self.pf_agents.size
+
+    def get_pf_state(self):
+        """(particles float64 [M][P][3], weights [M][P], last [M][3], streams uint64 [M][4]) of the armed filter, in the armed
+        list's order: what to keep next to a state blob"""
+        pf, m = self._pf_armed()
+        X, W, last = np.zeros(pf.cloud_shape(m)), np.zeros((m, pf.particles)), np.zeros((m, 3))
+        words = np.zeros((m, 4), dtype=np.uint64)
+        check(_ffi.lib().f110_pf_get(self._h, dptr(X), dptr(W), dptr(last), words.ctypes.data_as(_ffi._u64p)), self._h)
+        return X, W, last, words
+
+    def set_pf_state(self, particles=None, weights=None, last=None, streams=None):
+        """restore get_pf_state's arrays, or seed the clouds: particles must be finite, a weight row finite, >= 0 and with a sum
+        above 0.  None leaves that part alone."""
+        pf, m = self._pf_armed()
+        X = None if particles is None else as_f64(particles, pf.cloud_shape(m))
+        W = None if weights is None else as_f64(weights, (m, pf.particles))
+        la = None if last is None else as_f64(last, (m, 3))
+        words = None
+        if streams is not None:
+            words = np.ascontiguousarray(streams, dtype=np.uint64)
+            if words.shape != (m, 4):
+                raise ValueError("streams must be uint64 [%d][4]" % m)
+        check(_ffi.lib().f110_pf_put(self._h, None if X is None else dptr(X), None if W is None else dptr(W), None if la is None else dptr(la),
+                                     None if words is None else words.ctypes.data_as(_ffi._u64p)), self._h)
+
+    def localize_rows(self, spec, poses, scans, particles, weights, last, streams, slot=0, fresh=None):
+        """unit form on host rows (the same kernels; the armed filter is not touched): poses [m][3] the true poses on map slot
+        `slot`, scans [m][num_beams], particles [m][P][3], weights [m][P], last [m][3], streams uint64 [m][4], fresh int32 [m] (the
+        rows' step_count: 0 = a fresh row; None: none is).  Returns a dict: pose [m][3], info float32 [m][4], noise [m][P][3],
+        ancestors int32 [m][P], expected [m][P][B'], logw [m][P], and particles, weights, last and streams after the call."""
+        from .particle_filter import ParticleFilter
+        pf = ParticleFilter.coerce(spec)
+        pf.check_beams(self.B)
+        po = as_f64(poses)
+        if po.ndim != 2 or po.shape[1] != 3:
+            raise ValueError("poses must be [m][3]")
+        m, P = po.shape[0], pf.particles
+        sc = as_f64(scans, (m, self.B))
+        X, W, la = as_f64(particles, pf.cloud_shape(m)).copy(), as_f64(weights, (m, P)).copy(), as_f64(last, (m, 3)).copy()
+        words = np.array(streams, dtype=np.uint64, order="C")
+        if words.shape != (m, 4):
+            raise ValueError("streams must be uint64 [%d][4]" % m)
+        fr = None
+        if fresh is not None:
+            fr = np.ascontiguousarray(fresh, dtype=np.int32)
+            if fr.shape != (m,):
+                raise ValueError("fresh must be [m]")
+        pose, inf = np.zeros((m, 3)), np.zeros((m, 4), dtype=np.float32)
+        noise, anc = np.zeros((m, P, 3)), np.zeros((m, P), dtype=np.int32)
+        expect, logw = np.zeros((m, P, pf.n_beams)), np.zeros((m, P))
+        sp = pf.spec()
+        check(_ffi.lib().f110_pf_batch(self._h, C.byref(sp), int(slot), dptr(po), dptr(sc), None if fr is None else i32ptr(fr), m, dptr(X), dptr(W),
+                                       dptr(la), words.ctypes.data_as(_ffi._u64p), dptr(pose), inf.ctypes.data, dptr(noise), i32ptr(anc),
+                                       dptr(expect), dptr(logw)), self._h)
+        return dict(pose=pose, info=inf, noise=noise, ancestors=anc, expected=expect, logw=logw, particles=X, weights=W, last=la, streams=words)
+
     # ------------------------------------------------------------------ rendering (f110_render_device, DESIGN §6c)
     def render_device(self, agents=None, width=64, height=64, view='ego', m_per_px=0.05, center=(0.0, 0.0), angle=0.0,
                       fwd_offset=0.0, layers=('map', 'cars'), car_size=None, rgb=False, palette=None, out=None):
@@ -1544,6 +1657,15 @@ class BatchSim(object):
         a = d_actions.ptr if isinstance(d_actions, DeviceArray) else int(d_actions)
         check(_ffi.lib().f110_pure_pursuit_device(self._h, w, int(num_waypoints), float(lookahead), float(vgain), float(wheelbase),
                                                   float(max_reacquire), a), self._h)
+
+    def pure_pursuit_poses_device(self, d_waypoints, num_waypoints, d_poses, d_actions, lookahead, vgain, wheelbase, max_reacquire=20.0):
+        """the same policy on poses held in device memory, d_poses float64 [N][3] (localize_device's estimates, say) instead of the
+        live poses; a NaN pose gets (0, 4.0)"""
+        w = d_waypoints.ptr if isinstance(d_waypoints, DeviceArray) else int(d_waypoints)
+        p = d_poses.ptr if isinstance(d_poses, DeviceArray) else int(d_poses)
+        a = d_actions.ptr if isinstance(d_actions, DeviceArray) else int(d_actions)
+        check(_ffi.lib().f110_pure_pursuit_poses_device(self._h, w, int(num_waypoints), p, float(lookahead), float(vgain), float(wheelbase),
+                                                        float(max_reacquire), a), self._h)
 
     def scan_policy_device(self, d_actions, steer_gain=0.5, steer_max=0.4189, sector_limit=1.75, v_lo=1.0, v_hi=6.0, d_ref=6.0):
         """a reactive policy that reads the step's scans where they are (f110_scan_policy_device: steer towards the most open

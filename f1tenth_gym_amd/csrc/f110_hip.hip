@@ -245,6 +245,22 @@ struct f110_sim {
         double *d_end = nullptr;         // [m][K][2] (only with a track weight)
     } mppi;
     U128 *d_mppi_jump = nullptr;         // [2][kMppiJumps] the candidates' jump constants (from the first arming on)
+    // particle filter (f110_pf_set): m == 0: disarmed.  The clouds, the weights, the last poses and the streams are the filter's own memory.
+    struct Pf {
+        PfSpec sp{};
+        int m = 0, cur = 0;              // d_X[cur] is the stored cloud; a call moves it into d_X[cur ^ 1] and flips
+        std::vector<int32_t> agents;     // the armed list, ascending
+        int32_t *d_agents = nullptr;     // [m]
+        uint64_t *d_streams = nullptr;   // [m][4]
+        double *d_X[2] = {nullptr, nullptr};   // [m][P][3]
+        double *d_W = nullptr;           // [m][P]
+        double *d_last = nullptr;        // [m][3]
+        double *d_cum = nullptr;         // [m][P]
+        double *d_logw = nullptr;        // [m][P]
+        PfPlan *d_plan = nullptr;        // [m]
+        PfHdr *d_hdr = nullptr;          // [m][P]
+    } pf;
+    U128 *d_pf_jump = nullptr;           // [2][kPfJumps] the sub-streams' jump constants (from the first arming on)
     // rendering (f110_render_device): slot 0's occupancy grid, the slot table as last uploaded, per-frame / per-agent records
     uint8_t *d_occ0 = nullptr;
     std::vector<RenderSlot> render_slots;
@@ -367,6 +383,7 @@ static int mppi_ready(f110_sim *h);                                             
 static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, float *d_info);
 static int mppi_upload_tracks(f110_sim *h);
 static void mppi_free(f110_sim *h);
+static void pf_free(f110_sim *h);                                                     // (below, with the particle filter)
 struct EnvBlocks {
     EnvBlock b[kMaxEnvBlocks];
     int n = 0;
@@ -1071,6 +1088,8 @@ void f110_destroy(f110_sim *h)
     if (h->d_gap_assign) (void)hipFree(h->d_gap_assign);
     mppi_free(h);
     if (h->d_mppi_jump) (void)hipFree(h->d_mppi_jump);
+    pf_free(h);
+    if (h->d_pf_jump) (void)hipFree(h->d_pf_jump);
     {
         void *rp[] = {h->d_occ0, h->d_render_slots, h->d_render_frames, h->d_render_cars, h->d_render_agents, h->d_render_stage};
         for (void *p : rp)
@@ -5807,5 +5826,353 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
     if (h_cost) TRY(sc.down(h_cost, dcost, cands));
     if (h_weight) TRY(sc.down(h_weight, dw, cands));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- particle filter (f110_pf_*, include/f110.h) ------------------------------------------------------------------------------------
+// the spec's refusals; on success the kernels' spec
+static int pf_check_spec(f110_sim *h, const f110_pf *p, PfSpec &o)
+{
+    if (!p) return fail(h, F110_ERR_INVALID, "pf: null spec");
+    if (p->particles < 1 || p->particles > F110_PF_MAX_P) return fail(h, F110_ERR_INVALID, "pf: particles = %d is outside 1..%d", p->particles, (int)F110_PF_MAX_P);
+    if (p->n_beams < 1 || p->n_beams > F110_PF_MAX_BEAMS) return fail(h, F110_ERR_INVALID, "pf: n_beams = %d is outside 1..%d", p->n_beams, (int)F110_PF_MAX_BEAMS);
+    if (p->beam_first < 0 || p->beam_stride < 1) return fail(h, F110_ERR_INVALID, "pf: beam_first = %d must be >= 0 and beam_stride = %d >= 1", p->beam_first, p->beam_stride);
+    if ((long long)p->beam_first + (long long)(p->n_beams - 1) * p->beam_stride >= (long long)h->cfg.num_beams)
+        return fail(h, F110_ERR_INVALID, "pf: beam %lld is past the scan's %d beams", (long long)p->beam_first + (long long)(p->n_beams - 1) * p->beam_stride, h->cfg.num_beams);
+    const double d[] = {p->sigma_x, p->sigma_y, p->sigma_theta, p->init_x, p->init_y, p->init_theta, p->sigma_hit, p->squash, p->resample_frac};
+    for (double x : d)
+        if (!std::isfinite(x)) return fail(h, F110_ERR_INVALID, "pf: every setting but the clip must be finite");
+    if (p->clip != p->clip) return fail(h, F110_ERR_INVALID, "pf: clip is NaN");
+    if (p->sigma_x < 0 || p->sigma_y < 0 || p->sigma_theta < 0 || p->init_x < 0 || p->init_y < 0 || p->init_theta < 0)
+        return fail(h, F110_ERR_INVALID, "pf: the sigmas must be >= 0");
+    if (!(p->sigma_hit > 0) || !(p->clip > 0) || !(p->squash > 0)) return fail(h, F110_ERR_INVALID, "pf: sigma_hit, clip and squash must be > 0");
+    if (p->resample_frac < 0) return fail(h, F110_ERR_INVALID, "pf: resample_frac must be >= 0");
+    o = PfSpec{};
+    o.P = p->particles, o.B = p->n_beams, o.beam_first = p->beam_first, o.beam_stride = p->beam_stride;
+    o.sigma_x = p->sigma_x, o.sigma_y = p->sigma_y, o.sigma_theta = p->sigma_theta;
+    o.init_x = p->init_x, o.init_y = p->init_y, o.init_theta = p->init_theta;
+    o.sigma_hit = p->sigma_hit, o.clip = p->clip, o.squash = p->squash, o.resample_frac = p->resample_frac;
+    return F110_OK;
+}
+
+static int pf_check_count(f110_sim *h, const PfSpec &sp, int m)
+{
+    if ((size_t)m * sp.P * sp.B >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "pf: %d agents x %d particles x %d beams do not fit 31 bits", m, sp.P, sp.B);
+    return F110_OK;
+}
+
+static void pf_free(f110_sim::Pf &p)
+{
+    void *ptrs[] = {p.d_agents, p.d_streams, p.d_X[0], p.d_X[1], p.d_W, p.d_last, p.d_cum, p.d_logw, p.d_plan, p.d_hdr};
+    for (void *q : ptrs)
+        if (q) (void)hipFree(q);   // (hipFree waits for the calls in flight that read it)
+    p = f110_sim::Pf{};
+}
+
+static void pf_free(f110_sim *h) { pf_free(h->pf); }
+
+// the sub-streams' jump constants in device memory
+static int pf_jump_ensure(f110_sim *h)
+{
+    if (h->d_pf_jump) return F110_OK;
+    std::vector<U128> t(2 * (size_t)kPfJumps);
+    pf_jump_table(t.data(), t.data() + kPfJumps);
+    TRY(dmalloc(h, &h->d_pf_jump, t.size()));
+    HIPCHK(h, hipMemcpy(h->d_pf_jump, t.data(), t.size() * sizeof(U128), hipMemcpyHostToDevice));
+    return F110_OK;
+}
+
+// a caller's cloud and weights: finite particles; weight rows that are finite, >= 0 and sum to more than 0
+static int pf_check_cloud(f110_sim *h, const PfSpec &sp, const double *particles, const double *weights, size_t rows)
+{
+    if (particles)
+        for (size_t q = 0; q < rows * sp.P * 3; ++q)
+            if (!std::isfinite(particles[q])) return fail(h, F110_ERR_INVALID, "pf: particles[%zu][%zu][%d] is not finite", q / (3 * (size_t)sp.P), q / 3 % sp.P, (int)(q % 3));
+    if (weights)
+        for (size_t r = 0; r < rows; ++r) {
+            double sum = 0.0;
+            for (int p = 0; p < sp.P; ++p) {
+                const double w = weights[r * sp.P + p];
+                if (!std::isfinite(w) || w < 0) return fail(h, F110_ERR_INVALID, "pf: weights[%zu][%d] = %g is negative or not finite", r, p, w);
+                sum += w;
+            }
+            if (!(sum > 0)) return fail(h, F110_ERR_INVALID, "pf: the weights of row %zu do not sum to more than 0", r);
+        }
+    return F110_OK;
+}
+
+// armed indices [j.i0, j.i0 + j.count): the plan, the move, the rays, the update, one behind the other on `st`
+static void pf_launch(const PfJob &j, const ScanConst &k, hipStream_t st)
+{
+    if (j.count <= 0) return;
+    const int P = j.sp.P;
+    const size_t parts = (size_t)j.count * P;
+    const dim3 block(256);
+    hipLaunchKernelGGL(k_pf_plan, grid1d((size_t)j.count, 4), block, (size_t)4 * P * sizeof(double), st, j);
+    hipLaunchKernelGGL(k_pf_move, grid1d(parts, 256), block, 0, st, j, k);
+    const int ppw = pf_particles_per_group(j.sp.B);
+    hipLaunchKernelGGL(k_pf_sense, grid1d(parts, ppw), block, 0, st, j, k, ppw);
+    const int gs = pf_group_lanes(P), per = 256 / gs;
+    hipLaunchKernelGGL(k_pf_update, grid1d((size_t)j.count, per), block, (size_t)per * 6 * P * sizeof(double), st, j, gs);
+}
+
+// what every job of this handle shares: the generator's tables, the lidar's offset, the scan's width
+static void pf_job_common(f110_sim *h, PfJob &j)
+{
+    j.zk = h->d_zig_k;
+    j.zw = h->d_zig_w;
+    j.zf = h->d_zig_f;
+    j.jump_a = h->d_pf_jump;
+    j.jump_g = h->d_pf_jump + kPfJumps;
+    j.lidar_dist = h->dev.lidar_dist;
+    j.num_beams = h->cfg.num_beams;
+}
+
+static int pf_ready(f110_sim *h)
+{
+    if (h->pf.m == 0) return fail(h, F110_ERR_STATE, "pf: no filter is armed (f110_pf_set)");
+    if (!h->has_map) return fail(h, F110_ERR_STATE, "pf: the map is not set");
+    return F110_OK;
+}
+
+// the armed filter over the agents of one env block: the ascending list is split at the block's bounds
+static int pf_launch_armed(f110_sim *h, const EnvBlock &b, double *d_pose, float *d_info)
+{
+    const f110_sim::Pf &p = h->pf;
+    const int A = h->cfg.num_agents;
+    const size_t N = (size_t)h->N;
+    PfJob j{};
+    j.maps = h->multi_map ? h->d_maps_full : cold_consts(h);
+    if (!j.maps) return fail(h, F110_ERR_HIP, "pf: constant upload failed");
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.A = A;
+    j.N = h->N;
+    j.agents = p.d_agents;
+    j.px = h->dev.snap_pose;   // the post-step pose of the observation
+    j.py = h->dev.snap_pose + N;
+    j.pth = h->dev.snap_pose + 2 * N;
+    j.scans = h->dev.scans;
+    j.step_count = h->dev.step_count;
+    pf_job_common(h, j);
+    j.streams = p.d_streams;
+    j.X_in = p.d_X[p.cur];
+    j.X_out = p.d_X[p.cur ^ 1];
+    j.W = p.d_W;
+    j.last = p.d_last;
+    j.cum = p.d_cum;
+    j.plan = p.d_plan;
+    j.hdr = p.d_hdr;
+    j.logw = p.d_logw;
+    j.pose = d_pose;
+    j.info = d_info;
+    j.sp = p.sp;
+    const int32_t n0 = b.e0 * A, n1 = (b.e0 + b.count) * A;
+    j.i0 = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n0) - p.agents.begin());
+    j.count = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n1) - p.agents.begin()) - j.i0;
+    pf_launch(j, h->k, b.stream);
+    return F110_OK;
+}
+
+int f110_pf_set(f110_sim *h, const f110_pf *spec, const int32_t *h_agents, int32_t m, const uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (!spec && !h_agents && m == 0 && !h_streams) {   // disarm
+        ENTER(h);
+        pf_free(h);
+        return F110_OK;
+    }
+    if (!spec || !h_agents || !h_streams) return fail(h, F110_ERR_INVALID, "pf: a spec, the agents and their streams, or NULL, NULL, 0, NULL");
+    PfSpec sp;
+    TRY(pf_check_spec(h, spec, sp));
+    if (m < 1 || m > h->N) return fail(h, F110_ERR_INVALID, "pf: %d armed agents, but the handle has 1..%d", m, h->N);
+    for (int32_t i = 0; i < m; ++i) {
+        if (h_agents[i] < 0 || h_agents[i] >= h->N) return fail(h, F110_ERR_INVALID, "pf: agents[%d] = %d is outside 0..%d", i, h_agents[i], h->N - 1);
+        if (i > 0 && h_agents[i] <= h_agents[i - 1]) return fail(h, F110_ERR_INVALID, "pf: the agents are not strictly ascending at [%d]", i);
+    }
+    TRY(pf_check_count(h, sp, m));
+    ENTER(h);
+    TRY(pf_jump_ensure(h));
+    f110_sim::Pf p;   // built aside: a failure below leaves the filter that is armed (if any) as it is
+    const size_t M = (size_t)m, parts = M * sp.P;
+    std::vector<double> w(parts, 1.0 / (double)sp.P);
+    int rc = dmalloc(h, &p.d_agents, M);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_streams, 4 * M);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_X[0], 3 * parts);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_X[1], 3 * parts);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_W, parts);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_last, 3 * M);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_cum, parts);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_logw, parts);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_plan, M);
+    if (rc == F110_OK) rc = dmalloc(h, &p.d_hdr, parts);
+    if (rc == F110_OK && (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(p.d_W, w.data(), parts * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemset(p.d_X[0], 0, 3 * parts * sizeof(double)) != hipSuccess ||
+                          hipMemset(p.d_X[1], 0, 3 * parts * sizeof(double)) != hipSuccess ||
+                          hipMemset(p.d_last, 0, 3 * M * sizeof(double)) != hipSuccess))
+        rc = fail(h, F110_ERR_HIP, "pf: the upload failed");
+    if (rc != F110_OK) {
+        pf_free(p);
+        return rc;
+    }
+    p.sp = sp;
+    p.agents.assign(h_agents, h_agents + m);
+    p.m = m;
+    pf_free(h);
+    h->pf = std::move(p);
+    return F110_OK;
+}
+
+int f110_pf_device(f110_sim *h, double *d_pose, float *d_info)
+{
+    if (!h || !d_pose) return fail(h, F110_ERR_INVALID, "pf: null argument");
+    TRY(pf_ready(h));
+    EnvBlocks w;   // behind a two-block step: each block's armed agents on the block's own stream (an agent reads and writes its own rows)
+    TRY(env_blocks_follow(h, w));
+    for (const EnvBlock &b : w) TRY(pf_launch_armed(h, b, d_pose, d_info));
+    HIPCHK(h, hipGetLastError());
+    h->pf.cur ^= 1;
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_pf_get(f110_sim *h, double *h_particles, double *h_weights, double *h_last, uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    const f110_sim::Pf &p = h->pf;
+    if (p.m == 0) return fail(h, F110_ERR_STATE, "pf: no filter is armed (f110_pf_set)");
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t M = (size_t)p.m, parts = M * p.sp.P;
+    if (h_particles) HIPCHK(h, hipMemcpy(h_particles, p.d_X[p.cur], 3 * parts * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_weights) HIPCHK(h, hipMemcpy(h_weights, p.d_W, parts * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_last) HIPCHK(h, hipMemcpy(h_last, p.d_last, 3 * M * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_streams) HIPCHK(h, hipMemcpy(h_streams, p.d_streams, 4 * M * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return F110_OK;
+}
+
+int f110_pf_put(f110_sim *h, const double *h_particles, const double *h_weights, const double *h_last, const uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    const f110_sim::Pf &p = h->pf;
+    if (p.m == 0) return fail(h, F110_ERR_STATE, "pf: no filter is armed (f110_pf_set)");
+    const size_t M = (size_t)p.m, parts = M * p.sp.P;
+    TRY(pf_check_cloud(h, p.sp, h_particles, h_weights, M));
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h_particles) HIPCHK(h, hipMemcpy(p.d_X[p.cur], h_particles, 3 * parts * sizeof(double), hipMemcpyHostToDevice));
+    if (h_weights) HIPCHK(h, hipMemcpy(p.d_W, h_weights, parts * sizeof(double), hipMemcpyHostToDevice));
+    if (h_last) HIPCHK(h, hipMemcpy(p.d_last, h_last, 3 * M * sizeof(double), hipMemcpyHostToDevice));
+    if (h_streams) HIPCHK(h, hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return F110_OK;
+}
+
+int f110_pf_batch(f110_sim *h, const f110_pf *spec, int32_t slot, const double *h_poses, const double *h_scans, const int32_t *h_fresh, int32_t m,
+                  double *h_particles, double *h_weights, double *h_last, uint64_t *h_streams, double *h_pose, float *h_info, double *h_noise,
+                  int32_t *h_anc, double *h_expect, double *h_logw)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    PfJob j{};
+    TRY(pf_check_spec(h, spec, j.sp));
+    if (m < 0 || (m > 0 && (!h_poses || !h_scans || !h_particles || !h_weights || !h_last || !h_streams))) return fail(h, F110_ERR_INVALID, "pf: bad argument");
+    TRY(pf_check_count(h, j.sp, m));
+    if (!h->has_map) return fail(h, F110_ERR_STATE, "pf: the map is not set");
+    TRY(unit_slot_check(h, "pf", slot));
+    if (m == 0) return F110_OK;
+    const size_t M = (size_t)m, P = (size_t)j.sp.P, parts = M * P, B = (size_t)h->cfg.num_beams;
+    TRY(pf_check_cloud(h, j.sp, h_particles, h_weights, M));
+    std::vector<double> cols(3 * M);
+    for (size_t r = 0; r < M; ++r)
+        for (int c = 0; c < 3; ++c) cols[(size_t)c * M + r] = h_poses[3 * r + c];
+    ScanConst kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
+    ENTER(h);
+    TRY(pf_jump_ensure(h));
+    Scratch sc(h);
+    double *dcols = nullptr, *dscans = nullptr, *dX0 = nullptr, *dX1 = nullptr, *dW = nullptr, *dlast = nullptr, *dcum = nullptr, *dlogw = nullptr;
+    double *dpose = nullptr, *dnoise = nullptr, *dexp = nullptr;
+    int32_t *dfresh = nullptr, *danc = nullptr;
+    uint64_t *dstr = nullptr;
+    ScanConst *dk = nullptr;
+    PfPlan *dplan = nullptr;
+    PfHdr *dhdr = nullptr;
+    float *dinfo = nullptr;
+    TRY(sc.up(cols.data(), cols.size(), &dcols));
+    TRY(sc.up(h_scans, M * B, &dscans));
+    TRY(sc.up(&kc, 1, &dk));
+    if (h_fresh) TRY(sc.up(h_fresh, M, &dfresh));
+    TRY(sc.up((const double *)h_particles, 3 * parts, &dX0));
+    TRY(sc.up<double>(nullptr, 3 * parts, &dX1));
+    TRY(sc.up((const double *)h_weights, parts, &dW));
+    TRY(sc.up((const double *)h_last, 3 * M, &dlast));
+    TRY(sc.up((const uint64_t *)h_streams, 4 * M, &dstr));
+    TRY(sc.up<double>(nullptr, parts, &dcum));
+    TRY(sc.up<double>(nullptr, parts, &dlogw));
+    TRY(sc.up<PfPlan>(nullptr, M, &dplan));
+    TRY(sc.up<PfHdr>(nullptr, parts, &dhdr));
+    TRY(sc.up<double>(nullptr, 3 * M, &dpose));
+    TRY(sc.up<float>(nullptr, 4 * M, &dinfo));
+    if (h_noise) TRY(sc.up<double>(nullptr, 3 * parts, &dnoise));
+    if (h_anc) TRY(sc.up<int32_t>(nullptr, parts, &danc));
+    if (h_expect) TRY(sc.up<double>(nullptr, parts * j.sp.B, &dexp));
+    j.maps = dk;
+    j.A = 1;
+    j.N = m;
+    j.count = m;
+    j.px = dcols;
+    j.py = dcols + M;
+    j.pth = dcols + 2 * M;
+    j.scans = dscans;
+    j.step_count = dfresh;
+    pf_job_common(h, j);
+    j.streams = dstr;
+    j.X_in = dX0;
+    j.X_out = dX1;
+    j.W = dW;
+    j.last = dlast;
+    j.cum = dcum;
+    j.plan = dplan;
+    j.hdr = dhdr;
+    j.logw = dlogw;
+    j.noise = dnoise;
+    j.anc = danc;
+    j.expect = dexp;
+    j.pose = dpose;
+    j.info = dinfo;
+    pf_launch(j, h->k, h->stream);
+    HIPCHK(h, hipGetLastError());
+    TRY(sc.down(h_particles, dX1, 3 * parts));
+    TRY(sc.down(h_weights, dW, parts));
+    TRY(sc.down(h_last, dlast, 3 * M));
+    TRY(sc.down(h_streams, dstr, 4 * M));
+    if (h_pose) TRY(sc.down(h_pose, dpose, 3 * M));
+    if (h_info) TRY(sc.down(h_info, dinfo, 4 * M));
+    if (h_noise) TRY(sc.down(h_noise, dnoise, 3 * parts));
+    if (h_anc) TRY(sc.down(h_anc, danc, parts));
+    if (h_expect) TRY(sc.down(h_expect, dexp, parts * j.sp.B));
+    if (h_logw) TRY(sc.down(h_logw, dlogw, parts));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// the example policy on poses the caller holds in device memory (the filter's estimates): f110_pure_pursuit_device's launch per env
+// block, reading d_poses [N][3] instead of the live state
+int f110_pure_pursuit_poses_device(f110_sim *h, const double *d_waypoints, int32_t M, const double *d_poses, double lookahead, double vgain,
+                                   double wheelbase, double max_reacquire, double *d_actions)
+{
+    TRY(check_planner_args(h, d_waypoints, M, lookahead));
+    if (!d_poses || !d_actions) return fail(h, F110_ERR_INVALID, "pure pursuit: null poses or actions buffer");
+    EnvBlocks w;
+    TRY(env_blocks_follow(h, w));
+    const int A = h->cfg.num_agents;
+    for (const EnvBlock &b : w) {
+        const size_t i0 = (size_t)b.e0 * A;
+        const int n = b.count * A;
+        const double *p = d_poses + 3 * i0;
+        hipLaunchKernelGGL(k_pure_pursuit, grid1d((size_t)n * kPlanLanes, 256), dim3(256), 0, b.stream, d_waypoints, M, p, p + 1, p + 2, 3, n, lookahead, vgain,
+                           wheelbase, max_reacquire, d_actions + 2 * i0);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->touched = false;
     return F110_OK;
 }

@@ -5083,3 +5083,235 @@ __global__ void __launch_bounds__(256) k_mppi_update(MppiJob j, int GS)
     st[0] = s1.hi;
     st[1] = s1.lo;
 }
+
+// ---- particle filter (f110_pf_*; include/f110.h states the rule, f110_math.hpp / f110_rng.hpp pf_* the arithmetic) ----
+// Four kernels, one behind the other on a stream, over the armed indices [i0, i0 + count):
+// k_pf_plan: a wave per armed agent, four agents per workgroup.  The stored weights go into LDS; lane 0 sums their squares (the ESS),
+//  takes the decision, turns them into their cumulative sums in place and draws u from sub-stream 0; the wave stores the sums.  Lane 0
+//  also forms the odometry delta, once per agent instead of once per particle.
+// k_pf_move: one lane per (armed index, particle), particle-minor.  A lane jumps the agent's generator to its sub-stream with entry
+//  p + 1 of the jump table, draws its three normals, finds its ancestor by bisection in the cumulative sums, applies the fresh or the
+//  motion rule and writes into the OTHER cloud buffer (a lane reads its ancestor's row, which another lane would overwrite).  It also
+//  leaves the particle's ray header: the lidar position, the scan's start index and the first sample, which the particle's beams share.
+// k_pf_sense, the hot path of count * P * B' rays: lanes are (particle, beam), beam-minor; a workgroup holds as many whole particles
+//  as fit 256 lanes (ppw = 256 / B'), so one particle's beams sit in adjacent lanes and walk neighbouring cells, as a scan task's 64
+//  beams do, and no particle straddles a workgroup.  The ray is the scan's: beam_dir_index, the handle's trig table, the slot's table
+//  through trace_from_first (the fixed-point march with its exact fall-back) or, without a padded copy, march_from_first.  The B'
+//  terms go through LDS and the particle's first lane sums them ascending.
+// k_pf_update: a group of GS lanes per armed agent (the power of two >= min(P, 256), at least 16), 256 / GS agents per workgroup.
+//  Lanes spread over the particles for everything per particle (one exp, one sincos, the products); the sums are each walked ascending
+//  by ONE lane of the group over LDS — eta by lane 0, then the five sums of the estimate by lanes 0 .. 4 side by side, then the
+//  spread by lane 0 — and handed on through an LDS slot.  Idle groups shadow the last agent through the barriers and store nothing.
+struct PfJob {
+    const ScanConst *maps;       // [slots] (or one: the unit form's slot)
+    const int32_t *env_map;      // [E] or nullptr
+    int32_t A, num_beams;
+    int32_t i0, count, N, pad_;
+    const int32_t *agents;       // [M] the armed list, or nullptr: armed index i is row i (the unit form)
+    const double *px, *py, *pth; // [N] the true poses
+    const double *scans;         // [N][num_beams]
+    const int32_t *step_count;   // [N] or nullptr (no row is fresh)
+    double lidar_dist;
+    const uint64_t *zk;          // the ziggurat's tables
+    const double *zw, *zf;
+    const U128 *jump_a, *jump_g; // [kPfJumps]
+    uint64_t *streams;           // [M][4]
+    const double *X_in;          // [M][P][3] the stored cloud
+    double *X_out;               // [M][P][3] the moved cloud (the stored one after the call)
+    double *W;                   // [M][P]
+    double *last;                // [M][3]
+    double *cum;                 // [M][P]
+    PfPlan *plan;                // [M]
+    PfHdr *hdr;                  // [M][P]
+    double *logw;                // [M][P]
+    double *noise;               // [M][P][3] or nullptr (the unit form's outputs)
+    int32_t *anc;                // [M][P] or nullptr
+    double *expect;              // [M][P][B'] or nullptr
+    double *pose;                // [N][3]
+    float *info;                 // [N][4] or nullptr
+    PfSpec sp;
+};
+
+__global__ void __launch_bounds__(256) k_pf_plan(PfJob j)
+{
+    extern __shared__ double s_pf_plan[];   // [4][P]
+    const int P = j.sp.P;
+    const int grp = (int)threadIdx.x >> 6, t = (int)threadIdx.x & 63;
+    const long long a_raw = (long long)blockIdx.x * 4 + grp;
+    const bool live = a_raw < j.count;
+    const int i = j.i0 + (int)(live ? a_raw : j.count - 1);
+    const int n = j.agents ? j.agents[i] : i;
+    double *c = s_pf_plan + (size_t)grp * P;
+    const double *W = j.W + (size_t)i * P;
+    for (int p = t; p < P; p += 64) c[p] = W[p];
+    __syncthreads();
+    if (t == 0 && live) {
+        PfPlan pl;
+        pl.fresh = (j.step_count && j.step_count[n] == 0) ? 1 : 0;
+        pl.u = pf_uniform(j.streams + 4 * (size_t)i);
+        pl.resample = (!pl.fresh && pf_decide(j.sp, pf_ess(c, P))) ? 1 : 0;
+        pf_cumulate(c, P, c);
+        pl.ctot = c[P - 1];
+        pf_odometry(j.last + 3 * (size_t)i, j.px[n], j.py[n], j.pth[n], pl.a, pl.b, pl.dth);
+        j.plan[i] = pl;
+    }
+    __syncthreads();
+    if (!live) return;
+    double *cum = j.cum + (size_t)i * P;
+    for (int p = t; p < P; p += 64) cum[p] = c[p];
+}
+
+__global__ void __launch_bounds__(256) k_pf_move(PfJob j, ScanConst k)
+{
+    const int P = j.sp.P;
+    const long long total = (long long)j.count * P;
+    const long long g = (long long)blockIdx.x * 256 + (int)threadIdx.x;
+    if (g >= total) return;
+    const int a = (int)(g / P), p = (int)(g - (long long)a * P);
+    const int i = j.i0 + a;
+    const int n = j.agents ? j.agents[i] : i;
+    const size_t G = (size_t)i * P + (size_t)p;
+    const PfPlan pl = j.plan[i];
+    double e[3];
+    {
+        const ZigTables zt = {j.zk, j.zw, j.zf};
+        pf_normals(j.streams + 4 * (size_t)i, j.jump_a[p + 1], j.jump_g[p + 1], zt, e);
+    }
+    if (j.noise) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) j.noise[3 * G + q] = e[q];
+    }
+    double X[3];
+    int anc = p;
+    if (pl.fresh) {
+        pf_fresh(j.sp, j.px[n], j.py[n], j.pth[n], e, X);
+    } else {
+        if (pl.resample) anc = pf_ancestor(j.cum + (size_t)i * P, P, p, pl.u, pl.ctot);
+        pf_move(j.sp, pl.a, pl.b, pl.dth, j.X_in + ((size_t)i * P + (size_t)anc) * 3, e, X);
+    }
+    if (pl.fresh | pl.resample) j.W[G] = 1.0 / (double)P;
+    if (j.anc) j.anc[G] = anc;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) j.X_out[3 * G + q] = X[q];
+    const ScanConst &km = j.maps[j.env_map ? j.env_map[n / j.A] : 0];
+    double lp[3];
+    pf_lidar_pose(X, j.lidar_dist, lp);
+    PfHdr hd;
+    hd.x = lp[0];
+    hd.y = lp[1];
+    hd.start = scan_start_index(k, lp[2]);
+    int r0, c0;
+    hd.d0 = sample_distance<LAYOUT_ROWMAJOR, false, false>(km, nullptr, lp[0], lp[1], r0, c0);
+    hd.fast = 0;
+    hd.pad_ = 0;
+    if (km.pad) {
+        double ux, uy;
+        padded_position<false>(km, lp[0], lp[1], ux, uy);
+        hd.fast = padded_start_ok(km, ux, uy) ? 1 : 0;
+    }
+    j.hdr[G] = hd;
+}
+
+// a workgroup's whole particles
+inline int pf_particles_per_group(int B) { return 256 / B; }
+
+__global__ void __launch_bounds__(256) k_pf_sense(PfJob j, ScanConst k, int ppw)
+{
+    __shared__ double s_term[256];
+    const int P = j.sp.P, B = j.sp.B;
+    const int tid = (int)threadIdx.x, q = tid / B, jb = tid - q * B;
+    const long long total = (long long)j.count * P;
+    const long long gp = (long long)blockIdx.x * ppw + q;
+    const bool live = q < ppw && gp < total;
+    const size_t G = (size_t)j.i0 * P + (size_t)(live ? gp : 0);
+    double term = 0.0;
+    if (live) {
+        const int i = j.i0 + (int)(gp / P);
+        const int n = j.agents ? j.agents[i] : i;
+        const PfHdr hd = j.hdr[G];
+        const int beam = j.sp.beam_first + jb * j.sp.beam_stride;
+        const double z = j.scans[(size_t)n * j.num_beams + beam];
+        const ScanConst *cold = j.maps + (j.env_map ? j.env_map[n / j.A] : 0);
+        const ScanConst km = *cold;
+        int di = beam_dir_index(k, hd.start, beam);
+        di = di < 0 ? 0 : di;   // (a NaN heading)
+        const double2 cs = k.cs[di];
+        int hr = -1, hc = -1, nl, path;
+        double r;
+        if (km.pad)
+            r = trace_from_first<LAYOUT_PADDED, false, false, false>(km, cold, nullptr, hd.x, hd.y, hd.fast != 0, cs.x, cs.y, hd.d0, hr, hc, nl, path);
+        else
+            r = march_from_first<LAYOUT_ROWMAJOR, false, false>(km, nullptr, hd.x, hd.y, cs.x, cs.y, hd.d0, hr, hc, nl);
+        if (j.expect) j.expect[G * B + jb] = r;
+        term = pf_term(j.sp, z, r);
+    }
+    s_term[tid] = term;
+    __syncthreads();
+    if (live && jb == 0) j.logw[G] = pf_logw(j.sp, s_term + tid, B);
+}
+
+// the lanes per agent of k_pf_update
+inline int pf_group_lanes(int P)
+{
+    const int need = P < 256 ? P : 256;
+    int gs = 16;
+    while (gs < need) gs <<= 1;
+    return gs;
+}
+
+constexpr int kPfSlots = 8;   // Lmax, eta, x, y, sin, cos, q
+
+__global__ void __launch_bounds__(256) k_pf_update(PfJob j, int GS)
+{
+    extern __shared__ double s_pf_upd[];    // [256 / GS][6][P]
+    __shared__ double s_slot[16][kPfSlots];
+    const int P = j.sp.P;
+    const int per = 256 / GS, grp = (int)threadIdx.x / GS, t = (int)threadIdx.x - grp * GS;
+    const long long a_raw = (long long)blockIdx.x * per + grp;
+    const bool live = a_raw < j.count;
+    const int i = j.i0 + (int)(live ? a_raw : j.count - 1);
+    const int n = j.agents ? j.agents[i] : i;
+    double *sw = s_pf_upd + (size_t)grp * 6 * P, *sx = sw + P, *sy = sx + P, *ss = sy + P, *sc = ss + P, *sq = sc + P;
+    double *slot = s_slot[grp];
+    const double *L = j.logw + (size_t)i * P, *X = j.X_out + (size_t)i * P * 3;
+    double *W = j.W + (size_t)i * P;
+    for (int p = t; p < P; p += GS) sq[p] = L[p];
+    __syncthreads();
+    if (t == 0) slot[0] = pf_max(sq, P);
+    __syncthreads();
+    for (int p = t; p < P; p += GS) sw[p] = pf_unnorm(W[p], sq[p], slot[0]);
+    __syncthreads();
+    if (t == 0) slot[1] = pf_sum(sw, P);
+    __syncthreads();
+    for (int p = t; p < P; p += GS) {
+        const double w = pf_norm(sw[p], slot[1], P);
+        if (live) W[p] = w;
+        double c, s;
+        cos_sin(X[3 * p + 2], c, s);
+        sw[p] = w;
+        sx[p] = w * X[3 * p];
+        sy[p] = w * X[3 * p + 1];
+        ss[p] = w * s;
+        sc[p] = w * c;
+        sq[p] = w * w;
+    }
+    __syncthreads();
+    if (t < 5) slot[2 + t] = pf_sum(sx + (size_t)t * P, P);   // sx, sy, ss, sc, sq lie one behind the other
+    __syncthreads();
+    const double xh = slot[2], yh = slot[3];
+    for (int p = t; p < P; p += GS) sx[p] = pf_spread_term(sw[p], X[3 * p], X[3 * p + 1], xh, yh);
+    __syncthreads();
+    if (t != 0 || !live) return;
+    const double spread = pf_sum(sx, P);
+    const double x = j.px[n], y = j.py[n], th = j.pth[n];
+    double *o = j.pose + 3 * (size_t)n;
+    o[0] = xh;
+    o[1] = yh;
+    o[2] = atan2(slot[4], slot[5]);
+    if (j.info) pf_info(slot[6], spread, xh, yh, x, y, j.plan[i].resample, j.info + 4 * (size_t)n);
+    double *last = j.last + 3 * (size_t)i;
+    last[0] = x;
+    last[1] = y;
+    last[2] = th;
+    pf_stream_advance(j.streams + 4 * (size_t)i, j.jump_a[kPfJumps - 1], j.jump_g[kPfJumps - 1]);
+}

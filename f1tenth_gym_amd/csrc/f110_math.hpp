@@ -2064,4 +2064,163 @@ F110_HD void mppi_info(double beta, double c0, double eta, double q, int best, f
     o[3] = (float)best;
 }
 
+// ------------------------------------------------------------------ particle filter (include/f110.h, f110_pf)
+// Monte-Carlo localisation's own arithmetic around the scan's ray march: the fresh cloud, systematic resampling, the odometry motion,
+// the beam term, the weights and the estimate.  One text for the kernels (k_pf_*) and the host harness
+// (tests/host_harness/pf_harness.hip); the draws are f110_rng.hpp's (pf_uniform, pf_normals).  Every sum here runs over ascending
+// indices from 0.0, on the device too (one lane walks it): the header's rule bit for bit given the terms.
+enum { PF_MAX_P = 1024, PF_MAX_BEAMS = 128 };
+
+struct PfSpec {
+    int32_t P, B, beam_first, beam_stride;
+    double sigma_x, sigma_y, sigma_theta, init_x, init_y, init_theta, sigma_hit, clip, squash, resample_frac;
+};
+
+// what k_pf_plan leaves per armed agent for k_pf_move and k_pf_update
+struct PfPlan {
+    double u, ctot;        // the resampling draw; C[P - 1]
+    double a, b, dth;      // the odometry delta in the last pose's frame
+    int32_t resample, fresh;
+};
+
+// what k_pf_move leaves per particle for k_pf_sense: the lidar position, the scan's start index, the first sample (shared by the
+// particle's beams) and whether every sample stays inside the padded table
+struct PfHdr {
+    double x, y, start, d0;
+    int32_t fast, pad_;
+};
+
+// the step's own yaw wrap (advance_vehicle_with)
+F110_HD double pf_wrap(double th)
+{
+    if (th > kTwoPi)
+        th = th - kTwoPi;
+    else if (th < 0)
+        th = th + kTwoPi;
+    return th;
+}
+
+F110_HD double pf_sum(const double *v, int n)
+{
+    double s = 0.0;
+    for (int q = 0; q < n; ++q) s = s + v[q];
+    return s;
+}
+
+// 1 / sum W^2
+F110_HD double pf_ess(const double *W, int P)
+{
+    double q = 0.0;
+    for (int p = 0; p < P; ++p) q = q + W[p] * W[p];
+    return 1.0 / q;
+}
+
+F110_HD bool pf_decide(const PfSpec &s, double ess) { return ess < s.resample_frac * (double)s.P; }
+
+// C[j] = sum of W[0 .. j]; C may be W
+F110_HD void pf_cumulate(const double *W, int P, double *C)
+{
+    double c = 0.0;
+    for (int p = 0; p < P; ++p) {
+        c = c + W[p];
+        C[p] = c;
+    }
+}
+
+// slot i's ancestor: the least j with C[j] > t_i (P - 1 if none); C does not decrease, so a bisection finds it
+F110_HD int pf_ancestor(const double *C, int P, int i, double u, double ctot)
+{
+    const double t = ((double)i + u) / (double)P * ctot;
+    int lo = 0, hi = P - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (C[mid] > t)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
+}
+
+// the true pose's move since the last call, in the last pose's frame
+F110_HD void pf_odometry(const double *last, double x, double y, double th, double &a, double &b, double &dth)
+{
+    const double dx = x - last[0], dy = y - last[1];
+    double c, s;
+    cos_sin(last[2], c, s);
+    a = c * dx + s * dy;
+    b = -s * dx + c * dy;
+    dth = th - last[2];
+    if (dth > kPi)
+        dth = dth - kTwoPi;
+    else if (dth <= -kPi)
+        dth = dth + kTwoPi;
+}
+
+F110_HD void pf_fresh(const PfSpec &s, double x, double y, double th, const double *e, double *X)
+{
+    X[0] = x + s.init_x * e[0];
+    X[1] = y + s.init_y * e[1];
+    X[2] = pf_wrap(th + s.init_theta * e[2]);
+}
+
+// one particle's motion from its ancestor `src`
+F110_HD void pf_move(const PfSpec &s, double a, double b, double dth, const double *src, const double *e, double *X)
+{
+    const double fa = a + s.sigma_x * e[0], fb = b + s.sigma_y * e[1];
+    double c, sn;
+    cos_sin(src[2], c, sn);
+    X[0] = src[0] + (c * fa - sn * fb);
+    X[1] = src[1] + (sn * fa + c * fb);
+    X[2] = pf_wrap(src[2] + dth + s.sigma_theta * e[2]);
+}
+
+// the lidar pose of a particle: advance_vehicle_with's rule for scan_pose (the heading is wrapped already)
+F110_HD void pf_lidar_pose(const double *X, double lidar_dist, double *lp)
+{
+    const bool on_axle = lidar_dist == 0.0 && fabs(X[2]) < 1e300 && !(X[0] == 0.0 && signbit(X[0])) && !(X[1] == 0.0 && signbit(X[1]));
+    if (on_axle) {
+        lp[0] = X[0];
+        lp[1] = X[1];
+    } else {
+        double ch, sh;
+        cos_sin(X[2], ch, sh);
+        lp[0] = X[0] + lidar_dist * ch;
+        lp[1] = X[1] + lidar_dist * sh;
+    }
+    lp[2] = X[2];
+}
+
+// one beam's term: the squared error in sigmas, truncated at clip^2; a NaN takes the clip, or counts as 0 without truncation
+F110_HD double pf_term(const PfSpec &s, double z, double expect)
+{
+    const double e = (z - expect) / s.sigma_hit, e2 = e * e, c2 = s.clip * s.clip;
+    if (e2 < c2) return e2;
+    return (e2 != e2 && !(c2 < INFINITY)) ? 0.0 : c2;
+}
+
+F110_HD double pf_logw(const PfSpec &s, const double *t, int B) { return -(0.5 / s.squash) * pf_sum(t, B); }
+
+F110_HD double pf_max(const double *L, int P)
+{
+    double m = L[0];
+    for (int p = 1; p < P; ++p)
+        if (L[p] > m) m = L[p];
+    return m;
+}
+
+F110_HD double pf_unnorm(double W, double L, double Lmax) { return W * exp(L - Lmax); }
+
+F110_HD double pf_norm(double w, double eta, int P) { return eta > 0 ? w / eta : 1.0 / (double)P; }
+
+F110_HD double pf_spread_term(double w, double x, double y, double xh, double yh) { return w * ((x - xh) * (x - xh) + (y - yh) * (y - yh)); }
+
+F110_HD void pf_info(double q, double spread, double xh, double yh, double x, double y, int resampled, float *o)
+{
+    o[0] = (float)(1.0 / q);
+    o[1] = (float)sqrt(spread);
+    o[2] = (float)hypot(xh - x, yh - y);
+    o[3] = resampled ? 1.0f : 0.0f;
+}
+
 }  // namespace f110

@@ -418,20 +418,23 @@ F110_HD double mppi_normal(U128 &st, U128 inc, const ZigTables &t)
 constexpr int kMppiJumpLog2 = 20;
 constexpr int kMppiJumps = 257;   // entry 256 = 2^28 steps: where a call leaves the agent's generator
 
-inline void mppi_jump_table(U128 *a, U128 *g)
+// (A_n, G_n) for n = j * 2^log2, j = 0 .. count - 1
+inline void pcg_jump_table(U128 *a, U128 *g, int log2, int count)
 {
     U128 a1 = {kPcgMultHi, kPcgMultLo}, g1 = {0, 1};
-    for (int q = 0; q < kMppiJumpLog2; ++q) {   // A_2n = A_n * A_n, G_2n = G_n * (A_n + 1)
+    for (int q = 0; q < log2; ++q) {            // A_2n = A_n * A_n, G_2n = G_n * (A_n + 1)
         g1 = mul128(g1, add128(a1, U128{0, 1}));
         a1 = mul128(a1, a1);
     }
     a[0] = {0, 1};
     g[0] = {0, 0};
-    for (int j = 1; j < kMppiJumps; ++j) {      // A_(n+J) = A_n * A_J, G_(n+J) = G_n * A_J + G_J
+    for (int j = 1; j < count; ++j) {           // A_(n+J) = A_n * A_J, G_(n+J) = G_n * A_J + G_J
         a[j] = mul128(a[j - 1], a1);
         g[j] = add128(mul128(g[j - 1], a1), g1);
     }
 }
+
+inline void mppi_jump_table(U128 *a, U128 *g) { pcg_jump_table(a, g, kMppiJumpLog2, kMppiJumps); }
 
 // candidate k's row V[k][H][2] around the nominal U (fresh: (0, v_init)); stream = the agent's {state.hi, state.lo, inc.hi, inc.lo},
 // (ja, jg) = entry k of the jump table.  Candidate 0 is the nominal itself, without a draw.
@@ -449,6 +452,39 @@ F110_HD void mppi_sample_row(const MppiSpec &s, const double *U, bool fresh, int
         const double e_v = mppi_normal(st, inc, t);
         mppi_perturb(s, mppi_nominal(s, U, fresh, h, 0), mppi_nominal(s, U, fresh, h, 1), e_s, e_v, row + 2 * h);
     }
+}
+
+// ---- the particle filter's draws (include/f110.h, f110_pf) --------------------------------------------------------------------------
+// Sub-stream q of an agent's generator is the generator advanced by q * 2^kPfJumpLog2 steps: entry q of the table, q = 0 .. P.  A
+// call leaves the generator 2^28 steps on: entry kPfJumps - 1 (2^26 steps) four times.
+constexpr int kPfJumpLog2 = 16;
+constexpr int kPfJumps = 1025;
+
+inline void pf_jump_table(U128 *a, U128 *g) { pcg_jump_table(a, g, kPfJumpLog2, kPfJumps); }
+
+// sub-stream 0: Generator.random(), one output
+F110_HD double pf_uniform(const uint64_t *stream)
+{
+    const U128 st = pcg_step(U128{stream[0], stream[1]}, U128{stream[2], stream[3]});
+    return pcg_to_double(pcg_output(st));
+}
+
+// sub-stream p + 1 ((ja, jg) = entry p + 1): particle p's e_x, e_y, e_t
+F110_HD void pf_normals(const uint64_t *stream, U128 ja, U128 jg, const ZigTables &t, double *e)
+{
+    const U128 inc = {stream[2], stream[3]};
+    U128 st = pcg_jump(U128{stream[0], stream[1]}, inc, ja, jg);
+    for (int q = 0; q < 3; ++q) e[q] = mppi_normal(st, inc, t);
+}
+
+// where a call leaves the generator; (ja, jg) = the table's last entry
+F110_HD void pf_stream_advance(uint64_t *stream, U128 ja, U128 jg)
+{
+    const U128 inc = {stream[2], stream[3]};
+    U128 st = {stream[0], stream[1]};
+    for (int q = 0; q < 4; ++q) st = pcg_jump(st, inc, ja, jg);
+    stream[0] = st.hi;
+    stream[1] = st.lo;
 }
 
 }  // namespace f110

@@ -18,6 +18,7 @@ from . import _ffi
 from .core import DEFAULT_PARAMS
 from .gap_follower import coerce_scripted
 from .mppi import split_scripted
+from .particle_filter import split_filter
 from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
 from .sim import Integrator, Simulator
@@ -406,6 +407,14 @@ class F110VecEnv(object):
     relative heading and velocity, gap along the track, validity, index).  It belongs to the observation it comes with, is
     computed on the device behind the step and lands in page-locked memory, so it needs device_logic=True, and a track only
     for 'gap_s' (ValueError otherwise; any other loop calls env.sim.batch.neighbors_device after its step).  It holds no state.
+
+    Localisation (no reference counterpart): `particle_filter={slot: ParticleFilter | dict}` arms a particle filter on
+    every env's car `slot` and runs it on the device behind each step: obs['pose_estimate'], float64 [E][A][3], is the estimate
+    (x, y, theta) from the car's own scan and the pose's move since the last step, obs['pf_info'], float32 [E][A][4], is
+    particle_filter.INFO; the rows of the other cars are NaN.  A car's cloud is drawn afresh around its start pose when its env is
+    reset or re-seated.  Needs device_logic=True.  The clouds and stream positions are not part of snapshot() / restore(): keep
+    env.sim.batch.get_pf_state() next to a snapshot.  The device copies (env.pose_estimate_buffer, env.pf_info_buffer) feed a
+    device-side loop without a host wait (examples/particle_filter.py).
     """
 
     # every key of the reference's observation (base_classes.py:594-610, docs/api/obv.rst:6-14)
@@ -417,7 +426,7 @@ class F110VecEnv(object):
 
     def __init__(self, num_envs, auto_reset=False, device_logic=False, obs_fields=None, copy_obs=False,
                  episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, scripted=None,
-                 track_preview=None, neighbors=None, **kwargs):
+                 track_preview=None, neighbors=None, particle_filter=None, **kwargs):
         self.num_envs = int(num_envs)
         self.seed = kwargs.get('seed', 12345)
         self.map_name, self.map_path = _resolve_map_path(kwargs)
@@ -483,6 +492,14 @@ class F110VecEnv(object):
                 raise ValueError("neighbors= needs device_logic=True (any other loop calls env.sim.batch.neighbors_device after its step)")
             if self.neighbors.needs_track and not tracks:
                 raise ValueError("neighbors= with 'gap_s' needs a track (track= or tracks=)")
+        self.particle_filter = split_filter(particle_filter)   # (slot, ParticleFilter): every env's car `slot` localises
+        if self.particle_filter is not None:
+            if not self.device_logic:
+                raise ValueError("particle_filter= needs device_logic=True (any other loop arms env.sim.batch.set_particle_filter and calls "
+                                 "BatchSim.localize_device after its step)")
+            if not (0 <= self.particle_filter[0] < self.num_agents):
+                raise ValueError("particle_filter: slot %r is not one of the %d cars of an env" % (self.particle_filter[0], self.num_agents))
+            self.particle_filter[1].check_beams(kwargs.get('num_beams', 1080))
         self.encoded_stack = None
         if not tracks and any(f in self._TRACK for f in self.obs_fields):
             raise ValueError("the track fields of obs_fields need a track (track= or tracks=)")
@@ -539,6 +556,9 @@ class F110VecEnv(object):
             if self.planner is not None:   # agent_base: this handle's first global agent (ShardedVecEnv), so a sharded run draws the same numbers
                 b.set_mppi(self.planner[1], np.arange(self.num_envs) * self.num_agents + self.planner[0], seed=self.seed,
                            agent_base=int(kwargs.get('env_base', 0)) * self.num_agents)
+            if self.particle_filter is not None:   # likewise the filter's streams
+                b.set_particle_filter(self.particle_filter[1], np.arange(self.num_envs) * self.num_agents + self.particle_filter[0], seed=self.seed,
+                                      agent_base=int(kwargs.get('env_base', 0)) * self.num_agents)
 
     def _build_host_block(self):
         """the page-locked block f110_step_host fills, and the (obs, reward, done, info) tuple of views into it
@@ -603,6 +623,14 @@ class F110VecEnv(object):
             self._nbr_pinned = b.pinned_empty(shape, np.float32)
             self._nbr_pinned[...] = 0.0
             obs["neighbors"] = self._nbr_pinned.reshape((E, A) + shape[1:])
+        if self.particle_filter is not None:   # the estimates in device memory (NaN in the rows of cars that are not armed, written once
+            # here) and the host arrays every step's collect refills
+            self.pose_estimate_buffer = b.device_array((E * A, 3), np.float64)
+            self.pf_info_buffer = b.device_array((E * A, 4), np.float32)
+            self.pose_estimate_buffer.upload(np.full((E * A, 3), np.nan))
+            self.pf_info_buffer.upload(np.full((E * A, 4), np.nan, dtype=np.float32))
+            obs["pose_estimate"] = np.full((E, A, 3), np.nan)
+            obs["pf_info"] = np.full((E, A, 4), np.nan, dtype=np.float32)
         self._ret_views = (obs, reward, v["done"].view(np.bool_), info)
 
     def update_params_batch(self, params):
@@ -713,7 +741,7 @@ class F110VecEnv(object):
             self.sim._noise.ensure(b, self.sim._steps_since_full_reset + 1)
         if actions is not None and actions is not self.action_buffer:
             hb.actions[...] = np.asarray(actions, dtype=np.float64).reshape(hb.actions.shape)
-        if self._encode or self.track_preview is not None or self.neighbors is not None:
+        if self._encode or self.track_preview is not None or self.neighbors is not None or self.particle_filter is not None:
             # one wait per step: the step enqueued without a wait, the encode / the preview / the neighbours and their copies into page-locked memory behind it
             b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
                         scripted=self.scripted is not None or self.planner is not None)
@@ -724,6 +752,8 @@ class F110VecEnv(object):
                 b.track_preview_device(self.track_preview, self.preview_buffer, pinned=self._prv_pinned)
             if self.neighbors is not None:
                 b.neighbors_device(self.neighbors, self.neighbors_buffer, pinned=self._nbr_pinned)
+            if self.particle_filter is not None:
+                b.localize_device(self.pose_estimate_buffer, self.pf_info_buffer)
             if sync:
                 b.sync()
         else:
@@ -736,6 +766,10 @@ class F110VecEnv(object):
 
     def _collect(self):
         obs, r, done, info = self._ret_views
+        if self.particle_filter is not None:   # (the step has been waited for)
+            E, A = self.num_envs, self.num_agents
+            np.copyto(obs["pose_estimate"], self.pose_estimate_buffer.download().reshape(E, A, 3))
+            np.copyto(obs["pf_info"], self.pf_info_buffer.download().reshape(E, A, 4))
         if self.copy_obs:
             obs = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in obs.items()}
             done, info = done.copy(), {k: v.copy() for k, v in info.items()}

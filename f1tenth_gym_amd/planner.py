@@ -54,6 +54,15 @@ class PurePursuitPlanner(object):
         sim.pure_pursuit_device(self._d_wp, self._xyv.shape[0], d_actions, lookahead_distance, vgain, self.wheelbase,
                                 self.max_reacquire)
 
+    def plan_poses_device(self, sim, d_poses, d_actions, lookahead_distance, vgain):
+        """the same from poses in device memory, float64 [N][3] (a particle filter's estimates: BatchSim.localize_device)"""
+        if self._d_wp is None or self._d_wp_owner is not sim:
+            self._d_wp = sim.device_array(self._xyv.shape)
+            self._d_wp.upload(self._xyv)
+            self._d_wp_owner = sim
+        sim.pure_pursuit_poses_device(self._d_wp, self._xyv.shape[0], d_poses, d_actions, lookahead_distance, vgain, self.wheelbase,
+                                      self.max_reacquire)
+
     def close(self):
         if self._own and self._sim is not None:
             self._sim.close()

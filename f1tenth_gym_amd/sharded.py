@@ -100,6 +100,10 @@ class ShardedVecEnv(object):
         if kwargs.get('neighbors') is not None:      # one spec for every shard; obs['neighbors'] is concatenated along the env axis
             from .neighbors import Neighbors
             kwargs['neighbors'] = Neighbors.coerce(kwargs['neighbors'])
+        if kwargs.get('particle_filter') is not None:   # one filter for every shard; a shard's env_base gives its agents their global streams
+            from .particle_filter import split_filter
+            slot, pf = split_filter(kwargs['particle_filter'])
+            kwargs['particle_filter'] = {slot: pf}
         scripted = kwargs.pop('scripted', None)      # scripted cars: the global assignment [E][A], sliced by shard; the controllers shared
         from .mppi import split_scripted             # the planner: one for every shard; a shard's env_base gives its agents their global streams
         scripted, planner = split_scripted(scripted, kwargs.pop('planner', None))

@@ -518,6 +518,11 @@ int f110_pure_pursuit_batch(f110_sim *h, const double *h_waypoints, int32_t M, c
                             double max_reacquire, double *h_actions);
 int f110_pure_pursuit_device(f110_sim *h, const double *d_waypoints, int32_t M, double lookahead,
                              double vgain, double wheelbase, double max_reacquire, double *d_actions);
+/* _poses_device: the same policy for all N agents on poses the caller holds in device memory, d_poses [N][3] float64 = (x, y,
+ * theta) — a particle filter's estimates (f110_pf_device), say — instead of the live poses.  A row whose pose is NaN gets
+ * (0, 4.0), the policy's answer when it finds no waypoint.  Asynchronous, per env block behind a two-block step. */
+int f110_pure_pursuit_poses_device(f110_sim *h, const double *d_waypoints, int32_t M, const double *d_poses, double lookahead,
+                                   double vgain, double wheelbase, double max_reacquire, double *d_actions);
 /* A reactive policy that CONSUMES the step's scans on the device (NOT a reference function: the stand-in for an RL policy in
  * a device-resident loop — examples/rl_loop_device.py, bench.py's "scans consumed on device" leg).  Per agent: the num_beams
  * ranges in 64 sectors, steer = clamp(steer_gain * centre angle of the sector with the largest mean range among those within
@@ -1091,6 +1096,87 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
                     const double *h_params /* [m][18] or NULL */, const int32_t *h_fresh /* [m] or NULL */, int32_t m,
                     double *h_nominal /* [m][H][2] */, uint64_t *h_streams /* [m][4] */, double *h_actions /* [m][2] */,
                     float *h_info /* [m][4] */, double *h_cand /* [m][K][H][2] */, double *h_cost /* [m][K] */, double *h_weight /* [m][K] */);
+
+/* ---- particle filter: Monte-Carlo localisation per agent from its lidar scan (no reference counterpart: the particle filter of the
+ * MIT racecar stack that F1TENTH cars localise with, here against the distance table the simulator already keeps) ----
+ * It runs only when called (f110_pf_device), changes no simulator state and no blob format.  A filter is armed on a handle with ONE
+ * spec, a strictly ascending list of M agent indices (the armed agents, 1 <= M <= N) and one PCG64 stream per armed agent (the
+ * words of f110_pcg64_seed_spawn).  The handle owns per armed agent the cloud X[P][3] (x, y, theta of the car's reference point),
+ * the normalised weights W[P], the last true pose last[3] and the stream position.  They are configuration of the filter, not
+ * simulator state: the state blobs do not contain them (f110_pf_get / f110_pf_put checkpoint them next to a blob).  Arming stores
+ * a cloud of zeros with W = 1 / P and last = 0: a row becomes a cloud around its car at its first call with step_count == 0 (right
+ * after a reset), or through f110_pf_put.  Everything is float64 without contraction.
+ * One call does, for every armed agent n (the rows of other agents are never read or written), with P = particles, B' = n_beams,
+ * (x, y, th) = the agent's row of the observation's poses_x / poses_y / poses_theta and z[j] = beam b_j = beam_first +
+ * j * beam_stride of its live scan:
+ *   1 draws       sub-stream q of the agent's generator is the generator advanced by q * 2^16 steps (numpy.random.PCG64.advance).
+ *                 Sub-stream 0 yields u = Generator.random() (one output); sub-stream p + 1 yields particle p's e_x, e_y, e_t, three
+ *                 Generator.standard_normal() in this order.  After the call the generator stands 2^28 steps further on, whatever
+ *                 P is.
+ *   2 fresh row   if step_count[n] == 0: X[p] = (x + init_x * e_x, y + init_y * e_y, wrap(th + init_theta * e_t)), W[p] = 1 / P,
+ *                 a_p = p; 3 and 4 are skipped.  wrap(t) = t > 2 pi ? t - 2 pi : (t < 0 ? t + 2 pi : t), the step's own yaw wrap.
+ *   3 resample    ess = 1 / sum W[p]^2.  If ess < resample_frac * (double)P: C_j = sum_{i <= j} W[i]; for slot i
+ *                 t_i = ((double)i + u) / (double)P * C_{P-1}, the ancestor a_i is the least j with C_j > t_i (P - 1 if none), the
+ *                 new X[i] is the old X[a_i] and W[i] = 1 / P (systematic resampling).  Otherwise a_i = i.
+ *   4 motion      dx = x - last.x, dy = y - last.y, a = cos(last.th) * dx + sin(last.th) * dy, b = -sin(last.th) * dx +
+ *                 cos(last.th) * dy, dth = th - last.th, then dth - 2 pi if dth > pi, dth + 2 pi if dth <= -pi.  Per particle
+ *                 fa = a + sigma_x * e_x, fb = b + sigma_y * e_y, and with c = cos(X.th), s = sin(X.th) of the old heading
+ *                   X.x = X.x + (c * fa - s * fb),  X.y = X.y + (s * fa + c * fb),  X.th = wrap(X.th + dth + sigma_theta * e_t)
+ *   5 sensor      the particle's lidar pose is formed from X[p] as the step forms scan_pose from the state (lidar_dist along the
+ *                 heading).  r[p][j] is beam b_j of the noise-free scan at that pose on the env's map slot: the number
+ *                 f110_scan_batch returns for that pose and beam (the handle's trig tables, eps and max_range).
+ *                 e = (z[j] - r[p][j]) / sigma_hit, e2 = e * e, t_j = e2 if e2 < clip * clip, else clip * clip; a NaN e2 takes
+ *                 the clip, or counts as 0.0 when clip * clip is +inf.  L[p] = -(0.5 / squash) * sum_j t_j.
+ *   6 weights     Lmax = max L, w_p = W[p] * exp(L[p] - Lmax), eta = sum w_p, W'[p] = w_p / eta, or 1 / P for every p if
+ *                 !(eta > 0).
+ *   7 estimate    xh = sum W'[p] * X[p].x, yh = sum W'[p] * X[p].y, thh = atan2(sum W'[p] * sin(X[p].th), sum W'[p] * cos(X[p].th)).
+ *                 The agent's row of d_pose [N][3] float64 is (xh, yh, thh); of d_info [N][4] float32 (or NULL):
+ *                 (float)(1 / sum W'[p]^2), (float)sqrt(sum W'[p] * ((X.x - xh)^2 + (X.y - yh)^2)), (float)hypot(xh - x, yh - y),
+ *                 1.0 if 3 resampled, else 0.0.  Then last = (x, y, th), and X and W' are stored.
+ * Every sum runs over ascending indices from 0.0, on the device too (one lane walks it): given their terms the sums are defined bit
+ * for bit, and so are the draws, the ancestors, the motion's additions and L given r.  exp, sin, cos, atan2, hypot and sqrt are the
+ * device's; the rays are the scan's.
+ * Refused with F110_ERR_INVALID, nothing changed: particles outside 1..1024, n_beams outside 1..128, beam_first < 0, beam_stride < 1,
+ *   beam_first + (n_beams - 1) * beam_stride >= num_beams, a sigma or init sigma < 0, sigma_hit, clip or squash <= 0,
+ *   resample_frac < 0, any setting not finite except clip = +inf; a list that is not strictly ascending or has an index outside
+ *   0 .. N - 1; M * P * B' >= 2^31.  F110_ERR_STATE: nothing armed, or no map.
+ * Not offered: global localisation (a cloud over all free space), several specs per handle, a four-component beam model or a
+ * precomputed sensor table, KLD / adaptive P, noise proportional to the motion, opponents in the expected ranges (their returns are
+ * what clip is for), float32 particles, the filter inside the state blobs. */
+enum { F110_PF_MAX_P = 1024, F110_PF_MAX_BEAMS = 128 };
+typedef struct f110_pf {
+    int32_t particles;    /* P, 1..1024 */
+    int32_t n_beams;      /* B', 1..128 beams of the agent's scan that are compared */
+    int32_t beam_first;   /* >= 0 */
+    int32_t beam_stride;  /* >= 1; beam_first + (n_beams - 1) * beam_stride < the handle's num_beams */
+    double sigma_x, sigma_y, sigma_theta;   /* >= 0: odometry noise per call, car frame */
+    double init_x, init_y, init_theta;      /* >= 0: the fresh cloud around the true pose */
+    double sigma_hit;     /* > 0, metres */
+    double clip;          /* > 0, in sigmas; +inf allowed: no truncation */
+    double squash;        /* > 0: the log-likelihood is divided by it */
+    double resample_frac; /* >= 0, finite: resample when ESS < resample_frac * P */
+} f110_pf;               /* 4 * 4 + 10 * 8 = 96 bytes */
+/* arms the filter: h_agents [m] strictly ascending, h_streams [m][4] uint64.  NULL, NULL, 0, NULL disarms it and frees its memory.
+ * The new filter is built aside and swapped in on success; nothing is launched and no step looks at it. */
+int f110_pf_set(f110_sim *h, const f110_pf *spec, const int32_t *h_agents, int32_t m, const uint64_t *h_streams /* [m][4] */);
+/* one localisation call: the armed agents' rows of d_pose [N][3] float64 and of d_info [N][4] float32 (or NULL), device memory.
+ * Asynchronous on the handle's stream; right behind a two-block step it runs per env block on the block's own stream, the ascending
+ * list split at the block's bounds.  F110_ERR_STATE with nothing armed or without a map. */
+int f110_pf_device(f110_sim *h, double *d_pose, float *d_info);
+/* the filter's own memory, in the armed list's order: h_particles [m][P][3], h_weights [m][P], h_last [m][3], h_streams [m][4];
+ * each may be NULL.  get waits for the handle's work; put refuses (F110_ERR_INVALID, nothing changed) a particle that is not finite
+ * and a weight row with a negative or non-finite value or whose sum is not > 0.  F110_ERR_STATE with nothing armed. */
+int f110_pf_get(f110_sim *h, double *h_particles, double *h_weights, double *h_last, uint64_t *h_streams);
+int f110_pf_put(f110_sim *h, const double *h_particles, const double *h_weights, const double *h_last, const uint64_t *h_streams);
+/* unit form on host arrays, the same kernels on uploaded rows: h_poses [m][3] the true poses on map slot `slot`, h_scans [m][B]
+ * (B = num_beams), h_fresh [m] int32 (the rows' step_count; NULL: none is fresh); h_particles [m][P][3], h_weights [m][P], h_last
+ * [m][3] and h_streams [m][4] in and out, checked as f110_pf_put checks them.  Outputs, each may be NULL: h_pose [m][3], h_info
+ * [m][4], h_noise [m][P][3] (e_x, e_y, e_t), h_anc [m][P] int32 (a_p), h_expect [m][P][B'] (r), h_logw [m][P] (L).  The filter armed on
+ * the handle, if any, is not touched. */
+int f110_pf_batch(f110_sim *h, const f110_pf *spec, int32_t slot, const double *h_poses /* [m][3] */, const double *h_scans /* [m][B] */,
+                  const int32_t *h_fresh /* [m] or NULL */, int32_t m, double *h_particles /* [m][P][3] */, double *h_weights /* [m][P] */,
+                  double *h_last /* [m][3] */, uint64_t *h_streams /* [m][4] */, double *h_pose /* [m][3] */, float *h_info /* [m][4] */,
+                  double *h_noise /* [m][P][3] */, int32_t *h_anc /* [m][P] */, double *h_expect /* [m][P][B'] */, double *h_logw /* [m][P] */);
 
 #ifdef __cplusplus
 }
