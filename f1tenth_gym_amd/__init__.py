@@ -22,6 +22,7 @@ from .mppi import Mppi  # noqa: F401
 from .particle_filter import ParticleFilter  # noqa: F401
 from .obstacles import Obstacles  # noqa: F401
 from . import render  # noqa: F401
+from ._ffi import device_allocs  # noqa: F401
 from .functional import (accl_constraints, steering_constraint, vehicle_dynamics_ks, vehicle_dynamics_st, pid, func_KS, func_ST,  # noqa: F401
                          perpendicular, tripleProduct, avgPoint, indexOfFurthestPoint, support, collision, collision_multiple,
                          get_trmtx, get_vertices, get_dt, xy_2_rc, distance_transform, trace_ray, get_scan, check_ttc_jit, cross,

@@ -189,6 +189,7 @@ PROTOTYPES = {
     "f110_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "f110_device_pci_bus_id": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32]),
     "f110_build_info": (C.c_char_p, []),
+    "f110_device_allocs": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "f110_is_experimental": (C.c_int, []),
     "f110_exp_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "f110_create": (C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -394,6 +395,13 @@ def device_count():
     n = C.c_int(0)
     rc = lib().f110_device_count(C.byref(n))
     return n.value if rc == OK else 0
+
+
+def device_allocs():
+    """(live, bytes): the device allocations this process's handles own right now, and their size."""
+    live, nbytes = C.c_int64(0), C.c_int64(0)
+    check(lib().f110_device_allocs(C.byref(live), C.byref(nbytes)), None)
+    return live.value, nbytes.value
 
 
 def as_f64(a, shape=None):

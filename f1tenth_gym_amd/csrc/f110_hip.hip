@@ -25,6 +25,10 @@
 
 #include "../../include/f110.h"
 #include "f110_kernels.hpp"
+#include "f110_devmem.hpp"
+
+using devmem::DevArena;
+using devmem::DevBuf;
 
 
 // ============================================================================ host side
@@ -67,6 +71,7 @@ struct f110_sim {
     hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;          // k_collide runs here, concurrently with k_scan_rays
     hipEvent_t ev_integrated = nullptr, ev_collided = nullptr;
+    DevArena mem;       // what f110_create allocates for the handle's life: dev's columns (but the scans), the parameter / beam / trig tables, the staging columns, the noise generator's constants
     AgentArrays dev{};
     ScanConst k{};
     bool has_map = false;
@@ -78,38 +83,39 @@ struct f110_sim {
     double ttc_side_max = INFINITY, ttc_cos_max = INFINITY;  // see f110_set_beam_tables
     int dir_stride = 0;              // > 0: dedupe enabled
     int scan_block = 64;
-    double *d_params_all = nullptr;   // [N][18] when f110_set_params_batch is active
-    double *d_params = nullptr, *d_noise = nullptr, *d_scan_angles = nullptr, *d_beam_cos = nullptr, *d_side = nullptr;
+    DevBuf<double> d_params_all;   // [N][18] when f110_set_params_batch is active
+    DevBuf<double> d_noise;        // the noise table, or the row cache's current block
+    double *d_params = nullptr, *d_scan_angles = nullptr, *d_beam_cos = nullptr, *d_side = nullptr;   // (mem)
     // a different track per env: slot 0 is the map of f110_set_map_*, further slots come from
     // f110_add_map_*; f110_set_env_maps assigns them and builds the device tables
     struct MapSlot {
-        double *d_dt_row = nullptr, *d_dt_pad = nullptr;
+        DevBuf<double> d_dt_row, d_dt_pad;
         ScanConst k{};
-        uint8_t *d_occ = nullptr;   // f110_render_device's occupancy grid, built on first use
+        DevBuf<uint8_t> d_occ;      // f110_render_device's occupancy grid, built on first use
         bool occ_stale = false;     // ... and again after f110_set_map_obstacles re-stamped the table (the allocation stays)
         int base = -1;              // >= 0: a DERIVED slot (f110_add_map_obstacles), stamped from this base slot's table
     };
     std::vector<MapSlot> extra_maps;
-    MapFast *d_maps_fast = nullptr;
-    ScanConst *d_maps_full = nullptr;
+    DevBuf<MapFast> d_maps_fast;
+    DevBuf<ScanConst> d_maps_full;
     int n_maps_dev = 0;                 // slots d_maps_full holds
     // f110_*_map_obstacles: the byte mask, the active columns' distances and list, the boxes, the out-of-bounds value (grow-only)
     struct ObstScratch {
-        uint8_t *mask = nullptr;
-        uint32_t *g = nullptr;
-        int32_t *cols = nullptr;
-        ObstBox *boxes = nullptr;
-        double *oob = nullptr;
-        size_t mask_cap = 0, g_cap = 0, cols_cap = 0;
+        DevBuf<uint8_t> mask;
+        DevBuf<uint32_t> g;
+        DevBuf<int32_t> cols;
+        DevBuf<ObstBox> boxes;
+        DevBuf<double> oob;
     } obst;
-    int32_t *d_env_map = nullptr;
-    uint32_t *d_scan_order = nullptr;   // [N] agents sorted by map slot (nullptr while every env is on one slot)
+    DevBuf<int32_t> d_env_map;
+    DevBuf<uint32_t> d_scan_order;      // [N] agents sorted by map slot (nullptr while every env is on one slot)
     bool multi_map = false;
-    ScanConst *d_k = nullptr;  // HBM copy of k (RayJob::k_cold), refreshed by cold_consts()
+    DevBuf<ScanConst> d_k;     // HBM copy of k (RayJob::k_cold), refreshed by cold_consts()
     ScanConst k_uploaded{};
-    unsigned long long *d_path_stats = nullptr;  // [3], see f110_scan_path_stats
+    DevBuf<unsigned long long> d_path_stats;     // [3], see f110_scan_path_stats
     bool path_stats_on = false;
-    double *d_dt_row = nullptr, *d_dt_pad = nullptr, *d_actions = nullptr, *d_poses = nullptr;
+    DevBuf<double> d_dt_row, d_dt_pad;
+    double *d_actions = nullptr, *d_poses = nullptr;   // (mem)
     double2 *d_cs = nullptr;
     uint8_t *d_mask = nullptr;
     // env groups: the step of G > 1 independent env blocks runs on G streams of its own (no event
@@ -127,10 +133,10 @@ struct f110_sim {
     bool main_dirty = true;     // the main stream holds work the group streams have not waited for
     // device RNG for the scan noise (f110_set_noise_rng)
     NoiseGen noise_gen{};
-    uint64_t *d_zig_k = nullptr;
+    uint64_t *d_zig_k = nullptr;     // (mem, like the next three)
     double *d_zig_w = nullptr, *d_zig_f = nullptr;
     U128 *d_jump = nullptr;          // [2][65]
-    U128 *d_rng_state = nullptr, *d_rng_seed = nullptr, *d_rng_rowstate = nullptr;
+    DevBuf<U128> d_rng_state, d_rng_seed, d_rng_rowstate;
     int noise_rows_ready = 0;        // rows of the row cache generated so far
     int noise_rows_alloc = 0;        // rows the row cache has memory for (grows on demand up to dev.noise_rows)
     // the next rows are generated AHEAD of need on a stream of their own (noise_start_ahead): a row is 12.8 us of one wave, the rows of a
@@ -139,20 +145,20 @@ struct f110_sim {
     hipEvent_t ev_noise = nullptr, ev_noise_src = nullptr;
     bool noise_ahead = false;        // rows [noise_rows_ready, noise_ahead_upto) are being generated into noise_ahead_block
     int noise_ahead_upto = 0, noise_ahead_alloc = 0;
-    double *noise_ahead_block = nullptr;
-    std::vector<double *> noise_retired;   // earlier, smaller blocks of the cache (steps in flight may read them): freed with the cache
+    DevBuf<double> noise_ahead_block;
+    std::vector<DevBuf<double>> noise_retired;   // earlier, smaller blocks of the cache (steps in flight may read them): freed with the cache
     long long noise_ub = 0;          // upper bound of any agent's step_count (steps since the last full reset)
     // identity of the noise source, for the state blobs (0 off, 1 table, 2 shared stream, 3 a stream per agent): the table's
     // FNV-1a hash / rows / beams, or the shared stream's PCG64 words
     int noise_src = 0;
     uint64_t noise_src_id[4] = {0, 0, 0, 0};
-    void *d_state_blob = nullptr;    // f110_state_save / _load: the device side of the whole-handle blob (grows on demand)
-    size_t state_blob_bytes = 0;
-    unsigned long long *d_lookups = nullptr;  // f110_scan_lookup_count
+    DevBuf<unsigned char> d_state_blob;   // f110_state_save / _load: the device side of the whole-handle blob (grows on demand)
+    unsigned long long *d_lookups = nullptr;  // f110_scan_lookup_count (mem)
     bool lookups_on = false;
     int collide_mode = 0;        // where the pair tests run: 0 side stream, 1 fused into k_integrate, 2 in line, 3 inside k_finalize (A = 2)
     // longest-first order of the scan tasks (TaskSched, small batches): double-buffered flags / lists / counters
     bool task_order = false;
+    DevArena sched_mem;              // the five buffers below
     uint32_t *d_tflags[2] = {nullptr, nullptr}, *d_tlist[2] = {nullptr, nullptr}, *d_tcount = nullptr;
     TaskSched tsched[2]{};           // [parity], passed to the scan by value
     bool sched_allocated = false;
@@ -160,26 +166,27 @@ struct f110_sim {
     uint32_t task_epoch = 2, task_cap = 0, task_thr = 96;   // epochs start above the flags' initial 0
     uint32_t task_cap_div = 32, task_rev = 0;                // list capacity = tasks / task_cap_div; 1 = newest list entries first
     ExpSwitches exp;
-    uint32_t *d_env_done = nullptr;   // [num_envs] scan_env_counter probe
+    DevBuf<uint32_t> d_env_done;      // [num_envs] scan_env_counter probe
     ncclComm_t comm = nullptr;   // optional RCCL communicator for the observation gather
     bool beams_uniform = true;   // f110_set_beam_tables: scan_angles is (to a quarter of a spacing) the ramp base_classes.py:133-134 builds
     int comm_ranks = 0;
     // overlapped gather (f110_comm_set_overlap): scans are double-buffered, the all-gather of step t
     // runs on comm_stream while step t+1 fills the other buffer
     bool comm_overlap = false, comm_swap_next = false, comm_inflight = false;
-    double *scan_bufs[2] = {nullptr, nullptr};
-    double *obs_scal[2] = {nullptr, nullptr};   // [7][N] scalar observation block(s) of the observation gather
-    float *scan_f32[2] = {nullptr, nullptr};    // [N][B] float32 copies of the scans (F110_GATHER_F32 transport)
+    DevBuf<double> scan_bufs[2];                // the scans' owner: [0] from f110_create on, [1] with the overlapped gather; dev.scans is a view of one of them
+    DevBuf<double> obs_scal[2];                 // [7][N] scalar observation block(s) of the observation gather
+    DevBuf<float> scan_f32[2];                  // [N][B] float32 copies of the scans (F110_GATHER_F32 transport)
     int comm_rank = -1;
     bool comm_send_scalars = false;
     int scans_cur = 0;
     bool gather_pending[2] = {false, false};
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_step_done = nullptr, ev_gather_done[2] = {nullptr, nullptr};
+    DevArena ep_mem;            // ep's columns and d_rot_stage
     EpisodeArrays ep{};
     bool has_episode = false;
     double *d_rot_stage = nullptr;
-    void *d_packed = nullptr;   // f110_episode_step_host's packed block
+    DevBuf<unsigned char> d_packed;   // f110_episode_step_host's packed block
     // f110_step_host: the caller's block as last validated, and its device-side pointers
     bool hb_valid = false;
     f110_host_block hb_host{};
@@ -187,48 +194,47 @@ struct f110_sim {
     const double *hb_actions_host = nullptr, *hb_actions_dev = nullptr;
     bool hb_scans_by_kernel = false;             // the validated block's scans are stored by the kernel (small batch, page-locked)
     unsigned long long *hb_seq_host = nullptr;   // page-locked completion word (F110_STEP_SPIN_WAIT)
-    unsigned int *hb_blocks_done = nullptr;
+    DevBuf<unsigned int> hb_blocks_done;
     unsigned long long hb_seq = 0;
     double hs_enqueue_us = 0, hs_wait_us = 0;    // f110_step_host_stats
-    FusedHost *d_fused = nullptr;                // device copy of {episode arrays, host block, flags} for the pair kernel's epilogue
+    DevBuf<FusedHost> d_fused;                   // device copy of {episode arrays, host block, flags} for the pair kernel's epilogue
     FusedHost fused_host_copy{};                 // what d_fused holds
     bool fused_valid = false;
     long long hs_calls = 0;
     // the whole step of a tiny batch as ONE launch (k_step_tiny): counters + shadow columns, allocated on first use
     TinyCtl tiny{};
-    void *tiny_mem = nullptr;
+    DevBuf<unsigned char> tiny_mem;
     int tiny_off = 0;                 // lab A/B (f110_exp_set "step_tiny" = 0): the three-kernel form also for tiny batches
     int last_launches = 0;            // kernels the most recent step submitted its work as (f110_step_launches)
     // track progress (f110_track_*): a polyline per map slot, the step's columns, the per-agent cache of s
     struct TrackSlot {
-        double *d_cols = nullptr;   // [7][nseg] (TrackCol)
-        double *d_pts = nullptr;    // [npts][2] the points (after the closed-track dedupe), what a render draws
-        double *d_attr = nullptr;   // [nattr][npts] per-point attributes (f110_track_set_attrs), or null
+        DevBuf<double> d_cols;      // [7][nseg] (TrackCol)
+        DevBuf<double> d_pts;       // [npts][2] the points (after the closed-track dedupe), what a render draws
+        DevBuf<double> d_attr;      // [nattr][npts] per-point attributes (f110_track_set_attrs), or null
         int32_t nattr = 0;
         int32_t nseg = 0, closed = 0, npts = 0;
         double L = 0.0;
     };
     std::vector<TrackSlot> tracks;        // indexed by map slot (shorter than the slot list: the rest have no track)
-    TrackDesc *d_tracks = nullptr;        // [n_tracks_dev] what the kernels read
-    PreviewAttr *d_track_attrs = nullptr; // [n_tracks_dev] the slots' attribute columns (k_track_preview), uploaded with d_tracks
+    DevBuf<TrackDesc> d_tracks;           // [n_tracks_dev] what the kernels read
+    DevBuf<PreviewAttr> d_track_attrs;    // [n_tracks_dev] the slots' attribute columns (k_track_preview), uploaded with d_tracks
     int n_tracks_dev = 0;
     bool tracks_dirty = true;             // d_tracks does not reflect `tracks` / the slot count
     bool track_lds = false;               // some track fits the LDS-staged form
     bool track_on = false, track_checked = false;   // f110_track_enable; every env's slot has a track (checked since the last change)
     std::vector<int32_t> env_map_host;    // f110_set_env_maps' assignment (meaningful while multi_map)
-    double *d_trk = nullptr;              // [4][N] s, ds, lateral, heading_error
-    int32_t *d_trk_seg = nullptr;         // [N]
-    double *d_trk_cache = nullptr;        // [3][N] cached s, x, y
-    int32_t *d_trk_ok = nullptr;          // [N]
+    DevBuf<double> d_trk;                 // [4][N] s, ds, lateral, heading_error
+    DevBuf<int32_t> d_trk_seg;            // [N]
+    DevBuf<double> d_trk_cache;           // [3][N] cached s, x, y
+    DevBuf<int32_t> d_trk_ok;             // [N]
     f110_track_host trk_pinned{};         // f110_track_host_block, host pointers ...
     HostBlock trk_hb{};                   // ... and their device views (the trk_* fields)
     bool trk_pinned_on = false;
     const float *pinned_dst[kPinnedCount] = {};   // per device form: the page-locked block its last copy went to (f110_host_free)
-    double *d_roll_end = nullptr;            // f110_rollout_device: the candidates' end positions between its two kernels (grows on demand)
-    size_t roll_end_cap = 0;
+    DevBuf<double> d_roll_end;               // f110_rollout_device: the candidates' end positions between its two kernels (grows on demand)
     // scripted cars (f110_controllers_set): the specs and the per-agent assignment in device memory; gap_specs == 0: disarmed
-    GapSpec *d_gap_specs = nullptr;
-    int32_t *d_gap_assign = nullptr;
+    DevBuf<GapSpec> d_gap_specs;
+    DevBuf<int32_t> d_gap_assign;
     int gap_specs = 0, gap_max_w = 0;
     std::vector<int32_t> gap_assign_host;   // the armed assignment (empty while disarmed): what f110_mppi_set checks its agents against
     // MPPI planner (f110_mppi_set): m == 0: disarmed.  The nominal sequences and the streams are the planner's own memory.
@@ -236,46 +242,43 @@ struct f110_sim {
         MppiSpec sp{};
         int m = 0;
         std::vector<int32_t> agents;     // the armed list, ascending
-        int32_t *d_agents = nullptr;     // [m]
-        MppiSpec *d_spec = nullptr;      // sp, for the kernels
-        double *d_nominal = nullptr;     // [m][H][2]
-        uint64_t *d_streams = nullptr;   // [m][4]
-        double *d_V = nullptr;           // [m][K][H][2] the candidates of the last call
-        double *d_cost = nullptr;        // [m][K]
-        double *d_end = nullptr;         // [m][K][2] (only with a track weight)
+        DevBuf<int32_t> d_agents;        // [m]
+        DevBuf<MppiSpec> d_spec;         // sp, for the kernels
+        DevBuf<double> d_nominal;        // [m][H][2]
+        DevBuf<uint64_t> d_streams;      // [m][4]
+        DevBuf<double> d_V;              // [m][K][H][2] the candidates of the last call
+        DevBuf<double> d_cost;           // [m][K]
+        DevBuf<double> d_end;            // [m][K][2] (only with a track weight)
     } mppi;
-    U128 *d_mppi_jump = nullptr;         // [2][kMppiJumps] the candidates' jump constants (from the first arming on)
+    DevBuf<U128> d_mppi_jump;            // [2][kMppiJumps] the candidates' jump constants (from the first arming on)
     // particle filter (f110_pf_set): m == 0: disarmed.  The clouds, the weights, the last poses and the streams are the filter's own memory.
     struct Pf {
         PfSpec sp{};
         int m = 0, cur = 0;              // d_X[cur] is the stored cloud; a call moves it into d_X[cur ^ 1] and flips
         std::vector<int32_t> agents;     // the armed list, ascending
-        int32_t *d_agents = nullptr;     // [m]
-        uint64_t *d_streams = nullptr;   // [m][4]
-        double *d_X[2] = {nullptr, nullptr};   // [m][P][3]
-        double *d_W = nullptr;           // [m][P]
-        double *d_last = nullptr;        // [m][3]
-        double *d_cum = nullptr;         // [m][P]
-        double *d_logw = nullptr;        // [m][P]
-        PfPlan *d_plan = nullptr;        // [m]
-        PfHdr *d_hdr = nullptr;          // [m][P]
+        DevBuf<int32_t> d_agents;        // [m]
+        DevBuf<uint64_t> d_streams;      // [m][4]
+        DevBuf<double> d_X[2];           // [m][P][3]
+        DevBuf<double> d_W;              // [m][P]
+        DevBuf<double> d_last;           // [m][3]
+        DevBuf<double> d_cum;            // [m][P]
+        DevBuf<double> d_logw;           // [m][P]
+        DevBuf<PfPlan> d_plan;           // [m]
+        DevBuf<PfHdr> d_hdr;             // [m][P]
     } pf;
-    U128 *d_pf_jump = nullptr;           // [2][kPfJumps] the sub-streams' jump constants (from the first arming on)
+    DevBuf<U128> d_pf_jump;              // [2][kPfJumps] the sub-streams' jump constants (from the first arming on)
     // rendering (f110_render_device): slot 0's occupancy grid, the slot table as last uploaded, per-frame / per-agent records
-    uint8_t *d_occ0 = nullptr;
+    DevBuf<uint8_t> d_occ0;
     std::vector<RenderSlot> render_slots;
-    RenderSlot *d_render_slots = nullptr;
-    size_t render_slots_cap = 0;
-    RenderFrame *d_render_frames = nullptr;
-    size_t render_frames_cap = 0;
-    RenderCar *d_render_cars = nullptr;
-    int32_t *d_render_agents = nullptr;
-    size_t render_agents_cap = 0;
-    uint8_t *d_render_stage = nullptr;   // [F][H][pitch] when the caller's buffer cannot take 32-bit stores
-    size_t render_stage_cap = 0;
+    DevBuf<RenderSlot> d_render_slots;      // (this and the next three grow on demand)
+    DevBuf<RenderFrame> d_render_frames;
+    DevBuf<RenderCar> d_render_cars;
+    DevBuf<int32_t> d_render_agents;
+    DevBuf<uint8_t> d_render_stage;      // [F][H][pitch] when the caller's buffer cannot take 32-bit stores
     // randomised start poses (f110_reset_sampler_*): the settings, each env's stream, the explicit fallback poses, the counters
     struct ResetSampler {
         bool on = false;
+        DevArena mem;                // job's device buffers
         SamplerJob job{};            // settings + device buffers; tracks / maps / mode are filled per launch
     } rs;
     // timing
@@ -320,10 +323,27 @@ static int fail(f110_sim *h, int code, const char *fmt, ...)
             return fail(h, F110_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// device memory comes from one of the two owners of f110_devmem.hpp: a buffer of its own (replaced: what it held is freed
+// first) or one more allocation of an arena, whose pointer lands in *p
 template <typename T>
-static int dmalloc(f110_sim *h, T **p, size_t count)
+static int dmalloc(f110_sim *h, DevBuf<T> *buf, size_t count)
 {
-    HIPCHK(h, hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T) > 0 ? count * sizeof(T) : 8));
+    HIPCHK(h, buf->alloc(count));
+    return F110_OK;
+}
+
+template <typename T>
+static int dmalloc(f110_sim *h, DevArena &arena, T **p, size_t count)
+{
+    HIPCHK(h, arena.alloc(p, count));
+    return F110_OK;
+}
+
+// grow-only buffers (DevBuf::grow): a regrow frees the old allocation, and hipFree waits for the work in flight that reads it
+template <typename T>
+static int dgrow(f110_sim *h, DevBuf<T> &buf, size_t count)
+{
+    HIPCHK(h, buf.grow(count));
     return F110_OK;
 }
 
@@ -382,8 +402,6 @@ static void gap_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions);
 static int mppi_ready(f110_sim *h);                                                   // (below, with the planner)
 static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, float *d_info);
 static int mppi_upload_tracks(f110_sim *h);
-static void mppi_free(f110_sim *h);
-static void pf_free(f110_sim *h);                                                     // (below, with the particle filter)
 struct EnvBlocks {
     EnvBlock b[kMaxEnvBlocks];
     int n = 0;
@@ -458,17 +476,12 @@ static int env_blocks_output(f110_sim *h, const EnvBlocks &w, PinnedDst who, siz
 // RAII scratch for the unit entry points
 struct Scratch {
     f110_sim *h;
-    std::vector<void *> ptrs;
+    DevArena mem;
     explicit Scratch(f110_sim *hh) : h(hh) {}
-    ~Scratch()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
     template <typename T>
     int up(const T *host, size_t count, T **dev)
     {
-        TRY(dmalloc(h, dev, count));
-        ptrs.push_back(*dev);
+        TRY(dmalloc(h, mem, dev, count));
         if (host) HIPCHK(h, hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
         return F110_OK;
     }
@@ -529,7 +542,7 @@ static void set_div_magic(RayJob &j, uint32_t B)
 // the device copy of h->k, brought up to date (stream-ordered) if any field changed
 static const ScanConst *cold_consts(f110_sim *h)
 {
-    if (!h->d_k && hipMalloc(reinterpret_cast<void **>(&h->d_k), sizeof(ScanConst)) != hipSuccess) return nullptr;
+    if (!h->d_k && h->d_k.alloc(1) != hipSuccess) return nullptr;
     if (std::memcmp(&h->k, &h->k_uploaded, sizeof(ScanConst)) != 0) {
         std::memcpy(&h->k_uploaded, &h->k, sizeof(ScanConst));
         if (hipMemcpyAsync(h->d_k, &h->k_uploaded, sizeof(ScanConst), hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
@@ -574,13 +587,14 @@ static int task_order_setup(f110_sim *h, bool on)
         return F110_OK;
     }
     if (!h->sched_allocated) {
+        h->sched_mem.clear();   // (an earlier attempt that ran out of memory half-way)
         h->task_cap_alloc = (uint32_t)std::max<size_t>(64, kExperimental ? n_tasks : n_tasks / h->task_cap_div);
         for (int q = 0; q < 2; ++q) {
-            TRY(dmalloc(h, &h->d_tflags[q], n_tasks));
-            TRY(dmalloc(h, &h->d_tlist[q], (size_t)h->task_cap_alloc));
+            TRY(dmalloc(h, h->sched_mem, &h->d_tflags[q], n_tasks));
+            TRY(dmalloc(h, h->sched_mem, &h->d_tlist[q], (size_t)h->task_cap_alloc));
             HIPCHK(h, hipMemsetAsync(h->d_tflags[q], 0, sizeof(uint32_t) * n_tasks, h->stream));
         }
-        TRY(dmalloc(h, &h->d_tcount, 4));   // {task count of parity 0, of parity 1, spare, spare}
+        TRY(dmalloc(h, h->sched_mem, &h->d_tcount, 4));   // {task count of parity 0, of parity 1, spare, spare}
         HIPCHK(h, hipMemsetAsync(h->d_tcount, 0, 4 * sizeof(uint32_t), h->stream));
         h->sched_allocated = true;
     }
@@ -592,10 +606,38 @@ static int task_order_setup(f110_sim *h, bool on)
     return F110_OK;
 }
 
+static int finish_map(f110_sim *h, int H, int W, double res, double ox, double oy, double oc, double os);   // (below, with the map)
+
+// Slot 0's table is replaced by a fresh row-major one of n cells, which fill(table) enqueues the contents of.  Once the old
+// table is gone, a failure leaves the handle WITHOUT a map: it refuses a step ("Map is not set") instead of reading freed memory.
+template <typename Fill>
+static int replace_map(f110_sim *h, size_t n, int H, int W, double res, double ox, double oy, double oc, double os, Fill fill)
+{
+    const auto unset = [h](int rc) {
+        h->has_map = false;
+        h->k.table = h->k.table_rm = nullptr;
+        h->k.pad = nullptr;
+        return rc;
+    };
+    const bool freed = h->d_dt_row != nullptr;
+    int rc = dmalloc(h, &h->d_dt_row, n);
+    if (rc != F110_OK) return freed ? unset(rc) : rc;
+    rc = fill(h->d_dt_row.get());
+    if (rc == F110_OK) rc = finish_map(h, H, W, res, ox, oy, oc, os);
+    return rc == F110_OK ? rc : unset(rc);
+}
+
 extern "C" {
 
 const char *f110_last_error(const f110_sim *h) { return (h && h->err[0]) ? h->err : g_err; }
 int f110_abi_version(void) { return F110_ABI_VERSION; }
+
+int f110_device_allocs(int64_t *live, int64_t *bytes)
+{
+    if (live) *live = devmem::g_live.load();
+    if (bytes) *bytes = devmem::g_bytes.load();
+    return F110_OK;
+}
 
 int f110_device_count(int *count)
 {
@@ -701,8 +743,9 @@ static void default_beam_tables(const f110_config &c, std::vector<double> &sa, s
 static hipError_t streams_concurrent(hipStream_t a, hipStream_t b, bool *yes)
 {
     *yes = false;
-    unsigned *d = nullptr, hres[2] = {0u, 0u};
-    hipError_t e = hipMalloc(&d, 2 * sizeof(unsigned));
+    DevBuf<unsigned> d;
+    unsigned hres[2] = {0u, 0u};
+    hipError_t e = d.alloc(2);
     if (e != hipSuccess) return e;
     do {
         if ((e = hipMemsetAsync(d, 0, 2 * sizeof(unsigned), a)) != hipSuccess) break;
@@ -715,7 +758,6 @@ static hipError_t streams_concurrent(hipStream_t a, hipStream_t b, bool *yes)
         if ((e = hipMemcpy(hres, d, sizeof hres, hipMemcpyDeviceToHost)) != hipSuccess) break;
         *yes = hres[1] != 0u;
     } while (0);
-    (void)hipFree(d);
     return e;
 }
 
@@ -883,38 +925,39 @@ int f110_create(const f110_config *cfg, f110_sim **out)
     d.agents_per_env = cfg->num_agents;
     d.agent_begin = 0;
     d.agent_count = N;
-    CK(dmalloc(h, &d.state, (size_t)7 * N));
-    CK(dmalloc(h, &d.steer_buf, (size_t)2 * N));
-    CK(dmalloc(h, &d.buf_cnt, (size_t)N));
-    CK(dmalloc(h, &d.scan_pose, (size_t)3 * N));
-    CK(dmalloc(h, &d.snap_pose, (size_t)3 * N));
-    CK(dmalloc(h, &d.dir_start, (size_t)N));
-    CK(dmalloc(h, &d.ray_hdr, (size_t)N));
-    CK(dmalloc(h, &d.scans, (size_t)N * B));
-    CK(dmalloc(h, &d.collisions, (size_t)N));
-    CK(dmalloc(h, &d.collision_idx, (size_t)N));
-    CK(dmalloc(h, &d.in_collision, (size_t)N));
-    CK(dmalloc(h, &d.step_count, (size_t)N));
-    CK(dmalloc(h, &d.opp_window, (size_t)N * cfg->num_agents * 4));
-    CK(dmalloc(h, &d.opp_verts, (size_t)N * cfg->num_agents * 8));
-    CK(dmalloc(h, &h->d_params, (size_t)cfg->num_agents * NPARAMS));
-    CK(dmalloc(h, &h->d_scan_angles, (size_t)B));
-    CK(dmalloc(h, &h->d_beam_cos, (size_t)B));
-    CK(dmalloc(h, &h->d_side, (size_t)B));
-    CK(dmalloc(h, &h->d_cs, (size_t)cfg->theta_dis));
-    CK(dmalloc(h, &h->d_actions, (size_t)2 * N));
-    CK(dmalloc(h, &h->d_poses, (size_t)3 * N));
-    CK(dmalloc(h, &h->d_mask, (size_t)cfg->num_envs));
+    CK(dmalloc(h, h->mem, &d.state, (size_t)7 * N));
+    CK(dmalloc(h, h->mem, &d.steer_buf, (size_t)2 * N));
+    CK(dmalloc(h, h->mem, &d.buf_cnt, (size_t)N));
+    CK(dmalloc(h, h->mem, &d.scan_pose, (size_t)3 * N));
+    CK(dmalloc(h, h->mem, &d.snap_pose, (size_t)3 * N));
+    CK(dmalloc(h, h->mem, &d.dir_start, (size_t)N));
+    CK(dmalloc(h, h->mem, &d.ray_hdr, (size_t)N));
+    CK(dmalloc(h, &h->scan_bufs[0], (size_t)N * B));
+    d.scans = h->scan_bufs[0];
+    CK(dmalloc(h, h->mem, &d.collisions, (size_t)N));
+    CK(dmalloc(h, h->mem, &d.collision_idx, (size_t)N));
+    CK(dmalloc(h, h->mem, &d.in_collision, (size_t)N));
+    CK(dmalloc(h, h->mem, &d.step_count, (size_t)N));
+    CK(dmalloc(h, h->mem, &d.opp_window, (size_t)N * cfg->num_agents * 4));
+    CK(dmalloc(h, h->mem, &d.opp_verts, (size_t)N * cfg->num_agents * 8));
+    CK(dmalloc(h, h->mem, &h->d_params, (size_t)cfg->num_agents * NPARAMS));
+    CK(dmalloc(h, h->mem, &h->d_scan_angles, (size_t)B));
+    CK(dmalloc(h, h->mem, &h->d_beam_cos, (size_t)B));
+    CK(dmalloc(h, h->mem, &h->d_side, (size_t)B));
+    CK(dmalloc(h, h->mem, &h->d_cs, (size_t)cfg->theta_dis));
+    CK(dmalloc(h, h->mem, &h->d_actions, (size_t)2 * N));
+    CK(dmalloc(h, h->mem, &h->d_poses, (size_t)3 * N));
+    CK(dmalloc(h, h->mem, &h->d_mask, (size_t)cfg->num_envs));
     {
         // constants of the device noise generator (f110_rng.hpp): NumPy's ziggurat tables and the
         // PCG64 jump constants, 8 KB in all
         PcgJump jt;
         pcg_jump_table(jt);
-        CK(dmalloc(h, &h->d_zig_k, 256));
-        CK(dmalloc(h, &h->d_zig_w, 256));
-        CK(dmalloc(h, &h->d_zig_f, 256));
-        CK(dmalloc(h, &h->d_jump, 2 * 65));
-        CK(dmalloc(h, &h->d_lookups, 2));
+        CK(dmalloc(h, h->mem, &h->d_zig_k, 256));
+        CK(dmalloc(h, h->mem, &h->d_zig_w, 256));
+        CK(dmalloc(h, h->mem, &h->d_zig_f, 256));
+        CK(dmalloc(h, h->mem, &h->d_jump, 2 * 65));
+        CK(dmalloc(h, h->mem, &h->d_lookups, 2));
         CKH(hipMemcpy(h->d_zig_k, kZigK, sizeof kZigK, hipMemcpyHostToDevice));
         CKH(hipMemcpy(h->d_zig_w, kZigW, sizeof kZigW, hipMemcpyHostToDevice));
         CKH(hipMemcpy(h->d_zig_f, kZigF, sizeof kZigF, hipMemcpyHostToDevice));
@@ -1033,83 +1076,20 @@ void f110_destroy(f110_sim *h)
     if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
     (void)f110_comm_destroy(h);
     h->comm_inflight = false;
-    if (h->d_state_blob) (void)hipFree(h->d_state_blob);
     if (h->comm_stream) { (void)hipStreamSynchronize(h->comm_stream); (void)hipStreamDestroy(h->comm_stream); h->comm_stream = nullptr; }
     for (hipEvent_t e : {h->ev_step_done, h->ev_gather_done[0], h->ev_gather_done[1]})
         if (e) (void)hipEventDestroy(e);
-    if (h->comm_overlap || h->scan_bufs[1]) {
-        if (h->scan_bufs[0]) h->dev.scans = h->scan_bufs[0];   // the list below frees dev.scans
-        if (h->scan_bufs[1]) (void)hipFree(h->scan_bufs[1]);
-    }
-    for (double *p : h->obs_scal)
-        if (p) (void)hipFree(p);
-    for (float *p : h->scan_f32)
-        if (p) (void)hipFree(p);
     for (hipStream_t gs : h->gowned) (void)hipStreamDestroy(gs);
     for (hipEvent_t ge : h->gevents)
         if (ge) (void)hipEventDestroy(ge);
     if (h->ev_main) (void)hipEventDestroy(h->ev_main);
-    noise_release(h);
-    sampler_release(h);
-    if (h->noise_stream) (void)hipStreamDestroy(h->noise_stream);
+    if (h->noise_stream) {   // rows generated ahead of need may still be in flight
+        (void)hipStreamSynchronize(h->noise_stream);
+        (void)hipStreamDestroy(h->noise_stream);
+    }
     if (h->ev_noise) (void)hipEventDestroy(h->ev_noise);
     if (h->ev_noise_src) (void)hipEventDestroy(h->ev_noise_src);
-    {
-        void *rp[] = {h->d_env_done, h->d_tflags[0], h->d_tflags[1], h->d_tlist[0], h->d_tlist[1], h->d_tcount, h->d_zig_k, h->d_zig_w, h->d_zig_f, h->d_jump, h->d_rng_state, h->d_rng_seed, h->d_rng_rowstate, h->d_lookups};
-        for (void *p : rp)
-            if (p) (void)hipFree(p);
-    }
-    AgentArrays &d = h->dev;
-    void *ptrs[] = {d.opp_verts, d.ray_hdr, d.opp_window, d.state, d.steer_buf, d.buf_cnt, d.scan_pose, d.snap_pose, d.dir_start, d.scans, d.collisions,
-                    d.collision_idx, d.in_collision, d.step_count, h->d_params, h->d_noise, h->d_scan_angles,
-                    h->d_beam_cos, h->d_side, h->d_dt_row, h->d_dt_pad, h->d_actions, h->d_poses, h->d_cs, h->d_mask, h->d_path_stats, h->d_k, h->d_params_all};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto &ms : h->extra_maps) {
-        if (ms.d_dt_row) (void)hipFree(ms.d_dt_row);
-        if (ms.d_dt_pad) (void)hipFree(ms.d_dt_pad);
-        if (ms.d_occ) (void)hipFree(ms.d_occ);
-    }
-    if (h->d_maps_fast) (void)hipFree(h->d_maps_fast);
-    if (h->d_maps_full) (void)hipFree(h->d_maps_full);
-    {
-        void *op[] = {h->obst.mask, h->obst.g, h->obst.cols, h->obst.boxes, h->obst.oob};
-        for (void *p : op)
-            if (p) (void)hipFree(p);
-    }
-    if (h->d_env_map) (void)hipFree(h->d_env_map);
-    if (h->d_scan_order) (void)hipFree(h->d_scan_order);
-    for (auto &ts : h->tracks) {
-        if (ts.d_cols) (void)hipFree(ts.d_cols);
-        if (ts.d_pts) (void)hipFree(ts.d_pts);
-        if (ts.d_attr) (void)hipFree(ts.d_attr);
-    }
-    if (h->d_gap_specs) (void)hipFree(h->d_gap_specs);
-    if (h->d_gap_assign) (void)hipFree(h->d_gap_assign);
-    mppi_free(h);
-    if (h->d_mppi_jump) (void)hipFree(h->d_mppi_jump);
-    pf_free(h);
-    if (h->d_pf_jump) (void)hipFree(h->d_pf_jump);
-    {
-        void *rp[] = {h->d_occ0, h->d_render_slots, h->d_render_frames, h->d_render_cars, h->d_render_agents, h->d_render_stage};
-        for (void *p : rp)
-            if (p) (void)hipFree(p);
-    }
-    {
-        void *tp[] = {h->d_tracks, h->d_track_attrs, h->d_trk, h->d_trk_seg, h->d_trk_cache, h->d_trk_ok, h->d_roll_end};
-        for (void *p : tp)
-            if (p) (void)hipFree(p);
-    }
-    {
-        void *eptrs[] = {h->ep.start_poses, h->ep.rot, h->ep.current_time, h->ep.near_start, h->ep.toggle,
-                         h->ep.lap_count, h->ep.lap_time, h->ep.done, h->ep.checkpoint, h->d_rot_stage, h->d_packed};
-        for (void *p : eptrs)
-            if (p) (void)hipFree(p);
-    }
     if (h->hb_seq_host) (void)hipHostFree(h->hb_seq_host);
-    if (h->d_fused) (void)hipFree(h->d_fused);
-    if (h->tiny_mem) (void)hipFree(h->tiny_mem);
-    if (h->hb_blocks_done) (void)hipFree(h->hb_blocks_done);
     for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
     if (h->ev_integrated) (void)hipEventDestroy(h->ev_integrated);
     if (h->ev_collided) (void)hipEventDestroy(h->ev_collided);
@@ -1117,6 +1097,8 @@ void f110_destroy(f110_sim *h)
     if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
     if (h->ev_end) (void)hipEventDestroy(h->ev_end);
     if (h->stream) (void)hipStreamDestroy(h->stream);
+    // the device memory goes with the handle: every buffer is a DevBuf or sits in a DevArena (f110_devmem.hpp), so a feature
+    // that adds one adds no line here.  All streams were synchronised above and this thread's device is the handle's.
     delete h;
 }
 
@@ -1158,13 +1140,13 @@ static int finish_map(f110_sim *h, int H, int W, double res, double ox, double o
     TRY(track_invalidate(h));
     h->dev.maps_full = nullptr;
     h->dev.env_map = nullptr;
-    if (h->d_occ0) { (void)hipFree(h->d_occ0); h->d_occ0 = nullptr; }   // a render rebuilds it from the new table
+    h->d_occ0.reset();   // a render rebuilds it from the new table
     fill_map_fields(k, H, W, res, ox, oy, oc, os);
     HIPCHK(h, hipMemcpyAsync(&k.oob_value, h->d_dt_row + ((size_t)H * W - 1), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     k.table = h->d_dt_row;
     k.table_rm = h->d_dt_row;
     k.pad = nullptr;
-    if (h->d_dt_pad) { (void)hipFree(h->d_dt_pad); h->d_dt_pad = nullptr; }
+    h->d_dt_pad.reset();
     if (padded_family(h->cfg.map_layout) && setup_padded(k)) {
         // the table again with a border of out-of-bounds cells wide enough for any ray of a lidar
         // that is on (or within kPadSlack cells of) the map; maps too large for 16-bit cell
@@ -1183,8 +1165,7 @@ static int finish_map(f110_sim *h, int H, int W, double res, double ox, double o
             HIPCHK(h, hipStreamSynchronize(h->stream));
             k.table = k.table_rm = h->d_dt_pad + (size_t)k.pad_border * k.pad_width + k.pad_border;
             k.row_bytes = k.pad_row_bytes;
-            (void)hipFree(h->d_dt_row);
-            h->d_dt_row = nullptr;
+            h->d_dt_row.reset();
         }
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1206,14 +1187,14 @@ int f110_set_map_image(f110_sim *h, const uint8_t *h_img, int32_t H, int32_t W, 
     TRY(s.up<uint8_t>(nullptr, n, &d_bin));
     TRY(s.up<uint32_t>(nullptr, n, &d_g));
     TRY(s.up<uint32_t>(nullptr, n, &d_d2));
-    if (h->d_dt_row) { (void)hipFree(h->d_dt_row); h->d_dt_row = nullptr; }
-    TRY(dmalloc(h, &h->d_dt_row, n));
-    hipLaunchKernelGGL(k_flip_threshold, grid1d(n, 256), dim3(256), 0, h->stream, d_img, H, W, d_bin);
-    hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, d_bin, H, W, d_g);
-    hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, d_g, H, W, d_d2);
-    hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, d_d2, n, res, h->d_dt_row);
-    HIPCHK(h, hipGetLastError());
-    return finish_map(h, H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw));  // :421-422
+    return replace_map(h, n, H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw), [&](double *table) {  // :421-422
+        hipLaunchKernelGGL(k_flip_threshold, grid1d(n, 256), dim3(256), 0, h->stream, d_img, H, W, d_bin);
+        hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, d_bin, H, W, d_g);
+        hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, d_g, H, W, d_d2);
+        hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, d_d2, n, res, table);
+        HIPCHK(h, hipGetLastError());
+        return (int)F110_OK;
+    });
 }
 
 int f110_set_map_dt(f110_sim *h, const double *h_dt, int32_t H, int32_t W, double res, double ox, double oy, double oc, double os)
@@ -1224,15 +1205,15 @@ int f110_set_map_dt(f110_sim *h, const double *h_dt, int32_t H, int32_t W, doubl
     if ((unsigned long long)(H + 3) * (unsigned long long)(W + 3) * 8ull >= 0xFFFFFFFFull) return fail(h, F110_ERR_INVALID, "distance table must stay below 4 GiB");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t n = (size_t)H * W;
-    if (h->d_dt_row) { (void)hipFree(h->d_dt_row); h->d_dt_row = nullptr; }
-    TRY(dmalloc(h, &h->d_dt_row, n));
-    HIPCHK(h, hipMemcpyAsync(h->d_dt_row, h_dt, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    return finish_map(h, H, W, res, ox, oy, oc, os);
+    return replace_map(h, n, H, W, res, ox, oy, oc, os, [&](double *table) {
+        HIPCHK(h, hipMemcpyAsync(table, h_dt, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        return (int)F110_OK;
+    });
 }
 
 // ---- a different track per env ---------------------------------------------------------------------
 // the exact-EDT pipeline of f110_set_map_image into a fresh row-major table
-static int edt_table_from_image(f110_sim *h, const uint8_t *h_img, int H, int W, double res, double **d_dt_row)
+static int edt_table_from_image(f110_sim *h, const uint8_t *h_img, int H, int W, double res, DevBuf<double> &d_dt_row)
 {
     const size_t n = (size_t)H * W;
     uint8_t *d_img = nullptr, *d_bin = nullptr;
@@ -1242,34 +1223,30 @@ static int edt_table_from_image(f110_sim *h, const uint8_t *h_img, int H, int W,
     TRY(s.up<uint8_t>(nullptr, n, &d_bin));
     TRY(s.up<uint32_t>(nullptr, n, &d_g));
     TRY(s.up<uint32_t>(nullptr, n, &d_d2));
-    TRY(dmalloc(h, d_dt_row, n));
+    TRY(dmalloc(h, &d_dt_row, n));
     hipLaunchKernelGGL(k_flip_threshold, grid1d(n, 256), dim3(256), 0, h->stream, d_img, H, W, d_bin);
     hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, d_bin, H, W, d_g);
     hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, d_g, H, W, d_d2);
-    hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, d_d2, n, res, *d_dt_row);
+    hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, d_d2, n, res, d_dt_row.get());
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }
 
-static int add_map_slot(f110_sim *h, double *d_dt_row, int H, int W, double res, double ox, double oy, double oc, double os, int32_t *slot)
+// the row-major table becomes a slot: whatever fails, the table (and the slot's padded copy) go with the locals that own them
+static int add_map_slot(f110_sim *h, DevBuf<double> &&table, int H, int W, double res, double ox, double oy, double oc, double os, int32_t *slot)
 {
     f110_sim::MapSlot ms;
-    ms.d_dt_row = d_dt_row;
+    ms.d_dt_row = std::move(table);
+    double *const d_dt_row = ms.d_dt_row;
     ms.k = h->k;   // beam / trig / range constants are shared; the map fields follow
     fill_map_fields(ms.k, H, W, res, ox, oy, oc, os);
     ms.k.table = ms.k.table_rm = d_dt_row;
     HIPCHK(h, hipMemcpyAsync(&ms.k.oob_value, d_dt_row + ((size_t)H * W - 1), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!setup_padded(ms.k)) {
-        (void)hipFree(d_dt_row);
-        return fail(h, F110_ERR_INVALID, "f110_add_map: a per-env map must fit the padded layout (16-bit cell coordinates, < 4 GiB)");
-    }
+    if (!setup_padded(ms.k)) return fail(h, F110_ERR_INVALID, "f110_add_map: a per-env map must fit the padded layout (16-bit cell coordinates, < 4 GiB)");
     const size_t total = (size_t)ms.k.pad_width * ms.k.pad_height;
-    if (dmalloc(h, &ms.d_dt_pad, total) != F110_OK) {
-        (void)hipFree(d_dt_row);
-        return F110_ERR_NOMEM;
-    }
+    if (dmalloc(h, &ms.d_dt_pad, total) != F110_OK) return F110_ERR_NOMEM;
     hipLaunchKernelGGL(k_build_padded, grid1d(total, 256), dim3(256), 0, h->stream, d_dt_row, H, W, ms.k.pad_border, ms.k.pad_width,
                        ms.k.pad_height, ms.d_dt_pad);
     HIPCHK(h, hipGetLastError());
@@ -1278,9 +1255,8 @@ static int add_map_slot(f110_sim *h, double *d_dt_row, int H, int W, double res,
     // one table per track (see finish_map): the exact paths read the padded copy's interior
     ms.k.table = ms.k.table_rm = ms.d_dt_pad + (size_t)ms.k.pad_border * ms.k.pad_width + ms.k.pad_border;
     ms.k.row_bytes = ms.k.pad_row_bytes;
-    (void)hipFree(ms.d_dt_row);
-    ms.d_dt_row = nullptr;
-    h->extra_maps.push_back(ms);
+    ms.d_dt_row.reset();
+    h->extra_maps.push_back(std::move(ms));
     if (slot) *slot = (int32_t)h->extra_maps.size();   // slot 0 is the map of f110_set_map_*
     return F110_OK;
 }
@@ -1291,9 +1267,9 @@ int f110_add_map_image(f110_sim *h, const uint8_t *h_img, int32_t H, int32_t W, 
     ENTER(h);
     if (H < 1 || W < 1 || H > 16384 || W > 16384 || !(res > 0)) return fail(h, F110_ERR_INVALID, "f110_add_map_image: bad shape %dx%d or resolution", H, W);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    double *d_dt_row = nullptr;
-    TRY(edt_table_from_image(h, h_img, H, W, res, &d_dt_row));
-    return add_map_slot(h, d_dt_row, H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw), slot);
+    DevBuf<double> d_dt_row;
+    TRY(edt_table_from_image(h, h_img, H, W, res, d_dt_row));
+    return add_map_slot(h, std::move(d_dt_row), H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw), slot);
 }
 
 int f110_add_map_dt(f110_sim *h, const double *h_dt, int32_t H, int32_t W, double res, double ox, double oy, double oc, double os, int32_t *slot)
@@ -1302,10 +1278,10 @@ int f110_add_map_dt(f110_sim *h, const double *h_dt, int32_t H, int32_t W, doubl
     ENTER(h);
     if (H < 1 || W < 1 || !(res > 0)) return fail(h, F110_ERR_INVALID, "f110_add_map_dt: bad shape or resolution");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    double *d_dt_row = nullptr;
+    DevBuf<double> d_dt_row;
     TRY(dmalloc(h, &d_dt_row, (size_t)H * W));
     HIPCHK(h, hipMemcpyAsync(d_dt_row, h_dt, (size_t)H * W * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    return add_map_slot(h, d_dt_row, H, W, res, ox, oy, oc, os, slot);
+    return add_map_slot(h, std::move(d_dt_row), H, W, res, ox, oy, oc, os, slot);
 }
 
 int f110_set_env_maps(f110_sim *h, const int32_t *h_env_map)
@@ -1342,12 +1318,12 @@ int f110_set_env_maps(f110_sim *h, const int32_t *h_env_map)
         fast[m].pad_row_bytes = (uint32_t)full[m].pad_row_bytes;
         fast[m].pad_max_samples = full[m].pad_max_samples;
     }
-    if (h->d_maps_fast) { (void)hipFree(h->d_maps_fast); h->d_maps_fast = nullptr; }
-    if (h->d_maps_full) { (void)hipFree(h->d_maps_full); h->d_maps_full = nullptr; }
-    if (!h->d_env_map) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_env_map), sizeof(int32_t) * E));
-    HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_maps_fast), sizeof(MapFast) * M));
+    h->d_maps_fast.reset();
+    h->d_maps_full.reset();
+    if (!h->d_env_map) TRY(dmalloc(h, &h->d_env_map, (size_t)E));
+    TRY(dmalloc(h, &h->d_maps_fast, (size_t)M));
     h->n_maps_dev = 0;
-    HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_maps_full), sizeof(ScanConst) * M));
+    TRY(dmalloc(h, &h->d_maps_full, (size_t)M));
     h->n_maps_dev = M;
     HIPCHK(h, hipMemcpyAsync(h->d_maps_fast, fast.data(), sizeof(MapFast) * M, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_maps_full, full.data(), sizeof(ScanConst) * M, hipMemcpyHostToDevice, h->stream));
@@ -1362,9 +1338,9 @@ int f110_set_env_maps(f110_sim *h, const int32_t *h_env_map)
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h_env_map[a / A] < h_env_map[b / A]; });
         bool identity = true;
         for (int i = 0; i < h->N && identity; ++i) identity = order[i] == (uint32_t)i;
-        if (h->d_scan_order) { (void)hipFree(h->d_scan_order); h->d_scan_order = nullptr; }
+        h->d_scan_order.reset();
         if (!identity) {
-            HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_scan_order), sizeof(uint32_t) * h->N));
+            TRY(dmalloc(h, &h->d_scan_order, (size_t)h->N));
             HIPCHK(h, hipMemcpyAsync(h->d_scan_order, order.data(), sizeof(uint32_t) * h->N, hipMemcpyHostToDevice, h->stream));
         }
     }
@@ -1422,17 +1398,6 @@ static int obstacles_check(f110_sim *h, const char *who, const f110_obstacle *ob
     return F110_OK;
 }
 
-// grow-only scratch: *cap counts bytes
-static int obst_grow(f110_sim *h, void **p, size_t *cap, size_t bytes)
-{
-    if (*cap >= bytes && *p) return F110_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    *cap = 0;
-    HIPCHK(h, hipMalloc(p, bytes > 0 ? bytes : 8));
-    *cap = bytes;
-    return F110_OK;
-}
-
 // Stamp `obs` into derived slot m (>= 1) from its base's table: everything on the main stream (the caller went through ENTER, so
 // steps in flight on the env blocks come first and the next step's blocks fork from behind this), then one wait for the new
 // out-of-bounds value.  The list has been checked.
@@ -1465,9 +1430,9 @@ static int obstacles_stamp(f110_sim *h, const char *who, int m, const f110_obsta
     if (!sc.oob) TRY(dmalloc(h, &sc.oob, 1));
     if (!sc.boxes) TRY(dmalloc(h, &sc.boxes, (size_t)F110_MAX_OBSTACLES));
     if (Wa > 0) {
-        TRY(obst_grow(h, reinterpret_cast<void **>(&sc.mask), &sc.mask_cap, (size_t)H * W));
-        TRY(obst_grow(h, reinterpret_cast<void **>(&sc.g), &sc.g_cap, (size_t)H * Wa * sizeof(uint32_t)));
-        TRY(obst_grow(h, reinterpret_cast<void **>(&sc.cols), &sc.cols_cap, (size_t)W * sizeof(int32_t)));
+        TRY(dgrow(h, sc.mask, (size_t)H * W));
+        TRY(dgrow(h, sc.g, (size_t)H * Wa));
+        TRY(dgrow(h, sc.cols, (size_t)W));
         HIPCHK(h, hipMemsetAsync(sc.mask, 0, (size_t)H * W, h->stream));
         HIPCHK(h, hipMemcpyAsync(sc.boxes, boxes.data(), boxes.size() * sizeof(ObstBox), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(sc.cols, cols.data(), (size_t)Wa * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
@@ -1507,13 +1472,12 @@ int f110_add_map_obstacles(f110_sim *h, int32_t base_slot, const f110_obstacle *
     ms.k.table = ms.k.table_rm = ms.d_dt_pad + (size_t)ms.k.pad_border * ms.k.pad_width + ms.k.pad_border;
     ms.k.row_bytes = ms.k.pad_row_bytes;
     ms.base = base_slot;
-    h->extra_maps.push_back(ms);
+    h->extra_maps.push_back(std::move(ms));
     const int m = (int)h->extra_maps.size();
     const int rc = obstacles_stamp(h, who, m, h_obs, n);
     if (rc != F110_OK) {
         (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(ms.d_dt_pad);
-        h->extra_maps.pop_back();
+        h->extra_maps.pop_back();   // (and its table with it)
         return rc;
     }
     *slot = m;
@@ -1679,15 +1643,13 @@ static int noise_adopt(f110_sim *h);
 static void noise_release(f110_sim *h)
 {
     if (h->noise_stream) (void)hipStreamSynchronize(h->noise_stream);
-    if (h->noise_ahead && h->noise_ahead_block && h->noise_ahead_block != h->d_noise) (void)hipFree(h->noise_ahead_block);
     h->noise_ahead = false;
-    h->noise_ahead_block = nullptr;
-    for (double *p : h->noise_retired) (void)hipFree(p);
+    h->noise_ahead_block.reset();
     h->noise_retired.clear();
-    if (h->d_noise) { (void)hipFree(h->d_noise); h->d_noise = nullptr; }
-    if (h->d_rng_state) { (void)hipFree(h->d_rng_state); h->d_rng_state = nullptr; }
-    if (h->d_rng_seed) { (void)hipFree(h->d_rng_seed); h->d_rng_seed = nullptr; }
-    if (h->d_rng_rowstate) { (void)hipFree(h->d_rng_rowstate); h->d_rng_rowstate = nullptr; }
+    h->d_noise.reset();
+    h->d_rng_state.reset();
+    h->d_rng_seed.reset();
+    h->d_rng_rowstate.reset();
     h->dev.noise = nullptr;
     h->dev.noise_rows = 0;
     h->dev.noise_rng = 0;
@@ -1866,11 +1828,8 @@ int f110_reset_collided_device(f110_sim *h, const double *d_start_poses, int32_t
 // ---- randomised start poses (f110_reset_sampler_*) ------------------------------------------------------------
 static void sampler_release(f110_sim *h)
 {
-    SamplerJob &j = h->rs.job;
-    void *ptrs[] = {j.stream, j.last, j.cand, j.out_poses, j.out_rot, j.attempt, j.counters};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    j = SamplerJob{};
+    h->rs.mem.clear();
+    h->rs.job = SamplerJob{};
     h->rs.on = false;
 }
 
@@ -1928,13 +1887,13 @@ int f110_reset_sampler_set(f110_sim *h, const f110_reset_sampler *spec, const ui
     sampler_release(h);
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
     SamplerJob &j = h->rs.job;
-    TRY(dmalloc(h, &j.stream, 2 * E));
-    TRY(dmalloc(h, &j.last, 3 * N));
-    TRY(dmalloc(h, &j.cand, 3 * N));
-    TRY(dmalloc(h, &j.out_poses, 3 * N));
-    TRY(dmalloc(h, &j.out_rot, 4 * E));
-    TRY(dmalloc(h, &j.attempt, E));
-    TRY(dmalloc(h, &j.counters, 2));
+    TRY(dmalloc(h, h->rs.mem, &j.stream, 2 * E));
+    TRY(dmalloc(h, h->rs.mem, &j.last, 3 * N));
+    TRY(dmalloc(h, h->rs.mem, &j.cand, 3 * N));
+    TRY(dmalloc(h, h->rs.mem, &j.out_poses, 3 * N));
+    TRY(dmalloc(h, h->rs.mem, &j.out_rot, 4 * E));
+    TRY(dmalloc(h, h->rs.mem, &j.attempt, E));
+    TRY(dmalloc(h, h->rs.mem, &j.counters, 2));
     // {state.hi, state.lo, inc.hi, inc.lo} per env is the layout of two U128 {hi, lo}
     HIPCHK(h, hipMemcpy(j.stream, h_streams, sizeof(U128) * 2 * E, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemset(j.last, 0, sizeof(double) * 3 * N));
@@ -2106,8 +2065,7 @@ int f110_comm_set_overlap(f110_sim *h, int32_t enable)
             HIPCHK(h, hipEventCreateWithFlags(&h->ev_gather_done[0], hipEventDisableTiming));
             HIPCHK(h, hipEventCreateWithFlags(&h->ev_gather_done[1], hipEventDisableTiming));
         }
-        h->scan_bufs[0] = h->dev.scans;
-        h->scans_cur = 0;
+        h->scans_cur = 0;   // (dev.scans is scan_bufs[0] whenever the overlap is off)
         h->gather_pending[0] = h->gather_pending[1] = false;
         h->comm_swap_next = false;
         h->comm_overlap = true;
@@ -2268,16 +2226,17 @@ int f110_episode_init(f110_sim *h, int32_t ego_idx)
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
     EpisodeArrays &ep = h->ep;
     if (!h->has_episode) {
-        TRY(dmalloc(h, &ep.start_poses, 3 * N));
-        TRY(dmalloc(h, &ep.rot, 4 * E));
-        TRY(dmalloc(h, &ep.current_time, E));
-        TRY(dmalloc(h, &ep.near_start, N));
-        TRY(dmalloc(h, &ep.toggle, N));
-        TRY(dmalloc(h, &ep.lap_count, N));
-        TRY(dmalloc(h, &ep.lap_time, N));
-        TRY(dmalloc(h, &ep.done, E));
-        TRY(dmalloc(h, &ep.checkpoint, N));
-        TRY(dmalloc(h, &h->d_rot_stage, 4 * E));
+        h->ep_mem.clear();   // (an earlier attempt that ran out of memory half-way)
+        TRY(dmalloc(h, h->ep_mem, &ep.start_poses, 3 * N));
+        TRY(dmalloc(h, h->ep_mem, &ep.rot, 4 * E));
+        TRY(dmalloc(h, h->ep_mem, &ep.current_time, E));
+        TRY(dmalloc(h, h->ep_mem, &ep.near_start, N));
+        TRY(dmalloc(h, h->ep_mem, &ep.toggle, N));
+        TRY(dmalloc(h, h->ep_mem, &ep.lap_count, N));
+        TRY(dmalloc(h, h->ep_mem, &ep.lap_time, N));
+        TRY(dmalloc(h, h->ep_mem, &ep.done, E));
+        TRY(dmalloc(h, h->ep_mem, &ep.checkpoint, N));
+        TRY(dmalloc(h, h->ep_mem, &h->d_rot_stage, 4 * E));
         HIPCHK(h, hipMemsetAsync(ep.start_poses, 0, 3 * N * sizeof(double), h->stream));
         HIPCHK(h, hipMemsetAsync(ep.rot, 0, 4 * E * sizeof(double), h->stream));
         HIPCHK(h, hipMemsetAsync(ep.current_time, 0, E * sizeof(double), h->stream));
@@ -2441,7 +2400,7 @@ int f110_episode_step_host(f110_sim *h, const double *h_actions, int32_t auto_re
     TRY(check_step(h, true));
     ENTER(h);
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs, bytes = f110_episode_packed_bytes(h);
-    if (!h->d_packed) HIPCHK(h, hipMalloc(&h->d_packed, bytes));
+    if (!h->d_packed) TRY(dmalloc(h, &h->d_packed, bytes));
     HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
     StepRequest rq;
     rq.defer_draw = true;
@@ -2449,7 +2408,7 @@ int f110_episode_step_host(f110_sim *h, const double *h_actions, int32_t auto_re
     TRY(step_submit(h, h->d_actions, rq, host_written));
     ENTER(h);
     hipLaunchKernelGGL(k_episode, grid1d(E, 256), dim3(256), 0, h->stream, h->dev, h->ep, (int)E);
-    double *cols = reinterpret_cast<double *>(h->d_packed);
+    double *cols = reinterpret_cast<double *>(h->d_packed.get());
     uint8_t *flags = reinterpret_cast<uint8_t *>(cols + 9 * N + E);
     hipLaunchKernelGGL(k_pack_episode, grid1d(N > E ? N : E, 256), dim3(256), 0, h->stream, h->dev, h->ep, (int)E, cols, flags);
     HIPCHK(h, hipMemcpyAsync(h_packed, h->d_packed, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -2596,7 +2555,7 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
         fh.hb.seq = 0;   // (the sequence number travels in the kernel arguments: rq.seq)
         fh.episode = rq.episode;
         fh.auto_reset = rq.auto_reset;
-        if (!h->d_fused) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_fused), sizeof(FusedHost)));
+        if (!h->d_fused) TRY(dmalloc(h, &h->d_fused, 1));
         if (!h->fused_valid || std::memcmp(&fh, &h->fused_host_copy, sizeof fh) != 0) {
             h->fused_host_copy = fh;
             HIPCHK(h, hipMemcpyAsync(h->d_fused, &h->fused_host_copy, sizeof fh, hipMemcpyHostToDevice, h->stream));
@@ -2757,12 +2716,12 @@ static int noise_cache_extend(f110_sim *h, int upto)
         // grow the cache's memory (doubling, capped): the rows generated so far move to the new block
         const size_t B = (size_t)h->cfg.num_beams;
         const int want = std::min(cap, std::max(2 * h->noise_rows_alloc, upto));
-        double *bigger = nullptr;
+        DevBuf<double> bigger;
         TRY(dmalloc(h, &bigger, (size_t)want * B));
         HIPCHK(h, hipMemcpyAsync(bigger, h->d_noise, sizeof(double) * (size_t)h->noise_rows_ready * B, hipMemcpyDeviceToDevice, h->stream));
-        h->noise_retired.push_back(h->d_noise);   // earlier steps (env blocks on their own streams) may still read the old block
-        h->d_noise = bigger;
-        h->dev.noise = bigger;
+        h->noise_retired.push_back(std::move(h->d_noise));   // earlier steps (env blocks on their own streams) may still read the old block
+        h->d_noise = std::move(bigger);
+        h->dev.noise = h->d_noise;
         h->noise_rows_alloc = want;
     }
     hipLaunchKernelGGL(k_noise_cache, dim3(1), dim3(64), 0, h->stream, h->noise_gen, h->dev.rng_inc, h->d_rng_rowstate, h->d_noise, h->noise_rows_ready, upto,
@@ -2816,12 +2775,12 @@ static int noise_start_ahead(f110_sim *h)
     // behind whatever produced the rows so far (the main stream: f110_set_noise_rng, a step that could not wait; or this stream)
     HIPCHK(h, hipEventRecord(h->ev_noise_src, h->stream));
     HIPCHK(h, hipStreamWaitEvent(h->noise_stream, h->ev_noise_src, 0));
-    double *block = h->d_noise;
+    double *block = h->d_noise;   // the rows fit the cache's block, or they go into a new one that noise_ahead_block owns until adoption
     int alloc = h->noise_rows_alloc;
     if (upto > alloc) {
         alloc = std::min(cap, std::max(2 * alloc, upto));
-        block = nullptr;
-        TRY(dmalloc(h, &block, (size_t)alloc * B));
+        TRY(dmalloc(h, &h->noise_ahead_block, (size_t)alloc * B));
+        block = h->noise_ahead_block;
         HIPCHK(h, hipMemcpyAsync(block, h->d_noise, sizeof(double) * (size_t)ready * B, hipMemcpyDeviceToDevice, h->noise_stream));
     }
     hipLaunchKernelGGL(k_noise_cache, dim3(1), dim3(64), 0, h->noise_stream, h->noise_gen, h->dev.rng_inc, h->d_rng_rowstate, block, ready, upto, h->cfg.num_beams);
@@ -2830,7 +2789,6 @@ static int noise_start_ahead(f110_sim *h)
     h->noise_ahead = true;
     h->noise_ahead_upto = upto;
     h->noise_ahead_alloc = alloc;
-    h->noise_ahead_block = block;
     return F110_OK;
 }
 
@@ -2839,15 +2797,14 @@ static int noise_adopt(f110_sim *h)
 {
     if (!h->noise_ahead) return F110_OK;
     HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_noise, 0));
-    if (h->noise_ahead_block != h->d_noise) {
-        h->noise_retired.push_back(h->d_noise);
-        h->d_noise = h->noise_ahead_block;
+    if (h->noise_ahead_block) {
+        h->noise_retired.push_back(std::move(h->d_noise));
+        h->d_noise = std::move(h->noise_ahead_block);
         h->dev.noise = h->d_noise;
         h->noise_rows_alloc = h->noise_ahead_alloc;
     }
     h->noise_rows_ready = h->noise_ahead_upto;
     h->noise_ahead = false;
-    h->noise_ahead_block = nullptr;
     h->main_dirty = true;
     return F110_OK;
 }
@@ -2878,9 +2835,9 @@ static int tiny_setup(f110_sim *h)
     // one allocation: [done + pad | wall N | buf_cnt N] int32 then the double columns, then the headers
     const size_t ints = 16 + 2 * N, dbls = (7 + 2 + 3 + 3 + 1) * N;
     const size_t bytes = ((ints * 4 + 63) / 64) * 64 + dbls * 8 + N * sizeof(RayHdr);
-    HIPCHK(h, hipMalloc(&h->tiny_mem, bytes));
+    TRY(dmalloc(h, &h->tiny_mem, bytes));
     HIPCHK(h, hipMemsetAsync(h->tiny_mem, 0, bytes, h->stream));
-    char *base = static_cast<char *>(h->tiny_mem);
+    char *base = reinterpret_cast<char *>(h->tiny_mem.get());
     TinyCtl &t = h->tiny;
     t.done = reinterpret_cast<unsigned int *>(base);
     t.wall = reinterpret_cast<int32_t *>(base) + 16;
@@ -3710,14 +3667,9 @@ int f110_clone_envs_device(f110_sim *h, const int32_t *d_src, const int32_t *d_d
 
 static int state_scratch(f110_sim *h, size_t bytes)
 {
-    if (bytes <= h->state_blob_bytes) return F110_OK;
+    if (bytes <= h->d_state_blob.capacity()) return F110_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_state_blob) (void)hipFree(h->d_state_blob);
-    h->d_state_blob = nullptr;
-    h->state_blob_bytes = 0;
-    HIPCHK(h, hipMalloc(&h->d_state_blob, bytes));
-    h->state_blob_bytes = bytes;
-    return F110_OK;
+    return dgrow(h, h->d_state_blob, bytes);
 }
 
 int f110_state_save(f110_sim *h, void *h_blob, int32_t flags)
@@ -3730,7 +3682,7 @@ int f110_state_save(f110_sim *h, void *h_blob, int32_t flags)
     const size_t bytes = state_columns(h, cols, E, &t);
     TRY(state_scratch(h, bytes));
     const StateHeader hd = state_header(h, E, flags, cols, bytes);
-    TRY(state_launch(h, STATE_PACK, t, &hd, static_cast<char *>(h->d_state_blob), 0, nullptr, nullptr, E, nullptr));
+    TRY(state_launch(h, STATE_PACK, t, &hd, reinterpret_cast<char *>(h->d_state_blob.get()), 0, nullptr, nullptr, E, nullptr));
     HIPCHK(h, hipMemcpyAsync(h_blob, h->d_state_blob, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
@@ -4207,6 +4159,8 @@ int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_
         ENTER(h);
         h->gap_specs = 0;
         h->gap_assign_host.clear();
+        h->d_gap_specs.reset();   // (hipFree waits for the calls in flight that read them)
+        h->d_gap_assign.reset();
         return F110_OK;
     }
     if (!specs || !h_assign || n_specs < 1 || n_specs > F110_GAP_MAX_SPECS)
@@ -4290,7 +4244,7 @@ int f110_scan_path_stats(f110_sim *h, int32_t enable, int64_t *out3)
     ENTER(h);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     if (!h->d_path_stats) {
-        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_path_stats), 3 * sizeof(unsigned long long)));
+        TRY(dmalloc(h, &h->d_path_stats, 3));
         HIPCHK(h, hipMemsetAsync(h->d_path_stats, 0, 3 * sizeof(unsigned long long), h->stream));
     }
     if (out3) {
@@ -4617,10 +4571,8 @@ static int track_upload(f110_sim *h)
         }
     }
     if (h->n_tracks_dev != slots) {
-        if (h->d_tracks) HIPCHK(h, hipFree(h->d_tracks));
-        h->d_tracks = nullptr;
-        if (h->d_track_attrs) HIPCHK(h, hipFree(h->d_track_attrs));
-        h->d_track_attrs = nullptr;
+        h->d_tracks.reset();
+        h->d_track_attrs.reset();
         h->n_tracks_dev = 0;
         TRY(dmalloc(h, &h->d_tracks, (size_t)slots));
         TRY(dmalloc(h, &h->d_track_attrs, (size_t)slots));
@@ -4767,28 +4719,18 @@ int f110_track_set(f110_sim *h, int32_t slot, const double *h_xy, int32_t M, int
         cols[6 * (size_t)nseg + k] = cum;
         cum += len;
     }
-    double *d_cols = nullptr, *d_pts = nullptr;
+    DevBuf<double> d_cols, d_pts;   // built aside: a failure drops them, success moves them into the slot
     TRY(dmalloc(h, &d_cols, cols.size()));
-    if (dmalloc(h, &d_pts, 2 * (size_t)m) != F110_OK) {
-        (void)hipFree(d_cols);
-        return F110_ERR_NOMEM;
-    }
+    if (dmalloc(h, &d_pts, 2 * (size_t)m) != F110_OK) return F110_ERR_NOMEM;
     hipError_t e = hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_pts, h_xy, 2 * (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-        (void)hipFree(d_cols);
-        (void)hipFree(d_pts);
-        return fail(h, F110_ERR_HIP, "f110_track_set: upload failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, F110_ERR_HIP, "f110_track_set: upload failed: %s", hipGetErrorString(e));
     if ((int)h->tracks.size() <= slot) h->tracks.resize((size_t)slot + 1);
     f110_sim::TrackSlot &ts = h->tracks[slot];
-    if (ts.d_cols) HIPCHK(h, hipFree(ts.d_cols));   // (synchronised above: no step reads the old table any more)
-    if (ts.d_pts) HIPCHK(h, hipFree(ts.d_pts));
-    if (ts.d_attr) HIPCHK(h, hipFree(ts.d_attr));   // a new track: the old one's attributes go with it
-    ts.d_attr = nullptr;
+    ts.d_cols = std::move(d_cols);   // (synchronised above: no step reads the old table any more)
+    ts.d_pts = std::move(d_pts);
+    ts.d_attr.reset();               // a new track: the old one's attributes go with it
     ts.nattr = 0;
-    ts.d_cols = d_cols;
-    ts.d_pts = d_pts;
     ts.npts = m;
     ts.nseg = nseg;
     ts.closed = closed ? 1 : 0;
@@ -4921,18 +4863,14 @@ int f110_track_set_attrs(f110_sim *h, int32_t slot, const double *h_attr, int32_
             }
     }
     ENTER(h);
-    double *d_attr = nullptr;
+    DevBuf<double> d_attr;
     if (!clear) {
         TRY(dmalloc(h, &d_attr, cols.size()));
         const hipError_t e = hipMemcpyAsync(d_attr, cols.data(), cols.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(d_attr);
-            return fail(h, F110_ERR_HIP, "f110_track_set_attrs: upload failed: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(h, F110_ERR_HIP, "f110_track_set_attrs: upload failed: %s", hipGetErrorString(e));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (the source is a local; no preview reads the old columns any more)
-    if (ts.d_attr) HIPCHK(h, hipFree(ts.d_attr));
-    ts.d_attr = d_attr;
+    ts.d_attr = std::move(d_attr);
     ts.nattr = clear ? 0 : C;
     h->tracks_dirty = true;
     return F110_OK;
@@ -5191,26 +5129,14 @@ int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, dou
 // rendering.py's clear colour (OUTSIDE, FREE), its map points and waypoint_follow.py's waypoints (WALL, TRACK), then SCAN, CAR, SELF
 static const uint8_t kDefaultPalette[F110_NCLASSES * 3] = {9, 32, 87, 9, 32, 87, 183, 193, 222, 183, 193, 222, 255, 190, 0, 99, 52, 94, 172, 97, 185};
 
-template <typename T>
-static int render_grow(f110_sim *h, T **p, size_t *cap, size_t count)
-{
-    if (*p && *cap >= count) return F110_OK;
-    if (*p) HIPCHK(h, hipFree(*p));   // (hipFree waits for the renders in flight that read it)
-    *p = nullptr;
-    *cap = 0;
-    TRY(dmalloc(h, p, count));
-    *cap = count;
-    return F110_OK;
-}
-
 // the occupancy grid of a slot's table, built the first time a render reads the slot
-static int render_occ(f110_sim *h, const ScanConst &k, uint8_t **occ, bool *stale)
+static int render_occ(f110_sim *h, const ScanConst &k, DevBuf<uint8_t> *occ, bool *stale)
 {
     if (*occ && !(stale && *stale)) return F110_OK;
     const size_t n = (size_t)k.height * k.width;
     if (!*occ) TRY(dmalloc(h, occ, n));
     if (stale) *stale = false;
-    hipLaunchKernelGGL(k_render_occ, grid1d(n, 256), dim3(256), 0, h->stream, k.table, k.row_bytes, k.height, k.width, *occ);
+    hipLaunchKernelGGL(k_render_occ, grid1d(n, 256), dim3(256), 0, h->stream, k.table, k.row_bytes, k.height, k.width, occ->get());
     HIPCHK(h, hipGetLastError());
     return F110_OK;
 }
@@ -5247,7 +5173,7 @@ int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t 
         RenderSlot &r = rs[m];
         r = RenderSlot{};
         if (sp.layers & F110_LAYER_MAP) TRY(render_occ(h, k, m == 0 ? &h->d_occ0 : &h->extra_maps[m - 1].d_occ, m == 0 ? nullptr : &h->extra_maps[m - 1].occ_stale));
-        r.occ = m == 0 ? h->d_occ0 : h->extra_maps[m - 1].d_occ;
+        r.occ = m == 0 ? h->d_occ0.get() : h->extra_maps[m - 1].d_occ.get();
         if ((sp.layers & F110_LAYER_TRACK) && m < (int)h->tracks.size() && h->tracks[m].d_pts) {
             r.pts = h->tracks[m].d_pts;
             r.npts = h->tracks[m].npts;
@@ -5264,14 +5190,14 @@ int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t 
         r.h_res = k.h_res;
     }
     if (h->render_slots.size() != rs.size() || std::memcmp(h->render_slots.data(), rs.data(), rs.size() * sizeof(RenderSlot)) != 0) {
-        TRY(render_grow(h, &h->d_render_slots, &h->render_slots_cap, rs.size()));
+        TRY(dgrow(h, h->d_render_slots, rs.size()));
         h->render_slots = rs;   // (a pageable source: consumed before the call returns)
         HIPCHK(h, hipMemcpyAsync(h->d_render_slots, h->render_slots.data(), rs.size() * sizeof(RenderSlot), hipMemcpyHostToDevice, h->stream));
     }
-    TRY(render_grow(h, &h->d_render_frames, &h->render_frames_cap, (size_t)F));
+    TRY(dgrow(h, h->d_render_frames, (size_t)F));
     if (!h->d_render_cars) TRY(dmalloc(h, &h->d_render_cars, (size_t)N));
     if (h_agents) {
-        TRY(render_grow(h, &h->d_render_agents, &h->render_agents_cap, (size_t)F));
+        TRY(dgrow(h, h->d_render_agents, (size_t)F));
         HIPCHK(h, hipMemcpyAsync(h->d_render_agents, h_agents, (size_t)F * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     }
     // 32-bit stores straight into the caller's buffer when its rows allow them, else into an aligned copy with padded rows
@@ -5279,7 +5205,7 @@ int f110_render_device(f110_sim *h, const f110_render_spec *spec, const int32_t 
     const int pitch = (W + 3) & ~3;
     uint8_t *target = d_classes;
     if (!direct) {
-        TRY(render_grow(h, &h->d_render_stage, &h->render_stage_cap, (size_t)F * H * pitch));
+        TRY(dgrow(h, h->d_render_stage, (size_t)F * H * pitch));
         target = h->d_render_stage;
     }
     RenderJob j{};
@@ -5485,9 +5411,9 @@ int f110_rollout_device(f110_sim *h, const f110_rollout *spec, const double *d_a
     if (track) {
         TRY(tracks_in_use(h, "rollout: PROGRESS or END_LAT is requested"));
         TRY(tracks_current(h));
-        if (h->roll_end_cap < 2 * N * j.sp.K) {
+        if (h->d_roll_end.capacity() < 2 * N * j.sp.K) {
             ENTER(h);
-            TRY(render_grow(h, &h->d_roll_end, &h->roll_end_cap, 2 * N * j.sp.K));
+            TRY(dgrow(h, h->d_roll_end, 2 * N * j.sp.K));
         }
     }
     EnvBlocks w;   // behind a two-block step: each block's agents on the block's own stream (a candidate reads its own agent's rows and writes its own)
@@ -5496,7 +5422,7 @@ int f110_rollout_device(f110_sim *h, const f110_rollout *spec, const double *d_a
     j.actions = d_actions;
     j.out = d_out;
     j.traj = j.sp.traj ? d_traj : nullptr;
-    j.end_xy = track ? h->d_roll_end : nullptr;
+    j.end_xy = track ? h->d_roll_end.get() : nullptr;
     return env_blocks_output(h, w, kPinnedRollout, per_agent, d_out, h_pinned, [&](const EnvBlock &b) {
         j.begin = b.e0 * j.A;
         j.count = b.count * j.A;
@@ -5580,24 +5506,14 @@ static int mppi_check_spec(f110_sim *h, const f110_mppi *p, MppiSpec &o)
     return F110_OK;
 }
 
-static void mppi_free(f110_sim::Mppi &p)
+// a feature's jump constants in device memory, [2][count], from its first arming on: build fills the two halves
+static int jump_ensure(f110_sim *h, DevBuf<U128> &buf, void (*build)(U128 *, U128 *), int count)
 {
-    void *ptrs[] = {p.d_agents, p.d_spec, p.d_nominal, p.d_streams, p.d_V, p.d_cost, p.d_end};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);   // (hipFree waits for the calls in flight that read it)
-    p = f110_sim::Mppi{};
-}
-
-static void mppi_free(f110_sim *h) { mppi_free(h->mppi); }
-
-// the candidates' jump constants in device memory
-static int mppi_jump_ensure(f110_sim *h)
-{
-    if (h->d_mppi_jump) return F110_OK;
-    std::vector<U128> t(2 * (size_t)kMppiJumps);
-    mppi_jump_table(t.data(), t.data() + kMppiJumps);
-    TRY(dmalloc(h, &h->d_mppi_jump, t.size()));
-    HIPCHK(h, hipMemcpy(h->d_mppi_jump, t.data(), t.size() * sizeof(U128), hipMemcpyHostToDevice));
+    if (buf) return F110_OK;
+    std::vector<U128> t(2 * (size_t)count);
+    build(t.data(), t.data() + count);
+    TRY(dmalloc(h, &buf, t.size()));
+    HIPCHK(h, hipMemcpy(buf, t.data(), t.size() * sizeof(U128), hipMemcpyHostToDevice));
     return F110_OK;
 }
 
@@ -5673,7 +5589,7 @@ int f110_mppi_set(f110_sim *h, const f110_mppi *spec, const int32_t *h_agents, i
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     if (!spec && !h_agents && m == 0 && !h_streams) {   // disarm
         ENTER(h);
-        mppi_free(h);
+        h->mppi = {};   // (hipFree waits for the calls in flight that read its memory)
         return F110_OK;
     }
     if (!spec || !h_agents || !h_streams) return fail(h, F110_ERR_INVALID, "mppi: a spec, the agents and their streams, or NULL, NULL, 0, NULL");
@@ -5688,32 +5604,27 @@ int f110_mppi_set(f110_sim *h, const f110_mppi *spec, const int32_t *h_agents, i
     }
     if ((size_t)m * sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "mppi: %d agents x %d candidates do not fit 31 bits", m, sp.K);
     ENTER(h);
-    TRY(mppi_jump_ensure(h));
+    TRY(jump_ensure(h, h->d_mppi_jump, mppi_jump_table, kMppiJumps));
     f110_sim::Mppi p;   // built aside: a failure below leaves the planner that is armed (if any) as it is
     const size_t M = (size_t)m, seq = (size_t)sp.H * 2, cands = M * sp.K;
     std::vector<double> nominal(M * seq);
     for (size_t q = 0; q < nominal.size(); ++q) nominal[q] = (q & 1) ? sp.v_init : 0.0;
-    int rc = dmalloc(h, &p.d_agents, M);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_spec, 1);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_nominal, M * seq);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_streams, 4 * M);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_V, cands * seq);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_cost, cands);
-    if (rc == F110_OK && mppi_needs_track(sp)) rc = dmalloc(h, &p.d_end, 2 * cands);
-    if (rc == F110_OK && (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(p.d_spec, &sp, sizeof sp, hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(p.d_nominal, nominal.data(), nominal.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess))
-        rc = fail(h, F110_ERR_HIP, "mppi: the upload failed");
-    if (rc != F110_OK) {
-        mppi_free(p);
-        return rc;
-    }
+    TRY(dmalloc(h, &p.d_agents, M));
+    TRY(dmalloc(h, &p.d_spec, 1));
+    TRY(dmalloc(h, &p.d_nominal, M * seq));
+    TRY(dmalloc(h, &p.d_streams, 4 * M));
+    TRY(dmalloc(h, &p.d_V, cands * seq));
+    TRY(dmalloc(h, &p.d_cost, cands));
+    if (mppi_needs_track(sp)) TRY(dmalloc(h, &p.d_end, 2 * cands));
+    if (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_spec, &sp, sizeof sp, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_nominal, nominal.data(), nominal.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(h, F110_ERR_HIP, "mppi: the upload failed");
     p.sp = sp;
     p.agents.assign(h_agents, h_agents + m);
     p.m = m;
-    mppi_free(h);
-    h->mppi = std::move(p);
+    h->mppi = std::move(p);   // (the planner armed so far goes: hipFree waits for the calls in flight that read its memory)
     return F110_OK;
 }
 
@@ -5786,7 +5697,7 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
     UnitRows rows;
     TRY(unit_rows(h, "mppi", h_start, M, rows));
     ENTER(h);
-    TRY(mppi_jump_ensure(h));
+    TRY(jump_ensure(h, h->d_mppi_jump, mppi_jump_table, kMppiJumps));
     if (track) TRY(track_upload(h));
     Scratch sc(h);
     double *dnom = nullptr, *dV = nullptr, *dcost = nullptr, *dend = nullptr, *dw = nullptr, *dact = nullptr;
@@ -5858,27 +5769,6 @@ static int pf_check_spec(f110_sim *h, const f110_pf *p, PfSpec &o)
 static int pf_check_count(f110_sim *h, const PfSpec &sp, int m)
 {
     if ((size_t)m * sp.P * sp.B >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "pf: %d agents x %d particles x %d beams do not fit 31 bits", m, sp.P, sp.B);
-    return F110_OK;
-}
-
-static void pf_free(f110_sim::Pf &p)
-{
-    void *ptrs[] = {p.d_agents, p.d_streams, p.d_X[0], p.d_X[1], p.d_W, p.d_last, p.d_cum, p.d_logw, p.d_plan, p.d_hdr};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);   // (hipFree waits for the calls in flight that read it)
-    p = f110_sim::Pf{};
-}
-
-static void pf_free(f110_sim *h) { pf_free(h->pf); }
-
-// the sub-streams' jump constants in device memory
-static int pf_jump_ensure(f110_sim *h)
-{
-    if (h->d_pf_jump) return F110_OK;
-    std::vector<U128> t(2 * (size_t)kPfJumps);
-    pf_jump_table(t.data(), t.data() + kPfJumps);
-    TRY(dmalloc(h, &h->d_pf_jump, t.size()));
-    HIPCHK(h, hipMemcpy(h->d_pf_jump, t.data(), t.size() * sizeof(U128), hipMemcpyHostToDevice));
     return F110_OK;
 }
 
@@ -5978,7 +5868,7 @@ int f110_pf_set(f110_sim *h, const f110_pf *spec, const int32_t *h_agents, int32
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     if (!spec && !h_agents && m == 0 && !h_streams) {   // disarm
         ENTER(h);
-        pf_free(h);
+        h->pf = {};   // (hipFree waits for the calls in flight that read its memory)
         return F110_OK;
     }
     if (!spec || !h_agents || !h_streams) return fail(h, F110_ERR_INVALID, "pf: a spec, the agents and their streams, or NULL, NULL, 0, NULL");
@@ -5991,36 +5881,31 @@ int f110_pf_set(f110_sim *h, const f110_pf *spec, const int32_t *h_agents, int32
     }
     TRY(pf_check_count(h, sp, m));
     ENTER(h);
-    TRY(pf_jump_ensure(h));
+    TRY(jump_ensure(h, h->d_pf_jump, pf_jump_table, kPfJumps));
     f110_sim::Pf p;   // built aside: a failure below leaves the filter that is armed (if any) as it is
     const size_t M = (size_t)m, parts = M * sp.P;
     std::vector<double> w(parts, 1.0 / (double)sp.P);
-    int rc = dmalloc(h, &p.d_agents, M);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_streams, 4 * M);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_X[0], 3 * parts);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_X[1], 3 * parts);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_W, parts);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_last, 3 * M);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_cum, parts);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_logw, parts);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_plan, M);
-    if (rc == F110_OK) rc = dmalloc(h, &p.d_hdr, parts);
-    if (rc == F110_OK && (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(p.d_W, w.data(), parts * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemset(p.d_X[0], 0, 3 * parts * sizeof(double)) != hipSuccess ||
-                          hipMemset(p.d_X[1], 0, 3 * parts * sizeof(double)) != hipSuccess ||
-                          hipMemset(p.d_last, 0, 3 * M * sizeof(double)) != hipSuccess))
-        rc = fail(h, F110_ERR_HIP, "pf: the upload failed");
-    if (rc != F110_OK) {
-        pf_free(p);
-        return rc;
-    }
+    TRY(dmalloc(h, &p.d_agents, M));
+    TRY(dmalloc(h, &p.d_streams, 4 * M));
+    TRY(dmalloc(h, &p.d_X[0], 3 * parts));
+    TRY(dmalloc(h, &p.d_X[1], 3 * parts));
+    TRY(dmalloc(h, &p.d_W, parts));
+    TRY(dmalloc(h, &p.d_last, 3 * M));
+    TRY(dmalloc(h, &p.d_cum, parts));
+    TRY(dmalloc(h, &p.d_logw, parts));
+    TRY(dmalloc(h, &p.d_plan, M));
+    TRY(dmalloc(h, &p.d_hdr, parts));
+    if (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_W, w.data(), parts * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(p.d_X[0], 0, 3 * parts * sizeof(double)) != hipSuccess ||
+        hipMemset(p.d_X[1], 0, 3 * parts * sizeof(double)) != hipSuccess ||
+        hipMemset(p.d_last, 0, 3 * M * sizeof(double)) != hipSuccess)
+        return fail(h, F110_ERR_HIP, "pf: the upload failed");
     p.sp = sp;
     p.agents.assign(h_agents, h_agents + m);
     p.m = m;
-    pf_free(h);
-    h->pf = std::move(p);
+    h->pf = std::move(p);   // (the filter armed so far goes: hipFree waits for the calls in flight that read its memory)
     return F110_OK;
 }
 
@@ -6087,7 +5972,7 @@ int f110_pf_batch(f110_sim *h, const f110_pf *spec, int32_t slot, const double *
         for (int c = 0; c < 3; ++c) cols[(size_t)c * M + r] = h_poses[3 * r + c];
     ScanConst kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
     ENTER(h);
-    TRY(pf_jump_ensure(h));
+    TRY(jump_ensure(h, h->d_pf_jump, pf_jump_table, kPfJumps));
     Scratch sc(h);
     double *dcols = nullptr, *dscans = nullptr, *dX0 = nullptr, *dX1 = nullptr, *dW = nullptr, *dlast = nullptr, *dcum = nullptr, *dlogw = nullptr;
     double *dpose = nullptr, *dnoise = nullptr, *dexp = nullptr;

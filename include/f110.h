@@ -96,6 +96,10 @@ int f110_device_pci_bus_id(int32_t device, char *out, int32_t len);
 /* "csrc=<sha256 prefix of the kernel sources this library was built from>": profiles/ entries and
  * bench.py's roofline record carry the same hash, so a reader can tie a number to the code */
 const char *f110_build_info(void);
+/* Device allocations the library's handles own at this moment, process-wide: their count and their bytes (either pointer
+ * may be NULL).  Takes no handle, so that it can be read after f110_destroy: a handle that is gone has given everything
+ * back.  Caller-owned memory (f110_device_alloc) and page-locked host memory are not counted. */
+int f110_device_allocs(int64_t *live, int64_t *bytes);
 
 /* 1 for libf110_hip_exp.so (-DF110_EXPERIMENTAL), 0 for the product library */
 int f110_is_experimental(void);
