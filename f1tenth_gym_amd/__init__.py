@@ -19,6 +19,7 @@ from .track_preview import TrackPreview  # noqa: F401
 from .neighbors import Neighbors  # noqa: F401
 from .rollout import Rollout  # noqa: F401
 from .mppi import Mppi  # noqa: F401
+from .opponents import Opponents  # noqa: F401
 from .particle_filter import ParticleFilter  # noqa: F401
 from .obstacles import Obstacles  # noqa: F401
 from . import render  # noqa: F401

@@ -135,6 +135,14 @@ class MppiSpec(C.Structure):
 MPPI_MAX_K, MPPI_MAX_H, MPPI_MAX_REPEAT = 256, 64, 16
 
 
+class OpponentsSpec(C.Structure):
+    """struct f110_opponents"""
+    _fields_ = [("mode", C.c_int32), ("pad_", C.c_int32), ("radius", C.c_double), ("max_range", C.c_double)]
+
+
+OPP_CV, OPP_TRACK, OPP_MAX = 0, 1, 31
+
+
 class PfSpec(C.Structure):
     """struct f110_pf"""
     _fields_ = [("particles", C.c_int32), ("n_beams", C.c_int32), ("beam_first", C.c_int32), ("beam_stride", C.c_int32),
@@ -299,6 +307,13 @@ PROTOTYPES = {
     "f110_mppi_get": (C.c_int, [C.c_void_p, _dp, _u64p]),
     "f110_mppi_put": (C.c_int, [C.c_void_p, _dp, _u64p]),
     "f110_mppi_batch": (C.c_int, [C.c_void_p, C.POINTER(MppiSpec), C.c_int32, _dp, _dp, _i32p, C.c_int32, _dp, _u64p, _dp, C.c_void_p, _dp, _dp, _dp]),
+    "f110_rollout_opp_device": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.POINTER(OpponentsSpec), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "f110_rollout_opp_batch": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.POINTER(OpponentsSpec), C.c_int32, _dp, _dp, _dp, _dp, C.c_int32,
+                                         C.c_int32, C.c_void_p, _dp, C.c_void_p, _dp, _dp, _dp, C.c_void_p]),
+    "f110_mppi_set_opponents": (C.c_int, [C.c_void_p, C.POINTER(OpponentsSpec), C.c_double, C.c_double, C.c_double]),
+    "f110_mppi_opp_batch": (C.c_int, [C.c_void_p, C.POINTER(MppiSpec), C.POINTER(OpponentsSpec), C.c_double, C.c_double, C.c_double, C.c_int32,
+                                      _dp, _dp, _i32p, _dp, C.c_int32, C.c_int32, _dp, _u64p, _dp, C.c_void_p, _dp, _dp, _dp, _dp]),
     "f110_pf_set": (C.c_int, [C.c_void_p, C.POINTER(PfSpec), _i32p, C.c_int32, _u64p]),
     "f110_pf_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "f110_pf_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _u64p]),

@@ -1226,6 +1226,9 @@ class BatchSim(object):
         ones).  Enqueued on the handle's stream, per env block behind a two-block step (no host wait).  pinned: a pinned_empty
         float32 array of the summary's shape that also receives it, complete after sync().  'progress' and 'end_lat' need a track
         on every map slot in use (set_track); tracking need not be enabled."""
+        return self._rollout_device(spec, d_actions, out, traj, pinned)
+
+    def _rollout_device(self, spec, d_actions, out, traj, pinned, opponents=None, opp=None):
         from .rollout import Rollout
         ro = Rollout.coerce(spec)
         shape, tshape, ashape = ro.shape(self.N), ro.traj_shape(self.N), ro.actions_shape(self.N)
@@ -1239,8 +1242,56 @@ class BatchSim(object):
             traj = self._f32_out(tshape, traj, "traj")
         pp = self._pinned_ptr(shape, pinned)
         sp = ro.spec()
-        check(_ffi.lib().f110_rollout_device(self._h, C.byref(sp), d_actions.ptr, out.ptr, traj.ptr if ro.traj else None, pp), self._h)
-        return (out, traj) if ro.traj else out
+        if opponents is None:
+            check(_ffi.lib().f110_rollout_device(self._h, C.byref(sp), d_actions.ptr, out.ptr, traj.ptr if ro.traj else None, pp), self._h)
+            return (out, traj) if ro.traj else out
+        opp = self._f32_out((self.N, ro.k, 2), opp, "opp")
+        osp = opponents.spec()
+        check(_ffi.lib().f110_rollout_opp_device(self._h, C.byref(sp), C.byref(osp), d_actions.ptr, out.ptr, traj.ptr if ro.traj else None,
+                                                 opp.ptr, pp), self._h)
+        return (out, traj, opp) if ro.traj else (out, opp)
+
+    def rollout_opp_device(self, spec, opponents, d_actions, out=None, traj=None, opp=None, pinned=None):
+        """rollout_device with every candidate measured against the predicted motion of the other cars of its env
+        (opponents.Opponents): returns (summary, opp) or with spec.traj (summary, trajectory, opp); opp is a float32
+        DeviceArray [N][K][2] = (the smallest distance to a prediction, the first action within the radius of one, H when none).
+        The summary and the trajectory are rollout_device's, bit for bit.  'track' mode needs a track on every map slot in use."""
+        from .opponents import Opponents
+        return self._rollout_device(spec, d_actions, out, traj, pinned, Opponents.coerce(opponents), opp)
+
+    def rollout_opp(self, spec, opponents, actions):
+        """rollout_opp_device on host candidates, returned as NumPy: (summary, opp float32 [N][K][2]), or with spec.traj (summary,
+        trajectory, opp)"""
+        from .rollout import Rollout
+        ro = Rollout.coerce(spec)
+        a = as_f64(actions)
+        if tuple(a.shape) != ro.actions_shape(self.N):
+            raise ValueError("actions must have shape %s" % (ro.actions_shape(self.N),))
+        with DeviceArray(self, a.shape, np.float64) as d_act:
+            d_act.upload(a)
+            res = self.rollout_opp_device(ro, opponents, d_act)
+            host = tuple(r.download() for r in res)
+            for r in res:
+                r.free()
+        return host
+
+    @staticmethod
+    def _opp_rows(opp_rows, m):
+        """the unit forms' opponent rows [m][Ao][4] = x, y, v, theta (None: no opponents)"""
+        if opp_rows is None:
+            return np.zeros((m, 0, 4)), 0
+        r = as_f64(opp_rows)
+        if r.ndim != 3 or r.shape[0] != m or r.shape[2] != 4:
+            raise ValueError("opp_rows must be [m][Ao][4] = x, y, v, theta")
+        return r, int(r.shape[1])
+
+    def rollout_opp_rows(self, spec, opponents, start, actions, opp_rows, slot=0, params=None):
+        """rollout_rows with the opponent term on host rows: opp_rows [m][Ao][4] = (x, y, v, theta) of each row's opponents (None:
+        none) -> a dict: out, raw, traj, traj_raw as rollout_rows(raw=True) returns them (the trajectory entries None without
+        spec.traj), pred float64 [m][Ao][H][2] the predictions (NaN: ignored), opp_raw float64 [m][K][2] = (OPP_MIN, OPP_FREE) and
+        opp float32 [m][K][2] what the device form writes"""
+        from .opponents import Opponents
+        return self._rollout_rows(spec, start, actions, slot, params, True, Opponents.coerce(opponents), opp_rows)
 
     def rollout(self, spec, actions):
         """rollout_device on host candidates `actions` (spec.actions_shape(N)), returned as NumPy: the summary float32 [N][K][D],
@@ -1264,6 +1315,9 @@ class BatchSim(object):
         all on map slot `slot`; params [m][18] (None: this handle's row of agent slot 0); actions spec.actions_shape(m) -> the summary
         float32 [m][K][D]; with spec.traj also the trajectory float32 [m][K][H][4]; with raw also float64 [m][K][10] (every channel
         before scaling; 'progress' and 'end_lat' 0.0 when the slot has no track) and, with spec.traj, the float64 trajectory"""
+        return self._rollout_rows(spec, start, actions, slot, params, raw)
+
+    def _rollout_rows(self, spec, start, actions, slot, params, raw, opponents=None, opp_rows=None):
         from .rollout import Rollout
         ro = Rollout.coerce(spec)
         st = as_f64(start)
@@ -1283,10 +1337,19 @@ class BatchSim(object):
         tr = np.zeros(ro.traj_shape(m), dtype=np.float32) if ro.traj else None
         trw = np.zeros(ro.traj_shape(m)) if ro.traj and raw else None
         sp = ro.spec()
-        check(_ffi.lib().f110_rollout_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), dptr(a), m, out.ctypes.data,
-                                            None if rw is None else dptr(rw), None if tr is None else tr.ctypes.data,
-                                            None if trw is None else dptr(trw)), self._h)
-        return _with_extras(out, tr, rw, trw)
+        if opponents is None:
+            check(_ffi.lib().f110_rollout_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), dptr(a), m, out.ctypes.data,
+                                                None if rw is None else dptr(rw), None if tr is None else tr.ctypes.data,
+                                                None if trw is None else dptr(trw)), self._h)
+            return _with_extras(out, tr, rw, trw)
+        orows, Ao = self._opp_rows(opp_rows, m)
+        pred, oraw, o32 = np.zeros((m, Ao, ro.horizon, 2)), np.zeros((m, ro.k, 2)), np.zeros((m, ro.k, 2), dtype=np.float32)
+        osp = opponents.spec()
+        check(_ffi.lib().f110_rollout_opp_batch(self._h, C.byref(sp), C.byref(osp), int(slot), dptr(st), None if pv is None else dptr(pv), dptr(a),
+                                                dptr(orows) if Ao else None, Ao, m, out.ctypes.data, dptr(rw),
+                                                None if tr is None else tr.ctypes.data, None if trw is None else dptr(trw),
+                                                dptr(pred) if Ao else None, dptr(oraw), o32.ctypes.data), self._h)
+        return dict(out=out, raw=rw, traj=tr, traj_raw=trw, pred=pred, opp_raw=oraw, opp=o32)
 
     # ------------------------------------------------------------------ MPPI planner (f110_mppi_*)
     mppi_planner, mppi_agents = None, None
@@ -1308,13 +1371,33 @@ class BatchSim(object):
         words = np.ascontiguousarray(stream_words(seed, int(a[-1]) - lo + 1, int(agent_base) + lo)[a - lo], dtype=np.uint64)
         sp = mp.spec()
         check(_ffi.lib().f110_mppi_set(self._h, C.byref(sp), i32ptr(a), int(a.size), words.ctypes.data_as(_ffi._u64p)), self._h)
-        self.mppi_planner, self.mppi_agents = mp, a
+        self.mppi_planner, self.mppi_agents, self.mppi_opponents = mp, a, None
         return mp
 
     def clear_mppi(self):
-        """disarm the planner and free its memory"""
+        """disarm the planner and free its memory (the opponent term attached to it goes with it)"""
         check(_ffi.lib().f110_mppi_set(self._h, None, None, 0, None), self._h)
-        self.mppi_planner, self.mppi_agents = None, None
+        self.mppi_planner, self.mppi_agents, self.mppi_opponents = None, None, None
+
+    mppi_opponents = None
+
+    def set_mppi_opponents(self, opp, w_hit=0.0, w_near=0.0, near_ref=0.0):
+        """attach the opponent term (opponents.Opponents or a dict of its settings) to the armed planner: every
+        candidate then also costs w_hit * (actions from its first sample within the radius of a predicted opponent to the horizon)
+        + w_near * max(near_ref - its smallest distance to a prediction, 0).  Nothing is launched; mppi_device and
+        step_host(scripted=True) use it from the next call on.  set_mppi and clear_mppi drop it.  Returns the Opponents."""
+        from .opponents import Opponents, check_weights
+        op = Opponents.coerce(opp)
+        w_hit, w_near, near_ref = check_weights(w_hit, w_near, near_ref)
+        sp = op.spec()
+        check(_ffi.lib().f110_mppi_set_opponents(self._h, C.byref(sp), w_hit, w_near, near_ref), self._h)
+        self.mppi_opponents = (op, w_hit, w_near, near_ref)
+        return op
+
+    def clear_mppi_opponents(self):
+        """detach the opponent term; the planner stays armed"""
+        check(_ffi.lib().f110_mppi_set_opponents(self._h, None, 0.0, 0.0, 0.0), self._h)
+        self.mppi_opponents = None
 
     def mppi_device(self, d_actions, info=None):
         """one planning call: the armed agents' rows of the device action buffer [N][2] (float64, the step's layout) are written
@@ -1367,6 +1450,16 @@ class BatchSim(object):
         nominal [m][H][2], streams uint64 [m][4], params [m][18] (None: this handle's row of agent slot 0), fresh int32 [m] (the
         rows' step_count: 0 = a fresh row; None: none is).  Returns a dict: actions [m][2], info float32 [m][4], candidates
         [m][K][H][2], cost [m][K], weight [m][K], nominal and streams after the call."""
+        return self._mppi_rows(spec, start, nominal, streams, slot, params, fresh)
+
+    def mppi_opp_rows(self, spec, opponents, w_hit, w_near, near_ref, start, nominal, streams, opp_rows, slot=0, params=None, fresh=None):
+        """mppi_rows with the opponent term on host rows: opp_rows [m][Ao][4] = (x, y, v, theta) of each row's opponents (None:
+        none).  The dict also holds opp_raw float64 [m][K][2] = the candidates' (OPP_MIN, OPP_FREE)."""
+        from .opponents import Opponents, check_weights
+        return self._mppi_rows(spec, start, nominal, streams, slot, params, fresh, Opponents.coerce(opponents),
+                               check_weights(w_hit, w_near, near_ref), opp_rows)
+
+    def _mppi_rows(self, spec, start, nominal, streams, slot, params, fresh, opponents=None, weights=None, opp_rows=None):
         from .mppi import Mppi
         mp = Mppi.coerce(spec)
         st = as_f64(start)
@@ -1386,10 +1479,21 @@ class BatchSim(object):
         act, inf = np.zeros((m, 2)), np.zeros((m, 4), dtype=np.float32)
         cand, cost, wgt = np.zeros((m, mp.k, mp.horizon, 2)), np.zeros((m, mp.k)), np.zeros((m, mp.k))
         sp = mp.spec()
-        check(_ffi.lib().f110_mppi_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), None if fr is None else i32ptr(fr),
-                                         m, dptr(nom), words.ctypes.data_as(_ffi._u64p), dptr(act), inf.ctypes.data, dptr(cand), dptr(cost),
-                                         dptr(wgt)), self._h)
-        return dict(actions=act, info=inf, candidates=cand, cost=cost, weight=wgt, nominal=nom, streams=words)
+        res = dict(actions=act, info=inf, candidates=cand, cost=cost, weight=wgt, nominal=nom, streams=words)
+        if opponents is None:
+            check(_ffi.lib().f110_mppi_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), None if fr is None else i32ptr(fr),
+                                             m, dptr(nom), words.ctypes.data_as(_ffi._u64p), dptr(act), inf.ctypes.data, dptr(cand), dptr(cost),
+                                             dptr(wgt)), self._h)
+            return res
+        orows, Ao = self._opp_rows(opp_rows, m)
+        oraw = np.zeros((m, mp.k, 2))
+        osp = opponents.spec()
+        check(_ffi.lib().f110_mppi_opp_batch(self._h, C.byref(sp), C.byref(osp), weights[0], weights[1], weights[2], int(slot), dptr(st),
+                                             None if pv is None else dptr(pv), None if fr is None else i32ptr(fr), dptr(orows) if Ao else None, Ao, m,
+                                             dptr(nom), words.ctypes.data_as(_ffi._u64p), dptr(act), inf.ctypes.data, dptr(cand), dptr(cost), dptr(wgt),
+                                             dptr(oraw)), self._h)
+        res["opp_raw"] = oraw
+        return res
 
     # ------------------------------------------------------------------ particle filter (f110_pf_*)
     pf_filter, pf_agents = None, None

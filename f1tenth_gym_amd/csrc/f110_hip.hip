@@ -249,7 +249,14 @@ struct f110_sim {
         DevBuf<double> d_V;              // [m][K][H][2] the candidates of the last call
         DevBuf<double> d_cost;           // [m][K]
         DevBuf<double> d_end;            // [m][K][2] (only with a track weight)
+        // the opponent term (f110_mppi_set_opponents): attached while opp_on; it goes with the planner
+        bool opp_on = false;
+        OppSpec opp{};
+        DevBuf<OppSpec> d_opp_spec;      // opp, for the kernels
+        DevBuf<double> d_opp_table;      // [m][A - 1][H][2] the predictions of the last call
     } mppi;
+    DevBuf<double> d_roll_opp;           // f110_rollout_opp_device: the predictions [N][A - 1][H][2] (grows on demand)
+    DevBuf<OppSpec> d_roll_opp_spec;     // ... and its settings, one copy per env block, written by the block's own k_opp_predict
     DevBuf<U128> d_mppi_jump;            // [2][kMppiJumps] the candidates' jump constants (from the first arming on)
     // particle filter (f110_pf_set): m == 0: disarmed.  The clouds, the weights, the last poses and the streams are the filter's own memory.
     struct Pf {
@@ -5379,13 +5386,21 @@ static int roll_check_spec(f110_sim *h, const f110_rollout *p, RollSpec &o)
 }
 
 // agents [j.begin, j.begin + j.count): the candidates, then (track set) the two projections behind them on the same stream
-static void roll_launch(const RollJob &j, bool track, hipStream_t st)
+static void roll_launch(const RollJob &j, bool track, hipStream_t st, const OppLane *opp = nullptr)
 {
     if (j.count <= 0) return;
     const size_t lanes = (size_t)j.count * j.sp.K;
     const dim3 grid = grid1d(lanes, 256), block(256);
     const bool uni = j.sp.K % 64 == 0;
-    if (j.sp.traj) {
+    if (opp) {   // the same lanes with the opponent term's sampling (its predictions are on `st` already)
+        if (j.sp.traj) {
+            if (uni) hipLaunchKernelGGL((k_rollout_opp<true, true>), grid, block, 0, st, j, *opp);
+            else hipLaunchKernelGGL((k_rollout_opp<false, true>), grid, block, 0, st, j, *opp);
+        } else {
+            if (uni) hipLaunchKernelGGL((k_rollout_opp<true, false>), grid, block, 0, st, j, *opp);
+            else hipLaunchKernelGGL((k_rollout_opp<false, false>), grid, block, 0, st, j, *opp);
+        }
+    } else if (j.sp.traj) {
         if (uni) hipLaunchKernelGGL((k_rollout<true, true>), grid, block, 0, st, j);
         else hipLaunchKernelGGL((k_rollout<false, true>), grid, block, 0, st, j);
     } else {
@@ -5430,13 +5445,116 @@ int f110_rollout_device(f110_sim *h, const f110_rollout *spec, const double *d_a
     });
 }
 
-int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start, const double *h_params, const double *h_actions,
-                       int32_t m, float *h_out, double *h_raw, float *h_traj, double *h_traj_raw)
+// ---- opponents (f110_rollout_opp_*, f110_mppi_set_opponents, f110_mppi_opp_batch; include/f110.h) -------------------------------------
+// the settings' refusals; on success the kernels' settings (the planner's weights 0.0)
+static int opp_check_spec(f110_sim *h, const char *who, const f110_opponents *p, OppSpec &o)
 {
-    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (!p) return fail(h, F110_ERR_INVALID, "%s: null opponents", who);
+    if (p->mode != F110_OPP_CV && p->mode != F110_OPP_TRACK) return fail(h, F110_ERR_INVALID, "%s: unknown opponents mode %d", who, p->mode);
+    if (!(std::isfinite(p->radius) && p->radius > 0.0)) return fail(h, F110_ERR_INVALID, "%s: the opponents' radius must be finite and > 0", who);
+    if (!(p->max_range > 0.0)) return fail(h, F110_ERR_INVALID, "%s: the opponents' max_range must be > 0 and not NaN", who);
+    o = OppSpec{};
+    o.mode = p->mode;
+    o.radius = p->radius;
+    o.max_range = p->max_range;
+    return F110_OK;
+}
+
+static int opp_check_weights(f110_sim *h, double w_hit, double w_near, double near_ref, OppSpec &o)
+{
+    if (!(std::isfinite(w_hit) && w_hit >= 0.0) || !(std::isfinite(w_near) && w_near >= 0.0))
+        return fail(h, F110_ERR_INVALID, "mppi: w_hit and w_near must be finite and >= 0");
+    if (!std::isfinite(near_ref)) return fail(h, F110_ERR_INVALID, "mppi: near_ref must be finite");
+    o.w_hit = w_hit;
+    o.w_near = w_near;
+    o.near_ref = near_ref;
+    return F110_OK;
+}
+
+// what a unit form adds for the opponent term: the settings, the caller's opponent rows and its three outputs
+struct OppUnit {
+    OppSpec sp;
+    const double *h_rows;   // [m][Ao][4]
+    int Ao;
+    double *h_pred;         // [m][Ao][H][2] or null
+    double *h_raw;          // [m][K][2] or null
+    float *h_out;           // [m][K][2] or null
+};
+
+static int opp_unit_check(f110_sim *h, const char *who, const OppUnit &u, int m, int slot)
+{
+    if (u.Ao < 0 || u.Ao > OPP_MAX) return fail(h, F110_ERR_INVALID, "%s: %d opponents per row are outside 0..%d", who, u.Ao, (int)OPP_MAX);
+    if (m > 0 && u.Ao > 0 && !u.h_rows) return fail(h, F110_ERR_INVALID, "%s: h_opp_rows is null", who);
+    if (u.sp.mode == OPP_TRACK && h->has_map && slot >= 0 && slot <= (int)h->extra_maps.size() && !track_has(h, slot))
+        return fail(h, F110_ERR_STATE, "%s: the opponents follow the track, but map slot %d has no track (f110_track_set)", who, slot);
+    return F110_OK;
+}
+
+// the predictions of rows [r0, r0 + count) of a rollout's or a planner's job into `table`, on `st`
+template <typename Job>
+static void opp_predict_launch(const f110_sim *h, const Job &j, const OppSpec &sp, int H, int repeat, int r0, int count, int Ao, const int32_t *agents,
+                               const double *d_rows, OppSpec *sp_out, double *table, hipStream_t st)
+{
+    if (count <= 0 || Ao <= 0) return;
+    OppJob o{};
+    o.tracks = h->d_tracks.get();
+    o.env_map = j.env_map;
+    o.unit_slot = j.unit_slot;
+    o.A = j.A;
+    o.r0 = r0;
+    o.count = count;
+    o.N = j.N;
+    o.Ao = Ao;
+    o.agents = agents;
+    o.state = j.state;
+    o.opp_rows = d_rows;
+    o.H = H;
+    o.repeat = repeat;
+    o.time_step = j.time_step;
+    o.sp_out = sp_out;
+    o.table = table;
+    o.sp = sp;
+    hipLaunchKernelGGL(k_opp_predict, grid1d((size_t)count * Ao * kTrackLanes, 256), dim3(256), 0, st, o);
+}
+
+// a unit form's side of the term: the opponent rows, the settings and the buffers into scratch memory, the predictions on the
+// handle's stream, and the lanes' view
+template <typename Job>
+static int opp_unit_prepare(f110_sim *h, Scratch &sc, const Job &j, const OppUnit &u, int K, int H, int repeat, OppLane &lane, double **dtable)
+{
+    const size_t M = (size_t)j.count;
+    double *drows = nullptr, *draw = nullptr;
+    float *dout = nullptr;
+    OppSpec *dspec = nullptr;
+    *dtable = nullptr;
+    TRY(sc.up(&u.sp, 1, &dspec));
+    if (u.Ao > 0) {
+        TRY(sc.up(u.h_rows, M * u.Ao * 4, &drows));
+        TRY(sc.up<double>(nullptr, M * u.Ao * H * 2, dtable));
+    }
+    TRY(sc.up<double>(nullptr, M * K * 2, &draw));
+    TRY(sc.up<float>(nullptr, M * K * 2, &dout));
+    opp_predict_launch(h, j, u.sp, H, repeat, 0, (int)M, u.Ao, nullptr, drows, nullptr, *dtable, h->stream);
+    lane = OppLane{*dtable, dspec, dout, draw, u.Ao, 0};
+    return F110_OK;
+}
+
+static int opp_unit_collect(f110_sim *h, Scratch &sc, const OppUnit &u, const OppLane &lane, const double *dtable, size_t M, int K, int H)
+{
+    if (u.h_pred && u.Ao > 0) TRY(sc.down(u.h_pred, dtable, M * u.Ao * H * 2));
+    if (u.h_raw) TRY(sc.down(u.h_raw, (const double *)lane.raw, M * K * 2));
+    if (u.h_out) TRY(sc.down(u.h_out, (const float *)lane.out, M * K * 2));
+    return F110_OK;
+}
+
+// f110_rollout_batch, and with `ou` f110_rollout_opp_batch
+static int roll_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start, const double *h_params, const double *h_actions,
+                      int32_t m, float *h_out, double *h_raw, float *h_traj, double *h_traj_raw, const OppUnit *ou)
+{
     RollJob j{};
     TRY(roll_check_spec(h, spec, j.sp));
     if (m < 0 || (m > 0 && (!h_start || !h_actions || !h_out))) return fail(h, F110_ERR_INVALID, "rollout: bad argument");
+    if (ou) TRY(opp_unit_check(h, "rollout", *ou, m, slot));
     if (j.sp.traj && m > 0 && !h_traj) return fail(h, F110_ERR_INVALID, "rollout: traj = 1, but h_traj is null");
     if ((size_t)m * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "rollout: %d rows x %d candidates do not fit 31 bits", m, j.sp.K);
     if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
@@ -5449,7 +5567,7 @@ int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, cons
     UnitRows rows;
     TRY(unit_rows(h, "rollout", h_start, M, rows));
     ENTER(h);
-    if (track) TRY(track_upload(h));
+    if (track || (ou && ou->sp.mode == OPP_TRACK)) TRY(track_upload(h));
     Scratch sc(h);
     double *dact = nullptr, *draw = nullptr, *dtraw = nullptr, *dend = nullptr;
     float *dout = nullptr, *dtraj = nullptr;
@@ -5469,14 +5587,87 @@ int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, cons
     j.traj = dtraj;
     j.traj_raw = dtraw;
     j.end_xy = dend;
-    roll_launch(j, track, h->stream);
+    OppLane lane{};
+    double *dtable = nullptr;
+    if (ou) TRY(opp_unit_prepare(h, sc, j, *ou, j.sp.K, j.sp.H, j.sp.repeat, lane, &dtable));
+    roll_launch(j, track, h->stream, ou ? &lane : nullptr);
     HIPCHK(h, hipGetLastError());
     TRY(sc.down(h_out, dout, cands * j.sp.D));
     if (h_raw) TRY(sc.down(h_raw, draw, cands * F110_ROLL_NCHANNELS));
     if (dtraj) TRY(sc.down(h_traj, dtraj, steps * 4));
     if (dtraw) TRY(sc.down(h_traj_raw, dtraw, steps * 4));
+    if (ou) TRY(opp_unit_collect(h, sc, *ou, lane, dtable, M, j.sp.K, j.sp.H));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
+}
+
+int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start, const double *h_params, const double *h_actions,
+                       int32_t m, float *h_out, double *h_raw, float *h_traj, double *h_traj_raw)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    return roll_batch(h, spec, slot, h_start, h_params, h_actions, m, h_out, h_raw, h_traj, h_traj_raw, nullptr);
+}
+
+int f110_rollout_opp_batch(f110_sim *h, const f110_rollout *spec, const f110_opponents *opp, int32_t slot, const double *h_start, const double *h_params,
+                           const double *h_actions, const double *h_opp_rows, int32_t Ao, int32_t m, float *h_out, double *h_raw, float *h_traj,
+                           double *h_traj_raw, double *h_pred, double *h_opp_raw, float *h_opp)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    OppUnit u{};
+    TRY(opp_check_spec(h, "rollout", opp, u.sp));
+    u.h_rows = h_opp_rows;
+    u.Ao = Ao;
+    u.h_pred = h_pred;
+    u.h_raw = h_opp_raw;
+    u.h_out = h_opp;
+    return roll_batch(h, spec, slot, h_start, h_params, h_actions, m, h_out, h_raw, h_traj, h_traj_raw, &u);
+}
+
+int f110_rollout_opp_device(f110_sim *h, const f110_rollout *spec, const f110_opponents *opp, const double *d_actions, float *d_out, float *d_traj,
+                            float *d_opp, float *h_pinned)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    RollJob j{};
+    OppSpec os;
+    TRY(roll_check_spec(h, spec, j.sp));
+    TRY(opp_check_spec(h, "rollout", opp, os));
+    if (!d_actions || !d_out || !d_opp) return fail(h, F110_ERR_INVALID, "rollout: d_actions, d_out or d_opp is null");
+    if (j.sp.traj && (!d_traj || reinterpret_cast<uintptr_t>(d_traj) % 16 != 0)) return fail(h, F110_ERR_INVALID, "rollout: traj = 1, but d_traj is null or not 16-byte aligned");
+    const size_t N = (size_t)h->N, per_agent = (size_t)j.sp.K * j.sp.D;
+    if (N * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "rollout: %zu agents x %d candidates do not fit 31 bits", N, j.sp.K);
+    if (h_pinned && !pinned_block_holds(h_pinned, N * per_agent * sizeof(float)))
+        return fail(h, F110_ERR_INVALID, "rollout: h_pinned is not [N][K][D] floats of f110_host_alloc memory");
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    const bool track = (j.sp.channels & kRollTrackBits) != 0, opp_track = os.mode == OPP_TRACK;
+    const int Ao = h->cfg.num_agents - 1;
+    if (Ao > OPP_MAX) return fail(h, F110_ERR_INVALID, "rollout: %d opponents per agent, at most %d", Ao, (int)OPP_MAX);
+    if (track) TRY(tracks_in_use(h, "rollout: PROGRESS or END_LAT is requested"));
+    if (opp_track) TRY(tracks_in_use(h, "rollout: the opponents follow the track"));
+    if (track || opp_track) TRY(tracks_current(h));
+    const size_t table = N * (size_t)Ao * j.sp.H * 2;
+    if ((track && h->d_roll_end.capacity() < 2 * N * j.sp.K) || h->d_roll_opp.capacity() < table || !h->d_roll_opp_spec) {
+        ENTER(h);
+        if (track) TRY(dgrow(h, h->d_roll_end, 2 * N * j.sp.K));
+        if (table > 0) TRY(dgrow(h, h->d_roll_opp, table));
+        TRY(dgrow(h, h->d_roll_opp_spec, (size_t)kMaxEnvBlocks));
+    }
+    EnvBlocks w;   // as f110_rollout_device; an env's cars are in one block, so a block's predictions read the block's own agents
+    TRY(env_blocks_follow(h, w));
+    TRY(job_live_source(h, "rollout", track, j));
+    j.actions = d_actions;
+    j.out = d_out;
+    j.traj = j.sp.traj ? d_traj : nullptr;
+    j.end_xy = track ? h->d_roll_end.get() : nullptr;
+    return env_blocks_output(h, w, kPinnedRollout, per_agent, d_out, h_pinned, [&](const EnvBlock &b) {
+        j.begin = b.e0 * j.A;
+        j.count = b.count * j.A;
+        // the block's own copy of the settings, written by its prediction kernel on its own stream.  Without opponents (one car per
+        // env) nothing is predicted and no lane reads the settings.
+        OppSpec *spec_b = h->d_roll_opp_spec.get() + (&b - w.begin());
+        opp_predict_launch(h, j, os, j.sp.H, j.sp.repeat, j.begin, j.count, Ao, nullptr, nullptr, spec_b, h->d_roll_opp.get(), b.stream);
+        const OppLane lane{h->d_roll_opp.get(), spec_b, d_opp, nullptr, Ao, 0};
+        roll_launch(j, track, b.stream, &lane);
+    });
 }
 
 // ---- MPPI planner (f110_mppi_*, include/f110.h) -------------------------------------------------------------------------------------
@@ -5518,9 +5709,11 @@ static int jump_ensure(f110_sim *h, DevBuf<U128> &buf, void (*build)(U128 *, U12
 }
 
 // the tracks the armed planner's projection reads (nothing to do without a track weight)
+static bool mppi_reads_tracks(const f110_sim::Mppi &p) { return mppi_needs_track(p.sp) || (p.opp_on && p.opp.mode == OPP_TRACK); }
+
 static int mppi_upload_tracks(f110_sim *h)
 {
-    if (h->mppi.m > 0 && mppi_needs_track(h->mppi.sp)) TRY(track_upload(h));
+    if (h->mppi.m > 0 && mppi_reads_tracks(h->mppi)) TRY(track_upload(h));
     return F110_OK;
 }
 
@@ -5530,17 +5723,21 @@ static int mppi_ready(f110_sim *h)
     const f110_sim::Mppi &p = h->mppi;
     if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
     if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
-    if (!mppi_needs_track(p.sp)) return F110_OK;
-    return tracks_in_use(h, "mppi: w_progress or w_lat is set", &p.agents);   // (only the envs of the armed agents)
+    if (mppi_needs_track(p.sp)) TRY(tracks_in_use(h, "mppi: w_progress or w_lat is set", &p.agents));   // (only the envs of the armed agents)
+    if (p.opp_on && p.opp.mode == OPP_TRACK) TRY(tracks_in_use(h, "mppi: the opponents follow the track", &p.agents));
+    return F110_OK;
 }
 
 // armed indices [j.i0, j.i0 + j.count): the candidates, (track) the projections, the update, one behind the other on `st`
-static void mppi_launch(const MppiJob &j, hipStream_t st)
+static void mppi_launch(const MppiJob &j, hipStream_t st, const OppLane *opp = nullptr)
 {
     if (j.count <= 0) return;
     const size_t lanes = (size_t)j.count * j.sp.K;
     const dim3 block(256);
-    if (j.sp.K % 64 == 0) hipLaunchKernelGGL((k_mppi_roll<true>), grid1d(lanes, 256), block, 0, st, j);
+    if (opp) {   // the same lanes with the opponent term's sampling and its two cost terms (the predictions are on `st` already)
+        if (j.sp.K % 64 == 0) hipLaunchKernelGGL((k_mppi_roll_opp<true>), grid1d(lanes, 256), block, 0, st, j, *opp);
+        else hipLaunchKernelGGL((k_mppi_roll_opp<false>), grid1d(lanes, 256), block, 0, st, j, *opp);
+    } else if (j.sp.K % 64 == 0) hipLaunchKernelGGL((k_mppi_roll<true>), grid1d(lanes, 256), block, 0, st, j);
     else hipLaunchKernelGGL((k_mppi_roll<false>), grid1d(lanes, 256), block, 0, st, j);
     if (j.end_xy) hipLaunchKernelGGL(k_mppi_track, grid1d(lanes * kTrackLanes, 256), block, 0, st, j);
     const int gs = mppi_group_lanes(j.sp.K, j.sp.H);
@@ -5580,7 +5777,14 @@ static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, 
     const int32_t n0 = b.e0 * A, n1 = (b.e0 + b.count) * A;
     j.i0 = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n0) - p.agents.begin());
     j.count = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n1) - p.agents.begin()) - j.i0;
-    mppi_launch(j, b.stream);
+    if (!p.opp_on) {
+        mppi_launch(j, b.stream);
+        return F110_OK;
+    }
+    // the opponent term: the block's armed agents' predictions from the live columns first (an env's cars are in one block)
+    opp_predict_launch(h, j, p.opp, p.sp.H, p.sp.repeat, j.i0, j.count, A - 1, p.d_agents.get(), nullptr, nullptr, p.d_opp_table.get(), b.stream);
+    const OppLane lane{p.d_opp_table.get(), p.d_opp_spec.get(), nullptr, nullptr, A - 1, 0};
+    mppi_launch(j, b.stream, &lane);
     return F110_OK;
 }
 
@@ -5632,7 +5836,7 @@ int f110_mppi_device(f110_sim *h, double *d_actions, float *d_info)
 {
     if (!h || !d_actions) return fail(h, F110_ERR_INVALID, "mppi: null argument");
     TRY(mppi_ready(h));
-    if (mppi_needs_track(h->mppi.sp)) TRY(tracks_current(h));
+    if (mppi_reads_tracks(h->mppi)) TRY(tracks_current(h));
     EnvBlocks w;   // behind a two-block step: each block's armed agents on the block's own stream (an agent reads and writes its own rows)
     TRY(env_blocks_follow(h, w));
     for (const EnvBlock &b : w) TRY(mppi_launch_armed(h, b, d_actions, d_info));
@@ -5679,13 +5883,15 @@ int f110_mppi_put(f110_sim *h, const double *h_nominal, const uint64_t *h_stream
     return F110_OK;
 }
 
-int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const double *h_start, const double *h_params, const int32_t *h_fresh, int32_t m,
-                    double *h_nominal, uint64_t *h_streams, double *h_actions, float *h_info, double *h_cand, double *h_cost, double *h_weight)
+// f110_mppi_batch, and with `ou` f110_mppi_opp_batch
+static int mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const double *h_start, const double *h_params, const int32_t *h_fresh, int32_t m,
+                      double *h_nominal, uint64_t *h_streams, double *h_actions, float *h_info, double *h_cand, double *h_cost, double *h_weight,
+                      const OppUnit *ou)
 {
-    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     MppiJob j{};
     TRY(mppi_check_spec(h, spec, j.sp));
     if (m < 0 || (m > 0 && (!h_start || !h_nominal || !h_streams))) return fail(h, F110_ERR_INVALID, "mppi: bad argument");
+    if (ou) TRY(opp_unit_check(h, "mppi", *ou, m, slot));
     if ((size_t)m * j.sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "mppi: %d rows x %d candidates do not fit 31 bits", m, j.sp.K);
     if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
     TRY(unit_slot_check(h, "mppi", slot));
@@ -5698,7 +5904,7 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
     TRY(unit_rows(h, "mppi", h_start, M, rows));
     ENTER(h);
     TRY(jump_ensure(h, h->d_mppi_jump, mppi_jump_table, kMppiJumps));
-    if (track) TRY(track_upload(h));
+    if (track || (ou && ou->sp.mode == OPP_TRACK)) TRY(track_upload(h));
     Scratch sc(h);
     double *dnom = nullptr, *dV = nullptr, *dcost = nullptr, *dend = nullptr, *dw = nullptr, *dact = nullptr;
     int32_t *dfresh = nullptr;
@@ -5727,7 +5933,10 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
     j.actions = dact;
     j.info = dinfo;
     j.sp_dev = dspec;
-    mppi_launch(j, h->stream);
+    OppLane lane{};
+    double *dtable = nullptr;
+    if (ou) TRY(opp_unit_prepare(h, sc, j, *ou, j.sp.K, j.sp.H, j.sp.repeat, lane, &dtable));
+    mppi_launch(j, h->stream, ou ? &lane : nullptr);
     HIPCHK(h, hipGetLastError());
     TRY(sc.down(h_nominal, dnom, M * seq));
     TRY(sc.down(h_streams, dstr, 4 * M));
@@ -5736,7 +5945,64 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
     if (h_cand) TRY(sc.down(h_cand, dV, cands * seq));
     if (h_cost) TRY(sc.down(h_cost, dcost, cands));
     if (h_weight) TRY(sc.down(h_weight, dw, cands));
+    if (ou) TRY(opp_unit_collect(h, sc, *ou, lane, dtable, M, j.sp.K, j.sp.H));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const double *h_start, const double *h_params, const int32_t *h_fresh, int32_t m,
+                    double *h_nominal, uint64_t *h_streams, double *h_actions, float *h_info, double *h_cand, double *h_cost, double *h_weight)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    return mppi_batch(h, spec, slot, h_start, h_params, h_fresh, m, h_nominal, h_streams, h_actions, h_info, h_cand, h_cost, h_weight, nullptr);
+}
+
+int f110_mppi_opp_batch(f110_sim *h, const f110_mppi *spec, const f110_opponents *opp, double w_hit, double w_near, double near_ref, int32_t slot,
+                        const double *h_start, const double *h_params, const int32_t *h_fresh, const double *h_opp_rows, int32_t Ao, int32_t m,
+                        double *h_nominal, uint64_t *h_streams, double *h_actions, float *h_info, double *h_cand, double *h_cost, double *h_weight,
+                        double *h_opp_raw)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    OppUnit u{};
+    TRY(opp_check_spec(h, "mppi", opp, u.sp));
+    TRY(opp_check_weights(h, w_hit, w_near, near_ref, u.sp));
+    u.h_rows = h_opp_rows;
+    u.Ao = Ao;
+    u.h_raw = h_opp_raw;
+    return mppi_batch(h, spec, slot, h_start, h_params, h_fresh, m, h_nominal, h_streams, h_actions, h_info, h_cand, h_cost, h_weight, &u);
+}
+
+int f110_mppi_set_opponents(f110_sim *h, const f110_opponents *opp, double w_hit, double w_near, double near_ref)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    f110_sim::Mppi &p = h->mppi;
+    if (!opp) {   // detach (nothing to do while nothing is attached)
+        if (!p.opp_on) return F110_OK;
+        ENTER(h);
+        p.opp_on = false;
+        p.opp = OppSpec{};
+        p.d_opp_spec.reset();    // (hipFree waits for the calls in flight that read them)
+        p.d_opp_table.reset();
+        return F110_OK;
+    }
+    OppSpec os;
+    TRY(opp_check_spec(h, "mppi", opp, os));
+    TRY(opp_check_weights(h, w_hit, w_near, near_ref, os));
+    const int Ao = h->cfg.num_agents - 1;
+    if (Ao > OPP_MAX) return fail(h, F110_ERR_INVALID, "mppi: %d opponents per agent, at most %d", Ao, (int)OPP_MAX);
+    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
+    if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
+    if (os.mode == OPP_TRACK) TRY(tracks_in_use(h, "mppi: the opponents follow the track", &p.agents));
+    ENTER(h);
+    DevBuf<OppSpec> dspec;   // built aside: a failure leaves what is attached (if anything) as it is
+    DevBuf<double> dtable;
+    TRY(dmalloc(h, &dspec, 1));
+    if (Ao > 0) TRY(dmalloc(h, &dtable, (size_t)p.m * Ao * p.sp.H * 2));
+    HIPCHK(h, hipMemcpy(dspec, &os, sizeof os, hipMemcpyHostToDevice));
+    p.d_opp_spec = std::move(dspec);
+    p.d_opp_table = std::move(dtable);
+    p.opp = os;
+    p.opp_on = true;
     return F110_OK;
 }
 

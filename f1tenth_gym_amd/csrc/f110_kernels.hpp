@@ -4803,6 +4803,117 @@ struct RollEmitLds {
     }
 };
 
+// ---- opponents (f110_rollout_opp_*, f110_mppi_set_opponents; f110_math.hpp opp_* the arithmetic) -------------------------
+// k_opp_predict: 16 lanes per (row, opponent), row = an agent of the rollout or an armed index of the planner.  The group reads the
+// opponent (the live columns of the env's other agent in ascending slot, or the unit form's uploaded row), TRACK: projects it with
+// roll_search16 (every lane takes part; idle groups shadow the last one), then lane `sub` writes the predictions of the actions
+// h = sub, sub + 16, ... into the table [row][Ao][H][2].  The OPP lanes of the two rollout kernels read the agent's rows back once
+// per action: Ao * 16 bytes, wave-uniform when K % 64 == 0.  A lane carries only the minimum and the first hit across the step
+// loop; the radius is read from device memory at every sample and the weights behind the loop (see sp_dev in k_mppi_roll).
+__device__ __forceinline__ void roll_search16(const TrackDesc &td, double px, double py, int hint, int sub, int &best, double &s, double &lat);   // (below)
+
+struct OppJob {
+    const TrackDesc *tracks;
+    const int32_t *env_map;
+    int32_t unit_slot, A;
+    int32_t r0, count, N, Ao;   // rows [r0, r0 + count); columns of N entries; opponents per row
+    const int32_t *agents;      // [.] row -> agent, or nullptr: row r is agent r
+    const double *state;        // [7][N]
+    const double *opp_rows;     // [.][Ao][4] (x, y, v, theta) per row, or nullptr: the live columns
+    int32_t H, repeat;
+    double time_step;
+    OppSpec *sp_out;            // or nullptr: where the first lane leaves sp for the lanes that sample
+    double *table;              // [.][Ao][H][2]
+    OppSpec sp;
+};
+
+__global__ void __launch_bounds__(256) k_opp_predict(OppJob j)
+{
+    const long long total = (long long)j.count * j.Ao;
+    const long long gid = ((long long)blockIdx.x * 256 + (int)threadIdx.x) / kTrackLanes;
+    const int sub = (int)threadIdx.x & (kTrackLanes - 1);
+    const bool live = gid < total;
+    const long long g = live ? gid : total - 1;
+    if (j.sp_out && blockIdx.x == 0 && threadIdx.x == 0) *j.sp_out = j.sp;
+    const int r = j.r0 + (int)(g / j.Ao), o = (int)(g % j.Ao);
+    const int n = j.agents ? j.agents[r] : r;
+    const size_t N = (size_t)j.N;
+    double ov[4];
+    if (j.opp_rows) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ov[q] = j.opp_rows[((size_t)r * j.Ao + o) * 4 + q];
+    } else {
+        const int a = n % j.A, nb = n - a + (o < a ? o : o + 1);
+        ov[0] = j.state[nb];
+        ov[1] = j.state[N + nb];
+        ov[2] = j.state[3 * N + nb];
+        ov[3] = j.state[4 * N + nb];
+    }
+    const bool seen = opp_in_range(j.state[n], j.state[N + n], ov[0], ov[1], j.sp.max_range);
+    double a = 0.0, b = 0.0;   // CV: cos, sin; TRACK: s_o, lat_o
+    PreviewTrack tr{};
+    if (j.sp.mode == OPP_TRACK) {
+        const TrackDesc td = j.tracks[j.unit_slot >= 0 ? j.unit_slot : (j.env_map ? j.env_map[n / j.A] : 0)];
+        int seg;
+        roll_search16(td, ov[0], ov[1], -1, sub, seg, a, b);
+        tr = PreviewTrack{td.cols, nullptr, td.nseg, td.closed, 0, 0, td.L};
+    } else if (seen) {
+        cos_sin(ov[3], a, b);
+    }
+    if (!live) return;
+    double *p = j.table + ((size_t)r * j.Ao + o) * j.H * 2;
+    for (int h = sub; h < j.H; h += kTrackLanes) {
+        const double tau = opp_tau(h, j.repeat, j.time_step);
+        if (!seen) p[2 * h] = p[2 * h + 1] = NAN;
+        else if (j.sp.mode == OPP_CV) opp_predict_cv(ov[0], ov[1], ov[2], a, b, tau, p + 2 * h);
+        else opp_predict_track(tr, a, b, ov[2], tau, p + 2 * h);
+    }
+}
+
+// what a lane of k_rollout_opp / k_mppi_roll_opp reads and leaves
+struct OppLane {
+    const double *table;     // k_opp_predict's [.][Ao][H][2]: the row of agent n (rollout) or of armed index i (planner)
+    const OppSpec *sp_dev;   // the settings in device memory
+    float *out;              // [.][K][2] ((float)OPP_MIN, (float)OPP_FREE) per candidate, or nullptr
+    double *raw;             // [.][K][2] the same before the conversion, or nullptr
+    int32_t Ao, pad_;
+};
+
+// roll_candidate's xy hook: the candidate's position behind action h against its agent's rows
+struct OppEmit {
+    const double *rows;
+    const OppSpec *sp;
+    int Ao, H;
+    mutable double m;
+    mutable int free;
+    __device__ __forceinline__ void xy(int h, double x, double y) const { opp_sample(rows, Ao, H, h, x, y, *sp, m, free); }
+};
+
+__device__ __forceinline__ OppEmit opp_emit(const OppLane &o, size_t row, int H)
+{
+    return OppEmit{o.table + row * o.Ao * H * 2, o.sp_dev, o.Ao, H, INFINITY, H};
+}
+
+__device__ __forceinline__ void opp_store(const OppLane &o, size_t G, double m, int free)
+{
+    if (o.out) {
+        o.out[2 * G] = (float)m;
+        o.out[2 * G + 1] = (float)free;
+    }
+    if (o.raw) {
+        o.raw[2 * G] = m;
+        o.raw[2 * G + 1] = (double)free;
+    }
+}
+
+// an emit of the rollout with the opponent term's hook beside it
+template <class Base>
+struct RollEmitWithOpp : Base {
+    static constexpr bool kXY = true;
+    OppEmit opp;
+    __device__ __forceinline__ void xy(int h, double x, double y) const { opp.xy(h, x, y); }
+};
+
 template <bool UNI, bool TRAJ>
 __global__ void __launch_bounds__(256) k_rollout(RollJob j)
 {
@@ -4849,6 +4960,72 @@ __global__ void __launch_bounds__(256) k_rollout(RollJob j)
         fr = roll_frame(j.sp.frame, j.state[n], j.state[N + n], j.state[4 * N + n]);
     }
     if (!live) return;
+    double v[ROLL_NCHANNELS];
+    const int32_t all = (1 << ROLL_NCHANNELS) - 1;
+    roll_values(fr, car, alive, min_clear, j.raw ? all : j.sp.channels, v);
+    roll_store(j.sp, v, all & ~kRollTrackBits, j.out + G * j.sp.D, j.raw ? j.raw + G * ROLL_NCHANNELS : nullptr);
+    if (j.end_xy) {
+        j.end_xy[2 * G] = car.st[0];
+        j.end_xy[2 * G + 1] = car.st[1];
+    }
+}
+
+// k_rollout with the opponent term: the same lane with roll_candidate's xy hook sampling the agent's rows of k_opp_predict's table,
+// and d_opp written beside the summary.  A kernel of its own beside k_rollout, not a third template parameter of it: routing
+// k_rollout's lane through a shared function moved its register allocation (its SGPR spill counts), and the existing instantiations
+// stay exactly what they were.
+template <bool UNI, bool TRAJ>
+__global__ void __launch_bounds__(256) k_rollout_opp(RollJob j, OppLane o)
+{
+    __shared__ float4 s_stage[TRAJ ? 256 * kRollPitch : 1];
+    const int K = j.sp.K, H = j.sp.H;
+    const long long total = (long long)j.count * K;
+    const long long g0 = (long long)blockIdx.x * 256, g_lane = g0 + (int)threadIdx.x;
+    const bool live = g_lane < total;
+    const long long g = live ? g_lane : total - 1;
+    int a = (int)(g / K);
+    const int kk = (int)(g - (long long)a * K);
+    if (UNI) a = __builtin_amdgcn_readfirstlane(a);
+    const int n = j.begin + a;
+    const size_t N = (size_t)j.N;
+    const size_t G = (size_t)j.begin * K + (size_t)g;
+    const VehicleParams vp = load_params(j.params + (size_t)(j.params_per_agent ? n : n % j.A) * NPARAMS);
+    RollCar car;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) car.st[c] = j.state[(size_t)c * N + n];
+    car.b0 = j.steer_buf[n];
+    car.b1 = j.steer_buf[N + n];
+    car.cnt = j.buf_cnt[n];
+    const ScanConst &k = j.maps[j.env_map ? j.env_map[n / j.A] : 0];
+    const double *act = j.actions + (j.sp.layout == ROLL_PER_AGENT ? G : (size_t)kk) * H * 2;
+    int alive;
+    double min_clear, opp_m;
+    int opp_free;
+    RollFrame fr;
+    if constexpr (TRAJ) {
+        fr = roll_frame(j.sp.frame, car.st[0], car.st[1], car.st[4]);
+        RollEmitWithOpp<RollEmitLds> emit;
+        emit.opp = opp_emit(o, (size_t)n, H);
+        emit.stage = s_stage;
+        emit.traj = j.traj ? reinterpret_cast<float4 *>(j.traj) + ((size_t)j.begin * K + (size_t)g0) * H : nullptr;
+        emit.raw_row = j.traj_raw && live ? j.traj_raw + G * H * 4 : nullptr;
+        emit.rows = (int)(total - g0 < 256 ? total - g0 : 256);
+        emit.H = H;
+        emit.sx = j.sp.scale[ROLL_END_X];
+        emit.sy = j.sp.scale[ROLL_END_Y];
+        emit.sc = j.sp.scale[ROLL_END_COS];
+        emit.ss = j.sp.scale[ROLL_END_SIN];
+        roll_candidate(j.sp, k, vp, j.time_step, j.integrator, j.lidar_dist, car, act, fr, alive, min_clear, emit);
+        opp_m = emit.opp.m, opp_free = emit.opp.free;
+    } else {
+        RollEmitWithOpp<RollEmitNone> emit;
+        emit.opp = opp_emit(o, (size_t)n, H);
+        roll_candidate(j.sp, k, vp, j.time_step, j.integrator, j.lidar_dist, car, act, fr, alive, min_clear, emit);
+        opp_m = emit.opp.m, opp_free = emit.opp.free;
+        fr = roll_frame(j.sp.frame, j.state[n], j.state[N + n], j.state[4 * N + n]);
+    }
+    if (!live) return;
+    opp_store(o, G, opp_m, opp_free);
     double v[ROLL_NCHANNELS];
     const int32_t all = (1 << ROLL_NCHANNELS) - 1;
     roll_values(fr, car, alive, min_clear, j.raw ? all : j.sp.channels, v);
@@ -4968,8 +5145,9 @@ struct MppiJob {
     MppiSpec sp;
 };
 
-template <bool UNI>
-__global__ void __launch_bounds__(256) k_mppi_roll(MppiJob j)
+// a lane of k_mppi_roll (OPP false: `o` is not read) and of k_mppi_roll_opp
+template <bool UNI, bool OPP>
+__device__ __forceinline__ void mppi_roll_lane(const MppiJob &j, const OppLane &o)
 {
     const int K = j.sp.K, H = j.sp.H;
     const long long total = (long long)j.count * K;
@@ -5000,18 +5178,50 @@ __global__ void __launch_bounds__(256) k_mppi_roll(MppiJob j)
     int alive;
     double min_clear;
     RollFrame fr;
-    roll_candidate(rs, k, vp, j.time_step, j.integrator, j.lidar_dist, car, row, fr, alive, min_clear, RollEmitNone());
+    [[maybe_unused]] double opp_m;
+    [[maybe_unused]] int opp_free;
+    if constexpr (OPP) {
+        RollEmitWithOpp<RollEmitNone> emit;
+        emit.opp = opp_emit(o, (size_t)i, H);
+        roll_candidate(rs, k, vp, j.time_step, j.integrator, j.lidar_dist, car, row, fr, alive, min_clear, emit);
+        opp_m = emit.opp.m, opp_free = emit.opp.free;
+    } else {
+        roll_candidate(rs, k, vp, j.time_step, j.integrator, j.lidar_dist, car, row, fr, alive, min_clear, RollEmitNone());
+    }
     // The cost's settings come from the spec's copy in device memory, NOT from j.sp: read from the kernel's arguments they are
     // loaded at entry and held in SGPRs across the step loop, and the spill slots of that gave <UNI = false> a private segment of
     // 20 bytes (§6i rules scratch out).  Keep every use of the spec behind the loop on `sp`.
     const MppiSpec &sp = *j.sp_dev;
-    if (j.end_xy) {
+    if constexpr (OPP) {
+        // the opponent terms go between the map's and the track's, their weights read here from device memory for the same reason
+        const double c = mppi_cost_opp(*o.sp_dev, mppi_cost_map(sp, alive, min_clear), sp.H, opp_free, opp_m);
+        opp_store(o, G, opp_m, opp_free);
+        if (j.end_xy) {
+            j.cost[G] = c;
+            j.end_xy[2 * G] = car.st[0];
+            j.end_xy[2 * G + 1] = car.st[1];
+        } else {
+            j.cost[G] = mppi_cost_track(sp, c, 0.0, 0.0);
+        }
+    } else if (j.end_xy) {
         j.cost[G] = mppi_cost_map(sp, alive, min_clear);
         j.end_xy[2 * G] = car.st[0];
         j.end_xy[2 * G + 1] = car.st[1];
     } else {
         j.cost[G] = mppi_cost(sp, alive, min_clear, 0.0, 0.0);
     }
+}
+
+template <bool UNI>
+__global__ void __launch_bounds__(256) k_mppi_roll(MppiJob j)
+{
+    mppi_roll_lane<UNI, false>(j, OppLane{});
+}
+
+template <bool UNI>
+__global__ void __launch_bounds__(256) k_mppi_roll_opp(MppiJob j, OppLane o)
+{
+    mppi_roll_lane<UNI, true>(j, o);
 }
 
 __global__ void __launch_bounds__(256) k_mppi_track(MppiJob j)

@@ -1772,10 +1772,20 @@ F110_HD float roll_scaled(double v, double scale) { return (float)(v / scale); }
 // oob_value as every position outside the table does) kills the candidate: its state stays as that step left it.  The two loops are
 // not unrolled: advance_vehicle is ~1900 dependent instructions and appears once.  With Emit::kOn, emit(h, v) receives the pose
 // after action h's last repeat in the frame `fr` (read only then); every lane of a workgroup reaches every emit (a dead candidate
-// repeats its pose).
+// repeats its pose).  An Emit that declares kXY = true also has emit.xy(h, x, y), which receives the same instant's MAP-frame
+// position behind it, whatever `fr` is (the opponent term).
 struct RollEmitNone {
     static constexpr bool kOn = false;
     F110_HD void operator()(int, const double *) const {}
+};
+
+template <class Emit, class = void>
+struct RollEmitXY {
+    static constexpr bool value = false;
+};
+template <class Emit>
+struct RollEmitXY<Emit, decltype((void)Emit::kXY)> {
+    static constexpr bool value = Emit::kXY;
 };
 
 template <class Emit>
@@ -1804,6 +1814,7 @@ F110_HD void roll_candidate(const RollSpec &sp, const ScanConst &k, const Vehicl
             roll_pose(fr, car.st[0], car.st[1], car.st[4], true, v);
             emit(h, v);
         }
+        if constexpr (RollEmitXY<Emit>::value) emit.xy(h, car.st[0], car.st[1]);
     }
 }
 
@@ -2062,6 +2073,94 @@ F110_HD void mppi_info(double beta, double c0, double eta, double q, int best, f
     o[1] = (float)c0;
     o[2] = (float)(eta * eta / q);
     o[3] = (float)best;
+}
+
+// ------------------------------------------------------------------ opponents (include/f110.h, f110_opponents)
+// The other cars of an agent's env predicted over the horizon, and a candidate's distance to the predictions.  No reference
+// counterpart.  Float64 adds, multiplies, divides, compares and one sqrt per sample; one cos_sin per CV opponent.  One text for the
+// kernels (k_opp_predict, the OPP lanes of k_rollout_opp / k_mppi_roll_opp) and the host harness (tests/host_harness/opp_harness.hip).
+enum { OPP_CV = 0, OPP_TRACK = 1 };
+enum { OPP_MAX = 31 };
+
+// struct f110_opponents, then the planner's two weights and reference (0.0 where only the rollout asks)
+struct OppSpec {
+    int32_t mode, pad_;
+    double radius, max_range;
+    double w_hit, w_near, near_ref;
+};
+
+// the instant of the pose behind action h's last repeat
+F110_HD double opp_tau(int h, int repeat, double dt) { return (double)((h + 1) * repeat) * dt; }
+
+// is the opponent at (ox, oy) looked at by the agent that starts at (x, y)?  Written so that a NaN is not.
+F110_HD bool opp_in_range(double x, double y, double ox, double oy, double max_range)
+{
+    const double dx = ox - x, dy = oy - y;
+    return dx * dx + dy * dy <= max_range * max_range;
+}
+
+// constant velocity along the heading (c, s) = cos_sin(theta_o), taken once per opponent
+F110_HD void opp_predict_cv(double ox, double oy, double v, double c, double s, double tau, double *p)
+{
+    const double d = v * tau;
+    p[0] = ox + d * c;
+    p[1] = oy + d * s;
+}
+
+// along the raceline from the projection (s_o, lat_o), the lateral offset kept: the preview's station at s_o + v * tau
+F110_HD void opp_predict_track(const PreviewTrack &tr, double s_o, double lat_o, double v, double tau, double *p)
+{
+    double s = s_o + v * tau;
+    if (tr.closed) {
+        if (s >= tr.L) s = s - tr.L;
+        else if (s < 0.0) s = s + tr.L;
+    }
+    const int k = preview_segment(tr.cols + 6 * (size_t)tr.nseg, tr.nseg, s);
+    double w[PREVIEW_NCHANNELS];
+    preview_station(tr, k, s, PREVIEW_FRAME_WORLD, 0.0, 0.0, 1.0, 0.0, w);
+    p[0] = w[0] - lat_o * w[3];
+    p[1] = w[1] + lat_o * w[2];
+}
+
+// one opponent's whole row p[H][2] serially (the kernel gives an opponent 16 lanes; this is what the unit harness runs).  `cols`
+// [7][nseg] (TRACK only).  An opponent out of range: NaN.
+F110_HD void opp_predict_row(const OppSpec &sp, const double *cols, int nseg, int closed, double L, double x, double y, const double *o, int H,
+                             int repeat, double dt, double *p)
+{
+    const bool seen = opp_in_range(x, y, o[0], o[1], sp.max_range);
+    double a = 0.0, b = 0.0;   // CV: cos, sin; TRACK: s_o, lat_o
+    if (seen && sp.mode == OPP_CV) cos_sin(o[3], a, b);
+    if (seen && sp.mode == OPP_TRACK) roll_project(cols, nseg, o[0], o[1], a, b);
+    const PreviewTrack tr{cols, nullptr, nseg, closed, 0, 0, L};
+    for (int h = 0; h < H; ++h) {
+        const double tau = opp_tau(h, repeat, dt);
+        if (!seen) p[2 * h] = p[2 * h + 1] = NAN;
+        else if (sp.mode == OPP_CV) opp_predict_cv(o[0], o[1], o[2], a, b, tau, p + 2 * h);
+        else opp_predict_track(tr, a, b, o[2], tau, p + 2 * h);
+    }
+}
+
+// the candidate's position behind action h against the agent's rows [Ao][H][2]: the running minimum m (from +inf) and the first
+// action with a sample inside the radius, `free` (from H: no hit yet).  A NaN distance does neither.  The radius is read from `sp`
+// at the sample (on the device: from memory, so that it is not held in a register across the step loop).
+F110_HD void opp_sample(const double *rows, int Ao, int H, int h, double x, double y, const OppSpec &sp, double &m, int &free)
+{
+#pragma unroll 1
+    for (int o = 0; o < Ao; ++o) {
+        const double *p = rows + ((size_t)o * H + h) * 2;
+        const double dx = x - p[0], dy = y - p[1];
+        const double d = sqrt(dx * dx + dy * dy);
+        if (d < m) m = d;
+        if (free == H && d < sp.radius) free = h;
+    }
+}
+
+// the planner's two opponent terms, between the map's and the track's
+F110_HD double mppi_cost_opp(const OppSpec &o, double c, int H, int free, double m)
+{
+    c = c + o.w_hit * (double)(H - free);
+    c = c + o.w_near * (m < o.near_ref ? o.near_ref - m : 0.0);
+    return c;
 }
 
 // ------------------------------------------------------------------ particle filter (include/f110.h, f110_pf)

@@ -18,6 +18,7 @@ from . import _ffi
 from .core import DEFAULT_PARAMS
 from .gap_follower import coerce_scripted
 from .mppi import split_scripted
+from .opponents import split_mppi_opponents
 from .particle_filter import split_filter
 from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
@@ -394,6 +395,10 @@ class F110VecEnv(object):
     live state, behind the controllers, with the stream PCG64(SeedSequence(seed, spawn_key=(global agent index,))) of the env's
     `seed`.  `planner=(slot, Mppi)` says the same next to the (assign, [controllers]) form.  The planner's nominal sequences and
     stream positions are not part of snapshot() / restore(): keep env.sim.batch.get_mppi_state() next to a snapshot.
+    `mppi_opponents=dict(opponents=Opponents | dict, w_hit=..., w_near=..., near_ref=...)` lets that planner see the
+    other cars of its env: each is predicted over the horizon from its live state and every candidate pays for coming within the
+    radius of a prediction (w_hit per action from there on) and for its smallest distance below near_ref (w_near per metre).  It
+    holds no state.
 
     Track preview (no reference counterpart): `track_preview=` (a TrackPreview or a dict of its settings) adds
     obs['track_preview'], float32 [E][A][P][D]: P stations of the raceline ahead of each car, in its own frame or the map's,
@@ -426,7 +431,7 @@ class F110VecEnv(object):
 
     def __init__(self, num_envs, auto_reset=False, device_logic=False, obs_fields=None, copy_obs=False,
                  episode_fields=None, mapped_actions=True, spin_wait=False, fuse_host_block=True, poll_wait=True, obs_encoder=None, scripted=None,
-                 track_preview=None, neighbors=None, particle_filter=None, **kwargs):
+                 track_preview=None, neighbors=None, particle_filter=None, mppi_opponents=None, **kwargs):
         self.num_envs = int(num_envs)
         self.seed = kwargs.get('seed', 12345)
         self.map_name, self.map_path = _resolve_map_path(kwargs)
@@ -475,6 +480,12 @@ class F110VecEnv(object):
             if mp.needs_track and not tracks:
                 raise ValueError("the planner's w_progress and w_lat need a track (track= or tracks=)")
             self.planner = (slot, mp)
+        self.mppi_opponents = split_mppi_opponents(mppi_opponents)   # (Opponents, w_hit, w_near, near_ref): the planner sees the env's other cars
+        if self.mppi_opponents is not None:
+            if self.planner is None:
+                raise ValueError("mppi_opponents= needs a planner (scripted={slot: Mppi(...)})")
+            if self.mppi_opponents[0].needs_track and not tracks:
+                raise ValueError("mppi_opponents in 'track' mode needs a track (track= or tracks=)")
         self.track_preview = None
         if track_preview is not None:
             self.track_preview = TrackPreview.coerce(track_preview)
@@ -556,6 +567,8 @@ class F110VecEnv(object):
             if self.planner is not None:   # agent_base: this handle's first global agent (ShardedVecEnv), so a sharded run draws the same numbers
                 b.set_mppi(self.planner[1], np.arange(self.num_envs) * self.num_agents + self.planner[0], seed=self.seed,
                            agent_base=int(kwargs.get('env_base', 0)) * self.num_agents)
+                if self.mppi_opponents is not None:
+                    b.set_mppi_opponents(*self.mppi_opponents)
             if self.particle_filter is not None:   # likewise the filter's streams
                 b.set_particle_filter(self.particle_filter[1], np.arange(self.num_envs) * self.num_agents + self.particle_filter[0], seed=self.seed,
                                       agent_base=int(kwargs.get('env_base', 0)) * self.num_agents)

@@ -110,6 +110,10 @@ class ShardedVecEnv(object):
         self.planner = planner
         if planner is not None:
             kwargs['planner'] = planner
+        if kwargs.get('mppi_opponents') is not None:   # the planner's opponent term: validated once, the same for every shard (it holds no state)
+            from .opponents import split_mppi_opponents
+            op, w_hit, w_near, near_ref = split_mppi_opponents(kwargs['mppi_opponents'])
+            kwargs['mppi_opponents'] = dict(opponents=op, w_hit=w_hit, w_near=w_near, near_ref=near_ref)
         if scripted is not None:
             from .gap_follower import coerce_scripted
             scripted = coerce_scripted(scripted, E, self.num_agents)

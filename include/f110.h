@@ -990,9 +990,10 @@ int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, dou
  * of a set bit (with traj: of bits 0..3 too) that is not finite and > 0, a NaN margin, a null d_actions or d_out, traj = 1 with a
  * null d_traj, an h_pinned that is not [N][K][D] floats of f110_host_alloc memory.
  * Refused with F110_ERR_STATE: no map, PROGRESS or END_LAT while a map slot in use has no track.
- * Not offered: float32 action input, footprint-corner clearance, opponents, feeding the result into the observation encoder, a
+ * Not offered: float32 action input, footprint-corner clearance, feeding the result into the observation encoder, a
  * keyword on the env layers (a rollout is a function of the caller's candidates, not an observation).  A built-in cost and update
- * on top of it is the MPPI planner below (f110_mppi_*). */
+ * on top of it is the MPPI planner below (f110_mppi_*); the other cars' predicted motion is the opponent term below that
+ * (f110_opponents, f110_rollout_opp_*). */
 enum { F110_ROLL_END_X = 1, F110_ROLL_END_Y = 2, F110_ROLL_END_COS = 4, F110_ROLL_END_SIN = 8, F110_ROLL_END_V = 16,
        F110_ROLL_END_YAW_RATE = 32, F110_ROLL_ALIVE = 64, F110_ROLL_MIN_CLEAR = 128, F110_ROLL_PROGRESS = 256, F110_ROLL_END_LAT = 512,
        F110_ROLL_NCHANNELS = 10 };
@@ -1062,9 +1063,9 @@ int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, cons
  *   0 or 1, a NaN margin, any other setting not finite, a sigma < 0, steer_min > steer_max, speed_min > speed_max, lambda <= 0, a
  *   weight < 0, v_init outside [speed_min, speed_max]; a list that is not strictly ascending or has an index outside 0 .. N - 1; an
  *   armed agent with a follow-the-gap assignment (and f110_controllers_set on an armed agent); M * K >= 2^31.
- * Not offered: several specs per handle, opponents, the iTTC check or the footprint in the prediction (the rollout's own limits),
+ * Not offered: several specs per handle, the iTTC check or the footprint in the prediction (the rollout's own limits),
  * a control-effort term, a covariance or a temporal correlation of the noise, float32 candidates, the planner inside the state
- * blobs. */
+ * blobs.  The other cars enter the cost through the opponent term (f110_mppi_set_opponents, below). */
 enum { F110_MPPI_MAX_K = 256, F110_MPPI_MAX_H = 64, F110_MPPI_MAX_REPEAT = 16 };
 typedef struct f110_mppi {
     int32_t k;          /* K, 1..256 candidates per agent (candidate 0 is the nominal itself) */
@@ -1100,6 +1101,81 @@ int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const doub
                     const double *h_params /* [m][18] or NULL */, const int32_t *h_fresh /* [m] or NULL */, int32_t m,
                     double *h_nominal /* [m][H][2] */, uint64_t *h_streams /* [m][4] */, double *h_actions /* [m][2] */,
                     float *h_info /* [m][4] */, double *h_cand /* [m][K][H][2] */, double *h_cost /* [m][K] */, double *h_weight /* [m][K] */);
+
+/* ---- opponents: the other cars of an agent's env predicted over the horizon, for the rollout and the MPPI planner (no reference
+ * counterpart: what lets a sampling planner see the car in front) ----
+ * The rollout and the planner above fly free against the map.  With these settings every candidate is also measured against where
+ * the other cars of its env will be.  Everything is float64, nothing is contracted, operations run in the order written.
+ * Opponents.  For agent n = e * A + a they are the other agents of env e, in ascending slot b != a: A - 1 of them (none with
+ *   A = 1; A - 1 <= 31).  Opponent o is read from the LIVE columns at the call: x_o, y_o = state[0..1], v_o = state[3],
+ *   theta_o = state[4].  With dx = x_o - x, dy = y_o - y from the agent's own start position, opponent o is ignored for the whole
+ *   call if !(dx * dx + dy * dy <= max_range * max_range) (so a NaN ignores it); an ignored opponent's predictions are NaN.
+ * Sample times.  tau_h = (double)((h + 1) * repeat) * time_step for h = 0 .. H - 1: the instant of the pose after action h's last
+ *   repeat (the pose d_traj holds).
+ * Prediction p_o(h), once per call:
+ *   CV     (c, s) = cos, sin of theta_o, taken once.  d = v_o * tau_h;  p = (x_o + d * c, y_o + d * s).
+ *   TRACK  the opponent keeps its lateral offset and runs along the raceline.  (x_o, y_o) is projected on its env's track by the
+ *          rollout's rule (the first-minimum search of PROGRESS) -> (s_o, lat_o).  s = s_o + v_o * tau_h; on a closed track of
+ *          length L wrapped once: if (s >= L) s = s - L; else if (s < 0.0) s = s + L.  An open track does not wrap (the segment
+ *          parameter's clip holds s on the end segments).  k = the preview's segment of s (the last segment with cum[k] <= s, 0
+ *          when none), (X, Y) and the unit tangent (ux, uy) the preview's station there in the MAP frame:
+ *          t = clip((s - cum[k]) / len[k], 0, 1), X = ax + t * dx, Y = ay + t * dy, ux = dx / len, uy = dy / len.
+ *          p = (X - lat_o * uy, Y + lat_o * ux).  This mode needs a track (f110_track_set) on every map slot in use (the planner: on
+ *          the slots of the armed agents); tracking need not be enabled.
+ * Per candidate.  The candidate's position is its MAP-frame state[0..1] after action h's last repeat, whatever the spec's frame; a
+ *   candidate the map has killed repeats its frozen pose.  m = +inf, free = H, hit = false; for h ascending and o ascending:
+ *     dx = x - p.x, dy = y - p.y, d = sqrt(dx * dx + dy * dy);
+ *     if (d < m) m = d;   if (!hit && d < radius) { hit = true; free = h; }
+ *   A NaN d does neither.  OPP_MIN = m, OPP_FREE = free.
+ * Rollout.  f110_rollout_opp_device is f110_rollout_device plus d_opp [N][K][2] float32 = ((float)OPP_MIN, (float)OPP_FREE);
+ *   d_out and d_traj are bit for bit what f110_rollout_device writes; the same stream and env-block behaviour (an env's cars are
+ *   always in one block).
+ * Planner.  f110_mppi_set_opponents attaches the term to the ARMED planner with two weights and a reference distance; it launches
+ *   nothing.  With the term attached f110_mppi_device and a F110_STEP_SCRIPTED step cost every candidate as
+ *     c = w_dead * ...;  c = c + w_clear * ...;
+ *     c = c + w_hit * (double)(H - OPP_FREE);
+ *     c = c + w_near * (OPP_MIN < near_ref ? near_ref - OPP_MIN : 0.0);
+ *     c = c - w_progress * ...;  c = c + w_lat * ...;   a NaN c becomes +inf
+ *   opp == NULL detaches it; f110_mppi_set, arming anew or disarming, drops it.  The term has no state of its own:
+ *   f110_mppi_get / f110_mppi_put are unchanged.  Its prediction table is the planner's memory and goes with it.
+ * Refused with F110_ERR_INVALID, nothing launched, written or changed: an unknown mode, a radius that is not finite and > 0, a
+ *   max_range that is NaN or <= 0, a weight that is not finite or < 0, a near_ref that is not finite, a null d_opp, Ao outside
+ *   0 .. 31 (the device forms: A - 1 > 31), and everything the rollout's and the planner's own calls refuse.
+ * Refused with F110_ERR_STATE: no planner armed, no map (the rollout's forms: F110_ERR_NO_MAP, as f110_rollout_*), TRACK while a map
+ *   slot in use has no track — checked when attaching and again at every call.
+ * Not offered: the opponents' footprints (a disc of `radius` around the reference points), interaction (the opponents do not react
+ *   to the candidate), a prediction from anything but the live state, per-opponent settings. */
+enum { F110_OPP_CV = 0, F110_OPP_TRACK = 1 };
+enum { F110_OPP_MAX = 31 };
+typedef struct f110_opponents {
+    int32_t mode;       /* F110_OPP_CV / F110_OPP_TRACK */
+    int32_t pad_;       /* ignored */
+    double radius;      /* metres, finite, > 0: a sample closer than this to a predicted opponent is a hit */
+    double max_range;   /* metres, > 0, +inf allowed, not NaN: an opponent further than this from the agent at the start is ignored */
+} f110_opponents;       /* 24 bytes */
+/* f110_rollout_device with the opponent term: d_opp [N][K][2] float32 in device memory.  h_pinned receives d_out's copy. */
+int f110_rollout_opp_device(f110_sim *h, const f110_rollout *spec, const f110_opponents *opp, const double *d_actions,
+                            float *d_out /* [N][K][D] */, float *d_traj /* [N][K][H][4] or NULL */, float *d_opp /* [N][K][2] */,
+                            float *h_pinned);
+/* f110_rollout_batch with the opponent term on host rows: h_opp_rows [m][Ao][4] = (x, y, v, theta) of row r's opponents,
+ * 0 <= Ao <= 31 (NULL with Ao = 0).  Outputs beside f110_rollout_batch's, each may be NULL: h_pred [m][Ao][H][2] float64 the
+ * predictions, h_opp_raw [m][K][2] float64 (OPP_MIN, (double)OPP_FREE), h_opp [m][K][2] float32 what the device form writes. */
+int f110_rollout_opp_batch(f110_sim *h, const f110_rollout *spec, const f110_opponents *opp, int32_t slot,
+                           const double *h_start /* [m][10] */, const double *h_params /* [m][18] or NULL */, const double *h_actions,
+                           const double *h_opp_rows /* [m][Ao][4] */, int32_t Ao, int32_t m, float *h_out /* [m][K][D] */,
+                           double *h_raw /* [m][K][10] or NULL */, float *h_traj /* or NULL */, double *h_traj_raw /* or NULL */,
+                           double *h_pred /* [m][Ao][H][2] or NULL */, double *h_opp_raw /* [m][K][2] or NULL */,
+                           float *h_opp /* [m][K][2] or NULL */);
+/* attaches the opponent term to the armed planner (opp == NULL: detaches it; the numbers are then ignored).  Launches nothing. */
+int f110_mppi_set_opponents(f110_sim *h, const f110_opponents *opp, double w_hit, double w_near, double near_ref);
+/* f110_mppi_batch with the opponent term on host rows: h_opp_rows [m][Ao][4] as above; h_opp_raw [m][K][2] float64 (or NULL) the
+ * candidates' (OPP_MIN, (double)OPP_FREE).  The planner armed on the handle, and what is attached to it, is not touched. */
+int f110_mppi_opp_batch(f110_sim *h, const f110_mppi *spec, const f110_opponents *opp, double w_hit, double w_near, double near_ref,
+                        int32_t slot, const double *h_start /* [m][10] */, const double *h_params /* [m][18] or NULL */,
+                        const int32_t *h_fresh /* [m] or NULL */, const double *h_opp_rows /* [m][Ao][4] */, int32_t Ao, int32_t m,
+                        double *h_nominal /* [m][H][2] */, uint64_t *h_streams /* [m][4] */, double *h_actions /* [m][2] */,
+                        float *h_info /* [m][4] */, double *h_cand /* [m][K][H][2] */, double *h_cost /* [m][K] */,
+                        double *h_weight /* [m][K] */, double *h_opp_raw /* [m][K][2] or NULL */);
 
 /* ---- particle filter: Monte-Carlo localisation per agent from its lidar scan (no reference counterpart: the particle filter of the
  * MIT racecar stack that F1TENTH cars localise with, here against the distance table the simulator already keeps) ----
