@@ -1,8 +1,9 @@
 // f110_hip.hip — host side of libf110_hip.so: the handle (one MI355X, one HIP stream + a side
 // stream), device-memory ownership, kernel launches and the C ABI declared in include/f110.h.
 // The kernels live in f110_kernels.hpp, the scalar float64 building blocks in f110_math.hpp.
-// A step is k_integrate -> k_scan_rays_agent -> k_finalize_pair on one stream for two-agent envs,
-// k_integrate -> { k_scan_rays || k_collide (side stream) } -> k_finalize otherwise.
+// A step is integrate -> scan -> finalize on one stream, the pair tests inside the finalize kernel (k_finalize_pair_roles
+// for two-agent envs, k_finalize_multi up to 256 agents per env); beyond that k_collide runs on the side stream, under the
+// scan.  A tiny host-synchronised batch is one launch (k_step_tiny).  The table of forms stands above step_range.
 // Compiled with -ffp-contract=off.  There is no CPU fallback in this library.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -504,7 +505,12 @@ static inline bool padded_family(int layout) { return layout == F110_MAP_PADDED_
 
 static inline dim3 grid1d(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 
+// the kernel families of the step, by signature (the pickers below return these)
 typedef void (*scan_rays_fn)(RayJob, ScanConst);
+typedef void (*scan_agent_fn)(RayJob, ScanConst, const MapFast *, const ScanConst *, uint32_t);   // k_scan_rays_agent, k_scan_dirs_agent
+typedef void (*finalize_fn)(AgentArrays, int32_t);
+typedef void (*finalize_multi_fn)(AgentArrays, int32_t, int);
+typedef void (*step_tiny_fn)(AgentArrays, ScanConst, RayJob, const double *, TinyCtl, EpisodeArrays, HostBlock, int, int);
 static int copy_col(f110_sim *h, double *dst, const double *src, size_t n);
 
 // ray / B by multiply-high: find (magic, shift) with umulhi(x, magic) >> shift == x / B for every
@@ -555,6 +561,20 @@ static const ScanConst *cold_consts(f110_sim *h)
         if (hipMemcpyAsync(h->d_k, &h->k_uploaded, sizeof(ScanConst), hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
     }
     return h->d_k;
+}
+
+// the RayJob fields that every form of the step sets alike (step_scan, step_tiny)
+static int ray_job_step_fields(f110_sim *h, RayJob &j)
+{
+    j.noise = h->dev.noise;
+    j.ttc_side_max = h->ttc_side_max;
+    j.ttc_k = h->dev.ttc_thresh * (1.0 + 1e-9) * h->ttc_cos_max;
+    j.beam_cos = h->dev.beam_cos;
+    j.side_dist = h->dev.side_dist;
+    j.ttc_thresh = h->dev.ttc_thresh;
+    j.k_cold = cold_consts(h);
+    if (!j.k_cold) return fail(h, F110_ERR_HIP, "f110_step_device: constant upload failed");
+    return F110_OK;
 }
 
 // The step's scan runs agent-aligned (k_scan_rays_agent) with the PADDED layout unless that would
@@ -2445,6 +2465,107 @@ static int map_host_ptr(f110_sim *h, const void *host, void **dev, const char *w
     return F110_OK;
 }
 
+// the device view of the caller's block (and of its actions, when they are read in place): kept until either changes
+static int host_block_bind(f110_sim *h, const double *h_actions, const f110_host_block *out, bool mapped_actions)
+{
+    if (h->hb_valid && std::memcmp(&h->hb_host, out, sizeof *out) == 0 && h->hb_actions_host == (mapped_actions ? h_actions : nullptr)) return F110_OK;
+    const size_t N = (size_t)h->N;
+    HostBlock d{};
+    void *p = nullptr;
+#define MAP_FIELD(dst, src, name)                     \
+    do {                                              \
+        TRY(map_host_ptr(h, out->src, &p, name));     \
+        d.dst = reinterpret_cast<decltype(d.dst)>(p); \
+    } while (0)
+    MAP_FIELD(state, state, "state");
+    MAP_FIELD(collisions, collisions, "collisions");
+    MAP_FIELD(collision_idx, collision_idx, "collision_idx");
+    MAP_FIELD(agent_poses, agent_poses, "agent_poses");
+    MAP_FIELD(lap_time, lap_times, "lap_times");
+    MAP_FIELD(lap_count, lap_counts, "lap_counts");
+    MAP_FIELD(toggle, toggles, "toggles");
+    MAP_FIELD(current_time, current_time, "current_time");
+    MAP_FIELD(in_collision, in_collision, "in_collision");
+    MAP_FIELD(near_start, near_starts, "near_starts");
+    MAP_FIELD(checkpoint, checkpoint_done, "checkpoint_done");
+    MAP_FIELD(done, done, "done");
+#undef MAP_FIELD
+    // scans of a small batch: stored by the kernel too (needs page-locked memory; else, and for big batches, the DMA copy)
+    d.scans = nullptr;
+    d.num_beams = h->cfg.num_beams;
+    h->hb_scans_by_kernel = false;
+    if (out->scans && N * (size_t)h->cfg.num_beams * sizeof(double) <= kScansByKernelBytes) {
+        void *ps = nullptr;
+        if (hipHostGetDevicePointer(&ps, out->scans, 0) == hipSuccess && ps) {
+            d.scans = reinterpret_cast<double *>(ps);
+            h->hb_scans_by_kernel = true;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    TRY(map_host_ptr(h, mapped_actions ? h_actions : nullptr, &p, "h_actions"));
+    h->hb_actions_dev = reinterpret_cast<const double *>(p);
+    h->hb_actions_host = mapped_actions ? h_actions : nullptr;
+    h->hb_dev = d;
+    h->hb_host = *out;
+    h->hb_valid = true;
+    return F110_OK;
+}
+
+typedef std::chrono::steady_clock::time_point host_time;
+
+// f110_step_host's way out: the completion word (spin), the bounded poll of the stream, or the runtime's wait
+static int host_step_wait(f110_sim *h, int32_t flags, bool spin, bool tiny, host_time t_in, host_time t_enq)
+{
+    if (spin) {
+        // poll the completion word the last workgroup stores (no runtime call on the way out); a kernel that
+        // never signals (a device fault) is caught by the runtime after the spin budget
+        const unsigned long long want = h->hb_seq;
+        const volatile unsigned long long *w = h->hb_seq_host;
+        bool seen = false;
+        if (kExperimental && h->exp.tiny_start_probe && tiny && h->tiny.start_word) {
+            for (long it = 0; it < 200000000L && __atomic_load_n(w + 1, __ATOMIC_ACQUIRE) != want; ++it) __builtin_ia32_pause();
+            const auto t_start = std::chrono::steady_clock::now();
+            for (long it = 0; it < 200000000L && __atomic_load_n(w, __ATOMIC_ACQUIRE) != want; ++it) __builtin_ia32_pause();
+            const auto t_done = std::chrono::steady_clock::now();
+            h->exp.probe_calls += 1;
+            h->exp.probe_us[0] += std::chrono::duration<double, std::micro>(t_enq - t_in).count();
+            h->exp.probe_us[1] += std::chrono::duration<double, std::micro>(t_start - t_enq).count();
+            h->exp.probe_us[2] += std::chrono::duration<double, std::micro>(t_done - t_start).count();
+        }
+        for (long it = 0; it < 2000000000L; ++it) {
+            if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == want) {
+                seen = true;
+                break;
+            }
+            __builtin_ia32_pause();
+            if ((it & 0xfffff) == 0xfffff &&
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enq).count() > 5.0) break;
+        }
+        if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else if (!(flags & F110_STEP_NO_SYNC)) {
+        if (flags & F110_STEP_POLL) {
+            // hipStreamSynchronize wakes up in coarse quanta once a wait has lasted ~30 us (measured: a 40 us step is
+            // reported after 67 us); polling the stream costs a core for the step's duration and returns within ~1 us
+            // ... so the poll is BOUNDED (ADVICE r4): a step that has not finished after kPollBudgetUs hands the core back and
+            // sleeps in hipStreamSynchronize — the coarse wake-up is then a few per cent of a long wait, and ranks that share a
+            // CPU quota (8 ranks on 16 cores on the bench box) do not spin against their own policy threads
+            constexpr double kPollBudgetUs = 250.0;
+            hipError_t q;
+            uint32_t it = 0;
+            while ((q = hipStreamQuery(h->stream)) == hipErrorNotReady) {
+                __builtin_ia32_pause();
+                if ((++it & 0x3fu) == 0u && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enq).count() > kPollBudgetUs) break;
+            }
+            if (q == hipErrorNotReady) HIPCHK(h, hipStreamSynchronize(h->stream));
+            else if (q != hipSuccess) return fail(h, F110_ERR_HIP, "hipStreamQuery failed: %s", hipGetErrorString(q));
+        } else {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+    }
+    return F110_OK;
+}
+
 int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *out, int32_t flags)
 {
     TRY(check_step(h, h_actions && out));
@@ -2460,47 +2581,7 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
     // scripted cars: the actions always go through the staging buffer, where the controllers overwrite their agents' rows
     const bool mapped_actions = (flags & F110_STEP_ACTIONS_MAPPED) != 0 && !scripted;
-    if (!h->hb_valid || std::memcmp(&h->hb_host, out, sizeof *out) != 0 || h->hb_actions_host != (mapped_actions ? h_actions : nullptr)) {
-        HostBlock d{};
-        void *p = nullptr;
-#define MAP_FIELD(dst, src, name)                     \
-    do {                                              \
-        TRY(map_host_ptr(h, out->src, &p, name));     \
-        d.dst = reinterpret_cast<decltype(d.dst)>(p); \
-    } while (0)
-        MAP_FIELD(state, state, "state");
-        MAP_FIELD(collisions, collisions, "collisions");
-        MAP_FIELD(collision_idx, collision_idx, "collision_idx");
-        MAP_FIELD(agent_poses, agent_poses, "agent_poses");
-        MAP_FIELD(lap_time, lap_times, "lap_times");
-        MAP_FIELD(lap_count, lap_counts, "lap_counts");
-        MAP_FIELD(toggle, toggles, "toggles");
-        MAP_FIELD(current_time, current_time, "current_time");
-        MAP_FIELD(in_collision, in_collision, "in_collision");
-        MAP_FIELD(near_start, near_starts, "near_starts");
-        MAP_FIELD(checkpoint, checkpoint_done, "checkpoint_done");
-        MAP_FIELD(done, done, "done");
-#undef MAP_FIELD
-        // scans of a small batch: stored by the kernel too (needs page-locked memory; else, and for big batches, the DMA copy)
-        d.scans = nullptr;
-        d.num_beams = h->cfg.num_beams;
-        h->hb_scans_by_kernel = false;
-        if (out->scans && N * (size_t)h->cfg.num_beams * sizeof(double) <= kScansByKernelBytes) {
-            void *ps = nullptr;
-            if (hipHostGetDevicePointer(&ps, out->scans, 0) == hipSuccess && ps) {
-                d.scans = reinterpret_cast<double *>(ps);
-                h->hb_scans_by_kernel = true;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        TRY(map_host_ptr(h, mapped_actions ? h_actions : nullptr, &p, "h_actions"));
-        h->hb_actions_dev = reinterpret_cast<const double *>(p);
-        h->hb_actions_host = mapped_actions ? h_actions : nullptr;
-        h->hb_dev = d;
-        h->hb_host = *out;
-        h->hb_valid = true;
-    }
+    TRY(host_block_bind(h, h_actions, out, mapped_actions));
     const auto t_in = std::chrono::steady_clock::now();
     // a tiny batch is one launch whose last workgroup writes the block (k_step_tiny): its completion is ONE word stored by one
     // workgroup, so the host always waits on that word (no runtime call on the way out)
@@ -2586,52 +2667,7 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     // terminal observation), stream-ordered in front of the next step
     if (h->rs.on && (rq.auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, env_blocks_main(h)));
     const auto t_enq = std::chrono::steady_clock::now();
-    if (spin) {
-        // poll the completion word the last workgroup stores (no runtime call on the way out); a kernel that
-        // never signals (a device fault) is caught by the runtime after the spin budget
-        const unsigned long long want = h->hb_seq;
-        const volatile unsigned long long *w = h->hb_seq_host;
-        bool seen = false;
-        if (kExperimental && h->exp.tiny_start_probe && tiny && h->tiny.start_word) {
-            for (long it = 0; it < 200000000L && __atomic_load_n(w + 1, __ATOMIC_ACQUIRE) != want; ++it) __builtin_ia32_pause();
-            const auto t_start = std::chrono::steady_clock::now();
-            for (long it = 0; it < 200000000L && __atomic_load_n(w, __ATOMIC_ACQUIRE) != want; ++it) __builtin_ia32_pause();
-            const auto t_done = std::chrono::steady_clock::now();
-            h->exp.probe_calls += 1;
-            h->exp.probe_us[0] += std::chrono::duration<double, std::micro>(t_enq - t_in).count();
-            h->exp.probe_us[1] += std::chrono::duration<double, std::micro>(t_start - t_enq).count();
-            h->exp.probe_us[2] += std::chrono::duration<double, std::micro>(t_done - t_start).count();
-        }
-        for (long it = 0; it < 2000000000L; ++it) {
-            if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == want) {
-                seen = true;
-                break;
-            }
-            __builtin_ia32_pause();
-            if ((it & 0xfffff) == 0xfffff &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enq).count() > 5.0) break;
-        }
-        if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else if (!(flags & F110_STEP_NO_SYNC)) {
-        if (flags & F110_STEP_POLL) {
-            // hipStreamSynchronize wakes up in coarse quanta once a wait has lasted ~30 us (measured: a 40 us step is
-            // reported after 67 us); polling the stream costs a core for the step's duration and returns within ~1 us
-            // ... so the poll is BOUNDED (ADVICE r4): a step that has not finished after kPollBudgetUs hands the core back and
-            // sleeps in hipStreamSynchronize — the coarse wake-up is then a few per cent of a long wait, and ranks that share a
-            // CPU quota (8 ranks on 16 cores on the bench box) do not spin against their own policy threads
-            constexpr double kPollBudgetUs = 250.0;
-            hipError_t q;
-            uint32_t it = 0;
-            while ((q = hipStreamQuery(h->stream)) == hipErrorNotReady) {
-                __builtin_ia32_pause();
-                if ((++it & 0x3fu) == 0u && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enq).count() > kPollBudgetUs) break;
-            }
-            if (q == hipErrorNotReady) HIPCHK(h, hipStreamSynchronize(h->stream));
-            else if (q != hipSuccess) return fail(h, F110_ERR_HIP, "hipStreamQuery failed: %s", hipGetErrorString(q));
-        } else {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-        }
-    }
+    TRY(host_step_wait(h, flags, spin, tiny, t_in, t_enq));
     const auto t_out = std::chrono::steady_clock::now();
     h->hs_enqueue_us += std::chrono::duration<double, std::micro>(t_enq - t_in).count();
     h->hs_wait_us += std::chrono::duration<double, std::micro>(t_out - t_enq).count();
@@ -2739,31 +2775,6 @@ static int noise_cache_extend(f110_sim *h, int upto)
     return F110_OK;
 }
 
-// One step of the agents [begin, begin + count) (an env-aligned block) on stream `st`.
-// Product build, one dispatch per (agents per env, beams) case:
-//   A = 1                      k_integrate -> scan -> k_finalize_solo
-//   A = 2                      k_integrate -> scan -> k_finalize_pair_roles    (pair test + window inside the last kernel)
-//                              ... k_finalize_pair_wave in a step of two env blocks  (the same as one-wave workgroups, which fit under the other block's scan)
-//   A = 3 .. 16                k_integrate -> scan -> k_finalize_multi         (the same for every ordered pair of an env)
-//   A = 17 .. 256              k_integrate -> scan -> k_finalize_multi_tiled   (the env's ordered pairs in tiles of 256 records)
-//   A > 256                    k_integrate -> { scan || k_collide on the side stream } -> k_finalize
-// and the scan kernel by table / beam count: k_scan_rays_agent (PADDED table; longest-first order for small
-// batches), k_scan_dirs_agent (more beams than table directions), k_scan_rays (row-major table, few beams).
-// The experimental build adds collide_mode 1 (pair tests fused into k_integrate) / 2 (k_collide in line), the
-// other layouts' kernels, two-pass dedupe and the forced geometries of f110_exp_set.
-// ev[0..3] (or nullptr): profiling events before integrate / before scan / after scan / after finalize.
-enum ScanKind { SCAN_FLAT, SCAN_AGENT, SCAN_AGENT_SCHED, SCAN_DIRS };
-
-
-static ScanKind pick_scan(const f110_sim *h, int begin, int count)
-{
-    const bool padded = padded_family(h->cfg.map_layout) && h->k.pad;
-    if (h->dir_stride > 0) return padded ? SCAN_DIRS : SCAN_FLAT;   // (no PADDED table: every beam is marched)
-    if (!(h->multi_map || agent_aligned(h))) return SCAN_FLAT;
-    if (h->task_order && !h->multi_map && !h->lookups_on && begin == 0 && count == h->N && !h->exp.scan_env_counter) return SCAN_AGENT_SCHED;
-    return SCAN_AGENT;
-}
-
 // The next doubling of the row cache, started on the noise stream when HALF of the rows there are have been used: generation (12.8 us a
 // row) is faster than any step loop uses rows (a step of one env takes 30 us and more), so the rows are there when the episode reaches
 // them and no step waits.  The rows so far are immutable; a cache that outgrows its memory continues in a new block (old rows copied
@@ -2860,6 +2871,21 @@ static int tiny_setup(f110_sim *h)
     return F110_OK;
 }
 
+// One picker per kernel family of the step, each above the stage that launches it.  A picker names every instantiation the
+// library holds and no other (taking a kernel's address instantiates it) — and in the order the code object has always had
+// them: the device code stays byte for byte what it was (profiles/step_stage_split_device_code.txt).
+
+// k_step_tiny<PAIR, IDENT, HOST>: two cars per env / the map's rotation is the identity / the f110_step_host epilogue
+static step_tiny_fn pick_step_tiny(bool pair, bool ident, bool host)
+{
+    if (pair) {
+        if (host) return ident ? k_step_tiny<true, true, true> : k_step_tiny<true, false, true>;
+        return ident ? k_step_tiny<true, true, false> : k_step_tiny<true, false, false>;
+    }
+    if (host) return ident ? k_step_tiny<false, true, true> : k_step_tiny<false, false, true>;
+    return ident ? k_step_tiny<false, true, false> : k_step_tiny<false, false, false>;
+}
+
 static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions, const StepRequest &rq, bool &host_written)
 {
     TRY(tiny_setup(h));
@@ -2869,14 +2895,7 @@ static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions, const
     dev.agent_count = N;
     dev.sched_count_zero = nullptr;
     RayJob j{};
-    j.noise = h->dev.noise;
-    j.ttc_side_max = h->ttc_side_max;
-    j.ttc_k = h->dev.ttc_thresh * (1.0 + 1e-9) * h->ttc_cos_max;
-    j.beam_cos = h->dev.beam_cos;
-    j.side_dist = h->dev.side_dist;
-    j.ttc_thresh = h->dev.ttc_thresh;
-    j.k_cold = cold_consts(h);
-    if (!j.k_cold) return fail(h, F110_ERR_HIP, "f110_step_device: constant upload failed");
+    TRY(ray_job_step_fields(h, j));
     h->tiny.tasks_per_agent = ((uint32_t)h->k.num_beams + 63u) / 64u;
     h->tiny.trace = kExperimental ? reinterpret_cast<unsigned long long *>(h->exp.tiny_trace) : nullptr;
     h->tiny.act_inline = 0;
@@ -2908,16 +2927,7 @@ static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions, const
     // one env of two cars: finalize_duo_tiny puts the scans into the caller's block early (its idle wave copies, the window lanes follow)
     h->tiny.host_scans = (host && h->hb_valid && h->hb_scans_by_kernel && A == 2 && N == 2 && !(kExperimental && h->exp.tiny_general_tail)) ? h->hb_dev.scans : nullptr;
     if (h->track_on) TRY(track_launch(h, st, kTrackHead, 0, N));
-#define TINY(P, I, H_) hipLaunchKernelGGL((k_step_tiny<P, I, H_>), grid, block, 0, st, dev, h->k, j, d_actions, h->tiny, ep, hb, episode, auto_reset)
-    const bool ident = h->k.ident_rot != 0;
-    if (A == 2) {
-        if (host) { if (ident) TINY(true, true, true); else TINY(true, false, true); }
-        else { if (ident) TINY(true, true, false); else TINY(true, false, false); }
-    } else {
-        if (host) { if (ident) TINY(false, true, true); else TINY(false, false, true); }
-        else { if (ident) TINY(false, true, false); else TINY(false, false, false); }
-    }
-#undef TINY
+    hipLaunchKernelGGL(pick_step_tiny(A == 2, h->k.ident_rot != 0, host), grid, block, 0, st, dev, h->k, j, d_actions, h->tiny, ep, hb, episode, auto_reset);
     h->last_launches = 1;
     if (h->track_on) {   // (f110_step_host runs the host block as k_host_block behind this: no host epilogue while tracking)
         TRY(track_launch(h, st, kTrackPost, 0, N));
@@ -2926,286 +2936,387 @@ static int step_tiny(f110_sim *h, hipStream_t st, const double *d_actions, const
     return F110_OK;
 }
 
-static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const double *d_actions, int collide_mode, hipEvent_t *ev, const StepRequest &rq,
-                      bool &host_written)
+// ---- one step of an env-aligned block, stage by stage (step_range puts them in order) ----------------------------------------
+
+// the scan kernel family of a step
+enum ScanKind { SCAN_FLAT, SCAN_AGENT, SCAN_AGENT_SCHED, SCAN_DIRS };
+
+static ScanKind pick_scan(const f110_sim *h, int begin, int count)
 {
-    const int N = h->N, A = h->cfg.num_agents, B = h->k.num_beams;
-    AgentArrays dev = h->dev;
-    dev.agent_begin = begin;
-    dev.agent_count = count;
-    const bool multi = A > 1;
-    // the scan kernel of this step, decided ONCE: the launch below and what k_integrate prepares for it
-    // (the longest-first list counter) follow the same answer
-    const ScanKind scan = pick_scan(h, begin, count);
-    if (h->track_on) TRY(track_launch(h, st, kTrackHead, begin, count));   // s of the pose this step starts from (cache misses only)
-    dev.sched_count_zero = scan == SCAN_AGENT_SCHED ? h->d_tcount + (h->task_epoch & 1u) : nullptr;
+    const bool padded = padded_family(h->cfg.map_layout) && h->k.pad;
+    if (h->dir_stride > 0) return padded ? SCAN_DIRS : SCAN_FLAT;   // (no PADDED table: every beam is marched)
+    if (!(h->multi_map || agent_aligned(h))) return SCAN_FLAT;
+    if (h->task_order && !h->multi_map && !h->lookups_on && begin == 0 && count == h->N && !h->exp.scan_env_counter) return SCAN_AGENT_SCHED;
+    return SCAN_AGENT;
+}
+
+// where the pair tests (car against car) and the opponent windows of a step run
+enum PairTests {
+    PAIRS_NONE,               // one car per env
+    PAIRS_IN_INTEGRATE,       // lab, collide_mode 1: fused into k_integrate<2|4>
+    PAIRS_IN_FINALIZE_PAIR,   // A = 2: inside k_finalize_pair_roles / _wave
+    PAIRS_IN_FINALIZE_MULTI,  // A = 3 .. kMaxAgentsMulti, whole envs: inside k_finalize_multi / _tiled
+    PAIRS_COLLIDE_SIDE,       // k_collide on the side stream, under the scan
+    PAIRS_COLLIDE_IN_LINE     // lab, collide_mode 2: k_collide on the step's stream
+};
+
+// A = 2 inside the finalize kernel: one stream, no events.  (Round 2 kept the side-stream form for big batches stepped without the
+// in-step re-seat — crashed cars pile up, their windows grow to all beams, and fixed lanes per agent then serialise — the flattened
+// window loop balances that inside the workgroup: 65 536 parked cars 0.624 -> 0.579 ms, crashed cars piling up 0.899 -> 0.852.)
+static PairTests pair_tests_place(int A, int collide_mode, int begin, int count)
+{
+    if (A <= 1) return PAIRS_NONE;
+    if (kExperimental && collide_mode == 1 && (A == 2 || A == 4)) return PAIRS_IN_INTEGRATE;
+    if (collide_mode == 3 && A == 2 && begin % 2 == 0) return PAIRS_IN_FINALIZE_PAIR;
+    if (collide_mode == 3 && A > 2 && A <= kMaxAgentsMulti && begin % A == 0 && count % A == 0) return PAIRS_IN_FINALIZE_MULTI;
+    return (kExperimental && collide_mode == 2) ? PAIRS_COLLIDE_IN_LINE : PAIRS_COLLIDE_SIDE;
+}
+
+enum IntegrateForm { INTEGRATE_FAN, INTEGRATE_DUO, INTEGRATE_WAVE };
+
+// Two waves per 64 agents (k_integrate_duo); RK4: thirteen (k_integrate_fan) up to kFanMaxAgents agents — the kernel is a latency
+// chain there; big batches are throughput-bound and keep the two-wave form.  force_*: the lab's switches (-1 = this rule).
+static IntegrateForm integrate_form(int integrator, int count, int force_duo, int force_fan)
+{
+    const bool rk4 = integrator == F110_INTEGRATOR_RK4;
+    if (force_fan >= 0 ? (force_fan != 0 && rk4) : (rk4 && count <= kFanMaxAgents)) return INTEGRATE_FAN;
+    return force_duo == 0 ? INTEGRATE_WAVE : INTEGRATE_DUO;   // (k_integrate<0>, one wave per 64 agents: lab only)
+}
+
+// Lanes per agent in the finalize kernel.  With the pair test inside (A = 2): more agents per workgroup = fewer prologue waves and a
+// better-balanced item list; small batches want the workgroups many (measured: 65 536 agents AG 32 / 16 / 4: 0.726 / 0.738 / 0.815 ms;
+// 4096 agents AG 16 / 4: 0.1047 / 0.1053).  (Rounds 2-3's forms — fixed lanes per agent, the prologue dealt by agent — were retired in
+// round 5.)  Behind k_collide: few lanes per agent pay off when opponent windows are short (~36 beams); cars that have crashed into
+// each other see windows of up to all beams, so the narrow forms are used only when finished envs are re-seated inside the step
+// (narrow: f110_set_auto_reseat armed).
+static int finalize_lanes(bool narrow, int N, bool pair)
+{
+    if (pair) return N >= 32768 ? 8 : (N >= 4096 ? 16 : 64);
+    return narrow && N >= 131072 ? 8 : (narrow && N >= 32768 ? 16 : 64);
+}
+
+// k_finalize_pair_wave in a step of two env blocks: from 24 576 agents in the automatic mode, where the other block's scan fills the
+// GPU and the 256-thread form waits for its tail (two blocks, 256-thread / one-wave form, lab build, ms per step: 8192 agents 0.1235 /
+// 0.1333, 16 384: 0.1964 / 0.1987, 24 576: 0.2754 / 0.2747, 32 768: 0.3637 / 0.3586, 49 152: 0.5278 / 0.5218, 65 536: 0.6799 / 0.6515 —
+// profiles/two_block_pair_sweep.txt).  step_groups = 2, two blocks on request, takes it at every size: that keeps the form reachable
+// for small batches in the product build, where the tests hold it against the one-block step bit for bit.
+// One-wave workgroups fit the slots the OTHER block's scan frees wave by wave (a 256-thread workgroup waits for that scan's tail).
+// Alone it is the slower form — one block at 65 536 agents 0.6933 -> 0.7032 ms with the lab switch pair_wave = 1 — so one block keeps
+// the 256-thread form.  Priced in the bench's regime, re-seats armed; with re-seats off crashed pairs stay and their windows grow
+// towards all B beams: there it still led, 1.159 -> 1.097 ms (same file).
+static bool pair_wave_pays(bool env_blocks, bool groups_auto, int N)
+{
+    return env_blocks && (!groups_auto || N >= 24576);
+}
+
+static int step_noise_rows(f110_sim *h, hipStream_t st, const AgentArrays &dev, int count)
+{
     if (dev.noise_rng && (dev.noise_rng == 2 || h->noise_ub >= (long long)dev.noise_rows)) {
         const int apb = dev.noise_rng == 2 ? 16 : 64;   // per-agent streams: every agent needs a row, keep the waves many
-        hipLaunchKernelGGL(k_noise_rows, dim3((count + apb - 1) / apb), dim3(256), 0, st, dev, h->noise_gen, B, apb);
+        hipLaunchKernelGGL(k_noise_rows, dim3((count + apb - 1) / apb), dim3(256), 0, st, dev, h->noise_gen, h->k.num_beams, apb);
     }
-    if (ev) HIPCHK(h, hipEventRecord(ev[0], st));
-    bool fused_integrate = false;
+    return F110_OK;
+}
+
+static int step_integrate(f110_sim *h, hipStream_t st, const AgentArrays &dev, int count, const double *d_actions, PairTests pairs)
+{
 #ifdef F110_EXPERIMENTAL
-    if (multi && collide_mode == 1 && A == 2) {
-        hipLaunchKernelGGL(k_integrate<2>, grid1d(count, 64), dim3(64), 0, st, dev, h->k, d_actions);
-        fused_integrate = true;
-    } else if (multi && collide_mode == 1 && A == 4) {
-        hipLaunchKernelGGL(k_integrate<4>, grid1d(count, 64), dim3(64), 0, st, dev, h->k, d_actions);
-        fused_integrate = true;
+    if (pairs == PAIRS_IN_INTEGRATE) {
+        if (h->cfg.num_agents == 2) hipLaunchKernelGGL(k_integrate<2>, grid1d(count, 64), dim3(64), 0, st, dev, h->k, d_actions);
+        else hipLaunchKernelGGL(k_integrate<4>, grid1d(count, 64), dim3(64), 0, st, dev, h->k, d_actions);
+        return F110_OK;
     }
 #endif
-    if (!fused_integrate) {
-        bool duo = true;   // the integration in two waves per 64 agents (k_integrate_duo)
-        // RK4: thirteen waves per 64 agents (k_integrate_fan) up to kFanMaxAgents agents — the kernel is a latency
-        // chain there; big batches are throughput-bound and keep the two-wave form
-        bool fan = h->dev.integrator == F110_INTEGRATOR_RK4 && count <= kFanMaxAgents;
+    (void)pairs;
+    switch (integrate_form(h->dev.integrator, count, kExperimental ? h->exp.integrate_duo : -1, kExperimental ? h->exp.integrate_fan : -1)) {
+    case INTEGRATE_FAN: hipLaunchKernelGGL(k_integrate_fan, grid1d(count, 64), dim3(64 * kFanWaves), 0, st, dev, h->k, d_actions); break;
+    case INTEGRATE_DUO: hipLaunchKernelGGL(k_integrate_duo, grid1d(count, 64), dim3(128), 0, st, dev, h->k, d_actions); break;
+    case INTEGRATE_WAVE:
 #ifdef F110_EXPERIMENTAL
-        if (h->exp.integrate_duo >= 0) duo = h->exp.integrate_duo != 0;
-        if (h->exp.integrate_fan >= 0) fan = h->exp.integrate_fan != 0 && h->dev.integrator == F110_INTEGRATOR_RK4;
+        hipLaunchKernelGGL(k_integrate<0>, grid1d(count, 256), dim3(256), 0, st, dev, h->k, d_actions);
 #endif
-        if (fan) hipLaunchKernelGGL(k_integrate_fan, grid1d(count, 64), dim3(64 * kFanWaves), 0, st, dev, h->k, d_actions);
-        else if (duo) hipLaunchKernelGGL(k_integrate_duo, grid1d(count, 64), dim3(128), 0, st, dev, h->k, d_actions);
-#ifdef F110_EXPERIMENTAL
-        else hipLaunchKernelGGL(k_integrate<0>, grid1d(count, 256), dim3(256), 0, st, dev, h->k, d_actions);
-#endif
+        break;
     }
-    // A = 2: the pair test and the opponent window inside the finalize kernel (k_finalize_pair_flat): one stream, no
-    // events.  (Round 2 kept the side-stream form for big batches stepped without the in-step re-seat — crashed cars
-    // pile up, their windows grow to all beams, and fixed lanes per agent then serialise — the flattened window loop
-    // balances that inside the workgroup: 65 536 parked cars 0.624 -> 0.579 ms, crashed cars piling up 0.899 -> 0.852.)
-    const bool pair_in_finalize = multi && collide_mode == 3 && A == 2 && (begin % 2) == 0;
-    const bool multi_in_finalize = multi && collide_mode == 3 && A > 2 && A <= kMaxAgentsMulti && (begin % A) == 0 && (count % A) == 0;
-    const bool no_collide_launch = fused_integrate || pair_in_finalize || multi_in_finalize;
-    const bool side_collide = multi && !no_collide_launch && !(kExperimental && collide_mode == 2);
-    // k_collide only feeds k_finalize, k_scan_rays only needs k_integrate: run the two side by
-    // side (second stream, event fork/join) so the pair test + window set-up hides under the scan
-    if (multi && !no_collide_launch) {
-        if (side_collide) {
-            HIPCHK(h, hipEventRecord(h->ev_integrated, st));
-            HIPCHK(h, hipStreamWaitEvent(h->side_stream, h->ev_integrated, 0));
-            hipLaunchKernelGGL(k_collide, grid1d(count, 64), dim3(64), 0, h->side_stream, dev, B);
-            HIPCHK(h, hipEventRecord(h->ev_collided, h->side_stream));
-        } else {
-            hipLaunchKernelGGL(k_collide, grid1d(count, 64), dim3(64), 0, st, dev, B);
-        }
+    return F110_OK;
+}
+
+// k_collide only feeds k_finalize, the scan only needs k_integrate: run the two side by side (second stream, event fork here,
+// join in step_range behind the scan) so the pair test + window set-up hides under the scan
+static int step_collide(f110_sim *h, hipStream_t st, const AgentArrays &dev, int count, PairTests pairs)
+{
+    if (pairs == PAIRS_COLLIDE_SIDE) {
+        HIPCHK(h, hipEventRecord(h->ev_integrated, st));
+        HIPCHK(h, hipStreamWaitEvent(h->side_stream, h->ev_integrated, 0));
+        hipLaunchKernelGGL(k_collide, grid1d(count, 64), dim3(64), 0, h->side_stream, dev, h->k.num_beams);
+        HIPCHK(h, hipEventRecord(h->ev_collided, h->side_stream));
+    } else if (pairs == PAIRS_COLLIDE_IN_LINE) {
+        hipLaunchKernelGGL(k_collide, grid1d(count, 64), dim3(64), 0, st, dev, h->k.num_beams);
     }
-    if (ev) HIPCHK(h, hipEventRecord(ev[1], st));
-    {
-        RayJob j{};
-        j.n_rays = (uint32_t)N * (uint32_t)B;
-        j.n_poses = N;
-        j.pose_x = h->dev.scan_pose;
-        j.pose_y = h->dev.scan_pose + N;
-        j.dir_start = h->dev.dir_start;
-        j.ranges = h->dev.scans;
-        j.hdr = h->dev.ray_hdr;
-        j.noise = h->dev.noise;
-        j.ttc_side_max = h->ttc_side_max;
-        j.ttc_k = h->dev.ttc_thresh * (1.0 + 1e-9) * h->ttc_cos_max;
-        j.beam_cos = h->dev.beam_cos;
-        j.side_dist = h->dev.side_dist;
-        j.wall_flag = h->dev.in_collision;
-        j.ttc_thresh = h->dev.ttc_thresh;
-        j.div_magic = h->step_magic;
-        j.div_shift = h->step_shift;
-        j.lookups_total = h->lookups_on ? h->d_lookups : nullptr;
-        j.path_stats = h->path_stats_on ? h->d_path_stats : nullptr;   // (step form: only the ray pass counts here)
+    return F110_OK;
+}
+
+// k_scan_dirs_agent<PER_ENV_MAP, IDENT, COUNT> (per-env maps carry their own rotation: IDENT never applies)
+static scan_agent_fn pick_dirs_agent(bool per_env_map, bool ident, bool count)
+{
+    if (per_env_map) return count ? k_scan_dirs_agent<true, false, true> : k_scan_dirs_agent<true, false, false>;
+    if (ident) return count ? k_scan_dirs_agent<false, true, true> : k_scan_dirs_agent<false, true, false>;
+    return count ? k_scan_dirs_agent<false, false, true> : k_scan_dirs_agent<false, false, false>;
+}
+
+// Which k_scan_rays_agent<PER_ENV_MAP, IDENT, COUNT, SCHED, ENVCNT, ENV_ORDER> a launch takes; a combination the library does not
+// hold gets nullptr.
+struct ScanAgentForm {
+    bool per_env_map = false;     // every env marches its own map (its own rotation: IDENT never applies)
+    bool ident = false;           // the one map's rotation is the identity
+    bool count = false;           // table lookups are counted (f110_count_lookups)
+    bool longest_first = false;   // SCAN_AGENT_SCHED (pick_scan: never with a count or per-env maps)
+    bool env_order = false;       // an env's agents sector by sector (never with per-env maps: the kernel's static_assert)
+    bool env_counter = false;     // lab: finished tasks counted per env (alone: no count, no order)
+};
+
+static scan_agent_fn pick_rays_agent(const ScanAgentForm &f)
+{
+    if (f.longest_first) {
+        if (f.count || f.per_env_map || f.env_counter) return nullptr;
+        if (f.env_order) return f.ident ? k_scan_rays_agent<false, true, false, true, false, true> : k_scan_rays_agent<false, false, false, true, false, true>;
+        return f.ident ? k_scan_rays_agent<false, true, false, true> : k_scan_rays_agent<false, false, false, true>;
+    }
+    if (f.env_counter) {
 #ifdef F110_EXPERIMENTAL
-        j.trace = reinterpret_cast<unsigned long long *>(h->exp.scan_trace);
+        if (!f.count && !f.per_env_map) return f.ident ? k_scan_rays_agent<false, true, false, false, true> : k_scan_rays_agent<false, false, false, false, true>;
 #endif
-        j.k_cold = cold_consts(h);
-        if (!j.k_cold) return fail(h, F110_ERR_HIP, "f110_step_device: constant upload failed");
-        j.order = (h->multi_map && begin == 0 && count == N) ? h->d_scan_order : nullptr;
-        const bool cnt = j.lookups_total != nullptr;
-        // agent-aligned launch geometry: whole 64-ray tasks per agent, so every wave belongs to one agent (and one map)
-        const bool env_order = h->scan_env_order && !h->multi_map && (scan == SCAN_AGENT || scan == SCAN_AGENT_SCHED);
-        auto agent_grid = [&](uint32_t tpa, dim3 &grid, uint32_t &wpb, int tpw) {
-            (void)rays_grid(j, h->scan_block, tpw);
-            j.n_tasks = (uint32_t)count * tpa;
-            j.first_pose = (uint32_t)begin;
-            // k_scan_rays_agent<.., ENV_ORDER> walks an env's agents sector by sector (scan_task_agent): the launch must cover whole envs
-            j.agents_per_env = (env_order && A > 1 && begin % A == 0 && count % A == 0 && scan_task_inv_ok(tpa, (uint32_t)A)) ? (uint32_t)A : 1u;
-            j.agents_inv = scan_task_inv(j.agents_per_env);
-            wpb = (uint32_t)h->scan_block / 64u;
-            const uint32_t waves = (j.n_tasks + j.tasks_per_wave - 1) / j.tasks_per_wave;
-            grid = dim3((waves + wpb - 1) / wpb);
-        };
-        const dim3 block(h->scan_block);
-        dim3 grid;
-        uint32_t wpb = 1;
-        switch (scan) {
-        case SCAN_DIRS: {
-            // more beams than table directions, PADDED table: march each distinct direction once and write
-            // the beams that share it from the same wave (k_scan_dirs_agent)
-            const uint32_t tpa = (uint32_t)h->dir_stride / 64u;
-            // (a direction task ends with ~3 coalesced write passes: four per wave, where the beam kernel wants three —
-            // BASELINE configs[4] 42.8 M agent-steps/s at 3, 45.2 M at 4)
-            agent_grid(tpa, grid, wpb, h->scan_tasks_auto && h->scan_tasks_per_wave == 3 ? 4 : h->scan_tasks_per_wave);
-#define DIRS_SCAN(PM, ID)                                                                                                                    \
-    do {                                                                                                                                     \
-        if (cnt) hipLaunchKernelGGL((k_scan_dirs_agent<PM, ID, true>), grid, block, 0, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);     \
-        else hipLaunchKernelGGL((k_scan_dirs_agent<PM, ID, false>), grid, block, 0, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);        \
-    } while (0)
-            if (h->multi_map) DIRS_SCAN(true, false);
-            else if (h->k.ident_rot) DIRS_SCAN(false, true);
-            else DIRS_SCAN(false, false);
-#undef DIRS_SCAN
-            break;
-        }
-        case SCAN_AGENT_SCHED: {
-            // longest-first: last step's long tasks are served by the first blocks of the launch
-            const uint32_t tpa = ((uint32_t)B + 63u) / 64u;
-            agent_grid(tpa, grid, wpb, env_order ? h->scan_tasks_agent : h->scan_tasks_per_wave);
-            const uint32_t parity = h->task_epoch & 1u;
-            j.sched = h->tsched[parity];
+        return nullptr;
+    }
+    if (f.per_env_map) {
+        if (f.env_order) return nullptr;
+        return f.count ? k_scan_rays_agent<true, false, true> : k_scan_rays_agent<true, false, false>;
+    }
+    if (f.env_order) {
+        if (f.ident) return f.count ? k_scan_rays_agent<false, true, true, false, false, true> : k_scan_rays_agent<false, true, false, false, false, true>;
+        return f.count ? k_scan_rays_agent<false, false, true, false, false, true> : k_scan_rays_agent<false, false, false, false, false, true>;
+    }
+    if (f.ident) return f.count ? k_scan_rays_agent<false, true, true> : k_scan_rays_agent<false, true, false>;
+    return f.count ? k_scan_rays_agent<false, false, true> : k_scan_rays_agent<false, false, false>;
+}
+
+// Agent-aligned launch geometry: whole 64-ray tasks per agent (tpa of them), so every wave belongs to one agent (and one map).
+// Fills the job's task fields and returns the grid.
+static dim3 scan_agent_grid(const f110_sim *h, RayJob &j, int begin, int count, uint32_t tpa, int tasks_per_wave, bool env_order)
+{
+    const int A = h->cfg.num_agents;
+    (void)rays_grid(j, h->scan_block, tasks_per_wave);   // (for j.tasks_per_wave; the task count is the block's)
+    j.n_tasks = (uint32_t)count * tpa;
+    j.first_pose = (uint32_t)begin;
+    // k_scan_rays_agent<.., ENV_ORDER> walks an env's agents sector by sector (scan_task_agent): the launch must cover whole envs
+    j.agents_per_env = (env_order && A > 1 && begin % A == 0 && count % A == 0 && scan_task_inv_ok(tpa, (uint32_t)A)) ? (uint32_t)A : 1u;
+    j.agents_inv = scan_task_inv(j.agents_per_env);
+    const uint32_t wpb = (uint32_t)h->scan_block / 64u;
+    const uint32_t waves = (j.n_tasks + j.tasks_per_wave - 1) / j.tasks_per_wave;
+    return dim3((waves + wpb - 1) / wpb);
+}
+
+static int step_scan(f110_sim *h, hipStream_t st, int begin, int count, ScanKind scan)
+{
+    const int N = h->N, B = h->k.num_beams;
+    RayJob j{};
+    j.n_rays = (uint32_t)N * (uint32_t)B;
+    j.n_poses = N;
+    j.pose_x = h->dev.scan_pose;
+    j.pose_y = h->dev.scan_pose + N;
+    j.dir_start = h->dev.dir_start;
+    j.ranges = h->dev.scans;
+    j.hdr = h->dev.ray_hdr;
+    j.wall_flag = h->dev.in_collision;
+    j.div_magic = h->step_magic;
+    j.div_shift = h->step_shift;
+    j.lookups_total = h->lookups_on ? h->d_lookups : nullptr;
+    j.path_stats = h->path_stats_on ? h->d_path_stats : nullptr;   // (step form: only the ray pass counts here)
+#ifdef F110_EXPERIMENTAL
+    j.trace = reinterpret_cast<unsigned long long *>(h->exp.scan_trace);
+#endif
+    TRY(ray_job_step_fields(h, j));
+    j.order = (h->multi_map && begin == 0 && count == N) ? h->d_scan_order : nullptr;
+    const dim3 block(h->scan_block);
+    if (scan == SCAN_FLAT) {   // ray = agent * B + beam (row-major table, few beams, or — product build — beams beyond the table
+                               // directions on a map the PADDED layout cannot hold)
+        const dim3 fgrid = rays_grid(j, h->scan_block, h->scan_tasks_per_wave);
+        hipLaunchKernelGGL(pick_rays<true>(h->k, h->cfg.map_layout), fgrid, block, 0, st, j, h->k);
+        return F110_OK;
+    }
+    const bool count_lookups = j.lookups_total != nullptr, ident = h->k.ident_rot != 0;
+    scan_agent_fn fn = nullptr;
+    dim3 grid;
+    uint32_t tpa = 0;
+    size_t lds = 0;
+    if (scan == SCAN_DIRS) {
+        // more beams than table directions, PADDED table: march each distinct direction once and write
+        // the beams that share it from the same wave (k_scan_dirs_agent)
+        tpa = (uint32_t)h->dir_stride / 64u;
+        // (a direction task ends with ~3 coalesced write passes: four per wave, where the beam kernel wants three —
+        // BASELINE configs[4] 42.8 M agent-steps/s at 3, 45.2 M at 4)
+        grid = scan_agent_grid(h, j, begin, count, tpa, h->scan_tasks_auto && h->scan_tasks_per_wave == 3 ? 4 : h->scan_tasks_per_wave, false);
+        fn = pick_dirs_agent(h->multi_map, ident, count_lookups);
+    } else {   // SCAN_AGENT, SCAN_AGENT_SCHED
+        const bool env_order = h->scan_env_order && !h->multi_map;
+        tpa = ((uint32_t)B + 63u) / 64u;
+        grid = scan_agent_grid(h, j, begin, count, tpa, env_order ? h->scan_tasks_agent : h->scan_tasks_per_wave, env_order);
+        ScanAgentForm f;
+        f.per_env_map = h->multi_map;
+        f.ident = ident;
+        f.count = count_lookups;
+        f.longest_first = scan == SCAN_AGENT_SCHED;
+        f.env_order = j.agents_per_env > 1;
+        if (f.longest_first) {   // last step's long tasks are served by the first blocks of the launch
+            const uint32_t wpb = (uint32_t)h->scan_block / 64u;
+            j.sched = h->tsched[h->task_epoch & 1u];
             j.epoch_r = h->task_epoch - 1u;
             j.epoch_w = h->task_epoch;
             j.long_blocks = (h->task_cap + wpb - 1) / wpb;
             j.long_prio = (uint32_t)h->exp.long_prio;
             j.long_rev = h->task_rev;
             h->task_epoch += 1u;
-            const dim3 sgrid(grid.x + j.long_blocks);
-            size_t slds = 0;
-#ifdef F110_EXPERIMENTAL
-            // probe: fewer waves per SIMD (an LDS reservation per one-wave workgroup) so that last step's long tasks,
-            // which start first, march at the idle chip's latency — does the shorter chain beat the lost throughput?
-            if (h->exp.scan_occupancy > 0 && h->scan_block == 64) slds = (size_t)(160 * 1024 / (4 * h->exp.scan_occupancy)) & ~(size_t)255;
-#endif
-            const bool eo = j.agents_per_env > 1;
-            if (h->k.ident_rot && eo)
-                hipLaunchKernelGGL((k_scan_rays_agent<false, true, false, true, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
-            else if (eo)
-                hipLaunchKernelGGL((k_scan_rays_agent<false, false, false, true, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
-            else if (h->k.ident_rot)
-                hipLaunchKernelGGL((k_scan_rays_agent<false, true, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
-            else
-                hipLaunchKernelGGL((k_scan_rays_agent<false, false, false, true>), sgrid, block, slds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
-            break;
+            grid = dim3(grid.x + j.long_blocks);
         }
-        case SCAN_AGENT: {
-            const uint32_t tpa = ((uint32_t)B + 63u) / 64u;
-            agent_grid(tpa, grid, wpb, env_order ? h->scan_tasks_agent : h->scan_tasks_per_wave);
-            size_t lds = 0;
 #ifdef F110_EXPERIMENTAL
-            // fusion-feasibility probes: the occupancy a kernel with k_finalize_pair's 118 VGPRs
-            // would run at (LDS reservation per one-wave workgroup caps the CU at 16 waves), and the price of a
-            // per-env completion counter
-            if (h->exp.scan_occupancy > 0 && h->scan_block == 64) lds = (size_t)(160 * 1024 / (4 * h->exp.scan_occupancy)) & ~(size_t)255;
-            if (h->exp.scan_env_counter && !h->multi_map && !cnt) {
-                if (!h->d_env_done) {
-                    TRY(dmalloc(h, &h->d_env_done, (size_t)h->cfg.num_envs));
-                    HIPCHK(h, hipMemsetAsync(h->d_env_done, 0, sizeof(uint32_t) * h->cfg.num_envs, st));
-                }
-                j.env_done = h->d_env_done;
-                j.tasks_per_env = tpa * (uint32_t)A;
-                if (h->k.ident_rot)
-                    hipLaunchKernelGGL((k_scan_rays_agent<false, true, false, false, true>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
-                else
-                    hipLaunchKernelGGL((k_scan_rays_agent<false, false, false, false, true>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
-                break;
+        // probes.  Fewer waves per SIMD (an LDS reservation per one-wave workgroup): the occupancy a kernel with the pair
+        // finalize's 118 VGPRs would run at (fusion feasibility), and whether last step's long tasks, which start
+        // first, march at the idle chip's latency — does the shorter chain beat the lost throughput?
+        if (h->exp.scan_occupancy > 0 && h->scan_block == 64) lds = (size_t)(160 * 1024 / (4 * h->exp.scan_occupancy)) & ~(size_t)255;
+        // ... and the price of a per-env completion counter (its kernel has neither the lookup count nor the env order)
+        if (scan == SCAN_AGENT && h->exp.scan_env_counter && !h->multi_map && !count_lookups) {
+            if (!h->d_env_done) {
+                TRY(dmalloc(h, &h->d_env_done, (size_t)h->cfg.num_envs));
+                HIPCHK(h, hipMemsetAsync(h->d_env_done, 0, sizeof(uint32_t) * h->cfg.num_envs, st));
             }
+            j.env_done = h->d_env_done;
+            j.tasks_per_env = tpa * (uint32_t)h->cfg.num_agents;
+            f.env_counter = true;
+            f.env_order = false;
+        }
 #endif
-#define AGENT_SCAN_ENV(ID)                                                                                                                            \
-    do {                                                                                                                                              \
-        if (cnt)                                                                                                                                      \
-            hipLaunchKernelGGL((k_scan_rays_agent<false, ID, true, false, false, true>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);  \
-        else                                                                                                                                          \
-            hipLaunchKernelGGL((k_scan_rays_agent<false, ID, false, false, false, true>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa); \
-    } while (0)
-#define AGENT_SCAN(PM, ID)                                                                                                           \
-    do {                                                                                                                             \
-        if (cnt)                                                                                                                     \
-            hipLaunchKernelGGL((k_scan_rays_agent<PM, ID, true>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa); \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((k_scan_rays_agent<PM, ID, false>), grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa); \
-    } while (0)
-            if (h->multi_map)
-                AGENT_SCAN(true, false);
-            else if (j.agents_per_env > 1 && h->k.ident_rot)
-                AGENT_SCAN_ENV(true);
-            else if (j.agents_per_env > 1)
-                AGENT_SCAN_ENV(false);
-            else if (h->k.ident_rot)
-                AGENT_SCAN(false, true);
-            else
-                AGENT_SCAN(false, false);
-#undef AGENT_SCAN
-#undef AGENT_SCAN_ENV
-            break;
-        }
-        default: {   // SCAN_FLAT: ray = agent * B + beam (row-major table, few beams, or — product build — beams
-                     // beyond the table directions on a map the PADDED layout cannot hold)
-            const dim3 fgrid = rays_grid(j, h->scan_block, h->scan_tasks_per_wave);
-            hipLaunchKernelGGL(pick_rays<true>(h->k, h->cfg.map_layout), fgrid, block, 0, st, j, h->k);
-            break;
-        }
-        }
+        fn = pick_rays_agent(f);
     }
-    if (ev) HIPCHK(h, hipEventRecord(ev[2], st));
-    if (side_collide) HIPCHK(h, hipStreamWaitEvent(st, h->ev_collided, 0));
-    if (multi) {
-        // few lanes per agent pay off when opponent windows are short (~36 beams); cars that have
-        // crashed into each other see windows of up to all beams, so the narrow forms are used only
-        // when finished envs are re-seated inside the step (f110_set_auto_reseat)
-        const bool narrow = h->dev.reseat_poses != nullptr;
-        // (with the pair test inside the kernel a group also carries that prologue: 16 lanes from 8192 agents up)
-        int lanes = narrow && N >= 131072 ? 8 : (narrow && N >= (pair_in_finalize ? 8192 : 32768) ? 16 : 64);
-        if (pair_in_finalize) {
-            // k_finalize_pair_roles: the window loop flattened over the workgroup, AG agents per 256 threads, the prologue dealt
-            // by role.  More agents per workgroup = fewer prologue waves and a better-balanced item list; small batches want
-            // the workgroups many (measured: 65 536 agents AG 32 / 16 / 4: 0.726 / 0.738 / 0.815 ms; 4096 agents AG 16 / 4:
-            // 0.1047 / 0.1053).  (Rounds 2-3's forms — fixed lanes per agent, the prologue dealt by agent — were retired in round 5.)
-            lanes = N >= 32768 ? 8 : (N >= 4096 ? 16 : 64);
-            // k_finalize_pair_wave in a step of two env blocks: from 24 576 agents in the automatic mode, where the other block's scan
-            // fills the GPU and the 256-thread form waits for its tail (two blocks, 256-thread / one-wave form, lab build, ms per step:
-            // 8192 agents 0.1235 / 0.1333, 16 384: 0.1964 / 0.1987, 24 576: 0.2754 / 0.2747, 32 768: 0.3637 / 0.3586, 49 152: 0.5278 /
-            // 0.5218, 65 536: 0.6799 / 0.6515 — profiles/two_block_pair_sweep.txt).  step_groups = 2, two blocks on request, takes it at
-            // every size: that keeps the form reachable for small batches in the product build, where the tests hold it against the
-            // one-block step bit for bit.
-            bool pair_wave = rq.env_blocks && (!h->groups_auto || N >= 24576);
-#ifdef F110_EXPERIMENTAL
-            if (h->exp.pair_wave >= 0) pair_wave = h->exp.pair_wave != 0;
-#endif
-            if (rq.fuse && begin == 0 && count == N && !dev.reseat_poses) {   // f110_step_host: host block + episode logic as this kernel's epilogue
-                dev.fused_host = h->d_fused;
-                dev.fused_seq = rq.seq;
-                host_written = true;
-            }
-            if (dev.fused_host) {   // the instantiation that carries the f110_step_host epilogue
-                if (lanes <= 8) hipLaunchKernelGGL((k_finalize_pair_roles<32, true>), dim3((count + 31) / 32), dim3(256), 0, st, dev, B);
-                else if (lanes == 16) hipLaunchKernelGGL((k_finalize_pair_roles<16, true>), dim3((count + 15) / 16), dim3(256), 0, st, dev, B);
-                else hipLaunchKernelGGL((k_finalize_pair_roles<4, true>), dim3((count + 3) / 4), dim3(256), 0, st, dev, B);
-            } else if (pair_wave) {
-                // one-wave workgroups, which fit the slots the OTHER block's scan frees wave by wave (a 256-thread workgroup waits for
-                // that scan's tail).  Alone it is the slower form — one block at 65 536 agents 0.6933 -> 0.7032 ms with the lab switch
-                // pair_wave = 1 — so one block keeps the form below.  Priced in the bench's regime, re-seats armed; with re-seats off
-                // crashed pairs stay and their windows grow towards all B beams: there it still led, 1.159 -> 1.097 ms (same file).
-                constexpr int AG = kFinalizeWaveAgents;
-                hipLaunchKernelGGL(k_finalize_pair_wave<AG>, dim3((count + AG - 1) / AG), dim3(64), 0, st, dev, B);
-            } else if (lanes <= 8) hipLaunchKernelGGL(k_finalize_pair_roles<32>, dim3((count + 31) / 32), dim3(256), 0, st, dev, B);
-            else if (lanes == 16) hipLaunchKernelGGL(k_finalize_pair_roles<16>, dim3((count + 15) / 16), dim3(256), 0, st, dev, B);
-            else hipLaunchKernelGGL(k_finalize_pair_roles<4>, dim3((count + 3) / 4), dim3(256), 0, st, dev, B);
-        }
-        else if (multi_in_finalize) {
-            const int envs = count / A;   // whole envs per workgroup
-            if (A * (A - 1) <= kMaxRec) {
-                const int G = kMaxRec / (A * (A - 1));
-                hipLaunchKernelGGL(k_finalize_multi<kMaxRec>, dim3((envs + G - 1) / G), dim3(256), 0, st, dev, B, G);
-            } else if (A * (A - 1) <= kMaxRecBig) {
-                hipLaunchKernelGGL(k_finalize_multi<kMaxRecBig>, dim3(envs), dim3(256), 0, st, dev, B, 1);
-            } else {   // more than 16 agents: one env per workgroup, its A (A - 1) records in tiles of 256
-                hipLaunchKernelGGL(k_finalize_multi_tiled<kMaxRecBig>, dim3(envs), dim3(256), multi_lds_bytes(A, kMaxRecBig), st, dev, B, 1);
-            }
-        }
-        else if (lanes == 8)
-            hipLaunchKernelGGL(k_finalize<8>, dim3((count + 31) / 32), dim3(256), 0, st, dev, B);
-        else if (lanes == 16)
-            hipLaunchKernelGGL(k_finalize<16>, dim3((count + 15) / 16), dim3(256), 0, st, dev, B);
-        else
-            hipLaunchKernelGGL(k_finalize<64>, dim3((count + 3) / 4), dim3(256), 0, st, dev, B);
-    } else {
+    if (!fn) return fail(h, F110_ERR_STATE, "f110_step_device: no scan kernel for this combination of switches");
+    hipLaunchKernelGGL(fn, grid, block, lds, st, j, h->k, h->d_maps_fast, h->d_maps_full, tpa);
+    return F110_OK;
+}
+
+// A finalize kernel and how many agents one of its workgroups takes (the grid follows)
+struct FinalizeKernel { finalize_fn fn; int agents, threads; };
+
+// A = 2, the pair test inside the kernel.  k_finalize_pair_roles<AG, HOST>: the window loop flattened over the workgroup, AG agents
+// per 256 threads (lanes per agent = 256 / AG), the prologue dealt by role; HOST carries the f110_step_host epilogue and goes first.
+// k_finalize_pair_wave: one-wave workgroups (when: pair_wave_pays).
+static FinalizeKernel pick_finalize_pair(int lanes, bool host, bool wave)
+{
+    if (host) {
+        if (lanes <= 8) return {k_finalize_pair_roles<32, true>, 32, 256};
+        if (lanes == 16) return {k_finalize_pair_roles<16, true>, 16, 256};
+        return {k_finalize_pair_roles<4, true>, 4, 256};
+    }
+    if (wave) return {k_finalize_pair_wave<kFinalizeWaveAgents>, kFinalizeWaveAgents, 64};
+    if (lanes <= 8) return {k_finalize_pair_roles<32>, 32, 256};
+    if (lanes == 16) return {k_finalize_pair_roles<16>, 16, 256};
+    return {k_finalize_pair_roles<4>, 4, 256};
+}
+
+// A = 3 .. kMaxAgentsMulti, every ordered pair of an env inside the kernel: whole envs per 256-thread workgroup
+struct FinalizeMultiKernel { finalize_multi_fn fn; int envs; size_t lds; };
+
+static FinalizeMultiKernel pick_finalize_multi(int A)
+{
+    const int pairs = A * (A - 1);
+    if (pairs <= kMaxRec) return {k_finalize_multi<kMaxRec>, kMaxRec / pairs, 0};
+    if (pairs <= kMaxRecBig) return {k_finalize_multi<kMaxRecBig>, 1, 0};
+    return {k_finalize_multi_tiled<kMaxRecBig>, 1, multi_lds_bytes(A, kMaxRecBig)};   // more than 16 agents: the env's records in tiles of 256
+}
+
+// the pair tests done before it (k_collide, or the lab's fused integration): k_finalize<lanes per agent>
+static FinalizeKernel pick_finalize(int lanes)
+{
+    if (lanes == 8) return {k_finalize<8>, 32, 256};
+    if (lanes == 16) return {k_finalize<16>, 16, 256};
+    return {k_finalize<64>, 4, 256};
+}
+
+static int step_finalize(f110_sim *h, hipStream_t st, AgentArrays &dev, int begin, int count, PairTests pairs, const StepRequest &rq, bool &host_written)
+{
+    const int N = h->N, A = h->cfg.num_agents, B = h->k.num_beams;
+    const bool narrow = h->dev.reseat_poses != nullptr;
+    switch (pairs) {
+    case PAIRS_NONE:
         hipLaunchKernelGGL(k_finalize_solo, grid1d(count, 256), dim3(256), 0, st, dev);
+        break;
+    case PAIRS_IN_FINALIZE_PAIR: {
+        bool pair_wave = pair_wave_pays(rq.env_blocks, h->groups_auto, N);
+#ifdef F110_EXPERIMENTAL
+        if (h->exp.pair_wave >= 0) pair_wave = h->exp.pair_wave != 0;
+#endif
+        if (rq.fuse && begin == 0 && count == N && !dev.reseat_poses) {   // f110_step_host: host block + episode logic as this kernel's epilogue
+            dev.fused_host = h->d_fused;
+            dev.fused_seq = rq.seq;
+            host_written = true;
+        }
+        const FinalizeKernel k = pick_finalize_pair(finalize_lanes(narrow, N, true), dev.fused_host != nullptr, pair_wave);
+        hipLaunchKernelGGL(k.fn, grid1d(count, k.agents), dim3(k.threads), 0, st, dev, B);
+        break;
     }
+    case PAIRS_IN_FINALIZE_MULTI: {
+        const FinalizeMultiKernel k = pick_finalize_multi(A);
+        hipLaunchKernelGGL(k.fn, grid1d(count / A, k.envs), dim3(256), k.lds, st, dev, B, k.envs);
+        break;
+    }
+    default: {   // the pair tests are done (k_collide, or the lab's fused integration)
+        const FinalizeKernel k = pick_finalize(finalize_lanes(narrow, N, false));
+        hipLaunchKernelGGL(k.fn, grid1d(count, k.agents), dim3(k.threads), 0, st, dev, B);
+        break;
+    }
+    }
+    return F110_OK;
+}
+
+// One step of the agents [begin, begin + count) (an env-aligned block) on stream `st`: the stages above, in order.
+// Product build, by agents per env (pair_tests_place):
+//   A = 1          k_integrate_duo|fan -> scan -> k_finalize_solo
+//   A = 2          k_integrate_duo|fan -> scan -> k_finalize_pair_roles<32|16|4>   (pair test + window inside the last kernel; <.., HOST>
+//                                                                                  carries f110_step_host's block as its epilogue)
+//                                        ... -> k_finalize_pair_wave   in a step of two env blocks (pair_wave_pays): one-wave
+//                                                                      workgroups, which fit under the other block's scan
+//   A = 3 .. 16    k_integrate_duo|fan -> scan -> k_finalize_multi         (the same for every ordered pair of an env)
+//   A = 17 .. 256  k_integrate_duo|fan -> scan -> k_finalize_multi_tiled   (the env's ordered pairs in tiles of 256 records)
+//   A > 256        k_integrate_duo|fan -> { scan || k_collide on the side stream } -> join -> k_finalize<64|16|8>
+// (a block that does not cover whole envs of A = 3 .. 256 takes the last row), k_noise_rows in front when the step's noise rows are
+// not in the table / row cache, the two track passes around it all when tracking is on; and the scan by table / beam count (pick_scan):
+//   SCAN_AGENT        k_scan_rays_agent: PADDED table, every wave one agent's; in env order (an env's agents sector by sector)
+//                     where f110_create measured it to pay; per-env maps
+//   SCAN_AGENT_SCHED  ... last step's longest tasks first: the whole batch on one map, task order on (small batches)
+//   SCAN_DIRS         k_scan_dirs_agent: more beams than table directions, each distinct direction marched once
+//   SCAN_FLAT         k_scan_rays (pick_rays): row-major table, few beams, or beams beyond the directions without a PADDED table
+// A tiny host-synchronised batch does not come here at all: step_tiny, one launch.
+// The experimental build adds collide_mode 1 (pair tests fused into k_integrate<2|4>) / 2 (k_collide in line), k_integrate<0>,
+// the scan's env counter and occupancy probes and the forced choices of f110_exp_set.
+// ev[0..3] (or nullptr): profiling events before integrate / before scan / after scan / after finalize.
+static int step_range(f110_sim *h, hipStream_t st, int begin, int count, const double *d_actions, int collide_mode, hipEvent_t *ev, const StepRequest &rq,
+                      bool &host_written)
+{
+    AgentArrays dev = h->dev;
+    dev.agent_begin = begin;
+    dev.agent_count = count;
+    // the scan kernel of this step, decided ONCE: the scan stage and what k_integrate prepares for it
+    // (the longest-first list counter, of the parity the scan stage then moves on) follow the same answer
+    const ScanKind scan = pick_scan(h, begin, count);
+    const PairTests pairs = pair_tests_place(h->cfg.num_agents, collide_mode, begin, count);
+    if (h->track_on) TRY(track_launch(h, st, kTrackHead, begin, count));   // s of the pose this step starts from (cache misses only)
+    dev.sched_count_zero = scan == SCAN_AGENT_SCHED ? h->d_tcount + (h->task_epoch & 1u) : nullptr;
+    TRY(step_noise_rows(h, st, dev, count));
+    if (ev) HIPCHK(h, hipEventRecord(ev[0], st));
+    TRY(step_integrate(h, st, dev, count, d_actions, pairs));
+    TRY(step_collide(h, st, dev, count, pairs));
+    if (ev) HIPCHK(h, hipEventRecord(ev[1], st));
+    TRY(step_scan(h, st, begin, count, scan));
+    if (ev) HIPCHK(h, hipEventRecord(ev[2], st));
+    if (pairs == PAIRS_COLLIDE_SIDE) HIPCHK(h, hipStreamWaitEvent(st, h->ev_collided, 0));
+    TRY(step_finalize(h, st, dev, begin, count, pairs, rq, host_written));
     if (ev) HIPCHK(h, hipEventRecord(ev[3], st));
     // the track columns of the observation: from snap_pose, the post-step pose no re-seat overwrites (k_host_block runs behind)
     if (h->track_on) TRY(track_launch(h, st, kTrackPost, begin, count));

@@ -365,6 +365,32 @@ def test_step_many_agents_per_env(amd, orc):
     assert st["wall"] > 0
 
 
+def test_step_more_than_256_agents_per_env(amd, orc):
+    """257 cars per env: past the multi finalize's per-env table, so the pair tests run as k_collide on the
+    side stream, joined in front of k_finalize<64>.  Every env holds collided AND free cars at every step."""
+    E, A, B, T = 2, 257, 64, 12
+    img, res, origin = load_map_image("example_map")
+    dt, _, _ = oracle_map_dt("example_map")
+    noise = np.zeros((T + 1, B))
+    s = amd.BatchSim(num_envs=E, num_agents=A, num_beams=B)
+    s.set_map_image(img, res, origin); s.set_noise_table(noise)
+    ref = orc.SimOracle(E, A, num_beams=B)
+    ref.set_map_dt(dt, res, origin); ref.set_noise(noise)
+    poses = bench_start_poses(E, A, gap_wp=3)
+    s.reset(poses); ref.reset(poses)
+    rng = np.random.default_rng(0)
+    for t in range(T):
+        act = np.stack([rng.uniform(-0.2, 0.2, E * A), rng.uniform(2.0, 6.0, E * A)], axis=1)
+        s.step(act); ref.step(act, 8)
+        o = s.get("scans", "state", "collisions", "collision_idx", "in_collision")
+        hit = (ref.collisions.reshape(E, A) != 0).sum(axis=1)
+        assert np.all(hit > 0) and np.all(hit < A), (t, hit)
+        assert np.array_equal(o["collisions"], ref.collisions) and np.array_equal(o["in_collision"], ref.in_collision), t
+        assert np.array_equal(o["collision_idx"], ref.collision_idx), t
+        assert rel_err(o["state"], ref.state) < NORTH_STAR and rel_err(o["scans"], ref.scans) < NORTH_STAR, t
+    s.close()
+
+
 def test_config5_4096_beams_tiled_big_map(amd, orc):
     """BASELINE config 5 shape: 4096 beams on example_map tiled 2x2 (3200x3200 table)"""
     img, res, origin = load_map_image("example_map")
