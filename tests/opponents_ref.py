@@ -2,8 +2,8 @@
 the rollout's and the planner's models (tests/rollout_ref.py fly, tests/mppi_ref.py candidates / update; tests/_util.track_oracle
 for the projection).  Its stages are functions of their own: predict (where the opponents will be), sample (a candidate's poses
 against the predictions), cost (the planner's two terms).  math.cos / math.sin are the libm calls the host instantiation makes, so
-the host harness agrees bit for bit; the device's differ by its own sincos.  Shared by tests/test_opponents_host.py and
-tests/test_gpu_opponents.py."""
+the host harness agrees bit for bit; the device's differ by its own sincos.  Shared by tests/test_opponents_host.py,
+tests/test_gpu_opponents.py and tests/test_gpu_opponents_edges.py."""
 import functools
 import math
 
@@ -239,3 +239,85 @@ def gpu_inputs(case):
 def gpu_flown(map_name, K, H, repeat):
     start, params = (a[:GRID_ROWS] for a in rr.grid_rows(map_name))
     return rr.fly(rr.scan_oracle(map_name), start, params, rr.grid_actions(K, H, False), False, repeat, rr.GRID_MARGIN, 1)
+
+
+def live_opponents(state, A):
+    """[N][A - 1][4] = x, y, v, theta of every agent's opponents: the env's other agents in ascending slot"""
+    N = state.shape[0]
+    out = np.zeros((N, A - 1, 4))
+    for n in range(N):
+        e, a = divmod(n, A)
+        for o in range(A - 1):
+            nb = e * A + (o if o < a else o + 1)
+            out[n, o] = state[nb, [0, 1, 3, 4]]
+    return out
+
+
+# ---- the edge grid (tests/test_gpu_opponents_edges.py; tests/test_opponents_host.py holds it to the leave-out rule) ----------------------
+# k_opp_predict gives a (row, opponent) 16 lanes, lane `sub` writes the actions sub, sub + 16, ...: H = 15, 16, 17 lie around the end
+# of the first lap, 32 and 33 around the end of the second, 64 is the limit (four laps).  Three rows x Ao in {5, 16, 31} are 15, 48 and
+# 93 groups of 16 lanes in workgroups of 16 groups: one idle group, three full workgroups, a ragged last one; 31 is the limit.
+EDGE_KHR = ((5, 15, 1), (5, 16, 1), (5, 17, 1), (5, 32, 2), (5, 33, 1), (64, 64, 1))
+EDGE_AO = (5, 16, 31)
+EDGE_LIMITS = ("example_map", 5, 64, 16, 5)      # (map, K, H, repeat, Ao): both limits of the horizon at once
+EDGE_RANGED = ("berlin", 5, 33, 1, 31)           # the same with a finite max_range: some of the 31 are not looked at
+EDGE_MAX_RANGE = 1.5                             # grid_opponents places them 0.3 .. 2.5 m from the row's start
+
+
+def edge_cases(map_names=rr.GRID_MAPS, modes=MODES):
+    """(map, K, H, repeat, mode, Ao, max_range, seed) — seed is grid_opponents' (0 unless a case had to move off a leave-out)"""
+    cases = [(mp, K, H, repeat, mode, Ao, INF, 0) for mp in map_names for mode in modes for K, H, repeat in EDGE_KHR for Ao in EDGE_AO]
+    for (mp, K, H, repeat, Ao), max_range in ((EDGE_LIMITS, INF), (EDGE_RANGED, EDGE_MAX_RANGE)):
+        cases += [(mp, K, H, repeat, mode, Ao, max_range, 0) for mode in modes if mp in map_names]
+    return cases
+
+
+EDGE_CASES = tuple(edge_cases())
+
+
+def edge_settings(case):
+    return settings(mode=case[4], radius=RADIUS, max_range=case[6])
+
+
+def edge_inputs(case):
+    """(start [3][10], params [3][18], actions [K][H][2] shared, opp [3][Ao][4])"""
+    map_name, K, H, _, _, Ao, _, seed = case
+    start, params = (a[:GRID_ROWS] for a in rr.grid_rows(map_name))
+    return start, params, rr.grid_actions(K, H, False), grid_opponents(map_name, Ao, seed)
+
+
+def edge_pred(case):
+    """the model's predictions of a case [3][Ao][H][2]"""
+    map_name, _, H, repeat = case[:4]
+    s, (start, _, _, opp), track = edge_settings(case), edge_inputs(case), rr.grid_track(map_name)
+    return np.stack([predict(s, start[n, 0], start[n, 1], opp[n], H, repeat, track=track) for n in range(len(start))])
+
+
+def nan_rows_between_finite(pred):
+    """does every row of pred [m][Ao][H][2] hold an ignored opponent (all NaN) with a predicted one on either side of it?"""
+    gone = np.all(np.isnan(pred), axis=(2, 3))
+    assert np.array_equal(gone, np.any(np.isnan(pred), axis=(2, 3))), "an opponent is ignored at some actions only"
+    return all(any(row[o] and not row[:o].all() and not row[o + 1:].all() for o in range(1, len(row) - 1)) for row in gone)
+
+
+# ---- the hand cases both test files work out (tests/test_opponents_host.py on the host harness, tests/test_gpu_opponents_edges.py) -------
+def hand_row(x, y, theta, v=0.0, fill=2):
+    return np.array([[x, y, 0.0, v, theta, 0.0, 0.0, 0.0, 0.0, float(fill)]])
+
+
+def seam_opponents(track, lap_at=0.875, lat=(0.2, -0.1), tau_last=1.0):
+    """three opponents on a closed track [3][4]: one `lap_at` metres before the seam driving forward at 1 m/s, `lat[0]` m left of the
+    line; one `lap_at` metres behind the seam driving backward at 1 m/s, -lat[1] m right of it; one at the first fast enough
+    that s_o + v tau_last lies beyond 2 L (a single subtraction leaves s >= L)"""
+    cols, L = track_cols(track), track.length
+    out = []
+    for s_at, l, v in ((L - lap_at, lat[0], 1.0), (lap_at, lat[1], -1.0), (L - lap_at, lat[0], 2.5 * L / tau_last)):
+        X, Y, ux, uy = station(cols, s_at)
+        out.append([X - l * uy, Y + l * ux, v, 0.0])
+    return np.array(out)
+
+
+def stations_of(track, opp_row, H, repeat, time_step=rr.TIME_STEP):
+    """s_o + v tau_h before the wrap, per action: what the model's TRACK rule hands to its one subtraction"""
+    s_o = float(track_oracle(track, np.array([[opp_row[0], opp_row[1], 0.0]]))[0, 0])
+    return np.array([s_o + float(opp_row[2]) * tau(h, repeat, time_step) for h in range(H)])

@@ -1,7 +1,7 @@
 """The model of the particle filter (include/f110.h, f110_pf): plain Python loops over NumPy's own generator — a
 sub-stream is PCG64 with the agent's state, .advance(q << 16), then Generator.random() or Generator.standard_normal() draw by draw —
 the oracle's scan (ScanOracle.scan(pose)[b_j]) for the expected ranges, and math functions; every sum is a loop over ascending indices
-from 0.0.  The stages are functions of their own, so that the GPU tests (tests/test_gpu_particle_filter.py) can hold each stage of
+from 0.0.  The stages are functions of their own, so that the GPU tests (tests/test_gpu_particle_filter.py, tests/test_gpu_particle_filter_edges.py) can hold each stage of
 the device to the model on the device's own input to it; the CPU tests (tests/test_particle_filter_host.py) chain them (`call`)."""
 import bisect
 import math
@@ -250,6 +250,28 @@ def filter_of(amd, s):
     return amd.ParticleFilter(**s)
 
 
+# ---- the update kernel's lane groupings (tests/test_gpu_particle_filter_edges.py) -------------------------------------------------------
+def group_lanes(P):
+    """a Python copy of pf_group_lanes (f110_kernels.hpp): the lanes k_pf_update gives an agent — the power of two >= min(P, 256), at
+    least 16; a workgroup of 256 lanes then holds 256 / GS agents, and a lane walks its particles in ceil(P / GS) passes"""
+    need = min(P, 256)
+    gs = 16
+    while gs < need:
+        gs <<= 1
+    return gs
+
+
+# P on both sides of every bound of the grouping: 16 | 17 (GS 16 -> 32), 32 | 33 (-> 64), 128 | 129 (-> 256), and 256 | 257, where GS
+# stays 256 and the lanes take a second pass
+EDGE_P = (16, 17, 32, 33, 128, 129, 256, 257)
+EDGE_B = (7, 64)
+
+
+def edge_cases(map_names=("example_map", "berlin"), Ps=EDGE_P):
+    """(map, P, B', the largest stride?, q) in unit_case's terms: q = 0 .. 3 in itertools.product(EDGE_B, (False, True)) order"""
+    return [(mp, P, Bp, big, q) for mp in map_names for P in Ps for q, (Bp, big) in enumerate((b, g) for b in EDGE_B for g in (False, True))]
+
+
 def cloud_around(poses, P, seed, spread=(0.15, 0.15, 0.08)):
     """a stored cloud [m][P][3] around the poses, with weights [m][P] of uneven size (normalised)"""
     rng = np.random.default_rng(seed)
@@ -316,3 +338,46 @@ def check_stages(s, so, inp, got, what, stats, lidar_dist=0.0):
         _gate(got["pose"][n], est, (w, "estimate"), stats)
         _gate(got["info"][n, :3], info[:3], (w, "info"), stats, atol=1e-6)
         assert same_bits(got["last"][n], np.asarray(poses[n], dtype=np.float64)), "%s: last" % w
+
+
+# ---- the device form's inputs and outputs ---------------------------------------------------------------------------------------------
+STATE_KEYS = ("particles", "weights", "last", "streams")
+
+
+def live_rows(sim, agents):
+    """the device's own inputs of the armed rows: (poses, scans, step_count) of the observation, and the filter's state"""
+    o = sim.get("agent_poses", "scans", "step_count")
+    return o["agent_poses"][agents], o["scans"][agents], o["step_count"][agents].astype(np.int32), sim.get_pf_state()
+
+
+def poisoned(sim, seed):
+    rng = np.random.default_rng(seed)
+    pa, pi = rng.normal(size=(sim.N, 3)), rng.normal(size=(sim.N, 4)).astype(np.float32)
+    d_pose, d_info = sim.device_array((sim.N, 3)), sim.device_array((sim.N, 4), np.float32)
+    d_pose.upload(pa)
+    d_info.upload(pi)
+    return d_pose, d_info, pa, pi
+
+
+def localize_and_check(amd, sim, s, so, agents, d_pose, d_info, what, stats, slot=0):
+    """one device call held to the unit form on the state fetched before it (bit for bit), and the unit form to the model"""
+    poses, scans, count, (X, W, last, words) = live_rows(sim, agents)
+    sim.localize_device(d_pose, d_info)
+    pose, info = d_pose.download(), d_info.download()
+    after = dict(zip(STATE_KEYS, sim.get_pf_state()))
+    unit = sim.localize_rows(filter_of(amd, s), poses, scans, X, W, last, words, slot=slot, fresh=count)
+    assert same_bits(pose[agents], unit["pose"]) and same_bits(info[agents], unit["info"]), "%s: the device form against the unit form" % (what,)
+    for key in STATE_KEYS:
+        assert same_bits(after[key], unit[key]), "%s: %s, the device form against the unit form" % (what, key)
+    check_stages(s, so, (poses, scans, X, W, last, words, count), unit, what, stats)
+    return pose, info, count
+
+
+def seed_clouds(sim, s, agents, seed):
+    """clouds around the live poses with uneven weights, and the last poses a short move earlier"""
+    poses = sim.get("agent_poses")["agent_poses"][agents]
+    X, W = cloud_around(poses, s["particles"], seed)
+    last = poses - np.column_stack([0.03 * np.cos(poses[:, 2]), 0.03 * np.sin(poses[:, 2]), np.full(len(agents), 0.01)])
+    last[:, 2] = np.mod(last[:, 2], TWO_PI)
+    W[::2] = 1.0 / s["particles"]                     # every other row holds uniform weights: it is not resampled
+    sim.set_pf_state(X, W, last)

@@ -27,6 +27,7 @@ import opponents_ref as ref
 import rollout_ref as rr
 from _util import MAPS, bench_start_poses, load_map_image, map_stem
 from mppi_ref import gated, mppi_of, pin_fifo, same_bits, streams_for, two_maps, warm_sim
+from opponents_ref import live_opponents
 
 pytestmark = pytest.mark.gpu
 
@@ -47,18 +48,6 @@ def amd():
 
 def opp_of(amd, s):
     return amd.Opponents(**s)
-
-
-def live_opponents(state, A):
-    """[N][A - 1][4] = x, y, v, theta of every agent's opponents: the env's other agents in ascending slot"""
-    N = state.shape[0]
-    out = np.zeros((N, A - 1, 4))
-    for n in range(N):
-        e, a = divmod(n, A)
-        for o in range(A - 1):
-            nb = e * A + (o if o < a else o + 1)
-            out[n, o] = state[nb, [0, 1, 3, 4]]
-    return out
 
 
 # ---- (a) the unit form against the model -----------------------------------------------------------------------------------------------

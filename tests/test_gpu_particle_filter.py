@@ -29,12 +29,11 @@ import particle_filter_ref as ref
 import rollout_ref as rr
 from _util import bench_start_poses, load_map_image, map_stem
 from mppi_ref import two_maps, warm_sim
-from particle_filter_ref import check_stages, filter_of, same_bits, streams_for
+from particle_filter_ref import STATE_KEYS, check_stages, filter_of, live_rows, localize_and_check, poisoned, same_bits, seed_clouds, streams_for
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-STATE_KEYS = ("particles", "weights", "last", "streams")
 
 
 @pytest.fixture(scope="module")
@@ -88,46 +87,6 @@ def test_unit_form_matches_model_at_1024_particles(amd, unit_sim, map_name, Bp):
         got = run_unit(amd, unit_sim, s, inp, slot)
         check_stages(s, so, inp, got, (map_name, 1024, Bp, s["beam_stride"]), stats)
     report("pf unit form on %s, P = 1024, B' = %d" % (map_name, Bp), stats)
-
-
-# ---- the device form's inputs and outputs ---------------------------------------------------------------------------------------------------
-def live_rows(sim, agents):
-    """the device's own inputs of the armed rows: (poses, scans, step_count) of the observation, and the filter's state"""
-    o = sim.get("agent_poses", "scans", "step_count")
-    return o["agent_poses"][agents], o["scans"][agents], o["step_count"][agents].astype(np.int32), sim.get_pf_state()
-
-
-def poisoned(sim, seed):
-    rng = np.random.default_rng(seed)
-    pa, pi = rng.normal(size=(sim.N, 3)), rng.normal(size=(sim.N, 4)).astype(np.float32)
-    d_pose, d_info = sim.device_array((sim.N, 3)), sim.device_array((sim.N, 4), np.float32)
-    d_pose.upload(pa)
-    d_info.upload(pi)
-    return d_pose, d_info, pa, pi
-
-
-def localize_and_check(amd, sim, s, so, agents, d_pose, d_info, what, stats, slot=0):
-    """one device call held to the unit form on the state fetched before it (bit for bit), and the unit form to the model"""
-    poses, scans, count, (X, W, last, words) = live_rows(sim, agents)
-    sim.localize_device(d_pose, d_info)
-    pose, info = d_pose.download(), d_info.download()
-    after = dict(zip(STATE_KEYS, sim.get_pf_state()))
-    unit = sim.localize_rows(filter_of(amd, s), poses, scans, X, W, last, words, slot=slot, fresh=count)
-    assert same_bits(pose[agents], unit["pose"]) and same_bits(info[agents], unit["info"]), "%s: the device form against the unit form" % (what,)
-    for key in STATE_KEYS:
-        assert same_bits(after[key], unit[key]), "%s: %s, the device form against the unit form" % (what, key)
-    check_stages(s, so, (poses, scans, X, W, last, words, count), unit, what, stats)
-    return pose, info, count
-
-
-def seed_clouds(sim, s, agents, seed):
-    """clouds around the live poses with uneven weights, and the last poses a short move earlier"""
-    poses = sim.get("agent_poses")["agent_poses"][agents]
-    X, W = ref.cloud_around(poses, s["particles"], seed)
-    last = poses - np.column_stack([0.03 * np.cos(poses[:, 2]), 0.03 * np.sin(poses[:, 2]), np.full(len(agents), 0.01)])
-    last[:, 2] = np.mod(last[:, 2], ref.TWO_PI)
-    W[::2] = 1.0 / s["particles"]                     # every other row holds uniform weights: it is not resampled
-    sim.set_pf_state(X, W, last)
 
 
 # ---- (b) the device form ------------------------------------------------------------------------------------------------------------------

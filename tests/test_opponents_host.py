@@ -242,6 +242,33 @@ def test_the_gpu_grid_leaves_no_candidate_out():
     assert total > 10000
 
 
+def test_the_edge_grid_leaves_no_candidate_out_and_some_hit():
+    """the same for tests/test_gpu_opponents_edges.py's grid (opponents_ref.EDGE_CASES: H up to 64, repeat up to 16, 5, 16 and 31
+    opponents): no candidate of the model's own motion is within 1e-9 * radius of flipping, candidates hit under every (K, H, repeat),
+    and the case with a finite max_range ignores opponents that lie between predicted ones"""
+    total, hits, by_shape, ranged = 0, 0, {}, 0
+    for case in ref.EDGE_CASES:
+        map_name, K, H, repeat, mode, Ao, max_range, _ = case
+        s = ref.edge_settings(case)
+        pred = ref.edge_pred(case)
+        assert pred.shape == (ref.GRID_ROWS, Ao, H, 2)
+        if max_range == INF:
+            assert np.all(np.isfinite(pred)), case
+        else:
+            assert ref.nan_rows_between_finite(pred), (case, "no ignored opponent between two predicted ones")
+            ranged += 1
+        raw, near = ref.sample_rows(s, ref.gpu_flown(map_name, K, H, repeat)[3], pred)
+        assert not np.any(ref.left_out(near, s["radius"])), case
+        total += near.size
+        hit = int(np.count_nonzero(raw[..., 1] < H))
+        hits += hit
+        by_shape[K, H, repeat] = by_shape.get((K, H, repeat), 0) + hit
+    print("edge grid: %d candidates, none left out, %d hit" % (total, hits))
+    assert ranged == len(ref.MODES) and all(by_shape.values()), by_shape
+    assert set(by_shape) == set(ref.EDGE_KHR) | {ref.EDGE_LIMITS[1:4]} and {c[5] for c in ref.EDGE_CASES} == set(ref.EDGE_AO)
+    assert {c[0] for c in ref.EDGE_CASES} == set(rr.GRID_MAPS) and {c[4] for c in ref.EDGE_CASES} == set(ref.MODES)
+
+
 # ---- cases by hand ----------------------------------------------------------------------------------------------------------------------
 P1 = orc.params_vec()[None, :]
 FREE = (rr.grid_rows("example_map")[0][0, 0], rr.grid_rows("example_map")[0][0, 1], rr.grid_rows("example_map")[0][0, 4])   # on the example raceline
@@ -352,6 +379,28 @@ def test_hand_track_mode_across_the_seam(hh):
     tip = [ocols[0][e] + ocols[2][e], ocols[1][e] + ocols[3][e], 50.0, 0.0]
     p = ref.predict(ref.settings(mode="track"), tip[0], tip[1], [tip], 3, 5, track=otr)
     assert np.all(p[0] == p[0][0]) and np.allclose(p[0][0], tip[:2], atol=1e-9)
+
+
+@needs_hipcc
+def test_hand_track_mode_wraps_late_and_beyond_two_laps(hh):
+    """opponents_ref.seam_opponents, the rows tests/test_gpu_opponents_edges.py sends through the kernel: the two slow ones cross the
+    seam at an action >= 16 (the second lap of the kernel's stride loop), the fast one lies beyond 2 L at the last action, where the
+    rule's single subtraction leaves s >= L: the station is the track's end point, finite; all bit for bit the model's"""
+    track = rr.grid_track("example_map")
+    cols, L, H, repeat = ref.track_cols(track), track.length, 20, 5
+    opp = ref.seam_opponents(track)
+    s = ref.settings(mode="track", radius=0.2)
+    st = row(cols[0][0], cols[1][0], 0.0, v=1.0)
+    got, _ = straight(hh, s, opp, H=H, repeat=repeat, start=st, track=track)
+    want = ref.predict(s, st[0, 0], st[0, 1], opp, H, repeat, track=track)
+    same(got["pred"][0], want, "pred")
+    assert np.all(np.isfinite(want))
+    fwd, back, fast = (ref.stations_of(track, o, H, repeat) for o in opp)
+    assert 16 <= int(np.argmax(fwd >= L)) < H and not np.any(fwd[:16] >= L) and 16 <= int(np.argmax(back < 0.0)) < H and not np.any(back[:16] < 0.0)
+    assert fast[-1] > 2.0 * L and fast[-1] - L >= L
+    end = np.array([cols[0][-1] + cols[2][-1], cols[1][-1] + cols[3][-1]])
+    lat_o = float(orc_project(track, opp[2])[1])
+    assert abs(lat_o - 0.2) < 0.02 and np.allclose(want[2, -1], end + lat_o * np.array([-cols[3][-1], cols[2][-1]]) / cols[5][-1], atol=1e-9)
 
 
 def orc_project(track, p):

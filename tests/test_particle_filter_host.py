@@ -272,6 +272,25 @@ def test_the_model_leaves_nothing_out_on_the_gpu_tests_unit_grid():
     assert rows == 2 * len(cases)
 
 
+def test_the_model_leaves_nothing_out_on_the_gpu_tests_edge_grid():
+    """the same for tests/test_gpu_particle_filter_edges.py's grid (particle_filter_ref.edge_cases: P on both sides of every bound
+    of k_pf_update's lane grouping), whose P reach every grouping"""
+    cases = ref.edge_cases()
+    assert {ref.group_lanes(P) for P in ref.EDGE_P} == {16, 32, 64, 128, 256} and len(cases) == 2 * len(ref.EDGE_P) * 4
+    assert [ref.group_lanes(P) for P in (1, 16, 17, 32, 33, 64, 65, 128, 129, 256, 257, 1024)] == [16, 16, 32, 32, 64, 64, 128, 128, 256, 256, 256, 256]
+    rows, outcomes = 0, {}
+    for mp, P, Bp, big, q in cases:
+        s, (poses, scans, X, W, last, words, fresh) = ref.unit_case(mp, P, Bp, big, q)
+        assert ref.beams(s)[-1] < ref.NUM_BEAMS and (not big or ref.beams(s)[-1] + s["n_beams"] - 1 >= ref.NUM_BEAMS)
+        for n in np.flatnonzero(fresh != 0):
+            u = float(np.random.Generator(ref.generator(words[n], 0)).random())
+            res, anc, ess, near = ref.resampling(s, W[n], u)
+            assert abs(ess - s["resample_frac"] * P) > 1e-9 * P and np.all(near > 1e-9), (mp, P, Bp, big, q, n)
+            outcomes.setdefault((mp, P), set()).add(res)
+            rows += 1
+    assert rows == 128 and all(v == {False, True} for v in outcomes.values()), "both resampling outcomes per P"
+
+
 # ---- the sanitizers --------------------------------------------------------------------------------------------------------------------
 @needs_hipcc
 def test_harness_program_is_clean_under_the_sanitizers(tmp_path):
