@@ -434,6 +434,10 @@ def i32ptr(a):
     return a.ctypes.data_as(_i32p)
 
 
+def u64ptr(a):
+    return a.ctypes.data_as(_u64p)
+
+
 def params_vector(params):
     try:
         return np.array([float(params[k]) for k in PARAM_KEYS], dtype=np.float64)

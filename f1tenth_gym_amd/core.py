@@ -12,7 +12,7 @@ import weakref
 import numpy as np
 
 from . import _ffi
-from ._ffi import check, as_f64, dptr, i32ptr
+from ._ffi import check, as_f64, dptr, i32ptr, u64ptr
 
 DEFAULT_PARAMS = {'mu': 1.0489, 'C_Sf': 4.718, 'C_Sr': 5.4562, 'lf': 0.15875, 'lr': 0.17145,
                   'h': 0.074, 'm': 3.74, 'I': 0.04712, 's_min': -0.4189, 's_max': 0.4189,
@@ -632,7 +632,7 @@ class BatchSim(object):
         return int(g.value), int(p.value), int(l.value)
 
     def step_launches(self):
-        """1 when the most recent step ran as ONE kernel launch (k_step_tiny: at most 64 agents, one or two per env), else 0"""
+        """1 when the most recent step ran as ONE kernel launch (k_step_tiny: at most 4 agents, one or two per env), else 0"""
         n = C.c_int32(0)
         check(_ffi.lib().f110_step_launches(self._h, C.byref(n)), self._h)
         return int(n.value)
@@ -1149,6 +1149,66 @@ class BatchSim(object):
             raise ValueError("pinned must be a C-contiguous float32 array of shape %s (pinned_empty)" % (shape,))
         return pinned.ctypes.data
 
+    @staticmethod
+    def _opt(a, ptr=dptr):
+        """an optional array argument: ptr(a), None for None"""
+        return None if a is None else ptr(a)
+
+    def _armed_list(self, agents, seed, agent_base):
+        """what arming a feature takes: the agents (int32, strictly ascending; None: every agent) and their streams' words uint64
+        [m][4], agent n's from PCG64(SeedSequence(seed, spawn_key=(agent_base + n,)))"""
+        from .reset_sampler import stream_words
+        a = np.arange(self.N, dtype=np.int32) if agents is None else np.ascontiguousarray(np.asarray(agents).reshape(-1), dtype=np.int32)
+        if int(agent_base) < 0:
+            raise ValueError("agent_base must be >= 0, got %d" % int(agent_base))
+        if a.size == 0 or a.min() < 0 or a.max() >= self.N or np.any(np.diff(a) <= 0):
+            raise ValueError("agents must be a strictly ascending list of 1 .. %d indices within 0 .. %d" % (self.N, self.N - 1))
+        lo = int(a[0])
+        return a, np.ascontiguousarray(stream_words(seed, int(a[-1]) - lo + 1, int(agent_base) + lo)[a - lo], dtype=np.uint64)
+
+    @staticmethod
+    def _stream_rows(streams, m, copy=False):
+        """the streams argument uint64 [m][4]; copy: an array of its own, which the call then writes"""
+        words = np.array(streams, dtype=np.uint64, order="C") if copy else np.ascontiguousarray(streams, dtype=np.uint64)
+        if words.shape != (m, 4):
+            raise ValueError("streams must be uint64 [%d][4]" % m)
+        return words
+
+    @staticmethod
+    def _fresh_rows(fresh, m):
+        """the unit forms' fresh argument int32 [m] (None: no row is fresh)"""
+        if fresh is None:
+            return None
+        fr = np.ascontiguousarray(fresh, dtype=np.int32)
+        if fr.shape != (m,):
+            raise ValueError("fresh must be [m]")
+        return fr
+
+    @staticmethod
+    def _start_rows(start):
+        """the unit forms' start rows float64 [m][10], and m"""
+        st = as_f64(start)
+        if st.ndim != 2 or st.shape[1] != 10:
+            raise ValueError("start must be [m][10] = state[7], FIFO newest, FIFO older, FIFO count")
+        return st, st.shape[0]
+
+    def _rollout_host(self, spec, actions, device_form):
+        """a rollout on host candidates: uploaded, device_form(Rollout, d_actions) called, its DeviceArrays downloaded (a tuple)
+        and freed"""
+        from .rollout import Rollout
+        ro = Rollout.coerce(spec)
+        a = as_f64(actions)
+        if tuple(a.shape) != ro.actions_shape(self.N):
+            raise ValueError("actions must have shape %s" % (ro.actions_shape(self.N),))
+        with DeviceArray(self, a.shape, np.float64) as d_act:
+            d_act.upload(a)
+            res = device_form(ro, d_act)
+            res = res if isinstance(res, tuple) else (res,)
+            host = tuple(r.download() for r in res)
+            for r in res:
+                r.free()
+        return host
+
     # ------------------------------------------------------------------ track preview (f110_track_preview_*, DESIGN §6g)
     def track_preview_device(self, preview, out=None, pinned=None):
         """the raceline ahead of every agent (track_preview.TrackPreview) as a float32 DeviceArray [N][P][D], from the s column
@@ -1181,7 +1241,7 @@ class BatchSim(object):
         sg = np.zeros((m, pv.points), dtype=np.int32) if segments else None
         spec = pv.spec()
         check(_ffi.lib().f110_track_preview_batch(self._h, C.byref(spec), int(slot), dptr(rows), m, out.ctypes.data,
-                                                  None if rw is None else dptr(rw), None if sg is None else i32ptr(sg)), self._h)
+                                                  self._opt(rw), self._opt(sg, i32ptr)), self._h)
         return _with_extras(out, rw, sg)
 
     # ------------------------------------------------------------------ neighbours (f110_neighbors_*)
@@ -1215,7 +1275,7 @@ class BatchSim(object):
         ix = np.zeros((m, nb.k), dtype=np.int32) if indices else None
         sp = nb.spec()
         check(_ffi.lib().f110_neighbors_batch(self._h, C.byref(sp), int(A), float(track_L), dptr(r), m, out.ctypes.data,
-                                              None if rw is None else dptr(rw), None if ix is None else i32ptr(ix)), self._h)
+                                              self._opt(rw), self._opt(ix, i32ptr)), self._h)
         return _with_extras(out, rw, ix)
 
     # ------------------------------------------------------------------ rollout (f110_rollout_*)
@@ -1262,18 +1322,7 @@ class BatchSim(object):
     def rollout_opp(self, spec, opponents, actions):
         """rollout_opp_device on host candidates, returned as NumPy: (summary, opp float32 [N][K][2]), or with spec.traj (summary,
         trajectory, opp)"""
-        from .rollout import Rollout
-        ro = Rollout.coerce(spec)
-        a = as_f64(actions)
-        if tuple(a.shape) != ro.actions_shape(self.N):
-            raise ValueError("actions must have shape %s" % (ro.actions_shape(self.N),))
-        with DeviceArray(self, a.shape, np.float64) as d_act:
-            d_act.upload(a)
-            res = self.rollout_opp_device(ro, opponents, d_act)
-            host = tuple(r.download() for r in res)
-            for r in res:
-                r.free()
-        return host
+        return self._rollout_host(spec, actions, lambda ro, d_act: self.rollout_opp_device(ro, opponents, d_act))
 
     @staticmethod
     def _opp_rows(opp_rows, m):
@@ -1296,19 +1345,8 @@ class BatchSim(object):
     def rollout(self, spec, actions):
         """rollout_device on host candidates `actions` (spec.actions_shape(N)), returned as NumPy: the summary float32 [N][K][D],
         or with spec.traj the pair (summary, trajectory)"""
-        from .rollout import Rollout
-        ro = Rollout.coerce(spec)
-        a = as_f64(actions)
-        if tuple(a.shape) != ro.actions_shape(self.N):
-            raise ValueError("actions must have shape %s" % (ro.actions_shape(self.N),))
-        with DeviceArray(self, a.shape, np.float64) as d_act:
-            d_act.upload(a)
-            res = self.rollout_device(ro, d_act)
-            res = res if ro.traj else (res,)
-            host = tuple(r.download() for r in res)
-            for r in res:
-                r.free()
-        return host if ro.traj else host[0]
+        host = self._rollout_host(spec, actions, self.rollout_device)
+        return host if len(host) > 1 else host[0]
 
     def rollout_rows(self, spec, start, actions, slot=0, params=None, raw=False):
         """unit form on host rows: start [m][10] = state[7], the steering FIFO's newest and older entry and its fill count (0, 1, 2),
@@ -1320,10 +1358,7 @@ class BatchSim(object):
     def _rollout_rows(self, spec, start, actions, slot, params, raw, opponents=None, opp_rows=None):
         from .rollout import Rollout
         ro = Rollout.coerce(spec)
-        st = as_f64(start)
-        if st.ndim != 2 or st.shape[1] != 10:
-            raise ValueError("start must be [m][10] = state[7], FIFO newest, FIFO older, FIFO count")
-        m = st.shape[0]
+        st, m = self._start_rows(start)
         a = as_f64(actions)
         if tuple(a.shape) != ro.actions_shape(m):
             raise ValueError("actions must have shape %s" % (ro.actions_shape(m),))
@@ -1336,19 +1371,18 @@ class BatchSim(object):
         rw = np.zeros((m, ro.k, 10)) if raw else None
         tr = np.zeros(ro.traj_shape(m), dtype=np.float32) if ro.traj else None
         trw = np.zeros(ro.traj_shape(m)) if ro.traj and raw else None
-        sp = ro.spec()
+        sp, opt = ro.spec(), self._opt
+        trp = None if tr is None else tr.ctypes.data
         if opponents is None:
-            check(_ffi.lib().f110_rollout_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), dptr(a), m, out.ctypes.data,
-                                                None if rw is None else dptr(rw), None if tr is None else tr.ctypes.data,
-                                                None if trw is None else dptr(trw)), self._h)
+            check(_ffi.lib().f110_rollout_batch(self._h, C.byref(sp), int(slot), dptr(st), opt(pv), dptr(a), m, out.ctypes.data, opt(rw), trp,
+                                                opt(trw)), self._h)
             return _with_extras(out, tr, rw, trw)
         orows, Ao = self._opp_rows(opp_rows, m)
         pred, oraw, o32 = np.zeros((m, Ao, ro.horizon, 2)), np.zeros((m, ro.k, 2)), np.zeros((m, ro.k, 2), dtype=np.float32)
         osp = opponents.spec()
-        check(_ffi.lib().f110_rollout_opp_batch(self._h, C.byref(sp), C.byref(osp), int(slot), dptr(st), None if pv is None else dptr(pv), dptr(a),
-                                                dptr(orows) if Ao else None, Ao, m, out.ctypes.data, dptr(rw),
-                                                None if tr is None else tr.ctypes.data, None if trw is None else dptr(trw),
-                                                dptr(pred) if Ao else None, dptr(oraw), o32.ctypes.data), self._h)
+        check(_ffi.lib().f110_rollout_opp_batch(self._h, C.byref(sp), C.byref(osp), int(slot), dptr(st), opt(pv), dptr(a), dptr(orows) if Ao else None, Ao, m,
+                                                out.ctypes.data, dptr(rw), trp, opt(trw), dptr(pred) if Ao else None, dptr(oraw),
+                                                o32.ctypes.data), self._h)
         return dict(out=out, raw=rw, traj=tr, traj_raw=trw, pred=pred, opp_raw=oraw, opp=o32)
 
     # ------------------------------------------------------------------ MPPI planner (f110_mppi_*)
@@ -1360,17 +1394,10 @@ class BatchSim(object):
         agent in a larger run (a shard), so that the run draws the same numbers however it is split.  Every nominal starts as
         (0, v_init); nothing is launched.  The planner acts in mppi_device and in step_host(scripted=True).  Returns the Mppi."""
         from .mppi import Mppi
-        from .reset_sampler import stream_words
         mp = Mppi.coerce(spec)
-        a = np.arange(self.N, dtype=np.int32) if agents is None else np.ascontiguousarray(np.asarray(agents).reshape(-1), dtype=np.int32)
-        if int(agent_base) < 0:
-            raise ValueError("agent_base must be >= 0, got %d" % int(agent_base))
-        if a.size == 0 or a.min() < 0 or a.max() >= self.N or np.any(np.diff(a) <= 0):
-            raise ValueError("agents must be a strictly ascending list of 1 .. %d indices within 0 .. %d" % (self.N, self.N - 1))
-        lo = int(a[0])
-        words = np.ascontiguousarray(stream_words(seed, int(a[-1]) - lo + 1, int(agent_base) + lo)[a - lo], dtype=np.uint64)
+        a, words = self._armed_list(agents, seed, agent_base)
         sp = mp.spec()
-        check(_ffi.lib().f110_mppi_set(self._h, C.byref(sp), i32ptr(a), int(a.size), words.ctypes.data_as(_ffi._u64p)), self._h)
+        check(_ffi.lib().f110_mppi_set(self._h, C.byref(sp), i32ptr(a), int(a.size), u64ptr(words)), self._h)
         self.mppi_planner, self.mppi_agents, self.mppi_opponents = mp, a, None
         return mp
 
@@ -1427,7 +1454,7 @@ class BatchSim(object):
             raise _ffi.F110LibraryError("no planner is armed (set_mppi)")
         nom = np.zeros(mp.nominal_shape(self.mppi_agents.size))
         words = np.zeros((self.mppi_agents.size, 4), dtype=np.uint64)
-        check(_ffi.lib().f110_mppi_get(self._h, dptr(nom), words.ctypes.data_as(_ffi._u64p)), self._h)
+        check(_ffi.lib().f110_mppi_get(self._h, dptr(nom), u64ptr(words)), self._h)
         return nom, words
 
     def set_mppi_state(self, nominal=None, streams=None):
@@ -1438,12 +1465,8 @@ class BatchSim(object):
             raise _ffi.F110LibraryError("no planner is armed (set_mppi)")
         m = self.mppi_agents.size
         nom = None if nominal is None else as_f64(nominal, mp.nominal_shape(m))
-        words = None
-        if streams is not None:
-            words = np.ascontiguousarray(streams, dtype=np.uint64)
-            if words.shape != (m, 4):
-                raise ValueError("streams must be uint64 [%d][4]" % m)
-        check(_ffi.lib().f110_mppi_put(self._h, None if nom is None else dptr(nom), None if words is None else words.ctypes.data_as(_ffi._u64p)), self._h)
+        words = None if streams is None else self._stream_rows(streams, m)
+        check(_ffi.lib().f110_mppi_put(self._h, self._opt(nom), self._opt(words, u64ptr)), self._h)
 
     def mppi_rows(self, spec, start, nominal, streams, slot=0, params=None, fresh=None):
         """unit form on host rows (the same kernels; the armed planner is not touched): start [m][10] as rollout_rows takes it,
@@ -1462,36 +1485,25 @@ class BatchSim(object):
     def _mppi_rows(self, spec, start, nominal, streams, slot, params, fresh, opponents=None, weights=None, opp_rows=None):
         from .mppi import Mppi
         mp = Mppi.coerce(spec)
-        st = as_f64(start)
-        if st.ndim != 2 or st.shape[1] != 10:
-            raise ValueError("start must be [m][10] = state[7], FIFO newest, FIFO older, FIFO count")
-        m = st.shape[0]
+        st, m = self._start_rows(start)
         nom = as_f64(nominal, mp.nominal_shape(m)).copy()
-        words = np.array(streams, dtype=np.uint64, order="C")
-        if words.shape != (m, 4):
-            raise ValueError("streams must be uint64 [%d][4]" % m)
+        words = self._stream_rows(streams, m, copy=True)
         pv = None if params is None else as_f64(params, (m, 18))
-        fr = None
-        if fresh is not None:
-            fr = np.ascontiguousarray(fresh, dtype=np.int32)
-            if fr.shape != (m,):
-                raise ValueError("fresh must be [m]")
+        fr = self._fresh_rows(fresh, m)
         act, inf = np.zeros((m, 2)), np.zeros((m, 4), dtype=np.float32)
         cand, cost, wgt = np.zeros((m, mp.k, mp.horizon, 2)), np.zeros((m, mp.k)), np.zeros((m, mp.k))
-        sp = mp.spec()
+        sp, opt = mp.spec(), self._opt
         res = dict(actions=act, info=inf, candidates=cand, cost=cost, weight=wgt, nominal=nom, streams=words)
         if opponents is None:
-            check(_ffi.lib().f110_mppi_batch(self._h, C.byref(sp), int(slot), dptr(st), None if pv is None else dptr(pv), None if fr is None else i32ptr(fr),
-                                             m, dptr(nom), words.ctypes.data_as(_ffi._u64p), dptr(act), inf.ctypes.data, dptr(cand), dptr(cost),
-                                             dptr(wgt)), self._h)
+            check(_ffi.lib().f110_mppi_batch(self._h, C.byref(sp), int(slot), dptr(st), opt(pv), opt(fr, i32ptr), m, dptr(nom), u64ptr(words), dptr(act),
+                                             inf.ctypes.data, dptr(cand), dptr(cost), dptr(wgt)), self._h)
             return res
         orows, Ao = self._opp_rows(opp_rows, m)
         oraw = np.zeros((m, mp.k, 2))
         osp = opponents.spec()
-        check(_ffi.lib().f110_mppi_opp_batch(self._h, C.byref(sp), C.byref(osp), weights[0], weights[1], weights[2], int(slot), dptr(st),
-                                             None if pv is None else dptr(pv), None if fr is None else i32ptr(fr), dptr(orows) if Ao else None, Ao, m,
-                                             dptr(nom), words.ctypes.data_as(_ffi._u64p), dptr(act), inf.ctypes.data, dptr(cand), dptr(cost), dptr(wgt),
-                                             dptr(oraw)), self._h)
+        check(_ffi.lib().f110_mppi_opp_batch(self._h, C.byref(sp), C.byref(osp), weights[0], weights[1], weights[2], int(slot), dptr(st), opt(pv),
+                                             opt(fr, i32ptr), dptr(orows) if Ao else None, Ao, m, dptr(nom), u64ptr(words), dptr(act), inf.ctypes.data,
+                                             dptr(cand), dptr(cost), dptr(wgt), dptr(oraw)), self._h)
         res["opp_raw"] = oraw
         return res
 
@@ -1505,18 +1517,11 @@ class BatchSim(object):
         starts as zeros with uniform weights and becomes a cloud around its car at the first call after a reset (or through
         set_pf_state); nothing is launched.  The filter acts in localize_device.  Returns the ParticleFilter."""
         from .particle_filter import ParticleFilter
-        from .reset_sampler import stream_words
         pf = ParticleFilter.coerce(spec)
         pf.check_beams(self.B)
-        a = np.arange(self.N, dtype=np.int32) if agents is None else np.ascontiguousarray(np.asarray(agents).reshape(-1), dtype=np.int32)
-        if int(agent_base) < 0:
-            raise ValueError("agent_base must be >= 0, got %d" % int(agent_base))
-        if a.size == 0 or a.min() < 0 or a.max() >= self.N or np.any(np.diff(a) <= 0):
-            raise ValueError("agents must be a strictly ascending list of 1 .. %d indices within 0 .. %d" % (self.N, self.N - 1))
-        lo = int(a[0])
-        words = np.ascontiguousarray(stream_words(seed, int(a[-1]) - lo + 1, int(agent_base) + lo)[a - lo], dtype=np.uint64)
+        a, words = self._armed_list(agents, seed, agent_base)
         sp = pf.spec()
-        check(_ffi.lib().f110_pf_set(self._h, C.byref(sp), i32ptr(a), int(a.size), words.ctypes.data_as(_ffi._u64p)), self._h)
+        check(_ffi.lib().f110_pf_set(self._h, C.byref(sp), i32ptr(a), int(a.size), u64ptr(words)), self._h)
         self.pf_filter, self.pf_agents = pf, a
         return pf
 
@@ -1559,7 +1564,7 @@ class BatchSim(object):
         pf, m = self._pf_armed()
         X, W, last = np.zeros(pf.cloud_shape(m)), np.zeros((m, pf.particles)), np.zeros((m, 3))
         words = np.zeros((m, 4), dtype=np.uint64)
-        check(_ffi.lib().f110_pf_get(self._h, dptr(X), dptr(W), dptr(last), words.ctypes.data_as(_ffi._u64p)), self._h)
+        check(_ffi.lib().f110_pf_get(self._h, dptr(X), dptr(W), dptr(last), u64ptr(words)), self._h)
         return X, W, last, words
 
     def set_pf_state(self, particles=None, weights=None, last=None, streams=None):
@@ -1569,13 +1574,9 @@ class BatchSim(object):
         X = None if particles is None else as_f64(particles, pf.cloud_shape(m))
         W = None if weights is None else as_f64(weights, (m, pf.particles))
         la = None if last is None else as_f64(last, (m, 3))
-        words = None
-        if streams is not None:
-            words = np.ascontiguousarray(streams, dtype=np.uint64)
-            if words.shape != (m, 4):
-                raise ValueError("streams must be uint64 [%d][4]" % m)
-        check(_ffi.lib().f110_pf_put(self._h, None if X is None else dptr(X), None if W is None else dptr(W), None if la is None else dptr(la),
-                                     None if words is None else words.ctypes.data_as(_ffi._u64p)), self._h)
+        words = None if streams is None else self._stream_rows(streams, m)
+        opt = self._opt
+        check(_ffi.lib().f110_pf_put(self._h, opt(X), opt(W), opt(la), opt(words, u64ptr)), self._h)
 
     def localize_rows(self, spec, poses, scans, particles, weights, last, streams, slot=0, fresh=None):
         """unit form on host rows (the same kernels; the armed filter is not touched): poses [m][3] the true poses on map slot
@@ -1591,20 +1592,14 @@ class BatchSim(object):
         m, P = po.shape[0], pf.particles
         sc = as_f64(scans, (m, self.B))
         X, W, la = as_f64(particles, pf.cloud_shape(m)).copy(), as_f64(weights, (m, P)).copy(), as_f64(last, (m, 3)).copy()
-        words = np.array(streams, dtype=np.uint64, order="C")
-        if words.shape != (m, 4):
-            raise ValueError("streams must be uint64 [%d][4]" % m)
-        fr = None
-        if fresh is not None:
-            fr = np.ascontiguousarray(fresh, dtype=np.int32)
-            if fr.shape != (m,):
-                raise ValueError("fresh must be [m]")
+        words = self._stream_rows(streams, m, copy=True)
+        fr = self._fresh_rows(fresh, m)
         pose, inf = np.zeros((m, 3)), np.zeros((m, 4), dtype=np.float32)
         noise, anc = np.zeros((m, P, 3)), np.zeros((m, P), dtype=np.int32)
         expect, logw = np.zeros((m, P, pf.n_beams)), np.zeros((m, P))
         sp = pf.spec()
-        check(_ffi.lib().f110_pf_batch(self._h, C.byref(sp), int(slot), dptr(po), dptr(sc), None if fr is None else i32ptr(fr), m, dptr(X), dptr(W),
-                                       dptr(la), words.ctypes.data_as(_ffi._u64p), dptr(pose), inf.ctypes.data, dptr(noise), i32ptr(anc),
+        check(_ffi.lib().f110_pf_batch(self._h, C.byref(sp), int(slot), dptr(po), dptr(sc), self._opt(fr, i32ptr), m, dptr(X), dptr(W),
+                                       dptr(la), u64ptr(words), dptr(pose), inf.ctypes.data, dptr(noise), i32ptr(anc),
                                        dptr(expect), dptr(logw)), self._h)
         return dict(pose=pose, info=inf, noise=noise, ancestors=anc, expected=expect, logw=logw, particles=X, weights=W, last=la, streams=words)
 

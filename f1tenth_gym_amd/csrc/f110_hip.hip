@@ -66,6 +66,14 @@ struct ExpSwitches {
 // the device forms that copy a per-agent float32 output into a caller's page-locked block (env_blocks_output)
 enum PinnedDst { kPinnedObs, kPinnedPreview, kPinnedNeighbors, kPinnedRollout, kPinnedCount };
 
+// the agents a feature is armed on (f110_mppi_set, f110_pf_set; the armed_* helpers below): m == 0: disarmed
+struct ArmedList {
+    int m = 0;
+    std::vector<int32_t> agents;     // the armed list, ascending
+    DevBuf<int32_t> d_agents;        // [m]
+    DevBuf<uint64_t> d_streams;      // [m][4] each agent's generator
+};
+
 struct f110_sim {
     f110_config cfg{};
     int N = 0;
@@ -238,15 +246,12 @@ struct f110_sim {
     DevBuf<int32_t> d_gap_assign;
     int gap_specs = 0, gap_max_w = 0;
     std::vector<int32_t> gap_assign_host;   // the armed assignment (empty while disarmed): what f110_mppi_set checks its agents against
-    // MPPI planner (f110_mppi_set): m == 0: disarmed.  The nominal sequences and the streams are the planner's own memory.
+    // MPPI planner (f110_mppi_set): on.m == 0: disarmed.  The nominal sequences and the streams are the planner's own memory.
     struct Mppi {
         MppiSpec sp{};
-        int m = 0;
-        std::vector<int32_t> agents;     // the armed list, ascending
-        DevBuf<int32_t> d_agents;        // [m]
+        ArmedList on;
         DevBuf<MppiSpec> d_spec;         // sp, for the kernels
         DevBuf<double> d_nominal;        // [m][H][2]
-        DevBuf<uint64_t> d_streams;      // [m][4]
         DevBuf<double> d_V;              // [m][K][H][2] the candidates of the last call
         DevBuf<double> d_cost;           // [m][K]
         DevBuf<double> d_end;            // [m][K][2] (only with a track weight)
@@ -259,13 +264,11 @@ struct f110_sim {
     DevBuf<double> d_roll_opp;           // f110_rollout_opp_device: the predictions [N][A - 1][H][2] (grows on demand)
     DevBuf<OppSpec> d_roll_opp_spec;     // ... and its settings, one copy per env block, written by the block's own k_opp_predict
     DevBuf<U128> d_mppi_jump;            // [2][kMppiJumps] the candidates' jump constants (from the first arming on)
-    // particle filter (f110_pf_set): m == 0: disarmed.  The clouds, the weights, the last poses and the streams are the filter's own memory.
+    // particle filter (f110_pf_set): on.m == 0: disarmed.  The clouds, the weights, the last poses and the streams are the filter's own memory.
     struct Pf {
         PfSpec sp{};
-        int m = 0, cur = 0;              // d_X[cur] is the stored cloud; a call moves it into d_X[cur ^ 1] and flips
-        std::vector<int32_t> agents;     // the armed list, ascending
-        DevBuf<int32_t> d_agents;        // [m]
-        DevBuf<uint64_t> d_streams;      // [m][4]
+        ArmedList on;
+        int cur = 0;                     // d_X[cur] is the stored cloud; a call moves it into d_X[cur ^ 1] and flips
         DevBuf<double> d_X[2];           // [m][P][3]
         DevBuf<double> d_W;              // [m][P]
         DevBuf<double> d_last;           // [m][3]
@@ -2574,9 +2577,9 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
                      out->checkpoint_done || out->done || (flags & F110_STEP_AUTO_RESET)))
         return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
     const bool scripted = (flags & F110_STEP_SCRIPTED) != 0;
-    if (scripted && h->gap_specs == 0 && h->mppi.m == 0)
+    if (scripted && h->gap_specs == 0 && h->mppi.on.m == 0)
         return fail(h, F110_ERR_STATE, "f110_step_host: F110_STEP_SCRIPTED without controllers (f110_controllers_set) or a planner (f110_mppi_set)");
-    if (scripted && h->mppi.m > 0) TRY(mppi_ready(h));
+    if (scripted && h->mppi.on.m > 0) TRY(mppi_ready(h));
     ENTER(h);
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
     // scripted cars: the actions always go through the staging buffer, where the controllers overwrite their agents' rows
@@ -2600,7 +2603,7 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
         HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
     if (scripted) {   // the scans are the last step's, the staged rows of scripted agents are replaced, external rows stay
         if (h->gap_specs > 0) gap_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions);
-        if (h->mppi.m > 0) {   // the planner behind the controllers: its agents' rows, from the live state
+        if (h->mppi.on.m > 0) {   // the planner behind the controllers: its agents' rows, from the live state
             TRY(mppi_upload_tracks(h));
             TRY(mppi_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions, nullptr));
         }
@@ -4292,7 +4295,7 @@ int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_
     const size_t N = (size_t)h->N;
     for (size_t i = 0; i < N; ++i)
         if (h_assign[i] < -1 || h_assign[i] >= n_specs) return fail(h, F110_ERR_INVALID, "controllers: assignment[%zu] = %d is outside -1..%d", i, h_assign[i], n_specs - 1);
-    for (int32_t n : h->mppi.agents)
+    for (int32_t n : h->mppi.on.agents)
         if (h_assign[n] != -1) return fail(h, F110_ERR_INVALID, "controllers: agent %d is driven by the armed planner (f110_mppi_set)", n);
     ENTER(h);
     if (!h->d_gap_specs) TRY(dmalloc(h, &h->d_gap_specs, (size_t)kGapMaxSpecs));
@@ -5440,7 +5443,7 @@ template <typename Job>
 static int job_unit_source(f110_sim *h, Scratch &sc, int slot, bool track, UnitRows &u, const double *h_params, Job &j)
 {
     const size_t M = u.cnt.size();
-    u.kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
+    u.kc = slot_consts(h, slot);
     double *dcols = nullptr, *dpar = nullptr;
     int32_t *dcnt = nullptr;
     ScanConst *dk = nullptr;
@@ -5781,6 +5784,82 @@ int f110_rollout_opp_device(f110_sim *h, const f110_rollout *spec, const f110_op
     });
 }
 
+// ---- the armed list (ArmedList): what f110_mppi_* and f110_pf_* share; `who` is "mppi" / "pf" -----------------------------------------
+// the arguments of f110_<who>_set: all present arms (F110_OK), anything less is refused, but for the disarm form: kArmedDisarm, and
+// the handle is entered for the caller to drop its feature (hipFree waits for the calls in flight that read its memory)
+constexpr int kArmedDisarm = 1;
+static int armed_form(f110_sim *h, const char *who, const void *spec, const int32_t *h_agents, int32_t m, const uint64_t *h_streams)
+{
+    if (spec && h_agents && h_streams) return F110_OK;
+    if (spec || h_agents || m != 0 || h_streams) return fail(h, F110_ERR_INVALID, "%s: a spec, the agents and their streams, or NULL, NULL, 0, NULL", who);
+    ENTER(h);
+    return kArmedDisarm;
+}
+
+// the list's refusals, the first bad index decides: 1 .. N indices within 0 .. N - 1, strictly ascending, and with `drives` (the planner's) none with a controller
+static int armed_check_list(f110_sim *h, const char *who, const int32_t *h_agents, int32_t m, bool drives)
+{
+    if (m < 1 || m > h->N) return fail(h, F110_ERR_INVALID, "%s: %d armed agents, but the handle has 1..%d", who, m, h->N);
+    for (int32_t i = 0; i < m; ++i) {
+        if (h_agents[i] < 0 || h_agents[i] >= h->N) return fail(h, F110_ERR_INVALID, "%s: agents[%d] = %d is outside 0..%d", who, i, h_agents[i], h->N - 1);
+        if (i > 0 && h_agents[i] <= h_agents[i - 1]) return fail(h, F110_ERR_INVALID, "%s: the agents are not strictly ascending at [%d]", who, i);
+        if (drives && !h->gap_assign_host.empty() && h->gap_assign_host[h_agents[i]] != -1)
+            return fail(h, F110_ERR_INVALID, "%s: agent %d has a follow-the-gap controller (f110_controllers_set)", who, h_agents[i]);
+    }
+    return F110_OK;
+}
+
+// a checked list into `a`, which the caller builds aside and moves in on success
+static int armed_upload(f110_sim *h, const char *who, ArmedList &a, const int32_t *h_agents, size_t M, const uint64_t *h_streams)
+{
+    TRY(dmalloc(h, &a.d_agents, M));
+    TRY(dmalloc(h, &a.d_streams, 4 * M));
+    if (hipMemcpy(a.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(a.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(h, F110_ERR_HIP, "%s: the upload failed", who);
+    a.agents.assign(h_agents, h_agents + M);
+    a.m = (int)M;
+    return F110_OK;
+}
+
+// the armed indices [i0, i0 + count) of one env block: the ascending list is split at the block's bounds
+static void armed_split(const ArmedList &a, int A, const EnvBlock &b, int32_t &i0, int32_t &count)
+{
+    const int32_t n0 = b.e0 * A, n1 = (b.e0 + b.count) * A;
+    i0 = (int32_t)(std::lower_bound(a.agents.begin(), a.agents.end(), n0) - a.agents.begin());
+    count = (int32_t)(std::lower_bound(a.agents.begin(), a.agents.end(), n1) - a.agents.begin()) - i0;
+}
+
+// the refusals that begin a call on an armed feature: it (`noun`: "planner" / "filter") is armed, and with `map` the map is set
+static int armed_ready(f110_sim *h, const char *who, const char *noun, const ArmedList &a, bool map)
+{
+    if (a.m == 0) return fail(h, F110_ERR_STATE, "%s: no %s is armed (f110_%s_set)", who, noun, who);
+    if (map && !h->has_map) return fail(h, F110_ERR_STATE, "%s: the map is not set", who);
+    return F110_OK;
+}
+
+// f110_<who>_get (put false: the host side is written) / _put: once the handle's work so far is done, every part the caller
+// asks for (host != null) and then the streams' words [m][4] are copied
+struct ArmedPart { const void *host; void *dev; size_t bytes; };
+static int armed_transfer(f110_sim *h, const ArmedList &a, bool put, const uint64_t *h_streams, std::initializer_list<ArmedPart> parts)
+{
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<ArmedPart> all(parts);
+    all.push_back({h_streams, a.d_streams, 4 * (size_t)a.m * sizeof(uint64_t)});
+    for (const ArmedPart &q : all)
+        if (q.host) HIPCHK(h, put ? hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice) : hipMemcpy(const_cast<void *>(q.host), q.dev, q.bytes, hipMemcpyDeviceToHost));
+    return F110_OK;
+}
+
+// what every job of a feature that draws shares: the generator's tables and the feature's jump constants [2][count]
+template <typename Job>
+static void job_rng_tables(const f110_sim *h, Job &j, const U128 *jump, int count)
+{
+    j.zk = h->d_zig_k, j.zw = h->d_zig_w, j.zf = h->d_zig_f;
+    j.jump_a = jump, j.jump_g = jump + count;
+}
+
 // ---- MPPI planner (f110_mppi_*, include/f110.h) -------------------------------------------------------------------------------------
 // the spec's refusals; on success the kernels' spec
 static int mppi_check_spec(f110_sim *h, const f110_mppi *p, MppiSpec &o)
@@ -5824,7 +5903,7 @@ static bool mppi_reads_tracks(const f110_sim::Mppi &p) { return mppi_needs_track
 
 static int mppi_upload_tracks(f110_sim *h)
 {
-    if (h->mppi.m > 0 && mppi_reads_tracks(h->mppi)) TRY(track_upload(h));
+    if (h->mppi.on.m > 0 && mppi_reads_tracks(h->mppi)) TRY(track_upload(h));
     return F110_OK;
 }
 
@@ -5832,10 +5911,9 @@ static int mppi_upload_tracks(f110_sim *h)
 static int mppi_ready(f110_sim *h)
 {
     const f110_sim::Mppi &p = h->mppi;
-    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
-    if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
-    if (mppi_needs_track(p.sp)) TRY(tracks_in_use(h, "mppi: w_progress or w_lat is set", &p.agents));   // (only the envs of the armed agents)
-    if (p.opp_on && p.opp.mode == OPP_TRACK) TRY(tracks_in_use(h, "mppi: the opponents follow the track", &p.agents));
+    TRY(armed_ready(h, "mppi", "planner", p.on, true));
+    if (mppi_needs_track(p.sp)) TRY(tracks_in_use(h, "mppi: w_progress or w_lat is set", &p.on.agents));   // (only the envs of the armed agents)
+    if (p.opp_on && p.opp.mode == OPP_TRACK) TRY(tracks_in_use(h, "mppi: the opponents follow the track", &p.on.agents));
     return F110_OK;
 }
 
@@ -5855,17 +5933,7 @@ static void mppi_launch(const MppiJob &j, hipStream_t st, const OppLane *opp = n
     hipLaunchKernelGGL(k_mppi_update, grid1d((size_t)j.count, 256 / gs), block, 0, st, j, gs);
 }
 
-// what every job of this handle shares: the generator's tables
-static void mppi_job_common(f110_sim *h, MppiJob &j)
-{
-    j.zk = h->d_zig_k;
-    j.zw = h->d_zig_w;
-    j.zf = h->d_zig_f;
-    j.jump_a = h->d_mppi_jump;
-    j.jump_g = h->d_mppi_jump + kMppiJumps;
-}
-
-// the armed planner over the agents of one env block: the ascending list is split at the block's bounds
+// the armed planner over the agents of one env block
 static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, float *d_info)
 {
     const f110_sim::Mppi &p = h->mppi;
@@ -5873,11 +5941,11 @@ static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, 
     const bool track = mppi_needs_track(p.sp);
     MppiJob j{};
     TRY(job_live_source(h, "mppi", track, j));
-    j.agents = p.d_agents;
+    j.agents = p.on.d_agents;
     j.step_count = h->dev.step_count;
-    mppi_job_common(h, j);
+    job_rng_tables(h, j, h->d_mppi_jump, kMppiJumps);
     j.nominal = p.d_nominal;
-    j.streams = p.d_streams;
+    j.streams = p.on.d_streams;
     j.V = p.d_V;
     j.cost = p.d_cost;
     j.end_xy = track ? p.d_end : nullptr;
@@ -5885,15 +5953,13 @@ static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, 
     j.info = d_info;
     j.sp_dev = p.d_spec;
     j.sp = p.sp;
-    const int32_t n0 = b.e0 * A, n1 = (b.e0 + b.count) * A;
-    j.i0 = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n0) - p.agents.begin());
-    j.count = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n1) - p.agents.begin()) - j.i0;
+    armed_split(p.on, A, b, j.i0, j.count);
     if (!p.opp_on) {
         mppi_launch(j, b.stream);
         return F110_OK;
     }
     // the opponent term: the block's armed agents' predictions from the live columns first (an env's cars are in one block)
-    opp_predict_launch(h, j, p.opp, p.sp.H, p.sp.repeat, j.i0, j.count, A - 1, p.d_agents.get(), nullptr, nullptr, p.d_opp_table.get(), b.stream);
+    opp_predict_launch(h, j, p.opp, p.sp.H, p.sp.repeat, j.i0, j.count, A - 1, p.on.d_agents.get(), nullptr, nullptr, p.d_opp_table.get(), b.stream);
     const OppLane lane{p.d_opp_table.get(), p.d_opp_spec.get(), nullptr, nullptr, A - 1, 0};
     mppi_launch(j, b.stream, &lane);
     return F110_OK;
@@ -5902,21 +5968,12 @@ static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, 
 int f110_mppi_set(f110_sim *h, const f110_mppi *spec, const int32_t *h_agents, int32_t m, const uint64_t *h_streams)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
-    if (!spec && !h_agents && m == 0 && !h_streams) {   // disarm
-        ENTER(h);
-        h->mppi = {};   // (hipFree waits for the calls in flight that read its memory)
-        return F110_OK;
-    }
-    if (!spec || !h_agents || !h_streams) return fail(h, F110_ERR_INVALID, "mppi: a spec, the agents and their streams, or NULL, NULL, 0, NULL");
+    const int form = armed_form(h, "mppi", spec, h_agents, m, h_streams);
+    if (form == kArmedDisarm) h->mppi = {};
+    if (form != F110_OK) return form == kArmedDisarm ? F110_OK : form;
     MppiSpec sp;
     TRY(mppi_check_spec(h, spec, sp));
-    if (m < 1 || m > h->N) return fail(h, F110_ERR_INVALID, "mppi: %d armed agents, but the handle has 1..%d", m, h->N);
-    for (int32_t i = 0; i < m; ++i) {
-        if (h_agents[i] < 0 || h_agents[i] >= h->N) return fail(h, F110_ERR_INVALID, "mppi: agents[%d] = %d is outside 0..%d", i, h_agents[i], h->N - 1);
-        if (i > 0 && h_agents[i] <= h_agents[i - 1]) return fail(h, F110_ERR_INVALID, "mppi: the agents are not strictly ascending at [%d]", i);
-        if (!h->gap_assign_host.empty() && h->gap_assign_host[h_agents[i]] != -1)
-            return fail(h, F110_ERR_INVALID, "mppi: agent %d has a follow-the-gap controller (f110_controllers_set)", h_agents[i]);
-    }
+    TRY(armed_check_list(h, "mppi", h_agents, m, true));
     if ((size_t)m * sp.K >= (size_t)1 << 31) return fail(h, F110_ERR_INVALID, "mppi: %d agents x %d candidates do not fit 31 bits", m, sp.K);
     ENTER(h);
     TRY(jump_ensure(h, h->d_mppi_jump, mppi_jump_table, kMppiJumps));
@@ -5924,21 +5981,16 @@ int f110_mppi_set(f110_sim *h, const f110_mppi *spec, const int32_t *h_agents, i
     const size_t M = (size_t)m, seq = (size_t)sp.H * 2, cands = M * sp.K;
     std::vector<double> nominal(M * seq);
     for (size_t q = 0; q < nominal.size(); ++q) nominal[q] = (q & 1) ? sp.v_init : 0.0;
-    TRY(dmalloc(h, &p.d_agents, M));
     TRY(dmalloc(h, &p.d_spec, 1));
     TRY(dmalloc(h, &p.d_nominal, M * seq));
-    TRY(dmalloc(h, &p.d_streams, 4 * M));
     TRY(dmalloc(h, &p.d_V, cands * seq));
     TRY(dmalloc(h, &p.d_cost, cands));
     if (mppi_needs_track(sp)) TRY(dmalloc(h, &p.d_end, 2 * cands));
-    if (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p.d_spec, &sp, sizeof sp, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p.d_nominal, nominal.data(), nominal.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(p.d_spec, &sp, sizeof sp, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_nominal, nominal.data(), nominal.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return fail(h, F110_ERR_HIP, "mppi: the upload failed");
     p.sp = sp;
-    p.agents.assign(h_agents, h_agents + m);
-    p.m = m;
+    TRY(armed_upload(h, "mppi", p.on, h_agents, M, h_streams));
     h->mppi = std::move(p);   // (the planner armed so far goes: hipFree waits for the calls in flight that read its memory)
     return F110_OK;
 }
@@ -5956,19 +6008,6 @@ int f110_mppi_device(f110_sim *h, double *d_actions, float *d_info)
     return F110_OK;
 }
 
-int f110_mppi_get(f110_sim *h, double *h_nominal, uint64_t *h_streams)
-{
-    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
-    const f110_sim::Mppi &p = h->mppi;
-    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
-    ENTER(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t M = (size_t)p.m;
-    if (h_nominal) HIPCHK(h, hipMemcpy(h_nominal, p.d_nominal, M * p.sp.H * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_streams) HIPCHK(h, hipMemcpy(h_streams, p.d_streams, 4 * M * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return F110_OK;
-}
-
 // a caller's nominal: finite and within the spec's bounds
 static int mppi_check_nominal(f110_sim *h, const MppiSpec &sp, const double *nominal, size_t rows)
 {
@@ -5980,19 +6019,19 @@ static int mppi_check_nominal(f110_sim *h, const MppiSpec &sp, const double *nom
     return F110_OK;
 }
 
-int f110_mppi_put(f110_sim *h, const double *h_nominal, const uint64_t *h_streams)
+// f110_mppi_get / f110_mppi_put
+static int mppi_state(f110_sim *h, const double *h_nominal, const uint64_t *h_streams, bool put)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     const f110_sim::Mppi &p = h->mppi;
-    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
-    const size_t M = (size_t)p.m;
-    if (h_nominal) TRY(mppi_check_nominal(h, p.sp, h_nominal, M));
-    ENTER(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h_nominal) HIPCHK(h, hipMemcpy(p.d_nominal, h_nominal, M * p.sp.H * 2 * sizeof(double), hipMemcpyHostToDevice));
-    if (h_streams) HIPCHK(h, hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice));
-    return F110_OK;
+    TRY(armed_ready(h, "mppi", "planner", p.on, false));
+    const size_t M = (size_t)p.on.m;
+    if (put && h_nominal) TRY(mppi_check_nominal(h, p.sp, h_nominal, M));
+    return armed_transfer(h, p.on, put, h_streams, {{h_nominal, p.d_nominal, M * p.sp.H * 2 * sizeof(double)}});
 }
+
+int f110_mppi_get(f110_sim *h, double *h_nominal, uint64_t *h_streams) { return mppi_state(h, h_nominal, h_streams, false); }
+int f110_mppi_put(f110_sim *h, const double *h_nominal, const uint64_t *h_streams) { return mppi_state(h, h_nominal, h_streams, true); }
 
 // f110_mppi_batch, and with `ou` f110_mppi_opp_batch
 static int mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const double *h_start, const double *h_params, const int32_t *h_fresh, int32_t m,
@@ -6034,7 +6073,7 @@ static int mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const do
     TRY(sc.up<float>(nullptr, 4 * M, &dinfo));
     if (track) TRY(sc.up<double>(nullptr, 2 * cands, &dend));
     j.step_count = dfresh;
-    mppi_job_common(h, j);
+    job_rng_tables(h, j, h->d_mppi_jump, kMppiJumps);
     j.nominal = dnom;
     j.streams = dstr;
     j.V = dV;
@@ -6101,14 +6140,13 @@ int f110_mppi_set_opponents(f110_sim *h, const f110_opponents *opp, double w_hit
     TRY(opp_check_weights(h, w_hit, w_near, near_ref, os));
     const int Ao = h->cfg.num_agents - 1;
     if (Ao > OPP_MAX) return fail(h, F110_ERR_INVALID, "mppi: %d opponents per agent, at most %d", Ao, (int)OPP_MAX);
-    if (p.m == 0) return fail(h, F110_ERR_STATE, "mppi: no planner is armed (f110_mppi_set)");
-    if (!h->has_map) return fail(h, F110_ERR_STATE, "mppi: the map is not set");
-    if (os.mode == OPP_TRACK) TRY(tracks_in_use(h, "mppi: the opponents follow the track", &p.agents));
+    TRY(armed_ready(h, "mppi", "planner", p.on, true));
+    if (os.mode == OPP_TRACK) TRY(tracks_in_use(h, "mppi: the opponents follow the track", &p.on.agents));
     ENTER(h);
     DevBuf<OppSpec> dspec;   // built aside: a failure leaves what is attached (if anything) as it is
     DevBuf<double> dtable;
     TRY(dmalloc(h, &dspec, 1));
-    if (Ao > 0) TRY(dmalloc(h, &dtable, (size_t)p.m * Ao * p.sp.H * 2));
+    if (Ao > 0) TRY(dmalloc(h, &dtable, (size_t)p.on.m * Ao * p.sp.H * 2));
     HIPCHK(h, hipMemcpy(dspec, &os, sizeof os, hipMemcpyHostToDevice));
     p.d_opp_spec = std::move(dspec);
     p.d_opp_table = std::move(dtable);
@@ -6186,23 +6224,12 @@ static void pf_launch(const PfJob &j, const ScanConst &k, hipStream_t st)
 // what every job of this handle shares: the generator's tables, the lidar's offset, the scan's width
 static void pf_job_common(f110_sim *h, PfJob &j)
 {
-    j.zk = h->d_zig_k;
-    j.zw = h->d_zig_w;
-    j.zf = h->d_zig_f;
-    j.jump_a = h->d_pf_jump;
-    j.jump_g = h->d_pf_jump + kPfJumps;
+    job_rng_tables(h, j, h->d_pf_jump, kPfJumps);
     j.lidar_dist = h->dev.lidar_dist;
     j.num_beams = h->cfg.num_beams;
 }
 
-static int pf_ready(f110_sim *h)
-{
-    if (h->pf.m == 0) return fail(h, F110_ERR_STATE, "pf: no filter is armed (f110_pf_set)");
-    if (!h->has_map) return fail(h, F110_ERR_STATE, "pf: the map is not set");
-    return F110_OK;
-}
-
-// the armed filter over the agents of one env block: the ascending list is split at the block's bounds
+// the armed filter over the agents of one env block
 static int pf_launch_armed(f110_sim *h, const EnvBlock &b, double *d_pose, float *d_info)
 {
     const f110_sim::Pf &p = h->pf;
@@ -6214,14 +6241,14 @@ static int pf_launch_armed(f110_sim *h, const EnvBlock &b, double *d_pose, float
     j.env_map = h->multi_map ? h->d_env_map : nullptr;
     j.A = A;
     j.N = h->N;
-    j.agents = p.d_agents;
+    j.agents = p.on.d_agents;
     j.px = h->dev.snap_pose;   // the post-step pose of the observation
     j.py = h->dev.snap_pose + N;
     j.pth = h->dev.snap_pose + 2 * N;
     j.scans = h->dev.scans;
     j.step_count = h->dev.step_count;
     pf_job_common(h, j);
-    j.streams = p.d_streams;
+    j.streams = p.on.d_streams;
     j.X_in = p.d_X[p.cur];
     j.X_out = p.d_X[p.cur ^ 1];
     j.W = p.d_W;
@@ -6233,9 +6260,7 @@ static int pf_launch_armed(f110_sim *h, const EnvBlock &b, double *d_pose, float
     j.pose = d_pose;
     j.info = d_info;
     j.sp = p.sp;
-    const int32_t n0 = b.e0 * A, n1 = (b.e0 + b.count) * A;
-    j.i0 = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n0) - p.agents.begin());
-    j.count = (int32_t)(std::lower_bound(p.agents.begin(), p.agents.end(), n1) - p.agents.begin()) - j.i0;
+    armed_split(p.on, A, b, j.i0, j.count);
     pf_launch(j, h->k, b.stream);
     return F110_OK;
 }
@@ -6243,27 +6268,18 @@ static int pf_launch_armed(f110_sim *h, const EnvBlock &b, double *d_pose, float
 int f110_pf_set(f110_sim *h, const f110_pf *spec, const int32_t *h_agents, int32_t m, const uint64_t *h_streams)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
-    if (!spec && !h_agents && m == 0 && !h_streams) {   // disarm
-        ENTER(h);
-        h->pf = {};   // (hipFree waits for the calls in flight that read its memory)
-        return F110_OK;
-    }
-    if (!spec || !h_agents || !h_streams) return fail(h, F110_ERR_INVALID, "pf: a spec, the agents and their streams, or NULL, NULL, 0, NULL");
+    const int form = armed_form(h, "pf", spec, h_agents, m, h_streams);
+    if (form == kArmedDisarm) h->pf = {};
+    if (form != F110_OK) return form == kArmedDisarm ? F110_OK : form;
     PfSpec sp;
     TRY(pf_check_spec(h, spec, sp));
-    if (m < 1 || m > h->N) return fail(h, F110_ERR_INVALID, "pf: %d armed agents, but the handle has 1..%d", m, h->N);
-    for (int32_t i = 0; i < m; ++i) {
-        if (h_agents[i] < 0 || h_agents[i] >= h->N) return fail(h, F110_ERR_INVALID, "pf: agents[%d] = %d is outside 0..%d", i, h_agents[i], h->N - 1);
-        if (i > 0 && h_agents[i] <= h_agents[i - 1]) return fail(h, F110_ERR_INVALID, "pf: the agents are not strictly ascending at [%d]", i);
-    }
+    TRY(armed_check_list(h, "pf", h_agents, m, false));   // (the filter drives nothing: a scripted car may be localised)
     TRY(pf_check_count(h, sp, m));
     ENTER(h);
     TRY(jump_ensure(h, h->d_pf_jump, pf_jump_table, kPfJumps));
     f110_sim::Pf p;   // built aside: a failure below leaves the filter that is armed (if any) as it is
     const size_t M = (size_t)m, parts = M * sp.P;
     std::vector<double> w(parts, 1.0 / (double)sp.P);
-    TRY(dmalloc(h, &p.d_agents, M));
-    TRY(dmalloc(h, &p.d_streams, 4 * M));
     TRY(dmalloc(h, &p.d_X[0], 3 * parts));
     TRY(dmalloc(h, &p.d_X[1], 3 * parts));
     TRY(dmalloc(h, &p.d_W, parts));
@@ -6272,16 +6288,13 @@ int f110_pf_set(f110_sim *h, const f110_pf *spec, const int32_t *h_agents, int32
     TRY(dmalloc(h, &p.d_logw, parts));
     TRY(dmalloc(h, &p.d_plan, M));
     TRY(dmalloc(h, &p.d_hdr, parts));
-    if (hipMemcpy(p.d_agents, h_agents, M * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p.d_W, w.data(), parts * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+    if (hipMemcpy(p.d_W, w.data(), parts * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(p.d_X[0], 0, 3 * parts * sizeof(double)) != hipSuccess ||
         hipMemset(p.d_X[1], 0, 3 * parts * sizeof(double)) != hipSuccess ||
         hipMemset(p.d_last, 0, 3 * M * sizeof(double)) != hipSuccess)
         return fail(h, F110_ERR_HIP, "pf: the upload failed");
     p.sp = sp;
-    p.agents.assign(h_agents, h_agents + m);
-    p.m = m;
+    TRY(armed_upload(h, "pf", p.on, h_agents, M, h_streams));
     h->pf = std::move(p);   // (the filter armed so far goes: hipFree waits for the calls in flight that read its memory)
     return F110_OK;
 }
@@ -6289,7 +6302,7 @@ int f110_pf_set(f110_sim *h, const f110_pf *spec, const int32_t *h_agents, int32
 int f110_pf_device(f110_sim *h, double *d_pose, float *d_info)
 {
     if (!h || !d_pose) return fail(h, F110_ERR_INVALID, "pf: null argument");
-    TRY(pf_ready(h));
+    TRY(armed_ready(h, "pf", "filter", h->pf.on, true));
     EnvBlocks w;   // behind a two-block step: each block's armed agents on the block's own stream (an agent reads and writes its own rows)
     TRY(env_blocks_follow(h, w));
     for (const EnvBlock &b : w) TRY(pf_launch_armed(h, b, d_pose, d_info));
@@ -6299,36 +6312,19 @@ int f110_pf_device(f110_sim *h, double *d_pose, float *d_info)
     return F110_OK;
 }
 
-int f110_pf_get(f110_sim *h, double *h_particles, double *h_weights, double *h_last, uint64_t *h_streams)
+// f110_pf_get / f110_pf_put
+static int pf_state(f110_sim *h, const double *h_particles, const double *h_weights, const double *h_last, const uint64_t *h_streams, bool put)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     const f110_sim::Pf &p = h->pf;
-    if (p.m == 0) return fail(h, F110_ERR_STATE, "pf: no filter is armed (f110_pf_set)");
-    ENTER(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t M = (size_t)p.m, parts = M * p.sp.P;
-    if (h_particles) HIPCHK(h, hipMemcpy(h_particles, p.d_X[p.cur], 3 * parts * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_weights) HIPCHK(h, hipMemcpy(h_weights, p.d_W, parts * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_last) HIPCHK(h, hipMemcpy(h_last, p.d_last, 3 * M * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_streams) HIPCHK(h, hipMemcpy(h_streams, p.d_streams, 4 * M * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return F110_OK;
+    TRY(armed_ready(h, "pf", "filter", p.on, false));
+    const size_t M = (size_t)p.on.m, cloud = M * p.sp.P * sizeof(double);
+    if (put) TRY(pf_check_cloud(h, p.sp, h_particles, h_weights, M));
+    return armed_transfer(h, p.on, put, h_streams, {{h_particles, p.d_X[p.cur], 3 * cloud}, {h_weights, p.d_W, cloud}, {h_last, p.d_last, 3 * M * sizeof(double)}});
 }
 
-int f110_pf_put(f110_sim *h, const double *h_particles, const double *h_weights, const double *h_last, const uint64_t *h_streams)
-{
-    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
-    const f110_sim::Pf &p = h->pf;
-    if (p.m == 0) return fail(h, F110_ERR_STATE, "pf: no filter is armed (f110_pf_set)");
-    const size_t M = (size_t)p.m, parts = M * p.sp.P;
-    TRY(pf_check_cloud(h, p.sp, h_particles, h_weights, M));
-    ENTER(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h_particles) HIPCHK(h, hipMemcpy(p.d_X[p.cur], h_particles, 3 * parts * sizeof(double), hipMemcpyHostToDevice));
-    if (h_weights) HIPCHK(h, hipMemcpy(p.d_W, h_weights, parts * sizeof(double), hipMemcpyHostToDevice));
-    if (h_last) HIPCHK(h, hipMemcpy(p.d_last, h_last, 3 * M * sizeof(double), hipMemcpyHostToDevice));
-    if (h_streams) HIPCHK(h, hipMemcpy(p.d_streams, h_streams, 4 * M * sizeof(uint64_t), hipMemcpyHostToDevice));
-    return F110_OK;
-}
+int f110_pf_get(f110_sim *h, double *h_particles, double *h_weights, double *h_last, uint64_t *h_streams) { return pf_state(h, h_particles, h_weights, h_last, h_streams, false); }
+int f110_pf_put(f110_sim *h, const double *h_particles, const double *h_weights, const double *h_last, const uint64_t *h_streams) { return pf_state(h, h_particles, h_weights, h_last, h_streams, true); }
 
 int f110_pf_batch(f110_sim *h, const f110_pf *spec, int32_t slot, const double *h_poses, const double *h_scans, const int32_t *h_fresh, int32_t m,
                   double *h_particles, double *h_weights, double *h_last, uint64_t *h_streams, double *h_pose, float *h_info, double *h_noise,
@@ -6347,7 +6343,7 @@ int f110_pf_batch(f110_sim *h, const f110_pf *spec, int32_t slot, const double *
     std::vector<double> cols(3 * M);
     for (size_t r = 0; r < M; ++r)
         for (int c = 0; c < 3; ++c) cols[(size_t)c * M + r] = h_poses[3 * r + c];
-    ScanConst kc = slot == 0 ? h->k : h->extra_maps[slot - 1].k;
+    ScanConst kc = slot_consts(h, slot);
     ENTER(h);
     TRY(jump_ensure(h, h->d_pf_jump, pf_jump_table, kPfJumps));
     Scratch sc(h);

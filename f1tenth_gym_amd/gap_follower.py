@@ -8,15 +8,12 @@ scans already are, and the other agents' actions stay the caller's.  This class 
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce, is_int
 
 TARGETS = {"center": _ffi.GAP_TARGET_CENTER, "furthest": _ffi.GAP_TARGET_FURTHEST}
 MAX_SPECS, MAX_SMOOTH, MAX_WINDOW = _ffi.GAP_MAX_SPECS, _ffi.GAP_MAX_SMOOTH, _ffi.GAP_MAX_WINDOW
 _FLOATS = ("range_clip", "bubble_radius", "gap_threshold", "steer_gain", "steer_max", "v_lo", "v_hi", "d_ref", "steer_slow", "v_turn",
            "v_blocked")
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 class GapFollower(object):
@@ -31,16 +28,16 @@ class GapFollower(object):
                  steer_max=0.4189, v_lo=1.5, v_hi=4.0, d_ref=8.0, steer_slow=0.2, v_turn=2.5, v_blocked=0.5, num_beams=None):
         if beams is not None:
             beams = tuple(beams)
-            if len(beams) != 2 or not all(_is_int(v) for v in beams) or not (beams == (0, 0) or 0 <= beams[0] < beams[1]):
+            if len(beams) != 2 or not all(is_int(v) for v in beams) or not (beams == (0, 0) or 0 <= beams[0] < beams[1]):
                 raise ValueError("beams must be (lo, hi) with 0 <= lo < hi, or (0, 0) for all, got %r" % (beams,))
             beams = (int(beams[0]), int(beams[1]))
             if beams[1] - beams[0] > MAX_WINDOW:
                 raise ValueError("a window of %d beams exceeds %d" % (beams[1] - beams[0], MAX_WINDOW))
-        if not _is_int(smooth) or not (1 <= smooth <= MAX_SMOOTH) or smooth % 2 == 0:
+        if not is_int(smooth) or not (1 <= smooth <= MAX_SMOOTH) or smooth % 2 == 0:
             raise ValueError("smooth must be an odd integer in 1 .. %d, got %r" % (MAX_SMOOTH, smooth))
         if beams is not None and beams != (0, 0) and smooth > beams[1] - beams[0]:
             raise ValueError("smooth = %d exceeds the %d beams of the window" % (smooth, beams[1] - beams[0]))
-        if target in (_ffi.GAP_TARGET_CENTER, _ffi.GAP_TARGET_FURTHEST) and _is_int(target):
+        if target in (_ffi.GAP_TARGET_CENTER, _ffi.GAP_TARGET_FURTHEST) and is_int(target):
             target = "center" if target == _ffi.GAP_TARGET_CENTER else "furthest"
         if target not in TARGETS:
             raise ValueError("target must be one of %s, got %r" % (sorted(TARGETS), target))
@@ -66,11 +63,7 @@ class GapFollower(object):
     @classmethod
     def coerce(cls, spec):
         """a GapFollower, or a dict of its keyword arguments"""
-        if isinstance(spec, GapFollower):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("a controller must be a GapFollower or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "a controller")
 
     def window(self, num_beams):
         """(lo, hi) at a scan of num_beams beams, checked against it"""
@@ -107,7 +100,7 @@ def coerce_scripted(scripted, num_envs, num_agents):
         assign = np.full((E, A), -1, dtype=np.int32)
         ctrls = []
         for slot, c in sorted(scripted.items()):
-            if not _is_int(slot) or not (0 <= slot < A):
+            if not is_int(slot) or not (0 <= slot < A):
                 raise ValueError("scripted: slot %r is not one of the %d cars of an env" % (slot, A))
             assign[:, slot] = len(ctrls)
             ctrls.append(GapFollower.coerce(c))

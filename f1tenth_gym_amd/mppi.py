@@ -10,15 +10,12 @@ settings (include/f110.h, f110_mppi) and needs no GPU.
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce, is_int
 
 MAX_K, MAX_H, MAX_REPEAT = _ffi.MPPI_MAX_K, _ffi.MPPI_MAX_H, _ffi.MPPI_MAX_REPEAT
 INFO = ("beta", "cost_nominal", "effective_samples", "best")   # the columns of the info output
 _FLOATS = ("sigma_steer", "sigma_speed", "steer_min", "steer_max", "speed_min", "speed_max", "lam", "w_dead", "w_clear", "w_progress",
            "w_lat", "clear_ref", "v_init")
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 class Mppi(object):
@@ -36,9 +33,9 @@ class Mppi(object):
                  steer_max=0.4189, speed_min=0.5, speed_max=7.0, lam=1.0, w_dead=10.0, w_clear=20.0, w_progress=10.0, w_lat=0.0,
                  clear_ref=0.6, v_init=2.0):
         for name, v, hi in (("k", k, MAX_K), ("horizon", horizon, MAX_H), ("repeat", repeat, MAX_REPEAT)):
-            if not _is_int(v) or not (1 <= v <= hi):
+            if not is_int(v) or not (1 <= v <= hi):
                 raise ValueError("%s must be an integer in 1 .. %d, got %r" % (name, hi, v))
-        if not isinstance(shift, (bool, np.bool_)) and not (_is_int(shift) and shift in (0, 1)):
+        if not isinstance(shift, (bool, np.bool_)) and not (is_int(shift) and shift in (0, 1)):
             raise ValueError("shift must be False or True, got %r" % (shift,))
         margin = float(margin)
         if np.isnan(margin):
@@ -70,11 +67,7 @@ class Mppi(object):
     @classmethod
     def coerce(cls, spec):
         """an Mppi, or a dict of its keyword arguments"""
-        if isinstance(spec, Mppi):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("a planner must be an Mppi or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "a planner", "an")
 
     @property
     def needs_track(self):
@@ -133,7 +126,7 @@ def split_scripted(scripted, planner=None):
         scripted = rest or None
     if len(found) > 1:
         raise ValueError("at most one Mppi planner per env object, got %d" % len(found))
-    if found and not _is_int(found[0][0]):
+    if found and not is_int(found[0][0]):
         raise ValueError("the planner's slot must be an integer, got %r" % (found[0][0],))
     return scripted, ((int(found[0][0]), found[0][1]) if found else None)
 

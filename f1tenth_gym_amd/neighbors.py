@@ -9,15 +9,12 @@ f110_neighbors), restates the rule in NumPy (compute) and needs no GPU.
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce, is_int
 
 # channel name -> bit number; the output holds the requested channels in this order whatever order they are asked for in
 CHANNELS = ("dx", "dy", "dist", "cos_dth", "sin_dth", "v_x", "v_y", "gap_s", "valid", "index")
 MAX_K = _ffi.NBR_MAX_K
 MAX_AGENTS = _ffi.NBR_MAX_AGENTS
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 class Neighbors(object):
@@ -27,7 +24,7 @@ class Neighbors(object):
     finite.  scale: {channel: divisor} (default 1.0), finite and non-zero.  The output is float32 [N][K][D], D = len(channels)."""
 
     def __init__(self, k=1, channels=('dx', 'dy'), max_range=np.inf, pad=0.0, scale=None):
-        if not _is_int(k) or not (1 <= k <= MAX_K):
+        if not is_int(k) or not (1 <= k <= MAX_K):
             raise ValueError("k must be an integer in 1 .. %d, got %r" % (MAX_K, k))
         if isinstance(channels, str):
             channels = (channels,)
@@ -58,11 +55,7 @@ class Neighbors(object):
     @classmethod
     def coerce(cls, spec):
         """a Neighbors, or a dict of its keyword arguments"""
-        if isinstance(spec, Neighbors):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("neighbors must be a Neighbors or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "neighbors")
 
     @property
     def channel_mask(self):

@@ -9,16 +9,13 @@ needs no GPU.
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce, is_int
 
 POOLS = {"min": _ffi.OBS_POOL_MIN, "mean": _ffi.OBS_POOL_MEAN, "center": _ffi.OBS_POOL_CENTER}
 # feature name -> bit number; the features follow the lidar values in this order whatever order they are asked for in
 FEATURES = ("vx", "steer", "yaw_rate", "slip", "collision", "lateral", "heading_error", "ds")
 TRACK_FEATURES = ("lateral", "heading_error", "ds")
 MAX_FRAMES, MAX_STACK = _ffi.OBS_MAX_FRAMES, _ffi.OBS_MAX_STACK
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 class ObsEncoder(object):
@@ -30,13 +27,13 @@ class ObsEncoder(object):
 
     def __init__(self, sectors=108, pool='min', beams=None, features=('vx', 'steer', 'yaw_rate', 'slip', 'collision'), frames=1,
                  range_clip=30.0, range_scale=30.0, scales=None, num_beams=None):
-        if not _is_int(sectors) or sectors < 0:
+        if not is_int(sectors) or sectors < 0:
             raise ValueError("sectors must be an integer >= 0, got %r" % (sectors,))
         if pool not in POOLS:
             raise ValueError("pool must be one of %s, got %r" % (sorted(POOLS), pool))
         if beams is not None:
             beams = tuple(beams)
-            if len(beams) != 2 or not all(_is_int(v) for v in beams) or not (0 <= beams[0] < beams[1]):
+            if len(beams) != 2 or not all(is_int(v) for v in beams) or not (0 <= beams[0] < beams[1]):
                 raise ValueError("beams must be (lo, hi) with 0 <= lo < hi, got %r" % (beams,))
             beams = (int(beams[0]), int(beams[1]))
         if isinstance(features, str):
@@ -47,7 +44,7 @@ class ObsEncoder(object):
                 raise ValueError("unknown feature %r (known: %s)" % (f, ", ".join(FEATURES)))
         if len(set(features)) != len(features):
             raise ValueError("a feature is listed twice: %r" % (features,))
-        if not _is_int(frames) or not (1 <= frames <= MAX_FRAMES):
+        if not is_int(frames) or not (1 <= frames <= MAX_FRAMES):
             raise ValueError("frames must be an integer in 1 .. %d, got %r" % (MAX_FRAMES, frames))
         range_clip, range_scale = float(range_clip), float(range_scale)
         if not (np.isfinite(range_clip) and range_clip > 0.0 and np.isfinite(range_scale) and range_scale > 0.0):
@@ -75,11 +72,7 @@ class ObsEncoder(object):
     @classmethod
     def coerce(cls, spec):
         """an ObsEncoder, or a dict of its keyword arguments"""
-        if isinstance(spec, ObsEncoder):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("obs_encoder must be an ObsEncoder or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "obs_encoder", "an")
 
     def check_beams(self, num_beams):
         """the beam range and the sector count against a scan of num_beams beams; returns (lo, hi)"""

@@ -11,6 +11,7 @@ import math
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce
 
 MODES = {"cv": _ffi.OPP_CV, "track": _ffi.OPP_TRACK}
 MAX_OPPONENTS = _ffi.OPP_MAX
@@ -52,11 +53,7 @@ class Opponents(object):
     @classmethod
     def coerce(cls, spec):
         """an Opponents, or a dict of its keyword arguments"""
-        if isinstance(spec, Opponents):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("opponents must be an Opponents or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "opponents", "an")
 
     @property
     def needs_track(self):

@@ -11,15 +11,12 @@ the env's map slot, and the estimate lands in device memory next to the observat
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce, is_int
 
 MAX_P, MAX_BEAMS = _ffi.PF_MAX_P, _ffi.PF_MAX_BEAMS
 INFO = ("effective_samples", "spread_xy", "err_xy", "resampled")   # the columns of the info output
 _INTS = ("particles", "n_beams", "beam_first", "beam_stride")
 _FLOATS = ("sigma_x", "sigma_y", "sigma_theta", "init_x", "init_y", "init_theta", "sigma_hit", "clip", "squash", "resample_frac")
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 class ParticleFilter(object):
@@ -36,7 +33,7 @@ class ParticleFilter(object):
                  init_y=0.1, init_theta=0.05, sigma_hit=0.1, clip=3.0, squash=8.0, resample_frac=0.5):
         ints = dict(particles=particles, n_beams=n_beams, beam_first=beam_first, beam_stride=beam_stride)
         for name, lo, hi in (("particles", 1, MAX_P), ("n_beams", 1, MAX_BEAMS), ("beam_first", 0, 2 ** 31 - 1), ("beam_stride", 1, 2 ** 31 - 1)):
-            if not _is_int(ints[name]) or not (lo <= ints[name] <= hi):
+            if not is_int(ints[name]) or not (lo <= ints[name] <= hi):
                 raise ValueError("%s must be an integer in %d .. %d, got %r" % (name, lo, hi, ints[name]))
         if beam_first + (n_beams - 1) * beam_stride > 2 ** 31 - 1:
             raise ValueError("the last beam does not fit 31 bits")
@@ -62,11 +59,7 @@ class ParticleFilter(object):
     @classmethod
     def coerce(cls, spec):
         """a ParticleFilter, or a dict of its keyword arguments"""
-        if isinstance(spec, ParticleFilter):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("a filter must be a ParticleFilter or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "a filter")
 
     @property
     def beams(self):
@@ -105,7 +98,7 @@ def split_filter(particle_filter):
     if not isinstance(particle_filter, dict) or len(particle_filter) != 1:
         raise ValueError("particle_filter must be {slot: ParticleFilter} with one entry (one spec per handle), got %r" % (particle_filter,))
     (slot, pf), = particle_filter.items()
-    if not _is_int(slot):
+    if not is_int(slot):
         raise ValueError("the filter's slot must be an integer, got %r" % (slot,))
     return int(slot), ParticleFilter.coerce(pf)
 

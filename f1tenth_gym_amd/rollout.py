@@ -10,6 +10,7 @@ holds and validates the settings (include/f110.h, f110_rollout) and needs no GPU
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce, is_int
 
 # channel name -> bit number; the output holds the requested channels in this order whatever order they are asked for in
 CHANNELS = ("end_x", "end_y", "end_cos", "end_sin", "end_v", "end_yaw_rate", "alive", "min_clear", "progress", "end_lat")
@@ -17,10 +18,6 @@ FRAMES = {"ego": _ffi.ROLL_FRAME_EGO, "map": _ffi.ROLL_FRAME_MAP}
 LAYOUTS = {"shared": _ffi.ROLL_SHARED, "per_agent": _ffi.ROLL_PER_AGENT}
 MAX_K, MAX_H, MAX_REPEAT = _ffi.ROLL_MAX_K, _ffi.ROLL_MAX_H, _ffi.ROLL_MAX_REPEAT
 TRAJ_CHANNELS = CHANNELS[:4]
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 class Rollout(object):
@@ -35,7 +32,7 @@ class Rollout(object):
     def __init__(self, k=8, horizon=8, repeat=1, channels=('alive', 'min_clear'), margin=0.0, frame='ego', scale=None, layout='shared',
                  traj=False):
         for name, v, hi in (("k", k, MAX_K), ("horizon", horizon, MAX_H), ("repeat", repeat, MAX_REPEAT)):
-            if not _is_int(v) or not (1 <= v <= hi):
+            if not is_int(v) or not (1 <= v <= hi):
                 raise ValueError("%s must be an integer in 1 .. %d, got %r" % (name, hi, v))
         if isinstance(channels, str):
             channels = (channels,)
@@ -72,11 +69,7 @@ class Rollout(object):
     @classmethod
     def coerce(cls, spec):
         """a Rollout, or a dict of its keyword arguments"""
-        if isinstance(spec, Rollout):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("a rollout must be a Rollout or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "a rollout")
 
     @property
     def channel_mask(self):

@@ -9,15 +9,12 @@ holds and validates the settings (include/f110.h, f110_track_preview) and needs 
 import numpy as np
 
 from . import _ffi
+from ._spec import coerce, is_int
 
 # channel name -> bit number; the output holds the requested channels in this order whatever order they are asked for in
 CHANNELS = ("x", "y", "tan_x", "tan_y", "attr0", "attr1", "attr2", "attr3")
 FRAMES = {"ego": _ffi.PREVIEW_FRAME_EGO, "world": _ffi.PREVIEW_FRAME_WORLD}
 MAX_POINTS = _ffi.PREVIEW_MAX_POINTS
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 class TrackPreview(object):
@@ -27,7 +24,7 @@ class TrackPreview(object):
     {channel: divisor} (default 1.0), finite and non-zero.  The output is float32 [N][P][D], D = len(channels)."""
 
     def __init__(self, points=8, offset=0.5, spacing=0.5, channels=('x', 'y'), frame='ego', scale=None):
-        if not _is_int(points) or not (1 <= points <= MAX_POINTS):
+        if not is_int(points) or not (1 <= points <= MAX_POINTS):
             raise ValueError("points must be an integer in 1 .. %d, got %r" % (MAX_POINTS, points))
         if isinstance(channels, str):
             channels = (channels,)
@@ -60,11 +57,7 @@ class TrackPreview(object):
     @classmethod
     def coerce(cls, spec):
         """a TrackPreview, or a dict of its keyword arguments"""
-        if isinstance(spec, TrackPreview):
-            return spec
-        if isinstance(spec, dict):
-            return cls(**spec)
-        raise TypeError("track_preview must be a TrackPreview or a dict of its settings, got %r" % (spec,))
+        return coerce(cls, spec, "track_preview")
 
     @property
     def channel_mask(self):
