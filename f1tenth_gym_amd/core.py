@@ -444,6 +444,59 @@ class BatchSim(object):
         ob = Obstacles.coerce(obstacles)
         check(_ffi.lib().f110_set_map_obstacles(self._h, int(slot), ob.structs(), len(ob)), self._h)
 
+    # ---- a slot's centreline loop, extracted on the device (extension)
+    def slot_frame(self, slot=0):
+        """(res, ox, oy, oc, os) of a map slot as the library holds them"""
+        out = np.empty(5)
+        check(_ffi.lib().f110_slot_frame(self._h, int(slot), dptr(out)), self._h)
+        return tuple(float(v) for v in out)
+
+    def centerline_cells(self, slot=0, seed=(0.0, 0.0), heading=None, max_passes=None):
+        """f110_map_centerline: the slot's centreline loop as ordered table cells int32 [n][2] (r, c), T at each [n] (the half
+        width, metres) and the cells the three stages deleted int64 [3].  The seed is a world point on the track's free region;
+        heading (rad) picks the direction of travel, None means counter-clockwise.  Refusals raise ValueError (arguments, the
+        seed) or F110LibraryError (no loop, not a simple loop, not converged within max_passes)."""
+        h, w = C.c_int32(), C.c_int32()
+        check(_ffi.lib().f110_slot_shape(self._h, int(slot), C.byref(h), C.byref(w)), self._h)
+        cap = 2 * (int(h.value) + int(w.value)) + 64
+        deleted = np.zeros(3, dtype=np.int64)
+        n = C.c_int32(0)
+        for _ in range(2):   # a second call only when the first guess of the loop's length was too small: n says how much it takes
+            cells, hw = np.empty((cap, 2), dtype=np.int32), np.empty(cap)
+            rc = _ffi.lib().f110_map_centerline(self._h, int(slot), float(seed[0]), float(seed[1]), int(heading is not None),
+                                                0.0 if heading is None else float(heading), 0 if max_passes is None else int(max_passes),
+                                                _ffi.i32ptr(cells), dptr(hw), cap, C.byref(n), deleted.ctypes.data_as(_ffi._i64p))
+            if rc == _ffi.ERR_INVALID and n.value > cap:
+                cap = int(n.value)
+                continue
+            break
+        check(rc, self._h)
+        return cells[:n.value].copy(), hw[:n.value].copy(), deleted
+
+    def map_skeleton(self, slot=0, max_passes=None):
+        """f110_map_skeleton (debug): the final mask of the thinning rule uint8 [H][W] (row 0 = bottom) and the three totals"""
+        h, w = C.c_int32(), C.c_int32()
+        check(_ffi.lib().f110_slot_shape(self._h, int(slot), C.byref(h), C.byref(w)), self._h)
+        mask, deleted = np.empty((h.value, w.value), dtype=np.uint8), np.zeros(3, dtype=np.int64)
+        check(_ffi.lib().f110_map_skeleton(self._h, int(slot), 0 if max_passes is None else int(max_passes), mask.ctypes.data_as(_ffi._u8p),
+                                           deleted.ctypes.data_as(_ffi._i64p)), self._h)
+        return mask, deleted
+
+    def centerline_times(self):
+        """f110_map_centerline_times: {stage: ms} of the last centerline_cells / map_skeleton call, by the host's clock"""
+        ms = np.zeros(5)
+        check(_ffi.lib().f110_map_centerline_times(self._h, dptr(ms)), self._h)
+        return dict(thinning=float(ms[1]), staircase=float(ms[2]), pruning=float(ms[3]), host=float(ms[4]))
+
+    def centerline(self, slot=0, seed=(0.0, 0.0), heading=None, spacing=0.2, smooth=1.0, max_passes=None, return_cells=False):
+        """the slot's centreline as a closed Track with the attribute columns half_width and kappa: the loop of cells from the
+        device (centerline_cells), then smoothed over `smooth` metres of arc and resampled every `spacing` metres on the host
+        (f1tenth_gym_amd/centerline.py states the steps).  return_cells: -> (track, cells, half_width at the cells, deleted)."""
+        from .centerline import track_from_cells
+        cells, hw, deleted = self.centerline_cells(slot, seed, heading, max_passes)
+        track = track_from_cells(cells, hw, self.slot_frame(slot), spacing=spacing, smooth=smooth)
+        return (track, cells, hw, deleted) if return_cells else track
+
     def map_table_address(self, slot=0):
         """(device address of the slot's table cell [0][0], its row pitch in bytes): what the kernels read"""
         p, rb = C.c_void_p(), C.c_int32()

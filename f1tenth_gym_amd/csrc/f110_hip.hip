@@ -116,6 +116,15 @@ struct f110_sim {
         DevBuf<ObstBox> boxes;
         DevBuf<double> oob;
     } obst;
+    // f110_map_centerline / f110_map_skeleton: the free mask and the two planes the passes ping-pong between ([H][ceil(W / 64)]
+    // words each), the per-pass deletion counters, the loop's cells and their table values (grow-only)
+    struct CenterlineScratch {
+        DevBuf<uint64_t> free_plane, a, b;
+        DevBuf<unsigned long long> deleted;
+        DevBuf<int32_t> cells;
+        DevBuf<double> values;
+        double stage_ms[5] = {0, 0, 0, 0, 0};   // the last call's host time per stage (f110_map_centerline_times)
+    } cl;
     DevBuf<int32_t> d_env_map;
     DevBuf<uint32_t> d_scan_order;      // [N] agents sorted by map slot (nullptr while every env is on one slot)
     bool multi_map = false;
@@ -1566,6 +1575,305 @@ int f110_get_slot_dt(f110_sim *h, int32_t slot, double *out)
     const size_t row = (size_t)k.width * sizeof(double);
     HIPCHK(h, hipMemcpy2DAsync(out, row, k.table_rm, (size_t)k.row_bytes, row, (size_t)k.height, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- centreline extraction (include/f110.h) ----------------------------------------------------------------------
+constexpr int kClPoll = 16;   // passes between two looks at the deletion counters (the result does not depend on it)
+
+static int centerline_slot_check(f110_sim *h, const char *who, int slot)
+{
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "%s: slot %d, but %d maps are registered", who, slot, 1 + (int)h->extra_maps.size());
+    const ScanConst &k = slot_consts(h, slot);
+    if (k.height > 16384 || k.width > 16384) return fail(h, F110_ERR_INVALID, "%s: the map is %d x %d cells, at most 16384 a side are supported", who, k.height, k.width);
+    return F110_OK;
+}
+
+// Steps 1 - 3 of the rule on the whole free mask of the slot, everything on the main stream (the caller went through ENTER).  On
+// success the final mask is h->cl.a or .b (*final_plane), the free mask h->cl.free_plane, and deleted [3] holds the cells each
+// stage deleted.  Every pass adds to the counter of its place in the current group of kClPoll passes; the host reads a group's
+// counters at once: the first pass that deleted nothing ends the stage, the passes behind it in the group changed nothing.
+static int centerline_thin(f110_sim *h, const char *who, int slot, int max_passes, int64_t *deleted, const uint64_t **final_plane)
+{
+    const ScanConst &k = slot_consts(h, slot);
+    const int H = k.height, W = k.width, Ww = (W + 63) / 64;
+    const size_t nw = (size_t)H * Ww;
+    if (max_passes <= 0) max_passes = 4 * (H + W);
+    f110_sim::CenterlineScratch &sc = h->cl;
+    TRY(dgrow(h, sc.free_plane, nw));
+    TRY(dgrow(h, sc.a, nw));
+    TRY(dgrow(h, sc.b, nw));
+    TRY(dgrow(h, sc.deleted, (size_t)kClPoll));
+    hipLaunchKernelGGL(k_cl_free, dim3((unsigned)((Ww + 3) / 4), (unsigned)H), dim3(256), 0, h->stream, k.table_rm, k.row_bytes, H, W, Ww, sc.free_plane.get());
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(sc.a, sc.free_plane, nw * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+    uint64_t *cur = sc.a, *oth = sc.b;
+    const dim3 grid = grid1d(nw, 256);
+    // every stage ends with a wait for its counters: the host's clock between the waits is what the stage cost the caller
+    auto t_prev = std::chrono::steady_clock::now();
+    auto lap = [&](int i) {
+        const auto t = std::chrono::steady_clock::now();
+        sc.stage_ms[i] = std::chrono::duration<double, std::milli>(t - t_prev).count();
+        t_prev = t;
+    };
+    for (double &v : sc.stage_ms) v = 0.0;
+    unsigned long long cnt[kClPoll];
+    int64_t del[3] = {0, 0, 0};
+    // stage 0: thinning, a pass = the pair of sub-passes (cur -> oth -> cur); stage 2: pruning, a pass swaps the planes
+    for (int stage = 0; stage < 3; ++stage) {
+        if (stage == 1) {   // the four staircase passes, once each
+            HIPCHK(h, hipMemsetAsync(sc.deleted, 0, sizeof(unsigned long long), h->stream));
+            for (int q = 0; q < 4; ++q) {
+                hipLaunchKernelGGL(k_cl_stair, grid, dim3(256), 0, h->stream, q, (const uint64_t *)cur, oth, H, Ww, sc.deleted.get());
+                std::swap(cur, oth);
+            }
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(cnt, sc.deleted, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            del[1] = (int64_t)cnt[0];
+            lap(2);
+            continue;
+        }
+        bool done = false;
+        for (int used = 0; !done;) {
+            if (used == max_passes)
+                return fail(h, F110_ERR_STATE, "%s: %s has not converged within max_passes = %d on the %d x %d map of slot %d", who, stage == 0 ? "thinning" : "pruning",
+                            max_passes, H, W, slot);
+            const int m = std::min(kClPoll, max_passes - used);
+            HIPCHK(h, hipMemsetAsync(sc.deleted, 0, (size_t)m * sizeof(unsigned long long), h->stream));
+            for (int j = 0; j < m; ++j) {
+                if (stage == 0) {
+                    hipLaunchKernelGGL(k_cl_thin, grid, dim3(256), 0, h->stream, 0, (const uint64_t *)cur, oth, H, Ww, sc.deleted.get() + j);
+                    hipLaunchKernelGGL(k_cl_thin, grid, dim3(256), 0, h->stream, 1, (const uint64_t *)oth, cur, H, Ww, sc.deleted.get() + j);
+                } else {
+                    hipLaunchKernelGGL(k_cl_prune, grid, dim3(256), 0, h->stream, (const uint64_t *)cur, oth, H, Ww, sc.deleted.get() + j);
+                    std::swap(cur, oth);
+                }
+            }
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(cnt, sc.deleted, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (int j = 0; j < m && !done; ++j) {
+                del[stage] += (int64_t)cnt[j];
+                done = cnt[j] == 0;
+            }
+            used += m;
+        }
+        lap(stage == 0 ? 1 : 3);   // (thinning's figure includes the free mask's kernel and copy in front of it)
+    }
+    for (int i = 0; i < 3; ++i) deleted[i] = del[i];
+    *final_plane = cur;
+    return F110_OK;
+}
+
+// the neighbours P2 .. P9 of the rule as (row, column) offsets
+static const int kClDr[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, kClDc[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+
+struct ClPlane {
+    std::vector<uint64_t> words;
+    int H = 0, W = 0, Ww = 0;
+    bool at(int r, int c) const { return r >= 0 && r < H && c >= 0 && c < W && ((words[(size_t)r * Ww + (c >> 6)] >> (c & 63)) & 1u); }
+    void set(int r, int c) { words[(size_t)r * Ww + (c >> 6)] |= 1ull << (c & 63); }
+};
+
+// Steps 4 and 5 of the rule on the host.  cells: the ordered loop as (r, c) pairs.  0 ok, 1 no loop reachable, 2 not a simple
+// loop (`members` cells are connected to the start cell (sr, sc), `branching` of them have more than two neighbours).
+static int centerline_trace(const ClPlane &free_mask, const ClPlane &fin, int seed_r, int seed_c, bool has_heading, double hx, double hy, std::vector<int32_t> &cells,
+                            int &sr, int &sc, size_t &members, size_t &branching)
+{
+    const int H = fin.H, W = fin.W;
+    ClPlane seen;
+    seen.H = H, seen.W = W, seen.Ww = fin.Ww;
+    seen.words.assign(fin.words.size(), 0);
+    std::vector<int32_t> queue;
+    queue.push_back(seed_r * W + seed_c);
+    seen.set(seed_r, seed_c);
+    sr = sc = -1;
+    for (size_t q = 0; q < queue.size(); ++q) {
+        const int r = queue[q] / W, c = queue[q] % W;
+        if (fin.at(r, c)) {
+            sr = r, sc = c;
+            break;
+        }
+        for (int i = 0; i < 8; ++i) {
+            const int rr = r + kClDr[i], cc = c + kClDc[i];
+            if (free_mask.at(rr, cc) && !seen.at(rr, cc)) {
+                seen.set(rr, cc);
+                queue.push_back(rr * W + cc);
+            }
+        }
+    }
+    if (sr < 0) return 1;
+    // the set cells connected to the start, and how many neighbours each has
+    seen.words.assign(fin.words.size(), 0);
+    queue.clear();
+    queue.push_back(sr * W + sc);
+    seen.set(sr, sc);
+    branching = 0;
+    bool simple = true;
+    for (size_t q = 0; q < queue.size(); ++q) {
+        const int r = queue[q] / W, c = queue[q] % W;
+        int deg = 0;
+        for (int i = 0; i < 8; ++i) {
+            const int rr = r + kClDr[i], cc = c + kClDc[i];
+            if (!fin.at(rr, cc)) continue;
+            ++deg;
+            if (!seen.at(rr, cc)) {
+                seen.set(rr, cc);
+                queue.push_back(rr * W + cc);
+            }
+        }
+        if (deg > 2) ++branching;
+        if (deg != 2) simple = false;
+    }
+    members = queue.size();
+    if (!simple) return 2;
+    int first = -1, second = -1;
+    for (int i = 0; i < 8; ++i)
+        if (fin.at(sr + kClDr[i], sc + kClDc[i])) (first < 0 ? first : second) = i;
+    if (has_heading) {
+        const double d1 = (double)kClDc[first] * hx + (double)kClDr[first] * hy, d2 = (double)kClDc[second] * hx + (double)kClDr[second] * hy;
+        if (d2 > d1) first = second;
+    }
+    cells.clear();
+    cells.push_back(sr);
+    cells.push_back(sc);
+    int pr = sr, pc = sc, r = sr + kClDr[first], c = sc + kClDc[first];
+    while (!(r == sr && c == sc)) {
+        if (cells.size() / 2 >= members) return 2;   // (cannot happen on cells of degree two; never walk on)
+        cells.push_back(r);
+        cells.push_back(c);
+        int nr = -1, nc = -1;
+        for (int i = 0; i < 8; ++i) {
+            const int rr = r + kClDr[i], cc = c + kClDc[i];
+            if (fin.at(rr, cc) && !(rr == pr && cc == pc)) {
+                nr = rr, nc = cc;
+                break;
+            }
+        }
+        pr = r, pc = c, r = nr, c = nc;
+    }
+    if (cells.size() / 2 != members) return 2;
+    if (!has_heading) {   // counter-clockwise: the signed area in (column, row) has the sign of the world's, the frame being a rotation
+        const size_t n = members;
+        long long area2 = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t j = i + 1 == n ? 0 : i + 1;
+            area2 += (long long)cells[2 * i + 1] * cells[2 * j] - (long long)cells[2 * j + 1] * cells[2 * i];
+        }
+        if (area2 < 0)
+            for (size_t i = 1, j = n - 1; i < j; ++i, --j) {
+                std::swap(cells[2 * i], cells[2 * j]);
+                std::swap(cells[2 * i + 1], cells[2 * j + 1]);
+            }
+    }
+    return 0;
+}
+
+static int centerline_fetch(f110_sim *h, const uint64_t *d_plane, const ScanConst &k, ClPlane &out)
+{
+    out.H = k.height, out.W = k.width, out.Ww = (k.width + 63) / 64;
+    out.words.resize((size_t)out.H * out.Ww);
+    HIPCHK(h, hipMemcpyAsync(out.words.data(), d_plane, out.words.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    return F110_OK;
+}
+
+int f110_map_centerline(f110_sim *h, int32_t slot, double seed_x, double seed_y, int32_t has_heading, double seed_theta, int32_t max_passes, int32_t *h_cells,
+                        double *h_half_width, int32_t cap, int32_t *n, int64_t *h_deleted)
+{
+    static const char *const who = "f110_map_centerline";
+    if (n) *n = 0;
+    if (!h || !h_cells || !h_half_width || !n || !h_deleted) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    if (cap < 0) return fail(h, F110_ERR_INVALID, "%s: cap = %d", who, cap);
+    TRY(centerline_slot_check(h, who, slot));
+    if (!std::isfinite(seed_x) || !std::isfinite(seed_y) || (has_heading && !std::isfinite(seed_theta)))
+        return fail(h, F110_ERR_INVALID, "%s: the seed (%g, %g%s) is not finite", who, seed_x, seed_y, has_heading ? ", heading" : "");
+    const ScanConst &k = slot_consts(h, slot);
+    int seed_r = 0, seed_c = 0;
+    if (!cl_seed_cell(seed_x, seed_y, k.res, k.orig_x, k.orig_y, k.orig_c, k.orig_s, k.height, k.width, seed_r, seed_c))
+        return fail(h, F110_ERR_INVALID, "%s: the seed (%g, %g) lies outside the %d x %d table of slot %d", who, seed_x, seed_y, k.height, k.width, slot);
+    ENTER(h);
+    double seed_t = 0.0;   // one table value comes back before anything is launched or allocated
+    HIPCHK(h, hipMemcpyAsync(&seed_t, reinterpret_cast<const char *>(k.table_rm) + (size_t)seed_r * (size_t)k.row_bytes + (size_t)seed_c * 8, sizeof(double),
+                             hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!(seed_t > 0.0)) return fail(h, F110_ERR_INVALID, "%s: the seed (%g, %g) is cell (%d, %d) of slot %d, which is not free", who, seed_x, seed_y, seed_r, seed_c, slot);
+    int64_t deleted[3];
+    const uint64_t *d_final = nullptr;
+    TRY(centerline_thin(h, who, slot, max_passes, deleted, &d_final));
+    const auto t_host = std::chrono::steady_clock::now();
+    ClPlane free_mask, fin;
+    TRY(centerline_fetch(h, h->cl.free_plane, k, free_mask));
+    TRY(centerline_fetch(h, d_final, k, fin));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<int32_t> cells;
+    int sr, sc;
+    size_t members = 0, branching = 0;
+    double hx = 0.0, hy = 0.0;
+    if (has_heading) {   // the heading rotated into the table frame
+        const double ct = std::cos(seed_theta), st = std::sin(seed_theta);
+        hx = ct * k.orig_c + st * k.orig_s;
+        hy = -ct * k.orig_s + st * k.orig_c;
+    }
+    const int what = centerline_trace(free_mask, fin, seed_r, seed_c, has_heading != 0, hx, hy, cells, sr, sc, members, branching);
+    if (what == 1) return fail(h, F110_ERR_STATE, "%s: no loop is reachable from the seed (%g, %g) on slot %d: its free region thins to nothing", who, seed_x, seed_y, slot);
+    if (what == 2)
+        return fail(h, F110_ERR_STATE, "%s: not a simple loop: %zu of the %zu cells connected to the start cell (%d, %d) have more than two neighbours (islands and "
+                    "several loops are not supported)", who, branching, members, sr, sc);
+    const int32_t count = (int32_t)(cells.size() / 2);
+    *n = count;
+    if (count > cap) return fail(h, F110_ERR_INVALID, "%s: the loop has %d cells, cap = %d", who, count, cap);
+    TRY(dgrow(h, h->cl.cells, cells.size()));
+    TRY(dgrow(h, h->cl.values, (size_t)count));
+    HIPCHK(h, hipMemcpyAsync(h->cl.cells, cells.data(), cells.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_cl_gather, grid1d((size_t)count, 256), dim3(256), 0, h->stream, k.table_rm, k.row_bytes, (const int32_t *)h->cl.cells.get(), count, h->cl.values.get());
+    HIPCHK(h, hipGetLastError());
+    std::vector<double> values((size_t)count);
+    HIPCHK(h, hipMemcpyAsync(values.data(), h->cl.values, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::memcpy(h_cells, cells.data(), cells.size() * sizeof(int32_t));
+    std::memcpy(h_half_width, values.data(), values.size() * sizeof(double));
+    for (int i = 0; i < 3; ++i) h_deleted[i] = deleted[i];
+    h->cl.stage_ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();
+    return F110_OK;
+}
+
+int f110_map_centerline_times(f110_sim *h, double *ms)
+{
+    if (!h || !ms) return fail(h, F110_ERR_INVALID, "f110_map_centerline_times: null argument");
+    std::memcpy(ms, h->cl.stage_ms, sizeof h->cl.stage_ms);
+    return F110_OK;
+}
+
+int f110_slot_frame(f110_sim *h, int32_t slot, double *frame)
+{
+    if (!h || !frame) return fail(h, F110_ERR_INVALID, "f110_slot_frame: null argument");
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (slot < 0 || slot > (int)h->extra_maps.size()) return fail(h, F110_ERR_INVALID, "f110_slot_frame: slot %d, but %d maps are registered", slot, 1 + (int)h->extra_maps.size());
+    const ScanConst &k = slot_consts(h, slot);
+    const double v[5] = {k.res, k.orig_x, k.orig_y, k.orig_c, k.orig_s};
+    std::memcpy(frame, v, sizeof v);
+    return F110_OK;
+}
+
+int f110_map_skeleton(f110_sim *h, int32_t slot, int32_t max_passes, uint8_t *h_mask, int64_t *h_deleted)
+{
+    static const char *const who = "f110_map_skeleton";
+    if (!h || !h_mask) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    TRY(centerline_slot_check(h, who, slot));
+    ENTER(h);
+    const ScanConst &k = slot_consts(h, slot);
+    int64_t deleted[3];
+    const uint64_t *d_final = nullptr;
+    TRY(centerline_thin(h, who, slot, max_passes, deleted, &d_final));
+    ClPlane fin;
+    TRY(centerline_fetch(h, d_final, k, fin));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int r = 0; r < fin.H; ++r)
+        for (int c = 0; c < fin.W; ++c) h_mask[(size_t)r * fin.W + c] = fin.at(r, c) ? 1 : 0;
+    if (h_deleted)
+        for (int i = 0; i < 3; ++i) h_deleted[i] = deleted[i];
     return F110_OK;
 }
 

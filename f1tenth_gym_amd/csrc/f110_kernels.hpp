@@ -3402,6 +3402,64 @@ __global__ void __launch_bounds__(256) k_obst_rows(const uint32_t *__restrict__ 
     *out = obst_value(bv, best, res);
 }
 
+// ---- centreline extraction (include/f110.h, f110_map_centerline) --------------------------------------------------
+// The mask is a bit plane [H][Ww] of 64-bit words, Ww = ceil(W / 64): bit b of word w is column 64 w + b, bits from column W on
+// are 0 in every plane.  The per-word decisions are f110_math.hpp's cl_*.
+
+// The free mask of a slot's table: one wave per word, lane b tests T[r][64 w + b] > 0 and the wave's ballot IS the word.
+// blockIdx.y = row, a workgroup of four waves takes four consecutive words.
+__global__ void __launch_bounds__(256) k_cl_free(const double *__restrict__ table, int row_bytes, int H, int W, int Ww, uint64_t *__restrict__ plane)
+{
+    const int r = blockIdx.y, w = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const int c = w * 64 + lane;
+    bool free_cell = false;
+    if (w < Ww && c < W) free_cell = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(table) + (size_t)r * (size_t)row_bytes + (size_t)c * 8) > 0.0;
+    const uint64_t word = __ballot(free_cell);
+    if (lane == 0 && w < Ww) plane[(size_t)r * Ww + w] = word;
+}
+
+// One pass, src -> dst (never the same plane: every decision reads the mask as it was before the pass): a lane per word.  op as
+// cl_pass_word takes it.  The pass's deletions are added to *deleted, one atomic per wave that deleted anything.
+__device__ __forceinline__ void cl_pass(int op, const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, int H, int Ww, unsigned long long *__restrict__ deleted)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t mine = 0;
+    if (t < (size_t)H * Ww) {
+        const int r = (int)(t / (size_t)Ww), w = (int)(t - (size_t)r * Ww);
+        uint64_t out;
+        mine = (uint32_t)__popcll(cl_pass_word(op, src, H, Ww, r, w, out));
+        dst[t] = out;
+    }
+    for (int off = 32; off; off >>= 1) mine += __shfl_xor(mine, off);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(deleted, (unsigned long long)mine);
+}
+
+__global__ void __launch_bounds__(256) k_cl_thin(int sub, const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, int H, int Ww,
+                                                 unsigned long long *__restrict__ deleted)
+{
+    cl_pass(sub, src, dst, H, Ww, deleted);
+}
+
+__global__ void __launch_bounds__(256) k_cl_stair(int k, const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, int H, int Ww,
+                                                  unsigned long long *__restrict__ deleted)
+{
+    cl_pass(2 + k, src, dst, H, Ww, deleted);
+}
+
+__global__ void __launch_bounds__(256) k_cl_prune(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, int H, int Ww, unsigned long long *__restrict__ deleted)
+{
+    cl_pass(6, src, dst, H, Ww, deleted);
+}
+
+// T at a list of cells (r, c), all inside the table (the host traced them on the mask): the loop's half widths
+__global__ void __launch_bounds__(256) k_cl_gather(const double *__restrict__ table, int row_bytes, const int32_t *__restrict__ cells, int n, double *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int r = cells[2 * i], c = cells[2 * i + 1];
+    out[i] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(table) + (size_t)r * (size_t)row_bytes + (size_t)c * 8);
+}
+
 
 // A reactive policy that CONSUMES the scans where the scan kernel left them (round 5; not a reference function — the stand-in
 // for an RL policy in a device-resident loop: examples/rl_loop_device.py, bench.py's "scans consumed on device" leg).  One wave

@@ -2322,4 +2322,114 @@ F110_HD void pf_info(double q, double spread, double xh, double yh, double x, do
     o[3] = resampled ? 1.0f : 0.0f;
 }
 
+// ------------------------------------------------------------------ centreline extraction (f110_map_centerline)
+// The per-word decisions of the thinning rule include/f110.h states.  The mask is a bit plane: bit b of word w of a row is the cell
+// of column 64 w + b, so one 64-bit word decides 64 cells of a row at once, in bit-sliced boolean logic.  One text for the kernels
+// (k_cl_*) and the host program (tests/host_harness/centerline_main.hip).
+struct ClNbr {
+    uint64_t p2, p3, p4, p5, p6, p7, p8, p9;   // the eight neighbour planes of a word, aligned to its bits
+};
+
+// lo / mid / hi: rows r-1 / r / r+1 around word w, each as the words (w-1, w, w+1); a word or a row outside the plane is 0
+F110_HD ClNbr cl_neighbours(const uint64_t *lo, const uint64_t *mid, const uint64_t *hi)
+{
+    ClNbr n;
+    n.p2 = lo[1];
+    n.p3 = (lo[1] >> 1) | (lo[2] << 63);
+    n.p4 = (mid[1] >> 1) | (mid[2] << 63);
+    n.p5 = (hi[1] >> 1) | (hi[2] << 63);
+    n.p6 = hi[1];
+    n.p7 = (hi[1] << 1) | (hi[0] >> 63);
+    n.p8 = (mid[1] << 1) | (mid[0] >> 63);
+    n.p9 = (lo[1] << 1) | (lo[0] >> 63);
+    return n;
+}
+
+// A, the 0 -> 1 transitions around P2 .. P9, P2, as two planes: `any` A >= 1, `many` A >= 2
+F110_HD void cl_transitions(const ClNbr &n, uint64_t &any, uint64_t &many)
+{
+    const uint64_t p[9] = {n.p2, n.p3, n.p4, n.p5, n.p6, n.p7, n.p8, n.p9, n.p2};
+    any = many = 0;
+    for (int i = 0; i < 8; ++i) {
+        const uint64_t t = ~p[i] & p[i + 1];
+        many |= any & t;
+        any |= t;
+    }
+}
+
+// 2 <= B <= 6: the eight planes summed by full adders into the four bit planes of B
+F110_HD uint64_t cl_count_2_to_6(const ClNbr &n)
+{
+    const uint64_t s0 = n.p2 ^ n.p3 ^ n.p4, c0 = (n.p2 & n.p3) | (n.p4 & (n.p2 ^ n.p3));
+    const uint64_t s1 = n.p5 ^ n.p6 ^ n.p7, c1 = (n.p5 & n.p6) | (n.p7 & (n.p5 ^ n.p6));
+    const uint64_t s2 = n.p8 ^ n.p9, c2 = n.p8 & n.p9;
+    const uint64_t b0 = s0 ^ s1 ^ s2, c3 = (s0 & s1) | (s2 & (s0 ^ s1));     // ones
+    const uint64_t t = c0 ^ c1 ^ c2, c4 = (c0 & c1) | (c2 & (c0 ^ c1));      // twos: c0 + c1 + c2 + c3
+    const uint64_t b1 = t ^ c3, c5 = t & c3;
+    const uint64_t b2 = c4 ^ c5, b3 = c4 & c5;                               // fours, eights
+    return (b1 | b2 | b3) & ~b3 & ~(b2 & b1 & b0);
+}
+
+// the cells of `cur` that thinning sub-pass `sub` (0: the first, 1: the second) deletes
+F110_HD uint64_t cl_thin_word(int sub, uint64_t cur, const ClNbr &n)
+{
+    uint64_t any, many;
+    cl_transitions(n, any, many);
+    const uint64_t keep = sub == 0 ? (n.p2 & n.p4 & n.p6) | (n.p4 & n.p6 & n.p8) : (n.p2 & n.p4 & n.p8) | (n.p2 & n.p6 & n.p8);
+    return cur & cl_count_2_to_6(n) & any & ~many & ~keep;
+}
+
+// ... that staircase pass k (0 .. 3, in the rule's order) deletes
+F110_HD uint64_t cl_stair_word(int k, uint64_t cur, const ClNbr &n)
+{
+    switch (k) {
+    case 0: return cur & n.p2 & n.p4 & ~(n.p6 | n.p7 | n.p8);
+    case 1: return cur & n.p4 & n.p6 & ~(n.p8 | n.p9 | n.p2);
+    case 2: return cur & n.p6 & n.p8 & ~(n.p2 | n.p3 | n.p4);
+    default: return cur & n.p8 & n.p2 & ~(n.p4 | n.p5 | n.p6);
+    }
+}
+
+// ... that a prune pass deletes: A <= 1
+F110_HD uint64_t cl_prune_word(uint64_t cur, const ClNbr &n)
+{
+    uint64_t any, many;
+    cl_transitions(n, any, many);
+    return cur & ~many;
+}
+
+// One pass over a plane on the CPU or by one lane per word: op 0 / 1 the thinning sub-passes, 2 .. 5 the staircase passes, 6 prune.
+// Returns the word's deletions; `out` is the word after the pass.
+F110_HD uint64_t cl_pass_word(int op, const uint64_t *plane, int H, int Ww, int r, int w, uint64_t &out)
+{
+    const uint64_t cur = plane[(size_t)r * Ww + w];
+    out = cur;
+    if (cur == 0) return 0;
+    uint64_t rows[3][3];
+    for (int dr = -1; dr <= 1; ++dr) {
+        const int rr = r + dr;
+        for (int dw = -1; dw <= 1; ++dw) {
+            const int ww = w + dw;
+            rows[dr + 1][dw + 1] = (rr >= 0 && rr < H && ww >= 0 && ww < Ww) ? plane[(size_t)rr * Ww + ww] : 0;
+        }
+    }
+    const ClNbr n = cl_neighbours(rows[0], rows[1], rows[2]);
+    const uint64_t del = op < 2 ? cl_thin_word(op, cur, n) : (op < 6 ? cl_stair_word(op - 2, cur, n) : cl_prune_word(cur, n));
+    out = cur & ~del;
+    return del;
+}
+
+// the seed's table cell: the inverse of the stamp rule's transform, with xy_2_rc's bounds test and true division.  false: outside.
+F110_HD bool cl_seed_cell(double x, double y, double res, double ox, double oy, double oc, double os, int H, int W, int &r, int &c)
+{
+    const double xt = x - ox, yt = y - oy;
+    const double xr = xt * oc + yt * os, yr = -xt * os + yt * oc;
+    if (!((xr >= 0) & (xr < (double)W * res) & (yr >= 0) & (yr < (double)H * res))) return false;
+    c = (int)(xr / res);
+    r = (int)(yr / res);
+    if (c > W - 1) c = W - 1;
+    if (r > H - 1) r = H - 1;
+    return true;
+}
+
 }  // namespace f110

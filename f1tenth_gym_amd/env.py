@@ -26,6 +26,7 @@ from .sim import Integrator, Simulator
 from .track_preview import TrackPreview
 from .neighbors import Neighbors
 from .track import Track
+from .centerline import coerce_params
 
 try:  # pragma: no cover - gym is absent from the build image
     import gym as _gym
@@ -145,6 +146,11 @@ def _reward_mode(reward):
     return reward
 
 
+def _is_centerline(track):
+    """track='centerline': the slot's own centreline instead of a given line"""
+    return isinstance(track, str) and track == 'centerline'
+
+
 # the track columns' observation keys -> their names in BatchSim.track_views / track_host_block
 _TRACK_OBS = {key: src for src, key in Simulator.TRACK_KEYS}
 
@@ -209,7 +215,10 @@ class F110Env(_EnvBase):
         self.reward_mode = _reward_mode(kwargs.get('reward', 'timestep'))
         self.track = None
         if kwargs.get('track') is not None:
-            self.track = self.sim.set_track(Track.coerce(kwargs['track']))
+            track = kwargs['track']
+            if _is_centerline(track):   # the map's centreline loop, extracted on the device
+                track = self.sim.batch.centerline(0, **coerce_params(kwargs.get('centerline')))
+            self.track = self.sim.set_track(Track.coerce(track))
             self.sim.enable_track()
         elif self.reward_mode == 'progress':
             raise ValueError("reward='progress' needs a track (track=...)")
@@ -374,7 +383,9 @@ class F110VecEnv(object):
     Track progress (no reference counterpart): `track=` (a Track, an [M][2] array or a csv path) puts a raceline on
     slot 0, `tracks={slot: track}` one per map slot.  The observation then also carries progress, progress_delta,
     lateral_offset, heading_error and track_segment ([E][A] each; obs_fields selects among them too — by default all of them), and
-    reward='progress' makes the reward the ego's progress_delta, [E].
+    reward='progress' makes the reward the ego's progress_delta, [E].  A track given as the string 'centerline' is the slot's own
+    centreline loop, extracted from its distance table on the device (a derived obstacle slot: the line around its
+    obstacles); `centerline=dict(seed=…, heading=…, spacing=…, smooth=…, max_passes=…)` sets BatchSim.centerline's parameters.
 
     Compact observations (no reference counterpart): `obs_encoder=` (an ObsEncoder or a dict of its settings) adds
     obs['encoded'], float32 [E][A][F][D]: pooled lidar sectors and scaled state / track columns, the last F frames stacked
@@ -493,9 +504,10 @@ class F110VecEnv(object):
                 raise ValueError("track_preview= needs device_logic=True (any other loop calls env.sim.batch.track_preview_device after its step)")
             if not tracks:
                 raise ValueError("track_preview= needs a track (track= or tracks=)")
-            tracks = {slot: Track.coerce(t) for slot, t in tracks.items()}
+            tracks = {slot: t if _is_centerline(t) else Track.coerce(t) for slot, t in tracks.items()}
             for t in tracks.values():
-                self.track_preview.check_track(t)
+                if not _is_centerline(t):   # (a centreline is checked once it has been extracted, below)
+                    self.track_preview.check_track(t)
         self.neighbors = None
         if neighbors is not None:
             self.neighbors = Neighbors.coerce(neighbors)
@@ -529,6 +541,9 @@ class F110VecEnv(object):
         for path, ext in kwargs.get('extra_maps', ()):
             self.sim.batch.add_map(path, ext)
             self.map_slots.append((path, ext))
+        # track='centerline' (DESIGN §6n): the slot's centreline loop, extracted from its distance table on the device
+        self.centerline = kwargs.get('centerline')
+        self._extract_centerlines(tracks)
         # static obstacles: each entry registers a slot derived from slot 0 (or from the entry's base slot)
         self.obstacle_slots = {}
         for item in kwargs.get('obstacle_maps', ()):
@@ -538,6 +553,7 @@ class F110VecEnv(object):
             self.obstacle_slots[slot] = base
             if base in tracks and slot not in tracks:   # the same raceline (one Track object) on the derived slot
                 tracks[base] = tracks[slot] = Track.coerce(tracks[base])
+        self._extract_centerlines(tracks)   # (those of derived slots: the line around the obstacles)
         if kwargs.get('env_map') is not None:
             self.set_env_maps(kwargs['env_map'])
         self.tracks = {int(slot): self.sim.set_track(Track.coerce(t), int(slot)) for slot, t in sorted(tracks.items())}
@@ -650,6 +666,15 @@ class F110VecEnv(object):
         """a vehicle parameter set per agent of every env ([E*A] dicts or [E*A][18] array; None: back
         to the per-slot sets of update_params)"""
         self.sim.batch.set_params_batch(params)
+
+    def _extract_centerlines(self, tracks):
+        """replace the 'centerline' entries of `tracks` whose slot is registered by the slot's extracted centreline"""
+        b = self.sim.batch
+        for slot, t in sorted(tracks.items()):
+            if _is_centerline(t) and 0 <= int(slot) < len(self.map_slots):
+                tracks[slot] = b.centerline(int(slot), **coerce_params(self.centerline))
+                if self.track_preview is not None:
+                    self.track_preview.check_track(tracks[slot])
 
     def set_env_maps(self, env_map):
         """env_map [num_envs]: which registered track each env runs on (None: all on slot 0)"""

@@ -78,6 +78,14 @@ class Track(object):
         return cls(w[:, [int(xind), int(yind)]], closed=closed, attrs=cols)
 
     @classmethod
+    def from_map(cls, sim, slot=0, **kw):
+        """the centreline of a map slot, extracted on the device: BatchSim.centerline(slot, **kw) — seed, heading,
+        spacing, smooth, max_passes.  sim: a BatchSim, or an env layer that holds one."""
+        sim = getattr(sim, "sim", sim)        # F110Env / F110VecEnv -> their Simulator
+        sim = getattr(sim, "batch", sim)      # Simulator -> its BatchSim
+        return sim.centerline(slot, **kw)
+
+    @classmethod
     def coerce(cls, track):
         """a Track, an [M][2] array (closed) or a csv path (PurePursuitPlanner's defaults: x, y in columns 1, 2)"""
         if isinstance(track, Track):

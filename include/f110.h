@@ -210,6 +210,63 @@ int f110_get_slot_dt(f110_sim *h, int32_t slot, double *h_dt_out); /* row-major 
 int f110_slot_shape(f110_sim *h, int32_t slot, int32_t *height, int32_t *width);
 int f110_slot_table(f110_sim *h, int32_t slot, const double **d_table, int32_t *row_bytes);
 
+/* Extension: a map slot's CENTRELINE LOOP, extracted ON THE DEVICE from the slot's distance table T (slot 0, an added
+ * slot or a derived obstacle slot), as an ordered cycle of table cells with T at each: what a Track is made of (Track.from_map).
+ *
+ * The rule, in table coordinates (row 0 at the bottom, as the table is indexed).  Cell (r, c) is FREE iff T[r][c] > 0; cells
+ * outside the table count as not free and not set.  The neighbours of (r, c):
+ *   P2 = (r-1, c)  P3 = (r-1, c+1)  P4 = (r, c+1)  P5 = (r+1, c+1)  P6 = (r+1, c)  P7 = (r+1, c-1)  P8 = (r, c-1)  P9 = (r-1, c-1)
+ * B = the number of set neighbours; A = the number of 0 -> 1 transitions in the cyclic sequence P2, P3, ..., P9, P2.  Every pass
+ * is PARALLEL: all decisions of a pass read the mask as it was before that pass.
+ *   1. Thinning (Zhang-Suen).  Start from the free mask; repeat the pair of sub-passes until a full pair deletes nothing.
+ *      Sub-pass 1 deletes a set cell with 2 <= B <= 6, A == 1, P2*P4*P6 == 0 and P4*P6*P8 == 0; sub-pass 2 is the same with
+ *      P2*P4*P8 == 0 and P2*P6*P8 == 0.
+ *   2. Staircase removal.  Four passes, once each, in this order; each deletes the set cells that match its pattern:
+ *      P2 & P4 set with P6, P7, P8 clear;  P4 & P6 set with P8, P9, P2 clear;  P6 & P8 set with P2, P3, P4 clear;
+ *      P8 & P2 set with P4, P5, P6 clear.
+ *   3. Spur pruning.  Repeat until a pass deletes nothing: delete every set cell with A <= 1 (dead ends down to their last stub,
+ *      isolated cells, everything that is not on a cycle).
+ *   4. The start, on the host, from the final mask and the free mask.  The seed is a world point (x, y); with the slot's resolution
+ *      res, origin (ox, oy) and origin cosine / sine (oc, os), float64 in this order (the inverse of the stamp rule's transform):
+ *        xt = x - ox, yt = y - oy;  xr = xt * oc + yt * os, yr = -xt * os + yt * oc
+ *        inside iff xr >= 0 && xr < W * res && yr >= 0 && yr < H * res;  c = (int)(xr / res), r = (int)(yr / res)
+ *      The seed cell must be free.  A breadth-first search from it over free cells, 8-connected, neighbours taken in the order
+ *      P2 .. P9, visits cells in the order it reached them; the first set cell it visits is START.  A search that exhausts the
+ *      seed's free component found no loop.
+ *   5. The trace.  The set cells 8-connected to START must each have exactly two set neighbours, else the call is refused; they are
+ *      walked into a cycle that begins at START.  With a heading theta the first step goes to the neighbour whose offset (dr, dc)
+ *      has the larger dc * hx + dr * hy, (hx, hy) = (cos(theta) * oc + sin(theta) * os, -cos(theta) * os + sin(theta) * oc), a tie
+ *      to the earlier neighbour in P2 .. P9; without one, in the direction that makes the cycle's signed area positive in world
+ *      coordinates (counter-clockwise).
+ * Components do not influence each other under this rule; the library thins the WHOLE free mask.  The loop's cell centres in world
+ * coordinates are the stamp rule's (px, py) -> (wx, wy) above.
+ *
+ * max_passes <= 0: 4 * (H + W).  Thinning may take at most max_passes pairs of sub-passes and pruning at most max_passes passes,
+ * the one that deletes nothing included.  h_deleted [3]: the cells thinning, staircase removal and pruning deleted (how often the
+ * host looks at the counters does not show in them, nor anywhere else).  h_cells [cap][2] = (r, c), h_half_width [cap] = T at the
+ * cell, in metres; *n (always written: 0 where the loop was not reached) the loop's length.  The call runs on the handle's main
+ * stream behind every step in flight (on either env block) and returns when its results are on the host; scratch (three bit
+ * planes of ceil(W / 64) * H words, the loop's cells and values) grows with the map, never with the number of calls, and only the
+ * free mask's and the final mask's planes and the loop's values come back from the device.
+ * Refused up front, with nothing launched, allocated or written but *n = 0 (F110_ERR_INVALID): null arguments, cap < 0, a slot out
+ * of range, a side above 16384 cells, a non-finite seed or heading, a seed outside the table or on a cell that is not free (one
+ * table value is read back for that).  Refused after the passes, with nothing written to h_cells, h_half_width and h_deleted:
+ * thinning or pruning not converged within max_passes, no loop reachable from the seed, not a simple loop — the message carries
+ * the number of cells with more than two neighbours (a map with islands has several loops that share cells: not supported)
+ * (F110_ERR_STATE each); cap smaller than the loop (F110_ERR_INVALID, *n = the length needed).
+ * f110_map_skeleton: the final mask of steps 1 - 3, h_mask [H][W] one byte per cell (1 set), and the three totals (h_deleted may be
+ * NULL): what the tests compare cell for cell.
+ * f110_slot_frame: frame [5] = res, ox, oy, oc, os of a slot as the library holds them (what turns the loop's cells into points). */
+int f110_map_centerline(f110_sim *h, int32_t slot, double seed_x, double seed_y, int32_t has_heading, double seed_theta, int32_t max_passes,
+                        int32_t *h_cells /* [cap][2] r, c */, double *h_half_width /* [cap] */, int32_t cap, int32_t *n, int64_t *h_deleted /* [3] */);
+int f110_map_skeleton(f110_sim *h, int32_t slot, int32_t max_passes, uint8_t *h_mask /* [H][W] */, int64_t *h_deleted /* [3] or NULL */);
+int f110_slot_frame(f110_sim *h, int32_t slot, double *frame /* [5] */);
+/* the host's clock over the stages of the handle's last f110_map_centerline / f110_map_skeleton, milliseconds: ms [5] = (unused),
+ * the free mask and thinning, staircase removal, pruning, and what follows the passes in f110_map_centerline (the two planes back,
+ * the loop pick, the trace, the gather).  Every stage ends with a wait for its counters, so this is what the stage cost the caller
+ * (tools/centerline_bench.py). */
+int f110_map_centerline_times(f110_sim *h, double *ms /* [5] */);
+
 /* Simulator.update_params base_classes.py:514-534 (agent_idx<0: all slots) */
 int f110_set_params(f110_sim *h, int32_t agent_idx, const double *h_params18);
 /* Extension (domain randomisation over vehicle dynamics): one parameter set per AGENT, h_params
