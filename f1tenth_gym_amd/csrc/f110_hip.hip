@@ -493,22 +493,73 @@ static int env_blocks_output(f110_sim *h, const EnvBlocks &w, PinnedDst who, siz
     return F110_OK;
 }
 
-// RAII scratch for the unit entry points
+// RAII scratch for the unit entry points: the device buffers of one call, what has to come back from them, and the call's one
+// synchronise.  Each operation returns the device pointer, so the job's field is assigned where its buffer is made.  A null host
+// pointer is an optional input or output: nullptr comes back and nothing is allocated.  The first failed allocation or copy is
+// reported (fail(), under the entry point's name) and kept; whatever is asked afterwards returns nullptr and does nothing.  So
+// every function that owns or is handed a Scratch calls TRY(s.ready()) once, behind its last allocation and before its first
+// launch, memset or other device-side use of a scratch pointer: no kernel is ever handed a pointer of a failed call.  A new unit
+// form is a spec check, in / out lines that fill the job, ready, a launcher and finish.  Host memory that `in` read or that
+// finish() writes must live until finish() has returned.
 struct Scratch {
+    struct Back { void *host; const void *dev; size_t bytes; };
     f110_sim *h;
+    const char *who;
     DevArena mem;
-    explicit Scratch(f110_sim *hh) : h(hh) {}
+    std::vector<Back> back;   // the device-to-host copies finish() makes, in the order they were asked for
+    int rc = F110_OK;
+    explicit Scratch(f110_sim *hh, const char *name = __builtin_FUNCTION()) : h(hh), who(name) {}
+
+    // allocation only
     template <typename T>
-    int up(const T *host, size_t count, T **dev)
+    T *tmp(size_t count)
     {
-        TRY(dmalloc(h, mem, dev, count));
-        if (host) HIPCHK(h, hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
-        return F110_OK;
+        T *p = nullptr;
+        if (rc != F110_OK) return nullptr;
+        const hipError_t e = mem.alloc(&p, count);
+        if (e != hipSuccess) rc = fail(h, F110_ERR_HIP, "%s: a scratch allocation of %zu bytes failed: %s", who, count * sizeof(T), hipGetErrorString(e));
+        return p;
     }
+    // allocation and the host rows into it, on the handle's stream
     template <typename T>
-    int down(T *host, const T *dev, size_t count)
+    T *in(const T *host, size_t count)
     {
-        HIPCHK(h, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+        T *p = host ? tmp<T>(count) : nullptr;
+        if (!p) return nullptr;
+        const hipError_t e = hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) rc = fail(h, F110_ERR_HIP, "%s: a copy to scratch memory failed: %s", who, hipGetErrorString(e));
+        return rc == F110_OK ? p : nullptr;
+    }
+    // allocation that finish() copies into the host rows
+    template <typename T>
+    T *out(T *host, size_t count)
+    {
+        T *p = host ? tmp<T>(count) : nullptr;
+        later(host, p, count);
+        return p;
+    }
+    // in and out of the same host rows
+    template <typename T>
+    T *inout(T *host, size_t count)
+    {
+        T *p = in(host, count);
+        later(host, p, count);
+        return p;
+    }
+    // finish() copies `dev`, a buffer that exists anyway, into the host rows (none: nothing)
+    template <typename T>
+    void later(T *host, const T *dev, size_t count)
+    {
+        if (host && dev && rc == F110_OK) back.push_back(Back{host, dev, count * sizeof(T)});
+    }
+    int ready() const { return rc; }
+    // behind the last launch: the launches' status, the copies back and the call's one synchronise
+    int finish()
+    {
+        TRY(rc);
+        HIPCHK(h, hipGetLastError());
+        for (const Back &b : back) HIPCHK(h, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
         return F110_OK;
     }
 };
@@ -1212,25 +1263,33 @@ static int finish_map(f110_sim *h, int H, int W, double res, double ox, double o
     return F110_OK;
 }
 
+// The exact-EDT pipeline on a host image [H][W]: the image and the intermediates into scratch memory, then k_flip_threshold
+// (threshold: a raw image, else a bitmap already), k_edt_columns, k_edt_rows and, with a table, k_dt_from_d2 at `res` into it.
+// h_d2: the squared distances come back with the caller's finish().
+static int edt_launch(Scratch &s, const uint8_t *h_img, int H, int W, bool threshold, uint32_t *h_d2, double res, double *table)
+{
+    f110_sim *h = s.h;
+    const size_t n = (size_t)H * W;
+    const uint8_t *d_img = s.in(h_img, n);
+    uint8_t *d_bin = threshold ? s.tmp<uint8_t>(n) : nullptr;
+    uint32_t *d_g = s.tmp<uint32_t>(n), *d_d2 = s.tmp<uint32_t>(n);
+    s.later(h_d2, d_d2, n);
+    TRY(s.ready());
+    if (threshold) hipLaunchKernelGGL(k_flip_threshold, grid1d(n, 256), dim3(256), 0, h->stream, d_img, H, W, d_bin);
+    hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, threshold ? d_bin : d_img, H, W, d_g);
+    hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, d_g, H, W, d_d2);
+    if (table) hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, d_d2, n, res, table);
+    return F110_OK;
+}
+
 int f110_set_map_image(f110_sim *h, const uint8_t *h_img, int32_t H, int32_t W, double res, double ox, double oy, double oyaw)
 {
     if (!h || !h_img) return fail(h, F110_ERR_INVALID, "f110_set_map_image: null argument");
     ENTER(h);
     if (H < 1 || W < 1 || H > 16384 || W > 16384 || !(res > 0)) return fail(h, F110_ERR_INVALID, "f110_set_map_image: bad shape %dx%d or resolution", H, W);
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    const size_t n = (size_t)H * W;
-    uint8_t *d_img = nullptr, *d_bin = nullptr;
-    uint32_t *d_g = nullptr, *d_d2 = nullptr;
-    Scratch s(h);
-    TRY(s.up(h_img, n, &d_img));
-    TRY(s.up<uint8_t>(nullptr, n, &d_bin));
-    TRY(s.up<uint32_t>(nullptr, n, &d_g));
-    TRY(s.up<uint32_t>(nullptr, n, &d_d2));
-    return replace_map(h, n, H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw), [&](double *table) {  // :421-422
-        hipLaunchKernelGGL(k_flip_threshold, grid1d(n, 256), dim3(256), 0, h->stream, d_img, H, W, d_bin);
-        hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, d_bin, H, W, d_g);
-        hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, d_g, H, W, d_d2);
-        hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, d_d2, n, res, table);
+    Scratch s(h);   // (lives until finish_map has synchronised)
+    return replace_map(h, (size_t)H * W, H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw), [&](double *table) {  // :421-422
+        TRY(edt_launch(s, h_img, H, W, true, nullptr, res, table));
         HIPCHK(h, hipGetLastError());
         return (int)F110_OK;
     });
@@ -1242,7 +1301,6 @@ int f110_set_map_dt(f110_sim *h, const double *h_dt, int32_t H, int32_t W, doubl
     ENTER(h);
     if (H < 1 || W < 1 || !(res > 0)) return fail(h, F110_ERR_INVALID, "f110_set_map_dt: bad shape or resolution");
     if ((unsigned long long)(H + 3) * (unsigned long long)(W + 3) * 8ull >= 0xFFFFFFFFull) return fail(h, F110_ERR_INVALID, "distance table must stay below 4 GiB");
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t n = (size_t)H * W;
     return replace_map(h, n, H, W, res, ox, oy, oc, os, [&](double *table) {
         HIPCHK(h, hipMemcpyAsync(table, h_dt, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1254,22 +1312,10 @@ int f110_set_map_dt(f110_sim *h, const double *h_dt, int32_t H, int32_t W, doubl
 // the exact-EDT pipeline of f110_set_map_image into a fresh row-major table
 static int edt_table_from_image(f110_sim *h, const uint8_t *h_img, int H, int W, double res, DevBuf<double> &d_dt_row)
 {
-    const size_t n = (size_t)H * W;
-    uint8_t *d_img = nullptr, *d_bin = nullptr;
-    uint32_t *d_g = nullptr, *d_d2 = nullptr;
     Scratch s(h);
-    TRY(s.up(h_img, n, &d_img));
-    TRY(s.up<uint8_t>(nullptr, n, &d_bin));
-    TRY(s.up<uint32_t>(nullptr, n, &d_g));
-    TRY(s.up<uint32_t>(nullptr, n, &d_d2));
-    TRY(dmalloc(h, &d_dt_row, n));
-    hipLaunchKernelGGL(k_flip_threshold, grid1d(n, 256), dim3(256), 0, h->stream, d_img, H, W, d_bin);
-    hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, d_bin, H, W, d_g);
-    hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, d_g, H, W, d_d2);
-    hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, d_d2, n, res, d_dt_row.get());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    TRY(dmalloc(h, &d_dt_row, (size_t)H * W));
+    TRY(edt_launch(s, h_img, H, W, true, nullptr, res, d_dt_row.get()));
+    return s.finish();
 }
 
 // the row-major table becomes a slot: whatever fails, the table (and the slot's padded copy) go with the locals that own them
@@ -1883,13 +1929,10 @@ int f110_set_trig_tables(f110_sim *h, const double *s, const double *c, int32_t 
     ENTER(h);
     if (n != h->cfg.theta_dis) return fail(h, F110_ERR_INVALID, "trig tables must have theta_dis=%d entries (got %d)", h->cfg.theta_dis, n);
     Scratch sc(h);
-    double *ds = nullptr, *dc = nullptr;
-    TRY(sc.up(s, (size_t)n, &ds));
-    TRY(sc.up(c, (size_t)n, &dc));
+    const double *ds = sc.in(s, (size_t)n), *dc = sc.in(c, (size_t)n);
+    TRY(sc.ready());
     hipLaunchKernelGGL(k_interleave_cs, grid1d(n, 256), dim3(256), 0, h->stream, ds, dc, n, h->d_cs);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return sc.finish();
 }
 
 static const char *const kBeamsMsg = "the beam tables (f110_set_beam_tables) are not the uniform ramp scan_angles[i] = scan_angles[0] + i*inc of base_classes.py:133-134: "
@@ -2089,20 +2132,17 @@ int f110_noise_rows_batch(f110_sim *h, const uint64_t *state_inc, double std_dev
     if (!h || !state_inc || !h_out || rows < 1 || num_beams < 1) return fail(h, F110_ERR_INVALID, "f110_noise_rows_batch: bad argument");
     ENTER(h);
     Scratch s(h);
-    U128 *d_rs = nullptr;
-    double *d_out = nullptr;
-    TRY(s.up<U128>(nullptr, (size_t)rows + 1, &d_rs));
-    TRY(s.up<double>(nullptr, (size_t)rows * num_beams, &d_out));
+    U128 last{};
+    U128 *d_rs = s.tmp<U128>((size_t)rows + 1);
+    double *d_out = s.out(h_out, (size_t)rows * num_beams);
+    TRY(s.ready());
+    s.later(&last, d_rs + rows, 1);   // the state behind the last row
     const U128 st0 = {state_inc[0], state_inc[1]}, inc = {state_inc[2], state_inc[3]};
     HIPCHK(h, hipMemcpyAsync(d_rs, &st0, sizeof st0, hipMemcpyHostToDevice, h->stream));
     NoiseGen g = h->noise_gen;
     g.scale = std_dev;
     hipLaunchKernelGGL(k_noise_cache, dim3(1), dim3(64), 0, h->stream, g, inc, d_rs, d_out, 0, rows, num_beams);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(h_out, d_out, (size_t)rows * num_beams));
-    U128 last{};
-    HIPCHK(h, hipMemcpyAsync(&last, d_rs + rows, sizeof last, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    TRY(s.finish());
     if (h_state_out) {
         h_state_out[0] = last.hi;
         h_state_out[1] = last.lo;
@@ -4259,30 +4299,20 @@ int f110_scan_batch(f110_sim *h, const double *poses, int32_t m, double *ranges,
     if (m == 0) return F110_OK;
     const size_t B = (size_t)h->cfg.num_beams;
     Scratch s(h);
-    double *dp = nullptr, *dr = nullptr;
-    int32_t *dh = nullptr;
-    unsigned long long *dl = nullptr;
-    TRY(s.up(poses, (size_t)3 * m, &dp));
-    TRY(s.up<double>(nullptr, (size_t)m * B, &dr));
-    if (hit_rc) TRY(s.up<int32_t>(nullptr, (size_t)m * B * 2, &dh));
-    if (lookups) {
-        TRY(s.up<unsigned long long>(nullptr, (size_t)m, &dl));
-        HIPCHK(h, hipMemsetAsync(dl, 0, sizeof(unsigned long long) * m, h->stream));
-    }
-    double *dpx = nullptr, *dpy = nullptr, *dst = nullptr;
-    TRY(s.up<double>(nullptr, (size_t)m, &dpx));
-    TRY(s.up<double>(nullptr, (size_t)m, &dpy));
-    TRY(s.up<double>(nullptr, (size_t)m, &dst));
-    hipLaunchKernelGGL(k_prepare_poses, grid1d(m, 128), dim3(128), 0, h->stream, h->k, dp, m, dpx, dpy, dst);
     RayJob j{};
+    const double *dp = s.in(poses, (size_t)3 * m);
+    j.ranges = s.out(ranges, (size_t)m * B);
+    j.hit_rc = s.out(hit_rc, (size_t)m * B * 2);
+    j.lookups = s.out(reinterpret_cast<unsigned long long *>(lookups), (size_t)m);
+    double *dpx = s.tmp<double>((size_t)m), *dpy = s.tmp<double>((size_t)m), *dst = s.tmp<double>((size_t)m);
+    TRY(s.ready());
+    if (j.lookups) HIPCHK(h, hipMemsetAsync(j.lookups, 0, sizeof(unsigned long long) * m, h->stream));
+    hipLaunchKernelGGL(k_prepare_poses, grid1d(m, 128), dim3(128), 0, h->stream, h->k, dp, m, dpx, dpy, dst);
     j.n_rays = (uint32_t)m * (uint32_t)B;
     j.n_poses = m;
     j.pose_x = dpx;
     j.pose_y = dpy;
     j.dir_start = dst;
-    j.ranges = dr;
-    j.hit_rc = dh;
-    j.lookups = dl;
     j.path_stats = h->path_stats_on ? h->d_path_stats : nullptr;
     j.k_cold = cold_consts(h);
     if (!j.k_cold) return fail(h, F110_ERR_HIP, "f110_scan_batch: constant upload failed");
@@ -4290,13 +4320,7 @@ int f110_scan_batch(f110_sim *h, const double *poses, int32_t m, double *ranges,
     scan_rays_fn fn = pick_rays<false>(h->k, h->cfg.map_layout);
     const dim3 grid = rays_grid(j, h->scan_block, h->scan_tasks_per_wave);
     hipLaunchKernelGGL(fn, grid, dim3(h->scan_block), 0, h->stream, j, h->k);
-    HIPCHK(h, hipGetLastError());
-
-    TRY(s.down(ranges, dr, (size_t)m * B));
-    if (hit_rc) TRY(s.down(hit_rc, dh, (size_t)m * B * 2));
-    if (lookups) TRY(s.down(reinterpret_cast<unsigned long long *>(lookups), dl, (size_t)m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 // ---- the reference's example policy (examples/waypoint_follow.py) -----------------------------
@@ -4316,16 +4340,12 @@ int f110_pure_pursuit_batch(f110_sim *h, const double *h_waypoints, int32_t M, c
     if (m == 0) return F110_OK;
     ENTER(h);
     Scratch s(h);
-    double *dw = nullptr, *dp = nullptr, *da = nullptr;
-    TRY(s.up(h_waypoints, (size_t)3 * M, &dw));
-    TRY(s.up(h_poses, (size_t)3 * m, &dp));
-    TRY(s.up<double>(nullptr, (size_t)2 * m, &da));
+    const double *dw = s.in(h_waypoints, (size_t)3 * M), *dp = s.in(h_poses, (size_t)3 * m);
+    double *da = s.out(h_actions, (size_t)2 * m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_pure_pursuit, grid1d((size_t)m * kPlanLanes, 256), dim3(256), 0, h->stream, dw, M, dp, dp + 1, dp + 2, 3, m, lookahead, vgain, wheelbase,
                        max_reacquire, da);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(h_actions, da, (size_t)2 * m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_pure_pursuit_device(f110_sim *h, const double *d_waypoints, int32_t M, double lookahead, double vgain, double wheelbase,
@@ -4498,18 +4518,13 @@ int f110_obs_encode_batch(f110_sim *h, const f110_obs_spec *spec, const double *
     ENTER(h);
     Scratch s(h);
     const size_t B = (size_t)h->cfg.num_beams, per_agent = (size_t)spec->frames * j.rs.D;
-    double *ds = nullptr, *dc = nullptr;
-    int32_t *dn = nullptr;
-    float *dout = nullptr;
-    TRY(s.up(h_scans, (size_t)m * B, &ds));
-    TRY(s.up(h_cols, (size_t)m * F110_OBS_NFEATURES, &dc));
-    TRY(s.up(h_step_count, (size_t)m, &dn));
-    TRY(s.up(h_inout, (size_t)m * per_agent, &dout));
+    j.scans = s.in(h_scans, (size_t)m * B);
+    const double *dc = s.in(h_cols, (size_t)m * F110_OBS_NFEATURES);
+    j.step_count = s.in(h_step_count, (size_t)m);
+    j.out = s.inout(h_inout, (size_t)m * per_agent);
+    TRY(s.ready());
     for (int f = 0; f < F110_OBS_NFEATURES; ++f) j.fptr[f] = dc + (f < j.rs.nfeat ? j.rs.feat[f] : 0);
     j.col_stride = F110_OBS_NFEATURES;
-    j.scans = ds;
-    j.step_count = dn;
-    j.out = dout;
     j.B = (int)B;
     j.F = spec->frames;
     j.fill = (spec->flags & F110_OBS_FILL) ? 1 : 0;
@@ -4517,10 +4532,7 @@ int f110_obs_encode_batch(f110_sim *h, const f110_obs_spec *spec, const double *
     j.n = m;
     obs_plan_lds(j);
     obs_launch(j, h->stream);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(h_inout, dout, (size_t)m * per_agent));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 // ---- scripted cars: follow the gap (include/f110.h) --------------------------------------------------------------------------
@@ -4641,30 +4653,19 @@ int f110_follow_gap_batch(f110_sim *h, const f110_gap_follower *spec, const doub
     ENTER(h);
     Scratch s(h);
     const size_t B = (size_t)h->cfg.num_beams;
-    GapSpec *dspec = nullptr;
-    double *ds = nullptr, *da = nullptr;
-    int32_t *dn = nullptr, *di = nullptr;
-    TRY(s.up(&gs, 1, &dspec));
-    TRY(s.up(h_scans, (size_t)m * B, &ds));
-    if (h_step_count) TRY(s.up(h_step_count, (size_t)m, &dn));
-    TRY(s.up((const double *)nullptr, (size_t)m * 2, &da));
-    if (h_info) TRY(s.up((const int32_t *)nullptr, (size_t)m * 5, &di));
     GapJob j{};
-    j.specs = dspec;
-    j.scans = ds;
-    j.step_count = dn;
-    j.actions = da;
-    j.info = di;
+    j.specs = s.in(&gs, 1);
+    j.scans = s.in(h_scans, (size_t)m * B);
+    j.step_count = s.in(h_step_count, (size_t)m);
+    j.actions = s.out(h_actions, (size_t)m * 2);
+    j.info = s.out(h_info, (size_t)m * 5);
+    TRY(s.ready());
     j.fov = h->cfg.fov;
     j.B = (int)B;
     j.n = m;
     gap_plan_lds(j, gs.W);
     gap_launch(j, h->stream);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(h_actions, da, (size_t)m * 2));
-    if (h_info) TRY(s.down(h_info, di, (size_t)m * 5));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_scan_path_stats(f110_sim *h, int32_t enable, int64_t *out3)
@@ -4691,15 +4692,11 @@ int f110_beam_dir_index_batch(f110_sim *h, const double *thetas, int32_t m, int3
     ENTER(h);
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *dt = nullptr;
-    int32_t *di = nullptr;
-    TRY(s.up(thetas, (size_t)m, &dt));
-    TRY(s.up<int32_t>(nullptr, (size_t)m * h->cfg.num_beams, &di));
+    const double *dt = s.in(thetas, (size_t)m);
+    int32_t *di = s.out(idx, (size_t)m * h->cfg.num_beams);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_dir_index_unit, dim3(m), dim3(128), 0, h->stream, h->k, dt, m, di);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(idx, di, (size_t)m * h->cfg.num_beams));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_dynamics_batch(f110_sim *h, const double *x, const double *u, const double *params, int32_t m, double *f_st, double *f_ks)
@@ -4708,18 +4705,11 @@ int f110_dynamics_batch(f110_sim *h, const double *x, const double *u, const dou
     ENTER(h);
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *dx, *du, *dp, *dfs, *dfk;
-    TRY(s.up(x, (size_t)7 * m, &dx));
-    TRY(s.up(u, (size_t)2 * m, &du));
-    TRY(s.up(params, (size_t)NPARAMS, &dp));
-    TRY(s.up<double>(nullptr, (size_t)7 * m, &dfs));
-    TRY(s.up<double>(nullptr, (size_t)5 * m, &dfk));
+    const double *dx = s.in(x, (size_t)7 * m), *du = s.in(u, (size_t)2 * m), *dp = s.in(params, (size_t)NPARAMS);
+    double *dfs = s.out(f_st, (size_t)7 * m), *dfk = s.out(f_ks, (size_t)5 * m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_dynamics_unit, grid1d(m, 128), dim3(128), 0, h->stream, dx, du, dp, m, dfs, dfk);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(f_st, dfs, (size_t)7 * m));
-    TRY(s.down(f_ks, dfk, (size_t)5 * m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_pid_batch(f110_sim *h, const double *in, const double *params, int32_t m, double *out)
@@ -4728,15 +4718,11 @@ int f110_pid_batch(f110_sim *h, const double *in, const double *params, int32_t 
     ENTER(h);
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *di, *dp, *dout;
-    TRY(s.up(in, (size_t)4 * m, &di));
-    TRY(s.up(params, (size_t)NPARAMS, &dp));
-    TRY(s.up<double>(nullptr, (size_t)2 * m, &dout));
+    const double *di = s.in(in, (size_t)4 * m), *dp = s.in(params, (size_t)NPARAMS);
+    double *dout = s.out(out, (size_t)2 * m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_pid_unit, grid1d(m, 128), dim3(128), 0, h->stream, di, dp, m, dout);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(out, dout, (size_t)2 * m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_update_pose_batch(f110_sim *h, const double *s0, const double *b0, const int32_t *c0, const double *act,
@@ -4748,25 +4734,15 @@ int f110_update_pose_batch(f110_sim *h, const double *s0, const double *b0, cons
     if (integ != F110_INTEGRATOR_RK4 && integ != F110_INTEGRATOR_EULER) return fail(h, F110_ERR_INVALID, "Invalid Integrator Specified. Please choose RK4 or Euler");
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *ds0, *db0, *dact, *dp, *ds1, *db1, *dsp;
-    int32_t *dc0, *dc1;
-    TRY(s.up(s0, (size_t)7 * m, &ds0));
-    TRY(s.up(b0, (size_t)2 * m, &db0));
-    TRY(s.up(c0, (size_t)m, &dc0));
-    TRY(s.up(act, (size_t)2 * m, &dact));
-    TRY(s.up(params, (size_t)NPARAMS, &dp));
-    TRY(s.up<double>(nullptr, (size_t)7 * m, &ds1));
-    TRY(s.up<double>(nullptr, (size_t)2 * m, &db1));
-    TRY(s.up<int32_t>(nullptr, (size_t)m, &dc1));
-    TRY(s.up<double>(nullptr, (size_t)3 * m, &dsp));
+    const double *ds0 = s.in(s0, (size_t)7 * m), *db0 = s.in(b0, (size_t)2 * m);
+    const int32_t *dc0 = s.in(c0, (size_t)m);
+    const double *dact = s.in(act, (size_t)2 * m), *dp = s.in(params, (size_t)NPARAMS);
+    double *ds1 = s.out(s1, (size_t)7 * m), *db1 = s.out(b1, (size_t)2 * m);
+    int32_t *dc1 = s.out(c1, (size_t)m);
+    double *dsp = s.out(spose, (size_t)3 * m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_update_pose_unit, grid1d(m, 128), dim3(128), 0, h->stream, ds0, db0, dc0, dact, dp, dt, integ, lidar_dist, m, ds1, db1, dc1, dsp);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(s1, ds1, (size_t)7 * m));
-    TRY(s.down(b1, db1, (size_t)2 * m));
-    TRY(s.down(c1, dc1, (size_t)m));
-    TRY(s.down(spose, dsp, (size_t)3 * m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_get_vertices_batch(f110_sim *h, const double *poses, double length, double width, int32_t m, double *verts)
@@ -4775,14 +4751,11 @@ int f110_get_vertices_batch(f110_sim *h, const double *poses, double length, dou
     ENTER(h);
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *dp, *dv;
-    TRY(s.up(poses, (size_t)3 * m, &dp));
-    TRY(s.up<double>(nullptr, (size_t)8 * m, &dv));
+    const double *dp = s.in(poses, (size_t)3 * m);
+    double *dv = s.out(verts, (size_t)8 * m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_vertices_unit, grid1d(m, 128), dim3(128), 0, h->stream, dp, length, width, m, dv);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(verts, dv, (size_t)8 * m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_gjk_batch(f110_sim *h, const double *va, const double *vb, int32_t m, int32_t *flags)
@@ -4791,16 +4764,11 @@ int f110_gjk_batch(f110_sim *h, const double *va, const double *vb, int32_t m, i
     ENTER(h);
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *da, *db;
-    int32_t *df;
-    TRY(s.up(va, (size_t)8 * m, &da));
-    TRY(s.up(vb, (size_t)8 * m, &db));
-    TRY(s.up<int32_t>(nullptr, (size_t)m, &df));
+    const double *da = s.in(va, (size_t)8 * m), *db = s.in(vb, (size_t)8 * m);
+    int32_t *df = s.out(flags, (size_t)m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_gjk_unit, grid1d(m, 128), dim3(128), 0, h->stream, da, db, m, df);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(flags, df, (size_t)m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_collision_multiple_batch(f110_sim *h, const double *verts, int32_t groups, int32_t n, double *col, double *idx)
@@ -4810,16 +4778,11 @@ int f110_collision_multiple_batch(f110_sim *h, const double *verts, int32_t grou
     if (groups == 0) return F110_OK;
     const size_t t = (size_t)groups * n;
     Scratch s(h);
-    double *dv, *dc, *di;
-    TRY(s.up(verts, 8 * t, &dv));
-    TRY(s.up<double>(nullptr, t, &dc));
-    TRY(s.up<double>(nullptr, t, &di));
+    const double *dv = s.in(verts, 8 * t);
+    double *dc = s.out(col, t), *di = s.out(idx, t);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_collision_multiple_unit, grid1d(t, 128), dim3(128), 0, h->stream, dv, groups, n, dc, di);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(col, dc, t));
-    TRY(s.down(idx, di, t));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_ttc_batch(f110_sim *h, const double *scans, const double *vels, int32_t m, double thresh, int32_t *flags)
@@ -4829,16 +4792,11 @@ int f110_ttc_batch(f110_sim *h, const double *scans, const double *vels, int32_t
     if (m == 0) return F110_OK;
     const size_t B = (size_t)h->cfg.num_beams;
     Scratch s(h);
-    double *ds, *dv;
-    int32_t *df;
-    TRY(s.up(scans, (size_t)m * B, &ds));
-    TRY(s.up(vels, (size_t)m, &dv));
-    TRY(s.up<int32_t>(nullptr, (size_t)m, &df));
+    const double *ds = s.in(scans, (size_t)m * B), *dv = s.in(vels, (size_t)m);
+    int32_t *df = s.out(flags, (size_t)m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_ttc_unit, dim3(m), dim3(128), 0, h->stream, ds, dv, m, (int)B, h->d_beam_cos, h->d_side, thresh, df);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(flags, df, (size_t)m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_raycast_batch(f110_sim *h, const double *ego, const double *verts, int32_t m, double *scans, int32_t *minmax)
@@ -4848,18 +4806,12 @@ int f110_raycast_batch(f110_sim *h, const double *ego, const double *verts, int3
     if (m == 0) return F110_OK;
     const size_t B = (size_t)h->cfg.num_beams;
     Scratch s(h);
-    double *de, *dv, *ds;
-    int32_t *dm = nullptr;
-    TRY(s.up(ego, (size_t)3 * m, &de));
-    TRY(s.up(verts, (size_t)8 * m, &dv));
-    TRY(s.up(scans, (size_t)m * B, &ds));
-    if (minmax) TRY(s.up<int32_t>(nullptr, (size_t)2 * m, &dm));
+    const double *de = s.in(ego, (size_t)3 * m), *dv = s.in(verts, (size_t)8 * m);
+    double *ds = s.inout(scans, (size_t)m * B);
+    int32_t *dm = s.out(minmax, (size_t)2 * m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_raycast_unit, dim3(m), dim3(128), 0, h->stream, de, dv, m, (int)B, h->d_scan_angles, h->dev.angle_inc, h->beams_uniform ? 1 : 0, ds, dm);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(scans, ds, (size_t)m * B));
-    if (minmax) TRY(s.down(minmax, dm, (size_t)2 * m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_get_range_batch(f110_sim *h, const double *in, int32_t m, double *out)
@@ -4868,14 +4820,11 @@ int f110_get_range_batch(f110_sim *h, const double *in, int32_t m, double *out)
     ENTER(h);
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *di, *dout;
-    TRY(s.up(in, (size_t)8 * m, &di));
-    TRY(s.up<double>(nullptr, (size_t)m, &dout));
+    const double *di = s.in(in, (size_t)8 * m);
+    double *dout = s.out(out, (size_t)m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_get_range_unit, grid1d(m, 128), dim3(128), 0, h->stream, di, m, dout);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(out, dout, (size_t)m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 int f110_edt_sq(f110_sim *h, const uint8_t *img, int32_t H, int32_t W, uint32_t *d2)
@@ -4883,19 +4832,9 @@ int f110_edt_sq(f110_sim *h, const uint8_t *img, int32_t H, int32_t W, uint32_t 
     if (!h || !img || !d2) return fail(h, F110_ERR_INVALID, "null argument");
     ENTER(h);
     if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(h, F110_ERR_INVALID, "f110_edt_sq: bad shape %dx%d", H, W);
-    const size_t n = (size_t)H * W;
     Scratch s(h);
-    uint8_t *dimg;
-    uint32_t *dg, *dd;
-    TRY(s.up(img, n, &dimg));
-    TRY(s.up<uint32_t>(nullptr, n, &dg));
-    TRY(s.up<uint32_t>(nullptr, n, &dd));
-    hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, dimg, H, W, dg);
-    hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, dg, H, W, dd);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(d2, dd, n));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    TRY(edt_launch(s, img, H, W, false, d2, 0.0, nullptr));
+    return s.finish();
 }
 
 int f110_dt_from_bitmap(f110_sim *h, const uint8_t *img, int32_t H, int32_t W, double resolution, double *dt)
@@ -4903,22 +4842,11 @@ int f110_dt_from_bitmap(f110_sim *h, const uint8_t *img, int32_t H, int32_t W, d
     if (!h || !img || !dt) return fail(h, F110_ERR_INVALID, "null argument");
     ENTER(h);
     if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(h, F110_ERR_INVALID, "f110_dt_from_bitmap: bad shape %dx%d", H, W);
-    const size_t n = (size_t)H * W;
     Scratch s(h);
-    uint8_t *dimg;
-    uint32_t *dg, *dd;
-    double *ddt;
-    TRY(s.up(img, n, &dimg));
-    TRY(s.up<uint32_t>(nullptr, n, &dg));
-    TRY(s.up<uint32_t>(nullptr, n, &dd));
-    TRY(s.up<double>(nullptr, n, &ddt));
-    hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, dimg, H, W, dg);
-    hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, dg, H, W, dd);
-    hipLaunchKernelGGL(k_dt_from_d2, grid1d(n, 256), dim3(256), 0, h->stream, dd, n, resolution, ddt);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(dt, ddt, n));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    double *ddt = s.out(dt, (size_t)H * W);
+    TRY(s.ready());
+    TRY(edt_launch(s, img, H, W, false, nullptr, resolution, ddt));
+    return s.finish();
 }
 
 int f110_helper_batch(f110_sim *h, int32_t op, const double *in, int32_t m, int32_t n, double *out)
@@ -4946,14 +4874,11 @@ int f110_helper_batch(f110_sim *h, int32_t op, const double *in, int32_t m, int3
     if (needs_map && !h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
     if (m == 0) return F110_OK;
     Scratch s(h);
-    double *di, *dout;
-    TRY(s.up(in, (size_t)in_w * m, &di));
-    TRY(s.up<double>(nullptr, (size_t)out_w * m, &dout));
+    const double *di = s.in(in, (size_t)in_w * m);
+    double *dout = s.out(out, (size_t)out_w * m);
+    TRY(s.ready());
     hipLaunchKernelGGL(k_helper_unit, grid1d(m, 128), dim3(128), 0, h->stream, op, di, m, n, in_w, out_w, dout, h->k);
-    HIPCHK(h, hipGetLastError());
-    TRY(s.down(out, dout, (size_t)out_w * m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return s.finish();
 }
 
 }  // extern "C"
@@ -5249,10 +5174,10 @@ int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, i
     if (m == 0) return F110_OK;
     TRY(track_upload(h));
     Scratch sc(h);
-    double *dp = nullptr, *dout = nullptr;
-    TRY(sc.up(h_poses, 3 * (size_t)m, &dp));
-    TRY(sc.up<double>(nullptr, 5 * (size_t)m, &dout));
     TrackJob j{};
+    const double *dp = sc.in(h_poses, 3 * (size_t)m);
+    j.unit_out = sc.out(h_out, 5 * (size_t)m);
+    TRY(sc.ready());
     j.tracks = h->d_tracks;
     j.A = 1;
     j.count = m;
@@ -5261,14 +5186,10 @@ int f110_track_project_batch(f110_sim *h, int32_t slot, const double *h_poses, i
     j.py = dp + 1;
     j.pth = dp + 2;
     j.stride = 3;
-    j.unit_out = dout;
     const dim3 grid = grid1d((size_t)m * kTrackLanes, 256);
     if (h->tracks[slot].nseg <= kTrackLdsSegs) hipLaunchKernelGGL((k_track_project<kTrackUnit, true>), grid, dim3(256), 0, h->stream, j);
     else hipLaunchKernelGGL((k_track_project<kTrackUnit, false>), grid, dim3(256), 0, h->stream, j);
-    HIPCHK(h, hipGetLastError());
-    TRY(sc.down(h_out, dout, 5 * (size_t)m));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return sc.finish();
 }
 
 // ---- track preview (f110_track_set_attrs / f110_track_preview_*, include/f110.h) ------------------------------------------------
@@ -5406,13 +5327,11 @@ int f110_track_preview_batch(f110_sim *h, const f110_track_preview *spec, int32_
     TRY(track_upload(h));
     Scratch sc(h);
     const size_t rows = (size_t)m * j.sp.P;
-    double *din = nullptr, *draw = nullptr;
-    float *dout = nullptr;
-    int32_t *dseg = nullptr;
-    TRY(sc.up(h_in, 4 * (size_t)m, &din));
-    TRY(sc.up<float>(nullptr, rows * j.sp.D, &dout));
-    if (h_raw) TRY(sc.up<double>(nullptr, rows * F110_PREVIEW_NCHANNELS, &draw));
-    if (h_seg) TRY(sc.up<int32_t>(nullptr, rows, &dseg));
+    const double *din = sc.in(h_in, 4 * (size_t)m);
+    j.out = sc.out(h_out, rows * j.sp.D);
+    j.raw = sc.out(h_raw, rows * F110_PREVIEW_NCHANNELS);
+    j.seg = sc.out(h_seg, rows);
+    TRY(sc.ready());
     j.tracks = h->d_tracks;
     j.attrs = h->d_track_attrs;
     j.A = 1;
@@ -5423,16 +5342,8 @@ int f110_track_preview_batch(f110_sim *h, const f110_track_preview *spec, int32_
     j.pth = din + 2;
     j.ps = din + 3;
     j.stride = 4;
-    j.out = dout;
-    j.raw = draw;
-    j.seg = dseg;
     preview_launch(j, h->stream);
-    HIPCHK(h, hipGetLastError());
-    TRY(sc.down(h_out, dout, rows * j.sp.D));
-    if (h_raw) TRY(sc.down(h_raw, draw, rows * F110_PREVIEW_NCHANNELS));
-    if (h_seg) TRY(sc.down(h_seg, dseg, rows));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return sc.finish();
 }
 
 // ---- neighbours (f110_neighbors_*, include/f110.h) --------------------------------------------------------------------------------
@@ -5525,13 +5436,11 @@ int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, dou
     ENTER(h);
     Scratch sc(h);
     const size_t slots = (size_t)m * j.sp.K;
-    double *din = nullptr, *draw = nullptr;
-    float *dout = nullptr;
-    int32_t *didx = nullptr;
-    TRY(sc.up(h_in, 5 * (size_t)m, &din));
-    TRY(sc.up<float>(nullptr, slots * j.sp.D, &dout));
-    if (h_raw) TRY(sc.up<double>(nullptr, slots * F110_NBR_NCHANNELS, &draw));
-    if (h_idx) TRY(sc.up<int32_t>(nullptr, slots, &didx));
+    const double *din = sc.in(h_in, 5 * (size_t)m);
+    j.out = sc.out(h_out, slots * j.sp.D);
+    j.raw = sc.out(h_raw, slots * F110_NBR_NCHANNELS);
+    j.idx = sc.out(h_idx, slots);
+    TRY(sc.ready());
     j.A = A;
     j.env0 = 0;
     j.envs = m / A;
@@ -5542,16 +5451,8 @@ int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, dou
     j.ps = din + 4;
     j.stride = 5;
     j.unit_L = track_L;
-    j.out = dout;
-    j.raw = draw;
-    j.idx = didx;
     nbr_launch(j, h->stream);
-    HIPCHK(h, hipGetLastError());
-    TRY(sc.down(h_out, dout, slots * j.sp.D));
-    if (h_raw) TRY(sc.down(h_raw, draw, slots * F110_NBR_NCHANNELS));
-    if (h_idx) TRY(sc.down(h_idx, didx, slots));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return sc.finish();
 }
 
 // ---- rendering --------------------------------------------------------------------------------------------------------------
@@ -5752,14 +5653,11 @@ static int job_unit_source(f110_sim *h, Scratch &sc, int slot, bool track, UnitR
 {
     const size_t M = u.cnt.size();
     u.kc = slot_consts(h, slot);
-    double *dcols = nullptr, *dpar = nullptr;
-    int32_t *dcnt = nullptr;
-    ScanConst *dk = nullptr;
-    TRY(sc.up(u.cols.data(), u.cols.size(), &dcols));
-    TRY(sc.up(u.cnt.data(), u.cnt.size(), &dcnt));
-    TRY(sc.up(&u.kc, 1, &dk));
-    if (h_params) TRY(sc.up(h_params, M * NPARAMS, &dpar));
-    j.maps = dk;
+    double *dcols = sc.in(u.cols.data(), u.cols.size());
+    j.buf_cnt = sc.in(u.cnt.data(), u.cnt.size());
+    j.maps = sc.in(&u.kc, 1);
+    j.params = h_params ? sc.in(h_params, M * NPARAMS) : h->d_params;
+    TRY(sc.ready());
     j.tracks = track ? h->d_tracks : nullptr;
     j.unit_slot = slot;
     j.A = 1;
@@ -5768,8 +5666,6 @@ static int job_unit_source(f110_sim *h, Scratch &sc, int slot, bool track, UnitR
     j.params_per_agent = h_params ? 1 : 0;
     j.state = dcols;
     j.steer_buf = dcols + 7 * M;
-    j.buf_cnt = dcnt;
-    j.params = h_params ? dpar : h->d_params;
     job_step_consts(h, j);
     return F110_OK;
 }
@@ -5940,32 +5836,22 @@ static void opp_predict_launch(const f110_sim *h, const Job &j, const OppSpec &s
 }
 
 // a unit form's side of the term: the opponent rows, the settings and the buffers into scratch memory, the predictions on the
-// handle's stream, and the lanes' view
+// handle's stream, the lanes' view, and what of it the caller asked back
 template <typename Job>
-static int opp_unit_prepare(f110_sim *h, Scratch &sc, const Job &j, const OppUnit &u, int K, int H, int repeat, OppLane &lane, double **dtable)
+static int opp_unit_prepare(f110_sim *h, Scratch &sc, const Job &j, const OppUnit &u, int K, int H, int repeat, OppLane &lane)
 {
     const size_t M = (size_t)j.count;
-    double *drows = nullptr, *draw = nullptr;
-    float *dout = nullptr;
-    OppSpec *dspec = nullptr;
-    *dtable = nullptr;
-    TRY(sc.up(&u.sp, 1, &dspec));
-    if (u.Ao > 0) {
-        TRY(sc.up(u.h_rows, M * u.Ao * 4, &drows));
-        TRY(sc.up<double>(nullptr, M * u.Ao * H * 2, dtable));
-    }
-    TRY(sc.up<double>(nullptr, M * K * 2, &draw));
-    TRY(sc.up<float>(nullptr, M * K * 2, &dout));
-    opp_predict_launch(h, j, u.sp, H, repeat, 0, (int)M, u.Ao, nullptr, drows, nullptr, *dtable, h->stream);
-    lane = OppLane{*dtable, dspec, dout, draw, u.Ao, 0};
-    return F110_OK;
-}
-
-static int opp_unit_collect(f110_sim *h, Scratch &sc, const OppUnit &u, const OppLane &lane, const double *dtable, size_t M, int K, int H)
-{
-    if (u.h_pred && u.Ao > 0) TRY(sc.down(u.h_pred, dtable, M * u.Ao * H * 2));
-    if (u.h_raw) TRY(sc.down(u.h_raw, (const double *)lane.raw, M * K * 2));
-    if (u.h_out) TRY(sc.down(u.h_out, (const float *)lane.out, M * K * 2));
+    const OppSpec *dspec = sc.in(&u.sp, 1);
+    const double *drows = u.Ao > 0 ? sc.in(u.h_rows, M * u.Ao * 4) : nullptr;
+    double *dtable = u.Ao > 0 ? sc.tmp<double>(M * u.Ao * H * 2) : nullptr;
+    double *draw = sc.tmp<double>(M * K * 2);
+    float *dout = sc.tmp<float>(M * K * 2);
+    TRY(sc.ready());
+    opp_predict_launch(h, j, u.sp, H, repeat, 0, (int)M, u.Ao, nullptr, drows, nullptr, dtable, h->stream);
+    lane = OppLane{dtable, dspec, dout, draw, u.Ao, 0};
+    sc.later(u.h_pred, dtable, M * u.Ao * H * 2);
+    sc.later(u.h_raw, draw, M * K * 2);
+    sc.later(u.h_out, dout, M * K * 2);
     return F110_OK;
 }
 
@@ -5991,36 +5877,19 @@ static int roll_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const
     ENTER(h);
     if (track || (ou && ou->sp.mode == OPP_TRACK)) TRY(track_upload(h));
     Scratch sc(h);
-    double *dact = nullptr, *draw = nullptr, *dtraw = nullptr, *dend = nullptr;
-    float *dout = nullptr, *dtraj = nullptr;
     TRY(job_unit_source(h, sc, slot, track, rows, h_params, j));
-    TRY(sc.up(h_actions, (j.sp.layout == F110_ROLL_PER_AGENT ? steps : (size_t)j.sp.K * j.sp.H) * 2, &dact));
-    TRY(sc.up<float>(nullptr, cands * j.sp.D, &dout));
-    if (h_raw) {
-        TRY(sc.up<double>(nullptr, cands * F110_ROLL_NCHANNELS, &draw));
-        HIPCHK(h, hipMemsetAsync(draw, 0, cands * F110_ROLL_NCHANNELS * sizeof(double), h->stream));
-    }
-    if (j.sp.traj) TRY(sc.up<float>(nullptr, steps * 4, &dtraj));
-    if (j.sp.traj && h_traj_raw) TRY(sc.up<double>(nullptr, steps * 4, &dtraw));
-    if (track) TRY(sc.up<double>(nullptr, cands * 2, &dend));
-    j.actions = dact;
-    j.out = dout;
-    j.raw = draw;
-    j.traj = dtraj;
-    j.traj_raw = dtraw;
-    j.end_xy = dend;
+    j.actions = sc.in(h_actions, (j.sp.layout == F110_ROLL_PER_AGENT ? steps : (size_t)j.sp.K * j.sp.H) * 2);
+    j.out = sc.out(h_out, cands * j.sp.D);
+    j.raw = sc.out(h_raw, cands * F110_ROLL_NCHANNELS);
+    j.traj = j.sp.traj ? sc.out(h_traj, steps * 4) : nullptr;
+    j.traj_raw = j.sp.traj ? sc.out(h_traj_raw, steps * 4) : nullptr;
+    j.end_xy = track ? sc.tmp<double>(cands * 2) : nullptr;
+    TRY(sc.ready());
+    if (j.raw) HIPCHK(h, hipMemsetAsync(j.raw, 0, cands * F110_ROLL_NCHANNELS * sizeof(double), h->stream));
     OppLane lane{};
-    double *dtable = nullptr;
-    if (ou) TRY(opp_unit_prepare(h, sc, j, *ou, j.sp.K, j.sp.H, j.sp.repeat, lane, &dtable));
+    if (ou) TRY(opp_unit_prepare(h, sc, j, *ou, j.sp.K, j.sp.H, j.sp.repeat, lane));
     roll_launch(j, track, h->stream, ou ? &lane : nullptr);
-    HIPCHK(h, hipGetLastError());
-    TRY(sc.down(h_out, dout, cands * j.sp.D));
-    if (h_raw) TRY(sc.down(h_raw, draw, cands * F110_ROLL_NCHANNELS));
-    if (dtraj) TRY(sc.down(h_traj, dtraj, steps * 4));
-    if (dtraw) TRY(sc.down(h_traj_raw, dtraw, steps * 4));
-    if (ou) TRY(opp_unit_collect(h, sc, *ou, lane, dtable, M, j.sp.K, j.sp.H));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return sc.finish();
 }
 
 int f110_rollout_batch(f110_sim *h, const f110_rollout *spec, int32_t slot, const double *h_start, const double *h_params, const double *h_actions,
@@ -6364,48 +6233,28 @@ static int mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const do
     TRY(jump_ensure(h, h->d_mppi_jump, mppi_jump_table, kMppiJumps));
     if (track || (ou && ou->sp.mode == OPP_TRACK)) TRY(track_upload(h));
     Scratch sc(h);
-    double *dnom = nullptr, *dV = nullptr, *dcost = nullptr, *dend = nullptr, *dw = nullptr, *dact = nullptr;
-    int32_t *dfresh = nullptr;
-    uint64_t *dstr = nullptr;
-    MppiSpec *dspec = nullptr;
-    float *dinfo = nullptr;
     TRY(job_unit_source(h, sc, slot, track, rows, h_params, j));
-    if (h_fresh) TRY(sc.up(h_fresh, M, &dfresh));
-    TRY(sc.up(&j.sp, 1, &dspec));
-    TRY(sc.up((const double *)h_nominal, M * seq, &dnom));
-    TRY(sc.up((const uint64_t *)h_streams, 4 * M, &dstr));
-    TRY(sc.up<double>(nullptr, cands * seq, &dV));
-    TRY(sc.up<double>(nullptr, cands, &dcost));
-    TRY(sc.up<double>(nullptr, cands, &dw));
-    TRY(sc.up<double>(nullptr, 2 * M, &dact));
-    TRY(sc.up<float>(nullptr, 4 * M, &dinfo));
-    if (track) TRY(sc.up<double>(nullptr, 2 * cands, &dend));
-    j.step_count = dfresh;
+    j.step_count = sc.in(h_fresh, M);
+    j.sp_dev = sc.in(&j.sp, 1);
+    j.nominal = sc.inout(h_nominal, M * seq);
+    j.streams = sc.inout(h_streams, 4 * M);
+    j.V = sc.tmp<double>(cands * seq);
+    j.cost = sc.tmp<double>(cands);
+    j.weight = sc.tmp<double>(cands);
+    j.actions = sc.tmp<double>(2 * M);
+    j.info = sc.tmp<float>(4 * M);
+    j.end_xy = track ? sc.tmp<double>(2 * cands) : nullptr;
+    TRY(sc.ready());
+    sc.later(h_actions, j.actions, 2 * M);
+    sc.later(h_info, j.info, 4 * M);
+    sc.later(h_cand, j.V, cands * seq);
+    sc.later(h_cost, j.cost, cands);
+    sc.later(h_weight, j.weight, cands);
     job_rng_tables(h, j, h->d_mppi_jump, kMppiJumps);
-    j.nominal = dnom;
-    j.streams = dstr;
-    j.V = dV;
-    j.cost = dcost;
-    j.end_xy = dend;
-    j.weight = dw;
-    j.actions = dact;
-    j.info = dinfo;
-    j.sp_dev = dspec;
     OppLane lane{};
-    double *dtable = nullptr;
-    if (ou) TRY(opp_unit_prepare(h, sc, j, *ou, j.sp.K, j.sp.H, j.sp.repeat, lane, &dtable));
+    if (ou) TRY(opp_unit_prepare(h, sc, j, *ou, j.sp.K, j.sp.H, j.sp.repeat, lane));
     mppi_launch(j, h->stream, ou ? &lane : nullptr);
-    HIPCHK(h, hipGetLastError());
-    TRY(sc.down(h_nominal, dnom, M * seq));
-    TRY(sc.down(h_streams, dstr, 4 * M));
-    if (h_actions) TRY(sc.down(h_actions, dact, 2 * M));
-    if (h_info) TRY(sc.down(h_info, dinfo, 4 * M));
-    if (h_cand) TRY(sc.down(h_cand, dV, cands * seq));
-    if (h_cost) TRY(sc.down(h_cost, dcost, cands));
-    if (h_weight) TRY(sc.down(h_weight, dw, cands));
-    if (ou) TRY(opp_unit_collect(h, sc, *ou, lane, dtable, M, j.sp.K, j.sp.H));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return sc.finish();
 }
 
 int f110_mppi_batch(f110_sim *h, const f110_mppi *spec, int32_t slot, const double *h_start, const double *h_params, const int32_t *h_fresh, int32_t m,
@@ -6655,70 +6504,38 @@ int f110_pf_batch(f110_sim *h, const f110_pf *spec, int32_t slot, const double *
     ENTER(h);
     TRY(jump_ensure(h, h->d_pf_jump, pf_jump_table, kPfJumps));
     Scratch sc(h);
-    double *dcols = nullptr, *dscans = nullptr, *dX0 = nullptr, *dX1 = nullptr, *dW = nullptr, *dlast = nullptr, *dcum = nullptr, *dlogw = nullptr;
-    double *dpose = nullptr, *dnoise = nullptr, *dexp = nullptr;
-    int32_t *dfresh = nullptr, *danc = nullptr;
-    uint64_t *dstr = nullptr;
-    ScanConst *dk = nullptr;
-    PfPlan *dplan = nullptr;
-    PfHdr *dhdr = nullptr;
-    float *dinfo = nullptr;
-    TRY(sc.up(cols.data(), cols.size(), &dcols));
-    TRY(sc.up(h_scans, M * B, &dscans));
-    TRY(sc.up(&kc, 1, &dk));
-    if (h_fresh) TRY(sc.up(h_fresh, M, &dfresh));
-    TRY(sc.up((const double *)h_particles, 3 * parts, &dX0));
-    TRY(sc.up<double>(nullptr, 3 * parts, &dX1));
-    TRY(sc.up((const double *)h_weights, parts, &dW));
-    TRY(sc.up((const double *)h_last, 3 * M, &dlast));
-    TRY(sc.up((const uint64_t *)h_streams, 4 * M, &dstr));
-    TRY(sc.up<double>(nullptr, parts, &dcum));
-    TRY(sc.up<double>(nullptr, parts, &dlogw));
-    TRY(sc.up<PfPlan>(nullptr, M, &dplan));
-    TRY(sc.up<PfHdr>(nullptr, parts, &dhdr));
-    TRY(sc.up<double>(nullptr, 3 * M, &dpose));
-    TRY(sc.up<float>(nullptr, 4 * M, &dinfo));
-    if (h_noise) TRY(sc.up<double>(nullptr, 3 * parts, &dnoise));
-    if (h_anc) TRY(sc.up<int32_t>(nullptr, parts, &danc));
-    if (h_expect) TRY(sc.up<double>(nullptr, parts * j.sp.B, &dexp));
-    j.maps = dk;
+    const double *dcols = sc.in(cols.data(), cols.size());
+    j.scans = sc.in(h_scans, M * B);
+    j.maps = sc.in(&kc, 1);
+    j.step_count = sc.in(h_fresh, M);
+    j.X_in = sc.in(h_particles, 3 * parts);
+    j.X_out = sc.tmp<double>(3 * parts);
+    j.W = sc.inout(h_weights, parts);
+    j.last = sc.inout(h_last, 3 * M);
+    j.streams = sc.inout(h_streams, 4 * M);
+    j.cum = sc.tmp<double>(parts);
+    j.logw = sc.tmp<double>(parts);
+    j.plan = sc.tmp<PfPlan>(M);
+    j.hdr = sc.tmp<PfHdr>(parts);
+    j.pose = sc.tmp<double>(3 * M);
+    j.info = sc.tmp<float>(4 * M);
+    j.noise = sc.out(h_noise, 3 * parts);
+    j.anc = sc.out(h_anc, parts);
+    j.expect = sc.out(h_expect, parts * j.sp.B);
+    TRY(sc.ready());
+    sc.later(h_particles, j.X_out, 3 * parts);
+    sc.later(h_pose, j.pose, 3 * M);
+    sc.later(h_info, j.info, 4 * M);
+    sc.later(h_logw, j.logw, parts);
     j.A = 1;
     j.N = m;
     j.count = m;
     j.px = dcols;
     j.py = dcols + M;
     j.pth = dcols + 2 * M;
-    j.scans = dscans;
-    j.step_count = dfresh;
     pf_job_common(h, j);
-    j.streams = dstr;
-    j.X_in = dX0;
-    j.X_out = dX1;
-    j.W = dW;
-    j.last = dlast;
-    j.cum = dcum;
-    j.plan = dplan;
-    j.hdr = dhdr;
-    j.logw = dlogw;
-    j.noise = dnoise;
-    j.anc = danc;
-    j.expect = dexp;
-    j.pose = dpose;
-    j.info = dinfo;
     pf_launch(j, h->k, h->stream);
-    HIPCHK(h, hipGetLastError());
-    TRY(sc.down(h_particles, dX1, 3 * parts));
-    TRY(sc.down(h_weights, dW, parts));
-    TRY(sc.down(h_last, dlast, 3 * M));
-    TRY(sc.down(h_streams, dstr, 4 * M));
-    if (h_pose) TRY(sc.down(h_pose, dpose, 3 * M));
-    if (h_info) TRY(sc.down(h_info, dinfo, 4 * M));
-    if (h_noise) TRY(sc.down(h_noise, dnoise, 3 * parts));
-    if (h_anc) TRY(sc.down(h_anc, danc, parts));
-    if (h_expect) TRY(sc.down(h_expect, dexp, parts * j.sp.B));
-    if (h_logw) TRY(sc.down(h_logw, dlogw, parts));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return F110_OK;
+    return sc.finish();
 }
 
 // the example policy on poses the caller holds in device memory (the filter's estimates): f110_pure_pursuit_device's launch per env

@@ -1,5 +1,5 @@
 """Who owns device memory: every buffer a handle allocates is given back by close(), by the call that replaces it and by
-the call that disarms its feature, and a refused call allocates nothing that stays.  Held to f110_device_allocs, the process-wide
+the call that disarms its feature, a refused call allocates nothing that stays, and a unit call holds nothing once it has returned.  Held to f110_device_allocs, the process-wide
 count of the library's live device allocations and their bytes: each test creates no handle but its own and compares readings it
 took itself.  Memory the caller owns (DeviceArrays) is not counted.  Nothing here makes an allocation fail: the failure paths are
 the CPU program's (tests/host_harness/devmem_harness.cpp)."""
@@ -201,5 +201,106 @@ def test_refused_calls_do_not_leak(amd):
         b.add_map_image(_image(), 0.0, ORIGIN)
     assert amd.device_allocs() == armed
     assert b.get_mppi_state() is not None and b.localize()[0].shape == (N, 3)   # what was armed is as it was
+    b.close()
+    assert amd.device_allocs() == before
+
+
+# ---- (e) a unit call holds nothing once it has returned -------------------------------------------------------------------------------------
+def _unit_poses(m):
+    th = np.linspace(0.3, 2.3, m)   # on the circle track, heading along it
+    return np.column_stack([3.0 * np.cos(th), 3.0 * np.sin(th), th + np.pi / 2])
+
+
+def _unit_forms(amd, b, m):
+    """(name, call) for every unit form of the Python layer on m rows; each call returns the form's mandatory output"""
+    from f1tenth_gym_amd import _ffi
+    from f1tenth_gym_amd.reset_sampler import stream_words
+    rng = np.random.default_rng(m)
+    poses = _unit_poses(m)
+    scans = rng.uniform(0.5, 8.0, (m, B))
+    verts = np.array([[0.8, 0.15], [0.8, -0.15], [0.2, -0.15], [0.2, 0.15]])   # a car's corners ahead of the origin
+    start = np.zeros((m, 10))
+    start[:, 0], start[:, 1], start[:, 3], start[:, 4] = poses[:, 0], poses[:, 1], 1.0, poses[:, 2]
+    first = lambda r: r[0] if isinstance(r, tuple) else r
+    ro = amd.Rollout(k=4, horizon=4, channels=("alive", "progress"))
+    acts = np.zeros(ro.actions_shape(m))
+    acts[..., 1] = 1.0
+    mp, pf = amd.Mppi(**MPPI), amd.ParticleFilter(**PF)
+    words = np.ascontiguousarray(stream_words(3, max(m, 1))[:m], dtype=np.uint64)
+    opp = np.tile([0.0, 3.0, 1.0, np.pi], (m, 1, 1))   # one opponent per row: x, y, v, theta
+    cloud = poses[:, None, :] + rng.normal(0.0, 0.05, pf.cloud_shape(m))
+    enc = amd.ObsEncoder(sectors=8, frames=2)
+    wp = np.column_stack([_track(amd).xy, np.full(16, 2.0)])
+    forms = [("scan_batch hits=%d lookups=%d" % (hits, lk), lambda hits=hits, lk=lk: first(b.scan_batch(poses, want_hits=hits, want_lookups=lk)))
+             for hits in (False, True) for lk in (False, True)]
+    forms += [
+        ("pure_pursuit_batch", lambda: b.pure_pursuit_batch(wp, poses, 1.0, 1.0, 0.33)),
+        ("noise_rows_batch", lambda: b.noise_rows_batch(7, max(m, 1))[0]),
+        ("obs_encode_batch", lambda: b.obs_encode_batch(enc, scans, np.ones((m, 8)), np.arange(m), np.zeros(enc.shape(m), dtype=np.float32))),
+        ("follow_gap", lambda: b.follow_gap(scans)),
+        ("follow_gap info", lambda: b.follow_gap(scans, info=True)[0]),
+        ("beam_dir_index_batch", lambda: b.beam_dir_index_batch(poses[:, 2])),
+        ("dynamics_batch", lambda: b.dynamics_batch(np.ones((m, 7)), np.ones((m, 2)), amd.DEFAULT_PARAMS)[0]),
+        ("pid_batch", lambda: b.pid_batch(np.ones((m, 4)), amd.DEFAULT_PARAMS)),
+        ("update_pose_batch", lambda: b.update_pose_batch(np.ones((m, 7)), np.zeros((m, 2)), np.zeros(m, dtype=np.int32), np.ones((m, 2)),
+                                                          amd.DEFAULT_PARAMS, 0.01, 1, 0.0)[0]),
+        ("get_vertices_batch", lambda: b.get_vertices_batch(poses, 0.58, 0.31)),
+        ("gjk_batch", lambda: b.gjk_batch(np.tile(verts, (m, 1, 1)), np.tile(verts + 0.1, (m, 1, 1)))),
+        ("collision_multiple_batch", lambda: b.collision_multiple_batch(np.tile(verts, (m, 2, 1, 1)))[0]),
+        ("ttc_batch", lambda: b.ttc_batch(scans, np.ones(m))),
+        ("raycast_batch", lambda: first(b.raycast_batch(np.zeros((m, 3)), np.tile(verts, (m, 1, 1)), scans))),
+        ("get_range_batch", lambda: b.get_range_batch(np.tile([0.0, 0.0, 0.1, 1.0, -1.0, 1.0, 1.0, 0.0], (m, 1)))),
+        ("helper_batch, a map op", lambda: b.helper_batch(_ffi.OP_DISTANCE_TRANSFORM, poses[:, :2])),
+        ("helper_batch, a body op", lambda: b.helper_batch(_ffi.OP_AVG_POINT, np.tile(verts.reshape(1, 8), (m, 1)), n=4)),
+        ("track_project_batch", lambda: b.track_project_batch(poses)),
+        ("track_preview", lambda: b.track_preview(poses, np.zeros(m), amd.TrackPreview(points=4))),
+        ("neighbors", lambda: b.neighbors(np.column_stack([poses, np.ones(m), np.zeros(m)]), amd.Neighbors(k=2), m if m else 1)),
+        ("rollout_rows", lambda: b.rollout_rows(ro, start, acts)),
+        ("rollout_rows raw", lambda: b.rollout_rows(ro, start, acts, raw=True)[0]),
+        ("rollout_opp_rows", lambda: b.rollout_opp_rows(ro, amd.Opponents(), start, acts, opp)["out"]),
+        ("mppi_rows", lambda: b.mppi_rows(mp, start, mp.fresh_nominal(m), words)["actions"]),
+        ("mppi_opp_rows", lambda: b.mppi_opp_rows(mp, amd.Opponents(), 1.0, 1.0, 0.5, start, mp.fresh_nominal(m), words, opp)["actions"]),
+        ("localize_rows", lambda: b.localize_rows(pf, poses, scans, cloud, np.full((m, pf.particles), 1.0 / pf.particles), poses, words)["pose"]),
+    ]
+    if m:   # (an image has no empty form)
+        forms += [("dt_from_bitmap", lambda: b.dt_from_bitmap(_image(8 * m), RES)), ("edt_sq", lambda: b.edt_sq(_image(8 * m) != 0))]
+    return forms
+
+
+def test_unit_calls_hold_nothing_once_returned(amd):
+    from f1tenth_gym_amd import _ffi
+    before, b, slot = _with_map(amd)
+    bare = b.add_map_image(_image(), RES, ORIGIN)   # a slot without a track
+    forms = _unit_forms(amd, b, 3)
+    for name, call in forms:   # grow-only handle buffers and the planner's and the filter's jump constants settle
+        call()
+    held = amd.device_allocs()
+    got = {}
+    for name, call in forms:
+        got[name] = call()
+        assert amd.device_allocs() == held, name
+    # the optional outputs do not change the mandatory ones
+    same = lambda x, y: x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes()
+    for name in ("scan_batch hits=0 lookups=1", "scan_batch hits=1 lookups=0", "scan_batch hits=1 lookups=1"):
+        assert same(got[name], got["scan_batch hits=0 lookups=0"]), name
+    assert same(got["follow_gap info"], got["follow_gap"])
+    assert same(got["rollout_rows raw"], got["rollout_rows"])
+    # an empty batch returns empty and allocates nothing
+    for name, call in _unit_forms(amd, b, 0):
+        if name.split()[0] in ("scan_batch", "dynamics_batch", "track_project_batch", "rollout_rows"):
+            assert call().shape[0] == 0 and amd.device_allocs() == held, name
+    # a call refused behind the handle's entry leaves nothing behind, and the handle works as before
+    poses = _poses()[:3]
+    with pytest.raises(SyntaxError):
+        b.update_pose_batch(np.ones((3, 7)), np.zeros((3, 2)), np.zeros(3, dtype=np.int32), np.ones((3, 2)), amd.DEFAULT_PARAMS, 0.01, 99, 0.0)
+    assert amd.device_allocs() == held
+    rows, out = np.ones((3, 2)), np.zeros((3, 2))
+    assert _ffi.lib().f110_helper_batch(b._h, 9999, _ffi.dptr(rows), 3, 4, _ffi.dptr(out)) == _ffi.ERR_INVALID
+    assert "unknown op" in _ffi.last_error(b._h) and amd.device_allocs() == held
+    with pytest.raises(_ffi.F110LibraryError, match="has no track"):
+        b.track_project_batch(poses, slot=bare)
+    assert amd.device_allocs() == held
+    assert same(b.scan_batch(_unit_poses(3)), got["scan_batch hits=0 lookups=0"])
+    assert amd.device_allocs() == held
     b.close()
     assert amd.device_allocs() == before
