@@ -444,6 +444,57 @@ class BatchSim(object):
         ob = Obstacles.coerce(obstacles)
         check(_ffi.lib().f110_set_map_obstacles(self._h, int(slot), ob.structs(), len(ob)), self._h)
 
+    # ---- a corridor carved into a map slot (extension)
+    @staticmethod
+    def _corridor_args(tm):
+        from .trackgen import TrackMap
+        tm = TrackMap.coerce(tm)
+        xy, hw = tm.points(), np.ascontiguousarray(tm.widths(), dtype=np.float64)
+        return tm, xy, hw, (dptr(xy), dptr(hw), int(xy.shape[0]), int(tm.track.closed))
+
+    def add_track_map(self, tm):
+        """register a BASE map slot whose distance table is the corridor of `tm` (a TrackMap; a Track or a dict of random_track's
+        arguments are coerced), carved on the device in tm's frame; the line becomes the slot's track.  Returns the slot
+        (set_env_maps); obstacle slots may be derived from it."""
+        tm, xy, hw, line = self._corridor_args(tm)
+        slot = C.c_int32(0)
+        check(_ffi.lib().f110_add_map_corridor(self._h, *line, tm.shape[0], tm.shape[1], tm.resolution, tm.origin[0], tm.origin[1], tm.origin[2],
+                                               C.byref(slot)), self._h)
+        self.track_maps = dict(getattr(self, "track_maps", {}))
+        self.track_maps[int(slot.value)] = tm
+        self.set_track(tm.track, slot=int(slot.value))
+        return int(slot.value)
+
+    def set_track_map(self, slot, tm):
+        """re-carve a slot of add_track_map in place with another TrackMap of the same frame (ValueError otherwise) and make its line
+        the slot's track: ordered behind the steps in flight and in front of the next one.  Obstacle slots derived from it keep
+        their old contents until set_obstacles re-stamps them."""
+        tm, xy, hw, line = self._corridor_args(tm)
+        old = getattr(self, "track_maps", {}).get(int(slot))
+        if old is not None and not old.same_frame(tm):
+            raise ValueError("set_track_map: slot %d was carved in the frame %r x %r at %g m, the new map has %r x %r at %g m"
+                             % (int(slot), old.shape, old.origin, old.resolution, tm.shape, tm.origin, tm.resolution))
+        check(_ffi.lib().f110_set_map_corridor(self._h, int(slot), *line), self._h)
+        self.track_maps = dict(getattr(self, "track_maps", {}))
+        self.track_maps[int(slot)] = tm
+        self.set_track(tm.track, slot=int(slot))
+
+    def corridor_mask(self, tm):
+        """f110_corridor_mask_batch (unit form): the carved mask of `tm` uint8 [H][W] (row 0 = bottom, 1 = carved, the border ring 0)
+        and the number of carved cells"""
+        tm, xy, hw, line = self._corridor_args(tm)
+        mask, carved = np.zeros(tm.shape, dtype=np.uint8), np.zeros(1, dtype=np.int64)
+        check(_ffi.lib().f110_corridor_mask_batch(self._h, *line, tm.shape[0], tm.shape[1], *tm.frame(), mask.ctypes.data_as(_ffi._u8p),
+                                                  carved.ctypes.data_as(_ffi._i64p)), self._h)
+        return mask, int(carved[0])
+
+    def corridor_times(self):
+        """f110_map_corridor_times: {'mask', 'edt'} in ms of the last add_track_map / set_track_map, by HIP events: the mask kernel
+        alone and the two passes of the distance transform"""
+        ms = np.zeros(2)
+        check(_ffi.lib().f110_map_corridor_times(self._h, dptr(ms)), self._h)
+        return dict(mask=float(ms[0]), edt=float(ms[1]))
+
     # ---- a slot's centreline loop, extracted on the device (extension, DESIGN §6n)
     def slot_frame(self, slot=0):
         """(res, ox, oy, oc, os) of a map slot as the library holds them"""

@@ -103,6 +103,7 @@ struct f110_sim {
         DevBuf<uint8_t> d_occ;      // f110_render_device's occupancy grid, built on first use
         bool occ_stale = false;     // ... and again after f110_set_map_obstacles re-stamped the table (the allocation stays)
         int base = -1;              // >= 0: a DERIVED slot (f110_add_map_obstacles), stamped from this base slot's table
+        bool carved = false;        // a base slot of f110_add_map_corridor: f110_set_map_corridor may re-carve it in place
     };
     std::vector<MapSlot> extra_maps;
     DevBuf<MapFast> d_maps_fast;
@@ -116,6 +117,16 @@ struct f110_sim {
         DevBuf<ObstBox> boxes;
         DevBuf<double> oob;
     } obst;
+    // f110_*_map_corridor: the line, the carved mask, the column distances and the squared distances, the carved count (grow-only)
+    struct CorridorScratch {
+        DevBuf<double> line;   // [M][2] points, then [S] half widths
+        DevBuf<uint8_t> mask;
+        DevBuf<uint32_t> g, d2;
+        DevBuf<unsigned long long> carved;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // before the mask kernel, behind it, behind the EDT (f110_map_corridor_times)
+        double mask_ms = 0.0;                             // the last carve's mask kernel, read at the call's wait
+        bool timed = false;                               // ev[1], ev[2] bracket an EDT
+    } corr;
     // f110_map_centerline / f110_map_skeleton: the free mask and the two planes the passes ping-pong between ([H][ceil(W / 64)]
     // words each), the per-pass deletion counters, the loop's cells and their table values (grow-only)
     struct CenterlineScratch {
@@ -364,6 +375,19 @@ template <typename T>
 static int dgrow(f110_sim *h, DevBuf<T> &buf, size_t count)
 {
     HIPCHK(h, buf.grow(count));
+    return F110_OK;
+}
+
+// a scratch buffer back at the capacity it had when the call began (a refusal leaves the device allocations as it found them)
+template <typename T>
+static int dshrink(f110_sim *h, DevBuf<T> &buf, size_t was)
+{
+    if (buf.capacity() == was) return F110_OK;
+    if (!was) {
+        buf.reset();
+        return F110_OK;
+    }
+    HIPCHK(h, buf.alloc(was));
     return F110_OK;
 }
 
@@ -1178,6 +1202,8 @@ void f110_destroy(f110_sim *h)
         (void)hipStreamDestroy(h->noise_stream);
     }
     if (h->ev_noise) (void)hipEventDestroy(h->ev_noise);
+    for (hipEvent_t e : h->corr.ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->ev_noise_src) (void)hipEventDestroy(h->ev_noise_src);
     if (h->hb_seq_host) (void)hipHostFree(h->hb_seq_host);
     for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
@@ -1586,6 +1612,176 @@ int f110_set_map_obstacles(f110_sim *h, int32_t slot, const f110_obstacle *h_obs
     }
     ENTER(h);
     return obstacles_stamp(h, who, slot, h_obs, n);
+}
+
+// ---- a corridor carved into a map slot (include/f110.h) -------------------------------------------------------
+static_assert((int)F110_MAX_CORRIDOR_POINTS == kMaxCorridorPoints, "corridor limits");
+
+// the refusals that concern the line alone
+static int corridor_check(f110_sim *h, const char *who, const double *xy, const double *hw, int M, int closed)
+{
+    if (!xy || !hw) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    if (M < (closed ? 3 : 2)) return fail(h, F110_ERR_INVALID, "%s: M = %d points, %s corridor needs at least %d", who, M, closed ? "a closed" : "an open", closed ? 3 : 2);
+    if (M > F110_MAX_CORRIDOR_POINTS) return fail(h, F110_ERR_INVALID, "%s: M = %d points, at most %d are allowed", who, M, (int)F110_MAX_CORRIDOR_POINTS);
+    for (int i = 0; i < 2 * M; ++i)
+        if (!std::isfinite(xy[i])) return fail(h, F110_ERR_INVALID, "%s: point %d is not finite", who, i / 2);
+    const int S = closed ? M : M - 1;
+    for (int i = 0; i < S; ++i) {
+        if (!std::isfinite(hw[i])) return fail(h, F110_ERR_INVALID, "%s: the half width of segment %d is not finite", who, i);
+        if (hw[i] < 0) return fail(h, F110_ERR_INVALID, "%s: the half width of segment %d is negative", who, i);
+    }
+    return F110_OK;
+}
+
+// ... and the frame
+static int corridor_frame_check(f110_sim *h, const char *who, int H, int W, double res, double ox, double oy, double oc, double os)
+{
+    if (H < 1 || W < 1 || H > 16384 || W > 16384 || !(res > 0) || !std::isfinite(res)) return fail(h, F110_ERR_INVALID, "%s: bad shape %dx%d or resolution", who, H, W);
+    if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oc) || !std::isfinite(os)) return fail(h, F110_ERR_INVALID, "%s: the origin is not finite", who);
+    return F110_OK;
+}
+
+static void corridor_mask_launch(f110_sim *h, const double *d_xy, const double *d_hw, int M, int closed, const ObstFrame &fr, int H, int W, uint8_t *d_mask,
+                                 unsigned long long *d_carved)
+{
+    const dim3 grid((unsigned)((W + kCorrTileW - 1) / kCorrTileW), (unsigned)((H + kCorrTileH - 1) / kCorrTileH));   // (H <= 16384: at most 1024 rows of tiles)
+    hipLaunchKernelGGL(k_corridor_mask, grid, dim3(kCorrChunk), 0, h->stream, d_xy, d_hw, M, closed ? M : M - 1, fr, H, W, d_mask, d_carved);
+}
+
+// The mask of a checked line into the handle's scratch on the main stream (the caller went through ENTER), then the call's one
+// wait, for the carved count.  No cell carved: refused there, with the scratch as large as it was; the planes of the distance
+// transform have not been asked for yet.  Otherwise the two EDT passes follow on the stream, without a further wait.  Three
+// events bracket the mask kernel and the EDT for f110_map_corridor_times.
+static int corridor_carve(f110_sim *h, const char *who, const ObstFrame &fr, int H, int W, const double *xy, const double *hw, int M, int closed)
+{
+    f110_sim::CorridorScratch &sc = h->corr;
+    const size_t n = (size_t)H * W, S = (size_t)(closed ? M : M - 1);
+    const size_t was[3] = {sc.line.capacity(), sc.mask.capacity(), sc.carved.capacity()};
+    for (hipEvent_t &e : sc.ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    sc.timed = false;
+    TRY(dgrow(h, sc.line, 2 * (size_t)M + S));
+    TRY(dgrow(h, sc.mask, n));
+    TRY(dgrow(h, sc.carved, 1));
+    double *const d_hw = sc.line + 2 * (size_t)M;
+    HIPCHK(h, hipMemcpyAsync(sc.line, xy, 2 * (size_t)M * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_hw, hw, S * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(sc.carved, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(sc.ev[0], h->stream));
+    corridor_mask_launch(h, sc.line, d_hw, M, closed, fr, H, W, sc.mask, sc.carved);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(sc.ev[1], h->stream));
+    unsigned long long carved = 0;
+    HIPCHK(h, hipMemcpyAsync(&carved, sc.carved, sizeof carved, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    {
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
+        sc.mask_ms = ms;
+    }
+    if (carved == 0) {
+        TRY(dshrink(h, sc.line, was[0]));
+        TRY(dshrink(h, sc.mask, was[1]));
+        TRY(dshrink(h, sc.carved, was[2]));
+        return fail(h, F110_ERR_INVALID, "%s: no cell carved (every half width 0 between cell centres, or the line misses the table's interior)", who);
+    }
+    TRY(dgrow(h, sc.g, n));
+    TRY(dgrow(h, sc.d2, n));
+    HIPCHK(h, hipEventRecord(sc.ev[1], h->stream));   // (again: the EDT's interval begins behind the wait)
+    hipLaunchKernelGGL(k_edt_columns, grid1d(W, 64), dim3(64), 0, h->stream, sc.mask, H, W, sc.g);
+    hipLaunchKernelGGL(k_edt_rows, dim3(H), dim3(256), (size_t)W * sizeof(uint32_t), h->stream, sc.g, H, W, sc.d2);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(sc.ev[2], h->stream));
+    sc.timed = true;
+    return F110_OK;
+}
+
+// the slot's padded copy from the scratch's squared distances, behind corridor_carve on the main stream (no wait: the out-of-bounds
+// value is that of cell [H-1][W-1], a ring cell, so d2 = 0 there and res * sqrt(0) is 0.0 for every finite res > 0)
+static int corridor_table(f110_sim *h, f110_sim::MapSlot &ms, double *oob_dev)
+{
+    const size_t total = (size_t)ms.k.pad_width * ms.k.pad_height;
+    hipLaunchKernelGGL(k_corridor_table, grid1d(total, 256), dim3(256), 0, h->stream, h->corr.d2, ms.k.height, ms.k.width, ms.k.pad_border, ms.k.pad_width,
+                       ms.k.pad_height, ms.k.res, ms.d_dt_pad, oob_dev);
+    HIPCHK(h, hipGetLastError());
+    ms.k.oob_value = 0.0;
+    return F110_OK;
+}
+
+int f110_add_map_corridor(f110_sim *h, const double *h_xy, const double *h_hw, int32_t M, int32_t closed, int32_t H, int32_t W, double res, double ox, double oy,
+                          double oyaw, int32_t *slot)
+{
+    static const char *const who = "f110_add_map_corridor";
+    if (!h || !slot) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    TRY(corridor_check(h, who, h_xy, h_hw, M, closed));
+    TRY(corridor_frame_check(h, who, H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw)));
+    if (!h->has_map) return fail(h, F110_ERR_NO_MAP, "Map is not set for scan simulator.");
+    if (!padded_family(h->cfg.map_layout)) return fail(h, F110_ERR_STATE, "%s needs map_layout = F110_MAP_PADDED_F64", who);
+    f110_sim::MapSlot ms;
+    ms.k = h->k;   // beam / trig / range constants are shared; the map fields follow
+    fill_map_fields(ms.k, H, W, res, ox, oy, std::cos(oyaw), std::sin(oyaw));
+    if (!setup_padded(ms.k)) return fail(h, F110_ERR_INVALID, "%s: a per-env map must fit the padded layout (16-bit cell coordinates, < 4 GiB)", who);
+    ENTER(h);
+    TRY(corridor_carve(h, who, ObstFrame{ms.k.res, ms.k.orig_x, ms.k.orig_y, ms.k.orig_c, ms.k.orig_s}, H, W, h_xy, h_hw, M, closed));
+    TRY(dmalloc(h, &ms.d_dt_pad, (size_t)ms.k.pad_width * ms.k.pad_height));
+    ms.k.pad = ms.d_dt_pad;
+    ms.k.table = ms.k.table_rm = ms.d_dt_pad + (size_t)ms.k.pad_border * ms.k.pad_width + ms.k.pad_border;
+    ms.k.row_bytes = ms.k.pad_row_bytes;
+    ms.carved = true;
+    TRY(corridor_table(h, ms, nullptr));
+    h->extra_maps.push_back(std::move(ms));
+    *slot = (int32_t)h->extra_maps.size();
+    return F110_OK;
+}
+
+int f110_set_map_corridor(f110_sim *h, int32_t slot, const double *h_xy, const double *h_hw, int32_t M, int32_t closed)
+{
+    static const char *const who = "f110_set_map_corridor";
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "%s: null argument", who);
+    TRY(corridor_check(h, who, h_xy, h_hw, M, closed));
+    if (slot < 0 || slot > (int)h->extra_maps.size())
+        return fail(h, F110_ERR_INVALID, "%s: slot %d, but %d maps are registered", who, slot, 1 + (int)h->extra_maps.size());
+    if (slot == 0 || !h->extra_maps[slot - 1].carved) return fail(h, F110_ERR_INVALID, "%s: slot %d was not carved (f110_add_map_corridor makes one)", who, slot);
+    ENTER(h);
+    f110_sim::MapSlot &ms = h->extra_maps[slot - 1];
+    TRY(corridor_carve(h, who, ObstFrame{ms.k.res, ms.k.orig_x, ms.k.orig_y, ms.k.orig_c, ms.k.orig_s}, ms.k.height, ms.k.width, h_xy, h_hw, M, closed));
+    TRY(corridor_table(h, ms, (h->d_maps_full && slot < h->n_maps_dev) ? &h->d_maps_full[slot].oob_value : nullptr));
+    ms.occ_stale = true;
+    return F110_OK;
+}
+
+int f110_map_corridor_times(f110_sim *h, double *ms)
+{
+    if (!h || !ms) return fail(h, F110_ERR_INVALID, "f110_map_corridor_times: null argument");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    f110_sim::CorridorScratch &sc = h->corr;
+    ms[0] = sc.mask_ms;
+    ms[1] = 0.0;
+    if (sc.timed) {
+        float edt = 0.f;
+        HIPCHK(h, hipEventSynchronize(sc.ev[2]));
+        HIPCHK(h, hipEventElapsedTime(&edt, sc.ev[1], sc.ev[2]));
+        ms[1] = edt;
+    }
+    return F110_OK;
+}
+
+int f110_corridor_mask_batch(f110_sim *h, const double *h_xy, const double *h_hw, int32_t M, int32_t closed, int32_t H, int32_t W, double res, double ox, double oy,
+                             double oc, double os, uint8_t *h_mask, int64_t *h_carved)
+{
+    static const char *const who = "f110_corridor_mask_batch";
+    if (!h || !h_mask || !h_carved) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    TRY(corridor_check(h, who, h_xy, h_hw, M, closed));
+    TRY(corridor_frame_check(h, who, H, W, res, ox, oy, oc, os));
+    ENTER(h);
+    Scratch s(h);
+    const double *d_xy = s.in(h_xy, 2 * (size_t)M), *d_hw = s.in(h_hw, (size_t)(closed ? M : M - 1));
+    uint8_t *d_mask = s.out(h_mask, (size_t)H * W);
+    unsigned long long *d_carved = s.out(reinterpret_cast<unsigned long long *>(h_carved), 1);
+    TRY(s.ready());
+    HIPCHK(h, hipMemsetAsync(d_carved, 0, sizeof(unsigned long long), h->stream));
+    corridor_mask_launch(h, d_xy, d_hw, M, closed, ObstFrame{res, ox, oy, oc, os}, H, W, d_mask, d_carved);
+    return s.finish();
 }
 
 int f110_slot_shape(f110_sim *h, int32_t slot, int32_t *H, int32_t *W)

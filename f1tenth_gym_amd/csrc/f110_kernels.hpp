@@ -3402,6 +3402,113 @@ __global__ void __launch_bounds__(256) k_obst_rows(const uint32_t *__restrict__ 
     *out = obst_value(bv, best, res);
 }
 
+// ---- a corridor carved into a map slot (f110_add_map_corridor / f110_set_map_corridor) ----------------------------
+// The carved mask [H][W], 1 = carved, in the bitmap convention k_edt_columns reads (row 0 = bottom, non-zero = free), the border
+// ring already 0.  A workgroup of four waves takes a tile of kCorrTileH x kCorrTileW cells: lane = column, wave w the rows w, w + 4,
+// w + 8, w + 12 of the tile.  It first walks the S segments kCorrChunk at a time, one per lane, and keeps in LDS those whose capsule
+// can reach the tile (corridor_reaches: conservative); a list that fills up is swept against the tile's cells at once (a round) and
+// started again, so no kept segment is dropped.  A cell leaves a sweep at its first hit and is not tested again; a tile that keeps
+// nothing stores zeros without a cell test.  The carved cells are counted by ballot per row and one atomic per wave.
+__global__ void __launch_bounds__(kCorrChunk) k_corridor_mask(const double *__restrict__ xy, const double *__restrict__ hw, int M, int S, ObstFrame f, int H, int W,
+                                                              uint8_t *__restrict__ mask, unsigned long long *__restrict__ carved)
+{
+    static_assert(kCorrChunk == 256 && kCorrTileW == 64 && kCorrTileH == 16 && kCorrCap >= kCorrChunk,
+                  "four waves, a lane per column, four rows per wave; what a chunk leaves behind a round fits the list");
+    __shared__ CorridorSeg list[kCorrCap];
+    __shared__ int wave_kept[4];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c0 = (int)blockIdx.x * kCorrTileW, r0 = (int)blockIdx.y * kCorrTileH;   // (the grid covers the table: c0 < W, r0 < H)
+    const int c1 = (c0 + kCorrTileW < W ? c0 + kCorrTileW : W) - 1, r1 = (r0 + kCorrTileH < H ? r0 + kCorrTileH : H) - 1;
+    const CorridorTile tile = corridor_tile(f, r0, c0, r1, c1);
+    const int c = c0 + lane;
+    double wx[4], wy[4];
+    unsigned live = 0, hit = 0;   // bit q: the cell of row r0 + wave + 4 q is still undecided / is carved
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int r = r0 + wave + 4 * q;
+        wx[q] = wy[q] = 0.0;
+        if (r > 0 && r < H - 1 && c > 0 && c < W - 1) {   // inside the ring
+            live |= 1u << q;
+            cell_centre(f, r, c, wx[q], wy[q]);
+        }
+    }
+    const auto sweep = [&](int count) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!((live >> q) & 1u)) continue;
+            for (int i = 0; i < count; ++i)
+                if (corridor_hit(list[i], wx[q], wy[q])) {
+                    hit |= 1u << q;
+                    live &= ~(1u << q);
+                    break;
+                }
+        }
+    };
+    int n = 0;   // the list's length (the same in every lane)
+    for (int s0 = 0; s0 < S; s0 += kCorrChunk) {
+        const int s = s0 + tid;
+        bool keep = false;
+        double ax = 0.0, ay = 0.0, bx = 0.0, by = 0.0, w = 0.0;
+        if (s < S) {
+            const int e = s + 1 == M ? 0 : s + 1;
+            ax = xy[2 * s];
+            ay = xy[2 * s + 1];
+            bx = xy[2 * e];
+            by = xy[2 * e + 1];
+            w = hw[s];
+            keep = corridor_reaches(ax, ay, bx, by, w, tile);
+        }
+        const unsigned long long kept = __ballot(keep);
+        if (lane == 0) wave_kept[wave] = __popcll(kept);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int k = wave_kept[v];
+            before += v < wave ? k : 0;
+            total += k;
+        }
+        const int pos = n + before + __popcll(kept & ((1ull << lane) - 1ull));
+        int slot = keep ? corridor_list_slot(pos, true) : -1;
+        if (slot >= 0) list[slot] = corridor_seg(ax, ay, bx, by, w);
+        if (n + total > kCorrCap) {   // workgroup-uniform: the list is full, the chunk has more
+            __syncthreads();
+            sweep(kCorrCap);
+            __syncthreads();
+            slot = keep ? corridor_list_slot(pos, false) : -1;
+            if (slot >= 0) list[slot] = corridor_seg(ax, ay, bx, by, w);
+            n += total - kCorrCap;
+        } else {
+            n += total;
+        }
+        __syncthreads();   // the list is written, and wave_kept has been read before the next chunk writes it
+    }
+    sweep(n);
+    unsigned mine = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int r = r0 + wave + 4 * q;
+        const bool on = (hit >> q) & 1u;
+        if (c < W && r < H) mask[(size_t)r * W + c] = on ? 1 : 0;
+        mine += (unsigned)__popcll(__ballot(on));
+    }
+    if (lane == 0 && mine) atomicAdd(carved, (unsigned long long)mine);
+}
+
+// The slot's padded copy straight from the squared distances: res * sqrt(d2) (k_dt_from_d2's expression) inside, the value of cell
+// [H-1][W-1] in the border (k_build_padded's rule), which also goes into the slot's ScanConst on the device when there is one.
+__global__ void __launch_bounds__(256) k_corridor_table(const uint32_t *__restrict__ d2, int H, int W, int b, int Wp, int Hp, double res, double *__restrict__ pad,
+                                                        double *__restrict__ oob_dev)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)Wp * Hp) return;
+    const int r = (int)(i / Wp) - b, c = (int)(i % Wp) - b;
+    const bool inside = (r >= 0) & (r < H) & (c >= 0) & (c < W);
+    const double v = res * sqrt((double)d2[inside ? (size_t)r * W + c : (size_t)H * W - 1]);
+    pad[i] = v;
+    if (i == 0 && oob_dev) *oob_dev = v;   // (cell 0 of the padded copy is a border cell, or with b = 0 a ring cell: the same value)
+}
+
 // ---- centreline extraction (include/f110.h, f110_map_centerline) --------------------------------------------------
 // The mask is a bit plane [H][Ww] of 64-bit words, Ww = ceil(W / 64): bit b of word w is column 64 w + b, bits from column W on
 // are 0 in every plane.  The per-word decisions are f110_math.hpp's cl_*.

@@ -1917,10 +1917,18 @@ struct ObstFrame {
 
 // Is the centre of table cell (r, col) inside the shape?  include/f110.h states the rule; float64 in exactly this order, no
 // contraction, no trigonometry: the NumPy model (tests/obstacles_ref.py) evaluates the same expressions and agrees bit for bit.
-F110_HD bool obstacle_hit(const Obstacle &o, const ObstFrame &f, int r, int col)
+// the centre of table cell (r, col) in map coordinates: the stamp rule's px, py, wx, wy (the corridor rule's too)
+F110_HD void cell_centre(const ObstFrame &f, int r, int col, double &wx, double &wy)
 {
     const double px = ((double)col + 0.5) * f.res, py = ((double)r + 0.5) * f.res;
-    const double wx = f.ox + (px * f.oc - py * f.os), wy = f.oy + (px * f.os + py * f.oc);
+    wx = f.ox + (px * f.oc - py * f.os);
+    wy = f.oy + (px * f.os + py * f.oc);
+}
+
+F110_HD bool obstacle_hit(const Obstacle &o, const ObstFrame &f, int r, int col)
+{
+    double wx, wy;
+    cell_centre(f, r, col, wx, wy);
     const double dx = wx - o.x, dy = wy - o.y;
     if (o.shape == OBST_DISC) return dx * dx + dy * dy <= o.half_length * o.half_length;
     const double u = dx * o.c + dy * o.s, v = -dx * o.s + dy * o.c;
@@ -1953,6 +1961,89 @@ F110_HD void obstacle_cell_box(const Obstacle &o, const ObstFrame &f, int H, int
         r1 = H - 1;
     }
 }
+
+// ------------------------------------------------------------------ corridors (f110_add_map_corridor)
+// One text for k_corridor_mask and the host harness (tests/host_harness/corridor_harness.hip).
+constexpr int kMaxCorridorPoints = 65536;
+constexpr int kCorrTileW = 64, kCorrTileH = 16;   // a workgroup's tile of cells: a wave's lanes are 64 columns of one row
+constexpr int kCorrChunk = 256;                   // segments per cooperative step of the cull walk: one per lane of the workgroup
+constexpr int kCorrCap = 256;                     // segments the kept list holds (16 KiB of LDS, >= a chunk); a tile that keeps more works in rounds
+
+// a segment as the rule reads it: the ends and what the rule forms from them once (the same expressions, so the same bits)
+struct CorridorSeg {
+    double ax, ay, bx, by, dx, dy, L2, h2;
+};
+
+F110_HD CorridorSeg corridor_seg(double ax, double ay, double bx, double by, double hw)
+{
+    const double dx = bx - ax, dy = by - ay;
+    return CorridorSeg{ax, ay, bx, by, dx, dy, dx * dx + dy * dy, hw * hw};
+}
+
+// Is the point (wx, wy) — a cell centre — in the segment's capsule?  include/f110.h states the rule; float64 in exactly this order,
+// no contraction, no division, no square root: the NumPy model (tests/trackgen_ref.py) agrees bit for bit.
+F110_HD bool corridor_hit(const CorridorSeg &s, double wx, double wy)
+{
+    const double ux = wx - s.ax, uy = wy - s.ay;
+    const double t = ux * s.dx + uy * s.dy;
+    if (t <= 0.0) return ux * ux + uy * uy <= s.h2;
+    if (t >= s.L2) {
+        const double vx = wx - s.bx, vy = wy - s.by;
+        return vx * vx + vy * vy <= s.h2;
+    }
+    const double cr = ux * s.dy - uy * s.dx;
+    return cr * cr <= s.h2 * s.L2;
+}
+
+// the circle around the centres of the cells [r0, r1] x [c0, c1] of a tile (map coordinates), and the size of its numbers
+struct CorridorTile {
+    double cx, cy, rad, mag;
+};
+
+// The frame's map is affine, so the centres of a tile's cells lie in the parallelogram of its four corner cells' centres, and the
+// corner farthest from the parallelogram's centre bounds them all (whatever oc, os are: they need not be a rotation).
+F110_HD CorridorTile corridor_tile(const ObstFrame &f, int r0, int c0, int r1, int c1)
+{
+    double x[4], y[4];
+    cell_centre(f, r0, c0, x[0], y[0]);
+    cell_centre(f, r0, c1, x[1], y[1]);
+    cell_centre(f, r1, c0, x[2], y[2]);
+    cell_centre(f, r1, c1, x[3], y[3]);
+    CorridorTile t;
+    t.cx = 0.25 * x[0] + 0.25 * x[1] + 0.25 * x[2] + 0.25 * x[3];
+    t.cy = 0.25 * y[0] + 0.25 * y[1] + 0.25 * y[2] + 0.25 * y[3];
+    double far2 = 0.0;
+    t.mag = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        const double ex = x[i] - t.cx, ey = y[i] - t.cy, d2 = ex * ex + ey * ey;
+        far2 = d2 > far2 ? d2 : far2;
+        const double m = fabs(x[i]) + fabs(y[i]);
+        t.mag = m > t.mag ? m : t.mag;   // (a NaN corner: the comparisons drop it; corridor_reaches then sees rad or d2 NaN and keeps)
+    }
+    t.rad = sqrt(far2);
+    return t;
+}
+
+// Can the capsule of segment a -> b with half width hw reach a cell centre of the tile?  Conservative: the capsule lies in the
+// circle of radius |b - a| / 2 + hw around the segment's middle, and the two circles are compared with a margin of 1e-9 of their
+// radii plus 1e-9 of the magnitude of the numbers involved — many orders above the rounding of this arithmetic and of
+// corridor_hit's, so rounding can only keep too many.  Numbers whose squares may overflow (beyond 1e150), and anything that
+// compares as NaN, keep the segment: corridor_hit decides then.
+F110_HD bool corridor_reaches(double ax, double ay, double bx, double by, double hw, const CorridorTile &t)
+{
+    const double mag = fabs(ax) + fabs(ay) + fabs(bx) + fabs(by) + hw + t.mag + t.rad;
+    if (!(mag <= 1e150)) return true;
+    const double mx = 0.5 * ax + 0.5 * bx, my = 0.5 * ay + 0.5 * by;
+    const double ex = bx - ax, ey = by - ay;
+    const double R = (0.5 * sqrt(ex * ex + ey * ey) + hw + t.rad) * (1.0 + 1e-9) + 1e-9 * mag;
+    const double qx = t.cx - mx, qy = t.cy - my;
+    return !(qx * qx + qy * qy > R * R);
+}
+
+// The walk's bookkeeping, shared so that the kernel and the host harness cannot drift apart: a chunk's kept segments take the list
+// positions n, n + 1, ... in segment order; the list is swept against the tile's cells when it is full (a round) and the rest of
+// the chunk starts the next list.  pos: where a kept segment of this chunk goes, before (first) or after (!first) the round.
+F110_HD int corridor_list_slot(int pos, bool first) { return first ? (pos < kCorrCap ? pos : -1) : (pos >= kCorrCap ? pos - kCorrCap : -1); }
 
 // ------------------------------------------------------------------ MPPI planner (include/f110.h, f110_mppi)
 // The planner's own arithmetic around roll_candidate: the clamp of a sampled action, the cost of a rolled candidate, the weights and

@@ -27,6 +27,7 @@ from .track_preview import TrackPreview
 from .neighbors import Neighbors
 from .track import Track
 from .centerline import coerce_params
+from .trackgen import TrackMap
 
 try:  # pragma: no cover - gym is absent from the build image
     import gym as _gym
@@ -210,6 +211,13 @@ class F110Env(_EnvBase):
                              device_id=kwargs.get('device_id', 0),
                              map_layout=kwargs.get('map_layout', _ffi.MAP_DEFAULT))
         self.sim.set_map(self.map_path, self.map_ext)
+        # a carved track: track_map= (a TrackMap, a Track or a dict of random_track's arguments) registers its corridor
+        # as slot 1 and runs the env there, with its line as the track unless track= names another; `map` stays slot 0
+        self.track_map, self.map_slot = None, 0
+        if kwargs.get('track_map') is not None:
+            self.track_map = TrackMap.coerce(kwargs['track_map'])
+            self.map_slot = self.sim.batch.add_track_map(self.track_map)
+            self.sim.batch.set_env_maps([self.map_slot])
         # track progress (no reference counterpart): track= adds the obs keys of Simulator.TRACK_KEYS; reward='progress' pays the
         # ego's progress of the step (metres along the track) instead of the reference's constant timestep
         self.reward_mode = _reward_mode(kwargs.get('reward', 'timestep'))
@@ -217,8 +225,11 @@ class F110Env(_EnvBase):
         if kwargs.get('track') is not None:
             track = kwargs['track']
             if _is_centerline(track):   # the map's centreline loop, extracted on the device
-                track = self.sim.batch.centerline(0, **coerce_params(kwargs.get('centerline')))
-            self.track = self.sim.set_track(Track.coerce(track))
+                track = self.sim.batch.centerline(self.map_slot, **coerce_params(kwargs.get('centerline')))
+            self.track = self.sim.set_track(Track.coerce(track), self.map_slot)
+            self.sim.enable_track()
+        elif self.track_map is not None:
+            self.track = self.track_map.track
             self.sim.enable_track()
         elif self.reward_mode == 'progress':
             raise ValueError("reward='progress' needs a track (track=...)")
@@ -238,7 +249,7 @@ class F110Env(_EnvBase):
         # static obstacles: obstacles= puts the env on a slot derived from slot 0 with the shapes stamped in
         self.obstacle_slot = None
         if kwargs.get('obstacles') is not None:
-            self.obstacle_slot = self.sim.batch.add_obstacle_map(kwargs['obstacles'], 0)
+            self.obstacle_slot = self.sim.batch.add_obstacle_map(kwargs['obstacles'], self.map_slot)
             self.sim.batch.set_env_maps([self.obstacle_slot])
         # randomised start poses: random_start= (a ResetSampler or a dict of its settings) makes reset() without
         # poses draw them on the track
@@ -318,7 +329,7 @@ class F110Env(_EnvBase):
     def set_obstacles(self, obstacles):
         """stamp another Obstacles into this env's map (in place when the env already runs on a derived slot)"""
         if self.obstacle_slot is None:
-            self.obstacle_slot = self.sim.batch.add_obstacle_map(obstacles, 0)
+            self.obstacle_slot = self.sim.batch.add_obstacle_map(obstacles, self.map_slot)
             self.sim.batch.set_env_maps([self.obstacle_slot])
         else:
             self.sim.batch.set_obstacles(self.obstacle_slot, obstacles)
@@ -379,6 +390,11 @@ class F110VecEnv(object):
     map slots derived from slot 0 (or base_slot) with the shapes stamped into their distance tables on the device; they are numbered
     after `extra_maps` and usable in `env_map`, and carry their base's track.  `set_obstacles(slot, obstacles)` re-draws one in
     place between episodes.  Obstacles belong to a slot, not to an env: one padded table of device memory per slot.
+
+    Carved tracks (no reference counterpart): `track_maps=[TrackMap | Track | dict(random_track arguments), ...]` registers
+    base map slots whose distance tables are corridors carved around a line on the device, numbered after `extra_maps` and before
+    `obstacle_maps` (which may derive from them); each line is its slot's track unless `tracks=` names another.
+    `set_track_map(slot, tm)` re-carves one in place between episodes, in the same frame.
 
     Track progress (no reference counterpart): `track=` (a Track, an [M][2] array or a csv path) puts a raceline on
     slot 0, `tracks={slot: track}` one per map slot.  The observation then also carries progress, progress_delta,
@@ -456,6 +472,10 @@ class F110VecEnv(object):
         tracks = dict(kwargs.get('tracks') or {})
         if kwargs.get('track') is not None:
             tracks[0] = kwargs['track']
+        # carved tracks: slots behind extra_maps, each with its generating line as the track (a tracks= entry wins)
+        track_maps = [TrackMap.coerce(item) for item in kwargs.get('track_maps') or ()]
+        for i, tm in enumerate(track_maps):
+            tracks.setdefault(1 + len(kwargs.get('extra_maps', ())) + i, tm.track)
         self.reward_mode = _reward_mode(kwargs.get('reward', 'timestep'))
         if self.reward_mode == 'progress' and not tracks:
             raise ValueError("reward='progress' needs a track (track= or tracks=)")
@@ -541,6 +561,11 @@ class F110VecEnv(object):
         for path, ext in kwargs.get('extra_maps', ()):
             self.sim.batch.add_map(path, ext)
             self.map_slots.append((path, ext))
+        # carved tracks: each registers a base slot whose table is the corridor of its line, carved on the device
+        self.track_maps = {}
+        for tm in track_maps:
+            self.track_maps[self.sim.batch.add_track_map(tm)] = tm
+            self.map_slots.append(tm)
         # track='centerline' (DESIGN §6n): the slot's centreline loop, extracted from its distance table on the device
         self.centerline = kwargs.get('centerline')
         self._extract_centerlines(tracks)
@@ -685,6 +710,15 @@ class F110VecEnv(object):
         """re-stamp the derived slot `slot` (one of obstacle_maps=) with another Obstacles, in place: it applies from the next step
         on, behind whatever step is in flight"""
         self.sim.batch.set_obstacles(slot, obstacles)
+
+    def set_track_map(self, slot, tm):
+        """re-carve the slot `slot` (one of track_maps=) with another TrackMap of the same frame, in place, and make its line the
+        slot's track: it applies from the next step on, behind whatever step is in flight.  Reset the slot's envs afterwards."""
+        tm = TrackMap.coerce(tm)
+        self.sim.batch.set_track_map(slot, tm)
+        self.track_maps[int(slot)] = tm
+        if int(slot) in self.tracks:
+            self.tracks[int(slot)] = tm.track
 
     def device_views(self):
         v = self.sim.batch.device_views()

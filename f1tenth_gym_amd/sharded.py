@@ -100,6 +100,9 @@ class ShardedVecEnv(object):
         if kwargs.get('neighbors') is not None:      # one spec for every shard; obs['neighbors'] is concatenated along the env axis
             from .neighbors import Neighbors
             kwargs['neighbors'] = Neighbors.coerce(kwargs['neighbors'])
+        if kwargs.get('track_maps') is not None:     # one TrackMap per slot for every shard (a dict of random_track's arguments is drawn once)
+            from .trackgen import TrackMap
+            kwargs['track_maps'] = [TrackMap.coerce(tm) for tm in kwargs['track_maps']]
         if kwargs.get('particle_filter') is not None:   # one filter for every shard; a shard's env_base gives its agents their global streams
             from .particle_filter import split_filter
             slot, pf = split_filter(kwargs['particle_filter'])
@@ -259,6 +262,12 @@ class ShardedVecEnv(object):
     def set_obstacles(self, slot, obstacles):
         """F110VecEnv.set_obstacles on every shard (the slots are numbered alike on all of them)"""
         self._each(lambda k, s: s.set_obstacles(slot, obstacles))
+
+    def set_track_map(self, slot, tm):
+        """F110VecEnv.set_track_map on every shard, with one TrackMap (the slots are numbered alike on all of them)"""
+        from .trackgen import TrackMap
+        tm = TrackMap.coerce(tm)
+        self._each(lambda k, s: s.set_track_map(slot, tm))
 
     def set_env_maps(self, env_map):
         ms = [None] * len(self.shards) if env_map is None else self._slices(np.asarray(env_map, dtype=np.int32))

@@ -210,6 +210,50 @@ int f110_get_slot_dt(f110_sim *h, int32_t slot, double *h_dt_out); /* row-major 
 int f110_slot_shape(f110_sim *h, int32_t slot, int32_t *height, int32_t *width);
 int f110_slot_table(f110_sim *h, int32_t slot, const double **d_table, int32_t *row_bytes);
 
+/* Extension: a CORRIDOR carved into a map slot ON THE DEVICE — the step from a line to a distance table.
+ *
+ * A corridor: points xy [M][2] in map (world) coordinates, a `closed` flag, S = closed ? M : M - 1 segments, segment i from point i
+ * to point (i + 1) % M, and one half width hw[i] >= 0 per segment.  Table cell (r, c) — row 0 at the bottom — is CARVED (free) iff
+ * its centre lies in the capsule of some segment; float64 in exactly this order, never contracted, the cell centre (wx, wy) by the
+ * stamp rule's formula above (px, py, wx, wy from res, ox, oy, oc, os), segment a -> b with half width hw:
+ *   ux = wx - ax, uy = wy - ay;  dx = bx - ax, dy = by - ay
+ *   t  = ux*dx + uy*dy;          L2 = dx*dx + dy*dy;      h2 = hw*hw
+ *   t <= 0   : carved iff ux*ux + uy*uy <= h2               (also the whole rule when a == b)
+ *   t >= L2  : vx = wx - bx, vy = wy - by;  carved iff vx*vx + vy*vy <= h2
+ *   else     : cr = ux*dy - uy*dx;          carved iff cr*cr <= h2*L2
+ * No division, no square root, no trigonometric function.  The BORDER RING (row 0, row H-1, column 0, column W-1) is never carved,
+ * so a corridor that leaves the table is still closed by a wall; parts of a corridor outside the table are ignored.  The slot's
+ * table is T[r][c] = res * sqrt((double)d2[r][c]), d2 the exact squared Euclidean distance, in cells, to the nearest cell that is
+ * not carved: the reference pipeline (flip, > 128, resolution * distance_transform_edt), bit for bit, on the image that has the
+ * carved cells at 255 and all others at 0.  Out-of-bounds value and padded border as for every slot: T[H-1][W-1], 0 by the ring.
+ *
+ * f110_add_map_corridor registers a new BASE slot (not a derived one: obstacle slots may be derived from it) with a padded table of
+ * its own, in the frame (res, ox, oy, oyaw); preconditions and size limits as f110_add_map_image; takes effect at the next
+ * f110_set_env_maps.  f110_set_map_corridor re-carves such a slot IN PLACE: same frame, same allocation and address; scratch (the
+ * line, the byte mask, the two planes of the distance transform, the carved count) belongs to the handle and grows with the map,
+ * never with the number of calls.  The update is ordered behind every step in flight (on either env block) and in front of the next
+ * one; it refreshes the out-of-bounds value in the handle's constants and in the device-side slot table of f110_set_env_maps, marks
+ * the slot's cached render occupancy grid stale and leaves track data alone.  A derived obstacle slot of a re-carved base KEEPS ITS
+ * OLD CONTENTS until it is re-stamped (f110_set_map_obstacles stamps from the base's table as it is then).
+ * f110_corridor_mask_batch: the mask alone, for any frame (oc, os as the caller computed them), h_mask [H][W] 1 = carved, *h_carved
+ * their number: what the tests compare cell for cell.
+ * Refused (an error code, a message; nothing launched, nothing written, the slot list and the device allocations unchanged): null
+ * arguments, M < 2 (M < 3 closed), M > F110_MAX_CORRIDOR_POINTS, a non-finite point or width, a negative width, a bad shape (sides
+ * 1 .. 16384) or resolution or a non-finite origin, a map that does not fit the padded layout, a layout other than the padded one,
+ * f110_set_map_corridor on a slot that was not carved.  Decided once the mask exists, before the distance transform runs or any table
+ * is written: NO CELL CARVED (F110_ERR_INVALID; the count is reduced on the device and comes back with the call's one wait). */
+enum { F110_MAX_CORRIDOR_POINTS = 65536 };
+int f110_add_map_corridor(f110_sim *h, const double *h_xy, const double *h_half_width /* [S] */, int32_t M, int32_t closed,
+                          int32_t H, int32_t W, double res, double ox, double oy, double oyaw, int32_t *slot);
+int f110_set_map_corridor(f110_sim *h, int32_t slot, const double *h_xy, const double *h_half_width, int32_t M, int32_t closed);
+int f110_corridor_mask_batch(f110_sim *h, const double *h_xy, const double *h_half_width, int32_t M, int32_t closed,
+                             int32_t H, int32_t W, double res, double ox, double oy, double oc, double os,
+                             uint8_t *h_mask /* [H][W], 1 = carved */, int64_t *h_carved);
+/* the handle's last f110_add_map_corridor / f110_set_map_corridor by HIP events on its stream, milliseconds: ms [2] = the mask kernel
+ * alone (the line already on the device, the mask staying there), the two passes of the distance transform (0 after a call that was
+ * refused for carving nothing).  Waits for that call's distance transform (tools/trackgen_bench.py). */
+int f110_map_corridor_times(f110_sim *h, double *ms /* [2] */);
+
 /* Extension: a map slot's CENTRELINE LOOP, extracted ON THE DEVICE from the slot's distance table T (slot 0, an added
  * slot or a derived obstacle slot), as an ordered cycle of table cells with T at each: what a Track is made of (Track.from_map).
  *
