@@ -23,6 +23,7 @@ from .opponents import Opponents  # noqa: F401
 from .particle_filter import ParticleFilter  # noqa: F401
 from .obstacles import Obstacles  # noqa: F401
 from .trackgen import TrackMap, random_track  # noqa: F401
+from .raceline import Raceline  # noqa: F401
 from . import render  # noqa: F401
 from ._ffi import device_allocs  # noqa: F401
 from .functional import (accl_constraints, steering_constraint, vehicle_dynamics_ks, vehicle_dynamics_st, pid, func_KS, func_ST,  # noqa: F401

@@ -230,6 +230,7 @@ PROTOTYPES = {
     "f110_set_map_corridor": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.c_int32, C.c_int32]),
     "f110_corridor_mask_batch": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_double] * 5 + [_u8p, _i64p]),
     "f110_map_corridor_times": (C.c_int, [C.c_void_p, _dp]),
+    "f110_raceline_batch": (C.c_int, [C.c_void_p, _dp, _dp, _i32p, C.c_int32, C.c_int32, C.c_int32] + [C.c_double] * 5 + [_dp, _i32p] + [_dp] * 6),
     "f110_map_centerline": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, _i32p, _dp, C.c_int32, _i32p, _i64p]),
     "f110_map_skeleton": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _u8p, _i64p]),
     "f110_slot_frame": (C.c_int, [C.c_void_p, C.c_int32, _dp]),

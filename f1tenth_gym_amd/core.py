@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import check, as_f64, dptr, i32ptr, u64ptr
+from ._spec import is_int
 
 DEFAULT_PARAMS = {'mu': 1.0489, 'C_Sf': 4.718, 'C_Sr': 5.4562, 'lf': 0.15875, 'lr': 0.17145,
                   'h': 0.074, 'm': 3.74, 'I': 0.04712, 's_min': -0.4189, 's_max': 0.4189,
@@ -547,6 +548,57 @@ class BatchSim(object):
         cells, hw, deleted = self.centerline_cells(slot, seed, heading, max_passes)
         track = track_from_cells(cells, hw, self.slot_frame(slot), spacing=spacing, smooth=smooth)
         return (track, cells, hw, deleted) if return_cells else track
+
+    # ---- a racing line and a speed profile per closed track, solved on the device (extension)
+    def raceline_batch(self, lines, spec=None, line_iters=None):
+        """f110_raceline_batch (unit form): lines [(q [M][2], w [M]), ...] at the settings `spec` (a Raceline, a dict or None; its
+        spacing plays no part here), line_iters [T] or None -> (alpha, xy, kappa, vx) with the lines' rows one after the other,
+        length [T], lap_time [T]"""
+        from .raceline import Raceline
+        sp = Raceline.coerce(spec)
+        qs = [np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 2) for q, _ in lines]
+        ws = [np.ascontiguousarray(w, dtype=np.float64).reshape(-1) for _, w in lines]
+        if not lines or any(q.shape[0] != w.shape[0] for q, w in zip(qs, ws)):
+            raise ValueError("raceline: at least one line, each with one half width per point")
+        T = len(lines)
+        off = np.zeros(T + 1, dtype=np.int32)
+        off[1:] = np.cumsum([q.shape[0] for q in qs])
+        n = int(off[-1])
+        xy, hw, beta = np.concatenate(qs), np.concatenate(ws), sp.momentum()
+        li = None if line_iters is None else np.ascontiguousarray(line_iters, dtype=np.int32).reshape(T)
+        alpha, out_xy, kappa, vx, length, lap = np.zeros(n), np.zeros((n, 2)), np.zeros(n), np.zeros(n), np.zeros(T), np.zeros(T)
+        check(_ffi.lib().f110_raceline_batch(self._h, dptr(xy), dptr(hw), i32ptr(off), T, sp.levels, sp.iters, sp.margin, sp.v_max, sp.a_lat, sp.a_accel,
+                                             sp.a_brake, dptr(beta) if sp.iters else None, None if li is None else i32ptr(li), dptr(alpha), dptr(out_xy),
+                                             dptr(kappa), dptr(vx), dptr(length), dptr(lap)), self._h)
+        return alpha, out_xy, kappa, vx, length, lap
+
+    def raceline(self, tracks, spec=None):
+        """the raceline of closed tracks that carry a 'half_width' column: `tracks` is a Track, a slot number (that slot's track; on a
+        slot of add_track_map that runs on its generating line, the line with the half widths it was carved with) or a list of either; spec a Raceline, a dict of its settings or None.  One device call for the whole list (a workgroup per line,
+        and one more per line for the same speed profile on the centreline).  Returns closed Tracks (one for one input) with the
+        attribute columns kappa, vx and offset (metres to the left of the centreline) and the attributes lap_time [s], center (the
+        stations as a Track with half_width, kappa, vx) and center_lap_time."""
+        from .raceline import Raceline, assemble
+        from .track import Track
+        sp = Raceline.coerce(spec)
+        single = isinstance(tracks, Track) or is_int(tracks)
+        items = [tracks] if single else list(tracks)
+        src = []
+        for it in items:
+            if is_int(it):
+                if int(it) not in getattr(self, "tracks", {}):
+                    raise ValueError("raceline: map slot %d has no track (set_track, add_track_map or centerline make one)" % int(it))
+                tm = getattr(self, "track_maps", {}).get(int(it))
+                # a carved slot that still runs on its generating line: the half widths it was carved with, not the line's column
+                it = tm.carved_line() if tm is not None and self.tracks[int(it)] is tm.track and tm.track.closed else self.tracks[int(it)]
+            src.append(sp.stations(it))
+        lines, iters = [], []
+        for q, w in src:            # the line, then the same stations with no iteration: the centreline's own profile
+            lines += [(q, w), (q, w)]
+            iters += [sp.iters, 0]
+        out = self.raceline_batch(lines, sp, iters)
+        res = assemble(sp, src, out)
+        return res[0] if single else res
 
     def map_table_address(self, slot=0):
         """(device address of the slot's table cell [0][0], its row pitch in bytes): what the kernels read"""

@@ -1784,6 +1784,103 @@ int f110_corridor_mask_batch(f110_sim *h, const double *h_xy, const double *h_hw
     return s.finish();
 }
 
+// ---- raceline and speed profile (include/f110.h) ---------------------------------------------------------------
+static_assert((int)F110_RACELINE_MAX_POINTS == kRacelineMaxPoints, "raceline limits");
+
+// the refusals that can be decided before the solve; max_M: the longest line
+static int raceline_check(f110_sim *h, const char *who, const double *xy, const double *hw, const int32_t *off, int T, const RacelineSpec &sp, const double *beta,
+                          const int32_t *line_iters, int &max_M)
+{
+    if (T < 1) return fail(h, F110_ERR_INVALID, "%s: T = %d lines", who, T);
+    if (sp.levels < 0 || sp.levels > kRacelineMaxLevels) return fail(h, F110_ERR_INVALID, "%s: levels = %d, 0 .. %d are allowed", who, sp.levels, kRacelineMaxLevels);
+    if (sp.iters < 0 || sp.iters > kRacelineMaxIters) return fail(h, F110_ERR_INVALID, "%s: iters = %d, 0 .. %d are allowed", who, sp.iters, kRacelineMaxIters);
+    const double pos[4] = {sp.v_max, sp.a_lat, sp.a_accel, sp.a_brake};
+    for (double v : pos)
+        if (!(std::isfinite(v) && v > 0.0)) return fail(h, F110_ERR_INVALID, "%s: v_max, a_lat, a_accel and a_brake must be finite and > 0", who);
+    if (!(std::isfinite(sp.margin) && sp.margin >= 0.0)) return fail(h, F110_ERR_INVALID, "%s: margin must be finite and >= 0", who);
+    if (sp.iters > 0 && !beta) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    for (int k = 0; k < sp.iters; ++k)
+        if (!std::isfinite(beta[k])) return fail(h, F110_ERR_INVALID, "%s: beta[%d] is not finite", who, k);
+    if (off[0] != 0) return fail(h, F110_ERR_INVALID, "%s: offsets[0] must be 0", who);
+    max_M = 0;
+    const int unit = 1 << sp.levels;
+    for (int t = 0; t < T; ++t) {
+        const long long M = (long long)off[t + 1] - off[t];
+        if (M > kRacelineMaxPoints) return fail(h, F110_ERR_INVALID, "%s: line %d has %lld points, at most %d are allowed", who, t, M, kRacelineMaxPoints);
+        if (M < 1 || M % unit) return fail(h, F110_ERR_INVALID, "%s: line %d has %lld points, not a multiple of 2^levels = %d", who, t, M, unit);
+        if (M / unit < 8) return fail(h, F110_ERR_INVALID, "%s: line %d has %lld points, fewer than 8 on the coarsest level (2^levels = %d)", who, t, M, unit);
+        if (line_iters && (line_iters[t] < 0 || line_iters[t] > sp.iters))
+            return fail(h, F110_ERR_INVALID, "%s: line %d asks for %d iterations, 0 .. iters = %d are allowed", who, t, line_iters[t], sp.iters);
+        const double *q = xy + 2 * (size_t)off[t], *w = hw + off[t];
+        for (int i = 0; i < (int)M; ++i)
+            if (!std::isfinite(q[2 * i]) || !std::isfinite(q[2 * i + 1]) || !std::isfinite(w[i])) return fail(h, F110_ERR_INVALID, "%s: point %d of line %d is not finite", who, i, t);
+        for (int i = 0; i < (int)M; ++i) {
+            const int im = i == 0 ? (int)M - 1 : i - 1, ip = i + 1 == (int)M ? 0 : i + 1;
+            double nx, ny, b;
+            if (!(rl_frame(q[2 * im], q[2 * im + 1], q[2 * ip], q[2 * ip + 1], w[i], sp.margin, nx, ny, b) > 0.0))
+                return fail(h, F110_ERR_INVALID, "%s: points %d and %d of line %d coincide: point %d has no normal", who, im, ip, t, i);
+        }
+        max_M = std::max(max_M, (int)M);
+    }
+    return F110_OK;
+}
+
+// one workgroup per line; the kernel's lanes by the longest line, its beta table by the iteration count
+static void raceline_launch(f110_sim *h, const RacelineJob &job, int T, int max_M)
+{
+    const bool small = max_M <= 256 * kRacelinePerLane, few = job.sp.iters <= 512;
+    if (small && few) hipLaunchKernelGGL((k_raceline<256, 512>), dim3(T), dim3(256), 0, h->stream, job);
+    else if (small) hipLaunchKernelGGL((k_raceline<256, kRacelineMaxIters>), dim3(T), dim3(256), 0, h->stream, job);
+    else if (few) hipLaunchKernelGGL((k_raceline<1024, 512>), dim3(T), dim3(1024), 0, h->stream, job);
+    else hipLaunchKernelGGL((k_raceline<1024, kRacelineMaxIters>), dim3(T), dim3(1024), 0, h->stream, job);
+}
+
+int f110_raceline_batch(f110_sim *h, const double *h_xy, const double *h_hw, const int32_t *h_off, int32_t T, int32_t levels, int32_t iters, double margin, double v_max,
+                        double a_lat, double a_accel, double a_brake, const double *h_beta, const int32_t *h_line_iters, double *h_alpha, double *h_out_xy,
+                        double *h_kappa, double *h_vx, double *h_length, double *h_lap_time)
+{
+    static const char *const who = "f110_raceline_batch";
+    if (!h || !h_xy || !h_hw || !h_off || !h_alpha || !h_out_xy || !h_kappa || !h_vx || !h_length || !h_lap_time) return fail(h, F110_ERR_INVALID, "%s: null argument", who);
+    RacelineJob job{};
+    job.sp = RacelineSpec{levels, iters, margin, v_max, a_lat, a_accel, a_brake};
+    int max_M = 0;
+    TRY(raceline_check(h, who, h_xy, h_hw, h_off, T, job.sp, h_beta, h_line_iters, max_M));
+    const size_t n = (size_t)h_off[T];
+    // the outputs land in host rows of the call's own first: a line may still be refused once the solve has run
+    std::vector<double> rows(5 * n + 2 * (size_t)T);
+    std::vector<int32_t> status((size_t)T, 0), ints(h_off, h_off + T + 1);   // offsets [T + 1], then the lines' iteration counts [T]
+    if (h_line_iters) ints.insert(ints.end(), h_line_iters, h_line_iters + T);
+    else ints.insert(ints.end(), (size_t)T, iters);
+    const double no_beta = 0.0;   // iters = 0: the kernel reads no entry, the row exists
+    ENTER(h);
+    Scratch s(h);   // (few lines: an allocation costs more than these rows' copies)
+    job.xy = s.in(h_xy, 2 * n);
+    job.hw = s.in(h_hw, n);
+    job.off = s.in(ints.data(), ints.size());
+    job.beta = s.in(iters > 0 ? h_beta : &no_beta, (size_t)std::max(iters, 1));
+    double *const d_rows = s.out(rows.data(), rows.size());
+    job.status = s.out(status.data(), (size_t)T);
+    TRY(s.ready());
+    job.line_iters = job.off + T + 1;
+    job.alpha = d_rows;
+    job.out_xy = d_rows + n;
+    job.kappa = d_rows + 3 * n;
+    job.vx = d_rows + 4 * n;
+    job.length = d_rows + 5 * n;
+    job.lap_time = d_rows + 5 * n + T;
+    raceline_launch(h, job, T, max_M);
+    TRY(s.finish());
+    for (int t = 0; t < T; ++t)
+        if (status[(size_t)t]) return fail(h, F110_ERR_INVALID, "%s: the raceline of line %d has a segment of zero length or a curvature that is not finite", who, t);
+    std::memcpy(h_alpha, rows.data(), n * sizeof(double));
+    std::memcpy(h_out_xy, rows.data() + n, 2 * n * sizeof(double));
+    std::memcpy(h_kappa, rows.data() + 3 * n, n * sizeof(double));
+    std::memcpy(h_vx, rows.data() + 4 * n, n * sizeof(double));
+    std::memcpy(h_length, rows.data() + 5 * n, (size_t)T * sizeof(double));
+    std::memcpy(h_lap_time, rows.data() + 5 * n + T, (size_t)T * sizeof(double));
+    return F110_OK;
+}
+
 int f110_slot_shape(f110_sim *h, int32_t slot, int32_t *H, int32_t *W)
 {
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");

@@ -3509,6 +3509,234 @@ __global__ void __launch_bounds__(256) k_corridor_table(const uint32_t *__restri
     if (i == 0 && oob_dev) *oob_dev = v;   // (cell 0 of the padded copy is a border cell, or with b = 0 a ring cell: the same value)
 }
 
+// ---- raceline and speed profile (include/f110.h, f110_raceline_batch) ---------------------------------------------
+// One workgroup per line (the batch is the grid), NT lanes, point i of the line in lane i % NT as its slot i / NT (at most
+// kRacelinePerLane slots): q, n, b, alpha and y of a point stay in its lane's registers for the whole solve, p lives in LDS in two
+// copies (read-old / write-new, so an iteration costs ONE barrier), beta in LDS too: the iteration loop touches no global memory
+// and no atomics, and workgroups never talk.  On a coarse level only the lanes whose points are active work; nothing is compacted.
+// The per-point arithmetic is f110_math.hpp's rl_*.
+struct RacelineJob {
+    const double *xy, *hw;        // the lines one after the other: [sum M][2], [sum M]
+    const int32_t *off;           // [T + 1]: line t is rows off[t] .. off[t + 1]
+    const int32_t *line_iters;    // [T]: the line's iteration count per level (<= sp.iters)
+    const double *beta;           // [sp.iters]
+    RacelineSpec sp;
+    double *alpha, *out_xy, *kappa, *vx;   // rows as xy / hw
+    double *length, *lap_time;             // [T]
+    int32_t *status;                       // [T]: 0, or 1 = rl_degenerate: a raceline segment of zero length or a curvature that is not finite (nothing else written for the line)
+};
+
+// inclusive running minimum of a[0 .. M) (reverse: from the far end) by doubling between a and b, a barrier per round; the caller
+// wrote a and has not synchronised.  Returns where the result lies; the caller synchronises before it writes either buffer again.
+template <int NT>
+__device__ const double *rl_scan_min(double *a, double *b, int M, int tid, bool reverse)
+{
+    __syncthreads();
+    for (int d = 1; d < M; d <<= 1) {
+#pragma unroll
+        for (int e = 0; e < kRacelinePerLane; ++e) {
+            const int i = tid + e * NT;
+            if (i >= M) continue;
+            const int j = reverse ? i + d : i - d;
+            double v = a[i];
+            if (j >= 0 && j < M) v = rl_min(v, a[j]);
+            b[i] = v;
+        }
+        __syncthreads();
+        double *const t = a;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// NT lanes take lines of up to NT * kRacelinePerLane points, NB is the capacity of the beta table: LDS is 128 NT + 8 NB bytes
+// (NT = 1024, NB = 4096: all 160 KiB of the CU).
+template <int NT, int NB>
+__global__ void __launch_bounds__(NT) k_raceline(RacelineJob job)
+{
+    constexpr int CAP = NT * kRacelinePerLane;
+    __shared__ __attribute__((aligned(16))) double lds[4 * CAP];
+    __shared__ double s_beta[NB];
+    const int t = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int o = job.off[t], M = job.off[t + 1] - o;
+    const int iters = job.line_iters[t], levels = job.sp.levels;
+    double2 *cur = reinterpret_cast<double2 *>(lds), *nxt = reinterpret_cast<double2 *>(lds + 2 * CAP);
+    for (int k = tid; k < iters; k += NT) s_beta[k] = job.beta[k];
+
+    // step 1
+    double qx[kRacelinePerLane], qy[kRacelinePerLane], nx[kRacelinePerLane], ny[kRacelinePerLane], b[kRacelinePerLane], al[kRacelinePerLane], y[kRacelinePerLane];
+#pragma unroll
+    for (int e = 0; e < kRacelinePerLane; ++e) {
+        const int i = tid + e * NT;
+        qx[e] = qy[e] = nx[e] = ny[e] = b[e] = al[e] = y[e] = 0.0;
+        if (i >= M) continue;
+        const int im = i == 0 ? M - 1 : i - 1, ip = i + 1 == M ? 0 : i + 1;
+        qx[e] = job.xy[2 * (size_t)(o + i)];
+        qy[e] = job.xy[2 * (size_t)(o + i) + 1];
+        (void)rl_frame(job.xy[2 * (size_t)(o + im)], job.xy[2 * (size_t)(o + im) + 1], job.xy[2 * (size_t)(o + ip)], job.xy[2 * (size_t)(o + ip) + 1], job.hw[o + i],
+                       job.sp.margin, nx[e], ny[e], b[e]);
+    }
+
+    // step 2 (the first barrier below also publishes s_beta)
+    for (int lv = levels; lv >= 0; --lv) {
+        const int s = 1 << lv;
+        if (lv < levels) {   // prolong: the coarser level's alpha through LDS, then the points between
+            double *const a_lds = lds;
+#pragma unroll
+            for (int e = 0; e < kRacelinePerLane; ++e) {
+                const int i = tid + e * NT;
+                if (i < M && (i & (2 * s - 1)) == 0) a_lds[i] = al[e];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < kRacelinePerLane; ++e) {
+                const int i = tid + e * NT;
+                if (i < M && (i & (2 * s - 1)) == s) al[e] = rl_prolong(a_lds[i - s], a_lds[i + s == M ? 0 : i + s], b[e]);   // (2 s divides M: i + s <= M)
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int e = 0; e < kRacelinePerLane; ++e) {
+            const int i = tid + e * NT;
+            if (i >= M || (i & (s - 1))) continue;
+            y[e] = al[e];
+            double px, py;
+            rl_point(qx[e], qy[e], y[e], nx[e], ny[e], px, py);
+            cur[i] = make_double2(px, py);
+        }
+        __syncthreads();
+        for (int k = 0; k < iters; ++k) {
+            const double beta = s_beta[k];
+#pragma unroll
+            for (int e = 0; e < kRacelinePerLane; ++e) {
+                const int i = tid + e * NT;
+                if (i >= M || (i & (s - 1))) continue;
+                double px[5], py[5];
+#pragma unroll
+                for (int m = 0; m < 5; ++m) {   // (M / s >= 8: one wrap at most)
+                    int j = i + (m - 2) * s;
+                    j = j < 0 ? j + M : (j >= M ? j - M : j);
+                    const double2 p = cur[j];
+                    px[m] = p.x;
+                    py[m] = p.y;
+                }
+                rl_update(px, py, nx[e], ny[e], b[e], beta, y[e], al[e]);
+                double wx, wy;
+                rl_point(qx[e], qy[e], y[e], nx[e], ny[e], wx, wy);
+                nxt[i] = make_double2(wx, wy);
+            }
+            __syncthreads();
+            double2 *const sw = cur;
+            cur = nxt;
+            nxt = sw;
+        }
+    }
+
+    // step 3: the line in LDS, curvature and segment lengths per point, the running sum by one lane
+    double2 *const P = reinterpret_cast<double2 *>(lds);
+    double *const r0 = lds, *const r1 = lds + CAP, *const r2 = lds + 2 * CAP, *const r3 = lds + 3 * CAP;
+    double px[kRacelinePerLane], py[kRacelinePerLane], len[kRacelinePerLane], kap[kRacelinePerLane];
+#pragma unroll
+    for (int e = 0; e < kRacelinePerLane; ++e) {
+        const int i = tid + e * NT;
+        px[e] = py[e] = len[e] = kap[e] = 0.0;
+        if (i >= M) continue;
+        rl_point(qx[e], qy[e], al[e], nx[e], ny[e], px[e], py[e]);
+        P[i] = make_double2(px[e], py[e]);
+    }
+    if (tid == 0) r3[0] = 0.0;   // the line's refusal flag (r3[1]: its length)
+    __syncthreads();
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < kRacelinePerLane; ++e) {
+        const int i = tid + e * NT;
+        if (i >= M) continue;
+        const double2 a = P[i == 0 ? M - 1 : i - 1], c = P[i + 1 == M ? 0 : i + 1];
+        len[e] = rl_length(px[e], py[e], c.x, c.y);
+        kap[e] = rl_curvature(a.x, a.y, px[e], py[e], c.x, c.y);
+        bad |= rl_degenerate(len[e], kap[e]);
+        r2[i] = len[e];
+    }
+    if (bad) r3[0] = 1.0;
+    __syncthreads();
+    if (r3[0] != 0.0) {   // (the same answer in every lane)
+        if (tid == 0) job.status[t] = 1;
+        return;
+    }
+    if (tid == 0) {
+        double acc = 0.0;
+        for (int i = 0; i < M; ++i) {
+            const double l = r2[i];
+            r2[i] = acc;
+            acc += l;
+        }
+        r3[1] = acc;
+    }
+    __syncthreads();
+    const double L = r3[1];
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+
+    // step 4: the ceiling, the four minima as scans between r0 and r1, the profile, the lap time by one lane
+    double cum[kRacelinePerLane], cl[kRacelinePerLane], mn[4][kRacelinePerLane];
+#pragma unroll
+    for (int e = 0; e < kRacelinePerLane; ++e) {
+        const int i = tid + e * NT;
+        cum[e] = cl[e] = 0.0;
+        if (i >= M) continue;
+        cum[e] = r2[i];
+        cl[e] = rl_ceiling(kap[e], job.sp.v_max, job.sp.a_lat);
+    }
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {   // pre_f (j <= i), suf_f (j > i), suf_g (j >= i), pre_g (j < i)
+        const bool is_g = pass >= 2, reverse = pass == 1 || pass == 2, exclusive = pass == 1 || pass == 3;
+#pragma unroll
+        for (int e = 0; e < kRacelinePerLane; ++e) {
+            const int i = tid + e * NT;
+            if (i < M) r0[i] = is_g ? rl_G(cl[e], cum[e], job.sp.a_brake) : rl_F(cl[e], cum[e], job.sp.a_accel);
+        }
+        const double *const res = rl_scan_min<NT>(r0, r1, M, tid, reverse);
+#pragma unroll
+        for (int e = 0; e < kRacelinePerLane; ++e) {
+            const int i = tid + e * NT;
+            mn[pass][e] = inf;
+            if (i >= M) continue;
+            const int j = exclusive ? (reverse ? i + 1 : i - 1) : i;
+            if (j >= 0 && j < M) mn[pass][e] = res[j];
+        }
+        __syncthreads();
+    }
+    double v[kRacelinePerLane];
+#pragma unroll
+    for (int e = 0; e < kRacelinePerLane; ++e) {
+        const int i = tid + e * NT;
+        v[e] = 0.0;
+        if (i >= M) continue;
+        v[e] = rl_speed(cl[e], cum[e], L, job.sp.a_accel, job.sp.a_brake, mn[0][e], mn[1][e], mn[2][e], mn[3][e]);
+        r3[i] = v[e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < kRacelinePerLane; ++e) {
+        const int i = tid + e * NT;
+        if (i >= M) continue;
+        r2[i] = rl_lap_term(len[e], v[e], r3[i + 1 == M ? 0 : i + 1]);
+        job.alpha[o + i] = al[e];
+        job.out_xy[2 * (size_t)(o + i)] = px[e];
+        job.out_xy[2 * (size_t)(o + i) + 1] = py[e];
+        job.kappa[o + i] = kap[e];
+        job.vx[o + i] = v[e];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double lap = 0.0;
+        for (int i = 0; i < M; ++i) lap += r2[i];
+        job.length[t] = L;
+        job.lap_time[t] = lap;
+        job.status[t] = 0;
+    }
+}
+
 // ---- centreline extraction (include/f110.h, f110_map_centerline) --------------------------------------------------
 // The mask is a bit plane [H][Ww] of 64-bit words, Ww = ceil(W / 64): bit b of word w is column 64 w + b, bits from column W on
 // are 0 in every plane.  The per-word decisions are f110_math.hpp's cl_*.

@@ -2523,4 +2523,103 @@ F110_HD bool cl_seed_cell(double x, double y, double res, double ox, double oy, 
     return true;
 }
 
+// ------------------------------------------------------------------ raceline and speed profile (f110_raceline_batch)
+// The per-point arithmetic of the rule include/f110.h states: float64 in exactly this order, never contracted.  One text for
+// k_raceline and the host program (tests/host_harness/raceline_main.hip); the NumPy restatement (tests/raceline_ref.py) agrees bit
+// for bit.
+constexpr int kRacelineMaxPoints = 4096;
+constexpr int kRacelineMaxLevels = 6, kRacelineMaxIters = 4096;
+constexpr int kRacelinePerLane = 4;   // points of a line per lane of its workgroup: point i is lane i % lanes, slot i / lanes
+
+struct RacelineSpec {
+    int32_t levels, iters;
+    double margin, v_max, a_lat, a_accel, a_brake;
+};
+
+// min(max(x, lo), hi) for numbers that are no NaN
+F110_HD double rl_clamp(double x, double lo, double hi)
+{
+    const double m = x > lo ? x : lo;
+    return m < hi ? m : hi;
+}
+
+F110_HD double rl_min(double a, double b) { return b < a ? b : a; }
+
+// step 1: the normal and the bound of a point from its two neighbours; returns l = |q_{i+1} - q_{i-1}| (0: the line is refused)
+F110_HD double rl_frame(double qmx, double qmy, double qpx, double qpy, double w, double margin, double &nx, double &ny, double &b)
+{
+    const double dx = qpx - qmx, dy = qpy - qmy;
+    const double l = sqrt(dx * dx + dy * dy);
+    nx = -dy / l;
+    ny = dx / l;
+    const double d = w - margin;
+    b = d > 0.0 ? d : 0.0;
+    return l;
+}
+
+// step 2, prolong: a point between two points of the coarser level
+F110_HD double rl_prolong(double am, double ap, double b) { return rl_clamp(0.5 * (am + ap), -b, b); }
+
+// p = q + y * n, per component
+F110_HD void rl_point(double qx, double qy, double y, double nx, double ny, double &px, double &py)
+{
+    px = qx + y * nx;
+    py = qy + y * ny;
+}
+
+// step 2, one point's iteration: p[0 .. 4] = p_{j-2s} .. p_{j+2s} (x and y), the point's normal and bound, beta[k]; y and alpha are
+// the point's state, read and replaced
+F110_HD void rl_update(const double px[5], const double py[5], double nx, double ny, double b, double beta, double &y, double &alpha)
+{
+    double rx[3], ry[3];
+    for (int m = 0; m < 3; ++m) {
+        rx[m] = (px[m] - 2.0 * px[m + 1]) + px[m + 2];
+        ry[m] = (py[m] - 2.0 * py[m + 1]) + py[m + 2];
+    }
+    const double gx = (rx[0] - 2.0 * rx[1]) + rx[2], gy = (ry[0] - 2.0 * ry[1]) + ry[2];
+    const double gg = 2.0 * (nx * gx + ny * gy);
+    const double nw = rl_clamp(y - 0.03125 * gg, -b, b);
+    y = nw + beta * (nw - alpha);
+    alpha = nw;
+}
+
+// step 3: the signed curvature of the circle through a, b, c (centerline.curvature_closed's operation order)
+F110_HD double rl_curvature(double ax, double ay, double bx, double by, double cx, double cy)
+{
+    const double abx = bx - ax, aby = by - ay, bcx = cx - bx, bcy = cy - by, acx = cx - ax, acy = cy - ay;
+    const double cross = abx * bcy - aby * bcx;
+    const double den = sqrt(abx * abx + aby * aby) * sqrt(bcx * bcx + bcy * bcy) * sqrt(acx * acx + acy * acy);
+    return 2.0 * cross / den;
+}
+
+F110_HD double rl_length(double ax, double ay, double bx, double by)
+{
+    const double dx = bx - ax, dy = by - ay;
+    return sqrt(dx * dx + dy * dy);
+}
+
+// the refusal after the solve: a raceline segment of zero length, or a curvature that is no finite number (p_{i+1} = p_{i-1}, or
+// lengths whose product underflows: 0 / 0 or x / 0).  With these out of the way no NaN reaches a minimum below, so which operand
+// a minimum returns for a NaN is never asked.
+F110_HD bool rl_degenerate(double len, double kappa) { return !(len > 0.0) || !(fabs(kappa) <= 1.7976931348623157e308); }
+
+// step 4: the ceiling of v^2 (a zero curvature: a_lat / 0 = inf, then v_max^2)
+F110_HD double rl_ceiling(double kappa, double v_max, double a_lat) { return rl_min(v_max * v_max, a_lat / fabs(kappa)); }
+
+// step 4: vx from the ceiling, the arc length and the four minima: pre_f = min_{j<=i} F, suf_f = min_{j>i} F, suf_g = min_{j>=i} G,
+// pre_g = min_{j<i} G (an empty one +inf)
+F110_HD double rl_F(double c, double cum, double a_accel) { return c - (2.0 * a_accel) * cum; }
+F110_HD double rl_G(double c, double cum, double a_brake) { return c + (2.0 * a_brake) * cum; }
+F110_HD double rl_speed(double c, double cum, double L, double a_accel, double a_brake, double pre_f, double suf_f, double suf_g, double pre_g)
+{
+    const double ka = 2.0 * a_accel, kb = 2.0 * a_brake;
+    const double A = ka * cum, B = kb * cum;
+    const double up = rl_min(A + pre_f, (A + ka * L) + suf_f);
+    const double um = rl_min(suf_g - B, (pre_g + kb * L) - B);
+    return sqrt(rl_min(c, rl_min(up, um)));
+}
+
+// a term of the lap time
+F110_HD double rl_lap_term(double len, double vx, double vx_next) { return (2.0 * len) / (vx + vx_next); }
+
 }  // namespace f110

@@ -28,6 +28,7 @@ from .neighbors import Neighbors
 from .track import Track
 from .centerline import coerce_params
 from .trackgen import TrackMap
+from .raceline import Raceline
 
 try:  # pragma: no cover - gym is absent from the build image
     import gym as _gym
@@ -152,6 +153,26 @@ def _is_centerline(track):
     return isinstance(track, str) and track == 'centerline'
 
 
+def _is_raceline(track):
+    """track='raceline': the racing line and speed profile solved on the device from the slot's own line"""
+    return isinstance(track, str) and track == 'raceline'
+
+
+def _is_extracted(track):
+    return _is_centerline(track) or _is_raceline(track)
+
+
+def _raceline_source(batch, slot, track_map, centerline):
+    """what track='raceline' solves on map slot `slot`: a carved slot's generating line with the half widths it was CARVED with
+    (TrackMap.carved_line: per point the smaller of its two segments', whatever column the line itself carries), elsewhere the
+    slot's extracted centreline"""
+    if track_map is None:
+        return batch.centerline(int(slot), **coerce_params(centerline))
+    if not track_map.track.closed:
+        raise ValueError("track='raceline' needs a closed line (slot %d was carved from an open one)" % int(slot))
+    return track_map.carved_line()
+
+
 # the track columns' observation keys -> their names in BatchSim.track_views / track_host_block
 _TRACK_OBS = {key: src for src, key in Simulator.TRACK_KEYS}
 
@@ -226,6 +247,9 @@ class F110Env(_EnvBase):
             track = kwargs['track']
             if _is_centerline(track):   # the map's centreline loop, extracted on the device
                 track = self.sim.batch.centerline(self.map_slot, **coerce_params(kwargs.get('centerline')))
+            elif _is_raceline(track):   # ... or the racing line solved from it (from the carved line, on a carved slot)
+                track = self.sim.batch.raceline(_raceline_source(self.sim.batch, self.map_slot, self.track_map, kwargs.get('centerline')),
+                                                Raceline.coerce(kwargs.get('raceline')))
             self.track = self.sim.set_track(Track.coerce(track), self.map_slot)
             self.sim.enable_track()
         elif self.track_map is not None:
@@ -402,6 +426,10 @@ class F110VecEnv(object):
     reward='progress' makes the reward the ego's progress_delta, [E].  A track given as the string 'centerline' is the slot's own
     centreline loop, extracted from its distance table on the device (a derived obstacle slot: the line around its
     obstacles); `centerline=dict(seed=…, heading=…, spacing=…, smooth=…, max_passes=…)` sets BatchSim.centerline's parameters.
+    The string 'raceline' is the racing line with a speed profile solved on the device from the carved line and its half
+    widths on a slot of `track_maps`, from the extracted centreline elsewhere; `raceline=dict(spacing=…, levels=…, iters=…, margin=…,
+    v_max=…, a_lat=…, a_accel=…, a_brake=…)` sets it.  The slot's track then carries the attribute columns kappa, vx and offset
+    (the preview's attr0 .. attr2), and `set_track_map` on such a slot solves the new line's.
 
     Compact observations (no reference counterpart): `obs_encoder=` (an ObsEncoder or a dict of its settings) adds
     obs['encoded'], float32 [E][A][F][D]: pooled lidar sectors and scaled state / track columns, the last F frames stacked
@@ -472,6 +500,7 @@ class F110VecEnv(object):
         tracks = dict(kwargs.get('tracks') or {})
         if kwargs.get('track') is not None:
             tracks[0] = kwargs['track']
+        self.raceline = Raceline.coerce(kwargs.get('raceline'))
         # carved tracks: slots behind extra_maps, each with its generating line as the track (a tracks= entry wins)
         track_maps = [TrackMap.coerce(item) for item in kwargs.get('track_maps') or ()]
         for i, tm in enumerate(track_maps):
@@ -524,9 +553,9 @@ class F110VecEnv(object):
                 raise ValueError("track_preview= needs device_logic=True (any other loop calls env.sim.batch.track_preview_device after its step)")
             if not tracks:
                 raise ValueError("track_preview= needs a track (track= or tracks=)")
-            tracks = {slot: t if _is_centerline(t) else Track.coerce(t) for slot, t in tracks.items()}
+            tracks = {slot: t if _is_extracted(t) else Track.coerce(t) for slot, t in tracks.items()}
             for t in tracks.values():
-                if not _is_centerline(t):   # (a centreline is checked once it has been extracted, below)
+                if not _is_extracted(t):   # (a centreline or a raceline is checked once it has been made, below)
                     self.track_preview.check_track(t)
         self.neighbors = None
         if neighbors is not None:
@@ -568,6 +597,8 @@ class F110VecEnv(object):
             self.map_slots.append(tm)
         # track='centerline' (DESIGN §6n): the slot's centreline loop, extracted from its distance table on the device
         self.centerline = kwargs.get('centerline')
+        # track='raceline' (DESIGN §6p): the racing line and speed profile solved from the slot's line, on the device
+        self.raceline_slots = set()
         self._extract_centerlines(tracks)
         # static obstacles: each entry registers a slot derived from slot 0 (or from the entry's base slot)
         self.obstacle_slots = {}
@@ -693,13 +724,19 @@ class F110VecEnv(object):
         self.sim.batch.set_params_batch(params)
 
     def _extract_centerlines(self, tracks):
-        """replace the 'centerline' entries of `tracks` whose slot is registered by the slot's extracted centreline"""
+        """replace the 'centerline' and 'raceline' entries of `tracks` whose slot is registered by the slot's extracted centreline or by
+        the raceline solved from the slot's line"""
         b = self.sim.batch
         for slot, t in sorted(tracks.items()):
-            if _is_centerline(t) and 0 <= int(slot) < len(self.map_slots):
+            if not (_is_extracted(t) and 0 <= int(slot) < len(self.map_slots)):
+                continue
+            if _is_centerline(t):
                 tracks[slot] = b.centerline(int(slot), **coerce_params(self.centerline))
-                if self.track_preview is not None:
-                    self.track_preview.check_track(tracks[slot])
+            else:
+                tracks[slot] = b.raceline(_raceline_source(b, slot, self.track_maps.get(int(slot)), self.centerline), self.raceline)
+                self.raceline_slots.add(int(slot))
+            if self.track_preview is not None:
+                self.track_preview.check_track(tracks[slot])
 
     def set_env_maps(self, env_map):
         """env_map [num_envs]: which registered track each env runs on (None: all on slot 0)"""
@@ -717,7 +754,9 @@ class F110VecEnv(object):
         tm = TrackMap.coerce(tm)
         self.sim.batch.set_track_map(slot, tm)
         self.track_maps[int(slot)] = tm
-        if int(slot) in self.tracks:
+        if int(slot) in self.raceline_slots:   # tracks={slot: 'raceline'}: the new line's raceline, not the line itself
+            self.tracks[int(slot)] = self.sim.set_track(self.sim.batch.raceline(_raceline_source(self.sim.batch, slot, tm, self.centerline), self.raceline), int(slot))
+        elif int(slot) in self.tracks:
             self.tracks[int(slot)] = tm.track
 
     def device_views(self):

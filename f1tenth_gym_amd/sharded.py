@@ -103,6 +103,9 @@ class ShardedVecEnv(object):
         if kwargs.get('track_maps') is not None:     # one TrackMap per slot for every shard (a dict of random_track's arguments is drawn once)
             from .trackgen import TrackMap
             kwargs['track_maps'] = [TrackMap.coerce(tm) for tm in kwargs['track_maps']]
+        if kwargs.get('raceline') is not None:       # one Raceline for every shard: each solves its own slots, bit-equal (the rule is deterministic)
+            from .raceline import Raceline
+            kwargs['raceline'] = Raceline.coerce(kwargs['raceline'])
         if kwargs.get('particle_filter') is not None:   # one filter for every shard; a shard's env_base gives its agents their global streams
             from .particle_filter import split_filter
             slot, pf = split_filter(kwargs['particle_filter'])

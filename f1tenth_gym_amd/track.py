@@ -85,6 +85,13 @@ class Track(object):
         sim = getattr(sim, "batch", sim)      # Simulator -> its BatchSim
         return sim.centerline(slot, **kw)
 
+    def raceline(self, sim, spec=None):
+        """this track's racing line and speed profile, solved on the device: BatchSim.raceline(self, spec).  The track
+        must be closed and carry a 'half_width' column.  sim: a BatchSim, or an env layer that holds one."""
+        sim = getattr(sim, "sim", sim)
+        sim = getattr(sim, "batch", sim)
+        return sim.raceline(self, spec)
+
     @classmethod
     def coerce(cls, track):
         """a Track, an [M][2] array (closed) or a csv path (PurePursuitPlanner's defaults: x, y in columns 1, 2)"""

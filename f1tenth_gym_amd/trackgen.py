@@ -131,6 +131,15 @@ class TrackMap(object):
         """the line's points, [M][2] float64, contiguous"""
         return np.ascontiguousarray(self.track.xy, dtype=np.float64)
 
+    def carved_line(self):
+        """the closed line as a Track whose 'half_width' column is what was CARVED around each point: the smaller half width of the
+        point's two segments (the track's own column, if it has one, plays no part: `half_width=` may have overridden it, and a
+        varying column is carved at each segment's mean).  What a raceline on the carved slot is solved from."""
+        if not self.track.closed:
+            raise ValueError("a carved line with half widths per point needs a closed track")
+        hw = np.asarray(self._hw)
+        return Track(self.track.xy, closed=True, attrs={'half_width': np.minimum(hw, np.roll(hw, 1))})
+
     def same_frame(self, other):
         return (isinstance(other, TrackMap) and self._shape == other._shape and self.resolution == other.resolution
                 and self._origin == other._origin)

@@ -254,6 +254,52 @@ int f110_corridor_mask_batch(f110_sim *h, const double *h_xy, const double *h_ha
  * refused for carving nothing).  Waits for that call's distance transform (tools/trackgen_bench.py). */
 int f110_map_corridor_times(f110_sim *h, double *ms /* [2] */);
 
+/* Extension: a RACELINE AND SPEED PROFILE per closed line, ON THE DEVICE — the step from a centreline with half widths to
+ * what a racing stack drives on.  Stateless unit form: T lines in one call, one workgroup per line, nothing kept in the handle.
+ *
+ * A line: M points q_i (indices modulo M) with a half width w_i >= 0 each.  The lines lie one after the other: xy [sum M][2],
+ * half_width [sum M], offsets [T + 1] with offsets[0] = 0 and line t in rows offsets[t] .. offsets[t + 1].  float64 throughout, in
+ * exactly this order, never contracted; clamp(x, lo, hi) = min(max(x, lo), hi).
+ *   1. Frame.    d = q_{i+1} - q_{i-1};  l = sqrt(dx*dx + dy*dy);  n_i = (-dy / l, dx / l);  b_i = max(w_i - margin, 0).
+ *   2. Offsets.  alpha = 0.  For lv = levels .. 0, s = 2^lv, the ACTIVE points are i = 0 (mod s):
+ *        prolong (lv < levels only): for i = s (mod 2 s)   alpha_i = clamp(0.5 * (alpha_{i-s} + alpha_{i+s}), -b_i, b_i)
+ *        y = alpha; then for k = 0 .. iters - 1 on the active points, every point from the values of the iteration before (Jacobi):
+ *          p_j = q_j + y_j * n_j                                (per component)
+ *          r_j = (p_{j-s} - 2 * p_j) + p_{j+s};   g_j = (r_{j-s} - 2 * r_j) + r_{j+s}
+ *          gg  = 2 * (nx * gx + ny * gy);         new = clamp(y_j - 0.03125 * gg, -b_j, b_j)
+ *          y_j = new + beta[k] * (new - alpha_j);  alpha_j = new
+ *      Accelerated projected gradient on sum |r_j|^2, a box-constrained quadratic programme in alpha; the step 1/32 is 1 / (2 * 16):
+ *      the Hessian is 2 N' D2' D2 N with |D2|^2 <= 16 and unit normals.  beta[k] = (t_k - 1) / t_{k+1}, t_0 = 1,
+ *      t_{k+1} = (1 + sqrt(1 + 4 * t_k * t_k)) / 2 is the CALLER'S table (the device takes no square root in the loop); every level
+ *      restarts at beta[0].  line_iters [T] (or NULL: iters for every line) gives a line fewer iterations; 0 leaves alpha = 0, the
+ *      profile of the centreline itself.
+ *   3. Line.     p_i = q_i + alpha_i * n_i.  kappa_i with a = p_{i-1}, b = p_i, c = p_{i+1}:
+ *                  ab = b - a, bc = c - b, ac = c - a;  cross = abx * bcy - aby * bcx
+ *                  kappa = 2 * cross / (sqrt(ab.ab) * sqrt(bc.bc) * sqrt(ac.ac))          (x.x = xx*xx + xy*xy; products left to right)
+ *                len_i = |p_{i+1} - p_i|;  cum_0 = 0, cum_{i+1} = cum_i + len_i, L = cum_M: the running sum in order.
+ *   4. Speed.    c_i = min(v_max * v_max, a_lat / |kappa_i|)                               (kappa = 0: inf, then v_max^2)
+ *                ka = 2 * a_accel;  A_i = ka * cum_i;  F_i = c_i - A_i
+ *                up_i = min(A_i + min_{j<=i} F_j, (A_i + ka * L) + min_{j>i} F_j)
+ *                kb = 2 * a_brake;  B_i = kb * cum_i;  G_i = c_i + B_i
+ *                um_i = min((min_{j>=i} G_j) - B_i, ((min_{j<i} G_j) + kb * L) - B_i)          (an empty minimum is +inf)
+ *                vx_i = sqrt(min(c_i, min(up_i, um_i)))
+ *                lap_time = sum of (2 * len_i) / (vx_i + vx_{i+1}), added in order.
+ *      The forward / backward pass in v^2 once round the closed line, as prefix and suffix minima: exact under any evaluation order.
+ * Outputs, written only when the whole call succeeds: alpha [sum M], xy [sum M][2] (the p_i), kappa, vx [sum M], length [T] (L),
+ * lap_time [T].  Refused (F110_ERR_INVALID, a message; outputs untouched, the device allocations as they were): null arguments,
+ * T < 1, offsets[0] != 0, levels outside 0 .. 6, iters outside 0 .. 4096, a line_iters entry outside 0 .. iters, a non-finite point,
+ * half width or beta, v_max / a_lat / a_accel / a_brake not finite and > 0, margin not finite or < 0, and per line: M not a multiple
+ * of 2^levels, M / 2^levels < 8 (the five-point stencil must not alias on the coarsest level), M > F110_RACELINE_MAX_POINTS, a
+ * zero-length q_{i+1} - q_{i-1}; and, decided on the device once the solve has run, a raceline segment of zero length or a kappa_i
+ * that is no finite number (p_{i+1} = p_{i-1}, or lengths whose product underflows).  So no NaN ever reaches a minimum of step 4:
+ * min(a, b) there is the smaller of two numbers, and which operand an implementation returns for a NaN is not part of the rule.
+ * Ordered behind every step in flight; one wait, at the end. */
+enum { F110_RACELINE_MAX_POINTS = 4096 };
+int f110_raceline_batch(f110_sim *h, const double *h_xy, const double *h_half_width, const int32_t *h_offsets /* [T + 1] */, int32_t T,
+                        int32_t levels, int32_t iters, double margin, double v_max, double a_lat, double a_accel, double a_brake,
+                        const double *h_beta /* [iters] */, const int32_t *h_line_iters /* [T] or NULL */,
+                        double *h_alpha, double *h_out_xy, double *h_kappa, double *h_vx, double *h_length /* [T] */, double *h_lap_time /* [T] */);
+
 /* Extension: a map slot's CENTRELINE LOOP, extracted ON THE DEVICE from the slot's distance table T (slot 0, an added
  * slot or a derived obstacle slot), as an ordered cycle of table cells with T at each: what a Track is made of (Track.from_map).
  *
