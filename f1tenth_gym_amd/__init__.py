@@ -15,6 +15,7 @@ from .track import Track  # noqa: F401
 from .reset_sampler import ResetSampler  # noqa: F401
 from .obs_encoder import ObsEncoder  # noqa: F401
 from .gap_follower import GapFollower  # noqa: F401
+from .line_follower import LineFollower  # noqa: F401
 from .track_preview import TrackPreview  # noqa: F401
 from .neighbors import Neighbors  # noqa: F401
 from .rollout import Rollout  # noqa: F401

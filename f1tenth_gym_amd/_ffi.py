@@ -102,6 +102,17 @@ class NeighborsSpec(C.Structure):
 NBR_DX, NBR_DY, NBR_DIST, NBR_COS_DTH, NBR_SIN_DTH, NBR_V_X, NBR_V_Y, NBR_GAP_S, NBR_VALID, NBR_INDEX = (1 << b for b in range(10))
 NBR_NCHANNELS, NBR_MAX_K, NBR_MAX_AGENTS = 10, 8, 256
 
+LINE_FLOATS = ("look_base", "look_gain", "look_min", "look_max", "lane_offset", "wheelbase", "steer_max", "v_const", "vgain", "speed_look",
+               "lat_slow", "v_recover", "follow_range", "follow_gap", "follow_gain", "lane_width", "v_min", "v_max")
+
+
+class LineFollowerSpec(C.Structure):
+    """struct f110_line_follower"""
+    _fields_ = [(k, C.c_double) for k in LINE_FLOATS] + [("speed_attr", C.c_int32), ("pad_", C.c_int32)]
+
+
+LINE_MAX_SPECS, LINE_MAX_AGENTS, LINE_NRAW, LINE_NINFO = 8, 256, 12, 4
+
 
 class Obstacle(C.Structure):
     """struct f110_obstacle"""
@@ -309,6 +320,9 @@ PROTOTYPES = {
     "f110_track_preview_batch": (C.c_int, [C.c_void_p, C.POINTER(TrackPreviewSpec), C.c_int32, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
     "f110_neighbors_device": (C.c_int, [C.c_void_p, C.POINTER(NeighborsSpec), C.c_void_p, C.c_void_p]),
     "f110_neighbors_batch": (C.c_int, [C.c_void_p, C.POINTER(NeighborsSpec), C.c_int32, C.c_double, _dp, C.c_int32, C.c_void_p, _dp, _i32p]),
+    "f110_line_followers_set": (C.c_int, [C.c_void_p, C.POINTER(LineFollowerSpec), C.c_int32, _i32p]),
+    "f110_follow_line_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "f110_follow_line_batch": (C.c_int, [C.c_void_p, C.POINTER(LineFollowerSpec), C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp]),
     "f110_rollout_device": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "f110_rollout_batch": (C.c_int, [C.c_void_p, C.POINTER(RolloutSpec), C.c_int32, _dp, _dp, _dp, C.c_int32, C.c_void_p, _dp, C.c_void_p, _dp]),
     "f110_mppi_set": (C.c_int, [C.c_void_p, C.POINTER(MppiSpec), _i32p, C.c_int32, _u64p]),

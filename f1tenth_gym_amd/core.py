@@ -1894,6 +1894,55 @@ class BatchSim(object):
                                                None if inf is None else i32ptr(inf)), self._h)
         return (act, inf) if info else act
 
+    # ------------------------------------------------------------------ scripted cars on the line (f110_line_followers_set / f110_follow_line_*)
+    def set_line_followers(self, assign, followers):
+        """arm line followers: `followers` a list of 1 .. 8 line_follower.LineFollower (or dicts of their settings), `assign`
+        int32 [N] (or [E][A]): -1 = no line follower, else the index of the agent's follower.  Nothing is launched; they act in
+        follow_line_device and in step_host(scripted=True), on the track of the agent's map slot (tracking must be on then)."""
+        from .line_follower import LineFollower, MAX_SPECS
+        fs = [LineFollower.coerce(c) for c in followers]
+        if not (1 <= len(fs) <= MAX_SPECS):
+            raise ValueError("1 .. %d line followers, got %d" % (MAX_SPECS, len(fs)))
+        a = np.ascontiguousarray(np.asarray(assign).reshape(-1), dtype=np.int32)
+        if a.shape != (self.N,):
+            raise ValueError("assign must hold one entry per agent (%d), got %d" % (self.N, a.size))
+        specs = (_ffi.LineFollowerSpec * len(fs))(*[c.spec() for c in fs])
+        check(_ffi.lib().f110_line_followers_set(self._h, specs, len(fs), i32ptr(a)), self._h)
+        self.line_followers, self.line_follower_assign = fs, a
+
+    def clear_line_followers(self):
+        """disarm the line followers"""
+        check(_ffi.lib().f110_line_followers_set(self._h, None, 0, None), self._h)
+        self.line_followers, self.line_follower_assign = [], None
+
+    def follow_line_device(self, d_actions, info=None):
+        """the armed line followers write their agents' rows of the device action buffer [N][2] from the last step's track
+        columns; the other rows are left alone.  info: a float64 DeviceArray [N][4] (ld, vref, k, lim) whose armed rows are
+        written too.  Enqueued on the handle's stream, per env block behind a two-block step (no host wait)."""
+        a = d_actions.ptr if isinstance(d_actions, DeviceArray) else int(d_actions)
+        ip = None
+        if info is not None:
+            if not isinstance(info, DeviceArray) or tuple(info.shape) != (self.N, 4) or info.dtype != np.float64:
+                raise ValueError("info must be a float64 DeviceArray of shape %s" % ((self.N, 4),))
+            ip = info.ptr
+        check(_ffi.lib().f110_follow_line_device(self._h, a, ip), self._h)
+
+    def follow_line(self, rows, follower=None, A=1, slot=0, raw=False):
+        """unit form on host rows, on the track of map slot `slot`: rows [m][7] = x, y, theta, v, s, lateral, step_count,
+        env-major with A cars per env -> actions [m][2] (and, with raw, float64 [m][12]: line_follower.RAW).  It does not
+        project: s and lateral come from track_project."""
+        from .line_follower import LineFollower
+        c = LineFollower() if follower is None else LineFollower.coerce(follower)
+        rows = as_f64(rows)
+        if rows.ndim != 2 or rows.shape[1] != 7 or rows.shape[0] % int(A) != 0:
+            raise ValueError("rows must be [m][7] with m a multiple of A = %d" % int(A))
+        m = rows.shape[0]
+        act = np.zeros((m, 2))
+        rw = np.zeros((m, _ffi.LINE_NRAW)) if raw else None
+        spec = c.spec()
+        check(_ffi.lib().f110_follow_line_batch(self._h, C.byref(spec), int(slot), int(A), dptr(rows), m, dptr(act), self._opt(rw)), self._h)
+        return (act, rw) if raw else act
+
     # ------------------------------------------------------------------ the reference's example policy
     def pure_pursuit_batch(self, waypoints, poses, lookahead, vgain, wheelbase, max_reacquire=20.0):
         """PurePursuitPlanner.plan (examples/waypoint_follow.py:203-217) for host poses [m][3];

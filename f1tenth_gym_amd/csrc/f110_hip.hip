@@ -266,6 +266,14 @@ struct f110_sim {
     DevBuf<int32_t> d_gap_assign;
     int gap_specs = 0, gap_max_w = 0;
     std::vector<int32_t> gap_assign_host;   // the armed assignment (empty while disarmed): what f110_mppi_set checks its agents against
+    // line followers (f110_line_followers_set): the same shape; line_specs == 0: disarmed
+    DevBuf<LineSpec> d_line_specs;
+    DevBuf<int32_t> d_line_assign;
+    int line_specs = 0;
+    bool line_follow = false;                // some armed spec looks for a car ahead (follow_range > 0 and A > 1)
+    bool line_checked = false;               // line_ready's slot checks hold (since the last change of the tracks, the env maps or the arming)
+    LineSpec line_specs_host[LINE_MAX_SPECS] = {};
+    std::vector<int32_t> line_assign_host;   // (empty while disarmed): what f110_controllers_set and f110_mppi_set check against
     // MPPI planner (f110_mppi_set): on.m == 0: disarmed.  The nominal sequences and the streams are the planner's own memory.
     struct Mppi {
         MppiSpec sp{};
@@ -443,6 +451,9 @@ static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &
 constexpr int kMaxEnvBlocks = 16;
 struct EnvBlock { hipStream_t stream; int e0, count; };   // envs [e0, e0 + count) on `stream`
 static void gap_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions);   // (below, with the controllers)
+static int line_ready(f110_sim *h);                                                   // (below, with the line followers)
+static void line_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, double *d_info);
+static int track_upload(f110_sim *h);
 static int mppi_ready(f110_sim *h);                                                   // (below, with the planner)
 static int mppi_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, float *d_info);
 static int mppi_upload_tracks(f110_sim *h);
@@ -3218,8 +3229,9 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
                      out->checkpoint_done || out->done || (flags & F110_STEP_AUTO_RESET)))
         return fail(h, F110_ERR_STATE, "f110_episode_init has not been called");
     const bool scripted = (flags & F110_STEP_SCRIPTED) != 0;
-    if (scripted && h->gap_specs == 0 && h->mppi.on.m == 0)
-        return fail(h, F110_ERR_STATE, "f110_step_host: F110_STEP_SCRIPTED without controllers (f110_controllers_set) or a planner (f110_mppi_set)");
+    if (scripted && h->gap_specs == 0 && h->line_specs == 0 && h->mppi.on.m == 0)
+        return fail(h, F110_ERR_STATE, "f110_step_host: F110_STEP_SCRIPTED without controllers (f110_controllers_set), line followers (f110_line_followers_set) or a planner (f110_mppi_set)");
+    if (scripted && h->line_specs > 0) TRY(line_ready(h));
     if (scripted && h->mppi.on.m > 0) TRY(mppi_ready(h));
     ENTER(h);
     const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
@@ -3244,6 +3256,10 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
         HIPCHK(h, hipMemcpyAsync(h->d_actions, h_actions, sizeof(double) * 2 * N, hipMemcpyHostToDevice, h->stream));
     if (scripted) {   // the scans are the last step's, the staged rows of scripted agents are replaced, external rows stay
         if (h->gap_specs > 0) gap_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions);
+        if (h->line_specs > 0) {   // the line followers: their agents' rows, from the track columns of the last step
+            TRY(track_upload(h));
+            line_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions, nullptr);
+        }
         if (h->mppi.on.m > 0) {   // the planner behind the controllers: its agents' rows, from the live state
             TRY(mppi_upload_tracks(h));
             TRY(mppi_launch_armed(h, EnvBlock{h->stream, 0, h->cfg.num_envs}, h->d_actions, nullptr));
@@ -4910,6 +4926,10 @@ int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_
         if (h_assign[i] < -1 || h_assign[i] >= n_specs) return fail(h, F110_ERR_INVALID, "controllers: assignment[%zu] = %d is outside -1..%d", i, h_assign[i], n_specs - 1);
     for (int32_t n : h->mppi.on.agents)
         if (h_assign[n] != -1) return fail(h, F110_ERR_INVALID, "controllers: agent %d is driven by the armed planner (f110_mppi_set)", n);
+    if (!h->line_assign_host.empty())
+        for (size_t i = 0; i < N; ++i)
+            if (h_assign[i] != -1 && h->line_assign_host[i] != -1)
+                return fail(h, F110_ERR_INVALID, "controllers: agent %zu has a line follower (f110_line_followers_set)", i);
     ENTER(h);
     if (!h->d_gap_specs) TRY(dmalloc(h, &h->d_gap_specs, (size_t)kGapMaxSpecs));
     if (!h->d_gap_assign) TRY(dmalloc(h, &h->d_gap_assign, N));
@@ -5195,6 +5215,7 @@ static int track_alloc(f110_sim *h)
 static int track_invalidate(f110_sim *h)
 {
     h->track_checked = false;
+    h->line_checked = false;
     if (h->d_trk_ok) HIPCHK(h, hipMemsetAsync(h->d_trk_ok, 0, (size_t)h->N * sizeof(int32_t), h->stream));
     return F110_OK;
 }
@@ -5516,6 +5537,7 @@ int f110_track_set_attrs(f110_sim *h, int32_t slot, const double *h_attr, int32_
     ts.d_attr = std::move(d_attr);
     ts.nattr = clear ? 0 : C;
     h->tracks_dirty = true;
+    h->line_checked = false;
     return F110_OK;
 }
 
@@ -5745,6 +5767,207 @@ int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, dou
     j.stride = 5;
     j.unit_L = track_L;
     nbr_launch(j, h->stream);
+    return sc.finish();
+}
+
+// ---- scripted cars: line followers (f110_line_followers_set / f110_follow_line_*, include/f110.h) -----------------------------------
+// the spec's refusals; on success the kernel's spec
+static int line_check_spec(f110_sim *h, const f110_line_follower *p, LineSpec &o)
+{
+    if (!p) return fail(h, F110_ERR_INVALID, "line follower: null spec");
+    const double d[] = {p->look_base, p->look_gain, p->look_min, p->look_max, p->lane_offset, p->wheelbase, p->steer_max, p->v_const, p->vgain,
+                        p->speed_look, p->lat_slow, p->v_recover, p->follow_range, p->follow_gap, p->follow_gain, p->lane_width, p->v_min, p->v_max};
+    for (double x : d)
+        if (!std::isfinite(x)) return fail(h, F110_ERR_INVALID, "line follower: every setting must be finite");
+    if (!(p->look_min > 0) || p->look_min > p->look_max) return fail(h, F110_ERR_INVALID, "line follower: 0 < look_min <= look_max is required");
+    if (p->look_base < 0 || p->look_gain < 0 || p->speed_look < 0) return fail(h, F110_ERR_INVALID, "line follower: look_base, look_gain and speed_look must be >= 0");
+    if (!(p->wheelbase > 0)) return fail(h, F110_ERR_INVALID, "line follower: wheelbase must be > 0");
+    if (p->steer_max < 0) return fail(h, F110_ERR_INVALID, "line follower: steer_max must be >= 0");
+    if (p->v_min < 0 || p->v_min > p->v_max) return fail(h, F110_ERR_INVALID, "line follower: 0 <= v_min <= v_max is required");
+    if (p->follow_range < 0 || p->lane_width < 0 || p->lat_slow < 0) return fail(h, F110_ERR_INVALID, "line follower: follow_range, lane_width and lat_slow must be >= 0");
+    if (p->speed_attr < -1 || p->speed_attr >= F110_TRACK_MAX_ATTRS)
+        return fail(h, F110_ERR_INVALID, "line follower: speed_attr = %d is outside -1..%d", p->speed_attr, (int)F110_TRACK_MAX_ATTRS - 1);
+    o = LineSpec{};
+    o.look_base = p->look_base, o.look_gain = p->look_gain, o.look_min = p->look_min, o.look_max = p->look_max;
+    o.lane_offset = p->lane_offset, o.wheelbase = p->wheelbase, o.steer_max = p->steer_max;
+    o.v_const = p->v_const, o.vgain = p->vgain, o.speed_look = p->speed_look, o.lat_slow = p->lat_slow, o.v_recover = p->v_recover;
+    o.follow_range = p->follow_range, o.follow_gap = p->follow_gap, o.follow_gain = p->follow_gain, o.lane_width = p->lane_width;
+    o.v_min = p->v_min, o.v_max = p->v_max;
+    o.speed_attr = p->speed_attr;
+    return F110_OK;
+}
+
+// what a slot must offer a spec: a track, the speed's attribute column, and on a closed track more length than the spec reaches
+static int line_check_slot(f110_sim *h, const LineSpec &sp, int slot)
+{
+    if (!track_has(h, slot)) return fail(h, F110_ERR_STATE, "line follower: map slot %d has no track (f110_track_set)", slot);
+    const f110_sim::TrackSlot &ts = h->tracks[slot];
+    if (sp.speed_attr >= ts.nattr)
+        return fail(h, F110_ERR_STATE, "line follower: speed_attr = %d, but the track on slot %d has %d attributes (f110_track_set_attrs)", sp.speed_attr, slot, ts.nattr);
+    const double reach = std::max(sp.look_max, sp.speed_look);
+    if (ts.closed && !(ts.L > reach))
+        return fail(h, F110_ERR_STATE, "line follower: the closed track on slot %d is %.6g m long, not longer than the reach of %.6g m", slot, ts.L, reach);
+    if (ts.closed && !(ts.L > 2.0 * sp.follow_range))
+        return fail(h, F110_ERR_STATE, "line follower: the closed track on slot %d is %.6g m long, not longer than twice follow_range = %.6g m", slot, ts.L, sp.follow_range);
+    return F110_OK;
+}
+
+// can the armed line followers run?  The refusals of a call, nothing launched.  The slot checks are remembered until the tracks,
+// the env maps or the arming change.
+static int line_ready(f110_sim *h)
+{
+    if (h->line_specs == 0) return fail(h, F110_ERR_STATE, "follow line: no line followers are armed (f110_line_followers_set)");
+    if (!h->track_on) return fail(h, F110_ERR_STATE, "follow line: tracking is off (f110_track_enable)");
+    if (h->line_checked) return F110_OK;
+    const int A = h->cfg.num_agents, slots = 1 + (int)h->extra_maps.size();
+    std::vector<char> seen((size_t)slots * LINE_MAX_SPECS, 0);
+    for (size_t n = 0; n < h->line_assign_host.size(); ++n) {
+        const int k = h->line_assign_host[n];
+        if (k < 0) continue;
+        const int slot = h->multi_map ? h->env_map_host[n / A] : 0;
+        char &s = seen[(size_t)slot * LINE_MAX_SPECS + k];
+        if (s) continue;
+        TRY(line_check_slot(h, h->line_specs_host[k], slot));
+        s = 1;
+    }
+    h->line_checked = true;
+    return F110_OK;
+}
+
+static void line_launch(LineJob &j, hipStream_t st, bool follow)
+{
+    if (j.groups <= 0) return;
+    j.shift = 0;
+    while ((1 << j.shift) < j.GA) ++j.shift;
+    const dim3 grid = grid1d((size_t)j.groups, 256 >> j.shift), block(256);
+    if (follow) hipLaunchKernelGGL(k_follow_line<true>, grid, block, 0, st, j);
+    else hipLaunchKernelGGL(k_follow_line<false>, grid, block, 0, st, j);
+}
+
+// the armed line followers over the agents of one env block, into d_actions [N][2] (and d_info [N][4] or null)
+static void line_launch_armed(f110_sim *h, const EnvBlock &b, double *d_actions, double *d_info)
+{
+    const size_t N = (size_t)h->N;
+    const int A = h->cfg.num_agents;
+    LineJob j{};
+    j.specs = h->d_line_specs;
+    j.assign = h->d_line_assign;
+    j.tracks = h->d_tracks;
+    j.attrs = h->d_track_attrs;
+    j.env_map = h->multi_map ? h->d_env_map : nullptr;
+    j.A = A;
+    j.unit_slot = -1;
+    j.GA = h->line_follow ? A : 1;
+    j.i0 = b.e0 * A;
+    j.groups = h->line_follow ? b.count : b.count * A;
+    j.stride = 1;
+    j.px = h->dev.snap_pose;   // the post-step pose of the observation, the one s was computed from
+    j.py = h->dev.snap_pose + N;
+    j.pth = h->dev.snap_pose + 2 * N;
+    j.pv = h->dev.state + 3 * N;   // the live longitudinal speed (0 for an env re-seated inside the step)
+    j.ps = h->d_trk;
+    j.plat = h->d_trk + 2 * N;
+    j.cnt = h->dev.step_count;
+    j.actions = d_actions;
+    j.info = d_info;
+    line_launch(j, b.stream, h->line_follow);
+}
+
+int f110_line_followers_set(f110_sim *h, const f110_line_follower *specs, int32_t n_specs, const int32_t *h_assign)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    if (n_specs == 0 && !specs && !h_assign) {   // disarm
+        ENTER(h);
+        h->line_specs = 0;
+        h->line_follow = false;
+        h->line_checked = false;
+        h->line_assign_host.clear();
+        h->d_line_specs.reset();   // (hipFree waits for the calls in flight that read them)
+        h->d_line_assign.reset();
+        return F110_OK;
+    }
+    if (!specs || !h_assign || n_specs < 1 || n_specs > F110_LINE_MAX_SPECS)
+        return fail(h, F110_ERR_INVALID, "line followers: 1..%d specs and an assignment, or NULL, 0, NULL", (int)F110_LINE_MAX_SPECS);
+    LineSpec ls[LINE_MAX_SPECS] = {};
+    bool follow = false;
+    for (int k = 0; k < n_specs; ++k) {
+        TRY(line_check_spec(h, specs + k, ls[k]));
+        follow = follow || (ls[k].follow_range > 0.0 && h->cfg.num_agents > 1);
+    }
+    const size_t N = (size_t)h->N;
+    for (size_t i = 0; i < N; ++i) {
+        if (h_assign[i] < -1 || h_assign[i] >= n_specs) return fail(h, F110_ERR_INVALID, "line followers: assignment[%zu] = %d is outside -1..%d", i, h_assign[i], n_specs - 1);
+        if (h_assign[i] != -1 && !h->gap_assign_host.empty() && h->gap_assign_host[i] != -1)
+            return fail(h, F110_ERR_INVALID, "line followers: agent %zu has a follow-the-gap controller (f110_controllers_set)", i);
+    }
+    for (int32_t n : h->mppi.on.agents)
+        if (h_assign[n] != -1) return fail(h, F110_ERR_INVALID, "line followers: agent %d is driven by the armed planner (f110_mppi_set)", n);
+    if (follow && h->cfg.num_agents > F110_LINE_MAX_AGENTS)
+        return fail(h, F110_ERR_STATE, "line followers: follow_range > 0 with %d agents per env, more than %d", h->cfg.num_agents, (int)F110_LINE_MAX_AGENTS);
+    ENTER(h);
+    if (!h->d_line_specs) TRY(dmalloc(h, &h->d_line_specs, (size_t)LINE_MAX_SPECS));
+    if (!h->d_line_assign) TRY(dmalloc(h, &h->d_line_assign, N));
+    HIPCHK(h, hipMemcpyAsync(h->d_line_specs, ls, sizeof(LineSpec) * n_specs, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_line_assign, h_assign, sizeof(int32_t) * N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (the sources are the caller's and this function's stack)
+    h->line_specs = n_specs;
+    h->line_follow = follow;
+    h->line_checked = false;
+    std::copy(ls, ls + LINE_MAX_SPECS, h->line_specs_host);
+    h->line_assign_host.assign(h_assign, h_assign + N);
+    return F110_OK;
+}
+
+int f110_follow_line_device(f110_sim *h, double *d_actions, double *d_info)
+{
+    if (!h || !d_actions) return fail(h, F110_ERR_INVALID, "follow line: null argument");
+    if (reinterpret_cast<uintptr_t>(d_actions) % 16 != 0 || reinterpret_cast<uintptr_t>(d_info) % 16 != 0)
+        return fail(h, F110_ERR_INVALID, "follow line: the actions or the info buffer is not 16-byte aligned");
+    TRY(line_ready(h));
+    TRY(tracks_current(h));   // (tracks or attributes set since the last step)
+    EnvBlocks w;   // behind a two-block step: each block's envs on the block's own stream (an agent reads its own env's rows and writes its own)
+    TRY(env_blocks_follow(h, w));
+    for (const EnvBlock &b : w) line_launch_armed(h, b, d_actions, d_info);
+    HIPCHK(h, hipGetLastError());
+    h->touched = false;
+    return F110_OK;
+}
+
+int f110_follow_line_batch(f110_sim *h, const f110_line_follower *spec, int32_t slot, int32_t A, const double *h_in, int32_t m, double *h_actions,
+                           double *h_raw)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    LineSpec ls;
+    TRY(line_check_spec(h, spec, ls));
+    if (A < 1 || A > F110_LINE_MAX_AGENTS) return fail(h, F110_ERR_INVALID, "follow line: A = %d is outside 1..%d", A, (int)F110_LINE_MAX_AGENTS);
+    if (m < 0 || m % A != 0 || (m > 0 && (!h_in || !h_actions))) return fail(h, F110_ERR_INVALID, "follow line: bad argument (m must be a multiple of A)");
+    TRY(line_check_slot(h, ls, slot));
+    if (m == 0) return F110_OK;
+    ENTER(h);
+    TRY(track_upload(h));
+    Scratch sc(h);
+    const bool follow = ls.follow_range > 0.0 && A > 1;
+    LineJob j{};
+    j.specs = sc.in(&ls, 1);
+    const double *din = sc.in(h_in, 7 * (size_t)m);
+    j.actions = sc.out(h_actions, 2 * (size_t)m);
+    j.raw = sc.out(h_raw, (size_t)LINE_NRAW * m);
+    TRY(sc.ready());
+    j.tracks = h->d_tracks;
+    j.attrs = h->d_track_attrs;
+    j.A = A;
+    j.unit_slot = slot;
+    j.GA = follow ? A : 1;
+    j.groups = follow ? m / A : m;
+    j.stride = 7;
+    j.px = din;
+    j.py = din + 1;
+    j.pth = din + 2;
+    j.pv = din + 3;
+    j.ps = din + 4;
+    j.plat = din + 5;
+    j.cnt_f = din + 6;
+    line_launch(j, h->stream, follow);
     return sc.finish();
 }
 
@@ -6275,6 +6498,8 @@ static int armed_check_list(f110_sim *h, const char *who, const int32_t *h_agent
         if (i > 0 && h_agents[i] <= h_agents[i - 1]) return fail(h, F110_ERR_INVALID, "%s: the agents are not strictly ascending at [%d]", who, i);
         if (drives && !h->gap_assign_host.empty() && h->gap_assign_host[h_agents[i]] != -1)
             return fail(h, F110_ERR_INVALID, "%s: agent %d has a follow-the-gap controller (f110_controllers_set)", who, h_agents[i]);
+        if (drives && !h->line_assign_host.empty() && h->line_assign_host[h_agents[i]] != -1)
+            return fail(h, F110_ERR_INVALID, "%s: agent %d has a line follower (f110_line_followers_set)", who, h_agents[i]);
     }
     return F110_OK;
 }

@@ -5123,6 +5123,143 @@ __global__ void __launch_bounds__(256) k_neighbors(NbrJob j)
     }
 }
 
+// ---- line follower (f110_follow_line_*; include/f110.h states the rule, f110_math.hpp line_* the arithmetic) ---------------------
+// One lane per agent.  kFollow = false (no armed spec looks for a car ahead, or one car per env): the lanes are the agents in
+// order, GA = 1.  kFollow = true: a group of G lanes per env, G the power of two >= A = GA (as in k_neighbors), 256 / G envs per
+// workgroup; every lane leaves (s, lat, v) of its agent in three LDS columns (6 KiB) and an armed lane walks b = 0 .. A - 1 of its
+// group, which all lanes of a group read at the same address at the same time: a broadcast.
+// What an agent costs without the car-ahead term is one dependent chain: its columns, then ~log2(nseg) probes of cum for each of
+// the two stations (the steering station and the speed station, independent of each other), then one round of segment and
+// attribute loads.  cum of the workgroup's first agent's slot is staged in LDS when it has at most kPreviewLdsSegs segments, as
+// k_track_preview does; a lane on another slot, or on a longer track, probes L2.  The rule defines k uniquely, so where a probe
+// was served does not show.
+// The early exit comes before the kernel's one barrier: every wave reads the assignment of the workgroup's 256 lanes (four
+// coalesced loads) and so knows which waves hold an armed agent.  A wave without one leaves before it loads anything else — with
+// G > 64 only when no wave of its env holds one, since the env's armed cars need its columns.  The waves that stay share the
+// staging of cum among themselves.  Behind the barrier a lane without a line follower leaves.  Idle lanes (G > A, or past the last
+// group) shadow the last live agent and store nothing.  No atomics, no scratch.
+struct LineJob {
+    const LineSpec *specs;         // device memory
+    const int32_t *assign;         // [.] -1 = no line follower, else the spec; null: spec 0 for every row (unit form)
+    const TrackDesc *tracks;
+    const PreviewAttr *attrs;
+    const int32_t *env_map;        // or null: slot 0
+    int32_t A, GA, shift, unit_slot;   // cars per env; agents per lane group (A or 1); lanes per group = 1 << shift; -1 or the unit form's slot
+    int32_t i0, groups;            // agents [i0, i0 + groups * GA)
+    int32_t stride, pad_;
+    const double *px, *py, *pth, *pv, *ps, *plat;   // `stride` apart per agent
+    const int32_t *cnt;            // step_count [.] (device form) ...
+    const double *cnt_f;           // ... or the unit form's column, `stride` apart
+    double *actions;               // [.][2]
+    double *info;                  // [.][4] or null
+    double *raw;                   // [.][12] or null
+};
+
+template <bool kFollow>
+__global__ void __launch_bounds__(256) k_follow_line(LineJob j)
+{
+    __shared__ double s_cum[kPreviewLdsSegs];
+    __shared__ double s_col[kFollow ? 3 * 256 : 1];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int G = 1 << j.shift, GA = j.GA;
+    const int gpw = 256 >> j.shift;
+    const int g_first = (int)blockIdx.x * gpw;
+    const int g_here = min(gpw, j.groups - g_first);   // >= 1 by the grid
+    const size_t i_first = (size_t)j.i0 + (size_t)g_first * GA;
+    // which waves hold an armed agent, and which stay
+    int armed_waves = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int t = w * 64 + lane, tg = t >> j.shift, ts = t & (G - 1);
+        bool on = tg < g_here && ts < GA;
+        if (on && j.assign) on = j.assign[i_first + (size_t)tg * GA + ts] >= 0;
+        if (__ballot(on) != 0ull) armed_waves |= 1 << w;
+    }
+    const int gsh = kFollow && j.shift > 6 ? j.shift - 6 : 0;   // waves per env = 1 << gsh
+    int stay = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        if (armed_waves & (((1 << (1 << gsh)) - 1) << (w >> gsh << gsh))) stay |= 1 << w;
+    stay = __builtin_amdgcn_readfirstlane(stay);
+    if (!(stay >> wave & 1)) return;   // before the barrier: nothing but the assignment was loaded
+    const int n_stay = __popc(stay), rank = __popc(stay & ((1 << wave) - 1));
+
+    const int grp = tid >> j.shift, sub = tid & (G - 1);
+    const bool live = grp < g_here && sub < GA;
+    const int a = sub < GA ? sub : GA - 1;
+    const size_t i = i_first + (size_t)(grp < g_here ? grp : g_here - 1) * GA + a, r = i * j.stride;
+    const int ks = j.assign ? j.assign[i] : 0;
+    const bool armed = live && ks >= 0;
+    const int slot0 = j.unit_slot >= 0 ? j.unit_slot : (j.env_map ? j.env_map[i_first / j.A] : 0);
+    const TrackDesc t0 = j.tracks[slot0];
+    const bool staged = t0.nseg > 0 && t0.nseg <= kPreviewLdsSegs;
+    if (staged) {
+        const double *cum0 = t0.cols + (size_t)kTrkCum * t0.nseg;
+        for (int q = rank * 64 + lane; q < t0.nseg; q += 64 * n_stay) s_cum[q] = cum0[q];
+    }
+    const double s = j.ps[r], lat = j.plat[r], v = j.pv[r];
+    if (kFollow) {
+        s_col[tid] = s;
+        s_col[256 + tid] = lat;
+        s_col[512 + tid] = v;
+    }
+    __syncthreads();
+    if (!armed) return;
+
+    const LineSpec sp = j.specs[ks];
+    double2 *act = reinterpret_cast<double2 *>(j.actions) + i;
+    double2 *info = j.info ? reinterpret_cast<double2 *>(j.info) + 2 * i : nullptr;
+    double *raw = j.raw ? j.raw + (size_t)LINE_NRAW * i : nullptr;
+    if (j.cnt ? j.cnt[i] == 0 : j.cnt_f[r] == 0.0) {   // re-seated inside the step just taken
+        double z[2];
+        line_fresh(z, raw);
+        *act = make_double2(0.0, 0.0);
+        if (info) info[0] = make_double2(0.0, 0.0), info[1] = make_double2(-1.0, -1.0);
+        return;
+    }
+    const int slot = j.unit_slot >= 0 ? j.unit_slot : (j.env_map ? j.env_map[i / j.A] : 0);
+    const TrackDesc td = j.tracks[slot];
+    const PreviewAttr at = j.attrs[slot];
+    PreviewTrack tr;
+    tr.cols = td.cols;
+    tr.attr = at.a;
+    tr.nseg = td.nseg;
+    tr.closed = td.closed;
+    tr.C = at.a ? at.C : 0;
+    tr.npts = td.closed ? td.nseg : td.nseg + 1;
+    tr.L = td.L;
+    const bool in_lds = staged && slot == slot0;
+    const double *gcum = td.cols + (size_t)kTrkCum * td.nseg;
+    const double ld = line_lookahead(sp, v);
+    const double s_t = line_ahead(s, ld, td.closed, td.L);
+    const double s_v = line_ahead(s, sp.speed_look, td.closed, td.L);
+    const int k = in_lds ? preview_segment(s_cum, td.nseg, s_t) : preview_segment(gcum, td.nseg, s_t);
+    double vref = sp.v_const;
+    if (sp.speed_attr >= 0) {   // (a slot without the column is refused on the host)
+        const int kv = in_lds ? preview_segment(s_cum, td.nseg, s_v) : preview_segment(gcum, td.nseg, s_v);
+        vref = line_attr(tr, sp.speed_attr, kv, s_v);
+    }
+    double X, Y, Tx, Ty, lx, ly, c, sn;
+    line_target(tr, k, s_t, sp.lane_offset, X, Y, Tx, Ty);
+    cos_sin(j.pth[r], c, sn);
+    const double steer = line_steer(sp, c, sn, j.px[r], j.py[r], Tx, Ty, lx, ly);
+    double speed = line_speed(sp, vref, lat);
+    int lim = -1;
+    if (kFollow && sp.follow_range > 0.0) {
+        const int base = tid - sub;
+        const double Lw = td.closed ? td.L : 0.0;
+        for (int b = 0; b < GA; ++b)
+            if (b != a) line_offer(sp, s, lat, s_col[base + b], s_col[256 + base + b], s_col[512 + base + b], Lw, b, speed, lim);
+    }
+    *act = make_double2(steer, line_clamp(sp, speed));
+    if (info) info[0] = make_double2(ld, vref), info[1] = make_double2((double)k, (double)lim);
+    if (raw) {
+        raw[LINE_RAW_LD] = ld, raw[LINE_RAW_ST] = s_t, raw[LINE_RAW_K] = (double)k, raw[LINE_RAW_X] = X, raw[LINE_RAW_Y] = Y;
+        raw[LINE_RAW_TX] = Tx, raw[LINE_RAW_TY] = Ty, raw[LINE_RAW_LX] = lx, raw[LINE_RAW_LY] = ly, raw[LINE_RAW_VREF] = vref;
+        raw[LINE_RAW_LIM] = (double)lim, raw[LINE_RAW_SPEED] = speed;
+    }
+}
+
 // ---- rollout (f110_rollout_*; include/f110.h states the rule, f110_math.hpp roll_* the arithmetic) -------------------------------
 // k_rollout: one lane per (agent, candidate), candidate-minor, so an agent's K candidates are consecutive lanes; 256-lane workgroups
 // over the flat index.  A lane is one float64 dependent chain of H * repeat * ~1900 instructions with 16 bytes of action read per

@@ -1707,6 +1707,151 @@ F110_HD void nbr_env(const NbrSpec &sp, const double *rows, int A, double L, Nbr
     }
 }
 
+// ------------------------------------------------------------------ line follower (include/f110.h, f110_line_follower)
+// No reference counterpart.  Pure pursuit on the track of the agent's map slot, the speed from a track attribute, slower behind a
+// car ahead.  Float64 adds, multiplies, divides and compares, nothing to contract; cos_sin and atan are the only libm calls and
+// only lx, ly and steer sit behind them: no branch and no part of the speed does.
+enum { LINE_MAX_SPECS = 8, LINE_MAX_AGENTS = 256, LINE_NRAW = 12, LINE_NINFO = 4 };
+enum { LINE_RAW_LD = 0, LINE_RAW_ST, LINE_RAW_K, LINE_RAW_X, LINE_RAW_Y, LINE_RAW_TX, LINE_RAW_TY, LINE_RAW_LX, LINE_RAW_LY, LINE_RAW_VREF,
+       LINE_RAW_LIM, LINE_RAW_SPEED };
+
+struct LineSpec {
+    double look_base, look_gain, look_min, look_max;
+    double lane_offset, wheelbase, steer_max;
+    double v_const, vgain, speed_look, lat_slow, v_recover;
+    double follow_range, follow_gap, follow_gain, lane_width;
+    double v_min, v_max;
+    int32_t speed_attr, pad_;   // -1: v_const
+};
+
+// step 1: the lookahead distance; a NaN v gives look_min
+F110_HD double line_lookahead(const LineSpec &sp, double v)
+{
+    double ld = sp.look_base + sp.look_gain * fabs(v);
+    if (!(ld >= sp.look_min)) ld = sp.look_min;
+    else if (ld > sp.look_max) ld = sp.look_max;
+    return ld;
+}
+
+// steps 2 and 4: the arc length d ahead of s, the preview's station rule (one wrap on a closed track)
+F110_HD double line_ahead(double s, double d, int closed, double L) { return preview_station_s(s, d, 0.0, 0, closed, L); }
+
+// step 2: the station (X, Y) at arc length s_t in segment k, by the preview's station rule, and the target lane_offset to its left
+F110_HD void line_target(const PreviewTrack &tr, int k, double s_t, double lane_offset, double &X, double &Y, double &Tx, double &Ty)
+{
+    PreviewTrack geo = tr;
+    geo.C = 0;   // (the geometry channels only)
+    double w[PREVIEW_NCHANNELS];
+    preview_station(geo, k, s_t, PREVIEW_FRAME_WORLD, 0.0, 0.0, 1.0, 0.0, w);
+    X = w[0];
+    Y = w[1];
+    Tx = X - lane_offset * w[3];
+    Ty = Y + lane_offset * w[2];
+}
+
+// step 3: the target in the car's frame and the pure-pursuit steer, clamped
+F110_HD double line_steer(const LineSpec &sp, double c, double sn, double px, double py, double Tx, double Ty, double &lx, double &ly)
+{
+    const double rx = Tx - px, ry = Ty - py;
+    lx = c * rx + sn * ry;
+    ly = c * ry - sn * rx;
+    const double d2 = lx * lx + ly * ly;
+    double steer = d2 > 0.0 ? atan(2.0 * sp.wheelbase * ly / d2) : 0.0;
+    if (steer > sp.steer_max) steer = sp.steer_max;
+    else if (steer < -sp.steer_max) steer = -sp.steer_max;
+    return steer;
+}
+
+// step 4: attribute column c at arc length s in segment k, by the preview's attribute rule
+F110_HD double line_attr(const PreviewTrack &tr, int c, int k, double s)
+{
+    const size_t n = (size_t)tr.nseg;
+    const double len = tr.cols[5 * n + k], cum = tr.cols[6 * n + k];
+    const double t = preview_clip01((s - cum) / len);
+    const int k1 = k + 1 == tr.npts ? 0 : k + 1;
+    const double a0 = tr.attr[(size_t)c * tr.npts + k], a1 = tr.attr[(size_t)c * tr.npts + k1];
+    return a0 + t * (a1 - a0);
+}
+
+// step 4: the line's speed, or the recovery speed away from the lane
+F110_HD double line_speed(const LineSpec &sp, double vref, double lat)
+{
+    double speed = sp.vgain * vref;
+    if (fabs(lat - sp.lane_offset) > sp.lat_slow && sp.v_recover < speed) speed = sp.v_recover;
+    return speed;
+}
+
+// step 5: car b (s_b, lat_b, v_b) as the car at (s, lat) sees it; L: the wrap length (0: none).  A NaN cap never wins.
+F110_HD void line_offer(const LineSpec &sp, double s, double lat, double sb, double latb, double vb, double L, int b, double &speed, int &lim)
+{
+    const double g = nbr_gap(s, sb, L);
+    if (g > 0.0 && g <= sp.follow_range && fabs(latb - lat) <= sp.lane_width) {
+        const double cap = vb + sp.follow_gain * (g - sp.follow_gap);
+        if (cap < speed) {
+            speed = cap;
+            lim = b;
+        }
+    }
+}
+
+// step 6
+F110_HD double line_clamp(const LineSpec &sp, double speed)
+{
+    if (speed < sp.v_min) speed = sp.v_min;
+    if (speed > sp.v_max) speed = sp.v_max;
+    return speed;
+}
+
+// a row whose step_count is 0: the action (0, 0); raw (or null) all 0.0 but k and lim, which are -1.0
+F110_HD void line_fresh(double *action, double *raw)
+{
+    action[0] = 0.0;
+    action[1] = 0.0;
+    if (raw) {
+        for (int q = 0; q < LINE_NRAW; ++q) raw[q] = 0.0;
+        raw[LINE_RAW_K] = -1.0;
+        raw[LINE_RAW_LIM] = -1.0;
+    }
+}
+
+// one env, serially (the kernel gives every agent a lane; this is what the unit harness runs): rows [A][7] = x, y, theta, v, s,
+// lateral, step_count; actions [A][2], raw [A][12] or null
+F110_HD void line_env(const LineSpec &sp, const PreviewTrack &tr, const double *rows, int A, double *actions, double *raw)
+{
+    const double *cum = tr.cols + 6 * (size_t)tr.nseg;
+    const double Lw = tr.closed ? tr.L : 0.0;
+    for (int a = 0; a < A; ++a) {
+        const double *r = rows + 7 * (size_t)a;
+        double *act = actions + 2 * (size_t)a, *rw = raw ? raw + (size_t)LINE_NRAW * a : nullptr;
+        if (r[6] == 0.0) {
+            line_fresh(act, rw);
+            continue;
+        }
+        const double px = r[0], py = r[1], v = r[3], s = r[4], lat = r[5];
+        const double ld = line_lookahead(sp, v);
+        const double s_t = line_ahead(s, ld, tr.closed, tr.L);
+        const int k = preview_segment(cum, tr.nseg, s_t);
+        double X, Y, Tx, Ty, lx, ly, c, sn;
+        line_target(tr, k, s_t, sp.lane_offset, X, Y, Tx, Ty);
+        cos_sin(r[2], c, sn);
+        const double steer = line_steer(sp, c, sn, px, py, Tx, Ty, lx, ly);
+        const double s_v = line_ahead(s, sp.speed_look, tr.closed, tr.L);
+        const double vref = sp.speed_attr >= 0 ? line_attr(tr, sp.speed_attr, preview_segment(cum, tr.nseg, s_v), s_v) : sp.v_const;
+        double speed = line_speed(sp, vref, lat);
+        int lim = -1;
+        if (sp.follow_range > 0.0 && A > 1)
+            for (int b = 0; b < A; ++b)
+                if (b != a) line_offer(sp, s, lat, rows[7 * (size_t)b + 4], rows[7 * (size_t)b + 5], rows[7 * (size_t)b + 3], Lw, b, speed, lim);
+        act[0] = steer;
+        act[1] = line_clamp(sp, speed);
+        if (rw) {
+            rw[LINE_RAW_LD] = ld, rw[LINE_RAW_ST] = s_t, rw[LINE_RAW_K] = (double)k, rw[LINE_RAW_X] = X, rw[LINE_RAW_Y] = Y;
+            rw[LINE_RAW_TX] = Tx, rw[LINE_RAW_TY] = Ty, rw[LINE_RAW_LX] = lx, rw[LINE_RAW_LY] = ly, rw[LINE_RAW_VREF] = vref;
+            rw[LINE_RAW_LIM] = (double)lim, rw[LINE_RAW_SPEED] = speed;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ rollout (include/f110.h, f110_rollout)
 // No reference counterpart of its own: a candidate's motion is advance_vehicle (RaceCar.update_pose) called H * repeat times and its
 // clearance sample_distance (xy_2_rc + the table) at the reference point, both called as they are.  What is added here is the

@@ -17,6 +17,7 @@ import numpy as np
 from . import _ffi
 from .core import DEFAULT_PARAMS
 from .gap_follower import coerce_scripted
+from .line_follower import MAX_AGENTS as LINE_MAX_AGENTS, coerce_scripted_mixed, has_line_follower
 from .mppi import split_scripted
 from .opponents import split_mppi_opponents
 from .particle_filter import split_filter
@@ -446,6 +447,10 @@ class F110VecEnv(object):
     step(actions) keeps its [E][A][2] shape: the rows of scripted cars are ignored and replaced on the device.  A scripted
     car takes the zero action on the first step of an episode (reset()'s own step, and the step after an in-step re-seat).
     It needs device_logic=True (ValueError otherwise).  Controllers hold no state: snapshots do not change.
+    An entry may also be a LineFollower: that car drives the line of its env's map slot — pure pursuit on the track,
+    the speed from a track attribute (the raceline's vx with track='raceline'), slower behind a car ahead — from the track columns
+    of the last step.  It needs track= / tracks= (ValueError otherwise).  The list of the (assign, [controllers]) form may mix
+    the two controller classes, assign indexing the list; a dict in it is a GapFollower's settings.
     An entry may instead be an Mppi, at most one per env object: every env's car `slot` then plans on the device from its
     live state, behind the controllers, with the stream PCG64(SeedSequence(seed, spawn_key=(global agent index,))) of the env's
     `seed`.  `planner=(slot, Mppi)` says the same next to the (assign, [controllers]) form.  The planner's nominal sequences and
@@ -527,16 +532,27 @@ class F110VecEnv(object):
             if not self.device_logic:
                 raise ValueError("scripted= needs device_logic=True (any other loop arms env.sim.batch.set_controllers / set_mppi and calls "
                                  "BatchSim.follow_gap_device / mppi_device on its device action buffer)")
-        if scripted is not None:
+        self.line_followers = None   # (assign [E][A], [LineFollower]): the scripted cars that drive their slot's line
+        if scripted is not None and has_line_follower(scripted):
+            self.scripted, self.line_followers = coerce_scripted_mixed(scripted, self.num_envs, self.num_agents)
+        elif scripted is not None:
             self.scripted = coerce_scripted(scripted, self.num_envs, self.num_agents)
+        if self.scripted is not None:
             for c in self.scripted[1]:
                 c.window(kwargs.get('num_beams', 1080))
+        if self.line_followers is not None:
+            if not tracks:
+                raise ValueError("a LineFollower needs a track on its envs' map slots (track= or tracks=)")
+            if self.num_agents > LINE_MAX_AGENTS and any(c.follow_range > 0.0 for c in self.line_followers[1]):
+                raise ValueError("a LineFollower with follow_range > 0 serves at most %d cars per env" % LINE_MAX_AGENTS)
         if planner is not None:
             slot, mp = planner
             if not (0 <= slot < self.num_agents):
                 raise ValueError("scripted: slot %r is not one of the %d cars of an env" % (slot, self.num_agents))
             if self.scripted is not None and np.any(self.scripted[0][:, slot] != -1):
                 raise ValueError("scripted: car %d has both a follow-the-gap controller and the planner" % slot)
+            if self.line_followers is not None and np.any(self.line_followers[0][:, slot] != -1):
+                raise ValueError("scripted: car %d has both a line follower and the planner" % slot)
             if mp.needs_track and not tracks:
                 raise ValueError("the planner's w_progress and w_lat need a track (track= or tracks=)")
             self.planner = (slot, mp)
@@ -636,6 +652,8 @@ class F110VecEnv(object):
             self._build_host_block()
             if self.scripted is not None:
                 b.set_controllers(*self.scripted)
+            if self.line_followers is not None:
+                b.set_line_followers(*self.line_followers)
             if self.planner is not None:   # agent_base: this handle's first global agent (ShardedVecEnv), so a sharded run draws the same numbers
                 b.set_mppi(self.planner[1], np.arange(self.num_envs) * self.num_agents + self.planner[0], seed=self.seed,
                            agent_base=int(kwargs.get('env_base', 0)) * self.num_agents)
@@ -855,7 +873,7 @@ class F110VecEnv(object):
         if self._encode or self.track_preview is not None or self.neighbors is not None or self.particle_filter is not None:
             # one wait per step: the step enqueued without a wait, the encode / the preview / the neighbours and their copies into page-locked memory behind it
             b.step_host(hb, None, auto_reset=self.auto_reset, sync=False, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
-                        scripted=self.scripted is not None or self.planner is not None)
+                        scripted=self.scripted is not None or self.line_followers is not None or self.planner is not None)
             if self._encode:
                 b.encode_obs_device(self.obs_encoder, self.encoded_stack, fill=self._enc_fill, pinned=self._enc_pinned)
                 self._enc_fill = False
@@ -869,7 +887,7 @@ class F110VecEnv(object):
                 b.sync()
         else:
             b.step_host(hb, None, auto_reset=self.auto_reset, sync=sync, mapped_actions=self.mapped_actions, spin=self.spin_wait, fuse=self.fuse_host_block, poll=self.poll_wait,
-                        scripted=self.scripted is not None or self.planner is not None)
+                        scripted=self.scripted is not None or self.line_followers is not None or self.planner is not None)
         self.sim._steps_since_full_reset += 1
         if not sync:
             return None

@@ -122,7 +122,8 @@ class ShardedVecEnv(object):
             kwargs['mppi_opponents'] = dict(opponents=op, w_hit=w_hit, w_near=w_near, near_ref=near_ref)
         if scripted is not None:
             from .gap_follower import coerce_scripted
-            scripted = coerce_scripted(scripted, E, self.num_agents)
+            from .line_follower import has_line_follower, mixed_scripted   # (a mixed list is split by class in each shard)
+            scripted = (mixed_scripted if has_line_follower(scripted) else coerce_scripted)(scripted, E, self.num_agents)
         self.scripted = scripted
         self._workers = [_Worker(k) for k in range(K)]
         self.shards = [None] * K

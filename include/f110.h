@@ -481,9 +481,10 @@ typedef struct f110_host_block {
 #define F110_STEP_SCRIPTED 64       /* scripted cars (f110_controllers_set, below): h_actions is staged into device memory (as
                                        without F110_STEP_ACTIONS_MAPPED, which is ignored), the armed controllers overwrite their
                                        agents' rows there from the scans of the last step, and the step runs from that buffer.
-                                       An armed planner (f110_mppi_set, below) then writes its agents' rows behind them.
-                                       The one-launch form of tiny batches does not apply.  F110_ERR_STATE with neither kind
-                                       armed.  Without the flag the call looks at neither the controllers nor the planner. */
+                                       Armed line followers (f110_line_followers_set, below) then write theirs, and an armed
+                                       planner (f110_mppi_set, below) its agents' rows behind them.
+                                       The one-launch form of tiny batches does not apply.  F110_ERR_STATE with none of the
+                                       three kinds armed.  Without the flag the call looks at none of them. */
 int f110_step_host(f110_sim *h, const double *h_actions /* [N][2] */, const f110_host_block *out, int32_t flags);
 /* measurement aid: {calls, host microseconds spent enqueuing, host microseconds spent waiting} of the
  * f110_step_host calls since the last read (cleared by the read) */
@@ -977,7 +978,8 @@ typedef struct f110_gap_follower {
 /* arms the controllers: specs [n_specs], 1 <= n_specs <= F110_GAP_MAX_SPECS, and h_assign [N] int32: -1 = external (the agent's
  * action comes from the caller), else the index of the agent's spec (anything else: F110_ERR_INVALID, nothing changed).
  * NULL, 0, NULL disarms them.  Arming launches nothing and no step looks at it without F110_STEP_SCRIPTED.  An agent that the
- * armed planner (f110_mppi_set) drives cannot have a controller too: F110_ERR_INVALID, nothing changed. */
+ * armed planner (f110_mppi_set) or a line follower (f110_line_followers_set) drives cannot have a controller too:
+ * F110_ERR_INVALID, nothing changed. */
 int f110_controllers_set(f110_sim *h, const f110_gap_follower *specs, int32_t n_specs, const int32_t *h_assign);
 /* writes the armed agents' rows of d_actions [N][2] (device memory, 16-byte aligned) from the scans of the last step; rows of
  * external agents are never written (their waves leave before they load anything else).  Asynchronous on the handle's stream;
@@ -1095,6 +1097,72 @@ int f110_neighbors_device(f110_sim *h, const f110_neighbors *spec, float *d_out 
  * [m][K] or NULL: b per slot, -1 for an empty one. */
 int f110_neighbors_batch(f110_sim *h, const f110_neighbors *spec, int32_t A, double track_L, const double *h_in /* [m][5] x, y, theta, v, s */,
                          int32_t m, float *h_out /* [m][K][D] */, double *h_raw /* [m][K][10] or NULL */, int32_t *h_idx /* [m][K] or NULL */);
+
+/* ---- scripted cars: a line follower per agent (no reference counterpart: pure pursuit on the track of the agent's map slot,
+ * the speed from a track attribute, slower behind a car ahead; the opponent that drives the slot's raceline) ----
+ * A third kind of scripted car beside the follow-the-gap controller and the planner.  It is stateless, runs only when called
+ * (f110_follow_line_device, or f110_step_host with F110_STEP_SCRIPTED) and changes no simulator state; the state blobs do not
+ * contain it.  Everything is float64 without contraction, every operation one correctly rounded IEEE operation except cos_sin and
+ * atan in step 3, and only lx, ly and steer sit behind those: no branch and no part of the speed does.
+ * Agent n = e * A + a with spec S; its track (the one on its env's map slot) has the segments (ax, ay, dx, dy, len, cum)[k], the
+ * length L and the attributes a[c][.].  (px, py, th) is the observation's pose of the step just taken (agent_poses), s and lat
+ * the track columns s and lateral of that step, v is state[3] as it stands (the neighbours' rule), cnt its step_count.
+ *   0 fresh     cnt == 0 (re-seated inside the step just taken): the action is (0.0, 0.0)
+ *   1 lookahead ld = look_base + look_gain * fabs(v);  if (!(ld >= look_min)) ld = look_min; else if (ld > look_max) ld = look_max
+ *               (a NaN v gives look_min)
+ *   2 station   s_t = s + ld; on a closed track: if (s_t >= L) s_t = s_t - L, once.  k, t, (X, Y) and (ux, uy) by the track
+ *               preview's station rule at s_t (above; on an open track a station beyond the end clips to the last point).
+ *               Tx = X - lane_offset * uy;  Ty = Y + lane_offset * ux
+ *   3 steer     c = cos th, sn = sin th;  rx = Tx - px;  ry = Ty - py;  lx = c * rx + sn * ry;  ly = c * ry - sn * rx;
+ *               d2 = lx * lx + ly * ly;  steer = d2 > 0 ? atan(((2.0 * wheelbase) * ly) / d2) : 0.0;
+ *               if (steer > steer_max) steer = steer_max; else if (steer < -steer_max) steer = -steer_max
+ *   4 speed     s_v = s + speed_look, with the same single wrap;  vref = attribute speed_attr at s_v by the preview's k, t and
+ *               attribute rule, or v_const when speed_attr == -1;  speed = vgain * vref;
+ *               if (fabs(lat - lane_offset) > lat_slow && v_recover < speed) speed = v_recover
+ *   5 car ahead only when follow_range > 0 and A > 1; lim = -1; for b = 0 .. A - 1, b != a, ascending:
+ *               g = s_b - s, wrapped by the neighbours' GAP_S rule on a closed track;
+ *               b is eligible iff g > 0 && g <= follow_range && fabs(lat_b - lat) <= lane_width;
+ *               cap = v_b + follow_gain * (g - follow_gap);  if (cap < speed) { speed = cap; lim = b; }   (a NaN cap never wins)
+ *   6 clamp     if (speed < v_min) speed = v_min;  if (speed > v_max) speed = v_max.  The action is (steer, speed).
+ * Refused with F110_ERR_INVALID, nothing launched or written, device allocations as they were: a non-finite setting;
+ *   look_min <= 0, look_min > look_max, look_base < 0, look_gain < 0, speed_look < 0; wheelbase <= 0, steer_max < 0, v_min < 0,
+ *   v_min > v_max; follow_range < 0, lane_width < 0, lat_slow < 0, speed_attr outside -1..3; an assignment outside
+ *   -1..n_specs - 1, more than F110_LINE_MAX_SPECS specs; an agent that also has a follow-the-gap controller or the armed planner
+ *   (f110_controllers_set and f110_mppi_set in turn refuse an agent that a line follower drives); a null or not 16-byte
+ *   aligned action or info buffer.
+ * Refused with F110_ERR_STATE: tracking off (device form); an armed agent's slot without a track or without attribute column
+ *   speed_attr; a closed track in use with L <= max(look_max, speed_look) (one subtraction must be enough) or L <= 2 *
+ *   follow_range; num_agents > 256 with follow_range > 0 (at arming); nothing armed.
+ * Not offered: overtaking manoeuvres (the planner with the opponent term does those), a lane offset that varies along the line,
+ * a wheelbase read from the agent's parameter row. */
+enum { F110_LINE_MAX_SPECS = 8, F110_LINE_MAX_AGENTS = 256, F110_LINE_NRAW = 12, F110_LINE_NINFO = 4 };
+typedef struct f110_line_follower {
+    double look_base, look_gain, look_min, look_max;   /* m, s, m, m (0.8, 0.25, 0.6, 3.9) */
+    double lane_offset;                                /* m to the left of the line (0.0) */
+    double wheelbase, steer_max;                       /* (0.3302, 0.4189) */
+    double v_const, vgain, speed_look;                 /* (2.0, 0.8, 0.6) */
+    double lat_slow, v_recover;                        /* (0.5, 1.5) */
+    double follow_range, follow_gap, follow_gain;      /* m, m, 1/s (6.0, 1.0, 1.0); follow_range 0: no car-ahead term */
+    double lane_width;                                 /* m (0.6) */
+    double v_min, v_max;                               /* (0.0, 20.0) */
+    int32_t speed_attr;                                /* -1: v_const, else the track's attribute column (1: the raceline's vx) */
+    int32_t pad_;                                      /* alignment; ignored */
+} f110_line_follower;
+/* arms the line followers: specs [n_specs], 1 <= n_specs <= F110_LINE_MAX_SPECS, and h_assign [N] int32: -1 = no line follower,
+ * else the index of the agent's spec.  NULL, 0, NULL disarms them and frees their device memory.  Arming launches nothing and no
+ * step looks at it without F110_STEP_SCRIPTED. */
+int f110_line_followers_set(f110_sim *h, const f110_line_follower *specs, int32_t n_specs, const int32_t *h_assign /* [N] */);
+/* writes the armed agents' rows of d_actions [N][2] (device memory, 16-byte aligned) and, when given, of d_info [N][4] float64 =
+ * ld, vref, (double)k, (double)lim (-1.0 when no car limits; a fresh row: 0, 0, -1, -1).  Rows of agents without a line follower
+ * are never written.  Asynchronous on the handle's stream; right behind a two-block step it runs per env block on the block's
+ * own stream (as f110_follow_gap_device does). */
+int f110_follow_line_device(f110_sim *h, double *d_actions /* [N][2] */, double *d_info /* [N][4] or NULL */);
+/* unit form on host arrays, on the track of `slot` (tracking need not be on; it does not project): h_in [m][7] = x, y, theta, v,
+ * s, lateral, step_count per row, env-major; m a multiple of A, A in 1..256 whatever the handle's num_agents is.  h_actions
+ * [m][2]; h_raw [m][12] or NULL = ld, s_t, k, X, Y, Tx, Ty, lx, ly, vref, lim, the speed before step 6 (a fresh row: 0.0 but k and
+ * lim, which are -1.0). */
+int f110_follow_line_batch(f110_sim *h, const f110_line_follower *spec, int32_t slot, int32_t A, const double *h_in /* [m][7] */,
+                           int32_t m, double *h_actions /* [m][2] */, double *h_raw /* [m][12] or NULL */);
 
 /* ---- rollout: K candidate action sequences per agent rolled ahead from the agent's live state, against the map (no reference
  * counterpart: what MPPI, motion-primitive and lattice planners and safety shields ask K times per agent per step — "if I apply
