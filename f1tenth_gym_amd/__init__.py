@@ -13,6 +13,7 @@ from .sharded import ShardedVecEnv  # noqa: F401
 from .planner import PurePursuitPlanner  # noqa: F401
 from .track import Track  # noqa: F401
 from .reset_sampler import ResetSampler  # noqa: F401
+from .param_sampler import ParamSampler  # noqa: F401
 from .obs_encoder import ObsEncoder  # noqa: F401
 from .gap_follower import GapFollower  # noqa: F401
 from .line_follower import LineFollower  # noqa: F401

@@ -59,6 +59,16 @@ class ResetSamplerSpec(C.Structure):
                 ("heading", C.c_double), ("clearance", C.c_double), ("attempts", C.c_int32), ("pad", C.c_int32)]
 
 
+class ParamDist(C.Structure):
+    """struct f110_param_dist"""
+    _fields_ = [("kind", C.c_int32), ("scope", C.c_int32), ("a", C.c_double), ("b", C.c_double), ("lo", C.c_double),
+                ("hi", C.c_double), ("relative", C.c_int32), ("pad", C.c_int32)]
+
+
+PARAM_FIXED, PARAM_UNIFORM, PARAM_NORMAL = 0, 1, 2
+PARAM_SCOPE_AGENT, PARAM_SCOPE_ENV = 0, 1
+
+
 class ObsSpec(C.Structure):
     """struct f110_obs_spec"""
     _fields_ = [("beam_lo", C.c_int32), ("beam_hi", C.c_int32), ("sectors", C.c_int32), ("pool", C.c_int32),
@@ -355,6 +365,13 @@ PROTOTYPES = {
     "f110_reset_sample_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f110_reset_sampler_stats": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_int32]),
     "f110_reset_sampler_poses": (C.c_int, [C.c_void_p, _dp]),
+    "f110_param_sampler_set": (C.c_int, [C.c_void_p, C.c_void_p, _u64p]),
+    "f110_param_sample": (C.c_int, [C.c_void_p, _u8p]),
+    "f110_param_sample_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "f110_param_sampler_stats": (C.c_int, [C.c_void_p, _u64p, C.c_int32]),
+    "f110_params_get": (C.c_int, [C.c_void_p, _dp]),
+    "f110_params_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "f110_param_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int32, _u64p, C.c_int32, C.c_int32, _dp, _u64p]),
     "f110_episode_start_views": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "f110_edt_sq": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, _u32p]),
     "f110_beam_dir_index_batch": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i32p]),

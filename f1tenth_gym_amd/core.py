@@ -210,6 +210,9 @@ STATE_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("k", "<i4"), ("A"
 assert STATE_HEADER.itemsize == _ffi.STATE_HEADER_BYTES
 STATE_MAGIC = b"F110SNAP"
 STATE_COLUMNS = {"agent": 1, "scans": 2, "rng": 4, "rng_seed": 8, "episode": 16, "params": 32, "env_map": 64, "reset_rng": 128}
+# ... and the parameter sampler's stream column, which a handle has next to "params" and never together with set_params_batch's
+# rows: not every column of both tables can be active on one handle
+STATE_COLUMNS_SAMPLED = {"param_rng": 256}
 NOISE_MODES = ("off", "table", "shared_rng", "per_agent_rng")
 
 
@@ -235,7 +238,7 @@ class StateBlob(object):
         self.data = data
         self.header = {
             "version": int(h["version"]), "num_envs": int(h["k"]), "num_agents": int(h["A"]), "num_beams": int(h["B"]),
-            "scans": bool(int(h["flags"]) & _ffi.STATE_SCANS), "columns": tuple(n for n, b in STATE_COLUMNS.items() if cols & b),
+            "scans": bool(int(h["flags"]) & _ffi.STATE_SCANS), "columns": tuple(n for n, b in list(STATE_COLUMNS.items()) + list(STATE_COLUMNS_SAMPLED.items()) if cols & b),
             "noise_mode": NOISE_MODES[int(h["noise_mode"])] if 0 <= int(h["noise_mode"]) < len(NOISE_MODES) else int(h["noise_mode"]),
             "noise_rows": int(h["noise_rows"]), "noise_id": tuple(int(v) for v in h["noise_id"]), "std_dev": float(h["std_dev"]),
             "n_maps": int(h["n_maps"]), "ego_idx": int(h["ego_idx"]), "max_step": int(h["max_step"]), "total_bytes": int(h["total_bytes"])}
@@ -294,6 +297,7 @@ class BatchSim(object):
         pv = _ffi.params_vector(self.params)
         for i in range(_ffi.NPARAMS):
             cfg.params[i] = pv[i]
+        self._slot_rows = np.tile(np.asarray(pv, dtype=np.float64), (self.A, 1))   # the agent slots' parameter sets (set_params)
         h = C.c_void_p()
         check(L.f110_create(C.byref(cfg), C.byref(h)), None)
         self._h = h.value
@@ -615,6 +619,11 @@ class BatchSim(object):
     def set_params(self, params, agent_idx=-1):
         pv = _ffi.params_vector(params)
         check(_ffi.lib().f110_set_params(self._h, int(agent_idx), dptr(pv)), self._h, IndexError)
+        self._slot_rows[slice(None) if int(agent_idx) < 0 else int(agent_idx)] = pv
+
+    def agent_params_rows(self):
+        """[A][18] float64: the agent slots' parameter sets (the constructor's, then set_params'): a parameter sampler's nominal rows"""
+        return self._slot_rows.copy()
 
     def set_params_batch(self, params):
         """one vehicle parameter set per agent: a list of N dicts or an [N][18] array in PARAM_KEYS
@@ -1173,6 +1182,78 @@ class BatchSim(object):
         out = np.empty((self.N, 3))
         check(_ffi.lib().f110_reset_sampler_poses(self._h, dptr(out)), self._h)
         return out
+
+    # ------------------------------------------------------------------ randomised vehicle parameters
+    def set_param_sampler(self, sampler, env_base=0):
+        """arm the parameter sampler: every explicit sample_params and every re-seat then draws the env's rows of the per-agent
+        parameter block (f110_param_sampler_set); no draw happens here, the rows start as the per-slot sets.  sampler: a
+        ParamSampler or a dict of its settings; env e draws from PCG64(SeedSequence(seed, spawn_key=(env_base + e,))), the reset
+        sampler's rule: give the two different seeds.  Returns the ParamSampler."""
+        from .param_sampler import ParamSampler
+        ps = ParamSampler.coerce(sampler)
+        ps.validate(self._slot_rows)   # (a ValueError that names the parameter, before any ABI call)
+        if int(env_base) < 0:
+            raise ValueError("env_base must be >= 0, got %d" % int(env_base))
+        words = np.ascontiguousarray(ps.streams(self.E, int(env_base)), dtype=np.uint64)
+        entries = ps.entries()
+        check(_ffi.lib().f110_param_sampler_set(self._h, entries, words.ctypes.data_as(_ffi._u64p)), self._h)
+        self.param_sampler = ps
+        return ps
+
+    def clear_param_sampler(self):
+        check(_ffi.lib().f110_param_sampler_set(self._h, None, None), self._h)
+        self.param_sampler = None
+
+    param_sampler = None
+
+    def sample_params(self, env_mask=None):
+        """explicit draw for the envs of env_mask (None: all); nothing is reset"""
+        mptr, m = None, None
+        if env_mask is not None:
+            m = np.ascontiguousarray(env_mask, dtype=np.uint8)
+            if m.shape != (self.E,):
+                raise ValueError("env_mask must have num_envs=%d entries" % self.E)
+            mptr = m.ctypes.data_as(_ffi._u8p)
+        check(_ffi.lib().f110_param_sample(self._h, mptr), self._h)
+
+    def sample_params_device(self, d_mask=None):
+        ptr = None if d_mask is None else (d_mask.ptr if isinstance(d_mask, DeviceArray) else int(d_mask))
+        check(_ffi.lib().f110_param_sample_device(self._h, ptr), self._h)
+
+    def param_sampler_stats(self, clear=False):
+        """{'draws'}: envs drawn since the last clear"""
+        v = (C.c_uint64 * 1)()
+        check(_ffi.lib().f110_param_sampler_stats(self._h, v, 1 if clear else 0), self._h)
+        return {"draws": int(v[0])}
+
+    def get_params(self):
+        """[N][18] float64: the live per-agent rows (the parameter sampler's or set_params_batch's)"""
+        out = np.empty((self.N, _ffi.NPARAMS))
+        check(_ffi.lib().f110_params_get(self._h, dptr(out)), self._h)
+        return out
+
+    def params_view(self):
+        """the live per-agent rows [N][18] as a DeviceArray (no copy; exports through DLPack): what a policy or critic reads as
+        privileged input.  The view is the handle's memory: it ends with clear_param_sampler / close."""
+        p = C.c_void_p()
+        check(_ffi.lib().f110_params_view(self._h, C.byref(p)), self._h)
+        return DeviceArray(self, (self.N, _ffi.NPARAMS), np.float64, ptr=p.value)
+
+    def param_sample_rows(self, sampler, nominal, streams, rounds=1, num_agents=None):
+        """unit form (f110_param_sample_batch): the envs of `streams` ([m][4] words) drawn `rounds` times over the nominal rows
+        [A][18] (or one parameter dict and num_agents).  Returns (rows [rounds][m * A][18], the streams afterwards [m][4])."""
+        from .param_sampler import ParamSampler, nominal_rows
+        ps = ParamSampler.coerce(sampler)
+        nom = nominal_rows(nominal, num_agents)
+        words = np.ascontiguousarray(streams, dtype=np.uint64)
+        if words.ndim != 2 or words.shape[1] != 4:
+            raise ValueError("streams must be [m][4] uint64 words")
+        m, A, rounds = int(words.shape[0]), int(nom.shape[0]), int(rounds)
+        out = np.empty((max(rounds, 0), m * A, _ffi.NPARAMS))
+        after = np.empty_like(words)
+        check(_ffi.lib().f110_param_sample_batch(self._h, ps.entries(), dptr(nom), A, words.ctypes.data_as(_ffi._u64p), m, rounds, dptr(out),
+                                                 after.ctypes.data_as(_ffi._u64p)), self._h)
+        return out, after
 
     # ------------------------------------------------------------------ timing (bench.py)
     def timer_begin(self):

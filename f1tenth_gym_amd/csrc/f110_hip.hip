@@ -320,6 +320,14 @@ struct f110_sim {
         DevArena mem;                // job's device buffers
         SamplerJob job{};            // settings + device buffers; tracks / maps / mode are filled per launch
     } rs;
+    // randomised vehicle parameters (f110_param_sampler_*): the entries, the nominal rows, each env's stream, the counter.  The
+    // rows it draws are d_params_all, the block of f110_set_params_batch (the two refuse each other: the rows have one owner).
+    struct ParamSampler {
+        bool on = false;
+        bool owns_rows = false;      // arming allocated d_params_all: disarming frees it
+        DevArena mem;                // job's nominal, stream and counter
+        ParamJob job{};              // entries + device buffers; the mode and what it selects by are filled per launch
+    } ps;
     // timing
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool profiling = false;
@@ -443,6 +451,9 @@ static bool tiny_applies(const f110_sim *h);   // (below, with the step)
 static void noise_release(f110_sim *h);        // (below, with the noise entry points)
 static void sampler_release(f110_sim *h);      // (below, with the reset sampler)
 static int sampler_launch(f110_sim *h, hipStream_t st, int mode, int e0, int count, const uint8_t *d_mask, int ego);
+static int reseat_launch(f110_sim *h, hipStream_t st, int mode, int e0, int count, int ego);   // (below, with the parameter sampler)
+// does anything draw behind a re-seat?  (a reset sampler, a parameter sampler, or both)
+static inline bool reseat_draws(const f110_sim *h) { return h->rs.on || h->ps.on; }
 // the step behind f110_step_device, f110_step_host and f110_episode_step_* (below, with step_range); host_written: the step's
 // own kernel wrote the caller's host block (rq.fuse / rq.hb were honoured)
 static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &rq, bool &host_written);
@@ -2294,6 +2305,7 @@ int f110_set_params_batch(f110_sim *h, const double *h_params)
     if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
     ENTER(h);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    if (h->ps.on) return fail(h, F110_ERR_STATE, "a parameter sampler is armed (f110_param_sampler_set) and owns the per-agent rows; disarm it first");
     if (!h_params) {   // back to one parameter set per agent slot
         h->dev.params = h->d_params;
         h->dev.params_per_agent = 0;
@@ -2312,6 +2324,7 @@ int f110_set_params(f110_sim *h, int32_t agent_idx, const double *p)
 {
     if (!h || !p) return fail(h, F110_ERR_INVALID, "null argument");
     ENTER(h);
+    if (h->ps.on) return fail(h, F110_ERR_STATE, "a parameter sampler is armed (f110_param_sampler_set) and owns the per-agent rows; disarm it first");
     if (h->dev.params_per_agent) return fail(h, F110_ERR_STATE, "per-agent parameters are active (f110_set_params_batch); clear them first");
     const int A = h->cfg.num_agents;
     if (agent_idx >= A) return fail(h, F110_ERR_INVALID, "Index given is out of bounds for list of agents.");
@@ -2503,7 +2516,7 @@ int f110_reset_collided_device(f110_sim *h, const double *d_start_poses, int32_t
     if (h->rs.on) TRY(track_prepare(h));
     hipLaunchKernelGGL(k_reset_collided, grid1d(h->N, 256), dim3(256), 0, h->stream, h->dev, d_start_poses, ego_idx, d_count);
     HIPCHK(h, hipGetLastError());
-    if (h->rs.on) TRY(sampler_launch(h, h->stream, kSampleCollided, 0, h->cfg.num_envs, nullptr, ego_idx));
+    if (reseat_draws(h)) TRY(reseat_launch(h, h->stream, kSampleCollided, 0, h->cfg.num_envs, ego_idx));
     return F110_OK;
 }
 
@@ -2535,8 +2548,8 @@ static int sampler_launch(f110_sim *h, hipStream_t st, int mode, int e0, int cou
 // the draw behind a call that may have re-seated envs in-step, where that call's last kernel ran (the main stream, or per env block)
 static int sampler_after_step(f110_sim *h, const EnvBlocks &where)
 {
-    for (const EnvBlock &b : where) TRY(sampler_launch(h, b.stream, kSampleMarker, b.e0, b.count, nullptr, 0));
-    if (h->last_launches > 0) h->last_launches += 1;   // (the one-launch step is two launches with the draw behind it)
+    for (const EnvBlock &b : where) TRY(reseat_launch(h, b.stream, kSampleMarker, b.e0, b.count, 0));
+    if (h->last_launches > 0) h->last_launches += (h->rs.on ? 1 : 0) + (h->ps.on ? 1 : 0);   // (the one-launch step is two launches with a draw behind it)
     return F110_OK;
 }
 
@@ -2644,6 +2657,198 @@ int f110_reset_sampler_poses(f110_sim *h, double *h_poses)
     if (!h->rs.on) return fail(h, F110_ERR_STATE, "no reset sampler is armed (f110_reset_sampler_set)");
     HIPCHK(h, hipMemcpyAsync(h_poses, h->rs.job.last, sizeof(double) * 3 * h->N, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+// ---- randomised vehicle parameters (f110_param_sampler_*) ------------------------------------------------------
+static_assert(sizeof(ParamDist) == sizeof(f110_param_dist) && offsetof(ParamDist, relative) == offsetof(f110_param_dist, relative),
+              "ParamDist restates f110_param_dist");
+
+static void param_release(f110_sim *h)
+{
+    if (h->ps.on) {   // back to the per-slot sets
+        h->dev.params = h->d_params;
+        h->dev.params_per_agent = 0;
+    }
+    if (h->ps.owns_rows) h->d_params_all.reset();
+    h->ps.mem.clear();
+    h->ps.job = ParamJob{};
+    h->ps.owns_rows = false;
+    h->ps.on = false;
+}
+
+// the entries as the kernel takes them; `relative`: some drawn slot multiplies the nominal
+static void param_entries(const f110_param_dist *entries, ParamJob &j)
+{
+    j.relative = 0;
+    for (int p = 0; p < NPARAMS; ++p) {
+        const f110_param_dist &e = entries[p];
+        j.d[p] = ParamDist{e.kind, e.scope, e.a, e.b, e.lo, e.hi, e.relative ? 1 : 0, 0};
+        if (e.kind != F110_PARAM_FIXED && e.relative) j.relative = 1;
+    }
+}
+
+// one k_param_sample over envs [e0, e0 + count) on stream st
+static int param_launch(f110_sim *h, hipStream_t st, ParamJob j, int mode, int e0, int count, const uint8_t *d_mask, int ego)
+{
+    if (count <= 0) return F110_OK;
+    j.mode = mode;
+    j.mask = d_mask;
+    j.ego = ego;
+    j.zk = h->d_zig_k, j.zw = h->d_zig_w, j.zf = h->d_zig_f;
+    const size_t lds = j.relative ? sizeof(double) * NPARAMS * (size_t)j.A : 0;
+    hipLaunchKernelGGL(k_param_sample, grid1d(count, 256), dim3(256), lds, st, j, e0, count);
+    HIPCHK(h, hipGetLastError());
+    return F110_OK;
+}
+
+// what runs behind a re-seat of envs [e0, e0 + count) on stream st: the draw of every armed sampler (their streams and their
+// outputs are disjoint, so the order does not matter); the reset sampler needs track_prepare to have run
+static int reseat_launch(f110_sim *h, hipStream_t st, int mode, int e0, int count, int ego)
+{
+    if (h->rs.on) TRY(sampler_launch(h, st, mode, e0, count, nullptr, ego));
+    if (h->ps.on) {
+        ParamJob j = h->ps.job;
+        j.step_count = h->dev.step_count;
+        j.collisions = h->dev.collisions;
+        j.done = h->ep.done;
+        TRY(param_launch(h, st, j, mode, e0, count, nullptr, ego));
+    }
+    return F110_OK;
+}
+
+int f110_param_sampler_set(f110_sim *h, const f110_param_dist *entries18, const uint64_t *h_streams)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!entries18) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        param_release(h);
+        return F110_OK;
+    }
+    if (!h_streams) return fail(h, F110_ERR_INVALID, "f110_param_sampler_set: null stream words");
+    if (!h->ps.on && h->dev.params_per_agent)
+        return fail(h, F110_ERR_STATE, "per-agent parameters are active (f110_set_params_batch) and own the rows; clear them first");
+    const int A = h->cfg.num_agents;
+    if (A > kParamMaxAgents) return fail(h, F110_ERR_INVALID, "f110_param_sampler_set: at most %d agents per env, this handle has %d", kParamMaxAgents, A);
+    const size_t N = (size_t)h->N, E = (size_t)h->cfg.num_envs;
+    std::vector<double> nominal((size_t)A * NPARAMS);
+    HIPCHK(h, hipMemcpyAsync(nominal.data(), h->d_params, sizeof(double) * nominal.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ParamJob fresh{};
+    param_entries(entries18, fresh);
+    char why[256];
+    if (param_dists_check(fresh.d, nominal.data(), A, why, sizeof why)) return fail(h, F110_ERR_INVALID, "f110_param_sampler_set: %s", why);
+    param_release(h);
+    ParamJob &j = h->ps.job;
+    j = fresh;
+    if (!h->d_params_all) {
+        TRY(dmalloc(h, &h->d_params_all, N * NPARAMS));
+        h->ps.owns_rows = true;
+    }
+    TRY(dmalloc(h, h->ps.mem, &j.stream, 2 * E));
+    TRY(dmalloc(h, h->ps.mem, &j.counter, 1));
+    double *d_nominal = nullptr;
+    TRY(dmalloc(h, h->ps.mem, &d_nominal, nominal.size()));
+    std::vector<double> rows(N * NPARAMS);
+    for (size_t i = 0; i < N; ++i) std::memcpy(&rows[i * NPARAMS], &nominal[(i % A) * NPARAMS], sizeof(double) * NPARAMS);
+    HIPCHK(h, hipMemcpy(h->d_params_all, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_nominal, nominal.data(), sizeof(double) * nominal.size(), hipMemcpyHostToDevice));
+    // {state.hi, state.lo, inc.hi, inc.lo} per env is the layout of two U128 {hi, lo}
+    HIPCHK(h, hipMemcpy(j.stream, h_streams, sizeof(U128) * 2 * E, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemset(j.counter, 0, sizeof(unsigned long long)));
+    j.nominal = d_nominal;
+    j.rows = h->d_params_all;
+    j.A = A;
+    h->dev.params = h->d_params_all;
+    h->dev.params_per_agent = 1;
+    h->ps.on = true;
+    return F110_OK;
+}
+
+int f110_param_sample_device(f110_sim *h, const uint8_t *d_env_mask)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!h->ps.on) return fail(h, F110_ERR_STATE, "f110_param_sample: no parameter sampler is armed (f110_param_sampler_set)");
+    return param_launch(h, h->stream, h->ps.job, kSampleExplicit, 0, h->cfg.num_envs, d_env_mask, 0);
+}
+
+int f110_param_sample(f110_sim *h, const uint8_t *h_env_mask)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!h->ps.on) return fail(h, F110_ERR_STATE, "f110_param_sample: no parameter sampler is armed (f110_param_sampler_set)");
+    if (h_env_mask) HIPCHK(h, hipMemcpyAsync(h->d_mask, h_env_mask, (size_t)h->cfg.num_envs, hipMemcpyHostToDevice, h->stream));
+    TRY(f110_param_sample_device(h, h_env_mask ? h->d_mask : nullptr));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // the host mask is consumed on return
+    return F110_OK;
+}
+
+int f110_param_sampler_stats(f110_sim *h, uint64_t *draws, int32_t clear)
+{
+    if (!h) return fail(nullptr, F110_ERR_INVALID, "null handle");
+    ENTER(h);
+    if (!h->ps.on) return fail(h, F110_ERR_STATE, "no parameter sampler is armed (f110_param_sampler_set)");
+    unsigned long long v = 0;
+    HIPCHK(h, hipMemcpyAsync(&v, h->ps.job.counter, sizeof v, hipMemcpyDeviceToHost, h->stream));
+    if (clear) HIPCHK(h, hipMemsetAsync(h->ps.job.counter, 0, sizeof v, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (draws) *draws = v;
+    return F110_OK;
+}
+
+int f110_params_get(f110_sim *h, double *h_out)
+{
+    if (!h || !h_out) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    if (!h->dev.params_per_agent) return fail(h, F110_ERR_STATE, "no per-agent parameter rows are active (f110_param_sampler_set, f110_set_params_batch)");
+    HIPCHK(h, hipMemcpyAsync(h_out, h->d_params_all, sizeof(double) * NPARAMS * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return F110_OK;
+}
+
+int f110_params_view(f110_sim *h, const double **d_rows)
+{
+    if (!h || !d_rows) return fail(h, F110_ERR_INVALID, "null argument");
+    ENTER(h);
+    *d_rows = nullptr;
+    if (!h->dev.params_per_agent) return fail(h, F110_ERR_STATE, "no per-agent parameter rows are active (f110_param_sampler_set, f110_set_params_batch)");
+    *d_rows = h->d_params_all;
+    return F110_OK;
+}
+
+int f110_param_sample_batch(f110_sim *h, const f110_param_dist *entries18, const double *h_nominal, int32_t A, const uint64_t *h_streams,
+                            int32_t m, int32_t rounds, double *h_out, uint64_t *h_streams_out)
+{
+    if (!h || !entries18 || !h_nominal || !h_streams || !h_out) return fail(h, F110_ERR_INVALID, "f110_param_sample_batch: null argument");
+    ENTER(h);
+    if (A < 1 || A > kParamMaxAgents || m < 1 || rounds < 1 || (size_t)m * A * rounds > ((size_t)1 << 28))
+        return fail(h, F110_ERR_INVALID, "f110_param_sample_batch: A = %d (1 .. %d), m = %d, rounds = %d", A, kParamMaxAgents, m, rounds);
+    ParamJob j{};
+    param_entries(entries18, j);
+    char why[256];
+    if (param_dists_check(j.d, h_nominal, A, why, sizeof why)) return fail(h, F110_ERR_INVALID, "f110_param_sample_batch: %s", why);
+    const size_t per_round = (size_t)m * A * NPARAMS;
+    std::vector<double> rows0(per_round);   // every round starts from the rows before it: round 0 from the nominal ones
+    for (size_t i = 0; i < (size_t)m * A; ++i) std::memcpy(&rows0[i * NPARAMS], h_nominal + (i % A) * NPARAMS, sizeof(double) * NPARAMS);
+    Scratch s(h);
+    j.nominal = s.in(h_nominal, (size_t)A * NPARAMS);
+    uint64_t *d_streams = s.in(h_streams, 4 * (size_t)m);   // {state.hi, state.lo, inc.hi, inc.lo} per env: two U128 {hi, lo}
+    s.later(h_streams_out, static_cast<const uint64_t *>(d_streams), 4 * (size_t)m);
+    j.stream = reinterpret_cast<U128 *>(d_streams);
+    double *d_out = s.out(h_out, per_round * rounds);
+    j.counter = s.tmp<unsigned long long>(1);
+    TRY(s.ready());
+    HIPCHK(h, hipMemsetAsync(j.counter, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_out, rows0.data(), sizeof(double) * per_round, hipMemcpyHostToDevice, h->stream));
+    j.A = A;
+    for (int r = 0; r < rounds; ++r) {
+        j.rows = d_out + per_round * r;
+        if (r > 0) HIPCHK(h, hipMemcpyAsync(j.rows, j.rows - per_round, sizeof(double) * per_round, hipMemcpyDeviceToDevice, h->stream));
+        TRY(param_launch(h, h->stream, j, kSampleExplicit, 0, m, nullptr, 0));
+    }
+    TRY(s.finish());   // (rows0 lives until here)
     return F110_OK;
 }
 
@@ -2971,7 +3176,7 @@ int f110_episode_step_device(f110_sim *h, const double *d_actions)
     TRY(env_blocks_follow(h, w));
     for (const EnvBlock &b : w) hipLaunchKernelGGL(k_episode, grid1d(b.count, 256), dim3(256), 0, b.stream, h->dev, h->ep, b.count, b.e0);
     HIPCHK(h, hipGetLastError());
-    if (h->rs.on && h->dev.reseat_poses) TRY(sampler_after_step(h, w));
+    if (reseat_draws(h) && h->dev.reseat_poses) TRY(sampler_after_step(h, w));
     h->touched = false;
     return F110_OK;
 }
@@ -2989,7 +3194,7 @@ int f110_episode_reset_done_device(f110_sim *h, int32_t *d_count)
     const int A = h->cfg.num_agents;
     for (const EnvBlock &b : w) {
         hipLaunchKernelGGL(k_episode_reset_done, grid1d(b.count * A, 256), dim3(256), 0, b.stream, h->dev, h->ep, d_count, b.e0 * A, b.count * A);
-        if (h->rs.on) TRY(sampler_launch(h, b.stream, kSampleDone, b.e0, b.count, nullptr, 0));   // (done[] is still set)
+        if (reseat_draws(h)) TRY(reseat_launch(h, b.stream, kSampleDone, b.e0, b.count, 0));   // (done[] is still set)
         hipLaunchKernelGGL(k_episode_clear_done, grid1d(b.count, 256), dim3(256), 0, b.stream, h->ep, b.count, b.e0);
     }
     HIPCHK(h, hipGetLastError());
@@ -3099,7 +3304,7 @@ int f110_episode_step_host(f110_sim *h, const double *h_actions, int32_t auto_re
         hipLaunchKernelGGL(k_episode_clear_done, grid1d(E, 256), dim3(256), 0, h->stream, h->ep, (int)E);
     }
     HIPCHK(h, hipGetLastError());
-    if (h->rs.on && (auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, env_blocks_main(h)));
+    if (reseat_draws(h) && (auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, env_blocks_main(h)));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return F110_OK;
 }
@@ -3325,7 +3530,7 @@ int f110_step_host(f110_sim *h, const double *h_actions, const f110_host_block *
     HIPCHK(h, hipGetLastError());
     // a re-seat inside this call (auto reset, or an armed f110_set_auto_reseat): the draw, behind the block (which keeps the
     // terminal observation), stream-ordered in front of the next step
-    if (h->rs.on && (rq.auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, env_blocks_main(h)));
+    if (reseat_draws(h) && (rq.auto_reset || h->dev.reseat_poses)) TRY(sampler_after_step(h, env_blocks_main(h)));
     const auto t_enq = std::chrono::steady_clock::now();
     TRY(host_step_wait(h, flags, spin, tiny, t_in, t_enq));
     const auto t_out = std::chrono::steady_clock::now();
@@ -4086,7 +4291,7 @@ static int step_submit(f110_sim *h, const double *d_actions, const StepRequest &
     }
     // an in-step re-seat armed (f110_set_auto_reseat): the draw for the envs it re-seated, behind the step (per env block);
     // f110_step_host / f110_episode_step* launch it after their own last kernel instead (rq.defer_draw)
-    if (h->rs.on && h->dev.reseat_poses && !rq.defer_draw) TRY(sampler_after_step(h, w));
+    if (reseat_draws(h) && h->dev.reseat_poses && !rq.defer_draw) TRY(sampler_after_step(h, w));
     h->touched = false;
     h->last_blocks = grouped ? h->groups : 1;
     h->noise_ub += 1;
@@ -4197,13 +4402,14 @@ static uint32_t state_col_set(const f110_sim *h)
     if (h->dev.params_per_agent) c |= F110_STATE_COL_PARAMS;
     if (h->multi_map) c |= F110_STATE_COL_ENV_MAP;
     if (h->rs.on) c |= F110_STATE_COL_RESET_RNG;
+    if (h->ps.on) c |= F110_STATE_COL_PARAM_RNG;
     return c;
 }
 
 // the column table of a blob of k envs with column set `cols` (fixed order: the layout depends on cols, k, A and B only);
 // returns the blob's total bytes
-// the most columns state_columns adds: the agent core 17, noise 2, episode 9, params 1, env map 1, reset sampler 2, scans 1
-constexpr int kStateColsUsed = 17 + 2 + 9 + 1 + 1 + 2 + 1;
+// the most columns state_columns adds: the agent core 17, noise 2, episode 9, params 1, env map 1, reset sampler 2, parameter sampler 1, scans 1
+constexpr int kStateColsUsed = 17 + 2 + 9 + 1 + 1 + 2 + 1 + 1;
 static_assert(kStateColsUsed <= kStateMaxCols, "StateCols::c cannot hold every column state_columns may add");
 
 static size_t state_columns(const f110_sim *h, uint32_t cols, int k, StateCols *out)
@@ -4254,6 +4460,7 @@ static size_t state_columns(const f110_sim *h, uint32_t cols, int k, StateCols *
         add(h->rs.job.stream, 2 * sizeof(U128), 1);   // the env's sampler stream {state, inc}
         add(h->rs.job.last, 24, A);                   // ... and its explicit-draw fallback poses
     }
+    if (cols & F110_STATE_COL_PARAM_RNG) add(h->ps.job.stream, 2 * sizeof(U128), 1);   // the env's parameter stream {state, inc}
     if (cols & F110_STATE_COL_SCANS) add(h->dev.scans, B * 8, A);   // last: launched on its own (state_launch)
     t.num_envs = h->cfg.num_envs;
     t.step_count = h->dev.step_count;
@@ -4338,6 +4545,7 @@ static const char *state_col_name(uint32_t bit)
     case F110_STATE_COL_PARAMS: return "per-agent params (f110_set_params_batch)";
     case F110_STATE_COL_ENV_MAP: return "env map slots (f110_set_env_maps)";
     case F110_STATE_COL_RESET_RNG: return "reset sampler (f110_reset_sampler_set)";
+    case F110_STATE_COL_PARAM_RNG: return "parameter sampler (f110_param_sampler_set)";
     default: return "agent";
     }
 }
@@ -4362,13 +4570,13 @@ static int state_check(f110_sim *h, const StateHeader &hd)
     if (mb >= 2 && hd.std_dev != h->noise_gen.scale)
         return fail(h, F110_ERR_STATE, "state blob saved with noise std_dev %g, this handle has %g", hd.std_dev, h->noise_gen.scale);
     const uint32_t want = state_col_set(h), have = hd.cols & ~(uint32_t)F110_STATE_COL_SCANS;
-    for (uint32_t bit = F110_STATE_COL_RNG; bit <= F110_STATE_COL_RESET_RNG; bit <<= 1) {
+    for (uint32_t bit = F110_STATE_COL_RNG; bit <= F110_STATE_COL_PARAM_RNG; bit <<= 1) {
         if ((have & bit) && !(want & bit))
             return fail(h, F110_ERR_STATE, "state blob holds %s columns, which are not active on this handle", state_col_name(bit));
         if (!(have & bit) && (want & bit))
             return fail(h, F110_ERR_STATE, "state blob has no %s columns, which are active on this handle", state_col_name(bit));
     }
-    if (!(have & F110_STATE_COL_AGENT) || (hd.cols & ~0xffu)) return fail(h, F110_ERR_STATE, "state blob with an unknown column set 0x%x", hd.cols);
+    if (!(have & F110_STATE_COL_AGENT) || (hd.cols & ~0x1ffu)) return fail(h, F110_ERR_STATE, "state blob with an unknown column set 0x%x", hd.cols);
     if ((hd.cols & F110_STATE_COL_SCANS) != ((hd.flags & F110_STATE_SCANS) ? (uint32_t)F110_STATE_COL_SCANS : 0u))
         return fail(h, F110_ERR_STATE, "state blob header is inconsistent (flags / columns)");
     if ((have & F110_STATE_COL_ENV_MAP) && hd.n_maps > 1 + (int)h->extra_maps.size())

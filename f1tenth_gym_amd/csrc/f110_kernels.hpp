@@ -4652,6 +4652,55 @@ __global__ void k_sampler_keep(double *__restrict__ last, const double *__restri
     for (int c = 0; c < 3; ++c) last[3 * (size_t)i + c] = poses[3 * (size_t)i + c];
 }
 
+// ---- randomised vehicle parameters (f110_param_sampler_*; include/f110.h states the draw, f110_rng.hpp param_draw_env is it) ----
+// One lane per env, k_reset_sample's pattern and its SampleMode selection.  Env e owns the PCG64 stream {state, inc} = stream[2e],
+// stream[2e + 1] and the rows [e A, (e + 1) A) of the per-agent block; only drawn slots are written.  The 18 entries travel in the
+// arguments; the nominal rows [A][18] (needed by relative slots only) are staged in LDS once per workgroup.
+constexpr int kParamMaxAgents = 256;   // the nominal rows of an env fit LDS (36 KB)
+struct ParamJob {
+    ParamDist d[NPARAMS];
+    const double *nominal;          // [A][18] the agent slots' sets as of arming
+    double *rows;                   // [.][18] the per-agent block
+    U128 *stream;                   // [E][2] {state, inc}
+    unsigned long long *counter;    // envs drawn
+    const uint8_t *mask;            // kSampleExplicit: [E] or nullptr
+    const int32_t *step_count;      // kSampleMarker
+    const double *collisions;       // kSampleCollided
+    const uint8_t *done;            // kSampleDone
+    const uint64_t *zk;             // the ziggurat tables
+    const double *zw, *zf;
+    int32_t A, ego, mode, relative;   // relative: some drawn slot multiplies the nominal
+};
+
+// envs [e0, e0 + count)
+__global__ void __launch_bounds__(256) k_param_sample(ParamJob j, int e0, int count)
+{
+    extern __shared__ double param_nominal[];   // [A][18] when j.relative
+    const int A = j.A;
+    if (j.relative) {
+        for (int q = (int)threadIdx.x; q < A * NPARAMS; q += (int)blockDim.x) param_nominal[q] = j.nominal[q];
+        __syncthreads();
+    }
+    const int e = e0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    bool drew = false;
+    if (e < e0 + count) {
+        const size_t i0 = (size_t)e * A;
+        if (j.mode == kSampleExplicit) drew = !j.mask || j.mask[e];
+        else if (j.mode == kSampleMarker) drew = j.step_count[i0] == 0;
+        else if (j.mode == kSampleCollided) drew = j.collisions[i0 + j.ego] != 0.0;
+        else drew = j.done[e] != 0;
+    }
+    if (drew) {
+        const ZigTables zt = {j.zk, j.zw, j.zf};
+        U128 st = j.stream[2 * (size_t)e];
+        const U128 inc = j.stream[2 * (size_t)e + 1];
+        param_draw_env(j.d, param_nominal, A, st, inc, zt, j.rows + (size_t)e * A * NPARAMS);
+        j.stream[2 * (size_t)e] = st;
+    }
+    const unsigned long long bd = __ballot(drew);
+    if ((threadIdx.x & 63u) == 0u && bd) atomicAdd(j.counter, (unsigned long long)__popcll(bd));
+}
+
 // ---- compact observations (f110_obs_encode_*; include/f110.h states the rule, f110_math.hpp obs_* is the per-row arithmetic) ----
 // One wave per agent, k_scan_policy's pattern: the W beams of the row go through LDS with 64-lane coalesced loads (walking the
 // sectors straight from HBM touches 64 lines per instruction), then lane l takes elements l, l + 64, ... of the new frame (K above

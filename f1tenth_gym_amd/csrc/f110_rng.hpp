@@ -25,6 +25,8 @@
 // wedge test in 10^15) — accepted like the other measure-zero deviations listed in DESIGN.md.
 #pragma once
 
+#include <stdio.h>
+
 #include "f110_math.hpp"
 #include "f110_ziggurat_tables.hpp"
 
@@ -485,6 +487,98 @@ F110_HD void pf_stream_advance(uint64_t *stream, U128 ja, U128 jg)
     for (int q = 0; q < 4; ++q) st = pcg_jump(st, inc, ja, jg);
     stream[0] = st.hi;
     stream[1] = st.lo;
+}
+
+// ---- the parameter sampler's draws (include/f110.h, f110_param_dist) -----------------------------------------------------------
+// the layout of f110_param_dist
+struct ParamDist {
+    int32_t kind, scope;
+    double a, b, lo, hi;
+    int32_t relative, pad;
+};
+enum { kParamFixed = 0, kParamUniform = 1, kParamNormal = 2 };
+enum { kParamScopeAgent = 0, kParamScopeEnv = 1 };
+
+// one value of a drawn slot: Generator.uniform(a, b), or np.clip(Generator.normal(a, b), lo, hi)
+F110_HD double param_draw_value(const ParamDist &d, U128 &st, U128 inc, const ZigTables &t)
+{
+    if (d.kind == kParamUniform) {
+        st = pcg_step(st, inc);
+        return d.a + pcg_to_double(pcg_output(st)) * (d.b - d.a);
+    }
+    const double v = d.a + d.b * mppi_normal(st, inc, t);
+    return v < d.lo ? d.lo : (v > d.hi ? d.hi : v);
+}
+
+// one env's draw: slots in index order, within a slot the env's single value or agents 0 .. A - 1; only drawn slots of the env's
+// rows [A][18] are written.  nominal [A][18] is read for relative slots only.
+F110_HD void param_draw_env(const ParamDist *d, const double *nominal, int A, U128 &st, U128 inc, const ZigTables &t, double *rows)
+{
+    for (int p = 0; p < NPARAMS; ++p) {
+        const ParamDist dp = d[p];
+        if (dp.kind == kParamFixed) continue;
+        double v = 0.0;
+        if (dp.scope == kParamScopeEnv) v = param_draw_value(dp, st, inc, t);
+        for (int s = 0; s < A; ++s) {
+            if (dp.scope != kParamScopeEnv) v = param_draw_value(dp, st, inc, t);
+            rows[(size_t)s * NPARAMS + p] = dp.relative ? nominal[(size_t)s * NPARAMS + p] * v : v;
+        }
+    }
+}
+
+// May these 18 entries be armed over the nominal rows [A][18]?  nullptr when they may, else the reason (in `msg`), which names the
+// parameter.  Host only: validity is settled here, by intervals, so the draw has no rejection loop.
+inline const char *param_dists_check(const ParamDist *d, const double *nominal, int A, char *msg, size_t cap)
+{
+    static const char *const name[NPARAMS] = {"mu", "C_Sf", "C_Sr", "lf", "lr", "h", "m", "I", "s_min", "s_max", "sv_min", "sv_max",
+                                              "v_switch", "a_max", "v_min", "v_max", "width", "length"};
+    auto fin = [](double v) { return v == v && v - v == 0.0; };
+    double lo[NPARAMS], hi[NPARAMS];   // the interval v is drawn from (FIXED: unused)
+    for (int p = 0; p < NPARAMS; ++p) {
+        const ParamDist &e = d[p];
+        if (e.kind < kParamFixed || e.kind > kParamNormal) return snprintf(msg, cap, "parameter %s: unknown kind %d", name[p], e.kind), msg;
+        if (e.scope != kParamScopeAgent && e.scope != kParamScopeEnv) return snprintf(msg, cap, "parameter %s: unknown scope %d", name[p], e.scope), msg;
+        if (e.kind == kParamFixed) continue;
+        if (p == P_WIDTH || p == P_LENGTH)
+            return snprintf(msg, cap, "parameter %s cannot be drawn: the collision boxes and the iTTC side tables are the constructor's", name[p]), msg;
+        if (!fin(e.a) || !fin(e.b)) return snprintf(msg, cap, "parameter %s: a = %g, b = %g must be finite", name[p], e.a, e.b), msg;
+        if (e.kind == kParamUniform) {
+            if (e.a > e.b) return snprintf(msg, cap, "parameter %s: uniform needs a <= b, got %g, %g", name[p], e.a, e.b), msg;
+            lo[p] = e.a;
+            hi[p] = e.b;
+        } else {
+            if (e.b < 0.0) return snprintf(msg, cap, "parameter %s: normal needs scale >= 0, got %g", name[p], e.b), msg;
+            if (!fin(e.lo) || !fin(e.hi)) return snprintf(msg, cap, "parameter %s: normal needs finite clip bounds, got %g, %g", name[p], e.lo, e.hi), msg;
+            if (e.lo > e.hi) return snprintf(msg, cap, "parameter %s: normal needs lo <= hi, got %g, %g", name[p], e.lo, e.hi), msg;
+            lo[p] = e.lo;
+            hi[p] = e.hi;
+        }
+    }
+    static const int positive[] = {P_MU, P_CSF, P_CSR, P_LF, P_LR, P_H, P_M, P_I, P_VSWITCH, P_AMAX};
+    static const int below[][2] = {{P_SMIN, P_SMAX}, {P_SVMIN, P_SVMAX}, {P_VMIN, P_VMAX}};
+    for (int s = 0; s < A; ++s) {
+        const double *nom = nominal + (size_t)s * NPARAMS;
+        double rl[NPARAMS], rh[NPARAMS];   // what the row of agent slot s can hold
+        for (int p = 0; p < NPARAMS; ++p) {
+            if (d[p].kind == kParamFixed) {
+                rl[p] = rh[p] = nom[p];
+                continue;
+            }
+            const double x = d[p].relative ? nom[p] * lo[p] : lo[p], y = d[p].relative ? nom[p] * hi[p] : hi[p];
+            rl[p] = x < y ? x : y;
+            rh[p] = x < y ? y : x;
+            if (!fin(x) || !fin(y))
+                return snprintf(msg, cap, "parameter %s: its interval times the nominal value of agent slot %d is not finite", name[p], s), msg;
+        }
+        for (int p : positive)
+            if (d[p].kind != kParamFixed && !(rl[p] > 0.0))
+                return snprintf(msg, cap, "parameter %s must stay above 0, its draws reach %g (agent slot %d)", name[p], rl[p], s), msg;
+        for (const int(&q)[2] : below)
+            if ((d[q[0]].kind != kParamFixed || d[q[1]].kind != kParamFixed) && !(rh[q[0]] < rl[q[1]]))
+                return snprintf(msg, cap, "parameter %s must stay below %s, its draws reach %g against %g (agent slot %d)", name[q[0]], name[q[1]],
+                                rh[q[0]], rl[q[1]], s), msg;
+    }
+    return nullptr;
 }
 
 }  // namespace f110

@@ -23,6 +23,7 @@ from .opponents import split_mppi_opponents
 from .particle_filter import split_filter
 from .obs_encoder import ObsEncoder
 from .reset_sampler import ResetSampler
+from .param_sampler import ParamSampler
 from .sim import Integrator, Simulator
 from .track_preview import TrackPreview
 from .neighbors import Neighbors
@@ -281,6 +282,9 @@ class F110Env(_EnvBase):
         self.random_start = None
         if kwargs.get('random_start') is not None:
             self.random_start = self.sim.batch.set_reset_sampler(ResetSampler.coerce(kwargs['random_start']))
+        # randomised vehicle parameters: random_params= (a ParamSampler or a dict of its settings) makes every reset()
+        # draw the cars' parameter rows on the device, in front of the reset
+        self.random_params = _arm_random_params(self.sim.batch, kwargs.get('random_params'), 0)
         self.render_obs = None
         self.current_obs = None
         self._render_view = dict(RENDER_DEFAULTS)
@@ -333,6 +337,8 @@ class F110Env(_EnvBase):
     def reset(self, poses=None):
         """poses None (random_start only): the start poses are drawn on the track"""
         self.collisions = np.zeros((self.num_agents,))
+        if self.random_params is not None:
+            self.sim.batch.sample_params()
         if poses is None:
             if self.random_start is None:
                 raise ValueError("reset() without poses needs random_start=")
@@ -360,7 +366,16 @@ class F110Env(_EnvBase):
             self.sim.batch.set_obstacles(self.obstacle_slot, obstacles)
 
     def update_params(self, params, index=-1):
+        _params_owner_check(self)
         self.sim.update_params(params, agent_idx=index)
+
+    def get_params(self):
+        """[A][18] float64: the cars' live parameter rows (random_params, or a per-agent set)"""
+        return self.sim.batch.get_params()
+
+    def params_view(self):
+        """the live rows as a DeviceArray (BatchSim.params_view)"""
+        return self.sim.batch.params_view()
 
     def add_render_callback(self, callback_func):
         F110Env.render_callbacks.append(callback_func)
@@ -376,6 +391,18 @@ class F110Env(_EnvBase):
         if mode != 'rgb_array':
             raise NotImplementedError("the pyglet window is outside this build's scope; use render('rgb_array') for frames")
         return _render_call(self.sim, [int(self.ego_idx)], self._render_view, True, False)[1][0]
+
+
+def _arm_random_params(batch, spec, env_base):
+    """random_params= of the env classes: None, or the ParamSampler armed on `batch` """
+    if spec is None:
+        return None
+    return batch.set_param_sampler(ParamSampler.coerce(spec), env_base=env_base)
+
+
+def _params_owner_check(env):
+    if env.random_params is not None:
+        raise RuntimeError("random_params= is armed and owns the parameter rows: update_params / update_params_batch are refused")
 
 
 class F110VecEnv(object):
@@ -637,6 +664,9 @@ class F110VecEnv(object):
         if kwargs.get('random_start') is not None:
             self.random_start = self.sim.batch.set_reset_sampler(ResetSampler.coerce(kwargs['random_start']),
                                                                  env_base=int(kwargs.get('env_base', 0)))
+        # randomised vehicle parameters: reset() draws the masked envs' rows in front of the reset, every auto
+        # re-seat draws in the step; the same env_base rule
+        self.random_params = _arm_random_params(self.sim.batch, kwargs.get('random_params'), int(kwargs.get('env_base', 0)))
         self._start_poses = None
         self._d_actions = None
         self.copy_obs = bool(copy_obs)
@@ -739,7 +769,20 @@ class F110VecEnv(object):
     def update_params_batch(self, params):
         """a vehicle parameter set per agent of every env ([E*A] dicts or [E*A][18] array; None: back
         to the per-slot sets of update_params)"""
+        _params_owner_check(self)
         self.sim.batch.set_params_batch(params)
+
+    def update_params(self, params, index=-1):
+        _params_owner_check(self)
+        self.sim.update_params(params, agent_idx=index)
+
+    def get_params(self):
+        """[E * A][18] float64: the live per-agent parameter rows (random_params, or update_params_batch)"""
+        return self.sim.batch.get_params()
+
+    def params_view(self):
+        """the live rows as a DeviceArray (BatchSim.params_view): privileged input for a policy or critic, no copy"""
+        return self.sim.batch.params_view()
 
     def _extract_centerlines(self, tracks):
         """replace the 'centerline' and 'raceline' entries of `tracks` whose slot is registered by the slot's extracted centreline or by
@@ -807,6 +850,8 @@ class F110VecEnv(object):
         masked envs draw their start poses on the device."""
         partial = env_mask is not None and (bool(reseat_only) or not np.all(env_mask))
         steps = self.sim._steps_since_full_reset
+        if self.random_params is not None:
+            self.sim.batch.sample_params(env_mask)
         if poses is None:
             if self.random_start is None:
                 raise ValueError("reset() without poses needs random_start=")
@@ -933,6 +978,8 @@ class F110VecEnv(object):
         info = {'checkpoint_done': toggles, 'toggle_list': self._lap.toggle_list.copy(),
                 'near_starts': self._lap.near_starts.copy()}
         if self.auto_reset and done.any():
+            if self.random_params is not None:
+                self.sim.batch.sample_params(done)
             if self.random_start is not None:   # the draw on the device, the drawn poses back for the host lap logic
                 self.sim.batch.sample_reset(done)
                 if np.all(done):

@@ -91,6 +91,10 @@ class ShardedVecEnv(object):
         if kwargs.get('random_start') is not None:   # one sampler for every shard (seed=None: its entropy drawn once), env_base per shard
             from .reset_sampler import ResetSampler
             kwargs['random_start'] = ResetSampler.coerce(kwargs['random_start'])
+        self.random_params = None
+        if kwargs.get('random_params') is not None:   # one sampler for every shard, env_base per shard: K shards draw what one handle draws
+            from .param_sampler import ParamSampler
+            self.random_params = kwargs['random_params'] = ParamSampler.coerce(kwargs['random_params'])
         if kwargs.get('obs_encoder') is not None:    # one encoder for every shard; obs['encoded'] is concatenated along the env axis
             from .obs_encoder import ObsEncoder
             kwargs['obs_encoder'] = ObsEncoder.coerce(kwargs['obs_encoder'])
@@ -249,11 +253,23 @@ class ShardedVecEnv(object):
         """per shard: the page-locked [E_k][A][2] buffer its kernels read in place (fill them and call step(None))"""
         return [s.action_buffer for s in self.shards]
 
+    def get_params(self):
+        """[E * A][18] float64: the live per-agent parameter rows of every shard, global agent order"""
+        return np.concatenate(self._each(lambda k, s: s.get_params()), axis=0)
+
+    def params_view(self):
+        """per shard: the live rows as a DeviceArray on that shard's device (F110VecEnv.params_view)"""
+        return self._each(lambda k, s: s.params_view())
+
     def update_params(self, params, index=-1):
+        if self.random_params is not None:
+            raise RuntimeError("random_params= is armed and owns the parameter rows: update_params / update_params_batch are refused")
         self._each(lambda k, s: s.sim.update_params(params, agent_idx=index))
 
     def update_params_batch(self, params):
         """[E*A] dicts or [E*A][18] array, global agent order; None: back to the per-slot sets"""
+        if self.random_params is not None:
+            raise RuntimeError("random_params= is armed and owns the parameter rows: update_params / update_params_batch are refused")
         if params is None:
             self._each(lambda k, s: s.update_params_batch(None))
             return

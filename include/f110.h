@@ -549,7 +549,8 @@ enum {
     F110_STATE_COL_EPISODE = 16,
     F110_STATE_COL_PARAMS = 32,       /* f110_set_params_batch rows */
     F110_STATE_COL_ENV_MAP = 64,      /* f110_set_env_maps slot */
-    F110_STATE_COL_RESET_RNG = 128    /* f110_reset_sampler_set: per env its stream {state, inc}, per agent its fallback pose */
+    F110_STATE_COL_RESET_RNG = 128,   /* f110_reset_sampler_set: per env its stream {state, inc}, per agent its fallback pose */
+    F110_STATE_COL_PARAM_RNG = 256    /* f110_param_sampler_set: per env its stream {state, inc} (the rows travel as F110_STATE_COL_PARAMS) */
 };
 #define F110_STATE_HEADER_BYTES 256
 /* bytes of a blob of n_envs envs (the handle's current column set) */
@@ -848,6 +849,60 @@ int f110_reset_sampler_stats(f110_sim *h, uint64_t *out2, int32_t *h_attempt, in
 int f110_reset_sampler_poses(f110_sim *h, double *h_poses);
 /* device pointers of the episode logic's start poses [N][3] and start_rot [num_envs][4] (f110_episode_init) */
 int f110_episode_start_views(f110_sim *h, double **d_start_poses, double **d_start_rot);
+
+/* ---- randomised vehicle parameters (no reference counterpart: the reference's update_params is a host call between episodes).
+ * A parameter sampler draws an env's rows of the per-agent parameter block [N][18] on the device, wherever a reset sampler
+ * would draw its start poses.  Each of the 18 slots (f110_config.params order: mu, C_Sf, C_Sr, lf, lr, h, m, I, s_min, s_max,
+ * sv_min, sv_max, v_switch, a_max, v_min, v_max, width, length) has one f110_param_dist:
+ *   kind   FIXED   the slot is not drawn: it consumes nothing and holds the nominal value
+ *          UNIFORM v = a + u * (b - a), u the stream's next Generator.random(): bitwise Generator.uniform(a, b)
+ *          NORMAL  v = a + b * z, z the stream's next Generator.standard_normal() (NumPy's ziggurat), then v < lo ? lo :
+ *                  (v > hi ? hi : v): bitwise np.clip(Generator.normal(a, b), lo, hi)
+ *   scope  AGENT   every agent of the env gets its own draw, in agent order
+ *          ENV     one draw, shared by every agent of the env (surface friction belongs to the track, not to the car)
+ *   relative != 0  the row gets nominal * v (one float64 multiply), nominal = that slot's value in the agent slot's parameter
+ *                  set (f110_set_params) at arming; else v itself.
+ * Order within an env: slots in index order; within a slot the env's single draw, or agents 0 .. A - 1.  float64 without
+ * contraction.  Env e owns np.random.PCG64(np.random.SeedSequence(seed, spawn_key=(e,))) with e the GLOBAL env index
+ * (f110_pcg64_seed_spawn): the reset sampler's rule, so whoever arms both gives them different seeds.
+ * Refused at arming (F110_ERR_INVALID; nothing written or allocated, a sampler already armed stays as it is): an unknown kind or
+ * scope; a kind other than FIXED on width or length (the collision boxes and the iTTC side tables are the constructor's);
+ * UNIFORM with a > b or a non-finite a or b; NORMAL with a non-finite a or b, b < 0, non-finite lo or hi, or lo > hi; an entry
+ * whose reachable interval ([a, b] UNIFORM, [lo, hi] NORMAL, times the nominal of every agent slot when relative) leaves the
+ * model's domain: mu, C_Sf, C_Sr, lf, lr, h, m, I, a_max, v_switch > 0; s_min < s_max, sv_min < sv_max, v_min < v_max over the
+ * whole intervals (a slot that is not drawn counts with its nominal values).  So validity is settled once, on the host, by
+ * intervals, and the draw has no rejection loop.
+ * Refused for state (F110_ERR_STATE): arming while f110_set_params_batch rows are active, f110_set_params_batch and
+ * f110_set_params while a sampler is armed: the rows have one owner.
+ * Arming fills the block with the nominal rows and switches every consumer to it; no draw happens at arming.  In-step draws:
+ * behind every call that re-seats envs, as for the reset sampler (per env block, +1 launch); either sampler may be armed without
+ * the other, and with both the results do not depend on their order.  Disarming waits for the stream, returns to the per-slot
+ * sets and frees what arming allocated.  The stream position is state (F110_STATE_COL_PARAM_RNG), the rows travel as
+ * F110_STATE_COL_PARAMS; the entries are configuration. */
+enum { F110_PARAM_FIXED = 0, F110_PARAM_UNIFORM = 1, F110_PARAM_NORMAL = 2 };
+enum { F110_PARAM_SCOPE_AGENT = 0, F110_PARAM_SCOPE_ENV = 1 };
+typedef struct f110_param_dist {
+    int32_t kind, scope;
+    double a, b;           /* UNIFORM: the interval; NORMAL: loc, scale */
+    double lo, hi;         /* NORMAL: the clip */
+    int32_t relative, pad;
+} f110_param_dist;
+/* arm (entries18 != NULL; h_streams [num_envs][4] from f110_pcg64_seed_spawn) or disarm (entries18 = NULL).  Arming clears the counter. */
+int f110_param_sampler_set(f110_sim *h, const f110_param_dist *entries18, const uint64_t *h_streams);
+/* explicit draws for the envs of the mask ([num_envs], NULL = all), with no reset; _device is asynchronous on the handle's stream */
+int f110_param_sample(f110_sim *h, const uint8_t *h_env_mask);
+int f110_param_sample_device(f110_sim *h, const uint8_t *d_env_mask);
+/* *draws (or NULL) = envs drawn since the last clear; clear != 0 zeroes the counter */
+int f110_param_sampler_stats(f110_sim *h, uint64_t *draws, int32_t clear);
+/* the live per-agent rows [N][18], the sampler's or f110_set_params_batch's: a host copy (synchronous), the device pointer.
+ * F110_ERR_STATE while neither is active. */
+int f110_params_get(f110_sim *h, double *h_out);
+int f110_params_view(f110_sim *h, const double **d_rows);
+/* unit form: m envs of A agents with the nominal rows h_nominal [A][18] and the streams h_streams [m][4], drawn `rounds` times one
+ * after the other; h_out [rounds][m * A][18] (a FIXED slot: the nominal), h_streams_out [m][4] (or NULL) the streams afterwards.
+ * Refuses what arming refuses, and A outside 1..256, m < 1, rounds < 1. */
+int f110_param_sample_batch(f110_sim *h, const f110_param_dist *entries18, const double *h_nominal, int32_t A, const uint64_t *h_streams,
+                            int32_t m, int32_t rounds, double *h_out, uint64_t *h_streams_out);
 
 /* ---- rendering (rendering.py draws with pyglet: map points, one quad per car, a label; this is its rgb_array form) ----
  * A render makes F frames of H x W pixels, one uint8 class per pixel (the highest that applies wins):
